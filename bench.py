@@ -166,6 +166,33 @@ def timed_steps(eng, comm, step, warmup: int, steps: int, extra_sync=()) -> floa
     return time.perf_counter() - t0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SKIP_FIELDS = ("reserved", "path_info")     # padding / tie-break flags, and gyp_track_rec's diagnostic path word (gypsum_hip.h)
+
+
+def dump_outputs(out_dir: str, tables: dict) -> None:
+    """--dump-outputs: the timed path's last-step results, every field of every record table as <out_dir>/<table>_<field>.npy -- float32
+    fields as float32, all others as float64.  Tables are indexed by their first axis (a channel, a scanned stream, a unit); a table larger
+    than its share of DUMP_LIMIT_BYTES keeps a sample of its rows, chosen by a fixed seed, and <table>_rows.npy holds their numbers."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    fields = {name: [f for f in t.dtype.names if f not in DUMP_SKIP_FIELDS] for name, t in tables.items()}
+    as_type = {(name, f): np.float32 if t.dtype[f] == np.float32 else np.float64 for name, t in tables.items() for f in fields[name]}
+    size = {name: sum(t.size * np.dtype(as_type[name, f]).itemsize for f in fields[name]) for name, t in tables.items()}
+    budget = 0.9 * DUMP_LIMIT_BYTES           # (0.9: room for the row numbers and the .npy headers)
+    keep = {}
+    for name in sorted(tables, key=size.get):  # smallest first: a table that fits its share is kept whole, the rest share what is left
+        keep[name] = min(1.0, budget / (len(tables) - len(keep)) / max(1, size[name]))
+        budget -= keep[name] * size[name]
+    for name, t in tables.items():
+        if keep[name] < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], max(1, int(t.shape[0] * keep[name])), replace=False))
+            t = t[rows]
+            np.save(out / f"{name}_rows.npy", rows.astype(np.float64))
+        for f in fields[name]:
+            np.save(out / f"{name}_{f}.npy", t[f].astype(as_type[name, f]))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # CPU baselines (the numpy oracle, i.e. the reference's algorithm; test/bench infrastructure only)
 # ---------------------------------------------------------------------------------------------------------------
@@ -509,6 +536,13 @@ def run_cfg3(eng, comm, args, rng, eng_scan=None) -> dict:
     step = make_step(bool(d2h))
     others = tuple(e for e in (eng_scan, eng_copy) if e is not None)
     elapsed = timed_steps(eng, comm, step, args.warmup, args.steps, extra_sync=others)
+    # --dump-outputs: what the last timed step handed back -- the gathered scan records and that step's tracking records -- before the
+    # steps below reuse the buffers
+    outputs = None
+    if args.dump_outputs:
+        outputs = {"acquisition": acq_recv.download(ACQ_RESULT, comm.world * A * 32).reshape(comm.world * A, 32)}
+        if su.rec_devs:
+            outputs["tracking"] = su.records(slot=args.warmup + args.steps - 1).reshape(B * C_, T)
     # the same steps again, untimed, with rocm-smi polled beside them: shader clock and power UNDER this load without a fork / exec
     # every half second inside the metric; and a short pair with / without the D2H of the records
     n_tele = 0 if args.no_telemetry else max(2, int(math.ceil(2.5 / max(1e-3, comm.max(elapsed) / args.steps))))   # ~2.5 s, the same count on every rank
@@ -594,7 +628,7 @@ def run_cfg3(eng, comm, args, rng, eng_scan=None) -> dict:
         eng_copy.close()
     f_trk = C_ * (2 * fft_flops(n) + 18 * n)                          # SURVEY 8(d5), per stream-ms
     return {
-        "_su": su,
+        "_su": su, "_outputs": outputs,
         "workload_name": "cfg3",
         "config": {"workload": f"cfg3 {fs / 1e6:.3f}Msps x{B} streams/GPU: 32-sat acquire ({A} scans/step) + 12-ch E-P-L track {T}ms/step",
                    "iq": "resident in HBM (host-fed: legs.h2d)", "records_d2h_in_timed_region": bool(d2h),
@@ -900,7 +934,15 @@ def run_grid(eng, comm, args, rng, workload: str, steps: int, warmup: int) -> di
             eng.grid_best_bins_refined_dev(iq.ptr.value, n_units, n, 1, ALL_IDS, bins, GYP_NON_COHERENT, out_dev.ptr.value, send.ptr.value)
             comm.allgather(send, recv, pad_rows * BEST_BIN.itemsize)
 
+    def gathered(flat):     # the whole job's table as rank 0 holds it after the all-gather: every rank's rows, padding trimmed, in stream order
+        return np.concatenate([flat[r * pad_rows:r * pad_rows + (b - a) * T * 32]
+                               for r, (a, b) in enumerate(shard_bounds(64, r_, comm.world) for r_ in range(comm.world))])
+
     elapsed = timed_steps(eng, comm, step, warmup, steps)
+    outputs = None           # --dump-outputs: the last timed step's results, before the timing launch below rewrites the buffers
+    if args.dump_outputs:
+        outputs = {"cells": out_dev.download(CELL, n_cells).reshape(n_units, 32, len(bins))} if recv is None else \
+                  {"best_bins": gathered(recv.download(BEST_BIN, comm.world * pad_rows))}
     eng.timer_start(); step(0); k_ms = eng.timer_stop()
     out = out_dev.download(CELL, n_cells).reshape(n_units, 32, len(bins))
     hits = 0
@@ -918,10 +960,7 @@ def run_grid(eng, comm, args, rng, workload: str, steps: int, warmup: int) -> di
         plain = got["reserved"] == 0                     # rows the float64 tie-break did not touch: the float32 arg-max over the bins
         extra["gathered_best_bins_ok"] = bool(np.array_equal(got["bin"][plain], want[plain]))
         extra["rows_decided_in_float64"] = int(np.sum(~plain))
-        # the whole job's table as rank 0 holds it after the all-gather: every rank's rows, padding trimmed, in stream order
-        flat = recv.download(BEST_BIN, comm.world * pad_rows)
-        table = np.concatenate([flat[r * pad_rows:r * pad_rows + (b - a) * T * 32]
-                                for r, (a, b) in enumerate(shard_bounds(64, r_, comm.world) for r_ in range(comm.world))])
+        table = gathered(recv.download(BEST_BIN, comm.world * pad_rows))
         extra["gathered_table_rows"] = int(len(table))
     flops = n_units * (len(bins) * (6 * n + fft_flops(n)) + 32 * len(bins) * (6 * n + fft_flops(n) + 5 * n))
     return {
@@ -935,7 +974,7 @@ def run_grid(eng, comm, args, rng, workload: str, steps: int, warmup: int) -> di
         "total_samples_override": 64 * T * n * steps if workload == "cfg4" else None,
         "dominant": {"kernel": "grid_cells_wave_fused_kernel<2, false>", "ms": k_ms, "flops": flops,
                      "bytes": (8 * n + 32 * 32 * len(bins)) * n_units},
-        "extra": extra, "_sample": sample, "_table": table if recv is not None else None,
+        "extra": extra, "_sample": sample, "_table": table if recv is not None else None, "_outputs": outputs,
     }
 
 
@@ -983,6 +1022,7 @@ def run_cfg5(eng, comm, args, steps: int, warmup: int) -> dict:
                             for r, (a, b) in enumerate(shard_bounds(len(bins), r_, comm.world) for r_ in range(comm.world))], axis=2)
     return {
         "_table": table,
+        "_outputs": {"cells": table} if args.dump_outputs else None,    # (the timing launch above writes `send` only: recv is the last step's)
         "workload_name": "cfg5", "scaling": "strong", "divide_by_world": True,
         "config": {"workload": f"cfg5: synthetic IQ {fs / 1e6:.3f} Msps, {n_streams} stream(s), 32 sats x "
                                f"range(-10000,10000,100) Hz x 10 ms coherent = {n_total} cells",
@@ -1239,6 +1279,10 @@ def main() -> None:
     ap.add_argument("--rendezvous-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-table", default=None, help="cfg4 / cfg5: rank 0 saves the all-gathered record table (.npy) -- what tests/test_gpu_bench_n2.py "
                                                        "compares between an N-rank and a single-rank run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its last timed step -- every field of its record tables -- as "
+                         "DIR/<table>_<field>.npy (float32 / float64, <= 64 MB in all: a fixed, seeded sample of rows beyond that); the "
+                         "inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1342,7 +1386,7 @@ def main() -> None:
                   # headline since r06 -- r05's 32 streams x 4000 ms put 384 workgroups on 512 slots and measured that hole, not lock cost)
                   ("batched_locked", lambda: run_batched_rate(eng, comm, 8_184_000, B=128, T=4000, steps=2, **lock_kw(8184)))))
         try:
-            small = argparse.Namespace(**{**vars(args), "streams": 128, "grid_ms": 64})
+            small = argparse.Namespace(**{**vars(args), "streams": 128, "grid_ms": 64, "dump_outputs": None})
             extras["other_configs"] = {
                 "cfg2": summarise(run_grid(eng, comm, small, np.random.default_rng(5), "cfg2", 4, 2), 1, 4, not args.no_cpu_baseline),
                 "cfg5": summarise(run_cfg5(eng, comm, small, 8, 3), 1, 8, not args.no_cpu_baseline),
@@ -1364,6 +1408,8 @@ def main() -> None:
     result.pop("_su", None)
     if args.dump_table and rank == 0 and result.get("_table") is not None:
         np.save(args.dump_table, result["_table"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result["_outputs"])
     # ---- max over ranks, one JSON line from rank 0
     per_rank_s = comm.gather_floats(result["elapsed"])
     per_rank_kernel_ms = comm.gather_floats(result["dominant"]["ms"])

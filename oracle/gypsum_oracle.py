@@ -13,8 +13,9 @@ The oracle is pinned two ways:
     the build container by ``tests/golden/make_golden.py`` (which imports
     ``/root/reference/gypsum``); ``tests/test_oracle_golden.py`` checks the
     oracle against them on every run.
-  * ``tests/test_oracle_vs_reference.py`` runs oracle and reference side by
-    side whenever ``/root/reference`` is present.
+  * ``tests/test_oracle_vs_reference.py`` puts the oracle beside the
+    reference's outputs for random inputs drawn from fixed seeds
+    (``tests/golden/oracle_vs_reference.npz``, from the same generator).
   * the only golden vectors the reference's source holds for this path are the
     IS-GPS-200 first-10-chip octal markers (gps_ca_prn_codes.py:192-225); they
     are restated in ``PRN_OCTAL_MARKERS`` and checked by ``generate_ca_codes``.

@@ -217,8 +217,99 @@ def make_bits() -> None:
     np.savez_compressed(HERE / "bits.npz", **out)
 
 
+def make_vs_reference() -> None:
+    """The reference's side of tests/test_oracle_vs_reference.py, on the inputs that module draws: correlator math, one closed loop
+    (acquisition + 311 tracked ms), and the bit integrator on random streams with flips and slips."""
+    sys.path.insert(0, str(REPO / "tests"))
+    import test_oracle_vs_reference as t
+    from gypsum.antenna_sample_provider import AntennaSampleChunk
+    from gypsum.navigation_bit_intergrator import NavigationBitIntegrator
+    from gypsum.tracker import BitValue, EmittedPseudosymbol, NavigationBitPseudosymbol
+    from gypsum.utils import get_iq_constellation_circularity, get_iq_constellation_rotation
+    out = {}
+    for fs, n, sv, iq, peaks in t.correlator_cases():
+        k = f"corr{fs}__"
+        s = satellites_for(n)[GpsSatelliteId(sv)]
+        attrs = SampleProviderAttributes(fs, n)
+        out[k + "inputs_sha256"] = t._sha(iq, peaks)
+        out[k + "sv"] = sv
+        out[k + "prn"] = s.prn_as_complex
+        for rk, tag in ((IntegrationType.Coherent, "coherent"), (IntegrationType.NonCoherent, "non_coherent")):
+            out[k + tag] = integrate_correlation_with_doppler_shifted_prn(rk, iq, attrs, 1234.5, s.prn_as_complex)
+        out[k + "peak_strength"] = get_normalized_correlation_peak_strength(np.abs(out[k + "non_coherent"]))
+        out[k + "rotation"] = get_iq_constellation_rotation(peaks)
+        out[k + "circularity"] = get_iq_constellation_circularity(peaks)
+
+    fs, n, sv, iq = t.closed_loop_scene()
+    sats = satellites_for(n)
+    sid = GpsSatelliteId(sv)
+    attrs = SampleProviderAttributes(fs, n)
+    ra = GpsSatelliteDetector(sats)._attempt_acquisition_for_satellite_id(sid, iq[:10 * n], attrs)
+    params = GpsSatelliteTrackingParameters(satellite=sats[sid], current_doppler_shift=ra.doppler_shift,
+                                            current_carrier_wave_phase_shift=ra.carrier_wave_phase_shift,
+                                            current_prn_code_phase_shift=ra.prn_phase_shift, doppler_shifts=[])
+    rt = GpsSatelliteTracker(params, attrs)
+    rows = []
+    for ms in range(9, 320):
+        t0, t1 = round(ms * n / fs, 6), round((ms + 1) * n / fs, 6)
+        ps = rt.process_samples(AntennaSampleChunk(t0, t1, iq[ms * n:(ms + 1) * n]))
+        rows.append((params.correlation_peaks_rolling_buffer[-1], params.current_doppler_shift, params.current_carrier_wave_phase_shift,
+                     params.current_prn_code_phase_shift, ps.pseudosymbol.as_val(), ps.start_of_pseudosymbol, params.is_locked()))
+    cols = list(zip(*rows))
+    out["loop__iq_sha256"] = t._sha(iq)
+    out["loop__sv"] = sv
+    out["loop__acquisition"] = np.array([ra.doppler_shift, ra.prn_phase_shift, ra.correlation_strength, ra.carrier_wave_phase_shift])
+    for name, col in zip(("peak", "doppler", "carrier_phase", "code_phase", "pseudosymbol", "start_of_pseudosymbol", "locked"), cols):
+        out["loop__" + name] = np.array(col)
+
+    code = {BitValue.ZERO: 0, BitValue.ONE: 1, BitValue.UNKNOWN: 2}
+    events, cursors, shas = [], [], []
+    for case, (sym, start, end) in enumerate(t.bit_fuzz_cases()):
+        shas.append(t._sha(sym, start, end))
+        integ = NavigationBitIntegrator(GpsSatelliteId(1))
+        for v, st, en in zip(sym, start, end):
+            ps = EmittedPseudosymbol(float(st), float(en), NavigationBitPseudosymbol.from_val(int(v)), 0)
+            events += [(case, e.receiver_timestamp, e.trailing_edge_receiver_timestamp, code[e.bit_value])
+                       for e in integ.process_pseudosymbol(float(st), ps)]
+            cursors.append((case, ps.cursor_at_emit_time))
+    out["bits__inputs_sha256"] = np.array(shas)
+    out["bits__events"] = np.array(events, dtype=np.float64).reshape(-1, 4)          # case, receiver_timestamp, trailing edge, bit code
+    out["bits__cursors"] = np.array(cursors, dtype=np.int64).reshape(-1, 2)          # case, cursor_at_emit_time per pseudosymbol
+    np.savez_compressed(HERE / "oracle_vs_reference.npz", **out)
+    print("vs reference: closed loop acquisition", out["loop__acquisition"], "locked ms", int(out["loop__locked"].sum()),
+          "bit events", len(events))
+
+
+def make_file_provider() -> None:
+    """The reference's AntennaSampleProviderBackedByFile on tests/test_ingest.py's float32 recording (17 ms + 3 stray words):
+    every chunk's timestamps and the sha256 of its samples, until it reports the end of the data."""
+    import tempfile
+
+    sys.path.insert(0, str(REPO / "tests"))
+    import test_ingest as t
+    from gypsum.antenna_sample_provider import AntennaSampleProviderBackedByFile, NoMoreSamplesError
+    from gypsum.radio_input import InputFileInfo
+    with tempfile.TemporaryDirectory() as d:
+        t.write_recording(Path(d) / "rec", np.float32, 17, 3, 3)
+        p = AntennaSampleProviderBackedByFile(InputFileInfo.gnu_radio_recording_2x(Path(d) / "rec"))
+        times, shas, dtypes = [], [], set()
+        while True:
+            try:
+                c = p.get_samples(t.N)
+            except NoMoreSamplesError:
+                break
+            times.append((c.start_time, c.end_time))
+            shas.append(sha(c.samples))
+            dtypes.add(str(c.samples.dtype))
+        assert len(dtypes) == 1
+        np.savez_compressed(HERE / "file_provider_float32.npz", times=np.array(times, dtype=np.float64), samples_sha256=np.array(shas),
+                            dtype=dtypes.pop(), samples_per_prn_transmission=p.get_attributes().samples_per_prn_transmission)
+    print("file provider: chunks", len(times))
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["prn", "grid", "acq", "acq16368", "track", "track16368", "track4092", "lock16368", "lock", "long", "long8184", "bits"]
+    what = sys.argv[1:] or ["prn", "grid", "acq", "acq16368", "track", "track16368", "track4092", "lock16368", "lock", "long", "long8184", "bits",
+                            "vsref", "provider"]
     if "prn" in what:
         make_prn()
     if "grid" in what:
@@ -259,3 +350,7 @@ if __name__ == "__main__":
                       doppler_offsets=(0, 0, 250))
     if "bits" in what:
         make_bits()
+    if "vsref" in what:
+        make_vs_reference()
+    if "provider" in what:
+        make_file_provider()

@@ -8,6 +8,33 @@ from __future__ import annotations
 
 import os
 
+
+def _cpu_budget() -> int:
+    """CPUs this process may use: its affinity mask, a cgroup v2 CPU quota and a budget the environment declares (OMP_NUM_THREADS,
+    MAX_JOBS).  os.cpu_count() counts the whole host: on a shared machine a pool sized by it oversubscribes the share it runs in."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    for var in ("OMP_NUM_THREADS", "MAX_JOBS"):
+        v = os.environ.get(var, "")
+        if v.isdigit() and int(v) > 0:
+            n = min(n, int(v))
+    return n
+
+
+CPU_BUDGET = _cpu_budget()      # (read before the lines below set OMP_NUM_THREADS = 1 for the workers)
+
+
+def pool_size(n_jobs: int, cap: int = 64) -> int:
+    """Oracle worker processes for `n_jobs` jobs: the CPU budget less two for the parent (which drives the GPU and compares)."""
+    return max(1, min(cap, CPU_BUDGET - 2, n_jobs))
+
+
 # One BLAS thread per worker.  np.correlate of two 16368-sample vectors crosses OpenBLAS's threading threshold: with the default
 # thread pool a single-lag dot product takes 35 ms instead of 0.02 ms (and sixty workers times N threads oversubscribe the host) --
 # the reason the 16.368 Msps survey never finished in r03.  Must be set before numpy loads its BLAS.

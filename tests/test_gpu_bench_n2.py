@@ -3,8 +3,8 @@
 SURVEY section 8 e1-e2: streams sharded over the ranks (weak scaling), ONE all-gather of the acquisition records per step.  No 8-GPU node
 has been available to this build, so this is the closest the N > 1 line assembly can get to hardware: two ranks, both on device 0
 (GYP_BENCH_DEVICE_MAP=0,0), each with its own engine, scenes, bank and timed region.  RCCL refuses two ranks on one device ("duplicate
-GPU"), so the records cross through the host (--allow-host-gather, flagged `collective.fallback`); the real two-rank ncclAllGather on one
-device is attempted behind an xfail so that the first box that permits it reports it."""
+GPU"), so the records cross through the host (--allow-host-gather, flagged `collective.fallback`); without that flag the real two-rank
+ncclAllGather on one device is attempted: a box that permits it runs it, one that refuses it must make bench.py fail loudly."""
 import json
 import os
 import subprocess
@@ -106,14 +106,19 @@ def test_two_ranks_cfg4_streams_sharded_best_bin_gather_equals_the_single_rank_t
     assert line["value"] == pytest.approx(64 * 16 * 2046 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
 
 
-@pytest.mark.xfail(reason="RCCL refuses two ranks on one device (duplicate GPU); a box that permits it reports XPASS", strict=False)
 def test_real_two_rank_ncclAllGather_on_one_device(tmp_path):
-    try:
-        r, d = _bench(["--gpus", "2", "--streams", "16", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline", "--no-telemetry"],
-                      env_extra={"GYP_BENCH_DEVICE_MAP": "0,0"}, timeout=240, tmp=tmp_path)
-    except subprocess.TimeoutExpired:
-        pytest.xfail("ncclCommInitRank with two ranks on one device did not return")
-    assert r.returncode == 0, r.stderr[-1500:]
-    full = json.loads(d.read_text())
-    assert full["collective"]["uses_rccl"] == 1 and full["collective"]["world"] == 2
-    assert full["per_rank"]["acquisition_records_sha16"]["gathered_equals_sent"]
+    """Two ranks on device 0 WITHOUT --allow-host-gather.  Where RCCL builds a two-rank communicator on one device, the step's all-gather is
+    a real ncclAllGather and the record says so.  Where it refuses (ncclCommInitRank "invalid usage": a duplicate GPU), bench.py must fail
+    loudly -- a non-zero exit that names the refused communicator, no result line, no record -- and never measure a host-gathered figure."""
+    r, d = _bench(["--gpus", "2", "--streams", "16", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline", "--no-telemetry"],
+                  env_extra={"GYP_BENCH_DEVICE_MAP": "0,0"}, timeout=240, tmp=tmp_path)
+    if r.returncode == 0:
+        full = json.loads(d.read_text())
+        assert full["collective"]["uses_rccl"] == 1 and full["collective"]["world"] == 2 and "fallback" not in full["collective"]
+        assert full["per_rank"]["acquisition_records_sha16"]["gathered_equals_sent"]
+        print("RCCL built a two-rank communicator on one device: the all-gather was a real ncclAllGather")
+    else:
+        assert "the RCCL communicator did not come up" in r.stderr and "refusing to measure a host-gathered figure" in r.stderr, r.stderr[-1500:]
+        assert not r.stdout.strip() and not d.exists(), r.stdout[-1500:]
+        print("RCCL refused two ranks on one device; bench.py failed loudly:",
+              next(l for l in r.stderr.splitlines() if "did not come up" in l))

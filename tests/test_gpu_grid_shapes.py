@@ -42,10 +42,6 @@ def _shm_dir() -> str:
     return "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
 
 
-def _pool_size(n_jobs: int) -> int:
-    return max(1, min(64, (os.cpu_count() or 2) - 2, n_jobs))
-
-
 def _noncoherent_grid(eng, B, T, seed, rng_seed, refined=False):
     """bench.run_grid's launch: B streams x T ms at 2.046 Msps, every (stream, ms) a unit of stride N, 32 satellites x range(-5000, 5000, 500)."""
     import bench
@@ -80,7 +76,7 @@ def _check_rows(eng, cells, best, host_iq, rows, label):
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
     path = os.path.join(_shm_dir(), f"gyp_grid_{os.getpid()}.npy")
     np.save(path, host_iq)
-    procs = _pool_size(max(1, len(rows) // 16))
+    procs = survey_worker.pool_size(max(1, len(rows) // 16))
     per = max(1, -(-len(rows) // (procs * 4)))
     jobs = [(path, fs, n, 1, rows[i:i + per]) for i in range(0, len(rows), per)]
     t0 = time.time()
@@ -197,7 +193,7 @@ def test_cfg5_launch_shape_against_the_oracle(engine_factory):
     cells += [(int(s), int(sv), float(bins[b])) for s, sv, b in zip(rng.integers(0, n_streams, 96), rng.integers(1, 33, 96), rng.integers(0, len(bins), 96))]
     path = os.path.join(_shm_dir(), f"gyp_cfg5_{os.getpid()}.npy")
     np.save(path, host_iq)
-    procs = _pool_size(len(cells))
+    procs = survey_worker.pool_size(len(cells))
     per = max(1, -(-len(cells) // (procs * 2)))
     t0 = time.time()
     knife, worst_peak, worst_strength, n_done = 0, 0.0, 0.0, 0

@@ -200,7 +200,7 @@ def _survey(engine, seeds, n_ms, n_sats, label, FS=FS, N=N, regime="pull-in", lo
     """`regime` "pull-in": SURVEY d2's sigma = 6a scenes (no channel can lock); "lock": synth.lock_regime_scene (most do).
     The last `long_scenes` seeds run `long_ms` milliseconds -- past the 6-second watchdog -- instead of `n_ms`."""
     seeds = [s + SEED_OFFSET for s in seeds]
-    procs = max(1, min(64, (os.cpu_count() or 2) - 2, len(seeds)))
+    procs = survey_worker.pool_size(len(seeds))
     tally = _new_tally(regime)
     t_start = time.time()
     ctx = mp.get_context("spawn")      # the parent holds a HIP context: never fork it
@@ -413,7 +413,7 @@ def _multi_stream_survey(eng, specs, n_ms, label, FS=FS, N=N):
     kernels address `stream x stride`, `xcd_contiguous` spreads hundreds of channels over the XCDs and a block longer than 500 ms is cut
     into launches.  Returns (tally, n_chan)."""
     specs = [(seed + SEED_OFFSET, n_sats, regime) for seed, n_sats, regime in specs]
-    procs = max(1, min(64, (os.cpu_count() or 2) - 2, len(specs)))
+    procs = survey_worker.pool_size(len(specs))
     t_start = time.time()
     jobs = [(FS, n_ms, n_sats, seed, None, regime) for seed, n_sats, regime in specs]
     stream_of = {seed: b for b, (seed, _, _) in enumerate(specs)}
@@ -599,7 +599,7 @@ def test_acquisition_survey(engine_factory, fs, n_scenes):
     phase bit-exact for every visible satellite (the float64 tie-break kernels exist for exactly this)."""
     n = fs // 1000
     eng = engine_factory(fs, n)
-    procs = max(1, min(48, (os.cpu_count() or 2) - 2, n_scenes))
+    procs = survey_worker.pool_size(n_scenes, 48)
     tot = 0
     with mp.get_context("spawn").Pool(procs) as pool:
         for seed, want in pool.imap_unordered(survey_worker.run_acq_scene, [(fs, 5000 + k) for k in range(n_scenes)]):
@@ -619,7 +619,7 @@ def test_full_sky_acquisition_survey(engine_factory, fs, n_scenes):
     10-level search: Doppler bin and code phase bit-exact, strength to 1e-4."""
     n = fs // 1000
     eng = engine_factory(fs, n)
-    procs = max(1, min(48, (os.cpu_count() or 2) - 2, n_scenes))
+    procs = survey_worker.pool_size(n_scenes, 48)
     ids = list(range(1, 33))
     tot = noise = 0
     with mp.get_context("spawn").Pool(procs) as pool:

@@ -1,105 +1,42 @@
-"""Oracle and reference side by side.  Only runs where /root/reference exists (the build container)."""
-import sys
-import warnings
-from pathlib import Path
+"""Oracle and reference side by side.  The reference's outputs for these inputs are stored in tests/golden/oracle_vs_reference.npz
+(tests/golden/make_golden.py `vsref` regenerates them by running the reference); the inputs are drawn here, from fixed seeds, and
+their sha256 is stored beside the outputs."""
+import hashlib
 
 import numpy as np
-import pytest
 
-REF = Path("/root/reference")
-pytestmark = pytest.mark.skipif(not (REF / "gypsum" / "utils.py").exists(), reason="reference not present on this box")
+import golden_util as gu
 
 
-@pytest.fixture(scope="module")
-def ref():
-    sys.path.insert(0, str(REF))
-    warnings.filterwarnings("ignore", category=DeprecationWarning)
-    import gypsum.acquisition as acq
-    import gypsum.antenna_sample_provider as asp
-    import gypsum.gps_ca_prn_codes as codes
-    import gypsum.satellite as sat
-    import gypsum.tracker as trk
-    import gypsum.utils as utils
-    yield {"acq": acq, "asp": asp, "codes": codes, "sat": sat, "trk": trk, "utils": utils}
-    sys.path.remove(str(REF))
+def _sha(*arrays) -> str:
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
 
 
-def test_correlator_math(ref):
-    from gypsum_amd import synth
-    from oracle import gypsum_oracle as orc
-
+def correlator_cases():
+    """(fs, n, sv, iq, peaks) of test_correlator_math, in the order the seeded generator draws them."""
     rng = np.random.default_rng(3)
-    chips = orc.generate_ca_codes()
-    codes = ref["codes"].generate_replica_prn_signals()
     for fs in (2_046_000, 8_184_000):
         n = fs // 1000
-        ref["sat"].GpsSatellite.prn_as_complex.fget.cache_clear()
         sv = int(rng.integers(1, 33))
-        s = ref["sat"].GpsSatellite(ref["codes"].GpsSatelliteId(sv), codes[ref["codes"].GpsSatelliteId(sv)], n // 1023)
-        prn = orc.prn_as_complex(chips[sv - 1], n)
-        assert np.array_equal(prn, s.prn_as_complex)
         iq = (rng.standard_normal(3 * n + 17) + 1j * rng.standard_normal(3 * n + 17)).astype(np.complex64)
-        attrs = ref["asp"].SampleProviderAttributes(fs, n)
-        for kind, rk in ((orc.COHERENT, ref["utils"].IntegrationType.Coherent), (orc.NON_COHERENT, ref["utils"].IntegrationType.NonCoherent)):
-            a = orc.integrate_correlation(kind, iq, fs, n, 1234.5, prn)
-            b = ref["utils"].integrate_correlation_with_doppler_shifted_prn(rk, iq, attrs, 1234.5, s.prn_as_complex)
-            assert np.array_equal(a, b)
-        prof = np.abs(a)
-        assert orc.peak_strength(prof) == ref["utils"].get_normalized_correlation_peak_strength(prof)
         peaks = rng.standard_normal(300) * 20 + 1j * rng.standard_normal(300)
-        assert orc.constellation_rotation(peaks) == ref["utils"].get_iq_constellation_rotation(peaks)
-        assert orc.constellation_circularity(peaks) == ref["utils"].get_iq_constellation_circularity(peaks)
+        yield fs, n, sv, iq, peaks
 
 
-def test_acquisition_and_tracking_closed_loop(ref):
+def closed_loop_scene():
     from gypsum_amd import synth
-    from oracle import gypsum_oracle as orc
 
     fs, n = 2_046_000, 2046
     scene = synth.random_scene(fs, 320, 4, 77, noise_sigma=0.02)
-    iq = synth.render(scene)
-    chips = orc.generate_ca_codes()
-    codes = ref["codes"].generate_replica_prn_signals()
-    ref["sat"].GpsSatellite.prn_as_complex.fget.cache_clear()
-    sats = {sid: ref["sat"].GpsSatellite(sid, code, n // 1023) for sid, code in codes.items()}
-    det = ref["acq"].GpsSatelliteDetector(sats)
-    attrs = ref["asp"].SampleProviderAttributes(fs, n)
-    sv = scene.sats[0].sat_id
-    sid = ref["codes"].GpsSatelliteId(sv)
-    ra = det._attempt_acquisition_for_satellite_id(sid, iq[:10 * n], attrs)
-    oa = orc.acquire_satellite(sv, iq[:10 * n], fs, n, orc.prn_as_complex(chips[sv - 1], n))
-    assert (oa.doppler_shift, oa.prn_phase_shift, oa.correlation_strength, oa.carrier_wave_phase_shift) == \
-           (ra.doppler_shift, ra.prn_phase_shift, ra.correlation_strength, ra.carrier_wave_phase_shift)
-    params = ref["trk"].GpsSatelliteTrackingParameters(satellite=sats[sid], current_doppler_shift=ra.doppler_shift,
-                                                       current_carrier_wave_phase_shift=ra.carrier_wave_phase_shift,
-                                                       current_prn_code_phase_shift=ra.prn_phase_shift, doppler_shifts=[])
-    rt = ref["trk"].GpsSatelliteTracker(params, attrs)
-    ot = orc.Tracker(orc.TrackingState(oa.doppler_shift, oa.carrier_wave_phase_shift, oa.prn_phase_shift),
-                     orc.prn_as_complex(chips[sv - 1], n), fs, n)
-    for ms in range(9, 320):
-        t0, t1 = orc.chunk_times(ms * n, n, fs)
-        chunk = ref["asp"].AntennaSampleChunk(t0, t1, iq[ms * n:(ms + 1) * n])
-        ps = rt.process_samples(chunk)
-        rec = ot.process_samples(iq[ms * n:(ms + 1) * n], t0, t1)
-        assert rec.peak == params.correlation_peaks_rolling_buffer[-1]
-        assert rec.doppler_after == params.current_doppler_shift
-        assert rec.carrier_phase_after == params.current_carrier_wave_phase_shift
-        assert rec.code_phase_after == params.current_prn_code_phase_shift
-        assert rec.pseudosymbol == ps.pseudosymbol.as_val()
-        assert rec.start_of_pseudosymbol == ps.start_of_pseudosymbol
-        assert ot.s.is_locked() == params.is_locked()
+    return fs, n, scene.sats[0].sat_id, synth.render(scene)
 
 
-def test_bit_integrator_fuzz(ref):
-    """Random bit streams with flips, slips and junk: reference, oracle and the native integrator agree event for event."""
-    from gypsum.navigation_bit_intergrator import NavigationBitIntegrator
-    from gypsum_amd import _lib
-    from gypsum_amd.navigation_bit_intergrator import NavigationBitIntegratorBank
-    from oracle import gypsum_oracle as orc
-
+def bit_fuzz_cases():
+    """Random bit streams with flips, slips and junk: (pseudosymbols, start times, end times) per case."""
     rng = np.random.default_rng(77)
-    trk = ref["trk"]
-    code = {trk.BitValue.ZERO: 0, trk.BitValue.ONE: 1, trk.BitValue.UNKNOWN: 2}
     for case in range(12):
         n_ms = int(rng.integers(200, 4000))
         bits = rng.integers(0, 2, n_ms // 20 + 3) * 2 - 1
@@ -111,15 +48,76 @@ def test_bit_integrator_fuzz(ref):
         t0 = float(rng.choice([0.0, 37.5, 39.9]))
         start = np.round(t0 + np.arange(len(sym)) / 1000, 6)
         end = np.round(t0 + (np.arange(len(sym)) + 1) / 1000, 6)
-        r = NavigationBitIntegrator(ref["codes"].GpsSatelliteId(1))
+        yield sym, start, end
+
+
+def test_correlator_math():
+    from oracle import gypsum_oracle as orc
+
+    z = gu.load("oracle_vs_reference.npz")
+    chips = orc.generate_ca_codes()
+    for fs, n, sv, iq, peaks in correlator_cases():
+        k = f"corr{fs}__"
+        assert _sha(iq, peaks) == str(z[k + "inputs_sha256"]), "the seeded inputs changed (numpy RNG stream?)"
+        assert sv == int(z[k + "sv"])
+        prn = orc.prn_as_complex(chips[sv - 1], n)
+        assert np.array_equal(prn, z[k + "prn"]) and prn.dtype == z[k + "prn"].dtype
+        for kind, tag in ((orc.COHERENT, "coherent"), (orc.NON_COHERENT, "non_coherent")):
+            a = orc.integrate_correlation(kind, iq, fs, n, 1234.5, prn)
+            b = z[k + tag]
+            assert a.dtype == b.dtype and np.array_equal(a, b), tag
+        prof = np.abs(a)
+        assert orc.peak_strength(prof) == float(z[k + "peak_strength"])
+        assert orc.constellation_rotation(peaks) == float(z[k + "rotation"])
+        assert orc.constellation_circularity(peaks) == float(z[k + "circularity"])
+
+
+def test_acquisition_and_tracking_closed_loop():
+    from oracle import gypsum_oracle as orc
+
+    z = gu.load("oracle_vs_reference.npz")
+    fs, n, sv, iq = closed_loop_scene()
+    assert _sha(iq) == str(z["loop__iq_sha256"]), "the seeded scene changed (numpy RNG stream?)"
+    assert sv == int(z["loop__sv"])
+    chips = orc.generate_ca_codes()
+    oa = orc.acquire_satellite(sv, iq[:10 * n], fs, n, orc.prn_as_complex(chips[sv - 1], n))
+    assert (oa.doppler_shift, oa.prn_phase_shift, oa.correlation_strength, oa.carrier_wave_phase_shift) == tuple(z["loop__acquisition"])
+    ot = orc.Tracker(orc.TrackingState(oa.doppler_shift, oa.carrier_wave_phase_shift, oa.prn_phase_shift),
+                     orc.prn_as_complex(chips[sv - 1], n), fs, n)
+    peak, doppler, carrier, code = z["loop__peak"], z["loop__doppler"], z["loop__carrier_phase"], z["loop__code_phase"]
+    symbol, start, locked = z["loop__pseudosymbol"], z["loop__start_of_pseudosymbol"], z["loop__locked"]
+    assert len(peak) == 320 - 9
+    for j, ms in enumerate(range(9, 320)):
+        t0, t1 = orc.chunk_times(ms * n, n, fs)
+        rec = ot.process_samples(iq[ms * n:(ms + 1) * n], t0, t1)
+        assert rec.peak == peak[j], ms
+        assert rec.doppler_after == doppler[j], ms
+        assert rec.carrier_phase_after == carrier[j], ms
+        assert rec.code_phase_after == code[j], ms
+        assert rec.pseudosymbol == symbol[j], ms
+        assert rec.start_of_pseudosymbol == start[j], ms
+        assert ot.s.is_locked() == bool(locked[j]), ms
+
+
+def test_bit_integrator_fuzz():
+    """Random bit streams with flips, slips and junk: reference, oracle and the native integrator agree event for event."""
+    from gypsum_amd import _lib
+    from gypsum_amd.navigation_bit_intergrator import NavigationBitIntegratorBank
+    from oracle import gypsum_oracle as orc
+
+    z = gu.load("oracle_vs_reference.npz")
+    events, cursors = z["bits__events"], z["bits__cursors"]
+    for case, (sym, start, end) in enumerate(bit_fuzz_cases()):
+        assert _sha(sym, start, end) == str(z["bits__inputs_sha256"][case]), "the seeded inputs changed (numpy RNG stream?)"
+        mine = events[events[:, 0] == case]
+        want = [(float(a), float(b), int(c)) for a, b, c in mine[:, 1:]]
+        at_want = cursors[cursors[:, 0] == case][:, 1]
+        assert len(at_want) == len(sym)
         o = orc.BitIntegrator()
-        want, got_o = [], []
-        for v, st, en in zip(sym, start, end):
-            ps = trk.EmittedPseudosymbol(float(st), float(en), trk.NavigationBitPseudosymbol.from_val(int(v)), 0)
-            want += [(e.receiver_timestamp, e.trailing_edge_receiver_timestamp, code[e.bit_value])
-                     for e in r.process_pseudosymbol(float(st), ps)]
+        got_o = []
+        for v, st, en, at_ref in zip(sym, start, end, at_want):
             at, ev = o.process(float(st), float(st), float(en), int(v))
-            assert at == ps.cursor_at_emit_time
+            assert at == at_ref
             got_o += ev
         assert got_o == want, case
         recs = np.zeros((1, len(sym)), dtype=_lib.TRACK_REC)
