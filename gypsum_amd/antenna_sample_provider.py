@@ -9,6 +9,7 @@ parity tests and the benchmark use since no recording is available offline.
 """
 from __future__ import annotations
 
+import ctypes as C
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
 from pathlib import Path
@@ -175,3 +176,94 @@ class AntennaSampleProviderBackedByArray(_CursorProvider):
             end_time=self._elapsed(self.cursor + sample_count),
             samples=self.iq[self.cursor:self.cursor + sample_count],
         )
+
+
+class AntennaSampleProviderResampled(_CursorProvider):
+    """A recording at any whole-kHz rate served at a supported rate (gypsum_amd.resample): the file is read by the native
+    reader and resampled on the device (`gyp_ingest_open_resampled`); whole aligned output milliseconds come back through
+    `get_samples(N)` / `get_block(n_ms)` with the usual timestamps (round(cursor / fs_out, 6)) and NoMoreSamplesError after
+    the input file's `total_ms` milliseconds.  `get_attributes()` reports the output rate, so `GpsReceiver` and
+    `BatchedGpsReceiver` run on it unchanged.
+
+    `path` may be an `InputFileInfo` (e.g. `InputFileInfo.raw(path, 4_000_000, np.int16)`); `resample_to` defaults to
+    `nearest_supported_rate(sample_rate)`; `scale` multiplies integer words (an 8-bit front end wants about 1/100, see
+    gyp_ingest_set_scale)."""
+
+    def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
+                 sample_component_data_type=np.float32, scale: float = 1.0, taps: int = 32, block_ms: int = 250,
+                 engine=None, device: int = 0) -> None:
+        from .engine import GypsumEngine
+        from .ingest import IqFileIngest
+        from .resample import nearest_supported_rate
+
+        if hasattr(path, "sdr_sample_rate"):
+            info = path
+            path, sample_rate = info.path, info.sdr_sample_rate
+            utc_start_time = info.utc_start_time.timestamp()
+            sample_component_data_type = info.sample_component_data_type
+        if sample_rate is None:
+            raise TypeError("sample_rate is required when no InputFileInfo is given")
+        self.path = Path(path)
+        self.input_sample_rate = int(sample_rate)
+        self.sample_rate = int(resample_to) if resample_to is not None else nearest_supported_rate(self.input_sample_rate)
+        self.n = self.sample_rate // PRN_REPETITIONS_PER_SECOND
+        self.cursor = 0
+        self.utc_start_time = utc_start_time
+        self.sample_component_data_type = sample_component_data_type
+        if engine is None:
+            engine = GypsumEngine(device)
+            engine.set_stream_format(self.sample_rate, self.n)
+            self._own_engine = True
+        else:
+            self._own_engine = False
+        self.engine = engine
+        self._ingest = IqFileIngest(self.path, self.sample_rate, sample_component_data_type, block_ms=block_ms, engine=engine,
+                                    resample_from_hz=self.input_sample_rate, taps=taps)
+        if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
+            self._ingest.set_scale(scale)
+        self.total_ms = self._ingest.total_ms
+        self._block_first_ms = 0
+        self._block: np.ndarray | None = None    # [n_ms, N] complex64, downloaded
+        self._next_ms = 0                        # the first millisecond the ingest hands out next
+
+    def _ms(self, ms: int) -> np.ndarray:
+        if self._block is None or not (self._block_first_ms <= ms < self._block_first_ms + len(self._block)):
+            if ms != self._next_ms:
+                self._ingest.seek(ms)
+            got = self._ingest.next_device_block()
+            if got is None:
+                raise NoMoreSamplesError(f"Ran out of samples at {self.seconds_since_start():.2f}s")
+            first, count, dev = got
+            host = np.empty((count, self.n), dtype=np.complex64)
+            self.engine._check(self.engine.lib.gyp_memcpy_d2h(self.engine.ctx, host.ctypes.data_as(C.c_void_p), C.c_void_p(dev), host.nbytes))
+            self._block_first_ms, self._block, self._next_ms = first, host, first + count
+        return self._block[ms - self._block_first_ms]
+
+    def peek_samples(self, sample_count: int) -> AntennaSampleChunk:
+        if sample_count != self.n or self.cursor % self.n:
+            raise ValueError(f"a resampled recording is served in whole aligned milliseconds ({self.n} samples)")
+        ms = self.cursor // self.n
+        if ms >= self.total_ms:
+            raise NoMoreSamplesError(f"Ran out of samples at {self.seconds_since_start():.2f}s")
+        return AntennaSampleChunk(start_time=self.seconds_since_start(), end_time=self._elapsed(self.cursor + sample_count),
+                                  samples=self._ms(ms).copy())
+
+    def get_block(self, n_ms: int) -> AntennaSampleChunk:
+        if self.cursor % self.n:
+            raise ValueError(f"a resampled recording is served in whole aligned milliseconds ({self.n} samples)")
+        ms = self.cursor // self.n
+        k = min(int(n_ms), self.total_ms - ms)
+        if k <= 0:
+            raise NoMoreSamplesError(f"Ran out of samples at {self.seconds_since_start():.2f}s")
+        start = self.seconds_since_start()
+        samples = np.concatenate([self._ms(ms + i) for i in range(k)])
+        self.cursor += k * self.n
+        return AntennaSampleChunk(start_time=start, end_time=self.seconds_since_start(), samples=samples)
+
+    def close(self) -> None:
+        if getattr(self, "_ingest", None) is not None:
+            self._ingest.close()
+            self._ingest = None
+        if getattr(self, "_own_engine", False) and self.engine is not None:
+            self.engine.close()
+            self.engine = None

@@ -123,6 +123,9 @@ struct gyp_ctx {
     int widen_wg_per_cu = 2;      // gyp_debug_set("widen_wg_per_cu"): workgroups per CU of the ingest widen kernel's persistent grid (1..8).  It runs on the
                                   // upload stream BESIDE the previous block's kernels: with 8 per CU (r02-r05) it took the chip at every launch boundary of the
                                   // trackers; 2 per CU leave them their slots -- int8-fed / resident 0.934-0.942 -> 0.949-0.953 (profiles/r06zi / r06zj_widen_grid.txt)
+    int resample_tile = 4096;     // gyp_debug_set("resample_tile_samples"): LDS budget of one resample_kernel tile, in input samples (32 KiB: five
+                                  // workgroups per CU); same output for any value
+    std::vector<ResampleDesign> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps)
     int track_chunk_ms = 250;     // gyp_debug_set("track_chunk_ms"): the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
     float symbol_tau = 1e-4f;     // gyp_debug_set("symbol_tau"): |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
     bool no_shared_fwd = false;   // gyp_debug_set("no_shared_fwd"): A/B switch: flat grids transform every cell's rows themselves again
@@ -390,6 +393,7 @@ void gyp_destroy(gyp_ctx* ctx) {
     if (ctx->d_ntrans) (void)hipFree(ctx->d_ntrans);
     if (ctx->d_chipf) (void)hipFree(ctx->d_chipf);
     if (ctx->d_prof) (void)hipFree(ctx->d_prof);
+    for (auto& d : ctx->resample_designs) if (d.d_taps) (void)hipFree(d.d_taps);
     for (int i = 0; i < 4; ++i) if (ctx->ev_track[i]) (void)hipEventDestroy(ctx->ev_track[i]);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
@@ -2006,6 +2010,7 @@ const DebugKnob kDebugKnobs[] = {
     {"spec_debug", 0, 1, true}, {"acq_lanes", 1, gyp_ctx::kMaxAcqLanes, true}, {"track_chunk_ms", 0, 1e6, true}, {"widen_wg_per_cu", 1, 8, true},
     {"symbol_tau", 0, 100, false}, {"dll_prov_bias", -1e6, 1e6, false}, {"spec_fail_at", -1, 2147483647.0, true},
     {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"exact_prefetch", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
+    {"resample_tile_samples", 1024, 8192, true},
 };
 }  // namespace
 static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, double* out) {
@@ -2033,6 +2038,7 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
     GYP_KNOB_NUM("spec_fail_at", spec_fail_at, int)
     GYP_KNOB_NUM("exact_prefetch", exact_prefetch, int)
     GYP_KNOB_NUM("prof_wave", prof_wave, int)
+    GYP_KNOB_NUM("resample_tile_samples", resample_tile, int)
 #undef GYP_KNOB_BOOL
 #undef GYP_KNOB_NUM
     return GYP_E_BAD_ARG;
@@ -2254,6 +2260,128 @@ int gyp_bits_get_state(const gyp_bits* bits, int32_t channel, gyp_bits_state* ou
 // ---------------------------------------------------------------------------------------------------------
 #include "ingest.hpp"
 
+// ---------------------------------------------------------------------------------------------------------
+// Resampler (kernels_resample.hpp): fs_in recordings -> the stream format
+// ---------------------------------------------------------------------------------------------------------
+// The design for (fs_in, the context's rate, taps), built and uploaded on first use.  A copy: the context owns d_taps.
+static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, ResampleDesign* out, const char* who) {
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    const int32_t T = resample_taps(taps);
+    if (!T) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (32), 16, 24, 32, 48 or 64");
+    if (!resample_rates_ok(fs_in, ctx->fs))
+        return fail(ctx, GYP_E_BAD_RATE, std::string(who) + ": fs_in must be a positive multiple of 1000 Hz, differ from the stream format's rate "
+                                                            "and lie within a factor 2 of it");
+    for (const ResampleDesign& d : ctx->resample_designs)
+        if (d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T) {
+            *out = d;
+            return GYP_OK;
+        }
+    ResampleDesign d;
+    d.fs_in = fs_in;
+    d.fs_out = ctx->fs;
+    d.taps = T;
+    d.n_in = (int32_t)(fs_in / 1000);
+    d.n_out = (int32_t)(ctx->fs / 1000);
+    d.g = (int32_t)resample_gcd(d.n_in, d.n_out);
+    d.L = d.n_out / d.g;
+    d.M = d.n_in / d.g;
+    std::vector<float> rows((size_t)d.L * T), cols((size_t)d.L * T);
+    resample_design_rows(fs_in, ctx->fs, T, d.L, rows.data());
+    for (int32_t p = 0; p < d.L; ++p) {   // the kernel's layout: column p holds phase p's taps (design row p*M mod L)
+        const int64_t row = (int64_t)p * d.M % d.L;
+        for (int32_t j = 0; j < T; ++j) cols[(size_t)j * d.L + p] = rows[(size_t)row * T + j];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMalloc((void**)&d.d_taps, cols.size() * sizeof(float)));
+    const hipError_t e = hipMemcpyAsync(d.d_taps, cols.data(), cols.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `cols` is a temporary
+    if (e2 != hipSuccess) {
+        (void)hipFree(d.d_taps);
+        return fail(ctx, GYP_E_HIP, std::string(who) + ": table upload: " + hipGetErrorString(e2));
+    }
+    ctx->resample_designs.push_back(d);
+    *out = d;
+    return GYP_OK;
+}
+
+// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.
+static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, int32_t fmt, const void* raw, int32_t n_streams,
+                           int64_t in_stride, int64_t raw_first, int64_t raw_n, float scale, int64_t first_ms, int32_t n_ms,
+                           float* out, int64_t out_stride) {
+    const int64_t n_periods = (int64_t)n_ms * d.g;
+    const int32_t T = d.taps, TS = ctx->resample_tile;
+    int32_t np_tile = 1, pc_tile = d.L, n_pchunks = 1;
+    size_t lds_samples;
+    if (d.M + T - 1 <= TS) {      // whole periods: as many as fit
+        np_tile = (int32_t)std::min<int64_t>(std::max(1, (TS - T + 1) / d.M), n_periods);
+        lds_samples = (size_t)np_tile * d.M + T - 1;
+    } else {                      // one period, its phases in chunks whose span fits
+        pc_tile = (int32_t)std::max<int64_t>(1, (int64_t)(TS - T - 1) * d.L / d.M);
+        n_pchunks = (d.L + pc_tile - 1) / pc_tile;
+        lds_samples = (size_t)TS;
+    }
+    const int64_t n_tiles = (n_periods + np_tile - 1) / np_tile * n_pchunks;
+    if (n_tiles > INT32_MAX || n_streams > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample: launch too large (split it)");
+    const dim3 grid((unsigned)n_tiles, (unsigned)n_streams), block(256);
+    const size_t lds = lds_samples * sizeof(float2);
+    const int64_t p_first = first_ms * d.g;
+#define GYP_RS_LAUNCH(W, TT)                                                                                                      \
+    hipLaunchKernelGGL((resample_kernel<W, TT>), grid, block, lds, stream, (const W*)raw, in_stride, raw_first, raw_n, scale, d.d_taps, \
+                       d.L, d.M, p_first, n_periods, np_tile, pc_tile, n_pchunks, (float2*)out, out_stride)
+#define GYP_RS_TAPS(W)                        \
+    switch (T) {                              \
+        case 16: GYP_RS_LAUNCH(W, 16); break; \
+        case 24: GYP_RS_LAUNCH(W, 24); break; \
+        case 32: GYP_RS_LAUNCH(W, 32); break; \
+        case 48: GYP_RS_LAUNCH(W, 48); break; \
+        default: GYP_RS_LAUNCH(W, 64); break; \
+    }
+    switch (fmt) {
+        case GYP_FMT_F32: GYP_RS_TAPS(float) break;
+        case GYP_FMT_I8: GYP_RS_TAPS(int8_t) break;
+        case GYP_FMT_U8: GYP_RS_TAPS(uint8_t) break;
+        default: GYP_RS_TAPS(int16_t) break;
+    }
+#undef GYP_RS_TAPS
+#undef GYP_RS_LAUNCH
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_resample_design(int64_t fs_in_hz, int64_t fs_out_hz, int32_t taps, float* table_out, int32_t* n_phases_out) {
+    const int32_t T = resample_taps(taps);
+    if (!T) return fail(nullptr, GYP_E_BAD_ARG, "gyp_resample_design: taps must be 0 (32), 16, 24, 32, 48 or 64");
+    if (!resample_rates_ok(fs_in_hz, fs_out_hz))
+        return fail(nullptr, GYP_E_BAD_RATE, "gyp_resample_design: rates must be positive multiples of 1000 Hz, differ, and lie within a factor 2");
+    const int64_t n_out = fs_out_hz / 1000;
+    const int32_t L = (int32_t)(n_out / resample_gcd(fs_in_hz / 1000, n_out));
+    if (n_phases_out) *n_phases_out = L;
+    if (table_out) resample_design_rows(fs_in_hz, fs_out_hz, T, L, table_out);
+    return GYP_OK;
+}
+
+int gyp_resample_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_streams, int64_t in_stride_samples,
+                        int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t fs_in_hz, int32_t taps, int64_t first_ms,
+                        int32_t n_ms, int64_t out_stride_samples, float* out_dev) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (!ingest_word_bytes(fmt)) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample_iq_dev: fmt must be one of GYP_FMT_*");
+    ResampleDesign d;
+    if (const int rc = resample_get_design(ctx, fs_in_hz, taps, &d, "gyp_resample_iq_dev")) return rc;
+    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || raw_n_samples < 0 || in_stride_samples < raw_n_samples ||
+        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_resample_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, "
+                                        "in_stride >= raw_n_samples >= 0, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return resample_launch(ctx, ctx->stream, d, fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples, scale,
+                           first_ms, n_ms, out_dev, out_stride_samples);
+}
+
+}  // extern "C"
+
+
 static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
     if (g->ctx) {
@@ -2296,6 +2424,18 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     // the kernels of block k-1 when block k+1 is uploaded ahead, so the upload still overlaps block k's kernels)
     HIP_TRY(ctx, hipEventRecord(g->consumer_mark, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(g->copy_stream, g->consumer_mark, 0));
+    if (g->resampled) {   // the block's input span (halo included) in file width, resampled into the output slot
+        const int64_t span = (int64_t)u->n_ms * g->in_n + g->halo_lo + g->halo_hi;
+        HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream));
+        HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
+        if (const int rc = resample_launch(ctx, g->copy_stream, g->rs, g->fmt, g->dev_raw[d], 1, span, u->first_ms * g->in_n - g->halo_lo, span,
+                                           g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n))
+            return rc;
+        HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
+        g->in_flight.push_back(*u);
+        ++g->dev_blocks;
+        return 1;
+    }
     const size_t bytes = (size_t)u->n_ms * g->ms_bytes;
     const size_t words = (size_t)u->n_ms * g->n * 2;
     void* dst = g->fmt == kFmtF32 ? (void*)g->dev_iq[d] : (void*)g->dev_raw[d];
@@ -2325,24 +2465,11 @@ static double round6(double x) {
 
 extern "C" {
 
-int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, int32_t n, int32_t block_ms,
-                    int32_t depth, gyp_ingest** out) {
-    if (!out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open: out is NULL");
-    *out = nullptr;
-    const int wb = ingest_word_bytes(fmt);
-    if (!path || !wb || fs_hz <= 0 || n <= 0 || block_ms < 1 || depth < 3 || depth > 64)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open: bad arguments (format, fs, n, block_ms >= 1, 3 <= depth <= 64)");
-    if ((int64_t)n != fs_hz / 1000)   // antenna_sample_provider.py:135
-        return fail(ctx, GYP_E_BAD_RATE, "gyp_ingest_open: n must be fs // 1000");
-    gyp_ingest* g = new (std::nothrow) gyp_ingest();
-    if (!g) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open: out of memory");
-    g->ctx = ctx;
-    g->fmt = fmt;
-    g->fs = fs_hz;
-    g->n = n;
-    g->block_ms = block_ms;
-    g->depth = depth;
-    g->ms_bytes = (size_t)n * 2 * wb;
+}  // extern "C"
+
+// Opens the file and allocates the rings of a handle whose rates and sizes are filled in; frees it on failure.
+static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp_ingest** out) {
+    const int32_t depth = g->depth;
     g->fd = open(path, O_RDONLY | O_CLOEXEC);
     struct stat st;
     if (g->fd < 0 || fstat(g->fd, &st) != 0) {
@@ -2351,8 +2478,9 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
         return fail(ctx, GYP_E_IO, std::string("gyp_ingest_open: ") + path + ": " + why);
     }
     g->total_ms = st.st_size > 0 ? (int64_t)((st.st_size - 1) / (off_t)g->ms_bytes) : 0;
+    if (g->sample_bytes) g->file_samples = (int64_t)(st.st_size / (off_t)g->sample_bytes);
     (void)posix_fadvise(g->fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-    const size_t block_bytes = (size_t)block_ms * g->ms_bytes;
+    const size_t block_bytes = g->host_block_bytes;
     g->host.assign(depth, nullptr);
     g->host_first.assign(depth, 0);
     g->host_ms.assign(depth, 0);
@@ -2381,8 +2509,8 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
         g->uploaded.assign(depth, nullptr);
         g->ready.assign(depth, nullptr);
         for (int i = 0; i < depth; ++i) {
-            if (fmt != kFmtF32) HIP_TRY(ctx, hipMalloc((void**)&g->dev_raw[i], block_bytes));
-            HIP_TRY(ctx, hipMalloc((void**)&g->dev_iq[i], (size_t)block_ms * n * 2 * sizeof(float)));
+            if (g->raw_block_bytes) HIP_TRY(ctx, hipMalloc((void**)&g->dev_raw[i], g->raw_block_bytes));
+            HIP_TRY(ctx, hipMalloc((void**)&g->dev_iq[i], (size_t)g->block_ms * g->n * 2 * sizeof(float)));
             HIP_TRY(ctx, hipEventCreateWithFlags(&g->uploaded[i], hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&g->ready[i], hipEventDisableTiming));
         }
@@ -2396,6 +2524,61 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
     ingest_start_reader(g, 0);
     *out = g;
     return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, int32_t n, int32_t block_ms,
+                    int32_t depth, gyp_ingest** out) {
+    if (!out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open: out is NULL");
+    *out = nullptr;
+    const int wb = ingest_word_bytes(fmt);
+    if (!path || !wb || fs_hz <= 0 || n <= 0 || block_ms < 1 || depth < 3 || depth > 64)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open: bad arguments (format, fs, n, block_ms >= 1, 3 <= depth <= 64)");
+    if ((int64_t)n != fs_hz / 1000)   // antenna_sample_provider.py:135
+        return fail(ctx, GYP_E_BAD_RATE, "gyp_ingest_open: n must be fs // 1000");
+    gyp_ingest* g = new (std::nothrow) gyp_ingest();
+    if (!g) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open: out of memory");
+    g->ctx = ctx;
+    g->fmt = fmt;
+    g->fs = fs_hz;
+    g->n = n;
+    g->block_ms = block_ms;
+    g->depth = depth;
+    g->ms_bytes = (size_t)n * 2 * wb;
+    g->host_block_bytes = (size_t)block_ms * g->ms_bytes;
+    g->raw_block_bytes = fmt != kFmtF32 ? g->host_block_bytes : 0;
+    return ingest_finish_open(ctx, g, path, out);
+}
+
+int gyp_ingest_open_resampled(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int32_t taps, int32_t block_ms,
+                              int32_t depth, gyp_ingest** out) {
+    if (!out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: a context is required");
+    const int wb = ingest_word_bytes(fmt);
+    if (!path || !wb || block_ms < 1 || depth < 3 || depth > 64)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: bad arguments (format, block_ms >= 1, 3 <= depth <= 64)");
+    ResampleDesign d;
+    if (const int rc = resample_get_design(ctx, fs_in_hz, taps, &d, "gyp_ingest_open_resampled")) return rc;
+    gyp_ingest* g = new (std::nothrow) gyp_ingest();
+    if (!g) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open_resampled: out of memory");
+    g->ctx = ctx;
+    g->fmt = fmt;
+    g->fs = d.fs_out;
+    g->n = d.n_out;
+    g->block_ms = block_ms;
+    g->depth = depth;
+    g->resampled = true;
+    g->rs = d;
+    g->in_n = d.n_in;
+    g->halo_lo = d.taps / 2 - 1;
+    g->halo_hi = d.taps / 2;
+    g->sample_bytes = (size_t)2 * wb;
+    g->ms_bytes = (size_t)d.n_in * g->sample_bytes;   // total_ms: the input file's milliseconds, by the rule of gyp_ingest_open
+    g->host_block_bytes = ((size_t)block_ms * d.n_in + d.taps - 1) * g->sample_bytes;
+    g->raw_block_bytes = g->host_block_bytes;
+    return ingest_finish_open(ctx, g, path, out);
 }
 
 int gyp_device_locality(gyp_ctx* ctx, int32_t* numa_node_out, char* cpulist_out, int32_t cap) {
@@ -2445,6 +2628,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     if (!g || !raw_out || !first_ms_out || !n_ms_out) return fail(g ? g->ctx : nullptr, GYP_E_BAD_ARG, "gyp_ingest_next_host: NULL argument");
     *raw_out = nullptr;
     *n_ms_out = 0;
+    if (g->resampled) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now

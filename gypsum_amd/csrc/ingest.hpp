@@ -14,6 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cctype>
 #include <condition_variable>
 #include <cstdio>
@@ -136,6 +137,16 @@ struct gyp_ingest {
     int64_t total_ms = 0;     // milliseconds the reference provider delivers before NoMoreSamplesError
     std::string err;
     HostLocality locality;    // the GPU's NUMA node: the pinned ring is allocated there and the reader thread runs there
+    size_t host_block_bytes = 0, raw_block_bytes = 0;   // one ring slot on the host / of file-width words on the device (0: none)
+
+    // resampled handles (gyp_ingest_open_resampled): n / fs are the OUTPUT rate, ms_bytes the input file's millisecond.  A block
+    // of output milliseconds [first, first + n_ms) is read as input samples first*in_n - halo_lo .. (first+n_ms)*in_n + halo_hi - 1,
+    // zero outside the file's whole samples, and resampled where the widen kernel runs otherwise.
+    bool resampled = false;
+    ResampleDesign rs{};
+    int32_t in_n = 0, halo_lo = 0, halo_hi = 0;
+    size_t sample_bytes = 0;
+    int64_t file_samples = 0;
 
     // host ring, filled by the reader thread
     std::vector<uint8_t*> host;
@@ -166,6 +177,32 @@ struct gyp_ingest {
     int64_t dev_blocks = 0;          // uploads enqueued so far (device slot = index % depth)
 };
 
+// A resampled block's input span with its halo; what lies outside the file's whole samples reads as zero.  0 or an errno.
+static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
+    const size_t sb = g->sample_bytes;
+    const int64_t s0 = first * g->in_n - g->halo_lo;
+    const int64_t count = (int64_t)n_ms * g->in_n + g->halo_lo + g->halo_hi;
+    const int64_t a = std::max<int64_t>(s0, 0), b = std::min<int64_t>(s0 + count, g->file_samples);
+    if (b <= a) {
+        std::memset(buf, 0, (size_t)count * sb);
+        return 0;
+    }
+    std::memset(buf, 0, (size_t)(a - s0) * sb);
+    std::memset(buf + (size_t)(b - s0) * sb, 0, (size_t)(s0 + count - b) * sb);
+    const size_t want = (size_t)(b - a) * sb;
+    size_t got = 0;
+    while (got < want) {
+        const ssize_t r = pread(g->fd, buf + (size_t)(a - s0) * sb + got, want - got, (off_t)((size_t)a * sb + got));
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return errno;
+        }
+        if (r == 0) return EIO;   // file shrank under us
+        got += (size_t)r;
+    }
+    return 0;
+}
+
 static void ingest_reader_main(gyp_ingest* g) {
     for (;;) {
         int slot;
@@ -184,8 +221,8 @@ static void ingest_reader_main(gyp_ingest* g) {
             }
             slot = (int)(g->produced % g->depth);
         }
-        size_t want = (size_t)n_ms * g->ms_bytes, got = 0;
-        int err = 0;
+        size_t want = g->resampled ? 0 : (size_t)n_ms * g->ms_bytes, got = 0;
+        int err = g->resampled ? ingest_read_resampled(g, g->host[slot], first, n_ms) : 0;
         while (got < want) {
             const ssize_t r = pread(g->fd, g->host[slot] + got, want - got, (off_t)((size_t)first * g->ms_bytes + got));
             if (r < 0) {

@@ -19,6 +19,8 @@
 //                       form -- window correlations around the last peak lag on the serial chain, only the lock verdict
 //                       between a peak and the next wipe-off, track_verify_kernel proving every such millisecond's
 //                       arg-max from the full profile in parallel.
+//   resample_kernel     rational-rate resampler (fs_in -> the stream format): file-width words widened and filtered by a
+//                       polyphase FIR, one phase per lane, its taps in registers, the tile's input span in LDS.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -32,3 +34,4 @@
 #include "kernels_dll_exact.hpp"
 #include "kernels_acq.hpp"
 #include "kernels_misc.hpp"
+#include "kernels_resample.hpp"

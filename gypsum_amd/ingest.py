@@ -5,6 +5,10 @@ host buffers with whole blocks of milliseconds; with an engine, `next_device_blo
 uploaded (one block ahead, on a copy stream) as complex64 in HBM, integer recordings being widened on the device.
 Without an engine it is a host-only block reader, which `AntennaSampleProviderBackedByFile(block_ms=...)` uses to
 serve the reference's one-millisecond chunks without a file open per millisecond.
+
+With `resample_from_hz` the recording is at that rate (any whole kHz within a factor 2 of the engine's) and the device blocks
+come out resampled to the engine's stream format (`gyp_ingest_open_resampled`, `gypsum_amd.resample`); `n` and `fs` are then
+the output rate and there are no host blocks.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ _FORMATS = {np.dtype(np.float32): _lib.GYP_FMT_F32, np.dtype(np.int8): _lib.GYP_
 
 class IqFileIngest:
     def __init__(self, path, samples_per_second: int, sample_component_data_type=np.float32, block_ms: int = 100,
-                 depth: int = 4, engine=None) -> None:
+                 depth: int = 4, engine=None, resample_from_hz: Optional[int] = None, taps: int = 32) -> None:
         self.dtype = np.dtype(sample_component_data_type)
         if self.dtype not in _FORMATS:
             raise ValueError(f"unsupported sample component type {self.dtype} (float32, int8, int16, uint8)")
@@ -34,8 +38,17 @@ class IqFileIngest:
         self.block_ms = int(block_ms)
         self._h = C.c_void_p()
         ctx = engine.ctx if engine is not None else None
-        rc = self._lib.gyp_ingest_open(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.fs, self.n, self.block_ms,
-                                       int(depth), C.byref(self._h))
+        self.resample_from_hz = None if resample_from_hz is None else int(resample_from_hz)
+        if self.resample_from_hz is not None:
+            if engine is None:
+                raise ValueError("resampling runs on the device: pass an engine")
+            if engine.fs is not None and engine.fs != self.fs:
+                raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({engine.fs})")
+            rc = self._lib.gyp_ingest_open_resampled(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.resample_from_hz,
+                                                     int(taps), self.block_ms, int(depth), C.byref(self._h))
+        else:
+            rc = self._lib.gyp_ingest_open(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.fs, self.n, self.block_ms,
+                                           int(depth), C.byref(self._h))
         self._check(rc)
 
     def _check(self, rc: int) -> None:
@@ -56,7 +69,7 @@ class IqFileIngest:
 
     @property
     def total_ms(self) -> int:
-        """Milliseconds the reference's provider delivers before NoMoreSamplesError."""
+        """Milliseconds the reference's provider delivers before NoMoreSamplesError (of the input file, when resampling)."""
         return int(self._lib.gyp_ingest_total_ms(self._h))
 
     def set_scale(self, scale: float) -> None:

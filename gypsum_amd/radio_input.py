@@ -62,6 +62,16 @@ class InputFileInfo:
         return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=sample_rate,
                    utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=np.int8)
 
+    @classmethod
+    def raw(cls, path: Path, sample_rate: int, dtype=np.int16, utc_start_time: Optional[datetime.datetime] = None) -> "InputFileInfo":
+        """Interleaved I/Q words of `dtype` (int16, int8, uint8 or float32) at any whole-kHz `sample_rate` (not upstream).  A rate
+        that is not a multiple of 1.023 MHz is read through `AntennaSampleProviderResampled` (gypsum_amd.resample)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int16), np.dtype(np.int8), np.dtype(np.uint8), np.dtype(np.float32)):
+            raise ValueError(f"unsupported sample component type {dt} (int16, int8, uint8, float32)")
+        return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=int(sample_rate),
+                   utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=dt.type)
+
 
 INPUT_SOURCES: List[InputFileInfo] = []
 

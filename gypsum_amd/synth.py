@@ -130,6 +130,39 @@ def render(scene: SyntheticScene, block_ms: int = 50) -> np.ndarray:
     return out
 
 
+def render_at_rate(scene: SyntheticScene, fs: int, block_ms: int = 50) -> np.ndarray:
+    """The continuous-time model of `render` sampled at any rate `fs` (whole kHz; e.g. 4 Msps): complex64[n_ms * fs / 1000].
+
+    Satellite s's code delay is tau = s.code_phase / scene.fs seconds (chip floor((t - tau) * 1.023e6) at t = n / fs), its carrier
+    exp(1j * (2 pi d t + phi)) and its data bit that of receiver millisecond floor(t * 1000), exactly as `render` has them at
+    t = n / scene.fs; the noise is complex white with sigma `scene.noise_sigma` per component and sample at `fs`.  Resampled to
+    scene.fs, satellite s therefore acquires at code phase round(tau * scene.fs) = s.code_phase."""
+    fs = int(fs)
+    if fs % 1000:
+        raise ValueError("fs must be a whole number of kHz")
+    n = fs // 1000
+    chips = generate_ca_code_table().astype(np.float64) * 2 - 1
+    out = np.empty(scene.n_ms * n, dtype=np.complex64)
+    rng = np.random.default_rng([scene.seed, fs])
+    for b0 in range(0, scene.n_ms, block_ms):
+        b1 = min(scene.n_ms, b0 + block_ms)
+        idx = np.arange(b0 * n, b1 * n, dtype=np.int64)
+        t = idx / fs
+        ms = idx // n                                          # receiver millisecond of each sample (exact)
+        acc = np.zeros((b1 - b0) * n, dtype=complex)
+        for s in scene.sats:
+            # chip index floor((t - tau) * 1.023e6) in exact integer arithmetic: (idx * scene.fs - cp * fs) * 1023 // (fs * scene.fs / 1000)
+            num = (idx * scene.fs - s.code_phase * fs) * 1023
+            chip = np.floor_divide(num, fs * (scene.fs // 1000)) % 1023
+            sig = s.amplitude * chips[s.sat_id - 1][chip] * np.exp(1j * (2 * np.pi * s.doppler_hz * t + s.carrier_phase))
+            if s.nav_bits is not None:
+                sig = sig * s.nav_bits[((ms + s.nav_bit_offset_ms) // 20) % len(s.nav_bits)].astype(np.float64)
+            acc += sig
+        acc += scene.noise_sigma * (rng.standard_normal((b1 - b0) * n) + 1j * rng.standard_normal((b1 - b0) * n))
+        out[b0 * n:b1 * n] = acc.astype(np.complex64)
+    return out
+
+
 def nav_symbol_at(sat: SyntheticSatellite, ms: int) -> int:
     """The +-1 data symbol satellite `sat` carries during millisecond `ms` of the scene."""
     if sat.nav_bits is None:

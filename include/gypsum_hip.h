@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 203: gyp_debug_spec_layout_for added (sub-block length by rate: ~167 ms at 2.046 Msps, r06), gyp_grid_best_bins_refined_dev added (float64
+/* 204: on-device resampler for recordings at any whole-kHz rate: gyp_resample_design, gyp_resample_iq_dev, gyp_ingest_open_resampled;
+ *      gyp_debug_set name resample_tile_samples.  Nothing that existed changes.
+ * 203: gyp_debug_spec_layout_for added (sub-block length by rate: ~167 ms at 2.046 Msps, r06), gyp_grid_best_bins_refined_dev added (float64
  *      tie-break of the flat grids' best-bin selection); new gyp_debug_set names (no_grid_fused, grid_fused_waves, spec_sub_ms,
  *      widen_wg_per_cu) and the read-only "last_grid_path" / "last_grid_refined_rows"; defaults changed at the end of r06 (same results):
  *      track_chunk_ms 500 -> 250, the widen kernel's grid 8 -> 2 workgroups per CU.
@@ -36,7 +38,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 203 /* 0.2.3 */
+#define GYP_VERSION 204 /* 0.2.4 */
 
 enum {
     GYP_OK = 0,
@@ -513,6 +515,47 @@ int gyp_ingest_next_dev(gyp_ingest* ing, const float** iq_dev_out, int64_t* firs
  * (antenna_sample_provider.py:88-89), bit-identical to Python's round(). */
 int gyp_ingest_times(const gyp_ingest* ing, int64_t first_ms, int32_t n_ms, double* start_out, double* end_out);
 
+/* ---------------------------------------------------------------- resampler ---------------------------- */
+/* Recordings at any whole-kHz rate (RTL-SDR 2.048 Msps, USRP / bladeRF 4, 5, 10, 20, 25 Msps, ...) become a stream at the
+ * context's format on the device; everything downstream then runs unchanged at that rate.  Opt-in: gyp_set_stream_format and
+ * gyp_ingest_open still refuse such rates.
+ *
+ * Contract.  fs_in = N_in * 1000 Hz; fs_out = N_out * 1000 Hz is the context's stream format (GYP_E_NO_FORMAT if none is set)
+ * or, for gyp_resample_design, the argument.  0.5 <= fs_out / fs_in <= 2 and fs_in != fs_out, else GYP_E_BAD_RATE.  taps T is
+ * 16, 24, 32, 48 or 64 (0 = 32), else GYP_E_BAD_ARG.  Output millisecond m starts exactly at input sample m * N_in; its sample r
+ * (0 <= r < N_out) is
+ *     i0 = m*N_in + floor(r*N_in / N_out),   mu = ((r*N_in) mod N_out) / N_out
+ *     y  = sum_{j = -T/2+1 .. T/2} h_mu[j] * x[i0 + j]
+ *     h_mu[j] = c(j - mu) / sum_j' c(j' - mu),   c(t) = fc * sinc(fc*t) * I0(beta * sqrt(1 - (t/(T/2))^2)) / I0(beta),
+ *     fc = 0.9 * min(fs_in, fs_out) / fs_in,  beta = 8,  sinc(x) = sin(pi x) / (pi x)
+ * x is the recording, word * scale per component (integer formats widened as the ingest does), zero at indices below 0 and at or
+ * beyond the last whole sample of the file or buffer.  Each phase has unit DC gain and is symmetric about the output instant:
+ * output sample n lies at time n / fs_out (no delay), so a signal at code delay tau acquires at code phase round(tau * fs_out).
+ * The design has L = N_out / gcd(N_in, N_out) phases (1023 for 2.048 -> 2.046, 4.0 -> 4.092, 5.0 -> 5.115, 10 -> 8.184).
+ * Passband (float64 model, error of a complex tone <= 2e-4 of its amplitude): |f| <= 0.35 min(fs_in, fs_out) at T = 32, except
+ * at a ratio of 0.5, where 32 taps hold it to 0.25 min(fs_in, fs_out) and T = 64 to 0.35.
+ * An output sample is a fixed function of its inputs (one float32 fma chain in tap order, whatever the call's window, block or
+ * launch shape): blocks, windows and seeks give bit-identical samples. */
+
+/* Host only (no GPU): writes the L x T float32 design, row p = mu * L (phase-major), computed in float64 and rounded.  table_out
+ * NULL: only *n_phases_out = L is written. */
+int gyp_resample_design(int64_t fs_in_hz, int64_t fs_out_hz, int32_t taps, float* table_out, int32_t* n_phases_out);
+/* raw_dev holds n_streams streams of interleaved I,Q words of format fmt (GYP_FMT_*), stream s at raw_dev + s * in_stride_samples
+ * samples; its sample 0 is input sample raw_first_sample (may be negative), and only raw_n_samples of them (<= in_stride_samples)
+ * exist: the rest read as zero.  Writes output milliseconds first_ms .. first_ms+n_ms-1 of every stream, complex64, stream s at
+ * out_dev + s * out_stride_samples samples (>= n_ms * N_out).  Enqueued on the context's stream; the design is built on first
+ * use of each (fs_in, fs_out, taps) and cached on the context. */
+int gyp_resample_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_streams, int64_t in_stride_samples,
+                        int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t fs_in_hz, int32_t taps, int64_t first_ms,
+                        int32_t n_ms, int64_t out_stride_samples, float* out_dev);
+/* An ingest handle over a recording at fs_in_hz whose device blocks are at the context's rate (ctx required).  The reader preads
+ * each block's input span plus its (T-1)-sample halo (zero beyond the file's edges); the upload stream runs the resampler where
+ * it would run the widen kernel.  gyp_ingest_total_ms applies gyp_ingest_open's rule ((size - 1) / input millisecond bytes) to the
+ * input file; gyp_ingest_times gives round(k * N_out / fs_out, 6); set_scale, seek, next_dev and close keep their meaning;
+ * gyp_ingest_next_host returns GYP_E_BAD_ARG. */
+int gyp_ingest_open_resampled(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int32_t taps, int32_t block_ms,
+                              int32_t depth, gyp_ingest** out);
+
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
  * with a message otherwise) and defaults:
@@ -536,6 +579,7 @@ int gyp_ingest_times(const gyp_ingest* ing, int64_t first_ms, int32_t n_ms, doub
  *   "spec_redo" 0/1 (1)         0: a failed speculation is re-run on the throughput kernel (r03 behaviour)
  *   "spec_debug" 0/1 (0)        per-ms window dump for gyp_debug_spec_read
  *   "track_chunk_ms" 0 | >= 20 (250)   launch length of the throughput tracking kernel (0: whole blocks)
+ *   "resample_tile_samples" 1024..8192 (4096)  LDS budget of one resampler workgroup, in input samples; same output for any value
  *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring); same output for any value
  *   "exact_prefetch" 0/1 (0)    dll_exact_wave_kernel with its next window software-prefetched (A/B: measured slower, profiles/r04_exact_ab.txt)
  *   "prof_wave" 0..7 (0)        which wavefront of workgroup 0 stamps the counters of gyp_debug_track_profile
