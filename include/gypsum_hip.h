@@ -532,8 +532,14 @@ int gyp_ingest_times(const gyp_ingest* ing, int64_t first_ms, int32_t n_ms, doub
  * beyond the last whole sample of the file or buffer.  Each phase has unit DC gain and is symmetric about the output instant:
  * output sample n lies at time n / fs_out (no delay), so a signal at code delay tau acquires at code phase round(tau * fs_out).
  * The design has L = N_out / gcd(N_in, N_out) phases (1023 for 2.048 -> 2.046, 4.0 -> 4.092, 5.0 -> 5.115, 10 -> 8.184).
- * Passband (float64 model, error of a complex tone <= 2e-4 of its amplitude): |f| <= 0.35 min(fs_in, fs_out) at T = 32, except
- * at a ratio of 0.5, where 32 taps hold it to 0.25 min(fs_in, fs_out) and T = 64 to 0.35.
+ * Passband (float64 model, error of a complex tone <= 2e-4 of its amplitude): |f| <= B * min(fs_in, fs_out), measured at
+ * ratios near 1, near 2 and at exactly 0.5, where the T input taps span only T/2 outputs and the band is narrowest:
+ *         T    ratio near 1 or 2    ratio 0.5
+ *        16          0.25              0.12
+ *        24          0.30              0.20
+ *        32          0.35              0.25
+ *        48          0.35              0.30
+ *        64          0.35              0.35
  * An output sample is a fixed function of its inputs (one float32 fma chain in tap order, whatever the call's window, block or
  * launch shape): blocks, windows and seeks give bit-identical samples. */
 
