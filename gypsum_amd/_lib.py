@@ -58,7 +58,7 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_chan_in": CHAN_IN.itemsize, "gyp_chan_out": CHAN_OUT.itemsize, "gyp_best_bin": BEST_BIN.itemsize,
                 "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
-GYP_VERSION = 204
+GYP_VERSION = 205
 
 EXPORTS = (
     "gyp_version gyp_create gyp_destroy gyp_last_error gyp_device_name gyp_set_stream gyp_sync gyp_wait_for gyp_timer_start "
@@ -70,7 +70,7 @@ EXPORTS = (
     "gyp_grid_best_bins_dev gyp_grid_best_bins_refined_dev gyp_comm_unique_id gyp_comm_init gyp_comm_destroy gyp_comm_info gyp_allgather_dev gyp_host_alloc gyp_host_free gyp_widen_iq_dev "
     "gyp_bits_create gyp_bits_destroy gyp_bits_reset gyp_bits_push gyp_bits_push_block gyp_bits_drain gyp_bits_get_state "
     "gyp_ingest_open gyp_ingest_close gyp_ingest_total_ms gyp_ingest_set_scale gyp_ingest_seek gyp_ingest_next_host gyp_ingest_next_dev gyp_ingest_times "
-    "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled"
+    "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc"
 ).split()
 
 
@@ -183,6 +183,9 @@ def load() -> C.CDLL:
         "gyp_resample_design": (C.c_int, [i64, i64, i32, vp, C.POINTER(i32)]),
         "gyp_resample_iq_dev": (C.c_int, [vp, i32, vp, i32, i64, i64, i64, C.c_float, i64, i32, i64, i32, i64, vp]),
         "gyp_ingest_open_resampled": (C.c_int, [vp, C.c_char_p, i32, i64, i32, i32, i32, C.POINTER(vp)]),
+        "gyp_ddc_design": (C.c_int, [i64, i64, i64, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "gyp_ddc_iq_dev": (C.c_int, [vp, i32, vp, i32, i64, i64, i64, C.c_float, i64, i64, i32, i64, i32, i64, vp]),
+        "gyp_ingest_open_ddc": (C.c_int, [vp, C.c_char_p, i32, i64, i64, i32, i32, i32, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

@@ -187,25 +187,37 @@ class AntennaSampleProviderResampled(_CursorProvider):
 
     `path` may be an `InputFileInfo` (e.g. `InputFileInfo.raw(path, 4_000_000, np.int16)`); `resample_to` defaults to
     `nearest_supported_rate(sample_rate)`; `scale` multiplies integer words (an 8-bit front end wants about 1/100, see
-    gyp_ingest_set_scale)."""
+    gyp_ingest_set_scale).
+
+    A real recording at an intermediate frequency (`InputFileInfo.real_if(...)`, or `if_hz=`) is down-converted to complex
+    baseband instead (`gyp_ingest_open_ddc`); `resample_to` then defaults to `default_ddc_rate(sample_rate, if_hz)` and `taps`
+    to the down-converter's automatic choice."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
-                 sample_component_data_type=np.float32, scale: float = 1.0, taps: int = 32, block_ms: int = 250,
-                 engine=None, device: int = 0) -> None:
+                 sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
+                 engine=None, device: int = 0, if_hz: int | None = None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
-        from .resample import nearest_supported_rate
+        from .resample import default_ddc_rate, nearest_supported_rate
 
         if hasattr(path, "sdr_sample_rate"):
             info = path
             path, sample_rate = info.path, info.sdr_sample_rate
             utc_start_time = info.utc_start_time.timestamp()
             sample_component_data_type = info.sample_component_data_type
+            if if_hz is None:
+                if_hz = getattr(info, "if_hz", None)
         if sample_rate is None:
             raise TypeError("sample_rate is required when no InputFileInfo is given")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
-        self.sample_rate = int(resample_to) if resample_to is not None else nearest_supported_rate(self.input_sample_rate)
+        self.if_hz = None if if_hz is None else int(if_hz)
+        if resample_to is not None:
+            self.sample_rate = int(resample_to)
+        elif self.if_hz is not None:
+            self.sample_rate = default_ddc_rate(self.input_sample_rate, self.if_hz)
+        else:
+            self.sample_rate = nearest_supported_rate(self.input_sample_rate)
         self.n = self.sample_rate // PRN_REPETITIONS_PER_SECOND
         self.cursor = 0
         self.utc_start_time = utc_start_time
@@ -218,7 +230,7 @@ class AntennaSampleProviderResampled(_CursorProvider):
             self._own_engine = False
         self.engine = engine
         self._ingest = IqFileIngest(self.path, self.sample_rate, sample_component_data_type, block_ms=block_ms, engine=engine,
-                                    resample_from_hz=self.input_sample_rate, taps=taps)
+                                    resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
         if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
             self._ingest.set_scale(scale)
         self.total_ms = self._ingest.total_ms

@@ -2263,16 +2263,10 @@ int gyp_bits_get_state(const gyp_bits* bits, int32_t channel, gyp_bits_state* ou
 // ---------------------------------------------------------------------------------------------------------
 // Resampler (kernels_resample.hpp): fs_in recordings -> the stream format
 // ---------------------------------------------------------------------------------------------------------
-// The design for (fs_in, the context's rate, taps), built and uploaded on first use.  A copy: the context owns d_taps.
-static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, ResampleDesign* out, const char* who) {
-    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
-    const int32_t T = resample_taps(taps);
-    if (!T) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (32), 16, 24, 32, 48 or 64");
-    if (!resample_rates_ok(fs_in, ctx->fs))
-        return fail(ctx, GYP_E_BAD_RATE, std::string(who) + ": fs_in must be a positive multiple of 1000 Hz, differ from the stream format's rate "
-                                                            "and lie within a factor 2 of it");
+// The design for (fs_in, the context's rate, T, input kind), built and uploaded on first use.  A copy: the context owns d_taps.
+static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool real, ResampleDesign* out, const char* who) {
     for (const ResampleDesign& d : ctx->resample_designs)
-        if (d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T) {
+        if (d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T && d.real == real) {
             *out = d;
             return GYP_OK;
         }
@@ -2280,6 +2274,7 @@ static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, Resamp
     d.fs_in = fs_in;
     d.fs_out = ctx->fs;
     d.taps = T;
+    d.real = real;
     d.n_in = (int32_t)(fs_in / 1000);
     d.n_out = (int32_t)(ctx->fs / 1000);
     d.g = (int32_t)resample_gcd(d.n_in, d.n_out);
@@ -2304,10 +2299,73 @@ static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, Resamp
     return GYP_OK;
 }
 
-// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.
+static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, ResampleDesign* out, const char* who) {
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    const int32_t T = resample_taps(taps);
+    if (!T) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (32), 16, 24, 32, 48 or 64");
+    if (!resample_rates_ok(fs_in, ctx->fs))
+        return fail(ctx, GYP_E_BAD_RATE, std::string(who) + ": fs_in must be a positive multiple of 1000 Hz, differ from the stream format's rate "
+                                                            "and lie within a factor 2 of it");
+    return resample_cached_design(ctx, fs_in, T, false, out, who);
+}
+
+static const char* const kDdcRateRule = ": rates must be whole kHz with fs_in < 2^31 Hz and 8 fs_out >= fs_in, and the IF must satisfy "
+                                        "20 |if| >= 9 fs_out and 20 |if| + 9 fs_out <= 10 fs_in";
+
+static int ddc_get_design(gyp_ctx* ctx, int64_t fs_in, int64_t if_hz, int32_t taps, ResampleDesign* out, const char* who) {
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    if (taps && !ddc_taps(taps, 0, 0)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (auto), 32, 48, 64, 96 or 128");
+    if (!ddc_rates_ok(fs_in, ctx->fs, if_hz)) return fail(ctx, GYP_E_BAD_RATE, std::string(who) + kDdcRateRule);
+    return resample_cached_design(ctx, fs_in, ddc_taps(taps, fs_in, ctx->fs), true, out, who);
+}
+
+template <class S, int TT>
+static void resample_launch_one(dim3 grid, size_t lds, hipStream_t stream, const void* raw, int64_t in_stride, int64_t raw_first,
+                                int64_t raw_n, const typename S::Params& prm, const ResampleDesign& d, int64_t p_first, int64_t n_periods,
+                                int32_t np_tile, int32_t pc_tile, int32_t n_pchunks, float* out, int64_t out_stride) {
+    S stage;
+    static_cast<typename S::Params&>(stage) = prm;
+    hipLaunchKernelGGL((resample_kernel<S, TT>), grid, dim3(256), lds, stream, (const typename S::Word*)raw, in_stride, raw_first, raw_n,
+                       stage, d.d_taps, d.L, d.M, p_first, n_periods, np_tile, pc_tile, n_pchunks, (float2*)out, out_stride);
+}
+
+// The tap counts each policy is instantiated for: the resampler's 16..64, the down-converter's 32..128.
+template <class S, class... A>
+static void resample_launch_taps(int32_t T, const A&... a) {
+    if constexpr (S::kWords == 2) {
+        switch (T) {
+            case 16: resample_launch_one<S, 16>(a...); break;
+            case 24: resample_launch_one<S, 24>(a...); break;
+            case 32: resample_launch_one<S, 32>(a...); break;
+            case 48: resample_launch_one<S, 48>(a...); break;
+            default: resample_launch_one<S, 64>(a...); break;
+        }
+    } else {
+        switch (T) {
+            case 32: resample_launch_one<S, 32>(a...); break;
+            case 48: resample_launch_one<S, 48>(a...); break;
+            case 64: resample_launch_one<S, 64>(a...); break;
+            case 96: resample_launch_one<S, 96>(a...); break;
+            default: resample_launch_one<S, 128>(a...); break;
+        }
+    }
+}
+
+template <template <class> class Stage, class... A>
+static void resample_launch_fmt(int32_t fmt, int32_t T, const A&... a) {
+    switch (fmt) {
+        case GYP_FMT_F32: resample_launch_taps<Stage<float>>(T, a...); break;
+        case GYP_FMT_I8: resample_launch_taps<Stage<int8_t>>(T, a...); break;
+        case GYP_FMT_U8: resample_launch_taps<Stage<uint8_t>>(T, a...); break;
+        default: resample_launch_taps<Stage<int16_t>>(T, a...); break;
+    }
+}
+
+// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.  A real design (the
+// down-converter's) stages real words mixed down from if_hz; in_stride / raw_first / raw_n count samples either way.
 static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, int32_t fmt, const void* raw, int32_t n_streams,
                            int64_t in_stride, int64_t raw_first, int64_t raw_n, float scale, int64_t first_ms, int32_t n_ms,
-                           float* out, int64_t out_stride) {
+                           float* out, int64_t out_stride, int64_t if_hz = 0) {
     const int64_t n_periods = (int64_t)n_ms * d.g;
     const int32_t T = d.taps, TS = ctx->resample_tile;
     int32_t np_tile = 1, pc_tile = d.L, n_pchunks = 1;
@@ -2322,30 +2380,34 @@ static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesig
     }
     const int64_t n_tiles = (n_periods + np_tile - 1) / np_tile * n_pchunks;
     if (n_tiles > INT32_MAX || n_streams > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample: launch too large (split it)");
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_streams), block(256);
+    const dim3 grid((unsigned)n_tiles, (unsigned)n_streams);
     const size_t lds = lds_samples * sizeof(float2);
     const int64_t p_first = first_ms * d.g;
-#define GYP_RS_LAUNCH(W, TT)                                                                                                      \
-    hipLaunchKernelGGL((resample_kernel<W, TT>), grid, block, lds, stream, (const W*)raw, in_stride, raw_first, raw_n, scale, d.d_taps, \
-                       d.L, d.M, p_first, n_periods, np_tile, pc_tile, n_pchunks, (float2*)out, out_stride)
-#define GYP_RS_TAPS(W)                        \
-    switch (T) {                              \
-        case 16: GYP_RS_LAUNCH(W, 16); break; \
-        case 24: GYP_RS_LAUNCH(W, 24); break; \
-        case 32: GYP_RS_LAUNCH(W, 32); break; \
-        case 48: GYP_RS_LAUNCH(W, 48); break; \
-        default: GYP_RS_LAUNCH(W, 64); break; \
+    if (d.real) {
+        const int64_t fs = d.fs_in;
+        const int64_t f = (if_hz % fs + fs) % fs;
+        resample_launch_fmt<StageReal>(fmt, T, grid, lds, stream, raw, in_stride, raw_first, raw_n, StageRealParams{scale, fs, f, 4.0 / (double)fs, 0.5 / (double)fs},
+                                       d, p_first, n_periods, np_tile, pc_tile, n_pchunks, out, out_stride);
+    } else {
+        resample_launch_fmt<StageIQ>(fmt, T, grid, lds, stream, raw, in_stride, raw_first, raw_n, StageIQParams{scale}, d, p_first,
+                                     n_periods, np_tile, pc_tile, n_pchunks, out, out_stride);
     }
-    switch (fmt) {
-        case GYP_FMT_F32: GYP_RS_TAPS(float) break;
-        case GYP_FMT_I8: GYP_RS_TAPS(int8_t) break;
-        case GYP_FMT_U8: GYP_RS_TAPS(uint8_t) break;
-        default: GYP_RS_TAPS(int16_t) break;
-    }
-#undef GYP_RS_TAPS
-#undef GYP_RS_LAUNCH
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
+}
+
+// The argument checks and the launch of gyp_resample_iq_dev / gyp_ddc_iq_dev, on the context's stream.
+static int resample_iq_checked(gyp_ctx* ctx, const ResampleDesign& d, const char* who, int32_t fmt, const void* raw_dev, int32_t n_streams,
+                               int64_t in_stride_samples, int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t if_hz,
+                               int64_t first_ms, int32_t n_ms, int64_t out_stride_samples, float* out_dev) {
+    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || raw_n_samples < 0 || in_stride_samples < raw_n_samples ||
+        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, "
+                                                           "in_stride >= raw_n_samples >= 0, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return resample_launch(ctx, ctx->stream, d, fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples, scale,
+                           first_ms, n_ms, out_dev, out_stride_samples, if_hz);
 }
 
 extern "C" {
@@ -2369,14 +2431,32 @@ int gyp_resample_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t 
     if (!ingest_word_bytes(fmt)) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample_iq_dev: fmt must be one of GYP_FMT_*");
     ResampleDesign d;
     if (const int rc = resample_get_design(ctx, fs_in_hz, taps, &d, "gyp_resample_iq_dev")) return rc;
-    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || raw_n_samples < 0 || in_stride_samples < raw_n_samples ||
-        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_resample_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, "
-                                        "in_stride >= raw_n_samples >= 0, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
-    if (n_ms == 0) return GYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return resample_launch(ctx, ctx->stream, d, fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples, scale,
-                           first_ms, n_ms, out_dev, out_stride_samples);
+    return resample_iq_checked(ctx, d, "gyp_resample_iq_dev", fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples,
+                               scale, 0, first_ms, n_ms, out_stride_samples, out_dev);
+}
+
+int gyp_ddc_design(int64_t fs_in_hz, int64_t fs_out_hz, int64_t if_hz, int32_t taps, float* table_out, int32_t* n_phases_out,
+                   int32_t* taps_out) {
+    if (taps && !ddc_taps(taps, 0, 0)) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ddc_design: taps must be 0 (auto), 32, 48, 64, 96 or 128");
+    if (!ddc_rates_ok(fs_in_hz, fs_out_hz, if_hz)) return fail(nullptr, GYP_E_BAD_RATE, std::string("gyp_ddc_design") + kDdcRateRule);
+    const int32_t T = ddc_taps(taps, fs_in_hz, fs_out_hz);
+    const int64_t n_out = fs_out_hz / 1000;
+    const int32_t L = (int32_t)(n_out / resample_gcd(fs_in_hz / 1000, n_out));
+    if (n_phases_out) *n_phases_out = L;
+    if (taps_out) *taps_out = T;
+    if (table_out) resample_design_rows(fs_in_hz, fs_out_hz, T, L, table_out);
+    return GYP_OK;
+}
+
+int gyp_ddc_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_streams, int64_t in_stride_samples, int64_t raw_first_sample,
+                   int64_t raw_n_samples, float scale, int64_t fs_in_hz, int64_t if_hz, int32_t taps, int64_t first_ms, int32_t n_ms,
+                   int64_t out_stride_samples, float* out_dev) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (!ingest_word_bytes(fmt)) return fail(ctx, GYP_E_BAD_ARG, "gyp_ddc_iq_dev: fmt must be one of GYP_FMT_*");
+    ResampleDesign d;
+    if (const int rc = ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, "gyp_ddc_iq_dev")) return rc;
+    return resample_iq_checked(ctx, d, "gyp_ddc_iq_dev", fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples,
+                               scale, if_hz, first_ms, n_ms, out_stride_samples, out_dev);
 }
 
 }  // extern "C"
@@ -2429,7 +2509,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
         HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream));
         HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
         if (const int rc = resample_launch(ctx, g->copy_stream, g->rs, g->fmt, g->dev_raw[d], 1, span, u->first_ms * g->in_n - g->halo_lo, span,
-                                           g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n))
+                                           g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n, g->if_hz))
             return rc;
         HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
         g->in_flight.push_back(*u);
@@ -2526,6 +2606,40 @@ static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp
     return GYP_OK;
 }
 
+// gyp_ingest_open_resampled (I,Q words) and gyp_ingest_open_ddc (real words at an IF): one handle type, the same reader, halo,
+// ring and upload stream; `real` changes the bytes per sample and the kernel's staging policy.
+static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, bool real, int64_t if_hz, int32_t taps,
+                                int32_t block_ms, int32_t depth, gyp_ingest** out, const char* who) {
+    if (!out) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, std::string(who) + ": a context is required");
+    const int wb = ingest_word_bytes(fmt);
+    if (!path || !wb || block_ms < 1 || depth < 3 || depth > 64)
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (format, block_ms >= 1, 3 <= depth <= 64)");
+    ResampleDesign d;
+    if (const int rc = real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who)) return rc;
+    gyp_ingest* g = new (std::nothrow) gyp_ingest();
+    if (!g) return fail(ctx, GYP_E_NOMEM, std::string(who) + ": out of memory");
+    g->ctx = ctx;
+    g->fmt = fmt;
+    g->fs = d.fs_out;
+    g->n = d.n_out;
+    g->block_ms = block_ms;
+    g->depth = depth;
+    g->resampled = true;
+    g->real = real;
+    g->if_hz = if_hz;
+    g->rs = d;
+    g->in_n = d.n_in;
+    g->halo_lo = d.taps / 2 - 1;
+    g->halo_hi = d.taps / 2;
+    g->sample_bytes = (size_t)(real ? 1 : 2) * wb;
+    g->ms_bytes = (size_t)d.n_in * g->sample_bytes;   // total_ms: the input file's milliseconds, by the rule of gyp_ingest_open
+    g->host_block_bytes = ((size_t)block_ms * d.n_in + d.taps - 1) * g->sample_bytes;
+    g->raw_block_bytes = g->host_block_bytes;
+    return ingest_finish_open(ctx, g, path, out);
+}
+
 extern "C" {
 
 int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, int32_t n, int32_t block_ms,
@@ -2553,32 +2667,12 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
 
 int gyp_ingest_open_resampled(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int32_t taps, int32_t block_ms,
                               int32_t depth, gyp_ingest** out) {
-    if (!out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: out is NULL");
-    *out = nullptr;
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: a context is required");
-    const int wb = ingest_word_bytes(fmt);
-    if (!path || !wb || block_ms < 1 || depth < 3 || depth > 64)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open_resampled: bad arguments (format, block_ms >= 1, 3 <= depth <= 64)");
-    ResampleDesign d;
-    if (const int rc = resample_get_design(ctx, fs_in_hz, taps, &d, "gyp_ingest_open_resampled")) return rc;
-    gyp_ingest* g = new (std::nothrow) gyp_ingest();
-    if (!g) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open_resampled: out of memory");
-    g->ctx = ctx;
-    g->fmt = fmt;
-    g->fs = d.fs_out;
-    g->n = d.n_out;
-    g->block_ms = block_ms;
-    g->depth = depth;
-    g->resampled = true;
-    g->rs = d;
-    g->in_n = d.n_in;
-    g->halo_lo = d.taps / 2 - 1;
-    g->halo_hi = d.taps / 2;
-    g->sample_bytes = (size_t)2 * wb;
-    g->ms_bytes = (size_t)d.n_in * g->sample_bytes;   // total_ms: the input file's milliseconds, by the rule of gyp_ingest_open
-    g->host_block_bytes = ((size_t)block_ms * d.n_in + d.taps - 1) * g->sample_bytes;
-    g->raw_block_bytes = g->host_block_bytes;
-    return ingest_finish_open(ctx, g, path, out);
+    return ingest_open_filtered(ctx, path, fmt, fs_in_hz, false, 0, taps, block_ms, depth, out, "gyp_ingest_open_resampled");
+}
+
+int gyp_ingest_open_ddc(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int64_t if_hz, int32_t taps, int32_t block_ms,
+                        int32_t depth, gyp_ingest** out) {
+    return ingest_open_filtered(ctx, path, fmt, fs_in_hz, true, if_hz, taps, block_ms, depth, out, "gyp_ingest_open_ddc");
 }
 
 int gyp_device_locality(gyp_ctx* ctx, int32_t* numa_node_out, char* cpulist_out, int32_t cap) {

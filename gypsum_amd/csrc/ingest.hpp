@@ -143,6 +143,8 @@ struct gyp_ingest {
     // of output milliseconds [first, first + n_ms) is read as input samples first*in_n - halo_lo .. (first+n_ms)*in_n + halo_hi - 1,
     // zero outside the file's whole samples, and resampled where the widen kernel runs otherwise.
     bool resampled = false;
+    bool real = false;        // gyp_ingest_open_ddc: one real word per sample, mixed down from if_hz (the mixer index is the file index)
+    int64_t if_hz = 0;
     ResampleDesign rs{};
     int32_t in_n = 0, halo_lo = 0, halo_hi = 0;
     size_t sample_bytes = 0;

@@ -1,5 +1,7 @@
 // kernels_resample.hpp -- rational-rate resampler: interleaved I,Q words at fs_in -> complex64 at the stream format's fs_out
-// (gyp_resample_iq_dev, gyp_ingest_open_resampled; the contract is written down in include/gypsum_hip.h).
+// (gyp_resample_iq_dev, gyp_ingest_open_resampled), and the digital down-converter in front of the same filter: real words at an
+// intermediate frequency -> complex baseband (gyp_ddc_iq_dev, gyp_ingest_open_ddc).  The contracts are written down in
+// include/gypsum_hip.h ("resampler", "down-converter").
 //
 // Both rates are whole kHz.  With g = gcd(N_in, N_out), L = N_out / g and M = N_in / g the phase pattern repeats every L outputs
 // and M inputs: output n = P*L + p (period P, phase p) sits at input instant P*M + p*M/L, i.e. at the integer base
@@ -10,6 +12,10 @@
 // tile, so the taps are read once per tile instead of once per output, and neighbouring lanes read neighbouring LDS samples and
 // write neighbouring outputs.  Every output is the same chain of fmaf over its T taps in tap order whatever the tile, the
 // window or the launch, so blocks, windowed calls and seeks give bit-identical samples.
+//
+// The staging step is a compile-time policy: StageIQ widens an I,Q word pair to float2; StageReal widens one real word and
+// multiplies it by the mixer exp(-j 2 pi ((if_hz * i) mod fs_in) / fs_in) of its absolute input index i, a pure function of i
+// (exact integer phase, no accumulator), so the bit-identity argument above carries over unchanged.
 #pragma once
 
 #include <algorithm>
@@ -21,6 +27,7 @@
 struct ResampleDesign {
     int64_t fs_in = 0, fs_out = 0;
     int32_t taps = 0;
+    bool real = false;   // the down-converter's (real words at an IF); the cache key includes it
     int32_t n_in = 0, n_out = 0, g = 0, L = 0, M = 0;
     float* d_taps = nullptr;
 };
@@ -44,6 +51,24 @@ static inline int32_t resample_taps(int32_t taps) {
 static inline bool resample_rates_ok(int64_t fs_in, int64_t fs_out) {
     if (fs_in <= 0 || fs_out <= 0 || fs_in % 1000 || fs_out % 1000 || fs_in == fs_out) return false;
     return 2 * fs_out >= fs_in && fs_out <= 2 * fs_in;
+}
+
+// Down-converter taps: 0 -> the smallest of 32, 48, 64, 96, 128 with T * fs_out >= 16 * fs_in (the filter spans >= 16 outputs);
+// otherwise one of those five.  Returns 0 if not allowed (or if 0 cannot be resolved, which ddc_rates_ok rules out).
+static inline int32_t ddc_taps(int32_t taps, int64_t fs_in, int64_t fs_out) {
+    static const int32_t kTaps[] = {32, 48, 64, 96, 128};
+    for (int32_t t : kTaps)
+        if (taps == t || (taps == 0 && t * fs_out >= 16 * fs_in)) return t;
+    return 0;
+}
+
+// Rates and IF the down-converter accepts, in integers: whole kHz, fs_in < 2^31 Hz, 8 fs_out >= fs_in, 20 |if| >= 9 fs_out (the
+// mirror band at -2 if clears the +-0.45 fs_out passband), 20 |if| + 9 fs_out <= 10 fs_in (the band lies below the real Nyquist).
+static inline bool ddc_rates_ok(int64_t fs_in, int64_t fs_out, int64_t if_hz) {
+    if (fs_in <= 0 || fs_out <= 0 || fs_in % 1000 || fs_out % 1000 || fs_in > INT32_MAX || fs_out > fs_in) return false;
+    if (if_hz < -fs_in || if_hz > fs_in) return false;   // keeps 20 |if| in range; the last rule refuses these anyway
+    const int64_t a = if_hz < 0 ? -if_hz : if_hz;
+    return 8 * fs_out >= fs_in && 20 * a >= 9 * fs_out && 20 * a + 9 * fs_out <= 10 * fs_in;
 }
 
 static double resample_i0(double x) {   // modified Bessel function of the first kind, order 0 (power series; x <= 8 here)
@@ -88,10 +113,81 @@ __device__ __forceinline__ float2 resample_load(const W* __restrict__ s, float s
     return make_float2((float)s[0] * scale, (float)s[1] * scale);
 }
 
+// exp(-j 2 pi r / fs) for 0 <= r < fs, in float32 within 2^-22 of the exact value.  The nearest quarter turn k = rint(4 r / fs)
+// comes off exactly in integers (e = 4 r - k fs, |e| <= fs / 2), so sincospif sees |y| = |e| / (2 fs) <= 1/4 with an argument
+// error of at most half a float32 ulp there (2^-27: pi 2^-27 rad), and its own error is about an ulp of values below 1
+// (2^-24); the quarter turn is an exact swap and sign change.  A function of r alone: the same r gives the same bits.
+__device__ __forceinline__ float2 ddc_mixer(int64_t r, int64_t fs, double q_scale, double y_scale) {
+    const int64_t k = (int64_t)rint((double)r * q_scale);
+    const float y = (float)((double)(4 * r - k * fs) * y_scale);
+    float s, c;
+    sincospif(y, &s, &c);                   // theta = pi/2 k + pi y
+    const int q = (int)(k & 3);
+    const float ct = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
+    const float st = q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c;
+    return make_float2(ct, -st);
+}
+
+// Staging policies of resample_kernel: xs[k] = the filter input at absolute index s0 + k (zero outside [0, ...) and outside the
+// buffer's raw_n samples, which start at index raw_first).
+// Each policy is its W-independent parameter block plus the staging loop for word type W.
+struct StageIQParams {
+    float scale;
+};
+struct StageRealParams {
+    float scale;
+    int64_t fs;        // fs_in (< 2^31)
+    int64_t f;         // if_hz mod fs, in [0, fs)
+    double q_scale;    // 4 / fs
+    double y_scale;    // 1 / (2 fs)
+};
+
+template <class W>
+struct StageIQ : StageIQParams {   // interleaved I,Q words: (I, Q) * scale
+    using Word = W;
+    using Params = StageIQParams;
+    static constexpr int kWords = 2;   // words per sample
+    static constexpr bool kSplitPeriods = false;   // lanes split the tile's periods too (see resample_kernel)
+    __device__ __forceinline__ void stage(float2* xs, const W* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
+                                          int64_t raw_n) const {
+        for (int32_t k = threadIdx.x; k < span; k += blockDim.x) {
+            const int64_t idx = s0 + k;
+            const int64_t rel = idx - raw_first;
+            xs[k] = (idx >= 0 && rel >= 0 && rel < raw_n) ? resample_load(src + 2 * rel, scale) : make_float2(0.f, 0.f);
+        }
+    }
+};
+
+template <class W>
+struct StageReal : StageRealParams {   // real words at an IF: word * scale * exp(-j 2 pi ((if_hz * i) mod fs) / fs)
+    using Word = W;
+    using Params = StageRealParams;
+    static constexpr int kWords = 1;
+    static constexpr bool kSplitPeriods = true;
+    __device__ __forceinline__ void stage(float2* xs, const W* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
+                                          int64_t raw_n) const {
+        // r = (f * i) mod fs, exactly: one 64-bit reduction of this lane's first index, then steps of blockDim samples in
+        // integers below 2^32 (f, r, step < fs < 2^31)
+        int64_t i = (s0 + (int64_t)threadIdx.x) % fs;
+        if (i < 0) i += fs;
+        int64_t r = f * i % fs;
+        const int64_t step = f * (int64_t)blockDim.x % fs;
+        for (int32_t k = threadIdx.x; k < span; k += blockDim.x) {
+            const int64_t idx = s0 + k;
+            const int64_t rel = idx - raw_first;
+            const float x = (idx >= 0 && rel >= 0 && rel < raw_n) ? (float)src[rel] * scale : 0.f;
+            const float2 m = ddc_mixer(r, fs, q_scale, y_scale);
+            xs[k] = make_float2(x * m.x, x * m.y);
+            r += step;
+            if (r >= fs) r -= fs;
+        }
+    }
+};
+
 // grid: x = period tiles * phase chunks (chunk fastest), y = streams; dynamic LDS: the largest tile span in float2.
-template <class W, int T>
-__global__ __launch_bounds__(256) void resample_kernel(const W* __restrict__ raw, int64_t in_stride, int64_t raw_first, int64_t raw_n,
-                                                       float scale, const float* __restrict__ taps, int32_t L, int32_t M,
+template <class S, int T>
+__global__ __launch_bounds__(256) void resample_kernel(const typename S::Word* __restrict__ raw, int64_t in_stride, int64_t raw_first,
+                                                       int64_t raw_n, S stage, const float* __restrict__ taps, int32_t L, int32_t M,
                                                        int64_t p_first, int64_t n_periods, int32_t np_tile, int32_t pc_tile,
                                                        int32_t n_pchunks, float2* __restrict__ out, int64_t out_stride) {
     extern __shared__ float2 xs[];
@@ -107,22 +203,33 @@ __global__ __launch_bounds__(256) void resample_kernel(const W* __restrict__ raw
     // input samples s0 .. s0+span-1: from tap -T/2+1 of (P0, pa) to tap T/2 of (P1-1, pb-1)
     const int64_t s0 = P0 * M + off_a - (T / 2 - 1);
     const int32_t span = (int32_t)((P1 - 1 - P0) * M + off_b - off_a + T);
-    const W* src = raw + stream * in_stride * 2;
-    for (int32_t k = threadIdx.x; k < span; k += blockDim.x) {
-        const int64_t idx = s0 + k;
-        const int64_t rel = idx - raw_first;
-        xs[k] = (idx >= 0 && rel >= 0 && rel < raw_n) ? resample_load(src + 2 * rel, scale) : make_float2(0.f, 0.f);
-    }
+    stage.stage(xs, raw + stream * in_stride * S::kWords, s0, span, raw_first, raw_n);
     __syncthreads();
     float2* dst = out + stream * out_stride;
-    for (int32_t p = pa + (int32_t)threadIdx.x; p < pb; p += blockDim.x) {
+    // Lanes over (phase, group of four periods).  StageIQ: one lane per phase, every period of the tile.  StageReal also splits
+    // the periods when the tile has fewer phases than lanes, as its ratios often do (L = 1 at 16.368 -> 4.092, 3 at
+    // 38.192 -> 8.184): lane (p, grp) takes the quads grp, grp + n_grp, ...  Which lane computes an output changes, its chain not.
+    int32_t lane = threadIdx.x, grp = 0, n_grp = 1;
+    uint32_t lanes = 0;
+    if constexpr (S::kSplitPeriods) {
+        const int32_t nph = pb - pa;
+        if (nph < (int32_t)blockDim.x) {
+            n_grp = (int32_t)blockDim.x / nph;
+            grp = (int32_t)threadIdx.x / nph;
+            lane = grp < n_grp ? (int32_t)threadIdx.x % nph : nph;   // the blockDim % nph lanes left over idle
+            lanes = (uint32_t)nph;
+        } else {
+            lanes = blockDim.x;
+        }
+    }
+    for (int32_t p = pa + lane; p < pb; p += S::kSplitPeriods ? lanes : blockDim.x) {
         float h[T];
 #pragma unroll
         for (int j = 0; j < T; ++j) h[j] = taps[(size_t)j * L + p];
         const int32_t base = (int32_t)((int64_t)p * M / L - off_a);
-        int64_t P = P0;
+        int64_t P = P0 + 4 * grp;
         // four periods at a time (independent chains), then the rest; the per-output chain is the same either way
-        for (; P + 4 <= P1; P += 4) {
+        for (; P + 4 <= P1; P += 4 * n_grp) {
             const float2* x0 = xs + (int32_t)(P - P0) * M + base;
             float re[4] = {0.f, 0.f, 0.f, 0.f}, im[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll

@@ -225,6 +225,42 @@ class GypsumEngine:
             d_out.free()
         return out if w.ndim > 1 else out[0]
 
+    def ddc_iq_dev(self, fmt: int, raw_ptr: int, n_streams: int, in_stride: int, raw_first_sample: int, raw_n_samples: int,
+                   scale: float, fs_in: int, if_hz: int, taps: int, first_ms: int, n_ms: int, out_stride: int, out_ptr: int) -> None:
+        """gyp_ddc_iq_dev: as resample_iq_dev for real words at an IF of if_hz (strides in real samples; raw sample 0 is input
+        sample raw_first_sample, which is also the mixer's index).  Enqueued, not synchronised."""
+        self._check(self.lib.gyp_ddc_iq_dev(self.ctx, int(fmt), C.c_void_p(raw_ptr), int(n_streams), int(in_stride),
+                                            int(raw_first_sample), int(raw_n_samples), float(scale), int(fs_in), int(if_hz), int(taps),
+                                            int(first_ms), int(n_ms), int(out_stride), C.c_void_p(out_ptr)))
+
+    def ddc(self, words: np.ndarray, fmt, fs_in: int, if_hz: int, first_ms: int = 0, n_ms: Optional[int] = None, scale: float = 1.0,
+            taps: int = 0) -> np.ndarray:
+        """Host convenience: real `words` of a recording at fs_in with its band at if_hz (int8 / uint8 / int16 / float32; 2-D = one
+        stream per row) -> complex64 baseband output milliseconds first_ms .. first_ms+n_ms-1 at the stream format's rate (default:
+        every output millisecond whose first sample lies within the recording).  `fmt` is a GYP_FMT_* code or the words' dtype."""
+        from .ingest import _FORMATS
+        if self.n is None:
+            raise RuntimeError("set_stream_format first")
+        w = np.ascontiguousarray(words)
+        code = _FORMATS[np.dtype(fmt)] if not isinstance(fmt, (int, np.integer)) else int(fmt)
+        if _FORMATS.get(w.dtype) != code:
+            raise ValueError(f"words are {w.dtype}, format {code} expects another word type")
+        rows = w.reshape(-1, w.shape[-1]) if w.ndim > 1 else w.reshape(1, -1)
+        n_streams, n_samples = rows.shape
+        n_in = int(fs_in) // 1000
+        if n_ms is None:
+            n_ms = max(0, -(-n_samples // n_in) - int(first_ms))
+        out = np.empty((n_streams, n_ms * self.n), dtype=np.complex64)
+        if n_ms:
+            d_raw = self.alloc(max(1, rows.nbytes)).upload(rows)
+            d_out = self.alloc(out.nbytes)
+            self.ddc_iq_dev(code, d_raw.ptr.value, n_streams, n_samples, 0, n_samples, scale, fs_in, if_hz, taps, first_ms, n_ms,
+                            n_ms * self.n, d_out.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d_out.ptr, out.nbytes))
+            d_raw.free()
+            d_out.free()
+        return out if w.ndim > 1 else out[0]
+
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(_lib.GYP_COMM_ID_BYTES)
         rc = self.lib.gyp_comm_unique_id(buf)

@@ -8,7 +8,8 @@ serve the reference's one-millisecond chunks without a file open per millisecond
 
 With `resample_from_hz` the recording is at that rate (any whole kHz within a factor 2 of the engine's) and the device blocks
 come out resampled to the engine's stream format (`gyp_ingest_open_resampled`, `gypsum_amd.resample`); `n` and `fs` are then
-the output rate and there are no host blocks.
+the output rate and there are no host blocks.  With `if_hz` as well the recording holds one real word per sample at an
+intermediate frequency of `if_hz` Hz and is down-converted to complex baseband on the device (`gyp_ingest_open_ddc`).
 """
 from __future__ import annotations
 
@@ -26,7 +27,8 @@ _FORMATS = {np.dtype(np.float32): _lib.GYP_FMT_F32, np.dtype(np.int8): _lib.GYP_
 
 class IqFileIngest:
     def __init__(self, path, samples_per_second: int, sample_component_data_type=np.float32, block_ms: int = 100,
-                 depth: int = 4, engine=None, resample_from_hz: Optional[int] = None, taps: int = 32) -> None:
+                 depth: int = 4, engine=None, resample_from_hz: Optional[int] = None, taps: Optional[int] = None,
+                 if_hz: Optional[int] = None) -> None:
         self.dtype = np.dtype(sample_component_data_type)
         if self.dtype not in _FORMATS:
             raise ValueError(f"unsupported sample component type {self.dtype} (float32, int8, int16, uint8)")
@@ -39,13 +41,20 @@ class IqFileIngest:
         self._h = C.c_void_p()
         ctx = engine.ctx if engine is not None else None
         self.resample_from_hz = None if resample_from_hz is None else int(resample_from_hz)
+        self.if_hz = None if if_hz is None else int(if_hz)
+        if self.if_hz is not None and self.resample_from_hz is None:
+            raise ValueError("if_hz needs resample_from_hz (the real recording's sample rate)")
         if self.resample_from_hz is not None:
             if engine is None:
                 raise ValueError("resampling runs on the device: pass an engine")
             if engine.fs is not None and engine.fs != self.fs:
                 raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({engine.fs})")
-            rc = self._lib.gyp_ingest_open_resampled(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.resample_from_hz,
-                                                     int(taps), self.block_ms, int(depth), C.byref(self._h))
+            if self.if_hz is not None:   # taps None: the down-converter's automatic choice
+                rc = self._lib.gyp_ingest_open_ddc(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.resample_from_hz, self.if_hz,
+                                                   int(taps or 0), self.block_ms, int(depth), C.byref(self._h))
+            else:
+                rc = self._lib.gyp_ingest_open_resampled(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.resample_from_hz,
+                                                         32 if taps is None else int(taps), self.block_ms, int(depth), C.byref(self._h))
         else:
             rc = self._lib.gyp_ingest_open(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.fs, self.n, self.block_ms,
                                            int(depth), C.byref(self._h))

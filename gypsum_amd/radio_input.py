@@ -28,6 +28,7 @@ class InputFileInfo:
     sdr_sample_rate: int
     utc_start_time: datetime.datetime
     sample_component_data_type: Type[np.number]
+    if_hz: Optional[int] = None   # not upstream: set for a real-sampled recording with its band at this intermediate frequency
 
     @classmethod
     def gnu_radio_recording(cls, path: Path, sample_rate: int, utc_start_time: datetime.datetime) -> "InputFileInfo":
@@ -71,6 +72,19 @@ class InputFileInfo:
             raise ValueError(f"unsupported sample component type {dt} (int16, int8, uint8, float32)")
         return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=int(sample_rate),
                    utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=dt.type)
+
+    @classmethod
+    def real_if(cls, path: Path, sample_rate: int, if_hz: int, dtype=np.int8,
+                utc_start_time: Optional[datetime.datetime] = None) -> "InputFileInfo":
+        """One real word of `dtype` (int8, int16, uint8 or float32) per sample at the whole-kHz `sample_rate`, the GPS band at the
+        intermediate frequency `if_hz` (negative for a spectrally inverted recording; not upstream).  Read through
+        `AntennaSampleProviderResampled`, which down-converts it on the device (gypsum_amd.resample.default_ddc_rate)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int16), np.dtype(np.int8), np.dtype(np.uint8), np.dtype(np.float32)):
+            raise ValueError(f"unsupported sample component type {dt} (int16, int8, uint8, float32)")
+        return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=int(sample_rate),
+                   utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=dt.type,
+                   if_hz=int(if_hz))
 
 
 INPUT_SOURCES: List[InputFileInfo] = []

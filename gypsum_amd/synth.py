@@ -146,20 +146,52 @@ def render_at_rate(scene: SyntheticScene, fs: int, block_ms: int = 50) -> np.nda
     rng = np.random.default_rng([scene.seed, fs])
     for b0 in range(0, scene.n_ms, block_ms):
         b1 = min(scene.n_ms, b0 + block_ms)
-        idx = np.arange(b0 * n, b1 * n, dtype=np.int64)
-        t = idx / fs
-        ms = idx // n                                          # receiver millisecond of each sample (exact)
-        acc = np.zeros((b1 - b0) * n, dtype=complex)
-        for s in scene.sats:
-            # chip index floor((t - tau) * 1.023e6) in exact integer arithmetic: (idx * scene.fs - cp * fs) * 1023 // (fs * scene.fs / 1000)
-            num = (idx * scene.fs - s.code_phase * fs) * 1023
-            chip = np.floor_divide(num, fs * (scene.fs // 1000)) % 1023
-            sig = s.amplitude * chips[s.sat_id - 1][chip] * np.exp(1j * (2 * np.pi * s.doppler_hz * t + s.carrier_phase))
-            if s.nav_bits is not None:
-                sig = sig * s.nav_bits[((ms + s.nav_bit_offset_ms) // 20) % len(s.nav_bits)].astype(np.float64)
-            acc += sig
+        acc = _signal_at_rate(scene, fs, chips, b0, b1)
         acc += scene.noise_sigma * (rng.standard_normal((b1 - b0) * n) + 1j * rng.standard_normal((b1 - b0) * n))
         out[b0 * n:b1 * n] = acc.astype(np.complex64)
+    return out
+
+
+def _signal_at_rate(scene: SyntheticScene, fs: int, chips: np.ndarray, b0: int, b1: int) -> np.ndarray:
+    """render_at_rate's noiseless model, complex128, for receiver milliseconds b0 .. b1-1 at rate fs."""
+    n = fs // 1000
+    idx = np.arange(b0 * n, b1 * n, dtype=np.int64)
+    t = idx / fs
+    ms = idx // n                                          # receiver millisecond of each sample (exact)
+    acc = np.zeros((b1 - b0) * n, dtype=complex)
+    for s in scene.sats:
+        # chip index floor((t - tau) * 1.023e6) in exact integer arithmetic: (idx * scene.fs - cp * fs) * 1023 // (fs * scene.fs / 1000)
+        num = (idx * scene.fs - s.code_phase * fs) * 1023
+        chip = np.floor_divide(num, fs * (scene.fs // 1000)) % 1023
+        sig = s.amplitude * chips[s.sat_id - 1][chip] * np.exp(1j * (2 * np.pi * s.doppler_hz * t + s.carrier_phase))
+        if s.nav_bits is not None:
+            sig = sig * s.nav_bits[((ms + s.nav_bit_offset_ms) // 20) % len(s.nav_bits)].astype(np.float64)
+        acc += sig
+    return acc
+
+
+def render_real_if(scene: SyntheticScene, fs: int, if_hz: int, block_ms: int = 50) -> np.ndarray:
+    """The real recording of a front end with its band at `if_hz` (signed, whole Hz), sampled at `fs`: float64[n_ms * fs / 1000].
+
+    The signal is 2 Re{s(t) exp(j 2 pi if_hz t)}, s being render_at_rate's noiseless model at fs (the IF carrier's phase reduced
+    exactly, ((if_hz * n) mod fs) / fs turns at sample n), so a negative if_hz gives the inverted spectrum with no special case.  The
+    noise is real white Gaussian with sigma sqrt(2) * scene.noise_sigma: down-converted (gain 1/2 on the signal and on the noise's
+    power spectral density), the stream has the C/N0 of render_at_rate(scene, fs)."""
+    fs, if_hz = int(fs), int(if_hz)
+    if fs % 1000:
+        raise ValueError("fs must be a whole number of kHz")
+    n = fs // 1000
+    chips = generate_ca_code_table().astype(np.float64) * 2 - 1
+    out = np.empty(scene.n_ms * n, dtype=np.float64)
+    rng = np.random.default_rng([scene.seed, fs, 1])
+    f = if_hz % fs
+    for b0 in range(0, scene.n_ms, block_ms):
+        b1 = min(scene.n_ms, b0 + block_ms)
+        idx = np.arange(b0 * n, b1 * n, dtype=np.int64)
+        turns = ((idx % fs) * f % fs).astype(np.float64) / fs
+        acc = 2.0 * (_signal_at_rate(scene, fs, chips, b0, b1) * np.exp(2j * np.pi * turns)).real
+        acc += np.sqrt(2.0) * scene.noise_sigma * rng.standard_normal((b1 - b0) * n)
+        out[b0 * n:b1 * n] = acc
     return out
 
 

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 204: on-device resampler for recordings at any whole-kHz rate: gyp_resample_design, gyp_resample_iq_dev, gyp_ingest_open_resampled;
+/* 205: digital down-converter for real-sampled recordings at an intermediate frequency: gyp_ddc_design, gyp_ddc_iq_dev,
+ *      gyp_ingest_open_ddc.  Nothing that existed changes.
+ * 204: on-device resampler for recordings at any whole-kHz rate: gyp_resample_design, gyp_resample_iq_dev, gyp_ingest_open_resampled;
  *      gyp_debug_set name resample_tile_samples.  Nothing that existed changes.
  * 203: gyp_debug_spec_layout_for added (sub-block length by rate: ~167 ms at 2.046 Msps, r06), gyp_grid_best_bins_refined_dev added (float64
  *      tie-break of the flat grids' best-bin selection); new gyp_debug_set names (no_grid_fused, grid_fused_waves, spec_sub_ms,
@@ -38,7 +40,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 204 /* 0.2.4 */
+#define GYP_VERSION 205 /* 0.2.5 */
 
 enum {
     GYP_OK = 0,
@@ -561,6 +563,53 @@ int gyp_resample_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t 
  * gyp_ingest_next_host returns GYP_E_BAD_ARG. */
 int gyp_ingest_open_resampled(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int32_t taps, int32_t block_ms,
                               int32_t depth, gyp_ingest** out);
+
+/* ---------------------------------------------------------------- down-converter ----------------------- */
+/* Real-sampled recordings at an intermediate frequency (MAX2769-style front ends: 16.368 Msps, IF 4.092 MHz; the classic int8
+ * data set: 38.192 Msps, IF 9.548 MHz) become complex baseband at the context's format on the device: a mixer in front of the
+ * resampler's filter.
+ *
+ * Contract.  The input is one real word per sample, of format fmt (GYP_FMT_*): x[i] = word[i] * scale, integer formats widened
+ * as the ingest does; x is zero at indices below 0 and at or beyond the last sample of the buffer or file.  fs_in = N_in * 1000
+ * Hz; fs_out = N_out * 1000 Hz is the context's stream format (GYP_E_NO_FORMAT if none is set) or, for gyp_ddc_design, the
+ * argument.  if_hz is a signed whole number of Hz.
+ *     z[i] = x[i] * exp(-j theta_i),   theta_i = 2 pi ((if_hz * i) mod fs_in) / fs_in
+ * with i the absolute input index (from sample 0 of the file or buffer) and the reduction exact integer arithmetic, so windows,
+ * blocks and seeks see the same mixer value at the same i, whatever i (2^43 included).  The device evaluates each mixer value in
+ * float32 within 2^-22 of the exact one.  Output sample r of millisecond m is
+ *     y = sum_{j = -T/2+1 .. T/2} h_mu[j] * z[i0 + j]
+ * with i0, mu, h_mu and the tap range exactly the resampler's (fc = 0.9 * fs_out / fs_in, since fs_out < fs_in here).  There is
+ * no factor 2: a real tone A cos(2 pi (if_hz + d) t + phi) comes out as (A/2) exp(j (2 pi d t + phi)).  A negative if_hz selects
+ * the mirrored band: that is how a spectrally inverted (high-side LO) recording is read, a satellite at Doppler +d coming out at +d.
+ * Rates, checked in integers, else GYP_E_BAD_RATE: both whole kHz, fs_in < 2^31 Hz, 8 fs_out >= fs_in, 20 |if_hz| >= 9 fs_out
+ * (the mirror band at -2 if_hz clears the +-0.45 fs_out passband) and 20 |if_hz| + 9 fs_out <= 10 fs_in (the band lies below the
+ * real Nyquist frequency); together fs_out / fs_in <= 5/9, and if_hz = 0 is refused.  Admitted, e.g.: 16.368 Msps at IF
+ * +-4.092 MHz to 4.092 and 8.184 Msps; 38.192 Msps at IF 9.548 MHz to 8.184 and 16.368 Msps; 5 Msps at IF 1.25 MHz to 2.046 Msps.
+ * Taps T is 32, 48, 64, 96 or 128, else GYP_E_BAD_ARG; T = 0 picks the smallest with T * fs_out >= 16 * fs_in (the filter spans at
+ * least 16 output samples; the ratio bound 1/8 makes 128 always enough): 64 at 16.368 -> 4.092, 96 at 38.192 -> 8.184.
+ * Passband by the number of output samples the filter spans, T * fs_out / fs_in (float64 model: a real tone at if_hz + d with
+ * |d| <= B * fs_out comes out within 2e-4 of A/2, its mirror included; measured at ratios 1/8, 1/4 and 1/2):
+ *        T * ratio      6     8    12    16    24    32
+ *        B           0.02  0.12  0.23  0.29  0.34  0.37
+ * (below 0.01 at T * ratio = 4, which T = 32 gives at the ratio bound 1/8; T = 0 always spans 16 or more.)
+ * Each output is one float32 fma chain in tap order over mixed inputs that depend on i alone: blocks, windows,
+ * seeks and launch shapes give bit-identical samples. */
+
+/* Host only (no GPU): validates the rules above and writes the L x T float32 design in the resampler's layout (row p = mu * L),
+ * computed in float64 and rounded; *taps_out receives the T that 0 resolves to.  Any of the outputs may be NULL. */
+int gyp_ddc_design(int64_t fs_in_hz, int64_t fs_out_hz, int64_t if_hz, int32_t taps, float* table_out, int32_t* n_phases_out,
+                   int32_t* taps_out);
+/* As gyp_resample_iq_dev, with one real word per sample: strides count real samples, and raw_first_sample is the absolute index
+ * the mixer phase uses.  The design is cached on the context next to the resampler's. */
+int gyp_ddc_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_streams, int64_t in_stride_samples, int64_t raw_first_sample,
+                   int64_t raw_n_samples, float scale, int64_t fs_in_hz, int64_t if_hz, int32_t taps, int64_t first_ms, int32_t n_ms,
+                   int64_t out_stride_samples, float* out_dev);
+/* An ingest handle over a real recording at fs_in_hz whose device blocks are complex baseband at the context's rate (ctx required).
+ * The input millisecond is N_in * word bytes; the halo is T-1 samples and the mixer index of each staged sample is its absolute
+ * index in the file.  total_ms, times, set_scale, seek, next_dev and close behave as for a resampled handle; gyp_ingest_next_host
+ * returns GYP_E_BAD_ARG. */
+int gyp_ingest_open_ddc(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int64_t if_hz, int32_t taps, int32_t block_ms,
+                        int32_t depth, gyp_ingest** out);
 
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
