@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GPS L1 C/A correlator hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--track-ms T] [--workload cfg3|cfg2|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--track-ms T] [--workload cfg3|cfg2|cfg4|cfg5] [--full]
 
 Metric (BASELINE.json): IQ Msamples/s (and x real-time) for 32-satellite acquisition + tracking.
 
@@ -18,7 +18,8 @@ Workload cfg3 (default; BASELINE.json configs[2], the configuration the >= 200x 
   step, ncclAllGather over RCCL issued by the library on its own stream (gyp_allgather_dev), no host synchronisation.
 `value` is the batched figure with the IQ resident in HBM and -- from r05 on -- every step's per-ms records copied to page-locked host
 memory inside the timed region (gyp_memcpy_d2h_async on a copy stream; --no-records-d2h leaves them in HBM).  stdout carries ONE compact JSON
-line (keys: profiles/BENCH_NOTES.md); the full record goes to --detail-out.  On one GPU the line's `legs` also carry
+line (keys: profiles/BENCH_NOTES.md); the full record goes to --detail-out.  A plain run stops there: it sets up, warms up, times the
+steps, writes --dump-outputs and prints the line.  Everything below is measured with --full only.  On one GPU the line's `legs` then carry
   s8184 / s2046 / s16368        the STRICT configs[2] at the reference's three recording rates: ONE stream, one 32-satellite scan per 10 s of
                                 signal (on a second HIP stream, beside the tracking) + 12-channel tracking, per-ms records copied to the host,
                                 in steps of 10 s of signal; *_lock: the same on scenes in which the channels LOCK (lock_regime_amplitudes);
@@ -33,7 +34,7 @@ Workload cfg4 (configs[3]): the cfg2 grid on 64 concurrent streams in total, str
 Workload cfg5 (configs[4]): 49.104 Msps, 32 satellites x range(-10000, 10000, 100) Hz, 10 ms coherent; the Doppler axis
   (x 32 satellites = 6400 cells) is sharded over the ranks (strong scaling), one all-gather of the cell records.
 
-`roofline` names the BINDING resource (`bound: fp32_valu`: FP32 vector issue) and carries the HBM view
+--full: `roofline` names the BINDING resource (`bound: fp32_valu`: FP32 vector issue) and carries the HBM view
 north_star asks for in the same dict (`hbm_frac`, `hbm_achieved_gbps`, `traffic`); `cpu_baseline` is the numpy oracle -- the reference's
 algorithm -- timed on this box's host cores on a bounded sample, with `port_over_reference` from tools/calibrate_port.py.
 """
@@ -543,7 +544,23 @@ def run_cfg3(eng, comm, args, rng, eng_scan=None) -> dict:
         outputs = {"acquisition": acq_recv.download(ACQ_RESULT, comm.world * A * 32).reshape(comm.world * A, 32)}
         if su.rec_devs:
             outputs["tracking"] = su.records(slot=args.warmup + args.steps - 1).reshape(B * C_, T)
-    # the same steps again, untimed, with rocm-smi polled beside them: shader clock and power UNDER this load without a fork / exec
+    base = {
+        "_outputs": outputs,
+        "workload_name": "cfg3",
+        "config": {"workload": f"cfg3 {fs / 1e6:.3f}Msps x{B} streams/GPU: 32-sat acquire ({A} scans/step) + 12-ch E-P-L track {T}ms/step",
+                   "iq": "resident in HBM (host-fed: legs.h2d)", "records_d2h_in_timed_region": bool(d2h),
+                   "sample_rate_hz": fs, "streams_per_gpu": B, "tracking_channels_per_stream": C_,
+                   "track_ms_per_step": T, "acquisitions_per_step": A, "satellites_searched": 32,
+                   "scene": "SURVEY d2: a*N=41, sigma=6a (lock unreachable; lock-regime legs: *_lock)",
+                   "parallelism": f"streams sharded over {comm.world} GPU(s), one ncclAllGather/step (gyp_allgather_dev)"},
+        "samples_per_step": B * T * n, "elapsed": elapsed, "fs": fs, "streams_total": B * comm.world,
+    }
+    if not args.full:
+        if eng_copy is not None:
+            su.free_host()
+            eng_copy.close()
+        return base
+    # --full: the same steps again, untimed, with rocm-smi polled beside them: shader clock and power UNDER this load without a fork / exec
     # every half second inside the metric; and a short pair with / without the D2H of the records
     n_tele = 0 if args.no_telemetry else max(2, int(math.ceil(2.5 / max(1e-3, comm.max(elapsed) / args.steps))))   # ~2.5 s, the same count on every rank
     with GpuTelemetry(eng.device, enabled=comm.rank == 0 and not args.no_telemetry) as tele:      # (only rank 0 polls)
@@ -628,15 +645,7 @@ def run_cfg3(eng, comm, args, rng, eng_scan=None) -> dict:
         eng_copy.close()
     f_trk = C_ * (2 * fft_flops(n) + 18 * n)                          # SURVEY 8(d5), per stream-ms
     return {
-        "_su": su, "_outputs": outputs,
-        "workload_name": "cfg3",
-        "config": {"workload": f"cfg3 {fs / 1e6:.3f}Msps x{B} streams/GPU: 32-sat acquire ({A} scans/step) + 12-ch E-P-L track {T}ms/step",
-                   "iq": "resident in HBM (host-fed: legs.h2d)", "records_d2h_in_timed_region": bool(d2h),
-                   "sample_rate_hz": fs, "streams_per_gpu": B, "tracking_channels_per_stream": C_,
-                   "track_ms_per_step": T, "acquisitions_per_step": A, "satellites_searched": 32,
-                   "scene": "SURVEY d2: a*N=41, sigma=6a (lock unreachable; lock-regime legs: *_lock)",
-                   "parallelism": f"streams sharded over {comm.world} GPU(s), one ncclAllGather/step (gyp_allgather_dev)"},
-        "samples_per_step": B * T * n, "elapsed": elapsed, "fs": fs, "streams_total": B * comm.world,
+        "_su": su, **base,
         "telemetry": tele.summary(), "per_rank_acq_sha": acq_sha,
         "allgather": {"bytes_per_rank": acq_bytes, "ms_median_of_5": round(statistics.median(ag_ms), 4), "ms_first": round(ag_ms[0], 4),
                       "how": "hipEvents on the library's stream around gyp_allgather_dev alone, after a barrier, outside the timed region"},
@@ -943,6 +952,21 @@ def run_grid(eng, comm, args, rng, workload: str, steps: int, warmup: int) -> di
     if args.dump_outputs:
         outputs = {"cells": out_dev.download(CELL, n_cells).reshape(n_units, 32, len(bins))} if recv is None else \
                   {"best_bins": gathered(recv.download(BEST_BIN, comm.world * pad_rows))}
+    base = {
+        "workload_name": workload, "scaling": "strong" if workload == "cfg4" else "weak",
+        "config": {"workload": f"{workload}: synthetic IQ {fs / 1e6:.3f} Msps, 32 sats x range(-5000,5000,500) Hz x 1 ms "
+                               f"non-coherent grid, {B} streams x {T} ms per step",
+                   "sample_rate_hz": fs, "streams_per_gpu": B, "grid_ms_per_step": T,
+                   "parallelism": f"stream-ms sharded over {comm.world} GPU(s)" +
+                                  (", best bin per (stream-ms, satellite) on the device + one ncclAllGather" if workload == "cfg4" else "")},
+        "samples_per_step": B * T * n, "elapsed": elapsed, "fs": fs, "streams_total": 64 if workload == "cfg4" else B * comm.world,
+        "total_samples_override": 64 * T * n * steps if workload == "cfg4" else None,
+        "_outputs": outputs,
+    }
+    if not args.full:
+        # (--dump-table: the last timed step's gathered table -- the timing launch of --full below recomputes the same one)
+        table = gathered(recv.download(BEST_BIN, comm.world * pad_rows)) if recv is not None and args.dump_table else None
+        return {**base, "_table": table}
     eng.timer_start(); step(0); k_ms = eng.timer_stop()
     out = out_dev.download(CELL, n_cells).reshape(n_units, 32, len(bins))
     hits = 0
@@ -964,17 +988,10 @@ def run_grid(eng, comm, args, rng, workload: str, steps: int, warmup: int) -> di
         extra["gathered_table_rows"] = int(len(table))
     flops = n_units * (len(bins) * (6 * n + fft_flops(n)) + 32 * len(bins) * (6 * n + fft_flops(n) + 5 * n))
     return {
-        "workload_name": workload, "scaling": "strong" if workload == "cfg4" else "weak",
-        "config": {"workload": f"{workload}: synthetic IQ {fs / 1e6:.3f} Msps, 32 sats x range(-5000,5000,500) Hz x 1 ms "
-                               f"non-coherent grid, {B} streams x {T} ms per step",
-                   "sample_rate_hz": fs, "streams_per_gpu": B, "grid_ms_per_step": T,
-                   "parallelism": f"stream-ms sharded over {comm.world} GPU(s)" +
-                                  (", best bin per (stream-ms, satellite) on the device + one ncclAllGather" if workload == "cfg4" else "")},
-        "samples_per_step": B * T * n, "elapsed": elapsed, "fs": fs, "streams_total": 64 if workload == "cfg4" else B * comm.world,
-        "total_samples_override": 64 * T * n * steps if workload == "cfg4" else None,
+        **base,
         "dominant": {"kernel": "grid_cells_wave_fused_kernel<2, false>", "ms": k_ms, "flops": flops,
                      "bytes": (8 * n + 32 * 32 * len(bins)) * n_units},
-        "extra": extra, "_sample": sample, "_table": table if recv is not None else None, "_outputs": outputs,
+        "extra": extra, "_sample": sample, "_table": table if recv is not None else None,
     }
 
 
@@ -1000,6 +1017,26 @@ def run_cfg5(eng, comm, args, steps: int, warmup: int) -> dict:
         comm.allgather(send, recv, pad * CELL.itemsize)
 
     elapsed = timed_steps(eng, comm, step, warmup, steps)
+
+    def gathered_table():
+        # the whole grid as rank 0 holds it after the last step's all-gather: rank r's [stream][sat][its bins] block, padding trimmed,
+        # bins back in order
+        flat = recv.download(CELL, comm.world * pad)
+        return np.concatenate([flat[r * pad:r * pad + n_streams * 32 * (b - a)].reshape(n_streams, 32, b - a)
+                               for r, (a, b) in enumerate(shard_bounds(len(bins), r_, comm.world) for r_ in range(comm.world))], axis=2)
+
+    n_total = n_streams * 32 * len(bins)
+    base = {
+        "workload_name": "cfg5", "scaling": "strong", "divide_by_world": True,
+        "config": {"workload": f"cfg5: synthetic IQ {fs / 1e6:.3f} Msps, {n_streams} stream(s), 32 sats x "
+                               f"range(-10000,10000,100) Hz x 10 ms coherent = {n_total} cells",
+                   "sample_rate_hz": fs, "streams_total": n_streams, "cells_total": int(n_total),
+                   "parallelism": f"Doppler bins (x 32 satellites) sharded over {comm.world} GPU(s), one ncclAllGather of cell records"},
+        "samples_per_step": n_streams * n_ms * n, "elapsed": elapsed, "fs": fs, "streams_total": n_streams,
+    }
+    if not args.full:
+        table = gathered_table() if args.dump_outputs or args.dump_table else None
+        return {**base, "_table": table, "_outputs": {"cells": table} if args.dump_outputs else None}
     eng.timer_start()
     eng.correlate_grid_dev(iq.ptr.value, n_streams, n_ms * n, n_ms, ALL_IDS, my_bins, 0, send.ptr.value)
     k_ms = eng.timer_stop()
@@ -1015,20 +1052,11 @@ def run_cfg5(eng, comm, args, steps: int, warmup: int) -> dict:
             rows.append((int(sat["sat_id"]), b))
     sample = {"fs": fs, "n": n, "n_ms": n_ms, "coherent": True, "bins": my_bins, "cells": got[0].copy(), "iq": iq.download(np.complex64, n_ms * n),
               "rows": rows}
-    n_total = n_streams * 32 * len(bins)
-    # the whole grid as rank 0 holds it after the all-gather: rank r's [stream][sat][its bins] block, padding trimmed, bins back in order
-    flat = recv.download(CELL, comm.world * pad)
-    table = np.concatenate([flat[r * pad:r * pad + n_streams * 32 * (b - a)].reshape(n_streams, 32, b - a)
-                            for r, (a, b) in enumerate(shard_bounds(len(bins), r_, comm.world) for r_ in range(comm.world))], axis=2)
+    table = gathered_table()
     return {
         "_table": table,
         "_outputs": {"cells": table} if args.dump_outputs else None,    # (the timing launch above writes `send` only: recv is the last step's)
-        "workload_name": "cfg5", "scaling": "strong", "divide_by_world": True,
-        "config": {"workload": f"cfg5: synthetic IQ {fs / 1e6:.3f} Msps, {n_streams} stream(s), 32 sats x "
-                               f"range(-10000,10000,100) Hz x 10 ms coherent = {n_total} cells",
-                   "sample_rate_hz": fs, "streams_total": n_streams, "cells_total": int(n_total),
-                   "parallelism": f"Doppler bins (x 32 satellites) sharded over {comm.world} GPU(s), one ncclAllGather of cell records"},
-        "samples_per_step": n_streams * n_ms * n, "elapsed": elapsed, "fs": fs, "streams_total": n_streams,
+        **base,
         "dominant": {"kernel": "grid_wipe_kernel<48, true> + grid_boxcar_kernel<48> + grid_cells_wave_shared_kernel<48, 8> + grid_merge_parts_kernel", "ms": k_ms,
                      # SURVEY section 8 d5 with the coherent pre-fold: the wipe-off is per (stream, bin, ms), the forward transform per
                      # (stream, bin) -- shared by the 32 satellites -- and per cell one spectrum product, one inverse transform and the
@@ -1120,7 +1148,8 @@ def compact_line(d: dict) -> dict:
         if k in d:
             c[k] = d[k]
     c["x_realtime_aggregate"], c["x_realtime_per_stream"] = d["x_realtime_aggregate"], d["x_realtime_per_stream"]
-    c["roofline"] = {k: v for k, v in d["roofline"].items() if k not in ("unit_per_launch", "algorithmic_flop_per_launch")}
+    if "roofline" in d:          # (--full)
+        c["roofline"] = {k: v for k, v in d["roofline"].items() if k not in ("unit_per_launch", "algorithmic_flop_per_launch")}
     cb = d.get("cpu_baseline")
     if cb:
         c["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "x_realtime", "port_over_reference", "acq_s_per_sat",
@@ -1258,6 +1287,11 @@ def main() -> None:
     ap.add_argument("--streams", type=int, default=128, help="IQ streams per GPU")
     ap.add_argument("--track-ms", type=int, default=1000, help="ms of signal per stream per step (cfg3)")
     ap.add_argument("--grid-ms", type=int, default=64, help="ms of signal per stream per step (cfg2)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline: the workload's per-kernel times, roofline, telemetry and record "
+                         "checks, the CPU baselines with their parity samples and (cfg3 on one GPU) the extra legs.  Without it a run sets "
+                         "up, warms up, times the steps, writes --dump-outputs / --dump-table and prints the line.  --no-cpu-baseline, "
+                         "--no-telemetry, --no-extras and --only-legs trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-records", action="store_true", help="do not write per-ms tracking records")
     ap.add_argument("--no-records-d2h", action="store_true", help="leave the per-ms records in HBM (r01-r04's timed region) instead of copying every "
@@ -1324,7 +1358,7 @@ def main() -> None:
 
     extras = {}
     solo = rank == 0 and world == 1
-    with_extras = solo and args.workload == "cfg3" and not args.no_extras
+    with_extras = solo and args.workload == "cfg3" and args.full and not args.no_extras
     eng2 = GypsumEngine(device) if with_extras else None
 
     def run_legs(legs) -> None:
@@ -1394,7 +1428,7 @@ def main() -> None:
         except Exception as e:
             extras["other_configs"] = {"error": repr(e)}
         eng2.close()
-    if solo and not args.no_cpu_baseline:
+    if solo and args.full and not args.no_cpu_baseline:
         if args.workload == "cfg3":
             result["cpu_baseline"] = cpu_baseline_cfg3(8_184_000, 8184, getattr(result.get("_su"), "sample", None))
             try:
@@ -1412,36 +1446,37 @@ def main() -> None:
         dump_outputs(args.dump_outputs, result["_outputs"])
     # ---- max over ranks, one JSON line from rank 0
     per_rank_s = comm.gather_floats(result["elapsed"])
-    per_rank_kernel_ms = comm.gather_floats(result["dominant"]["ms"])
+    per_rank_kernel_ms = comm.gather_floats(result["dominant"]["ms"]) if args.full else None
     elapsed = comm.max(result["elapsed"])
     if rank == 0:
         total_samples = result.get("total_samples_override") or \
             result["samples_per_step"] * args.steps * (1 if result.get("divide_by_world") else world)
         value = total_samples / elapsed / 1e6
-        dom = result["dominant"]
-        traffic, traffic_rec = measured_traffic(result["workload_name"])
-        hbm_gbps = dom["bytes"] / (dom["ms"] * 1e-3) / 1e9
-        valu_tf = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
-        extra = result["extra"]
-        k_ms = extra.get("track_kernels_ms_per_step", {})
-        k_vals = [v for v in k_ms.values() if isinstance(v, (int, float))]
-        # `roofline` names the BINDING resource (FP32 vector issue, not HBM, not MFMA) and carries the HBM view
-        # north_star asks for inside the same dict (the driver's record keeps this dict whole)
-        traffic_stale = ((bool(traffic_rec.get("kernel_ms_during_counter_pass")) and
-                          abs(traffic_rec["kernel_ms_during_counter_pass"] / dom["ms"] - 1.0) > 0.15) if traffic_rec else None)
-        roofline = {"bound": "fp32_valu", "kernel": dom["kernel"], "achieved": round(valu_tf, 3), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(valu_tf / VALU_PEAK_TFLOPS, 5),
-                    "valu_frac": round(valu_tf / VALU_PEAK_TFLOPS, 5), "valu_achieved_tflops": round(valu_tf, 3),
-                    "hbm_frac": round(hbm_gbps / HBM_PEAK_GBS, 5), "hbm_achieved_gbps": round(hbm_gbps, 2), "hbm_peak_gbps": HBM_PEAK_GBS,
-                    "algorithmic_flop_per_launch": dom["flops"], "algorithmic_bytes_per_launch": dom["bytes"],
-                    "traffic": traffic,
-                    # (no ratio if the counters were collected on launches of another length: r06zg's line divided 500-ms counters by 250-ms bytes)
-                    "traffic_over_algorithmic": round(traffic / dom["bytes"], 3) if traffic and not traffic_stale else None,
-                    "traffic_stale": traffic_stale,
-                    "kernel_ms_per_launch": round(dom["ms"], 4),
-                    **({"launches_per_step": dom["launches_per_step"], "unit_per_launch": dom["unit_per_launch"]}
-                       if "launches_per_step" in dom else {}),
-                    **({"kernel_ms_per_step": {"track_block": k_vals[0], "dll_exact": k_vals[1], "dll_scan": k_vals[2]}} if len(k_vals) >= 3 else {})}
+        if args.full:
+            dom = result["dominant"]
+            traffic, traffic_rec = measured_traffic(result["workload_name"])
+            hbm_gbps = dom["bytes"] / (dom["ms"] * 1e-3) / 1e9
+            valu_tf = dom["flops"] / (dom["ms"] * 1e-3) / 1e12
+            extra = result["extra"]
+            k_ms = extra.get("track_kernels_ms_per_step", {})
+            k_vals = [v for v in k_ms.values() if isinstance(v, (int, float))]
+            # `roofline` names the BINDING resource (FP32 vector issue, not HBM, not MFMA) and carries the HBM view
+            # north_star asks for inside the same dict (the driver's record keeps this dict whole)
+            traffic_stale = ((bool(traffic_rec.get("kernel_ms_during_counter_pass")) and
+                              abs(traffic_rec["kernel_ms_during_counter_pass"] / dom["ms"] - 1.0) > 0.15) if traffic_rec else None)
+            roofline = {"bound": "fp32_valu", "kernel": dom["kernel"], "achieved": round(valu_tf, 3), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(valu_tf / VALU_PEAK_TFLOPS, 5),
+                        "valu_frac": round(valu_tf / VALU_PEAK_TFLOPS, 5), "valu_achieved_tflops": round(valu_tf, 3),
+                        "hbm_frac": round(hbm_gbps / HBM_PEAK_GBS, 5), "hbm_achieved_gbps": round(hbm_gbps, 2), "hbm_peak_gbps": HBM_PEAK_GBS,
+                        "algorithmic_flop_per_launch": dom["flops"], "algorithmic_bytes_per_launch": dom["bytes"],
+                        "traffic": traffic,
+                        # (no ratio if the counters were collected on launches of another length: r06zg's line divided 500-ms counters by 250-ms bytes)
+                        "traffic_over_algorithmic": round(traffic / dom["bytes"], 3) if traffic and not traffic_stale else None,
+                        "traffic_stale": traffic_stale,
+                        "kernel_ms_per_launch": round(dom["ms"], 4),
+                        **({"launches_per_step": dom["launches_per_step"], "unit_per_launch": dom["unit_per_launch"]}
+                           if "launches_per_step" in dom else {}),
+                        **({"kernel_ms_per_step": {"track_block": k_vals[0], "dll_exact": k_vals[1], "dll_scan": k_vals[2]}} if len(k_vals) >= 3 else {})}
         detail = {
             "metric": "iq_msamples_per_s_32sat_acquire_plus_track" if result["workload_name"] == "cfg3" else "iq_msamples_per_s_32sat_acquisition_grid",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1451,11 +1486,12 @@ def main() -> None:
             "config": result["config"],
             "x_realtime_aggregate": round(value * 1e6 / result["fs"], 2),
             "x_realtime_per_stream": round(value * 1e6 / result["fs"] / max(1, result["streams_total"]), 3),
-            "roofline": roofline,
-            "roofline_notes": {"traffic_source": "profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload "
-                                                 "(tools/gpu_visit.sh pmc), counters corrected by the factors tools/fetch_calib.hip measured for "
-                                                 "this access pattern; not collected inside this run",
-                               "traffic_record": {k: traffic_rec.get(k) for k in ("commit", "kernel_ms_during_counter_pass", "fetch_factor", "write_factor")}},
+            **({"roofline": roofline,
+                "roofline_notes": {"traffic_source": "profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload "
+                                                     "(tools/gpu_visit.sh pmc), counters corrected by the factors tools/fetch_calib.hip measured "
+                                                     "for this access pattern; not collected inside this run",
+                                   "traffic_record": {k: traffic_rec.get(k) for k in ("commit", "kernel_ms_during_counter_pass", "fetch_factor",
+                                                                                     "write_factor")}}} if args.full else {}),
             "collective": {**eng.comm_info(), "ranks_launched": world, **({"fallback": comm.fallback} if comm.fallback else {}),
                            "device_ordinal_of_rank0": device, **({"device_map": dev_map} if dev_map else {}),
                            "rank0_gpu_locality": {**{k: v for k, v in eng.locality().items() if k != "cpus"}, "host_thread_bound_to_it": host_bound},
@@ -1464,10 +1500,9 @@ def main() -> None:
                            **({"allgather": result["allgather"]} if "allgather" in result else {})},
             "per_rank": {"ms_per_step": [round(t / args.steps * 1e3, 4) for t in per_rank_s],
                          "ms_per_step_min_max": [round(min(per_rank_s) / args.steps * 1e3, 4), round(max(per_rank_s) / args.steps * 1e3, 4)],
-                         "dominant_kernel_ms_per_launch": [round(t, 4) for t in per_rank_kernel_ms],
+                         **({"dominant_kernel_ms_per_launch": [round(t, 4) for t in per_rank_kernel_ms]} if args.full else {}),
                          **({"acquisition_records_sha16": result["per_rank_acq_sha"]} if "per_rank_acq_sha" in result else {})},
-            "gpu_telemetry_rank0": result.get("telemetry"),
-            **extra, **extras,
+            **({"gpu_telemetry_rank0": result.get("telemetry"), **result["extra"], **extras} if args.full else {}),
         }
         h2d = extras.get("h2d_inclusive")
         if isinstance(h2d, dict) and "float32" in h2d:

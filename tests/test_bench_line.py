@@ -69,3 +69,21 @@ def test_port_calibration_is_committed_and_read():
     assert cal is not None and 0.8 < cal < 1.3
     rec = json.loads((REPO / "profiles" / "r05_port_calibration.json").read_text())
     assert rec["rates"]["8184000"]["track_ms_per_channel_ms"]["reference"] > 0
+
+
+def test_compact_line_of_a_plain_run_carries_the_contract_and_nothing_measured_beside_it():
+    """Without --full the record holds the headline and its description only: compact_line passes it through without a roofline, CPU
+    baseline or legs to report."""
+    import bench
+
+    d = _detail()
+    plain = {k: d[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                               "dtype", "data", "config", "x_realtime_aggregate", "x_realtime_per_stream", "collective", "per_rank")}
+    line = bench.compact_line(plain)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data"):
+        assert line[k] == plain[k], k
+    assert line["config"]["workload"] == plain["config"]["workload"][:118]
+    assert line["cpu_baseline"] is None
+    for k in ("roofline", "legs", "step_ms", "records_d2h", "gpu", "cpu_all_cores", "value_h2d_inclusive"):
+        assert k not in line, k

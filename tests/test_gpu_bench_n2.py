@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = Path(__file__).resolve().parents[1]
-ARGS = ["--streams", "32", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-telemetry"]
+ARGS = ["--streams", "32", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-telemetry"]
 
 
 def _bench(args, env_extra=None, timeout=600, tmp=None):
@@ -55,7 +55,7 @@ def test_two_ranks_on_one_gpu_assemble_the_n2_line(tmp_path):
     assert line["roofline"]["bound"] == "fp32_valu" and 0.05 < line["roofline"]["frac"] < 0.5
 
 
-GRID_ARGS = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-telemetry"]
+GRID_ARGS = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-telemetry"]
 
 
 def _tables(workload, extra_args, tmp_path):
@@ -110,7 +110,7 @@ def test_real_two_rank_ncclAllGather_on_one_device(tmp_path):
     """Two ranks on device 0 WITHOUT --allow-host-gather.  Where RCCL builds a two-rank communicator on one device, the step's all-gather is
     a real ncclAllGather and the record says so.  Where it refuses (ncclCommInitRank "invalid usage": a duplicate GPU), bench.py must fail
     loudly -- a non-zero exit that names the refused communicator, no result line, no record -- and never measure a host-gathered figure."""
-    r, d = _bench(["--gpus", "2", "--streams", "16", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline", "--no-telemetry"],
+    r, d = _bench(["--gpus", "2", "--streams", "16", "--steps", "1", "--warmup", "0", "--full", "--no-extras", "--no-cpu-baseline", "--no-telemetry"],
                   env_extra={"GYP_BENCH_DEVICE_MAP": "0,0"}, timeout=240, tmp=tmp_path)
     if r.returncode == 0:
         full = json.loads(d.read_text())

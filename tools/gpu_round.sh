@@ -13,7 +13,7 @@ if [ "${2:-}" != "notests" ]; then
   echo "pytest rc=$?" >> $O/pytest_gpu.log
   tail -3 $O/pytest_gpu.log
 fi
-timeout 600 python bench.py > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout 600 python bench.py --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 echo "bench rc=$?"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_cfg3 -o bench -- python bench.py --no-cpu-baseline --no-extras > $O/kt_cfg3.log 2>&1
 rm -f $O/*/bench_kernel_trace.csv $O/*/bench_agent_info.csv

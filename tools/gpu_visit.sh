@@ -23,7 +23,7 @@ for step in "$@"; do
     abexact)
       for v in 0 1 2 3; do
         echo "== exact_prefetch $v"
-        GYP_EXACT_PREFETCH=$v timeout 300 python bench.py --no-cpu-baseline --no-extras --steps 4 --warmup 1 2>/dev/null | python -c "
+        GYP_EXACT_PREFETCH=$v timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 4 --warmup 1 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print({k:l[k] for k in ('value','ms_per_step','acquire_ms_per_step','track_ms_per_step')}, l['track_kernels_ms_per_step'])"
       done ;;
@@ -34,9 +34,9 @@ l=json.loads(sys.stdin.read()); print({k:l[k] for k in ('value','ms_per_step','a
       timeout ${TESTS_TIMEOUT:-720} python -m pytest tests -m gpu -x -q -s > $O/pytest_gpu.log 2>&1
       echo "pytest rc=$?" >> $O/pytest_gpu.log; grep -v "^$" $O/pytest_gpu.log | tail -40 ;;
     bench)
-      timeout 900 python bench.py > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "bench rc=$?"; head -c 7000 $O/bench_cfg3.json; echo ;;
+      timeout 900 python bench.py --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "bench rc=$?"; head -c 7000 $O/bench_cfg3.json; echo ;;
     benchfast)
-      timeout 600 python bench.py --no-cpu-baseline --no-extras > $O/bench_fast.json 2> $O/bench_fast.err; echo "benchfast rc=$?"; head -c 4000 $O/bench_fast.json; echo ;;
+      timeout 600 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_fast.json 2> $O/bench_fast.err; echo "benchfast rc=$?"; head -c 4000 $O/bench_fast.json; echo ;;
     kt)
       timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_cfg3 -o bench -- python bench.py --no-cpu-baseline --no-extras --no-telemetry > $O/kt_cfg3.log 2>&1
       rm -f $O/kt_cfg3/bench_kernel_trace.csv $O/kt_cfg3/*/bench_kernel_trace.csv $O/kt_cfg3/bench_agent_info.csv
@@ -92,7 +92,7 @@ l=json.loads(sys.stdin.read()); print({k:l[k] for k in ('value','ms_per_step','a
       for v in 0 1; do
         echo "== GYP_NO_GRID_FUSED=$v"
         for W in cfg2 cfg4; do
-          GYP_NO_GRID_FUSED=$v timeout 300 python bench.py --workload $W --no-cpu-baseline --no-telemetry --steps 6 --warmup 2 --verbose 2>/dev/null | python -c "
+          GYP_NO_GRID_FUSED=$v timeout 300 python bench.py --full --workload $W --no-cpu-baseline --no-telemetry --steps 6 --warmup 2 --verbose 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('$W', {k:l[k] for k in ('value','ms_per_step')}, l['roofline']['kernel_ms_per_launch'], l['roofline']['valu_frac'], l.get('visible_sats_found_stream0_ms0'))"
         done
@@ -134,7 +134,7 @@ l=json.loads(sys.stdin.read()); print('$W', {k:l[k] for k in ('value','ms_per_st
       for v in 1 0; do
         echo "== GYP_NO_GRID_PARTS=$v"
         for W in cfg5 cfg2; do
-          GYP_NO_GRID_PARTS=$v timeout 300 python bench.py --workload $W --no-cpu-baseline --steps 10 --warmup 2 --verbose 2>/dev/null | python -c "
+          GYP_NO_GRID_PARTS=$v timeout 300 python bench.py --full --workload $W --no-cpu-baseline --steps 10 --warmup 2 --verbose 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('$W', {k:l[k] for k in ('value','ms_per_step')}, l['roofline']['kernel_ms_per_launch'], l['roofline']['valu_frac'])"
         done
@@ -147,13 +147,13 @@ l=json.loads(sys.stdin.read()); print('$W', {k:l[k] for k in ('value','ms_per_st
       GYP_SURVEY_SEED=7866000000 timeout 600 python -m pytest tests/test_gpu_track_survey.py -x -q -m gpu -s -k "16368000-speculative" 2>&1 | grep -v "^$" | cut -c1-700 | grep "^\[lock\|^    \|passed\|failed" | tail -8 ;;
     cfg5)
       timeout 300 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "grid or config5" 2>&1 | tail -2
-      timeout 300 python bench.py --workload cfg5 --no-cpu-baseline --steps 10 --warmup 2 --verbose 2>/dev/null | python -c "
+      timeout 300 python bench.py --full --workload cfg5 --no-cpu-baseline --steps 10 --warmup 2 --verbose 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('cfg5', {k:l[k] for k in ('value','ms_per_step')}, l['roofline']['kernel_ms_per_launch'], l['roofline']['valu_frac'])" ;;
     scanab)
       for v in 0 16 32; do
         echo "== GYP_BENCH_SCAN_CU_RESERVE=$v"
-        GYP_BENCH_SCAN_CU_RESERVE=$v timeout 300 python bench.py --no-cpu-baseline --steps 3 --warmup 1 --detail-out $O/bench_scanab$v.json 2>/dev/null | python -c "
+        GYP_BENCH_SCAN_CU_RESERVE=$v timeout 300 python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --detail-out $O/bench_scanab$v.json 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print({k:(v['x'], v['us_ms']) for k,v in l['legs'].items() if k.startswith('s') and isinstance(v, dict) and 'x' in v}, l['legs'].get('snr_x'))"
       done ;;
@@ -163,7 +163,7 @@ l=json.loads(sys.stdin.read()); print({k:(v['x'], v['us_ms']) for k,v in l['legs
       timeout 900 python -m pytest tests/test_gpu_bench_n2.py -x -q -m gpu -rxXs > $O/pytest_n2.log 2>&1
       echo "pytest rc=$?" >> $O/pytest_n2.log; grep -v "^$" $O/pytest_n2.log | cut -c1-400 | tail -25 ;;
     bench5)
-      timeout 900 python bench.py --detail-out $O/bench_detail.json > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "bench rc=$?"; wc -c $O/bench_cfg3.json; cat $O/bench_cfg3.json; tail -5 $O/bench_cfg3.err ;;
+      timeout 900 python bench.py --full --detail-out $O/bench_detail.json > $O/bench_cfg3.json 2> $O/bench_cfg3.err; echo "bench rc=$?"; wc -c $O/bench_cfg3.json; cat $O/bench_cfg3.json; tail -5 $O/bench_cfg3.err ;;
     locksurveys)
       # fresh seeds in the LOCK regime (synth.lock_regime_scene) through both tracking kernels at the reference's three recording rates
       export GYP_SURVEY_SEED=${LOCK_SEED_BASE:-0}

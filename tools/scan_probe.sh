@@ -1,7 +1,7 @@
 #!/bin/bash
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=$R/gpurun_out/${1:-sp}; mkdir -p $O
 for st in 8 32 128; do
-  cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$st -o b -- python $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 --streams $st 2>/dev/null | python -c "
+  cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$st -o b -- python $R/bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 --streams $st 2>/dev/null | python -c "
 import json,sys
 for line in sys.stdin:
     if line.startswith('{'):
