@@ -186,6 +186,30 @@ def run_full_sky_scene(args):
     return seed, out
 
 
+def run_full_sky_one(args):
+    """args = (fs, seed, sat_id).  ONE satellite of run_full_sky_scene's scene: the oracle's 10-level acquisition of `sat_id`, so that a
+    pool spreads a scene's 32 searches (~11 s each at 49.104 Msps) over its processes.  Returns (seed, sat_id, doppler_shift,
+    prn_phase_shift, correlation_strength, min_gap) with `min_gap` the smallest relative distance between a later level's strength and
+    the best strength before it (acquisition.py:92-101 keeps the earlier level unless the later one is strictly greater): how close the
+    search came to a cross-level tie the device's float64 tie-break has to settle.  inf for a single level."""
+    fs, seed, sv = args
+    from gypsum_amd import synth
+    from oracle import gypsum_oracle as orc
+
+    n = fs // 1000
+    scene = synth.random_scene(fs, 10, 6, seed, with_nav_bits=False, max_code_phase=(2046 if n > 2046 else None))
+    iq = synth.render(scene)
+    trace = []
+    r = orc.acquire_satellite(sv, iq, fs, n, orc.prn_as_complex(orc.generate_ca_codes()[sv - 1], n), trace=trace)
+    gap, best = math.inf, None
+    for _, _, level in trace:
+        if best is not None:
+            gap = min(gap, abs(level.strength - best) / max(abs(best), 1e-300))
+        if best is None or level.strength > best:
+            best = level.strength
+    return seed, int(sv), int(r.doppler_shift), int(r.prn_phase_shift), float(r.correlation_strength), gap
+
+
 def run_grid_rows(args):
     """args = (iq_path, fs, n, n_ms, rows) with rows = int array [k, 2] of (unit, sat_id); `iq_path` a .npy of complex64[n_units, n_ms * n]
     (memory-mapped: the whole benchmark-sized batch is shared by the pool).  Per row the oracle's flat-grid search of that unit's samples

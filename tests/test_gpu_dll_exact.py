@@ -116,11 +116,13 @@ def _oracle_rows(iq, inits, fs, n, n_ms):
     return out
 
 
-@pytest.mark.parametrize("fs", [8_184_000, 2_046_000, 16_368_000])
+@pytest.mark.parametrize("fs", [8_184_000, 2_046_000, 16_368_000] + [1_023_000 * k for k in RATES if k not in (2, 8, 16)])
 def test_forced_repairs_leave_records_and_state_exact(fs):
     """A bias of 20 on the PROVISIONAL discriminator (~0.04 samples per ms on the tracking kernels' accumulator) makes their
     int(self.phase) disagree with the exact one every few milliseconds: the scan must repair each of them.  Both tracking
-    kernels (the speculative one exists at 2.046, 8.184 and 16.368 Msps), with and without the bias: every integer equals the oracle's."""
+    kernels (the speculative one exists at 2.046, 8.184 and 16.368 Msps), with and without the bias: every integer equals the oracle's.
+    At the other nine rates only the throughput kernel runs: dll_exact_wave_kernel (K = 1, 3, 5, 6) and dll_exact_block_kernel
+    (K = 10, 12, 20, 48) behind the halo, own and general staging schemes, through the same dll_scan repairs."""
     n = fs // 1000
     n_ms, n_sats = (409, 4) if n <= 8184 else (209, 3)
     iq, inits = _scene_and_inits(fs, n, n_ms, n_sats, 880 + n)
@@ -143,6 +145,7 @@ def test_forced_repairs_leave_records_and_state_exact(fs):
         assert not bad.any()
         fast = float(np.mean((rec["path_info"] & 3) == 1))
         assert (fast > 0.5) == label.startswith("speculative"), (label, fast)      # it really was the path it is named after
+        print(f"[forced repairs {fs / 1e6:.3f} Msps] {label}: {int(rep.sum())} repaired milliseconds over {n_sats} x {n_ms - 9} channel-ms")
         if "biased" in label:
             assert rep.sum() > 20, (label, rep)                                     # and the repair path really ran
         for i in range(n_sats):

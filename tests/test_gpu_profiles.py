@@ -25,7 +25,9 @@ def _oracle_trackers(iq, inits, fs, n, first_ms, n_ms):
     return out
 
 
-@pytest.mark.parametrize("fs,bias", [(2_046_000, 0.0), (8_184_000, 0.0), (8_184_000, 20.0), (16_368_000, 0.0)])
+@pytest.mark.parametrize("fs,bias", [(2_046_000, 0.0), (8_184_000, 0.0), (8_184_000, 20.0), (16_368_000, 0.0),
+                                     # the halo (K = 3, 5) and general (K = 20, 48) staging schemes fill the rows too
+                                     (3_069_000, 0.0), (5_115_000, 20.0), (20_460_000, 0.0), (49_104_000, 20.0)])
 def test_block_path_keeps_the_trailing_prompt_profiles(fs, bias):
     """Two blocks (the second shorter than the depth): after each, the bank's rows are the oracle's last profiles, in order,
     within 1e-4 of the profile maximum.  With a bias on the provisional code loop (GYP_DLL_PROV_BIAS) the tracking kernel rolls

@@ -444,11 +444,14 @@ def _multi_stream_survey(eng, specs, n_ms, label, FS=FS, N=N):
     repairs = int(bank.dll_repairs().sum())
     bank.close()
     tally = _new_tally("mixed")
+    tally["n_lock"] = tally["n_pull_in"] = 0
     at = 0
     for seed, _, _ in specs:
         inits, traj = got[seed]
+        n_before = tally["n"]
         _tally_scene(rec[at:at + len(inits)], seed, traj, tally, f"{label} stream {stream_of[seed]}", regime_of[seed],
                      twin=lambda i, seed=seed, inits=inits, traj=traj: survey_worker.fragile_from(iq[stream_of[seed]], FS, inits[i], traj[i]))
+        tally["n_lock" if regime_of[seed] == "lock" else "n_pull_in"] += tally["n"] - n_before    # channel-ms compared, by regime
         at += len(inits)
     print(f"[{label}] ONE bank of {len(init_rec)} channels over {len(specs)} streams x {T} ms at {FS / 1e6:.3f} Msps (seed offset {SEED_OFFSET}; "
           f"oracle pool {procs} processes, {time.time() - t_start:.0f} s in all, gyp_track_block {t_gpu:.2f} s incl. the upload): {tally['n']} channel-ms compared, "
@@ -463,8 +466,8 @@ def _multi_stream_survey(eng, specs, n_ms, label, FS=FS, N=N):
     return tally, len(init_rec)
 
 
-def _bank_specs(seed0, n_pull_in, n_lock):
-    return [(seed0 + k, 12, "pull-in") for k in range(n_pull_in)] + [(seed0 + 500 + k, 0, "lock") for k in range(n_lock)]
+def _bank_specs(seed0, n_pull_in, n_lock, n_sats=12):
+    return [(seed0 + k, n_sats, "pull-in") for k in range(n_pull_in)] + [(seed0 + 500 + k, 0, "lock") for k in range(n_lock)]
 
 
 @pytest.mark.parametrize("fs,n_pull_in,n_lock,n_ms,path,seed0", [
