@@ -49,6 +49,8 @@ BITS_STATE = np.dtype([("determined_bit_phase", "<i4"), ("previous_bit_phase_dec
                        ("pseudosymbol_cursor_within_queue", "<i8"), ("slide", "<i8"), ("failed_bit_count", "<i8"),
                        ("emitted_bit_count", "<i8"), ("processed_pseudosymbol_count", "<i8"),
                        ("last_emitted_bits_len", "<i4"), ("last_emitted_bits", "i1", (52,))], align=True)
+PACKING = np.dtype([("bits", "<i4"), ("real", "<i4"), ("order", "<i4"), ("reserved", "<i4"), ("levels", "<f4", (16,))], align=True)
+GYP_PACK_MSB_FIRST, GYP_PACK_LSB_FIRST = 0, 1
 GYP_BIT_ZERO, GYP_BIT_ONE, GYP_BIT_UNKNOWN = 0, 1, 2
 GYP_COMM_ID_BYTES = 128
 # sizeof() of every record the header declares, derived from the mirrors above (tests/test_abi_and_host.py compiles the
@@ -56,9 +58,9 @@ GYP_COMM_ID_BYTES = 128
 RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STATE.itemsize, "gyp_synth_sat": SYNTH_SAT.itemsize,
                 "gyp_cell_desc": CELL_DESC.itemsize, "gyp_cell": CELL.itemsize, "gyp_acq_result": ACQ_RESULT.itemsize,
                 "gyp_chan_in": CHAN_IN.itemsize, "gyp_chan_out": CHAN_OUT.itemsize, "gyp_best_bin": BEST_BIN.itemsize,
-                "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize}
+                "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
-GYP_VERSION = 205
+GYP_VERSION = 206
 
 EXPORTS = (
     "gyp_version gyp_create gyp_destroy gyp_last_error gyp_device_name gyp_set_stream gyp_sync gyp_wait_for gyp_timer_start "
@@ -70,7 +72,8 @@ EXPORTS = (
     "gyp_grid_best_bins_dev gyp_grid_best_bins_refined_dev gyp_comm_unique_id gyp_comm_init gyp_comm_destroy gyp_comm_info gyp_allgather_dev gyp_host_alloc gyp_host_free gyp_widen_iq_dev "
     "gyp_bits_create gyp_bits_destroy gyp_bits_reset gyp_bits_push gyp_bits_push_block gyp_bits_drain gyp_bits_get_state "
     "gyp_ingest_open gyp_ingest_close gyp_ingest_total_ms gyp_ingest_set_scale gyp_ingest_seek gyp_ingest_next_host gyp_ingest_next_dev gyp_ingest_times "
-    "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc"
+    "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc "
+    "gyp_packed_span gyp_unpack_iq_dev gyp_resample_packed_dev gyp_ingest_open_packed"
 ).split()
 
 
@@ -186,6 +189,11 @@ def load() -> C.CDLL:
         "gyp_ddc_design": (C.c_int, [i64, i64, i64, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
         "gyp_ddc_iq_dev": (C.c_int, [vp, i32, vp, i32, i64, i64, i64, C.c_float, i64, i64, i32, i64, i32, i64, vp]),
         "gyp_ingest_open_ddc": (C.c_int, [vp, C.c_char_p, i32, i64, i64, i32, i32, i32, C.POINTER(vp)]),
+        "gyp_packed_span": (C.c_int, [vp, i32, i64, i64, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32),
+                                      C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "gyp_unpack_iq_dev": (C.c_int, [vp, vp, vp, i32, i64, i32, i64, C.c_float, i64, vp]),
+        "gyp_resample_packed_dev": (C.c_int, [vp, vp, vp, i32, i64, i32, i64, i64, C.c_float, i64, i64, i32, i64, i32, i64, vp]),
+        "gyp_ingest_open_packed": (C.c_int, [vp, C.c_char_p, vp, i64, i64, i32, i32, i32, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

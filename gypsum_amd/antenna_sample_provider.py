@@ -191,11 +191,15 @@ class AntennaSampleProviderResampled(_CursorProvider):
 
     A real recording at an intermediate frequency (`InputFileInfo.real_if(...)`, or `if_hz=`) is down-converted to complex
     baseband instead (`gyp_ingest_open_ddc`); `resample_to` then defaults to `default_ddc_rate(sample_rate, if_hz)` and `taps`
-    to the down-converter's automatic choice."""
+    to the down-converter's automatic choice.
+
+    A recording of 1-, 2- or 4-bit packed words (`InputFileInfo.packed(...)`, or `packing=`, gypsum_amd.packing) is unpacked on
+    the device (`gyp_ingest_open_packed`).  With a packing, and only then, `resample_to` may equal the input rate (an I,Q
+    recording at a supported rate, the default `resample_to` then): its words are only unpacked."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
                  sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
-                 engine=None, device: int = 0, if_hz: int | None = None) -> None:
+                 engine=None, device: int = 0, if_hz: int | None = None, packing=None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
         from .resample import default_ddc_rate, nearest_supported_rate
@@ -207,11 +211,14 @@ class AntennaSampleProviderResampled(_CursorProvider):
             sample_component_data_type = info.sample_component_data_type
             if if_hz is None:
                 if_hz = getattr(info, "if_hz", None)
+            if packing is None:
+                packing = getattr(info, "packing", None)
         if sample_rate is None:
             raise TypeError("sample_rate is required when no InputFileInfo is given")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
         self.if_hz = None if if_hz is None else int(if_hz)
+        self.packing = packing
         if resample_to is not None:
             self.sample_rate = int(resample_to)
         elif self.if_hz is not None:
@@ -229,10 +236,16 @@ class AntennaSampleProviderResampled(_CursorProvider):
         else:
             self._own_engine = False
         self.engine = engine
-        self._ingest = IqFileIngest(self.path, self.sample_rate, sample_component_data_type, block_ms=block_ms, engine=engine,
-                                    resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
-        if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
-            self._ingest.set_scale(scale)
+        if packing is not None:
+            self._ingest = IqFileIngest(self.path, self.sample_rate, block_ms=block_ms, engine=engine, resample_from_hz=self.input_sample_rate,
+                                        taps=taps, if_hz=self.if_hz, packing=packing)
+            if scale != 1.0:
+                self._ingest.set_scale(scale)
+        else:
+            self._ingest = IqFileIngest(self.path, self.sample_rate, sample_component_data_type, block_ms=block_ms, engine=engine,
+                                        resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
+            if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
+                self._ingest.set_scale(scale)
         self.total_ms = self._ingest.total_ms
         self._block_first_ms = 0
         self._block: np.ndarray | None = None    # [n_ms, N] complex64, downloaded

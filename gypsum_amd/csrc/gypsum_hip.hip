@@ -126,6 +126,7 @@ struct gyp_ctx {
     int resample_tile = 4096;     // gyp_debug_set("resample_tile_samples"): LDS budget of one resample_kernel tile, in input samples (32 KiB: five
                                   // workgroups per CU); same output for any value
     std::vector<ResampleDesign> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps)
+    std::vector<std::pair<std::vector<float>, float*>> packed_levels;   // packed recordings: each level table met, in device memory
     int track_chunk_ms = 250;     // gyp_debug_set("track_chunk_ms"): the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
     float symbol_tau = 1e-4f;     // gyp_debug_set("symbol_tau"): |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
     bool no_shared_fwd = false;   // gyp_debug_set("no_shared_fwd"): A/B switch: flat grids transform every cell's rows themselves again
@@ -394,6 +395,7 @@ void gyp_destroy(gyp_ctx* ctx) {
     if (ctx->d_chipf) (void)hipFree(ctx->d_chipf);
     if (ctx->d_prof) (void)hipFree(ctx->d_prof);
     for (auto& d : ctx->resample_designs) if (d.d_taps) (void)hipFree(d.d_taps);
+    for (auto& l : ctx->packed_levels) (void)hipFree(l.second);
     for (int i = 0; i < 4; ++i) if (ctx->ev_track[i]) (void)hipEventDestroy(ctx->ev_track[i]);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
@@ -2332,7 +2334,7 @@ static void resample_launch_one(dim3 grid, size_t lds, hipStream_t stream, const
 // The tap counts each policy is instantiated for: the resampler's 16..64, the down-converter's 32..128.
 template <class S, class... A>
 static void resample_launch_taps(int32_t T, const A&... a) {
-    if constexpr (S::kWords == 2) {
+    if constexpr (!S::kReal) {
         switch (T) {
             case 16: resample_launch_one<S, 16>(a...); break;
             case 24: resample_launch_one<S, 24>(a...); break;
@@ -2361,13 +2363,25 @@ static void resample_launch_fmt(int32_t fmt, int32_t T, const A&... a) {
     }
 }
 
-// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.  A real design (the
-// down-converter's) stages real words mixed down from if_hz; in_stride / raw_first / raw_n count samples either way.
-static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, int32_t fmt, const void* raw, int32_t n_streams,
-                           int64_t in_stride, int64_t raw_first, int64_t raw_n, float scale, int64_t first_ms, int32_t n_ms,
-                           float* out, int64_t out_stride, int64_t if_hz = 0) {
+template <template <int> class Stage, class... A>
+static void resample_launch_bits(int32_t bits, int32_t T, const A&... a) {
+    switch (bits) {
+        case 1: resample_launch_taps<Stage<1>>(T, a...); break;
+        case 2: resample_launch_taps<Stage<2>>(T, a...); break;
+        default: resample_launch_taps<Stage<4>>(T, a...); break;
+    }
+}
+
+// resample_kernel's launch shape for output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.
+struct ResampleShape {
+    dim3 grid;
+    size_t lds;
+    int64_t p_first, n_periods;
+    int32_t np_tile, pc_tile, n_pchunks;
+};
+static int resample_shape(gyp_ctx* ctx, const ResampleDesign& d, int32_t n_streams, int64_t first_ms, int32_t n_ms, int32_t TS, ResampleShape* sh) {
     const int64_t n_periods = (int64_t)n_ms * d.g;
-    const int32_t T = d.taps, TS = ctx->resample_tile;
+    const int32_t T = d.taps;
     int32_t np_tile = 1, pc_tile = d.L, n_pchunks = 1;
     size_t lds_samples;
     if (d.M + T - 1 <= TS) {      // whole periods: as many as fit
@@ -2380,20 +2394,112 @@ static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesig
     }
     const int64_t n_tiles = (n_periods + np_tile - 1) / np_tile * n_pchunks;
     if (n_tiles > INT32_MAX || n_streams > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample: launch too large (split it)");
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_streams);
-    const size_t lds = lds_samples * sizeof(float2);
-    const int64_t p_first = first_ms * d.g;
+    *sh = ResampleShape{dim3((unsigned)n_tiles, (unsigned)n_streams), lds_samples * sizeof(float2), first_ms * d.g, n_periods, np_tile,
+                        pc_tile, n_pchunks};
+    return GYP_OK;
+}
+
+// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.  A real design (the
+// down-converter's) stages real words mixed down from if_hz; in_stride / raw_first / raw_n count samples either way.
+static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, int32_t fmt, const void* raw, int32_t n_streams,
+                           int64_t in_stride, int64_t raw_first, int64_t raw_n, float scale, int64_t first_ms, int32_t n_ms,
+                           float* out, int64_t out_stride, int64_t if_hz = 0) {
+    ResampleShape sh;
+    if (const int rc = resample_shape(ctx, d, n_streams, first_ms, n_ms, ctx->resample_tile, &sh)) return rc;
+    const int32_t T = d.taps;
     if (d.real) {
         const int64_t fs = d.fs_in;
         const int64_t f = (if_hz % fs + fs) % fs;
-        resample_launch_fmt<StageReal>(fmt, T, grid, lds, stream, raw, in_stride, raw_first, raw_n, StageRealParams{scale, fs, f, 4.0 / (double)fs, 0.5 / (double)fs},
-                                       d, p_first, n_periods, np_tile, pc_tile, n_pchunks, out, out_stride);
+        resample_launch_fmt<StageReal>(fmt, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n,
+                                       StageRealParams{scale, fs, f, 4.0 / (double)fs, 0.5 / (double)fs}, d, sh.p_first, sh.n_periods,
+                                       sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
     } else {
-        resample_launch_fmt<StageIQ>(fmt, T, grid, lds, stream, raw, in_stride, raw_first, raw_n, StageIQParams{scale}, d, p_first,
-                                     n_periods, np_tile, pc_tile, n_pchunks, out, out_stride);
+        resample_launch_fmt<StageIQ>(fmt, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n, StageIQParams{scale}, d, sh.p_first,
+                                     sh.n_periods, sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
     }
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
+}
+
+// The packing's level table in device memory: uploaded on first use and cached on the context (which frees it), like a design.
+static int packed_levels_dev(gyp_ctx* ctx, const PackedFormat& pk, const float** out) {
+    const std::vector<float> key(pk.levels.v, pk.levels.v + 16);
+    for (const auto& l : ctx->packed_levels)
+        if (std::memcmp(l.first.data(), key.data(), sizeof(pk.levels.v)) == 0) {
+            *out = l.second;
+            return GYP_OK;
+        }
+    float* d = nullptr;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMalloc((void**)&d, sizeof(pk.levels.v)));
+    const hipError_t e = hipMemcpyAsync(d, key.data(), sizeof(pk.levels.v), hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `key` is a temporary
+    if (e2 != hipSuccess) {
+        (void)hipFree(d);
+        return fail(ctx, GYP_E_HIP, std::string("packed level table upload: ") + hipGetErrorString(e2));
+    }
+    ctx->packed_levels.emplace_back(key, d);
+    *out = d;
+    return GYP_OK;
+}
+
+// resample_launch on packed words: in_stride counts bytes, and the buffer's sample 0 (input sample raw_first) starts bit0 bits
+// into its first byte.  The design's kind (real or not) matches pk.real.
+static int resample_launch_packed(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, const PackedFormat& pk, const void* raw,
+                                  int32_t n_streams, int64_t in_stride, int32_t bit0, int64_t raw_first, int64_t raw_n, float scale,
+                                  int64_t first_ms, int32_t n_ms, float* out, int64_t out_stride, int64_t if_hz) {
+    ResampleShape sh;
+    // the 16-entry level table takes 64 bytes of LDS beside the tile: the tile gives up 8 samples, so five workgroups still fit a
+    // CU (the tile's shape does not change an output's bits)
+    if (const int rc = resample_shape(ctx, d, n_streams, first_ms, n_ms, ctx->resample_tile - 8, &sh)) return rc;
+    const float* levels = nullptr;
+    if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
+    const int32_t T = d.taps;
+    if (d.real) {
+        const int64_t fs = d.fs_in;
+        StageRealPackedParams prm;
+        static_cast<StagePackedParams&>(prm) = StagePackedParams{levels, scale, pk.order, bit0};
+        prm.fs = fs;
+        prm.f = (if_hz % fs + fs) % fs;
+        prm.q_scale = 4.0 / (double)fs;
+        prm.y_scale = 0.5 / (double)fs;
+        resample_launch_bits<StageRealPacked>(pk.bits, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n, prm, d, sh.p_first,
+                                              sh.n_periods, sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
+    } else {
+        resample_launch_bits<StageIQPacked>(pk.bits, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n,
+                                            StagePackedParams{levels, scale, pk.order, bit0}, d, sh.p_first, sh.n_periods, sh.np_tile,
+                                            sh.pc_tile, sh.n_pchunks, out, out_stride);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+// Enqueue ingest_unpack_kernel on `stream` (packed I,Q words at their own rate).
+static int unpack_launch(gyp_ctx* ctx, hipStream_t stream, const PackedFormat& pk, const void* raw, int32_t n_streams, int64_t in_stride,
+                         int32_t bit0, int64_t n_samples, float scale, float* out, int64_t out_stride) {
+    const int64_t kS = 64 / pk.bits;
+    const int64_t n_items = (n_samples + kS - 1) / kS * n_streams;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu));
+    const int32_t vec4 = ((uintptr_t)out & 15u) == 0 && out_stride % 2 == 0;   // every row starts 16-byte aligned
+    const float* levels = nullptr;
+    if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
+    const uint8_t* r = (const uint8_t*)raw;
+    float2* o = (float2*)out;
+    switch (pk.bits) {
+        case 1: hipLaunchKernelGGL(ingest_unpack_kernel<1>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
+        case 2: hipLaunchKernelGGL(ingest_unpack_kernel<2>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
+        default: hipLaunchKernelGGL(ingest_unpack_kernel<4>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+// The checks common to the packed device entries: the buffer holds bit0 + n * B bits per stream, bit0 a sample edge below 8.
+static bool packed_buffer_ok(const PackedFormat& pk, int64_t in_stride_bytes, int32_t bit0, int64_t n_samples) {
+    const int64_t B = pk.sample_bits();
+    if (bit0 < 0 || bit0 >= 8 || bit0 % B || n_samples < 0 || in_stride_bytes < 0) return false;
+    if (n_samples > (INT64_MAX - 8) / B / 2 || in_stride_bytes > INT64_MAX / 16) return false;
+    return in_stride_bytes * 8 >= bit0 + n_samples * B;
 }
 
 // The argument checks and the launch of gyp_resample_iq_dev / gyp_ddc_iq_dev, on the context's stream.
@@ -2459,6 +2565,66 @@ int gyp_ddc_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_str
                                scale, if_hz, first_ms, n_ms, out_stride_samples, out_dev);
 }
 
+int gyp_packed_span(const gyp_packing* packing, int32_t samples_per_ms, int64_t file_bytes, int64_t first_sample, int64_t n_samples,
+                    int64_t* in_first_out, int64_t* in_n_out, int64_t* first_byte_out, int32_t* bit0_out, int64_t* n_bytes_out,
+                    int64_t* file_samples_out, int64_t* total_ms_out) {
+    PackedFormat pk;
+    if (const char* why = packing_check(packing, &pk)) return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_packed_span: ") + why);
+    if (samples_per_ms < 1 || file_bytes < 0 || file_bytes > ((int64_t)1 << 58) || n_samples < 0 || n_samples > ((int64_t)1 << 61) ||
+        first_sample < -((int64_t)1 << 61) || first_sample > ((int64_t)1 << 61))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_packed_span: bad arguments (samples_per_ms >= 1, 0 <= file_bytes < 2^58, 0 <= n_samples <= 2^61, "
+                                            "|first_sample| <= 2^61)");
+    const int64_t file_samples = file_bytes * 8 / pk.sample_bits();
+    const PackedSpan sp = packed_span(pk.sample_bits(), file_samples, first_sample, n_samples);
+    if (in_first_out) *in_first_out = sp.in_first;
+    if (in_n_out) *in_n_out = sp.in_n;
+    if (first_byte_out) *first_byte_out = sp.first_byte;
+    if (bit0_out) *bit0_out = sp.bit0;
+    if (n_bytes_out) *n_bytes_out = sp.n_bytes;
+    if (file_samples_out) *file_samples_out = file_samples;
+    if (total_ms_out) *total_ms_out = file_samples > 0 ? (file_samples - 1) / samples_per_ms : 0;
+    return GYP_OK;
+}
+
+int gyp_unpack_iq_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_dev, int32_t n_streams, int64_t in_stride_bytes,
+                      int32_t bit0, int64_t n_samples, float scale, int64_t out_stride_samples, float* out_dev) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    PackedFormat pk;
+    if (const char* why = packing_check(packing, &pk)) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_unpack_iq_dev: ") + why);
+    if (pk.real) return fail(ctx, GYP_E_BAD_ARG, "gyp_unpack_iq_dev: real words are down-converted (gyp_resample_packed_dev), not unpacked");
+    if (n_streams < 1 || n_streams > 65535 || !packed_buffer_ok(pk, in_stride_bytes, bit0, n_samples) || out_stride_samples < n_samples ||
+        !std::isfinite(scale) || (n_samples > 0 && (!raw_dev || !out_dev)))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_unpack_iq_dev: bad arguments (1 <= n_streams <= 65535, n_samples >= 0, 0 <= bit0 < 8 a multiple "
+                                        "of the sample's bits, 8 in_stride_bytes >= bit0 + n_samples * sample bits, out_stride >= n_samples, "
+                                        "finite scale, non-NULL buffers)");
+    if (n_samples == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return unpack_launch(ctx, ctx->stream, pk, raw_dev, n_streams, in_stride_bytes, bit0, n_samples, scale, out_dev, out_stride_samples);
+}
+
+int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_dev, int32_t n_streams, int64_t in_stride_bytes,
+                            int32_t bit0, int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t fs_in_hz, int64_t if_hz,
+                            int32_t taps, int64_t first_ms, int32_t n_ms, int64_t out_stride_samples, float* out_dev) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    const char* who = "gyp_resample_packed_dev";
+    PackedFormat pk;
+    if (const char* why = packing_check(packing, &pk)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why);
+    if (pk.real != (if_hz != 0))
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": real words need if_hz != 0, I,Q words if_hz = 0");
+    ResampleDesign d;
+    if (const int rc = pk.real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who))
+        return rc;
+    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || !packed_buffer_ok(pk, in_stride_bytes, bit0, raw_n_samples) ||
+        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, raw_n_samples >= 0, "
+                                                           "0 <= bit0 < 8 a multiple of the sample's bits, 8 in_stride_bytes >= bit0 + "
+                                                           "raw_n_samples * sample bits, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return resample_launch_packed(ctx, ctx->stream, d, pk, raw_dev, n_streams, in_stride_bytes, bit0, raw_first_sample, raw_n_samples, scale,
+                                  first_ms, n_ms, out_dev, out_stride_samples, if_hz);
+}
+
 }  // extern "C"
 
 
@@ -2504,6 +2670,21 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     // the kernels of block k-1 when block k+1 is uploaded ahead, so the upload still overlaps block k's kernels)
     HIP_TRY(ctx, hipEventRecord(g->consumer_mark, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(g->copy_stream, g->consumer_mark, 0));
+    if (g->packed) {   // the bytes covering the block's samples (halo included), unpacked / resampled / down-converted into the output slot
+        const PackedSpan sp = ingest_packed_span(g, u->first_ms, u->n_ms);
+        if (sp.n_bytes) HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)sp.n_bytes, hipMemcpyHostToDevice, g->copy_stream));
+        HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
+        const int rc = g->resampled
+                           ? resample_launch_packed(ctx, g->copy_stream, g->rs, g->pk, g->dev_raw[d], 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n,
+                                                    g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n, g->if_hz)
+                           : unpack_launch(ctx, g->copy_stream, g->pk, g->dev_raw[d], 1, sp.n_bytes, sp.bit0, (int64_t)u->n_ms * g->n, g->scale,
+                                           g->dev_iq[d], (int64_t)u->n_ms * g->n);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
+        g->in_flight.push_back(*u);
+        ++g->dev_blocks;
+        return 1;
+    }
     if (g->resampled) {   // the block's input span (halo included) in file width, resampled into the output slot
         const int64_t span = (int64_t)u->n_ms * g->in_n + g->halo_lo + g->halo_hi;
         HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream));
@@ -2559,6 +2740,10 @@ static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp
     }
     g->total_ms = st.st_size > 0 ? (int64_t)((st.st_size - 1) / (off_t)g->ms_bytes) : 0;
     if (g->sample_bytes) g->file_samples = (int64_t)(st.st_size / (off_t)g->sample_bytes);
+    if (g->packed) {   // counted in samples (gyp_packed_span)
+        g->file_samples = (int64_t)st.st_size * 8 / g->pk.sample_bits();
+        g->total_ms = g->file_samples > 0 ? (g->file_samples - 1) / g->in_n : 0;
+    }
     (void)posix_fadvise(g->fd, 0, 0, POSIX_FADV_SEQUENTIAL);
     const size_t block_bytes = g->host_block_bytes;
     g->host.assign(depth, nullptr);
@@ -2675,6 +2860,51 @@ int gyp_ingest_open_ddc(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_
     return ingest_open_filtered(ctx, path, fmt, fs_in_hz, true, if_hz, taps, block_ms, depth, out, "gyp_ingest_open_ddc");
 }
 
+int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* packing, int64_t fs_in_hz, int64_t if_hz, int32_t taps,
+                           int32_t block_ms, int32_t depth, gyp_ingest** out) {
+    const char* who = "gyp_ingest_open_packed";
+    if (!out) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, std::string(who) + ": a context is required");
+    PackedFormat pk;
+    if (const char* why = packing_check(packing, &pk)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why);
+    if (pk.real != (if_hz != 0)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": real words need if_hz != 0, I,Q words if_hz = 0");
+    if (!path || block_ms < 1 || depth < 3 || depth > 64)
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (path, block_ms >= 1, 3 <= depth <= 64)");
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    const bool native = !pk.real && fs_in_hz == ctx->fs;
+    const float* levels = nullptr;   // uploaded now, not on the copy stream's first block
+    if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
+    ResampleDesign d;
+    if (!native)
+        if (const int rc = pk.real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who))
+            return rc;
+    gyp_ingest* g = new (std::nothrow) gyp_ingest();
+    if (!g) return fail(ctx, GYP_E_NOMEM, std::string(who) + ": out of memory");
+    g->ctx = ctx;
+    g->fmt = -1;   // no file-width word format: set_scale applies
+    g->fs = ctx->fs;
+    g->n = (int32_t)(ctx->fs / 1000);
+    g->block_ms = block_ms;
+    g->depth = depth;
+    g->packed = true;
+    g->pk = pk;
+    g->resampled = !native;
+    g->real = pk.real;
+    g->if_hz = if_hz;
+    g->in_n = native ? g->n : d.n_in;
+    if (!native) {
+        g->rs = d;
+        g->halo_lo = d.taps / 2 - 1;
+        g->halo_hi = d.taps / 2;
+    }
+    g->ms_bytes = 1;   // total_ms is counted in samples (ingest_finish_open)
+    const int64_t span = (int64_t)block_ms * g->in_n + g->halo_lo + g->halo_hi;
+    g->host_block_bytes = (size_t)((span * pk.sample_bits() + 7) / 8 + 1);
+    g->raw_block_bytes = g->host_block_bytes;
+    return ingest_finish_open(ctx, g, path, out);
+}
+
 int gyp_device_locality(gyp_ctx* ctx, int32_t* numa_node_out, char* cpulist_out, int32_t cap) {
     if (!ctx) return GYP_E_BAD_ARG;
     const HostLocality loc = device_locality(ctx->device);
@@ -2723,6 +2953,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     *raw_out = nullptr;
     *n_ms_out = 0;
     if (g->resampled) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
+    if (g->packed) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now

@@ -126,6 +126,115 @@ __global__ __launch_bounds__(256) void ingest_widen_kernel(const T* __restrict__
         for (size_t i = n_vec * kPer + threadIdx.x; i < n_words; i += blockDim.x) out[i] = (float)raw[i] * scale;
 }
 
+// Packed I,Q words -> complex64 (gyp_unpack_iq_dev; the packed ingest at the context's rate).  The widen kernel's shape: a
+// persistent grid, 16 aligned input bytes per lane per iteration, contiguous float stores.  Item (stream s, vector v) writes
+// samples v*kS .. v*kS+kS-1 of stream s, whose 128 bits start e0 = 8 * (stream base mod 16) + bit0 bits into aligned block v:
+// the lane loads blocks v and v+1 (v+1 only if those bits reach into it and it holds bytes of the stream), turns an MSB-first
+// packing into a little-endian bit string and shifts it down by e0 (a select on e0 / 32, then v_alignbit), so word j of the
+// item sits at bits [j*BITS, (j+1)*BITS).  An aligned block that holds any byte of the stream lies in that byte's page, so no
+// load can fault beyond the buffer.  Values are levels[code] * scale from an LDS table: no dynamically indexed registers.
+template <int BITS>
+__device__ __forceinline__ uint32_t packed_lsb_first(uint32_t x) {   // reverse the order of the BITS-bit fields within each byte
+    if (BITS == 1) x = ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u);
+    if (BITS <= 2) x = ((x & 0x33333333u) << 2) | ((x >> 2) & 0x33333333u);
+    return ((x & 0x0f0f0f0fu) << 4) | ((x >> 4) & 0x0f0f0f0fu);
+}
+
+template <int BITS>
+__global__ __launch_bounds__(256) void ingest_unpack_kernel(const uint8_t* __restrict__ raw, int64_t in_stride, int32_t bit0,
+                                                            int64_t n_samples, int32_t n_streams, const float* __restrict__ levels, float scale,
+                                                            int32_t order, float2* __restrict__ out, int64_t out_stride, int32_t vec4) {
+    __shared__ float tab[16];
+    packed_table<BITS>(tab, levels, scale);
+    __syncthreads();
+    constexpr int kS = 64 / BITS;                 // samples per 16 bytes (2 BITS bits each)
+    constexpr uint32_t kMask = (1u << BITS) - 1u;
+    const bool msb = order == GYP_PACK_MSB_FIRST;
+    const int64_t n_vec = (n_samples + kS - 1) / kS;
+    const int64_t n_bytes = (bit0 + n_samples * (2 * BITS) + 7) >> 3;   // of each stream, from its base
+    const int64_t n_items = n_vec * n_streams;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < n_items; it += stride) {
+        const int64_t s = it / n_vec, v = it - s * n_vec;
+        const uint8_t* base = raw + s * in_stride;
+        const uint32_t a = (uint32_t)((uintptr_t)base & 15u);
+        const uint4* blk = reinterpret_cast<const uint4*>(base - a);
+        const uint32_t e0 = a * 8u + (uint32_t)bit0;   // 0 .. 127
+        const uint4 w0 = blk[v];                       // holds the stream's byte (e0 + 128 v) / 8
+        const uint4 w1 = (e0 != 0 && 16 * (v + 1) < a + n_bytes) ? blk[v + 1] : make_uint4(0u, 0u, 0u, 0u);
+        uint32_t d[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+        if (msb) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) d[k] = packed_lsb_first<BITS>(d[k]);
+        }
+        const uint32_t q = e0 >> 5, r = e0 & 31u;
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t lo = q == 0 ? d[k] : q == 1 ? d[k + 1] : q == 2 ? d[k + 2] : d[k + 3];
+            const uint32_t hi = q == 0 ? d[k + 1] : q == 1 ? d[k + 2] : q == 2 ? d[k + 3] : d[k + 4];
+            w[k] = __builtin_amdgcn_alignbit(hi, lo, r);
+        }
+        const int64_t n0 = v * kS;
+        float2* o = out + s * out_stride + n0;
+#define GYP_WORD(j) tab[(w[((j) * BITS) >> 5] >> (((j) * BITS) & 31)) & kMask]
+        if (vec4 && n0 + kS <= n_samples) {
+#pragma unroll
+            for (int i = 0; i < kS / 2; ++i)
+                reinterpret_cast<float4*>(o)[i] = make_float4(GYP_WORD(4 * i), GYP_WORD(4 * i + 1), GYP_WORD(4 * i + 2), GYP_WORD(4 * i + 3));
+        } else {
+#pragma unroll
+            for (int i = 0; i < kS; ++i)
+                if (n0 + i < n_samples) o[i] = make_float2(GYP_WORD(2 * i), GYP_WORD(2 * i + 1));
+        }
+#undef GYP_WORD
+    }
+}
+
+// A validated packing as the kernels take it.
+struct PackedFormat {
+    int32_t bits = 0, order = 0;
+    bool real = false;
+    PackedLevels levels{};
+    int64_t sample_bits() const { return (int64_t)bits * (real ? 1 : 2); }
+};
+// GYP_E_BAD_ARG's reason, or nullptr if the packing is valid (then *out holds it).
+static const char* packing_check(const gyp_packing* p, PackedFormat* out) {
+    if (!p) return "packing is NULL";
+    if (p->bits != 1 && p->bits != 2 && p->bits != 4) return "packing.bits must be 1, 2 or 4";
+    if (p->real != 0 && p->real != 1) return "packing.real must be 0 or 1";
+    if (p->order != GYP_PACK_MSB_FIRST && p->order != GYP_PACK_LSB_FIRST) return "packing.order must be GYP_PACK_MSB_FIRST or GYP_PACK_LSB_FIRST";
+    if (p->reserved != 0) return "packing.reserved must be 0";
+    PackedFormat f;
+    f.bits = p->bits;
+    f.order = p->order;
+    f.real = p->real == 1;
+    for (int c = 0; c < (1 << p->bits); ++c) {
+        if (!std::isfinite(p->levels[c])) return "packing.levels[c] must be finite for every code c < 2^bits";
+        f.levels.v[c] = p->levels[c];
+    }
+    if (out) *out = f;
+    return nullptr;
+}
+
+// Where samples first .. first+n-1 lie in a packed file of file_samples samples of B bits: the part inside the file and the bytes
+// that cover it (all zero if none).  gyp_packed_span is this function; the ingest reads exactly these bytes.
+struct PackedSpan {
+    int64_t in_first = 0, in_n = 0, first_byte = 0, n_bytes = 0;
+    int32_t bit0 = 0;
+};
+static PackedSpan packed_span(int64_t B, int64_t file_samples, int64_t first, int64_t n) {
+    PackedSpan sp;
+    const int64_t a = std::max<int64_t>(first, 0), b = std::min<int64_t>(first + n, file_samples);
+    if (b <= a) return sp;
+    sp.in_first = a;
+    sp.in_n = b - a;
+    sp.first_byte = a * B / 8;
+    sp.bit0 = (int32_t)(a * B % 8);
+    sp.n_bytes = (b * B + 7) / 8 - sp.first_byte;
+    return sp;
+}
+
 struct gyp_ingest {
     gyp_ctx* ctx = nullptr;   // null: host-only (no pinned memory, no device ring)
     int fd = -1;
@@ -149,6 +258,10 @@ struct gyp_ingest {
     int32_t in_n = 0, halo_lo = 0, halo_hi = 0;
     size_t sample_bytes = 0;
     int64_t file_samples = 0;
+    // packed handles (gyp_ingest_open_packed): words of pk.bits bits; a block reads the bytes covering its samples (halo included
+    // when resampled), which the upload stream unpacks, resamples or down-converts.  in_n is the input millisecond either way.
+    bool packed = false;
+    PackedFormat pk{};
 
     // host ring, filled by the reader thread
     std::vector<uint8_t*> host;
@@ -205,6 +318,27 @@ static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int
     return 0;
 }
 
+// A packed block's span: its input samples with the halo, the part inside the file, and the bytes covering that part.
+static PackedSpan ingest_packed_span(const gyp_ingest* g, int64_t first, int32_t n_ms) {
+    return packed_span(g->pk.sample_bits(), g->file_samples, first * g->in_n - g->halo_lo, (int64_t)n_ms * g->in_n + g->halo_lo + g->halo_hi);
+}
+
+// A packed block: the bytes covering its samples, as they are in the file.  0 or an errno.
+static int ingest_read_packed(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
+    const PackedSpan sp = ingest_packed_span(g, first, n_ms);
+    size_t got = 0;
+    while (got < (size_t)sp.n_bytes) {
+        const ssize_t r = pread(g->fd, buf + got, (size_t)sp.n_bytes - got, (off_t)((size_t)sp.first_byte + got));
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return errno;
+        }
+        if (r == 0) return EIO;   // file shrank under us
+        got += (size_t)r;
+    }
+    return 0;
+}
+
 static void ingest_reader_main(gyp_ingest* g) {
     for (;;) {
         int slot;
@@ -223,8 +357,9 @@ static void ingest_reader_main(gyp_ingest* g) {
             }
             slot = (int)(g->produced % g->depth);
         }
-        size_t want = g->resampled ? 0 : (size_t)n_ms * g->ms_bytes, got = 0;
-        int err = g->resampled ? ingest_read_resampled(g, g->host[slot], first, n_ms) : 0;
+        size_t want = g->resampled || g->packed ? 0 : (size_t)n_ms * g->ms_bytes, got = 0;
+        int err = g->packed ? ingest_read_packed(g, g->host[slot], first, n_ms)
+                  : g->resampled ? ingest_read_resampled(g, g->host[slot], first, n_ms) : 0;
         while (got < want) {
             const ssize_t r = pread(g->fd, g->host[slot] + got, want - got, (off_t)((size_t)first * g->ms_bytes + got));
             if (r < 0) {

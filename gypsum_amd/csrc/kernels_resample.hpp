@@ -16,6 +16,11 @@
 // The staging step is a compile-time policy: StageIQ widens an I,Q word pair to float2; StageReal widens one real word and
 // multiplies it by the mixer exp(-j 2 pi ((if_hz * i) mod fs_in) / fs_in) of its absolute input index i, a pure function of i
 // (exact integer phase, no accumulator), so the bit-identity argument above carries over unchanged.
+//
+// Packed recordings (1-, 2- or 4-bit words, include/gypsum_hip.h "packed recordings") stage through StageIQPacked / StageRealPacked:
+// a sample's code comes out of its one byte at its bit offset and its value is a table entry levels[code] * scale, the same single
+// float32 multiply as (float)word * scale.  After the staging step nothing differs, so packed and int8 words holding the same levels
+// give the same bits.
 #pragma once
 
 #include <algorithm>
@@ -147,6 +152,7 @@ struct StageIQ : StageIQParams {   // interleaved I,Q words: (I, Q) * scale
     using Word = W;
     using Params = StageIQParams;
     static constexpr int kWords = 2;   // words per sample
+    static constexpr bool kReal = false;   // the down-converter's tap counts (resample_launch_taps)
     static constexpr bool kSplitPeriods = false;   // lanes split the tile's periods too (see resample_kernel)
     __device__ __forceinline__ void stage(float2* xs, const W* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
                                           int64_t raw_n) const {
@@ -163,6 +169,7 @@ struct StageReal : StageRealParams {   // real words at an IF: word * scale * ex
     using Word = W;
     using Params = StageRealParams;
     static constexpr int kWords = 1;
+    static constexpr bool kReal = true;
     static constexpr bool kSplitPeriods = true;
     __device__ __forceinline__ void stage(float2* xs, const W* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
                                           int64_t raw_n) const {
@@ -176,6 +183,101 @@ struct StageReal : StageRealParams {   // real words at an IF: word * scale * ex
             const int64_t idx = s0 + k;
             const int64_t rel = idx - raw_first;
             const float x = (idx >= 0 && rel >= 0 && rel < raw_n) ? (float)src[rel] * scale : 0.f;
+            const float2 m = ddc_mixer(r, fs, q_scale, y_scale);
+            xs[k] = make_float2(x * m.x, x * m.y);
+            r += step;
+            if (r >= fs) r -= fs;
+        }
+    }
+};
+
+// --- packed words -------------------------------------------------------------------------------------------------------------
+// The levels a packing gives its codes, before scale (entries >= 2^bits unused).  The kernels read them from a 16-float table in
+// device memory (cached on the context): passed by value in the kernel arguments, the same 16 floats made the scheduler double
+// resample_kernel's registers at T = 16 and 24 (6 -> 3 waves per SIMD).
+struct PackedLevels {
+    float v[16];
+};
+
+// levels[c] * scale into an LDS table, one lane per entry: the lookup of a code is then one LDS read, never a dynamically
+// indexed register array (scratch).  The caller syncs before reading the table.
+template <int BITS>
+__device__ __forceinline__ void packed_table(float* tab, const float* __restrict__ levels, float scale) {
+    if (threadIdx.x < (1u << BITS)) tab[threadIdx.x] = levels[threadIdx.x] * scale;
+}
+
+// The code of the word `slot` bits into byte `b` (slot a multiple of BITS below 8), in the packing's bit order.
+template <int BITS>
+__device__ __forceinline__ uint32_t packed_code(uint32_t b, uint32_t slot, bool msb_first) {
+    const uint32_t sh = msb_first ? 8u - BITS - slot : slot;
+    return (b >> sh) & ((1u << BITS) - 1u);
+}
+
+struct StagePackedParams {
+    const float* levels; // 16 floats in device memory
+    float scale;
+    int32_t order;       // GYP_PACK_MSB_FIRST / GYP_PACK_LSB_FIRST
+    int32_t bit0;        // bit offset of the buffer's sample 0 in its first byte
+};
+struct StageRealPackedParams : StagePackedParams {
+    int64_t fs;          // as StageRealParams
+    int64_t f;
+    double q_scale;
+    double y_scale;
+};
+
+template <int BITS>
+struct StageIQPacked : StagePackedParams {   // I,Q words packed BITS to a word: (levels[cI], levels[cQ]) * scale
+    using Word = uint8_t;
+    using Params = StagePackedParams;
+    static constexpr int kWords = 1;   // strides count bytes
+    static constexpr bool kReal = false;
+    static constexpr bool kSplitPeriods = false;
+    __device__ __forceinline__ void stage(float2* xs, const uint8_t* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
+                                          int64_t raw_n) const {
+        __shared__ float tab[16];
+        packed_table<BITS>(tab, levels, scale);
+        __syncthreads();
+        const bool msb = order == GYP_PACK_MSB_FIRST;
+        for (int32_t k = threadIdx.x; k < span; k += blockDim.x) {
+            const int64_t idx = s0 + k;
+            const int64_t rel = idx - raw_first;
+            float2 x = make_float2(0.f, 0.f);
+            if (idx >= 0 && rel >= 0 && rel < raw_n) {
+                const int64_t pos = bit0 + rel * (2 * BITS);   // a sample's 2 BITS bits never straddle a byte
+                const uint32_t b = src[pos >> 3], slot = (uint32_t)(pos & 7);
+                x = make_float2(tab[packed_code<BITS>(b, slot, msb)], tab[packed_code<BITS>(b, slot + BITS, msb)]);
+            }
+            xs[k] = x;
+        }
+    }
+};
+
+template <int BITS>
+struct StageRealPacked : StageRealPackedParams {   // real words packed BITS to a word, mixed down as StageReal does
+    using Word = uint8_t;
+    using Params = StageRealPackedParams;
+    static constexpr int kWords = 1;
+    static constexpr bool kReal = true;
+    static constexpr bool kSplitPeriods = true;
+    __device__ __forceinline__ void stage(float2* xs, const uint8_t* __restrict__ src, int64_t s0, int32_t span, int64_t raw_first,
+                                          int64_t raw_n) const {
+        __shared__ float tab[16];
+        packed_table<BITS>(tab, levels, scale);
+        __syncthreads();
+        const bool msb = order == GYP_PACK_MSB_FIRST;
+        int64_t i = (s0 + (int64_t)threadIdx.x) % fs;   // the mixer index exactly as StageReal steps it
+        if (i < 0) i += fs;
+        int64_t r = f * i % fs;
+        const int64_t step = f * (int64_t)blockDim.x % fs;
+        for (int32_t k = threadIdx.x; k < span; k += blockDim.x) {
+            const int64_t idx = s0 + k;
+            const int64_t rel = idx - raw_first;
+            float x = 0.f;
+            if (idx >= 0 && rel >= 0 && rel < raw_n) {
+                const int64_t pos = bit0 + rel * BITS;
+                x = tab[packed_code<BITS>(src[pos >> 3], (uint32_t)(pos & 7), msb)];
+            }
             const float2 m = ddc_mixer(r, fs, q_scale, y_scale);
             xs[k] = make_float2(x * m.x, x * m.y);
             r += step;

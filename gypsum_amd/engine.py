@@ -233,6 +233,24 @@ class GypsumEngine:
                                             int(raw_first_sample), int(raw_n_samples), float(scale), int(fs_in), int(if_hz), int(taps),
                                             int(first_ms), int(n_ms), int(out_stride), C.c_void_p(out_ptr)))
 
+    def unpack_iq_dev(self, packing, raw_ptr: int, n_streams: int, in_stride_bytes: int, bit0: int, n_samples: int, scale: float,
+                      out_stride: int, out_ptr: int) -> None:
+        """gyp_unpack_iq_dev: packed I,Q words (gypsum_amd.packing.Packing) in HBM -> complex64 at their own rate; stream s starts
+        at byte raw_ptr + s * in_stride_bytes, its sample 0 bit0 bits into that byte.  Enqueued, not synchronised."""
+        rec = packing.record()
+        self._check(self.lib.gyp_unpack_iq_dev(self.ctx, ptr(rec), C.c_void_p(raw_ptr), int(n_streams), int(in_stride_bytes), int(bit0),
+                                               int(n_samples), float(scale), int(out_stride), C.c_void_p(out_ptr)))
+
+    def resample_packed_dev(self, packing, raw_ptr: int, n_streams: int, in_stride_bytes: int, bit0: int, raw_first_sample: int,
+                            raw_n_samples: int, scale: float, fs_in: int, if_hz: int, taps: int, first_ms: int, n_ms: int,
+                            out_stride: int, out_ptr: int) -> None:
+        """gyp_resample_packed_dev: resample_iq_dev (an I,Q packing, if_hz 0) or ddc_iq_dev (a real packing) on packed words; strides
+        in bytes, the buffer's sample 0 (input sample raw_first_sample) bit0 bits into its first byte.  Enqueued, not synchronised."""
+        rec = packing.record()
+        self._check(self.lib.gyp_resample_packed_dev(self.ctx, ptr(rec), C.c_void_p(raw_ptr), int(n_streams), int(in_stride_bytes),
+                                                     int(bit0), int(raw_first_sample), int(raw_n_samples), float(scale), int(fs_in),
+                                                     int(if_hz), int(taps), int(first_ms), int(n_ms), int(out_stride), C.c_void_p(out_ptr)))
+
     def ddc(self, words: np.ndarray, fmt, fs_in: int, if_hz: int, first_ms: int = 0, n_ms: Optional[int] = None, scale: float = 1.0,
             taps: int = 0) -> np.ndarray:
         """Host convenience: real `words` of a recording at fs_in with its band at if_hz (int8 / uint8 / int16 / float32; 2-D = one

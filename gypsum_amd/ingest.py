@@ -10,6 +10,11 @@ With `resample_from_hz` the recording is at that rate (any whole kHz within a fa
 come out resampled to the engine's stream format (`gyp_ingest_open_resampled`, `gypsum_amd.resample`); `n` and `fs` are then
 the output rate and there are no host blocks.  With `if_hz` as well the recording holds one real word per sample at an
 intermediate frequency of `if_hz` Hz and is down-converted to complex baseband on the device (`gyp_ingest_open_ddc`).
+
+With `packing` (gypsum_amd.packing) the recording holds 1-, 2- or 4-bit words packed into bytes, read as they are and unpacked on
+the device (`gyp_ingest_open_packed`): I,Q at the engine's rate (`resample_from_hz` None or equal to it) are only unpacked, I,Q at
+another rate are resampled, and a real packing (with `if_hz`) is down-converted.  The word type is then the packing's, so
+`sample_component_data_type` must be left out.
 """
 from __future__ import annotations
 
@@ -26,10 +31,14 @@ _FORMATS = {np.dtype(np.float32): _lib.GYP_FMT_F32, np.dtype(np.int8): _lib.GYP_
 
 
 class IqFileIngest:
-    def __init__(self, path, samples_per_second: int, sample_component_data_type=np.float32, block_ms: int = 100,
+    def __init__(self, path, samples_per_second: int, sample_component_data_type=None, block_ms: int = 100,
                  depth: int = 4, engine=None, resample_from_hz: Optional[int] = None, taps: Optional[int] = None,
-                 if_hz: Optional[int] = None) -> None:
-        self.dtype = np.dtype(sample_component_data_type)
+                 if_hz: Optional[int] = None, packing=None) -> None:
+        self.packing = packing
+        if packing is not None:
+            self._open_packed(path, samples_per_second, sample_component_data_type, block_ms, depth, engine, resample_from_hz, taps, if_hz)
+            return
+        self.dtype = np.dtype(np.float32 if sample_component_data_type is None else sample_component_data_type)
         if self.dtype not in _FORMATS:
             raise ValueError(f"unsupported sample component type {self.dtype} (float32, int8, int16, uint8)")
         self._lib = _lib.load()
@@ -58,6 +67,32 @@ class IqFileIngest:
         else:
             rc = self._lib.gyp_ingest_open(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.fs, self.n, self.block_ms,
                                            int(depth), C.byref(self._h))
+        self._check(rc)
+
+    def _open_packed(self, path, samples_per_second, dtype, block_ms, depth, engine, resample_from_hz, taps, if_hz) -> None:
+        if dtype is not None:
+            raise ValueError("a packed recording's words are given by its packing: leave sample_component_data_type out")
+        if engine is None:
+            raise ValueError("packed recordings are unpacked on the device: pass an engine")
+        self.dtype = None
+        self._lib = _lib.load()
+        self.engine = engine
+        self.path = Path(path)
+        self.fs = int(samples_per_second)
+        self.n = self.fs // 1000
+        self.block_ms = int(block_ms)
+        self._h = C.c_void_p()
+        if engine.fs is not None and engine.fs != self.fs:
+            raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({engine.fs})")
+        self.resample_from_hz = self.fs if resample_from_hz is None else int(resample_from_hz)
+        self.if_hz = None if if_hz is None else int(if_hz)
+        if self.packing.real and self.if_hz is None:
+            raise ValueError("a real packing needs if_hz (the recording's intermediate frequency)")
+        if not self.packing.real and self.if_hz is not None:
+            raise ValueError("if_hz is for real packings (an I,Q packing has no intermediate frequency)")
+        self._record = self.packing.record()
+        rc = self._lib.gyp_ingest_open_packed(engine.ctx, str(self.path).encode(), _lib.ptr(self._record), self.resample_from_hz,
+                                              int(self.if_hz or 0), int(taps or 0), self.block_ms, int(depth), C.byref(self._h))
         self._check(rc)
 
     def _check(self, rc: int) -> None:

@@ -29,6 +29,7 @@ class InputFileInfo:
     utc_start_time: datetime.datetime
     sample_component_data_type: Type[np.number]
     if_hz: Optional[int] = None   # not upstream: set for a real-sampled recording with its band at this intermediate frequency
+    packing: Optional[object] = None   # not upstream: a gypsum_amd.packing.Packing for a recording of 1-, 2- or 4-bit packed words
 
     @classmethod
     def gnu_radio_recording(cls, path: Path, sample_rate: int, utc_start_time: datetime.datetime) -> "InputFileInfo":
@@ -85,6 +86,21 @@ class InputFileInfo:
         return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=int(sample_rate),
                    utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=dt.type,
                    if_hz=int(if_hz))
+
+    @classmethod
+    def packed(cls, path: Path, sample_rate: int, packing, if_hz: Optional[int] = None,
+               utc_start_time: Optional[datetime.datetime] = None) -> "InputFileInfo":
+        """1-, 2- or 4-bit words packed into bytes as `packing` (gypsum_amd.packing.Packing) says, at the whole-kHz `sample_rate`
+        (not upstream).  An I,Q packing is read at its own rate if the engine supports it, else resampled; a real packing needs
+        `if_hz` and is down-converted.  Read through `AntennaSampleProviderResampled`, which unpacks it on the device;
+        sample_component_data_type is uint8, the bytes that hold the words."""
+        if packing.real and if_hz is None:
+            raise ValueError("a real packing needs if_hz (the recording's intermediate frequency)")
+        if not packing.real and if_hz is not None:
+            raise ValueError("if_hz is for real packings")
+        return cls(path=Path(path), format=InputFileType.Raw, sdr_sample_rate=int(sample_rate),
+                   utc_start_time=utc_start_time or datetime.datetime.utcfromtimestamp(0), sample_component_data_type=np.uint8,
+                   if_hz=None if if_hz is None else int(if_hz), packing=packing)
 
 
 INPUT_SOURCES: List[InputFileInfo] = []

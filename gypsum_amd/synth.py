@@ -214,3 +214,48 @@ def kat_grid_scene() -> tuple[np.ndarray, int, int]:
         x += 0.02 * np.roll(rep, cp) * np.exp(1j * (2 * np.pi * d * idx / fs + phi))
     x += 0.05 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
     return x.astype(np.complex64), fs, n
+
+
+def write_packed(x: np.ndarray, packing, path, twin_path=None, scale: float | None = None, tail_words: int = 0) -> dict:
+    """Write `x` (complex for an I,Q packing, real for a real one) as a packed recording (gypsum_amd.packing), quantized to the
+    nearest level of x / scale (scale None: the rms of one component, so the words span the levels), plus `tail_words` words of a
+    partial sample at the end (fewer than a sample's words: they are ignored by readers).  With `twin_path`, also write the int8
+    recording of the same file's whole samples: each word its level, so the int8 path on the twin gives the packed path's bits.
+    Returns {"scale", "file_samples", "bytes"}."""
+    from . import packing as pk
+
+    x = np.asarray(x)
+    if scale is None:
+        comp = np.concatenate([x.real.ravel(), x.imag.ravel()]) if np.iscomplexobj(x) else x.ravel()
+        scale = float(np.sqrt(np.mean(comp.astype(np.float64) ** 2))) or 1.0
+    codes = pk.quantize(x, packing, scale)
+    if tail_words:
+        if tail_words >= packing.words_per_sample:
+            raise ValueError("tail_words must be fewer than a sample's words")
+        codes = np.concatenate([codes, np.full(tail_words, (1 << packing.bits) - 1, dtype=np.int64)])
+    data = pk.pack(codes, packing)
+    with open(path, "wb") as f:
+        f.write(data)
+    n = packing.file_samples(len(data))
+    if twin_path is not None:
+        whole = np.zeros(n * packing.words_per_sample, dtype=np.int64)   # the pad bits of the last byte are code 0 words
+        k = min(whole.size, codes.size)
+        whole[:k] = codes[:k]
+        lv = np.asarray(packing.levels)
+        if not np.array_equal(lv, np.rint(lv)) or np.abs(lv).max() > 127:
+            raise ValueError("the int8 twin needs integer levels of magnitude <= 127")
+        lv.astype(np.int8)[whole].tofile(twin_path)
+    return {"scale": scale, "file_samples": n, "bytes": len(data)}
+
+
+def write_packed_scene(scene: SyntheticScene, fs: int, packing, path, twin_path=None, if_hz: int | None = None,
+                       scale: float | None = None) -> dict:
+    """A scene as a packed recording at `fs` (render_at_rate for an I,Q packing; render_real_if at `if_hz` for a real one), plus
+    its int8 twin (write_packed)."""
+    if packing.real:
+        if if_hz is None:
+            raise ValueError("a real packing needs if_hz")
+        x = render_real_if(scene, fs, if_hz)
+    else:
+        x = render_at_rate(scene, fs)
+    return write_packed(x, packing, path, twin_path, scale)

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 205: digital down-converter for real-sampled recordings at an intermediate frequency: gyp_ddc_design, gyp_ddc_iq_dev,
+/* 206: recordings of 1-, 2- or 4-bit words packed into bytes, unpacked on the device: gyp_packing, gyp_packed_span,
+ *      gyp_unpack_iq_dev, gyp_resample_packed_dev, gyp_ingest_open_packed.  Nothing that existed changes.
+ * 205: digital down-converter for real-sampled recordings at an intermediate frequency: gyp_ddc_design, gyp_ddc_iq_dev,
  *      gyp_ingest_open_ddc.  Nothing that existed changes.
  * 204: on-device resampler for recordings at any whole-kHz rate: gyp_resample_design, gyp_resample_iq_dev, gyp_ingest_open_resampled;
  *      gyp_debug_set name resample_tile_samples.  Nothing that existed changes.
@@ -40,7 +42,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 205 /* 0.2.5 */
+#define GYP_VERSION 206 /* 0.2.6 */
 
 enum {
     GYP_OK = 0,
@@ -610,6 +612,61 @@ int gyp_ddc_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_str
  * returns GYP_E_BAD_ARG. */
 int gyp_ingest_open_ddc(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int64_t if_hz, int32_t taps, int32_t block_ms,
                         int32_t depth, gyp_ingest** out);
+
+/* ---------------------------------------------------------------- packed recordings -------------------- */
+/* Dedicated GNSS front ends (MAX2769-class boards) and many published data sets store 1-, 2- or 4-bit words packed into bytes:
+ * files 2-8 times smaller than int8.  They cross PCIe packed and are unpacked on the device, by the kernels that widen words
+ * elsewhere: native-rate I,Q (gyp_unpack_iq_dev), the resampler and the down-converter (gyp_resample_packed_dev).
+ *
+ * Contract.  Word w of the file occupies bits [w * bits, (w + 1) * bits) of the byte stream: byte (w * bits) / 8, and within
+ * that byte the earliest word sits in the most significant bits (GYP_PACK_MSB_FIRST) or in the least (GYP_PACK_LSB_FIRST).
+ * 2-bit MSB-first, byte 0b00011011 holds codes 0, 1, 2, 3 in that order; LSB-first it holds 3, 2, 1, 0.  The value of word w
+ * is levels[code] * scale, one float32 multiply, exactly as (float)word * scale is for the byte-wide formats.  real = 0: words
+ * alternate I, Q and a sample is 2 words; real = 1: one real word per sample at an intermediate frequency.  A sample spans
+ * B = bits * (2 - real) bits, which divide 8, so no sample straddles a byte.  file_samples = floor(8 * size / B): the
+ * trailing bits of a partial sample are ignored.  The file's milliseconds follow gyp_ingest_open's rule counted in samples,
+ * total_ms = (file_samples - 1) / N_in, which equals (size - 1) / ms_bytes of the int8 file holding the same words.
+ * Millisecond and block edges need not fall on byte boundaries: a buffer starts bit0 bits into its first byte (bit0 a
+ * multiple of B below 8), and samples outside the buffer's raw_n_samples, or outside the file, are zero by index -- never
+ * the level of a zero-filled byte (code 0 is +1 under sign-magnitude).  With those values, packed results are bit-identical to
+ * the int8 path on a file whose words are the levels. */
+#define GYP_PACK_MSB_FIRST 0   /* the earliest word of a byte sits in its most significant bits */
+#define GYP_PACK_LSB_FIRST 1
+typedef struct gyp_packing {
+    int32_t bits;       /* 1, 2 or 4 bits per word */
+    int32_t real;       /* 0: words alternate I, Q (a sample = 2 words); 1: one real word per sample (IF recordings) */
+    int32_t order;      /* GYP_PACK_MSB_FIRST / GYP_PACK_LSB_FIRST */
+    int32_t reserved;   /* must be 0 */
+    float levels[16];   /* value of code c, 0 <= c < 2^bits, before scale; finite; entries >= 2^bits ignored */
+} gyp_packing;
+/* Host only (no GPU): where samples first_sample .. first_sample + n_samples - 1 (first_sample may be negative) lie in a file
+ * of file_bytes bytes.  Only the part inside [0, file_samples) is read: *in_first_out / *in_n_out are that part (in_n 0 if none),
+ * and *first_byte_out, *bit0_out, *n_bytes_out the bytes that cover it and the bit offset of its first sample in the first
+ * byte.  *file_samples_out and *total_ms_out (samples_per_ms = N_in) follow the contract.  Any output may be NULL.  The ingest
+ * reads exactly these bytes.  GYP_E_BAD_ARG for an invalid packing, n_samples < 0, file_bytes < 0 or samples_per_ms < 1. */
+int gyp_packed_span(const gyp_packing* packing, int32_t samples_per_ms, int64_t file_bytes, int64_t first_sample, int64_t n_samples,
+                    int64_t* in_first_out, int64_t* in_n_out, int64_t* first_byte_out, int32_t* bit0_out, int64_t* n_bytes_out,
+                    int64_t* file_samples_out, int64_t* total_ms_out);
+/* Packed I,Q words (real = 0 only) -> complex64 at their own rate, on the context's stream.  Stream s starts at byte
+ * raw_dev + s * in_stride_bytes, its sample 0 bit0 bits into that byte; n_samples samples are written per stream, stream s at
+ * out_dev + s * out_stride_samples.  in_stride_bytes must hold bit0 + n_samples * B bits.  Equal, bit for bit, to
+ * gyp_widen_iq_dev on the int8 words holding the levels. */
+int gyp_unpack_iq_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_dev, int32_t n_streams, int64_t in_stride_bytes,
+                      int32_t bit0, int64_t n_samples, float scale, int64_t out_stride_samples, float* out_dev);
+/* gyp_resample_iq_dev (real = 0, if_hz must be 0) or gyp_ddc_iq_dev (real = 1, if_hz required) on packed words: the packing in
+ * place of fmt, strides in bytes, and the bit offset of the buffer's sample 0 (raw_first_sample) in its first byte.  Same rate,
+ * tap and error rules, same cached designs, bit-identical to the int8 path on the words holding the levels. */
+int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_dev, int32_t n_streams, int64_t in_stride_bytes,
+                            int32_t bit0, int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t fs_in_hz, int64_t if_hz,
+                            int32_t taps, int64_t first_ms, int32_t n_ms, int64_t out_stride_samples, float* out_dev);
+/* An ingest handle over a packed recording (ctx required).  I,Q at the context's rate: unpacked only (taps ignored); I,Q at another
+ * whole-kHz rate: resampled; real: down-converted, if_hz required (and 0 for I,Q).  The reader preads the bytes that cover each
+ * block's samples (gyp_packed_span) and the upload stream unpacks them; there is no repacking on the host.  total_ms follows
+ * the contract; times, set_scale, seek, next_dev and close keep their meaning; gyp_ingest_next_host returns GYP_E_BAD_ARG.
+ * GYP_E_BAD_ARG for bits not 1, 2 or 4, reserved != 0, an unknown order, a non-finite level, real without if_hz or I,Q with one;
+ * the rate rules return GYP_E_BAD_RATE as for the other handles. */
+int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* packing, int64_t fs_in_hz, int64_t if_hz, int32_t taps,
+                           int32_t block_ms, int32_t depth, gyp_ingest** out);
 
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
