@@ -130,6 +130,7 @@ struct gyp_ctx {
     int track_chunk_ms = 250;     // gyp_debug_set("track_chunk_ms"): the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
     float symbol_tau = 1e-4f;     // gyp_debug_set("symbol_tau"): |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
     bool no_shared_fwd = false;   // gyp_debug_set("no_shared_fwd"): A/B switch: flat grids transform every cell's rows themselves again
+    bool no_acq_shared_fwd = false;   // gyp_debug_set("no_acq_shared_fwd"): A/B switch: acquisition levels transform every cell's rows themselves again
     int cells_cu_reserve = 0;     // gyp_debug_set("cells_cu_reserve", n): CUs the correlation-cell launches leave free (see launch_cells)
     int last_grid_refined_rows = 0;   // gyp_debug_get("last_grid_refined_rows"): rows the last gyp_grid_best_bins_refined_dev call decided in float64
     int last_grid_path = 0;       // gyp_debug_get("last_grid_path"): which cells kernel the last gyp_correlate_grid* call took (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
@@ -174,7 +175,7 @@ struct gyp_ctx {
     int track_launches = 0;     // launches of the tracking kernel behind the last timed call   // the events below have been recorded since timing was switched on (the speculative path records none)
     hipEvent_t ev_track[4] = {nullptr, nullptr, nullptr, nullptr};
     // growable scratch for the host-buffer entry points and the acquisition driver
-    static constexpr int kScratchSlots = 11;
+    static constexpr int kScratchSlots = 13;
     void* scratch[kScratchSlots] = {};
     size_t scratch_cap[kScratchSlots] = {};
 };
@@ -612,6 +613,16 @@ static int launch_cells(gyp_ctx* ctx, const CellsParams& p, int integration) {
     return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
 }
 
+// A level's shared forward transforms (acquire_search): MODE 1 over the units, then MODE 2 over their cells.  Both walk device-side work
+// lists with a persistent grid of one workgroup per CU, like the unshared pipelined launch.
+static int launch_cells_shared(gyp_ctx* ctx, const CellsParams& p_units, const CellsParams& p_cells) {
+    const int cus = std::max(ctx->n_xcd, ctx->n_cus - ctx->cells_cu_reserve);
+    const int grid1 = std::max(1, std::min(p_cells.n_cells, cus) & ~7);
+    int rc = launch_k(ctx, corr_cells_pipe_kernel<8, false, 1>, 8, grid1, p_units, lds_bytes_pipe<8>());
+    if (rc) return rc;
+    return launch_k(ctx, corr_cells_pipe_kernel<8, false, 2>, 8, grid1, p_cells, lds_bytes_pipe<8>());
+}
+
 static int launch_track_step(gyp_ctx* ctx, const TrackStepParams& p) {
     const int grid = std::max(1, std::min(p.n_chan, ctx->n_cus * blocks_per_cu(ctx->k)) & ~7);
     switch (ctx->k) {
@@ -718,14 +729,8 @@ extern "C" {
 // ---------------------------------------------------------------- correlation cells ----------------------
 }   // extern "C"
 // order_dev / n_active_dev: optional work list of the acquisition driver (see CellsParams)
-static int correlate_cells_listed(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
-                                  const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
-                                  gyp_cell* out_dev, float* profile_out_dev, const int32_t* order_dev, const int32_t* n_active_dev) {
-    if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    if (!iq_dev || !cells_dev || !out_dev || n_ms < 0 || n_cells < 0 || (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells_dev: bad argument");
-    if (n_cells == 0) return GYP_OK;
+static CellsParams cells_params(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms, const gyp_cell_desc* cells_dev,
+                                int32_t n_cells, gyp_cell* out_dev, float* profile_out_dev, const int32_t* order_dev, const int32_t* n_active_dev) {
     CellsParams p;
     p.iq = reinterpret_cast<const cf*>(iq_dev);
     p.stream_stride = stream_stride_samples;
@@ -741,7 +746,20 @@ static int correlate_cells_listed(gyp_ctx* ctx, const float* iq_dev, int64_t str
     p.prof_wave = std::min(ctx->prof_wave, 7);
     p.order = order_dev;
     p.n_active = n_active_dev;
-    return launch_cells(ctx, p, integration);
+    p.spectra = nullptr;
+    p.unit_of = nullptr;
+    return p;
+}
+static int correlate_cells_listed(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
+                                  const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
+                                  gyp_cell* out_dev, float* profile_out_dev, const int32_t* order_dev, const int32_t* n_active_dev) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (!iq_dev || !cells_dev || !out_dev || n_ms < 0 || n_cells < 0 || (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells_dev: bad argument");
+    if (n_cells == 0) return GYP_OK;
+    return launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, n_ms, cells_dev, n_cells, out_dev, profile_out_dev, order_dev,
+                                          n_active_dev), integration);
 }
 extern "C" {
 int gyp_correlate_cells_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
@@ -1066,6 +1084,29 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
     AcqSearchState* d_states = (AcqSearchState*)ctx->scratch[4];
     gyp_cell_desc* d_cells = (gyp_cell_desc*)ctx->scratch[1];
     gyp_cell* d_out = (gyp_cell*)ctx->scratch[2];
+    // Shared forward transforms (K == 8, the pipelined path): the first three levels of a scan put every satellite of a stream on the
+    // same Doppler bins -- range(-7000, 7000, 700) for all at level 1, multiples of 350 and 175 Hz at levels 2 and 3 -- so the
+    // wipe-off and the 8 forward transforms of a (stream, bin) unit are run once (corr_cells_pipe_kernel MODE 1) and read back by
+    // each of its satellites (MODE 2).  From level 4 on every satellite has a grid of its own: no unit to speak of.  The spectra
+    // take 128 KiB per unit-millisecond: room for 3 * kMaxBins units per stream (level 3 needs ~70 at most), capped at 1 GiB; units
+    // beyond the room stay on the unshared kernel.
+    const bool can_share = ctx->k == 8 && !ctx->no_pipe && !ctx->no_acq_shared_fwd;
+    AcqUnits units = {};
+    cf* d_spectra = nullptr;
+    if (can_share) {
+        const size_t unit_bytes = (size_t)n_ms * kSpecUnitMs * sizeof(cf);
+        const size_t want = std::min<size_t>((size_t)1 << 30, (size_t)n_streams * 3 * kMaxBins * unit_bytes);
+        units.max_units = (int32_t)std::min<size_t>(n_cells, want / unit_bytes);
+        if (units.max_units > 0) {
+            if ((rc = ensure_scratch(ctx, 11, (size_t)units.max_units * unit_bytes))) return rc;
+            if ((rc = ensure_scratch(ctx, 12, ((size_t)units.max_units + 2 * n_cells + 4) * sizeof(int32_t)))) return rc;
+            d_spectra = (cf*)ctx->scratch[11];
+            units.unit_cell = (int32_t*)ctx->scratch[12];
+            units.sh_cell = units.unit_cell + units.max_units;
+            units.sh_unit = units.sh_cell + n_cells;
+            units.counts = units.sh_unit + n_cells;
+        }
+    }
     const int tpb = 64, nblk = (n_states + tpb - 1) / tpb;
     {
         AcqSatList sl;
@@ -1075,7 +1116,22 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
     for (double spread = spread0; single_level ? spread == spread0 : spread >= ctx->params.acq_min_spread_hz; spread /= 2.0) {  // acquisition.py:81,89
         hipLaunchKernelGGL(acq_plan_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_cells, d_reuse, ctx->params.acq_bins_per_spread,
                            ctx->params.acq_reuse_level_records != 0.0 ? 1 : 0);
-        hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand);
+        const bool shared = d_spectra && spread * 4.0 >= ctx->params.acq_initial_spread_hz;   // levels 1-3 of a scan
+        if (shared) {
+            hipLaunchKernelGGL(acq_compact_units_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells,
+                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units);
+            CellsParams pu = cells_params(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, d_out, nullptr, units.unit_cell,
+                                          units.counts);
+            pu.prof = nullptr;
+            pu.spectra = d_spectra;
+            CellsParams pc = pu;
+            pc.order = units.sh_cell;
+            pc.n_active = units.counts + 1;
+            pc.unit_of = units.sh_unit;
+            if ((rc = launch_cells_shared(ctx, pu, pc))) return rc;
+        } else {
+            hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand);
+        }
         rc = correlate_cells_listed(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, GYP_NON_COHERENT, d_out, nullptr,
                                     d_order, d_n_active);
         if (rc) return rc;
@@ -1139,7 +1195,7 @@ static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
         if (gyp_set_stream_format(h, ctx->fs, ctx->n) != GYP_OK) return nullptr;
     h->params = ctx->params;
     // the helper runs under the caller's switches (it never read an environment of its own)
-    h->no_pipe = ctx->no_pipe; h->no_shared_fwd = ctx->no_shared_fwd; h->symbol_tau = ctx->symbol_tau; h->cells_cu_reserve = ctx->cells_cu_reserve;
+    h->no_pipe = ctx->no_pipe; h->no_shared_fwd = ctx->no_shared_fwd; h->no_acq_shared_fwd = ctx->no_acq_shared_fwd; h->symbol_tau = ctx->symbol_tau; h->cells_cu_reserve = ctx->cells_cu_reserve;
     h->track_chunk_ms = ctx->track_chunk_ms; h->no_spec = ctx->no_spec;
     return h;
 }
@@ -2008,7 +2064,7 @@ int gyp_synth_iq_dev(gyp_ctx* ctx, float* out_dev, int32_t n_streams, int64_t st
 namespace {
 struct DebugKnob { const char* name; double lo, hi; bool integral; };
 const DebugKnob kDebugKnobs[] = {
-    {"no_pipe", 0, 1, true}, {"no_shared_fwd", 0, 1, true}, {"no_acq_split", 0, 1, true}, {"no_spec", 0, 1, true},
+    {"no_pipe", 0, 1, true}, {"no_shared_fwd", 0, 1, true}, {"no_acq_shared_fwd", 0, 1, true}, {"no_acq_split", 0, 1, true}, {"no_spec", 0, 1, true},
     {"spec_debug", 0, 1, true}, {"acq_lanes", 1, gyp_ctx::kMaxAcqLanes, true}, {"track_chunk_ms", 0, 1e6, true}, {"widen_wg_per_cu", 1, 8, true},
     {"symbol_tau", 0, 100, false}, {"dll_prov_bias", -1e6, 1e6, false}, {"spec_fail_at", -1, 2147483647.0, true},
     {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"exact_prefetch", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
@@ -2021,6 +2077,7 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
 #define GYP_KNOB_NUM(N, FIELD, T) if (is(N)) { if (set) ctx->FIELD = (T)v; else *out = (double)ctx->FIELD; return GYP_OK; }
     GYP_KNOB_BOOL("no_pipe", no_pipe)
     GYP_KNOB_BOOL("no_shared_fwd", no_shared_fwd)
+    GYP_KNOB_BOOL("no_acq_shared_fwd", no_acq_shared_fwd)
     GYP_KNOB_BOOL("no_grid_parts", no_grid_parts)
     GYP_KNOB_BOOL("no_grid_fused", no_grid_fused)
     GYP_KNOB_NUM("grid_fused_waves", grid_fused_waves, int)

@@ -1,6 +1,7 @@
 // kernels_acq.hpp -- acquisition bookkeeping on the device (acquisition.py:70-152).
 // A part of kernels.hpp (which lists every kernel); the parts build on each other in the order kernels.hpp includes them.
 #pragma once
+#include <climits>
 #include "kernels_dll_exact.hpp"
 
 namespace gyp {
@@ -95,6 +96,98 @@ __global__ __launch_bounds__(1024) void acq_compact_kernel(const gyp_cell_desc* 
     }
     if (threadIdx.x == 0) { *n_active = base; *n_cand = 0; n_cand[1] = 0; }   // n_cand[1]: the level's pending-pair count
 }
+// Exclusive prefix sum of v over the 1024 threads of a workgroup (thread order); *total = the sum over all of them.
+__device__ __forceinline__ int block_excl_scan_1024(int v, int* wave_tot, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wave_tot[wave] = x;
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < 16; ++w) { off += w < wave ? wave_tot[w] : 0; tot += wave_tot[w]; }
+    __syncthreads();   // wave_tot is free again
+    *total = tot;
+    return off + x - v;
+}
+
+// acq_compact_kernel for a level whose forward transforms are shared (gyp_ctx::no_acq_shared_fwd, K == 8): the level's active cells
+// grouped by exact (stream, Doppler) equality -- the plan's Doppler values are integers -- into units.  A unit of >= 2 cells gets ONE
+// forward pass (corr_cells_pipe_kernel MODE 1) and its cells are listed for the consumer (MODE 2), grouped by unit so that the
+// consumers of a unit run side by side on one XCD; every other active cell goes to the work list of the unshared kernel as before.
+// Units are numbered in the order of their first cell; those beyond max_units (the spectra buffer's capacity) stay unshared.
+// The cells of a stream are contiguous (state = stream * n_sats + satellite, kMaxBins cells each), at most 32 * 28 = 896 of them:
+// one thread per cell and an LDS hash table of the stream's Doppler values, one stream after the other.
+struct AcqUnits {
+    int32_t* unit_cell;   // [unit]: the first cell of the unit (its stream and Doppler are the unit's)
+    int32_t* sh_cell;     // [n_shared]: the cells of the shared units, unit after unit
+    int32_t* sh_unit;     // [n_shared]: the unit of sh_cell[i]
+    int32_t* counts;      // [0] units, [1] shared cells
+    int32_t max_units;
+};
+constexpr int kUnitHash = 2048;
+__global__ __launch_bounds__(1024) void acq_compact_units_kernel(const gyp_cell_desc* __restrict__ cells, int n_cells, int cells_per_stream,
+                                                                 int32_t* order, int32_t* n_active, int32_t* n_cand, AcqUnits u) {
+    __shared__ int key[kUnitHash], first[kUnitHash], cnt[kUnitHash], uid[kUnitHash], fill[kUnitHash];
+    __shared__ int wave_tot[16];
+    int pipe_base = 0, unit_base = 0, shared_base = 0;   // (uniform: every thread adds the same totals)
+    const int t = threadIdx.x;
+    for (int s0 = 0; s0 < n_cells; s0 += cells_per_stream) {
+        for (int i = t; i < kUnitHash; i += 1024) { key[i] = INT_MIN; first[i] = INT_MAX; cnt[i] = 0; fill[i] = 0; }
+        __syncthreads();
+        const int c = s0 + t;
+        bool on = false;
+        int dop = 0, slot = -1;
+        if (t < cells_per_stream && c < n_cells) {
+            const gyp_cell_desc d = cells[c];
+            on = d.sat_id >= 1 && d.sat_id <= 32 && d.reserved != kCellSkip;
+            dop = (int)d.doppler_hz;
+        }
+        if (on) {
+            int hsh = (int)(((unsigned)dop * 2654435761u) >> 21) & (kUnitHash - 1);
+            for (;;) {   // at most 896 keys in 2048 slots: a free or matching slot is always found
+                const int prev = atomicCAS(&key[hsh], INT_MIN, dop);
+                if (prev == INT_MIN || prev == dop) break;
+                hsh = (hsh + 1) & (kUnitHash - 1);
+            }
+            slot = hsh;
+            atomicMin(&first[slot], t);
+            atomicAdd(&cnt[slot], 1);
+        }
+        __syncthreads();
+        const bool multi = on && cnt[slot] >= 2;
+        const bool lead = multi && first[slot] == t;
+        int n_lead;
+        const int my_unit = unit_base + block_excl_scan_1024(lead ? 1 : 0, wave_tot, &n_lead);
+        const bool lead_ok = lead && my_unit < u.max_units;
+        int n_sh;
+        const int my_ofs = shared_base + block_excl_scan_1024(lead_ok ? cnt[slot] : 0, wave_tot, &n_sh);
+        if (lead) uid[slot] = lead_ok ? my_unit : -1;
+        if (lead_ok) { first[slot] = my_ofs; u.unit_cell[my_unit] = c; }   // first[]: from here on the unit's offset in the shared list
+        __syncthreads();
+        const bool share = multi && uid[slot] >= 0;
+        if (share) {
+            const int pos = first[slot] + atomicAdd(&fill[slot], 1);   // (the order within a unit is free: it moves no result)
+            u.sh_cell[pos] = c;
+            u.sh_unit[pos] = uid[slot];
+        }
+        int n_pipe;
+        const int my_pipe = block_excl_scan_1024(on && !share ? 1 : 0, wave_tot, &n_pipe);
+        if (on && !share) order[pipe_base + my_pipe] = c;
+        pipe_base += n_pipe;
+        unit_base += min(n_lead, max(0, u.max_units - unit_base));
+        shared_base += n_sh;
+        __syncthreads();   // every read of the table precedes the next stream's reset
+    }
+    if (t == 0) {
+        *n_active = pipe_base; *n_cand = 0; n_cand[1] = 0;   // as acq_compact_kernel
+        u.counts[0] = unit_base; u.counts[1] = shared_base;
+    }
+}
+
 // out[i][b] <- the previous level's record of the same bin; then the level's records become "the previous level's".
 // Also the work list of the float64 tie-break (acq_refine_kernel): the bins whose peak is within kTieBand of the level's
 // maximum -- the top bin always -- are appended to `cand` (*n_cand was zeroed by acq_compact_kernel); every other bin's

@@ -26,6 +26,11 @@ struct CellsParams {
     // workgroups every time (half of them idle through levels 2 and 3), the compacted list spreads what is left evenly.
     const int32_t* order;
     const int32_t* n_active;
+    // shared forward transforms (acquisition levels 1-3 at K == 8, corr_cells_pipe_kernel MODE 1 / 2): the 8 branch spectra of a
+    // (stream, Doppler) unit, [unit][ms][branch][32 registers][64 lanes] complex -- the layout of the replica table -- and, for the
+    // consumer, the unit each entry of `order` reads (unit_of[w] belongs to order[w])
+    cf* spectra;
+    const int32_t* unit_of;
 };
 __device__ __forceinline__ int cells_work(const CellsParams& p) { return p.order ? *p.n_active : p.n_cells; }
 __device__ __forceinline__ int cells_pick(const CellsParams& p, int v, int n_work) {
@@ -124,7 +129,83 @@ __global__ __launch_bounds__(Geom<K>::kThreads, Geom<K>::kMinWavesPerSimd) void 
 template <int K>
 constexpr int lds_bytes_pipe() { return 2 * kTablesBytes + 2 * Geom<K>::W * kXchWaveBytes + kRedBytes + 2 * kHaloBytes; }
 
-template <int K, bool PROF>
+// The statistics of a pipelined cell's profile and its record (MODE 0 and 2 of corr_cells_pipe_kernel).
+template <int K>
+__device__ __forceinline__ void pipe_finish_cell(const CellsParams& p, const float (&mag)[16], int cell, const Smem& sm, int tid) {
+    constexpr int N = K * kChips;
+    LaneStats ls = lane_stats_init();
+    lane_stats_update<K, false>(ls, mag, nullptr, 0, tid, [](int idx) { return idx; });
+    if (p.profile_out) {
+        const int base = lag_base<K>(tid, 0);
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (slot_valid(j, tid)) p.profile_out[(int64_t)cell * N + base + 32 * K * j] = mag[j];
+    }
+    const ProfileStats st = lane_stats_finish<K>(ls, sm.red, tid);
+    if (threadIdx.x == 0) {
+        gyp_cell* o = p.out + cell;
+        o->peak = st.best.v;
+        o->argmax = st.best.key;
+        o->sum = st.sum;
+        o->n_max = st.n_max;
+        o->reserved = 0;
+        o->tap_re = 0.f;
+        o->tap_im = 0.f;
+    }
+}
+
+constexpr int kSpecUnitMs = 8 * 32 * 64;   // complex values of one unit-millisecond's branch spectra (K == 8): 128 KiB
+
+// MODE 2 of corr_cells_pipe_kernel: one cell from its unit's stored spectra.  Registers: the replica (64), the spectrum being
+// inverted (64), the inverse's output (32) and the running profile (16); the staging registers of MODE 0 (the samples in flight,
+// 32) are not needed.  The 32 loads of a millisecond are issued together and waited for once; each wavefront walks its own branch
+// and transposes in its own tile of buffer 0, so nothing but the reduction at the end synchronises the workgroup.
+template <int K>
+__device__ __forceinline__ void pipe_consume_cell(const CellsParams& p, const gyp_cell_desc& d, int cell, int unit, const Smem& sm,
+                                                  const LdsTables& tables) {
+    constexpr int W = Geom<K>::W;
+    static_assert(W * 32 * 64 == kSpecUnitMs, "spectra layout: 8 branches of 2048 bins");
+    const int tid = launder(threadIdx.x);
+    const int wave = tid >> 6, lane = tid & 63, l = lane & 31, h = lane >> 5;
+    const cf* rep = replica_of(p.replica_table, d.sat_id - 1);
+    cf prn[32];
+    {
+        const cf* row = rep + launder(lane);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) prn[i] = row[64 * i];
+    }
+    float mag[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) mag[j] = 0.f;
+    float* tile_half = reinterpret_cast<float*>(sm.xch + wave * kXchWave) + h * kXchTile;
+    const cf* spec = p.spectra + ((int64_t)unit * p.n_ms * W + wave) * (32 * 64);
+#pragma unroll 1
+    for (int ms = 0; ms < p.n_ms; ++ms) {
+        const cf* src = spec + (int64_t)ms * kSpecUnitMs + launder(lane);
+        cf x[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) x[i] = src[64 * i];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) x[i] = cmul(x[i], prn[i]);
+        pin_values(x);
+        __builtin_amdgcn_sched_barrier(0);
+        cf c[16];
+        wave_fft_inv<16>(x, c, tile_half, tables, l, h);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) mag[j] += __builtin_amdgcn_sqrtf(fmaf(c[j].x, c[j].x, c[j].y * c[j].y));
+    }
+    pipe_finish_cell<K>(p, mag, cell, sm, tid);
+    __syncthreads();   // the reduction scratch is read by every wavefront before the next cell's statistics overwrite it
+}
+
+// MODE 1 and 2 split a cell's work where acquisition levels share it (the first levels of a scan put every satellite of a stream on the
+// same Doppler bins): MODE 1, one work item per (stream, Doppler) unit -- order[] lists a cell of each unit -- runs the same staging
+// and forward transforms as MODE 0 and stores the 8 branch spectra of every millisecond (kSpecUnitMs complex per unit-ms) instead of
+// multiplying and inverting them; MODE 2, one work item per cell of a unit, reads those spectra back (from the L2 of its XCD: the
+// work order puts a unit's satellites on neighbouring workgroups of one XCD) and runs only the replica multiply, the inverse and
+// the statistics.  The stored spectra are the values MODE 0 multiplies, so every record is bit-identical.  MODE 2's wavefronts
+// share nothing but the reduction scratch: no barrier per millisecond; the two wavefronts of each SIMD cover each other's loads.
+template <int K, bool PROF, int MODE = 0>
 __global__ __launch_bounds__(Geom<K>::kThreads, 2) void corr_cells_pipe_kernel(CellsParams p) {
     static_assert(Geom<K>::R == 1, "pipelined cells need all K branches resident");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -146,10 +227,15 @@ __global__ __launch_bounds__(Geom<K>::kThreads, 2) void corr_cells_pipe_kernel(C
 #define GYP_TICK(var) const long long var = PROF ? (long long)__builtin_readcyclecounter() : 0
     const int n_work = cells_work(p);
     for (int v = blockIdx.x; v < n_work; v += gridDim.x) {
-        const int cell = cells_pick(p, v, n_work);
+        const int w_item = xcd_contiguous(v, n_work);
+        const int cell = p.order ? p.order[w_item] : w_item;
         const gyp_cell_desc d = p.cells[cell];
         // padding cell, or (acquisition driver's work list only: gyp_cell_desc::reserved is the caller's otherwise) a cached one
         if (d.sat_id < 1 || d.sat_id > 32 || (p.order && d.reserved == kCellSkip)) continue;   // uniform across the workgroup
+        if constexpr (MODE == 2) {
+            pipe_consume_cell<K>(p, d, cell, p.unit_of[w_item], sm, tables);
+            continue;
+        }
         const cf* rep = replica_of(p.replica_table, d.sat_id - 1);
         const double du = d.doppler_hz * p.inv_fs;
         const CarrierSteps cs = carrier_steps<K>(du);
@@ -163,7 +249,7 @@ __global__ __launch_bounds__(Geom<K>::kThreads, 2) void corr_cells_pipe_kernel(C
         // This satellite's replica spectrum stays in registers for all the cell's blocks: re-reading it every
         // millisecond cost 4 exposed L2 latencies (the sample stream flushes it out of L1), 26 % of the iteration.
         cf prn[32];
-        {
+        if constexpr (MODE == 0) {
             const cf* row = rep + launder(lane);
 #pragma unroll
             for (int i = 0; i < 32; ++i) prn[i] = row[64 * i];
@@ -202,6 +288,14 @@ __global__ __launch_bounds__(Geom<K>::kThreads, 2) void corr_cells_pipe_kernel(C
             cf c[16];
             wave_fft_fwd<16>(x, tile_half, tables, l, h);   // 256 VGPRs: twiddle batches of 16
             GYP_TICK(t_c);
+            if constexpr (MODE == 1) {   // the unit's spectra: stored as the replica multiply below would read them
+                cf* dst = p.spectra + (((int64_t)w_item * p.n_ms + ms) * W + wave) * (32 * 64) + lane;
+#pragma unroll
+                for (int i = 0; i < 32; ++i) dst[64 * i] = x[i];
+                if (ms + 2 < p.n_ms) stage_fetch_own<K>(stream + (int64_t)(ms + 2) * N, smp, launder(tid));
+                __syncthreads();
+                continue;
+            }
 #pragma unroll
             for (int i = 0; i < 32; ++i) x[i] = cmul(x[i], prn[i]);
             pin_values(x);
@@ -223,25 +317,7 @@ __global__ __launch_bounds__(Geom<K>::kThreads, 2) void corr_cells_pipe_kernel(C
                 tp[0] += t_b - t_a; tp[1] += t_c - t_b; tp[2] += t_d - t_c; tp[3] += t_e - t_d; tp[4] += t_f - t_e; tp[5] += 1;
             }
         }
-        LaneStats ls = lane_stats_init();
-        lane_stats_update<K, false>(ls, mag, nullptr, 0, tid, [](int idx) { return idx; });
-        if (p.profile_out) {
-            const int base = lag_base<K>(tid, 0);
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (slot_valid(j, tid)) p.profile_out[(int64_t)cell * N + base + 32 * K * j] = mag[j];
-        }
-        const ProfileStats st = lane_stats_finish<K>(ls, sm.red, tid);
-        if (threadIdx.x == 0) {
-            gyp_cell* o = p.out + cell;
-            o->peak = st.best.v;
-            o->argmax = st.best.key;
-            o->sum = st.sum;
-            o->n_max = st.n_max;
-            o->reserved = 0;
-            o->tap_re = 0.f;
-            o->tap_im = 0.f;
-        }
+        if constexpr (MODE == 0) pipe_finish_cell<K>(p, mag, cell, sm, tid);
     }
 #undef GYP_TICK
     if (prof) for (int i = 0; i < 8; ++i) p.prof[i] = tp[i];

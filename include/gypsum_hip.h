@@ -673,6 +673,9 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
  * with a message otherwise) and defaults:
  *   "no_pipe" 0/1 (0)           the two-workgroups-per-CU cells kernel instead of the pipelined one; no speculative tracker
  *   "no_shared_fwd" 0/1 (0)     flat grids transform every cell's rows themselves
+ *   "no_acq_shared_fwd" 0/1 (0) acquisition levels 1-3 at 8 samples per chip transform every cell's rows themselves (default: one
+ *                               forward pass per (stream, Doppler bin) shared by the satellites on that bin; same records); the helper
+ *                               contexts of a split scan inherit it
  *   "no_grid_parts" 0/1 (0)     flat-grid work items take whole (unit, satellite group)s even where that leaves the last round of a
  *                               launch partly empty (default: a unit's polyphase branches are cut into runs, merged afterwards)
  *   "no_grid_fused" 0/1 (0)     flat grids that fill the chip (<= 8 samples per chip, single block) fold into rows in HBM first (r05's
