@@ -133,6 +133,9 @@ struct gyp_ctx {
     bool no_acq_shared_fwd = false;   // gyp_debug_set("no_acq_shared_fwd"): A/B switch: acquisition levels transform every cell's rows themselves again
     int cells_cu_reserve = 0;     // gyp_debug_set("cells_cu_reserve", n): CUs the correlation-cell launches leave free (see launch_cells)
     int last_grid_refined_rows = 0;   // gyp_debug_get("last_grid_refined_rows"): rows the last gyp_grid_best_bins_refined_dev call decided in float64
+    int32_t* d_acq_witness = nullptr;   // [kAcqWitnessInts] gyp_debug_get("last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells", and "..._l<k>" per level): what the levels of
+                                        // the last search on this context did (acq_init_kernel zeroes, the compact kernels add; read on request only)
+    int acq_witness_lanes = 1;          // parts of that search: this context and the first acq_witness_lanes - 1 helpers
     int last_grid_path = 0;       // gyp_debug_get("last_grid_path"): which cells kernel the last gyp_correlate_grid* call took (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
     int grid_fused_waves = 12;    // gyp_debug_set("grid_fused_waves"): 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
     bool no_grid_fused = false;   // gyp_debug_set("no_grid_fused"): A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
@@ -376,6 +379,10 @@ int gyp_create(int device_ordinal, gyp_ctx** out) {
         return fail(nullptr, GYP_E_HIP, "stream/event creation failed");
     }
     ctx->stream = ctx->own_stream;
+    if (hipMalloc((void**)&ctx->d_acq_witness, kAcqWitnessInts * sizeof(int32_t)) != hipSuccess || hipMemset(ctx->d_acq_witness, 0, kAcqWitnessInts * sizeof(int32_t)) != hipSuccess) {
+        gyp_destroy(ctx);
+        return fail(nullptr, GYP_E_HIP, "gyp_create: no device memory for the acquisition counters");
+    }
     *out = ctx;
     return GYP_OK;
 }
@@ -395,6 +402,7 @@ void gyp_destroy(gyp_ctx* ctx) {
     if (ctx->d_ntrans) (void)hipFree(ctx->d_ntrans);
     if (ctx->d_chipf) (void)hipFree(ctx->d_chipf);
     if (ctx->d_prof) (void)hipFree(ctx->d_prof);
+    if (ctx->d_acq_witness) (void)hipFree(ctx->d_acq_witness);
     for (auto& d : ctx->resample_designs) if (d.d_taps) (void)hipFree(d.d_taps);
     for (auto& l : ctx->packed_levels) (void)hipFree(l.second);
     for (int i = 0; i < 4; ++i) if (ctx->ev_track[i]) (void)hipEventDestroy(ctx->ev_track[i]);
@@ -1111,15 +1119,17 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
     {
         AcqSatList sl;
         for (int i = 0; i < 32; ++i) sl.id[i] = i < n_sats ? sat_ids_host[i] : 0;
-        hipLaunchKernelGGL(acq_init_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, n_sats, sl, center0, spread0);   // acquisition.py:78-79
+        hipLaunchKernelGGL(acq_init_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, n_sats, sl, center0, spread0,
+                           ctx->d_acq_witness);   // acquisition.py:78-79
     }
-    for (double spread = spread0; single_level ? spread == spread0 : spread >= ctx->params.acq_min_spread_hz; spread /= 2.0) {  // acquisition.py:81,89
+    int level = 0;
+    for (double spread = spread0; single_level ? spread == spread0 : spread >= ctx->params.acq_min_spread_hz; spread /= 2.0, ++level) {  // acquisition.py:81,89
         hipLaunchKernelGGL(acq_plan_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_cells, d_reuse, ctx->params.acq_bins_per_spread,
                            ctx->params.acq_reuse_level_records != 0.0 ? 1 : 0);
         const bool shared = d_spectra && spread * 4.0 >= ctx->params.acq_initial_spread_hz;   // levels 1-3 of a scan
         if (shared) {
             hipLaunchKernelGGL(acq_compact_units_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells,
-                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units);
+                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units, ctx->d_acq_witness, level);
             CellsParams pu = cells_params(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, d_out, nullptr, units.unit_cell,
                                           units.counts);
             pu.prof = nullptr;
@@ -1130,7 +1140,8 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
             pc.unit_of = units.sh_unit;
             if ((rc = launch_cells_shared(ctx, pu, pc))) return rc;
         } else {
-            hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand);
+            hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand,
+                               ctx->d_acq_witness, level);
         }
         rc = correlate_cells_listed(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, GYP_NON_COHERENT, d_out, nullptr,
                                     d_order, d_n_active);
@@ -1208,6 +1219,7 @@ int gyp_acquire_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_
     gyp_ctx* lane_ctx[gyp_ctx::kMaxAcqLanes] = {ctx};
     for (int i = 1; i < lanes; ++i)
         if (!(lane_ctx[i] = acquire_helper(ctx, i - 1))) { lanes = 1; break; }
+    ctx->acq_witness_lanes = lanes;
     if (lanes == 1)
         return acquire_search(ctx, iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, 0.0,
                               ctx->params.acq_initial_spread_hz, false, out_dev);
@@ -1242,6 +1254,7 @@ int gyp_search_level_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, i
     const int step = (int)(spread_hz / ctx->params.acq_bins_per_spread);
     if (!(spread_hz > 0) || step < 1 || ((int)(center_hz + spread_hz) - (int)(center_hz - spread_hz) + step - 1) / step > kMaxBins)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_search_level_dev: the level must have between 1 and 28 Doppler bins");
+    ctx->acq_witness_lanes = 1;
     return acquire_search(ctx, iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, true, out_dev);
 }
 
@@ -2083,6 +2096,32 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
     GYP_KNOB_NUM("grid_fused_waves", grid_fused_waves, int)
     if (is("last_grid_refined_rows")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_refined_rows; return GYP_OK; }
     if (is("last_grid_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_path; return GYP_OK; }
+    for (int w = 0; w < 3; ++w) {
+        // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)
+        static const char* const kWitness[3] = {"last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"};
+        const size_t len = std::strlen(kWitness[w]);
+        if (std::strncmp(name, kWitness[w], len) != 0) continue;
+        int at = w;
+        if (name[len] != 0) {
+            char* end = nullptr;
+            const long k = name[len] == '_' && name[len + 1] == 'l' && name[len + 2] >= '1' && name[len + 2] <= '9' ? std::strtol(name + len + 2, &end, 10) : 0;
+            if (k < 1 || k > kAcqWitnessLevels || !end || *end != 0) continue;
+            at = 3 * (int)k + w;
+        }
+        if (set) return GYP_E_BAD_ARG;
+        // the one place the counters are waited for and copied: this context's part of the last search plus the helpers' parts
+        long long total = 0;
+        for (int i = 0; i < ctx->acq_witness_lanes; ++i) {
+            gyp_ctx* c = i == 0 ? ctx : ctx->helper[i - 1];
+            if (!c || !c->d_acq_witness) continue;
+            int32_t v = 0;
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return GYP_E_HIP;
+            if (hipMemcpy(&v, c->d_acq_witness + at, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return GYP_E_HIP;
+            total += v;
+        }
+        *out = (double)total;
+        return GYP_OK;
+    }
     GYP_KNOB_NUM("cells_cu_reserve", cells_cu_reserve, int)
     GYP_KNOB_BOOL("no_acq_split", no_acq_split)
     GYP_KNOB_BOOL("no_spec", no_spec)
@@ -2117,7 +2156,9 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
 }
 int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
-    if (debug_apply(ctx, name, 0.0, false, out) != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_get: no such switch: ") + name);
+    const int rc = debug_apply(ctx, name, 0.0, false, out);
+    if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");
+    if (rc != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_get: no such switch: ") + name);
     return GYP_OK;
 }
 

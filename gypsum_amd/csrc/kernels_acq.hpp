@@ -27,9 +27,20 @@ struct AcqSearchState {
 // The search states at acquisition.py:78-79: centre and spread of the first level, nothing found yet.  (On the device: the entry
 // points stay asynchronous -- a host-built table would have to be waited for.)
 struct AcqSatList { int32_t id[32]; };
-__global__ void acq_init_kernel(AcqSearchState* states, int n_states, int n_sats, AcqSatList sats, double center, double spread) {
+// witness: what the search's levels did -- units given a forward pass of their own, cells that read a unit's spectra, cells on the
+// unshared work list (gyp_debug_get "last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells").  [0..2] summed over the
+// levels, then the same three per level for the first kAcqWitnessLevels of them ("..._l1", "..._l2", ...).  Zeroed here, added to by
+// thread 0 of each level's compact kernel, read by the host only when asked.
+constexpr int kAcqWitnessLevels = 16;
+constexpr int kAcqWitnessInts = 3 * (1 + kAcqWitnessLevels);
+__device__ __forceinline__ void acq_witness_add(int32_t* witness, int level, int units, int shared, int unshared) {
+    witness[0] += units; witness[1] += shared; witness[2] += unshared;
+    if (level < kAcqWitnessLevels) { witness[3 + 3 * level] = units; witness[4 + 3 * level] = shared; witness[5 + 3 * level] = unshared; }
+}
+__global__ void acq_init_kernel(AcqSearchState* states, int n_states, int n_sats, AcqSatList sats, double center, double spread, int32_t* witness) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_states) return;
+    if (i == 0) for (int w = 0; w < kAcqWitnessInts; ++w) witness[w] = 0;
     AcqSearchState a = {};
     a.stream = i / n_sats;
     a.sat_id = sats.id[i % n_sats];
@@ -73,7 +84,7 @@ __global__ void acq_plan_kernel(AcqSearchState* states, int n_states, gyp_cell_d
 constexpr float kTieBand = 2e-5f;   // float64 tie-break band of a level's bins (see acq_refine_kernel)
 // The level's work list: indices of the cells that are neither padding nor cached, ascending (one block).
 __global__ __launch_bounds__(1024) void acq_compact_kernel(const gyp_cell_desc* __restrict__ cells, int n_cells, int32_t* order, int32_t* n_active,
-                                                           int32_t* n_cand) {
+                                                           int32_t* n_cand, int32_t* witness, int level) {
     __shared__ int wave_tot[16];
     __shared__ int base;
     if (threadIdx.x == 0) base = 0;
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(1024) void acq_compact_kernel(const gyp_cell_desc* 
         if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; ++w) t += wave_tot[w]; base += t; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { *n_active = base; *n_cand = 0; n_cand[1] = 0; }   // n_cand[1]: the level's pending-pair count
+    if (threadIdx.x == 0) { *n_active = base; *n_cand = 0; n_cand[1] = 0; acq_witness_add(witness, level, 0, 0, base); }   // n_cand[1]: the level's pending-pair count
 }
 // Exclusive prefix sum of v over the 1024 threads of a workgroup (thread order); *total = the sum over all of them.
 __device__ __forceinline__ int block_excl_scan_1024(int v, int* wave_tot, int* total) {
@@ -130,7 +141,8 @@ struct AcqUnits {
 };
 constexpr int kUnitHash = 2048;
 __global__ __launch_bounds__(1024) void acq_compact_units_kernel(const gyp_cell_desc* __restrict__ cells, int n_cells, int cells_per_stream,
-                                                                 int32_t* order, int32_t* n_active, int32_t* n_cand, AcqUnits u) {
+                                                                 int32_t* order, int32_t* n_active, int32_t* n_cand, AcqUnits u,
+                                                                 int32_t* witness, int level) {
     __shared__ int key[kUnitHash], first[kUnitHash], cnt[kUnitHash], uid[kUnitHash], fill[kUnitHash];
     __shared__ int wave_tot[16];
     int pipe_base = 0, unit_base = 0, shared_base = 0;   // (uniform: every thread adds the same totals)
@@ -185,6 +197,7 @@ __global__ __launch_bounds__(1024) void acq_compact_units_kernel(const gyp_cell_
     if (t == 0) {
         *n_active = pipe_base; *n_cand = 0; n_cand[1] = 0;   // as acq_compact_kernel
         u.counts[0] = unit_base; u.counts[1] = shared_base;
+        acq_witness_add(witness, level, unit_base, shared_base, pipe_base);
     }
 }
 

@@ -684,6 +684,13 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
  *                               multiplied in from L1 / L2 in batches), 8 = two per SIMD at 256 (the next replica prefetched into registers); same cells
  *   "last_grid_path" (read only, gyp_debug_get)  the cells kernel the last gyp_correlate_grid* call took: 1 fused, 2 shared forward
  *                               transforms out of folded rows, 3 one wavefront per cell, 4 one workgroup per cell
+ *   "last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells" (read only, gyp_debug_get)  what the levels of the last
+ *                               gyp_acquire(_dev) / gyp_search_level(_dev) on the context did, summed over its levels: (stream, Doppler bin) units
+ *                               given one forward pass of their own, cells that read a unit's spectra, cells on the unshared work list (every
+ *                               correlated cell is one or the other); "<name>_l<k>", k = 1..16: level k alone.  Counted on the device by the
+ *                               work-list kernels; the scan itself copies and waits for nothing -- gyp_debug_get waits for the context's stream
+ *                               (and its helpers') and copies then.  The caller's context reports its own part plus the parts its helper
+ *                               contexts ran.  With "no_acq_shared_fwd" 1, at rates other than 8 samples per chip and from level 4 on the first two are 0
  *   "spec_sub_ms" 0, 100..2000 (0)  target length of the sub-blocks of a speculative tracking block (a failed verification costs its
  *                               channel one); 0: by rate -- 167 ms at 2.046 Msps, 500 ms otherwise
  *   "no_acq_split" 0/1 (0)      a multi-stream scan runs on the caller's stream alone

@@ -210,6 +210,26 @@ def run_full_sky_one(args):
     return seed, int(sv), int(r.doppler_shift), int(r.prn_phase_shift), float(r.correlation_strength), gap
 
 
+def run_acq_trace_one(args):
+    """args = (fs, n_ms, seed, sat_id, changes).  run_full_sky_one's search over an n_ms-millisecond scene, with the oracle's module
+    constants in `changes` ({"ACQ_BINS_PER_SPREAD": 7, ...}) set in this process first, and the trace kept: returns (seed, sat_id,
+    doppler_shift, prn_phase_shift, correlation_strength, [the Doppler bin each level ended on]).  The level winners are what the
+    device's shared-forward planner groups by (tests/acq_units_model.py)."""
+    fs, n_ms, seed, sv, changes = args
+    from gypsum_amd import synth
+    from oracle import gypsum_oracle as orc
+
+    for name, value in (changes or {}).items():
+        setattr(orc, name, value)
+    n = fs // 1000
+    scene = synth.random_scene(fs, n_ms, 6, seed, with_nav_bits=False, max_code_phase=(2046 if n > 2046 else None))
+    iq = synth.render(scene)
+    trace = []
+    r = orc.acquire_satellite(sv, iq, fs, n, orc.prn_as_complex(orc.generate_ca_codes()[sv - 1], n), trace=trace)
+    return (seed, int(sv), int(r.doppler_shift), int(r.prn_phase_shift), float(r.correlation_strength),
+            [int(level.doppler_hz) for _, _, level in trace])
+
+
 def run_grid_rows(args):
     """args = (iq_path, fs, n, n_ms, rows) with rows = int array [k, 2] of (unit, sat_id); `iq_path` a .npy of complex64[n_units, n_ms * n]
     (memory-mapped: the whole benchmark-sized batch is shared by the pool).  Per row the oracle's flat-grid search of that unit's samples

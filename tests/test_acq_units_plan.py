@@ -1,4 +1,5 @@
-"""CPU model of the shared-forward planner of the acquisition search (acq_compact_units_kernel, kernels_acq.hpp): the level's
+"""CPU model of the shared-forward planner of the acquisition search (acq_compact_units_kernel, kernels_acq.hpp; the model itself
+is tests/acq_units_model.py, which the GPU tests hold the device's counters against): the level's
 active cells (acq_plan_kernel's bins, minus the bins whose records the previous level already holds) grouped by exact
 (stream, Doppler) equality; a unit of two or more cells gets one forward pass, units are numbered in the order of their first cell
 and those beyond the spectra buffer's room stay on the unshared kernel.  Checked here: how many distinct bins the first three levels
@@ -8,57 +9,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-MAX_BINS = 28
-N_SATS = 32
-
-
-def level_bins(center: float, spread: float, bins_per_spread: float = 10.0) -> list[int]:
-    """acq_plan_kernel: range(int(c - s), int(c + s), int(s / 10))."""
-    lo, hi, step = int(center - spread), int(center + spread), int(spread / bins_per_spread)
-    return list(range(lo, hi, step))[:MAX_BINS]
-
-
-def plan_level(centers: np.ndarray, spread: float, prev: list[list[int]] | None):
-    """Cells [state][28] of one level: (stream, doppler, active).  A bin the previous level evaluated is not active (record reuse)."""
-    n_streams = centers.shape[0]
-    cells = []
-    for s in range(n_streams):
-        for sat in range(N_SATS):
-            bins = level_bins(centers[s, sat], spread)
-            done = set(prev[s * N_SATS + sat]) if prev is not None else set()
-            for b in range(MAX_BINS):
-                cells.append((s, bins[b] if b < len(bins) else 0, b < len(bins) and bins[b] not in done))
-    return cells
-
-
-def plan_units(cells, max_units: int):
-    """The kernel's lists: units (first cell of each), the shared cells unit after unit with their unit, the unshared cells ascending."""
-    per_stream = N_SATS * MAX_BINS
-    units, sh_cell, sh_unit, order = [], [], [], []
-    for s0 in range(0, len(cells), per_stream):
-        members: dict[int, list[int]] = {}
-        for c in range(s0, s0 + per_stream):
-            if cells[c][2]:
-                members.setdefault(cells[c][1], []).append(c)
-        shared = set()
-        for dop, cs in sorted(members.items(), key=lambda kv: kv[1][0]):   # units in the order of their first cell
-            if len(cs) >= 2 and len(units) < max_units:
-                u = len(units)
-                units.append(cs[0])
-                sh_cell += cs
-                sh_unit += [u] * len(cs)
-                shared.update(cs)
-        order += [c for c in range(s0, s0 + per_stream) if cells[c][2] and c not in shared]
-    return units, sh_cell, sh_unit, order
-
-
-def _check_partition(cells, units, sh_cell, sh_unit, order):
-    active = [c for c, (_, _, on) in enumerate(cells) if on]
-    assert sorted(sh_cell + order) == active                       # nothing lost, nothing twice
-    assert order == sorted(order)
-    for c, u in zip(sh_cell, sh_unit):                             # a cell reads the spectra of its own (stream, Doppler)
-        assert cells[c][:2] == cells[units[u]][:2]
-    assert all(np.diff(sh_unit) >= 0)                              # grouped: a unit's consumers are neighbours in the list
+from acq_units_model import MAX_BINS, N_SATS, _check_partition, expected_counts, level_bins, max_units_for, plan_level, plan_units
 
 
 def _scan_levels(winners_1, winners_2, n_streams):
@@ -125,3 +76,23 @@ def test_one_satellite_shares_nothing():
     units, sh_cell, sh_unit, order = plan_units(cells, max_units=10**6)
     _check_partition(cells, units, sh_cell, sh_unit, order)
     assert not units and len(order) == 2 * 20
+
+
+def test_expected_counts_on_the_hand_cases():
+    """expected_counts (what gyp_debug_get "last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells" are held against) on
+    the three cases counted by hand above, and the room for units as acquire_search computes it."""
+    for n_streams in (1, 6, 13):
+        z = np.zeros((n_streams, N_SATS), dtype=int)
+        l1, _, _ = _scan_levels(z, z, n_streams)
+        assert expected_counts([l1], max_units=10**6) == (20 * n_streams, 20 * N_SATS * n_streams, 0)
+    _, l2, _ = _scan_levels(np.array([[10] * 16 + [0] * 16]), np.zeros((1, N_SATS), dtype=int), 1)
+    assert expected_counts([l2], max_units=10**6) == (25, 16 * 10 + 16 * 15, 0)
+    z = np.zeros((3, N_SATS), dtype=int)
+    l1, _, _ = _scan_levels(z, z, 3)
+    for cap in (0, 1, 19, 20, 21, 59, 60):
+        assert expected_counts([l1], max_units=cap) == (min(cap, 60), min(cap, 60) * N_SATS, (60 - min(cap, 60)) * N_SATS)
+    assert expected_counts([l1, l2], max_units=10**6) == (60 + 25, 60 * N_SATS + 400, 0)     # summed over the levels given
+    # the room: 84 units per stream, 1 GiB of spectra at most, never more than there are cells
+    assert max_units_for(13, 32, 10) == 819 and max_units_for(2, 32, 10) == 168 and max_units_for(7, 32, 10) == 588
+    assert max_units_for(12, 32, 40) == 204 and max_units_for(6, 32, 40) == 204
+    assert max_units_for(1, 2, 1) == 56 and max_units_for(1, 1, 10) == 28

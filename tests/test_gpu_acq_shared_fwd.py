@@ -8,6 +8,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from acq_units_model import level_bins
 from gypsum_amd._lib import ACQ_RESULT, SYNTH_SAT
 from gypsum_amd.engine import GypsumEngine
 
@@ -55,6 +56,11 @@ def samples():
     return host, n_streams
 
 
+def _witness(eng):
+    """(units given a forward pass of their own, cells that read a unit's spectra, cells on the unshared list) of the last search."""
+    return tuple(int(eng.debug_get(k)) for k in ("last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"))
+
+
 def _scan(eng, host, n_streams, sat_ids):
     stride = N_MS * N
     buf = eng.alloc(n_streams * stride * 8)
@@ -73,6 +79,10 @@ def test_shared_forward_scan_is_byte_equal(samples, knobs):
     got = _scan(eng, host, n_streams, ALL_IDS)
     assert got.tobytes() == want.tobytes(), int(np.sum(got != want))
     assert sum(int(r["strength"] > 3.0) for r in want) >= 4 * (n_streams - 1)   # the planted satellites are found
+    w_off, w_on = _witness(ref_eng), _witness(eng)                               # (helper contexts included)
+    assert w_off[0] == 0 and w_off[1] == 0, w_off
+    assert w_on[0] >= 20 * n_streams and w_on[1] >= 20 * 32 * n_streams, w_on   # level 1 alone: 20 units per stream, every cell shared
+    assert w_on[1] + w_on[2] == w_off[2], (w_on, w_off)                         # no cell lost, none served twice
     ref_eng.close()
     eng.close()
 
@@ -84,19 +94,33 @@ def test_one_stream_one_satellite_shares_nothing_and_matches(samples):
         want = _scan(ref_eng, host, 1, sats)
         got = _scan(eng, host, 1, sats)
         assert got.tobytes() == want.tobytes(), sats
+        assert _witness(ref_eng)[:2] == (0, 0)
+        if len(sats) == 1:
+            assert _witness(eng)[:2] == (0, 0) and _witness(eng)[2] == _witness(ref_eng)[2]      # [7] shares nothing
+        else:
+            assert int(eng.debug_get("last_acq_units_l1")) == 20 and _witness(eng)[0] >= 20        # [7, 19]: level 1's 20 bins, two cells each
+            assert int(eng.debug_get("last_acq_shared_cells_l1")) == 40
         ref_eng.close()
         eng.close()
 
 
 @pytest.mark.parametrize("center,spread", [(-2100.0, 3500.0), (1400.0, 3500.0), (-1050.0, 1750.0), (2450.0, 1750.0), (350.0, 875.0)])
 def test_single_levels_at_level_2_and_3_centres_are_byte_equal(samples, center, spread):
-    """gyp_search_level_dev with every satellite on one grid: the level's winners, their code phases and float64 strengths."""
+    """gyp_search_level_dev with every satellite on one grid: the level's winners, their code phases and float64 strengths.
+    (350, 875) is a level-4 spread -- 875 * 4 < 7000 -- and never enters the shared branch: there the two engines run the same
+    kernel, and the witness must say so (no unit); the other four share every cell."""
     host, n_streams = samples
     ref_eng, eng = _engine(1), _engine(0)
     iq = host[: n_streams * N_MS * N]
     want = ref_eng.search_level(iq, n_streams, N_MS, ALL_IDS, center, spread)
     got = eng.search_level(iq, n_streams, N_MS, ALL_IDS, center, spread)
     assert got.tobytes() == want.tobytes(), int(np.sum(got != want))
+    n_bins = len(level_bins(center, spread))                  # 20, and 21 for (350, 875): range(-525, 1225, 87)
+    assert _witness(ref_eng) == (0, 0, n_bins * 32 * n_streams)
+    if spread * 4 < 7000.0:
+        assert _witness(eng) == (0, 0, n_bins * 32 * n_streams)
+    else:
+        assert _witness(eng) == (n_bins * n_streams, n_bins * 32 * n_streams, 0)
     ref_eng.close()
     eng.close()
 

@@ -196,11 +196,11 @@ def test_full_sky_worker_is_the_oracles_search():
 
 
 # ------------------------------------------------------------------ 6. strided, guarded layouts
-def _guarded(streams, n, pad):
-    """One complex64 buffer: `pad` NaN samples, then the streams at a stride of len(stream) + n + 1 samples (odd: odd streams start
-    at odd sample offsets) with NaN in every gap and after the last stream.  Returns (buffer, stride)."""
+def _guarded(streams, n, pad, gap=None):
+    """One complex64 buffer: `pad` NaN samples, then the streams at a stride of len(stream) + gap samples (gap = n + 1 unless given;
+    odd: odd streams start at odd sample offsets) with NaN in every gap and after the last stream.  Returns (buffer, stride)."""
     length = streams[0].size
-    stride = length + n + 1
+    stride = length + (n + 1 if gap is None else gap)
     buf = np.full(pad + len(streams) * stride, np.complex64(complex(np.nan, np.nan)), dtype=np.complex64)
     for b, s in enumerate(streams):
         buf[pad + b * stride:pad + b * stride + length] = s
