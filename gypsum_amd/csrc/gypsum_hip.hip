@@ -160,6 +160,8 @@ struct gyp_ctx {
     bool spec_redo = true;       // gyp_debug_set("spec_redo"): 0 = A/B switch back to re-running a failed speculation on the throughput kernel
     int prof_wave = 0;           // gyp_debug_set("prof_wave"): which wavefront of workgroup 0 stamps gyp_debug_track_profile's counters
     int exact_prefetch = 0;      // gyp_debug_set("exact_prefetch"): A/B switch of dll_exact_wave_kernel's software prefetch depth
+    bool no_exact_shared = false;   // gyp_debug_set("no_exact_shared"): A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
+    int last_exact_path = 0;     // gyp_debug_get("last_exact_path"): the exact-sums kernel of the last plain throughput call (0 none yet, 1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel)
     bool no_spec = false;        // gyp_debug_set("no_spec"): A/B switch: lightly loaded banks use the throughput kernel too
     int spec_fail_at = -1;       // gyp_debug_set("spec_fail_at", ms) (test hook): channel 0's verification is made to fail at that millisecond of a block
     bool spec_debug = false;     // gyp_debug_set("spec_debug"): per-ms window dump of the speculative tracker (gyp_debug_spec_read)
@@ -195,6 +197,8 @@ struct gyp_bank {
     SpecIn* d_spec = nullptr;
     double* d_disc = nullptr;    // [n_chan][n_ms] exact discriminators from the verify pass (dll_scan_kernel's input)
     DllExact* d_dllx = nullptr;  // [n_chan] the exactly re-integrated code loop between sub-blocks
+    ExactGroup* d_groups = nullptr;  // [n_chan] + one int32 counter behind them: dll_exact_shared_kernel's channel groups (exact_group_kernel, every call)
+    int last_n_ms = 0;           // row length of d_spec / d_disc in the last throughput call (gyp_debug_disc_read)
     size_t spec_cap = 0;         // in records
     int32_t* d_bad = nullptr;
     int32_t* d_bad_from = nullptr;   // per channel: first verify sub-block that failed
@@ -718,6 +722,22 @@ static int launch_dll_exact(gyp_ctx* ctx, const DllExactParams& p, hipStream_t s
 #undef X
         default: return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
     }
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+// The same sums for the plain throughput call at 8 samples per chip: the channels are grouped by stream on the device, then one
+// workgroup per CU stages each (group, millisecond) once for all the group's channels (dll_exact_shared_kernel).
+static bool exact_shared_applies(const gyp_ctx* ctx, int n_chan) { return ctx->k == 8 && !ctx->no_exact_shared && n_chan <= kExactGroupMaxChan; }
+static int launch_dll_exact_shared(gyp_ctx* ctx, const DllExactParams& p, ExactGroup* groups, hipStream_t stream) {
+    if (p.n_chan <= 0 || p.ms_end <= p.ms_begin) return GYP_OK;
+    int32_t* n_groups = reinterpret_cast<int32_t*>(groups + p.n_chan);
+    HIP_TRY(ctx, hipMemsetAsync(n_groups, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(exact_group_kernel, dim3((p.n_chan + 255) / 256), dim3(256), 0, stream, p.states, p.n_chan, groups, n_groups);
+    DllExactSharedParams s;
+    s.x = p; s.groups = groups; s.n_groups = n_groups;
+    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dll_exact_shared_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)exact_shared_lds_bytes<8>()));
+    hipLaunchKernelGGL(dll_exact_shared_kernel<8>, dim3(ctx->n_cus), dim3(kExactSharedThreads), exact_shared_lds_bytes<8>(), stream, s);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
@@ -1394,6 +1414,7 @@ void gyp_bank_destroy(gyp_bank* bank) {
     if (bank->d_spec) (void)hipFree(bank->d_spec);
     if (bank->d_disc) (void)hipFree(bank->d_disc);
     if (bank->d_dllx) (void)hipFree(bank->d_dllx);
+    if (bank->d_groups) (void)hipFree(bank->d_groups);
     if (bank->d_bad) (void)hipFree(bank->d_bad);
     if (bank->d_bad_from) (void)hipFree(bank->d_bad_from);
     if (bank->d_hist) (void)hipFree(bank->d_hist);
@@ -1448,6 +1469,7 @@ int gyp_bank_drop_channel(gyp_bank* bank, int32_t index) {
 static int ensure_dll_buffers(gyp_bank* bank, size_t n_rec) {
     gyp_ctx* ctx = bank->ctx;
     if (!bank->d_dllx) HIP_TRY(ctx, hipMalloc((void**)&bank->d_dllx, (size_t)bank->n_chan * sizeof(DllExact)));
+    if (!bank->d_groups) HIP_TRY(ctx, hipMalloc((void**)&bank->d_groups, ((size_t)bank->n_chan + 1) * sizeof(ExactGroup)));
     if (bank->spec_cap < n_rec) {
         if (bank->d_spec) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1520,7 +1542,14 @@ static int track_block_throughput(gyp_bank* bank, TrackBlockParams p, const int3
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[1], ctx->stream));
     DllExactParams x = dll_exact_params(bank, p);
     x.only_if = only_if; x.from_sub = from_sub; x.sub = sub;
-    if ((rc = launch_dll_exact(ctx, x, ctx->stream))) return rc;
+    bank->last_n_ms = p.n_ms;
+    if (!only_if && !from_sub && exact_shared_applies(ctx, bank->n_chan)) {
+        if ((rc = launch_dll_exact_shared(ctx, x, bank->d_groups, ctx->stream))) return rc;
+        ctx->last_exact_path = 2;
+    } else {
+        if ((rc = launch_dll_exact(ctx, x, ctx->stream))) return rc;
+        if (!only_if && !from_sub) ctx->last_exact_path = ctx->k <= 8 ? 1 : 3;
+    }
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[2], ctx->stream));
     DllScanParams d = dll_scan_params(bank, p);
     d.bad = only_if; d.only_bad = only_if ? 1 : 0; d.from_sub = from_sub; d.sub = sub;
@@ -2016,6 +2045,21 @@ int gyp_debug_dll_read(gyp_bank* bank, int32_t* repairs_out) {
     return GYP_OK;
 }
 
+int gyp_debug_disc_read(gyp_bank* bank, int32_t n_ms, double* disc_out) {
+    if (!bank) return GYP_E_BAD_ARG;
+    gyp_ctx* ctx = bank->ctx;
+    if (!disc_out || n_ms <= 0 || n_ms != bank->last_n_ms || !bank->d_disc || !bank->d_spec)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_disc_read: n_ms must be the length of the bank's last block on the throughput path");
+    const size_t n_rec = (size_t)bank->n_chan * n_ms;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<SpecIn> spec(n_rec);
+    HIP_TRY(ctx, hipMemcpy(disc_out, bank->d_disc, n_rec * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(spec.data(), bank->d_spec, n_rec * sizeof(SpecIn), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_rec; ++i)
+        if (spec[i].key == kSpecKeyLost) disc_out[i] = 0.0;   // not processed: the pass wrote nothing there
+    return GYP_OK;
+}
+
 int gyp_bank_reset_dev(gyp_bank* bank, const gyp_chan_init* inits_dev) {
     if (!bank) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
@@ -2080,7 +2124,7 @@ const DebugKnob kDebugKnobs[] = {
     {"no_pipe", 0, 1, true}, {"no_shared_fwd", 0, 1, true}, {"no_acq_shared_fwd", 0, 1, true}, {"no_acq_split", 0, 1, true}, {"no_spec", 0, 1, true},
     {"spec_debug", 0, 1, true}, {"acq_lanes", 1, gyp_ctx::kMaxAcqLanes, true}, {"track_chunk_ms", 0, 1e6, true}, {"widen_wg_per_cu", 1, 8, true},
     {"symbol_tau", 0, 100, false}, {"dll_prov_bias", -1e6, 1e6, false}, {"spec_fail_at", -1, 2147483647.0, true},
-    {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"exact_prefetch", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
+    {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"exact_prefetch", 0, 1, true}, {"no_exact_shared", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
     {"resample_tile_samples", 1024, 8192, true},
 };
 }  // namespace
@@ -2135,6 +2179,8 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
     GYP_KNOB_NUM("dll_prov_bias", dll_prov_bias, double)
     GYP_KNOB_NUM("spec_fail_at", spec_fail_at, int)
     GYP_KNOB_NUM("exact_prefetch", exact_prefetch, int)
+    GYP_KNOB_BOOL("no_exact_shared", no_exact_shared)
+    if (is("last_exact_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_exact_path; return GYP_OK; }
     GYP_KNOB_NUM("prof_wave", prof_wave, int)
     GYP_KNOB_NUM("resample_tile_samples", resample_tile, int)
 #undef GYP_KNOB_BOOL

@@ -220,6 +220,180 @@ __global__ __launch_bounds__(256, MINW) void dll_exact_wave_kernel(DllExactParam
         if (lane == 63) p.disc_out[at] = dll_discriminator_exact(acc);
     }
 }
+// ---- the same sums with a stream's millisecond staged once for all its channels (throughput path) -----------------------------
+// dll_exact_wave_kernel lets every channel fetch and convert its stream's samples itself: twelve channels of a stream read the
+// same 8K-sample millisecond twelve times, at a 8K-byte lane stride, and convert it float32 -> float64 twelve times.  Here the work
+// item is a (channel group, millisecond): a group is up to kExactSharedConsumers channels of ONE stream (exact_group_kernel builds
+// the table from the device's channel states -- gyp_bank_reset_dev rewrites ChanState::stream on the device, no host copy is
+// trusted).  One 16-wavefront workgroup per CU:
+//   producers (4 wavefronts)  hold the NEXT item's millisecond as raw float32 in registers, requested in lane order (16 bytes per
+//                             lane, 1 KiB per load) while the consumers sum, and convert + store it into LDS between the two barriers;
+//   consumers (12 wavefronts) one channel each: dll_exact_wave_kernel's arithmetic on float64 samples out of LDS -- the same operands
+//                             in the same order, so the same bits.
+// LDS layout: sample n (n = -K .. N + K - 1, K zeros on either side of the block: the cut windows -1 and 1022 become ordinary ones, a
+// zero adds what the predicated load added) lives at 16-byte unit (n + K) + (n + K) / K, i.e. 16 bytes of padding behind every K
+// samples.  Lanes read windows m = lane + 64 c - 1 at a lane stride of K + 1 units (K = 8: 144 B = 36 banks, sixteen lanes on sixteen
+// different 4-bank groups) whatever r = s mod K is.  (N + 2K) / K * (K + 1) units: 147 600 bytes at K = 8, one workgroup per CU.
+constexpr int kExactSharedConsumers = 12;
+constexpr int kExactSharedProducers = 4;
+constexpr int kExactSharedThreads = 64 * (kExactSharedConsumers + kExactSharedProducers);
+constexpr int kExactGroupMaxChan = 16384;   // exact_group_kernel keeps every channel's stream index in LDS
+struct ExactGroup {
+    int32_t stream, n;                      // n channels (1 .. kExactSharedConsumers) of this stream, ascending
+    int32_t ch[kExactSharedConsumers];
+    int32_t pad[2];
+};
+static_assert(sizeof(ExactGroup) == 64, "ExactGroup");
+template <int K>
+constexpr int exact_shared_lds_units() { return (K * kChips + 2 * K) / K * (K + 1); }
+template <int K>
+constexpr size_t exact_shared_lds_bytes() { return (size_t)exact_shared_lds_units<K>() * sizeof(double2); }
+
+// Channel c leads a group if the number of channels before it on its stream is a multiple of kExactSharedConsumers; it then collects
+// the following channels of that stream.  One thread per channel; any channel order, any number of channels per stream.  *n_groups
+// is zeroed by the host in front of the launch.  (Group ORDER depends on the atomic's arrival order; the sums do not.)
+__global__ __launch_bounds__(256) void exact_group_kernel(const ChanState* __restrict__ states, int32_t n_chan, ExactGroup* __restrict__ groups,
+                                                          int32_t* __restrict__ n_groups) {
+    __shared__ int32_t s_stream[kExactGroupMaxChan];
+    for (int i = threadIdx.x; i < n_chan; i += blockDim.x) s_stream[i] = states[i].stream;
+    __syncthreads();
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chan) return;
+    const int s = s_stream[c];
+    int before = 0;
+    for (int i = 0; i < c; ++i) before += s_stream[i] == s ? 1 : 0;
+    if (before % kExactSharedConsumers) return;
+    ExactGroup g;
+    g.stream = s; g.n = 1; g.ch[0] = c; g.pad[0] = g.pad[1] = 0;
+#pragma unroll
+    for (int k = 1; k < kExactSharedConsumers; ++k) g.ch[k] = -1;
+    for (int i = c + 1; i < n_chan && g.n < kExactSharedConsumers; ++i) {
+        if (s_stream[i] != s) continue;
+#pragma unroll
+        for (int k = 1; k < kExactSharedConsumers; ++k)      // (static indices: the record stays in registers)
+            if (k == g.n) g.ch[k] = i;
+        ++g.n;
+    }
+    groups[atomicAdd(n_groups, 1)] = g;
+}
+
+struct DllExactSharedParams {
+    DllExactParams x;              // only_if / from_sub / trk_round are null on this path
+    const ExactGroup* groups;
+    const int32_t* n_groups;
+};
+template <int K>
+__device__ __forceinline__ void exact_window_fold64(const double2 (&x)[K], float cm1, float c0, float cp1, double2 rho, double2 step,
+                                                    double2& sp, double2& se, double2& sl) {   // exact_window_fold on converted samples
+    const double dj = (double)c0, gl = (double)(cm1 - c0), ge = (double)(c0 - cp1);
+    double2 h = x[K - 1];
+#pragma unroll
+    for (int i = K - 2; i >= 0; --i) h = horner64(h, rho, x[i]);
+    const double2 xe = x[K - 1], xl = x[0];
+    sp = horner64(sp, step, make_double2(dj * h.x, dj * h.y));
+    se = horner64(se, step, make_double2(ge * xe.x, ge * xe.y));
+    sl = horner64(sl, step, make_double2(gl * xl.x, gl * xl.y));
+}
+// Workgroup b walks items [n_items b / grid, n_items (b + 1) / grid) of (group, millisecond), milliseconds innermost: consecutive
+// milliseconds of a stream stay on one CU.  The two roles run separate loops with the same two barriers per item (wave-uniform
+// branch), so that the producers' 64 sample registers are not live in the consumers' loop.
+template <int K>
+__global__ __launch_bounds__(kExactSharedThreads) void dll_exact_shared_kernel(DllExactSharedParams ps) {
+    static_assert(K <= 8, "a window's samples in registers");
+    constexpr int N = K * kChips;
+    static_assert(K % 2 == 0, "the producers fetch sample pairs");
+    constexpr int PT = 64 * kExactSharedProducers;       // producer threads
+    constexpr int PAIRS = N / 2;                         // 16-byte sample pairs of a millisecond
+    constexpr int LOADS = (PAIRS + PT - 1) / PT;         // pairs per producer lane
+    extern __shared__ double2 s_x[];
+    const DllExactParams& p = ps.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int span = p.ms_end - p.ms_begin;
+    const int64_t n_items = (int64_t)__builtin_amdgcn_readfirstlane(ps.n_groups[0]) * span;
+    const int64_t lo = n_items * blockIdx.x / gridDim.x, hi = n_items * (blockIdx.x + 1) / gridDim.x;
+    if (lo >= hi) return;
+    if (threadIdx.x < 2 * K) {                            // the zero halos, once
+        const int np = threadIdx.x < K ? (int)threadIdx.x : N + (int)threadIdx.x;   // n + K of samples -K .. -1 and N .. N + K - 1
+        s_x[np + np / K] = make_double2(0.0, 0.0);
+    }
+    if (wave >= kExactSharedConsumers) {
+        typedef float4 __attribute__((aligned(8))) float4_a8;
+        const int pt = lane + 64 * (wave - kExactSharedConsumers);
+        float4 hold[LOADS];                               // pair t = pt + PT j: samples 2t, 2t + 1 (lane order: 1 KiB per wavefront and load)
+        auto request = [&](int64_t item) {
+            const int g = (int)(item / span), ms = p.ms_begin + (int)(item % span);
+            const int stream = __builtin_amdgcn_readfirstlane(ps.groups[g].stream);
+            const float4_a8* block = reinterpret_cast<const float4_a8*>(p.iq + (int64_t)stream * p.stream_stride + (int64_t)ms * N);
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) {
+                const int t = pt + PT * j;
+                if (PT * j + PT <= PAIRS) hold[j] = block[t];
+                else hold[j] = t < PAIRS ? (float4)block[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        };
+        request(lo);
+        for (int64_t item = lo; item < hi; ++item) {
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) {
+                const int t = pt + PT * j, np = 2 * t + K;   // (np and K even: both samples in front of the same padding)
+                if (PT * j + PT <= PAIRS || t < PAIRS) {
+                    s_x[np + np / K] = make_double2((double)hold[j].x, (double)hold[j].y);
+                    s_x[np + np / K + 1] = make_double2((double)hold[j].z, (double)hold[j].w);
+                }
+            }
+            __syncthreads();                              // the millisecond is staged
+            if (item + 1 < hi) request(item + 1);
+            __syncthreads();                              // the consumers are done with it
+        }
+        return;
+    }
+    const double2* win0 = s_x + (K + 1) * lane;           // window m = lane - 1 at r = 0
+    for (int64_t item = lo; item < hi; ++item) {
+        __syncthreads();                                  // the millisecond is staged
+        const int g = (int)(item / span), ms = p.ms_begin + (int)(item % span);
+        const ExactGroup* grp = ps.groups + g;
+        const int ch = wave < __builtin_amdgcn_readfirstlane(grp->n) ? __builtin_amdgcn_readfirstlane(grp->ch[wave]) : -1;
+        if (ch >= 0) {                                    // wave-uniform
+            const int64_t at = (int64_t)ch * p.n_ms + ms;
+            const SpecIn in = p.spec[at];
+            if (in.key != kSpecKeyLost) {                 // wave-uniform
+                const int sat = __builtin_amdgcn_readfirstlane(p.states[ch].sat_id);
+                const float* chipf = p.chipf + (sat - 1) * 2048;
+                const double du = in.doppler * p.inv_fs;
+                const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
+                const int sN = __builtin_amdgcn_readfirstlane(mod_n(in.code_phase, N));
+                const int q = sN / K, r = sN % K;
+                int off[K];                               // sample i of a window: r + i units on, one more behind the padding
+#pragma unroll
+                for (int i = 0; i < K; ++i) off[i] = r + i + (r + i >= K ? 1 : 0);
+                double2 sp = make_double2(0.0, 0.0), se = sp, sl = sp;
+                const double2 rho = carrier64(du), step = carrier64(du * (double)(K * 64));
+#pragma unroll 2
+                for (int c = 15; c >= 0; --c) {
+                    const int m = lane + 64 * c - 1;
+                    const double2* w = win0 + (K + 1) * 64 * c;
+                    double2 x[K];
+#pragma unroll
+                    for (int i = 0; i < K; ++i) x[i] = w[off[i]];
+                    int j = m - q;
+                    j = j < 0 ? j + kChips : j;
+                    j = j < 0 ? j + kChips : j;
+                    const float* cp = chipf + j + kChips;
+                    exact_window_fold64<K>(x, cp[-1], cp[0], cp[1], rho, step, sp, se, sl);
+                }
+                const double2 rho_a = carrier64(du);
+                const double2 anchor = carrier64(u0 + du * (double)(K * (lane - 1) + r));
+                const double2 pp = cmul64(sp, anchor), ee = cmul64(cmul64(se, cpow_km1<K>(rho_a)), anchor), ll = cmul64(sl, anchor);
+                double acc[6] = {pp.x, pp.y, ee.x, ee.y, ll.x, ll.y};
+#pragma unroll
+                for (int v = 0; v < 6; ++v) acc[v] = wave_sum_last(acc[v]);
+                if (lane == 63) p.disc_out[at] = dll_discriminator_exact(acc);
+            }
+        }
+        __syncthreads();                                  // done with the millisecond
+    }
+}
 // Rates above 8 samples per chip (16.368 ... 49.104 Msps): one 256-thread workgroup per unit walks the block (exact_epl_generic).
 template <int K>
 __global__ __launch_bounds__(256) void dll_exact_block_kernel(DllExactParams p) {

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 206: recordings of 1-, 2- or 4-bit words packed into bytes, unpacked on the device: gyp_packing, gyp_packed_span,
+/* 207: gyp_debug_disc_read added (the float64 discriminators of a bank's last throughput block); gyp_debug_set name no_exact_shared and
+ *      the read-only "last_exact_path".  Nothing that existed changes.
+ * 206: recordings of 1-, 2- or 4-bit words packed into bytes, unpacked on the device: gyp_packing, gyp_packed_span,
  *      gyp_unpack_iq_dev, gyp_resample_packed_dev, gyp_ingest_open_packed.  Nothing that existed changes.
  * 205: digital down-converter for real-sampled recordings at an intermediate frequency: gyp_ddc_design, gyp_ddc_iq_dev,
  *      gyp_ingest_open_ddc.  Nothing that existed changes.
@@ -42,7 +44,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 206 /* 0.2.6 */
+#define GYP_VERSION 207 /* 0.2.7 */
 
 enum {
     GYP_OK = 0,
@@ -704,6 +706,13 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
  *   "resample_tile_samples" 1024..8192 (4096)  LDS budget of one resampler workgroup, in input samples; same output for any value
  *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring); same output for any value
  *   "exact_prefetch" 0/1 (0)    dll_exact_wave_kernel with its next window software-prefetched (A/B: measured slower, profiles/r04_exact_ab.txt)
+ *   "no_exact_shared" 0/1 (0)   the exact code-loop sums behind the throughput tracking kernel fetch and convert a stream's samples once per
+ *                               channel again (dll_exact_wave_kernel).  Default at 8 samples per chip, plain gyp_track_block(_dev) calls on the
+ *                               throughput path: the channels are grouped by stream on the device and each (stream, millisecond) is staged once, as
+ *                               float64 in LDS, for up to twelve channels (dll_exact_shared_kernel); same sums bit for bit.  Other rates, the
+ *                               speculative tracker's rounds and its re-runs keep the per-channel kernels either way
+ *   "last_exact_path" (read only, gyp_debug_get)  the exact-sums kernel of the context's last plain throughput call: 0 none yet,
+ *                               1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel (more than 8 samples per chip)
  *   "prof_wave" 0..7 (0)        which wavefront of workgroup 0 stamps the counters of gyp_debug_track_profile
  *   "symbol_tau" 0..100 (1e-4)  |Re peak| / |peak| below which dll_scan_kernel decides the pseudosymbol in float64 (test: 10 = always)
  *   "dll_prov_bias" (0)         test hook: added to the PROVISIONAL discriminator so that the repair path runs; results must not change
@@ -726,7 +735,7 @@ int gyp_debug_track_profile(gyp_ctx* ctx, int enable, long long* out16);
 int gyp_debug_spec_read(gyp_bank* bank, float* out, int32_t n_floats, int32_t* bad_out);
 /* Debug / measurement: HIP events on the context's stream around the three stages behind gyp_track_block(_dev) on the
  * throughput path (banks of more than one channel per CU): enable != 0 arms it; out4 (may be NULL) receives, for the last
- * call, {ms in track_block_kernel (all its launches), ms in the dll_exact kernel, ms in dll_scan_kernel, number of
+ * call, {ms in track_block_kernel (all its launches), ms in the dll_exact kernel (with dll_exact_shared_kernel: its grouping kernel too), ms in dll_scan_kernel, number of
  * track_block_kernel launches: blocks longer than 250 ms go through in chunks, gyp_debug_set "track_chunk_ms"} -- zeros when that call
  * ran on the speculative path (lightly loaded banks), which has no such split.  bench.py's per-kernel roofline uses it. */
 int gyp_debug_track_timing(gyp_ctx* ctx, int enable, float* out4);
@@ -734,6 +743,11 @@ int gyp_debug_track_timing(gyp_ctx* ctx, int enable, float* out4);
  * the exactly re-integrated code loop (dll_scan_kernel) had int(self.phase) differ from the tracking kernel's provisional one
  * and formed that millisecond's float64 sums again for the right lag.  Synchronises the stream. */
 int gyp_debug_dll_read(gyp_bank* bank, int32_t* repairs_out);
+/* Debug (throughput path): disc_out[n_chan][n_ms] = the float64 discriminators (tracker.py:297) the exact-sums kernel formed for the
+ * bank's last gyp_track_block(_dev) call, at the lag the tracking kernel ran each millisecond with -- dll_scan_kernel's input, before
+ * any repair; milliseconds a lost channel did not process read 0.  n_ms must be that call's length (GYP_E_BAD_ARG otherwise, or if the
+ * bank has not tracked a block on the throughput path).  Synchronises the stream. */
+int gyp_debug_disc_read(gyp_bank* bank, int32_t n_ms, double* disc_out);
 /* Debug / telemetry (speculative block tracker): out4 = {sub-blocks of the last gyp_track_block(_dev) call, rounds enqueued for it,
  * sub-blocks tracked AGAIN from their checkpoint because a millisecond's window had not held the profile's arg-max (the failed
  * millisecond then takes the transform path), channels finished by the transform kernel instead (out of forced-transform slots or

@@ -86,10 +86,16 @@ for k, v in entry.items():
                           "correction": "FETCH_SIZE / WRITE_SIZE are in KB; factors = bytes moved per counted byte measured by "
                                         "tools/fetch_calib.hip for this kernel's patterns (16 B per lane at a 64-byte lane stride: "
                                         "read_staging; 56-byte records written dword by dword: write_records)"}
-    if "dll_exact_wave_kernel<8" in k and "FETCH_SIZE" in v:
-        latest["cfg3_dll_exact"] = {"kernel": k, "fetch_kb_raw": v["FETCH_SIZE"]["mean_per_launch"], "fetch_factor": factor["read_windows"],
-                                    "hbm_bytes_per_launch": factor["read_windows"] * v["FETCH_SIZE"]["mean_per_launch"] * 1024.0,
-                                    "kernel_ms_during_counter_pass": durs.get(k)}
+# the exact sums of the step: dll_exact_shared_kernel where it ran (lane-order 16-byte loads, the pattern gfx950 under-reports: read_contiguous),
+# else the per-channel dll_exact_wave_kernel (8-byte-aligned window reads, counted as moved: read_windows)
+for name, pattern in (("dll_exact_shared_kernel<8", "read_contiguous"), ("dll_exact_wave_kernel<8", "read_windows")):
+    hits = [k for k, v in entry.items() if name in k and "FETCH_SIZE" in v]
+    if hits:
+        k = hits[0]
+        fetch = entry[k]["FETCH_SIZE"]["mean_per_launch"]
+        latest["cfg3_dll_exact"] = {"kernel": k, "fetch_kb_raw": fetch, "fetch_factor": factor[pattern], "fetch_pattern": pattern,
+                                    "hbm_bytes_per_launch": factor[pattern] * fetch * 1024.0, "kernel_ms_during_counter_pass": durs.get(k)}
+        break
 # the flat-grid workloads (tools/gpu_visit.sh pmcgrid): every gyp kernel of one `bench.py --workload cfgN` step summed -- fold / wipe /
 # boxcar + cells -- with the guide's gfx950 correction for wide coalesced reads (x2 on FETCH_SIZE; writes as counted)
 for w in ("cfg2", "cfg5"):
