@@ -190,6 +190,16 @@ class BatchedGpsReceiver:
         period = float(self._engine.get_params()["watchdog_period_s"])
         return min(first_step_at_least(self._time_after, i, last, period) for last in self._last_watchdog.values())
 
+    def _take(self, n_ms: int) -> np.ndarray:
+        """The next (up to) `n_ms` milliseconds of samples; none when the provider has run dry (its error is kept for run())."""
+        if n_ms <= 0:
+            return np.zeros(0, dtype=np.complex64)
+        try:
+            return np.ascontiguousarray(self.antenna_samples_provider.get_block(n_ms).samples, dtype=np.complex64)
+        except NoMoreSamplesError as e:
+            self._ran_dry = e
+            return np.zeros(0, dtype=np.complex64)
+
     def _scan(self, samples: np.ndarray, now: float) -> None:
         from .tracker import GpsSatelliteTrackingParameters
         self._time_of_last_scan = now
@@ -221,23 +231,24 @@ class BatchedGpsReceiver:
         remaining = n_ms
         while remaining > 0:
             i = self.steps_done
-            s = self._next_scan_step(i)
+            # step i scans with the ten newest chunks, i included -- BEFORE the block is cut: the scan sets the time of the next one,
+            # and the channels it starts look too (at once, when their first millisecond lies a watchdog period into the recording)
+            head = self._take(1) if self._next_scan_step(i) == i else None
+            if head is not None and len(head):
+                self._scan(np.concatenate([self._recent, head])[-ACQUISITION_INTEGRATION_PERIOD_MS * n:], self._time_after(i + 1))
             length = min(remaining, self.block_ms)
-            if s is not None and s > i:
-                length = min(length, s - i)                  # stop right before the millisecond that scans
+            s = self._next_scan_step(i if head is None else i + 1)
+            if s is not None:
+                length = min(length, s - i)                  # stop right before the next millisecond that scans
             w = self._next_watchdog_step(i)
             if w is not None:
                 length = min(length, w - i + 1)              # a millisecond that may drop a satellite ends its block
-            try:
-                block = self.antenna_samples_provider.get_block(length)
-            except NoMoreSamplesError:
+            iq = self._take(length) if head is None else np.concatenate([head, self._take(length - 1)])
+            if len(iq) == 0:
                 if remaining == n_ms:
-                    raise
+                    raise self._ran_dry                      # the provider's own NoMoreSamplesError
                 break
-            iq = np.ascontiguousarray(block.samples, dtype=np.complex64)
             length = len(iq) // n
-            if s == i:                                       # step i scans with the ten newest chunks, i included
-                self._scan(np.concatenate([self._recent, iq[:n]])[-ACQUISITION_INTEGRATION_PERIOD_MS * n:], self._time_after(i + 1))
             t0 = np.array([self._time_after(i + k) for k in range(length)])
             t1 = np.array([self._time_after(i + k + 1) for k in range(length)])
             if self.tracked_satellite_ids_to_tracking_params:
