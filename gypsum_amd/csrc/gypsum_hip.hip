@@ -159,7 +159,6 @@ struct gyp_ctx {
     int spec_sub_ms = 0;         // gyp_debug_set("spec_sub_ms"): target length of a speculative block's sub-blocks (a failed verification costs one); 0 = by rate (spec_sub_ms_for)
     bool spec_redo = true;       // gyp_debug_set("spec_redo"): 0 = A/B switch back to re-running a failed speculation on the throughput kernel
     int prof_wave = 0;           // gyp_debug_set("prof_wave"): which wavefront of workgroup 0 stamps gyp_debug_track_profile's counters
-    int exact_prefetch = 0;      // gyp_debug_set("exact_prefetch"): A/B switch of dll_exact_wave_kernel's software prefetch depth
     bool no_exact_shared = false;   // gyp_debug_set("no_exact_shared"): A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
     int last_exact_path = 0;     // gyp_debug_get("last_exact_path"): the exact-sums kernel of the last plain throughput call (0 none yet, 1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel)
     bool no_spec = false;        // gyp_debug_set("no_spec"): A/B switch: lightly loaded banks use the throughput kernel too
@@ -594,11 +593,15 @@ static int blocks_per_cu(int k) { return k > 8 ? 1 : 16 / k; }
 static int threads_for(int k) { return 64 * largest_divisor_up_to_8(k); }
 
 template <typename KernelT, typename ParamsT>
-static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds) {
+static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds, hipStream_t stream) {
     HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads_for(k)), lds, ctx->stream, p);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads_for(k)), lds, stream, p);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
+}
+template <typename KernelT, typename ParamsT>
+static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds) {   // on the context's stream
+    return launch_k(ctx, kernel, k, grid, p, lds, ctx->stream);
 }
 
 
@@ -682,42 +685,29 @@ static int launch_track_verify(gyp_ctx* ctx, const TrackVerifyParams& p, hipStre
         grid = X * std::max(4, per_xcd - need);
         grid = std::max(X, std::min(grid, n_units / X * X));
     }
-    if (ctx->k == 2) {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(track_verify_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes<2>()));
-        hipLaunchKernelGGL(track_verify_kernel<2>, dim3(grid), dim3(threads_for(2)), lds_bytes<2>(), stream, p);
-    } else if (ctx->k == 16) {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(track_verify_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes<16>()));
-        hipLaunchKernelGGL(track_verify_kernel<16>, dim3(grid), dim3(threads_for(16)), lds_bytes<16>(), stream, p);
-    } else {
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(track_verify_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes<8>()));
-        hipLaunchKernelGGL(track_verify_kernel<8>, dim3(grid), dim3(threads_for(8)), lds_bytes<8>(), stream, p);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
+    if (ctx->k == 2) return launch_k(ctx, track_verify_kernel<2>, 2, grid, p, lds_bytes<2>(), stream);
+    if (ctx->k == 16) return launch_k(ctx, track_verify_kernel<16>, 16, grid, p, lds_bytes<16>(), stream);
+    return launch_k(ctx, track_verify_kernel<8>, 8, grid, p, lds_bytes<8>(), stream);
 }
 
 // tracker.py:297 in float64 for every (channel, millisecond) of [ms_begin, ms_end), then the code loop re-integrated from it
+template <int K>
+static void launch_dll_exact_k(const gyp_ctx* ctx, const DllExactParams& p, int n_units, hipStream_t stream) {
+    if constexpr (K <= 8) {
+        const int grid = std::max(1, std::min((n_units + 3) / 4, ctx->n_cus * 8));
+        hipLaunchKernelGGL(dll_exact_wave_kernel<K>, dim3(grid), dim3(256), 0, stream, p);
+    } else {
+        const int grid = std::max(1, std::min(n_units, ctx->n_cus * 8));
+        hipLaunchKernelGGL(dll_exact_block_kernel<K>, dim3(grid), dim3(256), 0, stream, p);
+    }
+}
 static int launch_dll_exact(gyp_ctx* ctx, const DllExactParams& p, hipStream_t stream) {
     // (round protocol: a round holds at most one sub-block per channel -- the kernels walk n_chan * round_length() units -- so the grid is
     // sized by the longest sub-block like launch_track_verify's, not by the whole block)
     const int n_units = p.n_chan * (p.trk_round ? p.sub.longest : p.ms_end - p.ms_begin);
     if (n_units <= 0) return GYP_OK;
     switch (ctx->k) {
-#define X(K)                                                                                                                   \
-    case K:                                                                                                                    \
-        if constexpr (K <= 8) {                                                                                                \
-            const int grid = std::max(1, std::min((n_units + 3) / 4, ctx->n_cus * 8));                                         \
-            constexpr int KK = K <= 8 ? K : 8;                                                                                 \
-            if (ctx->exact_prefetch == 1) hipLaunchKernelGGL((dll_exact_wave_kernel<KK, 1, 4>), dim3(grid), dim3(256), 0, stream, p); \
-            else hipLaunchKernelGGL((dll_exact_wave_kernel<KK, 0, 4>), dim3(grid), dim3(256), 0, stream, p);                     \
-        } else {                                                                                                               \
-            const int grid = std::max(1, std::min(n_units, ctx->n_cus * 8));                                                   \
-            hipLaunchKernelGGL(dll_exact_block_kernel<K>, dim3(grid), dim3(256), 0, stream, p);                                 \
-        }                                                                                                                      \
-        break;
+#define X(K) case K: launch_dll_exact_k<K>(ctx, p, n_units, stream); break;
         GYP_FOR_EACH_RATE(X)
 #undef X
         default: return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
@@ -2124,7 +2114,7 @@ const DebugKnob kDebugKnobs[] = {
     {"no_pipe", 0, 1, true}, {"no_shared_fwd", 0, 1, true}, {"no_acq_shared_fwd", 0, 1, true}, {"no_acq_split", 0, 1, true}, {"no_spec", 0, 1, true},
     {"spec_debug", 0, 1, true}, {"acq_lanes", 1, gyp_ctx::kMaxAcqLanes, true}, {"track_chunk_ms", 0, 1e6, true}, {"widen_wg_per_cu", 1, 8, true},
     {"symbol_tau", 0, 100, false}, {"dll_prov_bias", -1e6, 1e6, false}, {"spec_fail_at", -1, 2147483647.0, true},
-    {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"exact_prefetch", 0, 1, true}, {"no_exact_shared", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
+    {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"no_exact_shared", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
     {"resample_tile_samples", 1024, 8192, true},
 };
 }  // namespace
@@ -2178,7 +2168,6 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
     GYP_KNOB_NUM("symbol_tau", symbol_tau, float)
     GYP_KNOB_NUM("dll_prov_bias", dll_prov_bias, double)
     GYP_KNOB_NUM("spec_fail_at", spec_fail_at, int)
-    GYP_KNOB_NUM("exact_prefetch", exact_prefetch, int)
     GYP_KNOB_BOOL("no_exact_shared", no_exact_shared)
     if (is("last_exact_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_exact_path; return GYP_OK; }
     GYP_KNOB_NUM("prof_wave", prof_wave, int)

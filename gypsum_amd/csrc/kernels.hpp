@@ -32,6 +32,7 @@
 #include "kernels_track_step.hpp"
 #include "kernels_track_block.hpp"
 #include "kernels_dll_exact.hpp"
+#include "kernels_bank.hpp"
 #include "kernels_acq.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_resample.hpp"

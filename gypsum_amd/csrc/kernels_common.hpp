@@ -84,6 +84,24 @@ __device__ __forceinline__ int round_length(const int32_t* __restrict__ trk_roun
     }
     return len;
 }
+// The (channel, millisecond) units of such a kernel's launch, for any params struct with these fields: unit u is channel u % n_chan
+// in millisecond u / n_chan of [ms_begin, ms_end) or, under the round protocol, of the channel's sub-block trk_round[ch].
+template <typename ParamsT>
+__device__ __forceinline__ int unit_span(const ParamsT& p) {   // milliseconds per channel
+    return p.trk_round ? round_length(p.trk_round, p.n_chan, p.sub, p.n_ms) : p.ms_end - p.ms_begin;
+}
+template <typename ParamsT>
+__device__ __forceinline__ bool unit_decode(const ParamsT& p, int u, int& ch, int& ms) {   // false: no such unit in this round
+    ms = p.ms_begin + u / p.n_chan;
+    ch = u % p.n_chan;             // the channels of a millisecond are neighbours: shared IQ
+    if (p.trk_round) {
+        const int sub = p.trk_round[ch];
+        if (sub < 0) return false;
+        ms = p.sub.begin(sub) + u / p.n_chan;
+        if (ms >= p.sub.end(sub, p.n_ms)) return false;
+    }
+    return true;
+}
 
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector-memory queue (s_waitcnt
 // vmcnt(0)), which in a latency-bound loop means waiting for prefetches and record stores nobody reads here.

@@ -40,6 +40,7 @@ __device__ __forceinline__ double2 horner64(double2 acc, double2 w, double2 x) {
     return make_double2(fma(acc.x, w.x, fma(-acc.y, w.y, x.x)), fma(acc.x, w.y, fma(acc.y, w.x, x.y)));
 }
 __device__ __forceinline__ double2 cvt64(cf x) { return make_double2((double)x.x, (double)x.y); }
+__device__ __forceinline__ double2 cvt64(double2 x) { return x; }   // (samples staged in LDS are converted already)
 // One wavefront per (channel, millisecond), any K <= 8.  With s = K q + r the samples are taken in REPLICA-aligned windows:
 // "virtual chip" m (m = -1 .. 1022) is the K samples n = K m + r + i, i < K -- exactly the samples that meet replica chip
 // j = (m - q) mod 1023 at lag s -- so no window is split between two code chips and nothing in the arithmetic depends on r
@@ -53,12 +54,24 @@ __device__ __forceinline__ double2 cvt64(cf x) { return make_double2((double)x.x
 // windows are folded last one first with the window-stride rotation S = rho^(64 K) (Horner again: acc = acc S + term), the
 // lane's anchor carrier (times rho^(K-1) for E) is applied once at the end, six DPP reductions finish the unit.  No LDS, no
 // barrier; ~46 float64 operations + 19 converts per window.
+// dll_exact_shared_kernel folds the same windows out of LDS: there is ONE copy of the window arithmetic, so the two agree bit for bit.
+struct ExactChips { float cm1, c0, cp1; };           // replica chips j - 1, j, j + 1 of a window
+__device__ __forceinline__ ExactChips exact_window_chips(const float* chipf, int m, int q) {
+    int j = m - q;
+    j = j < 0 ? j + kChips : j;                      // (m - q) mod 1023 for m >= 0; m = -1 -> (1022 - q) mod 1023 (q <= 1022)
+    j = j < 0 ? j + kChips : j;
+    const float* cp = chipf + j + kChips;
+    return ExactChips{cp[-1], cp[0], cp[1]};
+}
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Walign-mismatch"   // two samples in one 16-byte load at any sample offset: 8-byte alignment is intended
+typedef float4 __attribute__((aligned(8))) float4_a8;
+__device__ __forceinline__ float4 load_pair_a8(const cf* src, int pair = 0) { return reinterpret_cast<const float4_a8*>(src)[pair]; }
+#pragma clang diagnostic pop
 template <int K, bool EDGE>
-__device__ __forceinline__ void exact_window(const cf* __restrict__ block, int m, int r, int q, const float* __restrict__ chipf,
-                                             double2 rho, double2 step, double2& sp, double2& se, double2& sl) {
+__device__ __forceinline__ ExactChips exact_window_load(const cf* __restrict__ block, int m, int r, int q, const float* __restrict__ chipf, cf (&x)[K]) {
     constexpr int N = K * kChips;
     const int n0 = K * m + r;                        // first sample of the window; [n0, n0 + K) leaves [0, N) only at m = -1 / 1022
-    cf x[K];
     if constexpr (EDGE) {
 #pragma unroll
         for (int i = 0; i < K; ++i) {
@@ -68,23 +81,20 @@ __device__ __forceinline__ void exact_window(const cf* __restrict__ block, int m
             x[i] = make_float2(in ? v.x : 0.f, in ? v.y : 0.f);
         }
     } else {
-        typedef float4 __attribute__((aligned(8))) float4_a8;
-        typedef float2 __attribute__((aligned(8))) float2_a8;
         const cf* src = block + n0;
 #pragma unroll
         for (int i = 0; i + 1 < K; i += 2) {
-            const float4 v = *reinterpret_cast<const float4_a8*>(src + i);
+            const float4 v = load_pair_a8(src + i);
             x[i] = make_float2(v.x, v.y);
             x[i + 1] = make_float2(v.z, v.w);
         }
-        if (K & 1) x[K - 1] = *reinterpret_cast<const float2_a8*>(src + K - 1);
+        if (K & 1) x[K - 1] = src[K - 1];
     }
-    int j = m - q;
-    j = j < 0 ? j + kChips : j;                      // (m - q) mod 1023 for m >= 0; m = -1 -> (1022 - q) mod 1023 (q <= 1022)
-    j = j < 0 ? j + kChips : j;
-    const float* cp = chipf + j + kChips;
-    const float cm1 = cp[-1], c0 = cp[0], cp1 = cp[1];
-    const double dj = (double)c0, gl = (double)(cm1 - c0), ge = (double)(c0 - cp1);
+    return exact_window_chips(chipf, m, q);
+}
+template <int K, typename S>   // S: cf (converted where the Horner chain uses it) or double2
+__device__ __forceinline__ void exact_window_fold(const S (&x)[K], const ExactChips& c, double2 rho, double2 step, double2& sp, double2& se, double2& sl) {
+    const double dj = (double)c.c0, gl = (double)(c.cm1 - c.c0), ge = (double)(c.c0 - c.cp1);
     double2 h = cvt64(x[K - 1]);
 #pragma unroll
     for (int i = K - 2; i >= 0; --i) h = horner64(h, rho, cvt64(x[i]));
@@ -93,6 +103,13 @@ __device__ __forceinline__ void exact_window(const cf* __restrict__ block, int m
     se = horner64(se, step, make_double2(ge * xe.x, ge * xe.y));
     sl = horner64(sl, step, make_double2(gl * xl.x, gl * xl.y));
 }
+template <int K, bool EDGE>
+__device__ __forceinline__ void exact_window(const cf* __restrict__ block, int m, int r, int q, const float* __restrict__ chipf,
+                                             double2 rho, double2 step, double2& sp, double2& se, double2& sl) {
+    cf x[K];
+    const ExactChips c = exact_window_load<K, EDGE>(block, m, r, q, chipf, x);
+    exact_window_fold<K>(x, c, rho, step, sp, se, sl);
+}
 template <int K>
 __device__ __forceinline__ double2 cpow_km1(double2 w) {   // w^(K-1), K <= 8
     double2 r = make_double2(1.0, 0.0);
@@ -100,124 +117,74 @@ __device__ __forceinline__ double2 cpow_km1(double2 w) {   // w^(K-1), K <= 8
     for (int i = 0; i < K - 1; ++i) r = cmul64(r, w);
     return r;
 }
-// exact_window in two halves for the software-prefetched form of the kernel: the window's samples and its three code chips are
-// REQUESTED (load) one or two windows before they are folded into the sums (fold).
-template <int K>
-struct ExactWin {
-    cf x[K];
-    float cm1, c0, cp1;
+// What the windows of one (channel, millisecond) are summed with: the carrier (du cycles per sample, u0 at the block's first
+// sample), the lag K q + r and the satellite's code.
+struct ExactUnit {
+    double du, u0;
+    int q, r;
+    const float* chipf;
 };
-template <int K, bool EDGE>
-__device__ __forceinline__ void exact_window_load(const cf* __restrict__ block, int m, int r, int q, const float* __restrict__ chipf, ExactWin<K>& w) {
-    constexpr int N = K * kChips;
-    const int n0 = K * m + r;
-    if constexpr (EDGE) {
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const int n = n0 + i;
-            const cf v = block[min(max(n, 0), N - 1)];
-            const bool in = n >= 0 && n < N;
-            w.x[i] = make_float2(in ? v.x : 0.f, in ? v.y : 0.f);
-        }
-    } else {
-        typedef float4 __attribute__((aligned(8))) float4_a8;
-        typedef float2 __attribute__((aligned(8))) float2_a8;
-        const cf* src = block + n0;
-#pragma unroll
-        for (int i = 0; i + 1 < K; i += 2) {
-            const float4 v = *reinterpret_cast<const float4_a8*>(src + i);
-            w.x[i] = make_float2(v.x, v.y);
-            w.x[i + 1] = make_float2(v.z, v.w);
-        }
-        if (K & 1) w.x[K - 1] = *reinterpret_cast<const float2_a8*>(src + K - 1);
-    }
-    int j = m - q;
-    j = j < 0 ? j + kChips : j;
-    j = j < 0 ? j + kChips : j;
-    const float* cp = chipf + j + kChips;
-    w.cm1 = cp[-1]; w.c0 = cp[0]; w.cp1 = cp[1];
-}
 template <int K>
-__device__ __forceinline__ void exact_window_fold(const ExactWin<K>& w, double2 rho, double2 step, double2& sp, double2& se, double2& sl) {
-    const double dj = (double)w.c0, gl = (double)(w.cm1 - w.c0), ge = (double)(w.c0 - w.cp1);
-    double2 h = cvt64(w.x[K - 1]);
-#pragma unroll
-    for (int i = K - 2; i >= 0; --i) h = horner64(h, rho, cvt64(w.x[i]));
-    const double2 xe = cvt64(w.x[K - 1]), xl = cvt64(w.x[0]);
-    sp = horner64(sp, step, make_double2(dj * h.x, dj * h.y));
-    se = horner64(se, step, make_double2(ge * xe.x, ge * xe.y));
-    sl = horner64(sl, step, make_double2(gl * xl.x, gl * xl.y));
+__device__ __forceinline__ ExactUnit exact_unit(const DllExactParams& p, const SpecIn& in, int sat, int ms) {
+    ExactUnit u;
+    u.chipf = p.chipf + (sat - 1) * 2048;
+    u.du = in.doppler * p.inv_fs;
+    u.u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
+    const int sN = __builtin_amdgcn_readfirstlane(mod_n(in.code_phase, K * kChips));
+    u.q = sN / K; u.r = sN % K;
+    return u;
 }
-// PF: software prefetch depth in windows (0: the windows are loaded where they are folded, two at a time by unrolling; 1, 2: the
-// loads of window c - PF are issued before window c is folded -- 16 more sample registers per step of depth at K = 8).
-// Measured at the headline batch (profiles/r04_exact_ab.txt): PF 0 at 5 wavefronts per SIMD 8.13-8.22 ms per 1536 channels x
-// 1000 ms; PF 1 (128 VGPRs, 4 per SIMD) 10.27; PF 2 10.32; PF 0 squeezed to 6 per SIMD (80 VGPRs, 7 spills) 9.72; PF 1 at 5 per
-// SIMD (20 spills) 10.49.  The waits VERDICT r03 pointed at are covered best by the fifth wavefront: PF 0 stays the default.
-template <int K, int PF, int MINW = 4>
-__global__ __launch_bounds__(256, MINW) void dll_exact_wave_kernel(DllExactParams p) {
+// A lane's three window sums -> the unit's discriminator: the lane's anchor carrier (times rho^(K-1) for E), the wavefront's sums, the
+// store.  n_anchor = K (lane - 1) + r, the first sample of the lane's first window: the kernel forms it, next to the same expression
+// of that window's load (formed here, the compiler no longer sees the two as one and the wave kernel takes more registers).
+template <int K>
+__device__ __forceinline__ void exact_unit_store(double2 sp, double2 se, double2 sl, const ExactUnit& u, int lane, int n_anchor, double* out) {
+    const double2 rho_a = carrier64(u.du);
+    const double2 anchor = carrier64(u.u0 + u.du * (double)n_anchor);
+    const double2 pp = cmul64(sp, anchor), ee = cmul64(cmul64(se, cpow_km1<K>(rho_a)), anchor), ll = cmul64(sl, anchor);
+    double acc[6] = {pp.x, pp.y, ee.x, ee.y, ll.x, ll.y};
+#pragma unroll
+    for (int v = 0; v < 6; ++v) acc[v] = wave_sum_last(acc[v]);
+    if (lane == 63) *out = dll_discriminator_exact(acc);
+}
+// Unit u of a launch -> its (channel, millisecond); false: not this round's or not part of the re-run.  Uniform over the unit's threads.
+__device__ __forceinline__ bool exact_unit_decode(const DllExactParams& p, int u, int& ch, int& ms) {
+    if (!unit_decode(p, u, ch, ms)) return false;
+    if (p.only_if && !p.only_if[ch]) return false;
+    if (p.from_sub && ms < p.sub.begin(p.from_sub[ch])) return false;
+    return true;
+}
+// The windows are loaded where they are folded, two at a time by unrolling; a fifth wavefront per SIMD covers the waits.  Requesting
+// a window one or two ahead of its fold was measured and rejected (10.3 against 8.2 ms, profiles/r04_exact_ab.txt; commit ffb6ef5
+// is the last one that carried that code).
+template <int K>
+__global__ __launch_bounds__(256, 4) void dll_exact_wave_kernel(DllExactParams p) {
     static_assert(K <= 8, "a window's samples in registers");
     constexpr int N = K * kChips;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int n_units = p.n_chan * (p.trk_round ? round_length(p.trk_round, p.n_chan, p.sub, p.n_ms) : p.ms_end - p.ms_begin);
+    const int n_units = p.n_chan * unit_span(p);
     const int n_groups = (n_units + 3) >> 2;
     for (int g = blockIdx.x; g < n_groups; g += gridDim.x) {
         // four consecutive units per workgroup, consecutive groups inside an XCD's slice: the channels of a stream-ms (shared IQ) meet in one L2
         const int u = ((n_groups & 7) ? g : xcd_contiguous(g, n_groups)) * 4 + wave;
         if (u >= n_units) continue;
-        int ms = p.ms_begin + u / p.n_chan;
-        const int ch = u % p.n_chan;
-        if (p.trk_round) {                                        // wave-uniform
-            const int sub = p.trk_round[ch];
-            if (sub < 0) continue;
-            ms = p.sub.begin(sub) + u / p.n_chan;
-            if (ms >= p.sub.end(sub, p.n_ms)) continue;
-        }
-        if (p.only_if && !p.only_if[ch]) continue;                // wave-uniform
-        if (p.from_sub && ms < p.sub.begin(p.from_sub[ch])) continue;
+        int ch, ms;
+        if (!exact_unit_decode(p, u, ch, ms)) continue;           // wave-uniform
         const int64_t at = (int64_t)ch * p.n_ms + ms;
         const SpecIn in = p.spec[at];
-        if (in.key == kSpecKeyLost) continue;                     // wave-uniform
+        if (in.key == kSpecKeyLost) continue;                     // wave-uniform: the tracker never processed it
         const ChanState* st = p.states + ch;
         const int sat = __builtin_amdgcn_readfirstlane(st->sat_id), stream = __builtin_amdgcn_readfirstlane(st->stream);
         const cf* block = p.iq + (int64_t)stream * p.stream_stride + (int64_t)ms * N;
-        const float* chipf = p.chipf + (sat - 1) * 2048;
-        const double du = in.doppler * p.inv_fs;
-        const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
-        const int sN = __builtin_amdgcn_readfirstlane(mod_n(in.code_phase, N));
-        const int q = sN / K, r = sN % K;
+        const ExactUnit x = exact_unit<K>(p, in, sat, ms);
         double2 sp = make_double2(0.0, 0.0), se = sp, sl = sp;
-        if constexpr (PF == 0) {
-            const double2 rho = carrier64(du), step = carrier64(du * (double)(K * 64));
-            exact_window<K, true>(block, lane + 64 * 15 - 1, r, q, chipf, rho, step, sp, se, sl);     // holds window 1022 (lane 63)
+        const double2 rho = carrier64(x.du), step = carrier64(x.du * (double)(K * 64));
+        exact_window<K, true>(block, lane + 64 * 15 - 1, x.r, x.q, x.chipf, rho, step, sp, se, sl);     // holds window 1022 (lane 63)
 #pragma unroll 2
-            for (int c = 14; c >= 1; --c) exact_window<K, false>(block, lane + 64 * c - 1, r, q, chipf, rho, step, sp, se, sl);
-            exact_window<K, true>(block, lane - 1, r, q, chipf, rho, step, sp, se, sl);               // holds window -1 (lane 0)
-        } else {
-            // windows 15 (edge), 14 .. 1, 0 (edge), each requested PF windows before it is folded; the carriers are formed under
-            // the first requests
-            ExactWin<K> w[PF + 1];
-            exact_window_load<K, true>(block, lane + 64 * 15 - 1, r, q, chipf, w[0]);
-            if constexpr (PF == 2) exact_window_load<K, false>(block, lane + 64 * 14 - 1, r, q, chipf, w[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const double2 rho = carrier64(du), step = carrier64(du * (double)(K * 64));
-#pragma unroll
-            for (int c = 15; c >= 0; --c) {
-                const int cn = c - PF;                                      // the window requested now
-                if (cn >= 1) exact_window_load<K, false>(block, lane + 64 * cn - 1, r, q, chipf, w[(15 - cn) % (PF + 1)]);
-                else if (cn == 0) exact_window_load<K, true>(block, lane - 1, r, q, chipf, w[(15 - cn) % (PF + 1)]);
-                __builtin_amdgcn_sched_barrier(0);
-                exact_window_fold<K>(w[(15 - c) % (PF + 1)], rho, step, sp, se, sl);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        const double2 rho_a = carrier64(du);
-        const double2 anchor = carrier64(u0 + du * (double)(K * (lane - 1) + r));
-        const double2 pp = cmul64(sp, anchor), ee = cmul64(cmul64(se, cpow_km1<K>(rho_a)), anchor), ll = cmul64(sl, anchor);
-        double acc[6] = {pp.x, pp.y, ee.x, ee.y, ll.x, ll.y};
-#pragma unroll
-        for (int v = 0; v < 6; ++v) acc[v] = wave_sum_last(acc[v]);
-        if (lane == 63) p.disc_out[at] = dll_discriminator_exact(acc);
+        for (int c = 14; c >= 1; --c) exact_window<K, false>(block, lane + 64 * c - 1, x.r, x.q, x.chipf, rho, step, sp, se, sl);
+        exact_window<K, true>(block, lane - 1, x.r, x.q, x.chipf, rho, step, sp, se, sl);               // holds window -1 (lane 0)
+        exact_unit_store<K>(sp, se, sl, x, lane, K * (lane - 1) + x.r, p.disc_out + at);
     }
 }
 // ---- the same sums with a stream's millisecond staged once for all its channels (throughput path) -----------------------------
@@ -282,18 +249,6 @@ struct DllExactSharedParams {
     const ExactGroup* groups;
     const int32_t* n_groups;
 };
-template <int K>
-__device__ __forceinline__ void exact_window_fold64(const double2 (&x)[K], float cm1, float c0, float cp1, double2 rho, double2 step,
-                                                    double2& sp, double2& se, double2& sl) {   // exact_window_fold on converted samples
-    const double dj = (double)c0, gl = (double)(cm1 - c0), ge = (double)(c0 - cp1);
-    double2 h = x[K - 1];
-#pragma unroll
-    for (int i = K - 2; i >= 0; --i) h = horner64(h, rho, x[i]);
-    const double2 xe = x[K - 1], xl = x[0];
-    sp = horner64(sp, step, make_double2(dj * h.x, dj * h.y));
-    se = horner64(se, step, make_double2(ge * xe.x, ge * xe.y));
-    sl = horner64(sl, step, make_double2(gl * xl.x, gl * xl.y));
-}
 // Workgroup b walks items [n_items b / grid, n_items (b + 1) / grid) of (group, millisecond), milliseconds innermost: consecutive
 // milliseconds of a stream stay on one CU.  The two roles run separate loops with the same two barriers per item (wave-uniform
 // branch), so that the producers' 64 sample registers are not live in the consumers' loop.
@@ -318,18 +273,17 @@ __global__ __launch_bounds__(kExactSharedThreads) void dll_exact_shared_kernel(D
         s_x[np + np / K] = make_double2(0.0, 0.0);
     }
     if (wave >= kExactSharedConsumers) {
-        typedef float4 __attribute__((aligned(8))) float4_a8;
         const int pt = lane + 64 * (wave - kExactSharedConsumers);
         float4 hold[LOADS];                               // pair t = pt + PT j: samples 2t, 2t + 1 (lane order: 1 KiB per wavefront and load)
         auto request = [&](int64_t item) {
             const int g = (int)(item / span), ms = p.ms_begin + (int)(item % span);
             const int stream = __builtin_amdgcn_readfirstlane(ps.groups[g].stream);
-            const float4_a8* block = reinterpret_cast<const float4_a8*>(p.iq + (int64_t)stream * p.stream_stride + (int64_t)ms * N);
+            const cf* block = p.iq + (int64_t)stream * p.stream_stride + (int64_t)ms * N;
 #pragma unroll
             for (int j = 0; j < LOADS; ++j) {
                 const int t = pt + PT * j;
-                if (PT * j + PT <= PAIRS) hold[j] = block[t];
-                else hold[j] = t < PAIRS ? (float4)block[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (PT * j + PT <= PAIRS) hold[j] = load_pair_a8(block, t);
+                else hold[j] = t < PAIRS ? load_pair_a8(block, t) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         };
         request(lo);
@@ -358,40 +312,62 @@ __global__ __launch_bounds__(kExactSharedThreads) void dll_exact_shared_kernel(D
             const int64_t at = (int64_t)ch * p.n_ms + ms;
             const SpecIn in = p.spec[at];
             if (in.key != kSpecKeyLost) {                 // wave-uniform
-                const int sat = __builtin_amdgcn_readfirstlane(p.states[ch].sat_id);
-                const float* chipf = p.chipf + (sat - 1) * 2048;
-                const double du = in.doppler * p.inv_fs;
-                const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
-                const int sN = __builtin_amdgcn_readfirstlane(mod_n(in.code_phase, N));
-                const int q = sN / K, r = sN % K;
+                const ExactUnit u = exact_unit<K>(p, in, __builtin_amdgcn_readfirstlane(p.states[ch].sat_id), ms);
                 int off[K];                               // sample i of a window: r + i units on, one more behind the padding
 #pragma unroll
-                for (int i = 0; i < K; ++i) off[i] = r + i + (r + i >= K ? 1 : 0);
+                for (int i = 0; i < K; ++i) off[i] = u.r + i + (u.r + i >= K ? 1 : 0);
                 double2 sp = make_double2(0.0, 0.0), se = sp, sl = sp;
-                const double2 rho = carrier64(du), step = carrier64(du * (double)(K * 64));
+                const double2 rho = carrier64(u.du), step = carrier64(u.du * (double)(K * 64));
 #pragma unroll 2
                 for (int c = 15; c >= 0; --c) {
-                    const int m = lane + 64 * c - 1;
                     const double2* w = win0 + (K + 1) * 64 * c;
                     double2 x[K];
 #pragma unroll
                     for (int i = 0; i < K; ++i) x[i] = w[off[i]];
-                    int j = m - q;
-                    j = j < 0 ? j + kChips : j;
-                    j = j < 0 ? j + kChips : j;
-                    const float* cp = chipf + j + kChips;
-                    exact_window_fold64<K>(x, cp[-1], cp[0], cp[1], rho, step, sp, se, sl);
+                    exact_window_fold<K>(x, exact_window_chips(u.chipf, lane + 64 * c - 1, u.q), rho, step, sp, se, sl);
                 }
-                const double2 rho_a = carrier64(du);
-                const double2 anchor = carrier64(u0 + du * (double)(K * (lane - 1) + r));
-                const double2 pp = cmul64(sp, anchor), ee = cmul64(cmul64(se, cpow_km1<K>(rho_a)), anchor), ll = cmul64(sl, anchor);
-                double acc[6] = {pp.x, pp.y, ee.x, ee.y, ll.x, ll.y};
-#pragma unroll
-                for (int v = 0; v < 6; ++v) acc[v] = wave_sum_last(acc[v]);
-                if (lane == 63) p.disc_out[at] = dll_discriminator_exact(acc);
+                exact_unit_store<K>(sp, se, sl, u, lane, K * (lane - 1) + u.r, p.disc_out + at);
             }
         }
         __syncthreads();                                  // done with the millisecond
+    }
+}
+// The first NV of the exact sums of one millisecond at lag `lag`, by a whole workgroup of T threads walking the block
+// (exact_epl_generic), with the carrier the millisecond ran with (`in`): the wavefronts' sums meet in `part` and, behind a barrier,
+// thread 0 alone runs use(ex) on their sum.  (A callable, not an array handed back: an array filled under `tid == 0` and read by the
+// caller cost both kernels some 40 registers.)  The two users add the wavefronts in different associations and each keeps its own,
+// they are not the same bits: PAIRS (p0 + p1) + (p2 + p3), else ((p0 + p1) + p2) + p3.  GUARD: a barrier in front of the hand-over,
+// for a caller that has none between thread 0's reads of `part` and the next call.
+template <int K, int T, int NV, bool PAIRS, bool GUARD, typename ParamsT, typename UseT>
+__device__ __forceinline__ void workgroup_exact_sums(const cf* block, const ParamsT& p, const SpecIn& in, int ms, int lag,
+                                                     const float* chipf, int tid, double (*part)[6], UseT use) {
+    static_assert(!PAIRS || T == 256, "four wavefronts");
+    const double du = in.doppler * p.inv_fs;
+    const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
+    double acc[6];
+    exact_epl_generic<K, T>(block, u0, du, lag, chipf, tid, acc);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = wave_sum_last(acc[v]);
+    if (GUARD) __syncthreads();
+    if ((tid & 63) == 63) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) part[tid >> 6][v] = acc[v];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double ex[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            if (PAIRS) {
+                ex[v] = (part[0][v] + part[1][v]) + (part[2][v] + part[3][v]);
+            } else {
+                double t = part[0][v];
+#pragma unroll
+                for (int w = 1; w < T / 64; ++w) t += part[w][v];
+                ex[v] = t;
+            }
+        }
+        use(ex);
     }
 }
 // Rates above 8 samples per chip (16.368 ... 49.104 Msps): one 256-thread workgroup per unit walks the block (exact_epl_generic).
@@ -400,42 +376,17 @@ __global__ __launch_bounds__(256) void dll_exact_block_kernel(DllExactParams p) 
     constexpr int N = K * kChips;
     __shared__ double part[4][6];
     const int tid = threadIdx.x;
-    const int n_units = p.n_chan * (p.trk_round ? round_length(p.trk_round, p.n_chan, p.sub, p.n_ms) : p.ms_end - p.ms_begin);
+    const int n_units = p.n_chan * unit_span(p);
     for (int v = blockIdx.x; v < n_units; v += gridDim.x) {
-        const int u = (n_units & 7) ? v : xcd_contiguous(v, n_units);
-        int ms = p.ms_begin + u / p.n_chan;
-        const int ch = u % p.n_chan;
-        if (p.trk_round) {                                        // uniform
-            const int sub = p.trk_round[ch];
-            if (sub < 0) continue;
-            ms = p.sub.begin(sub) + u / p.n_chan;
-            if (ms >= p.sub.end(sub, p.n_ms)) continue;
-        }
-        if (p.only_if && !p.only_if[ch]) continue;                // uniform
-        if (p.from_sub && ms < p.sub.begin(p.from_sub[ch])) continue;
+        int ch, ms;
+        if (!exact_unit_decode(p, (n_units & 7) ? v : xcd_contiguous(v, n_units), ch, ms)) continue;   // uniform
         const int64_t at = (int64_t)ch * p.n_ms + ms;
         const SpecIn in = p.spec[at];
         if (in.key == kSpecKeyLost) continue;                     // uniform
         const ChanState* st = p.states + ch;
         const cf* block = p.iq + (int64_t)st->stream * p.stream_stride + (int64_t)ms * N;
-        const double du = in.doppler * p.inv_fs;
-        const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
-        double acc[6];
-        exact_epl_generic<K, 256>(block, u0, du, mod_n(in.code_phase, N), p.chipf + (st->sat_id - 1) * 2048, tid, acc);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc[k] = wave_sum_last(acc[k]);
-        __syncthreads();                       // the previous unit's reader is done with `part`
-        if ((tid & 63) == 63) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) part[tid >> 6][k] = acc[k];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double ex[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ex[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-            p.disc_out[at] = dll_discriminator_exact(ex);
-        }
+        workgroup_exact_sums<K, 256, 6, true, true>(block, p, in, ms, mod_n(in.code_phase, N), p.chipf + (st->sat_id - 1) * 2048, tid, part,
+                                                    [&](const double (&ex)[6]) { p.disc_out[at] = dll_discriminator_exact(ex); });
     }
 }
 
@@ -476,6 +427,11 @@ struct DllScanParams {
 constexpr int kScanThreads = 256;
 constexpr int kScanChunk = 512;     // milliseconds staged in LDS at a time
 constexpr int kSpecKeyRepaired = -3;
+// The satellite's +-1 code (twice over) into LDS, by the whole workgroup: once per launch, at the first millisecond whose sums it forms.
+__device__ __forceinline__ void scan_stage_code(float* s_chipf, const float* chipf, int tid) {
+    for (int k = tid; k < 2048; k += kScanThreads) s_chipf[k] = chipf[k];
+    __syncthreads();
+}
 template <int K>
 __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p) {
     constexpr int N = K * kChips;
@@ -486,7 +442,7 @@ __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p)
     __shared__ int s_cpout[kScanChunk];     // exact code phase after the update (the record's)
     __shared__ int s_key[kScanChunk];       // SpecIn::key; kSpecKeyRepaired once the millisecond has been repaired
     __shared__ double part[kScanThreads / 64][6];
-    __shared__ float s_chipf[2048];         // this satellite's +-1 code twice over, fetched at the first repair
+    __shared__ float s_chipf[2048];         // this satellite's +-1 code twice over (scan_stage_code)
     __shared__ double s_a;
     __shared__ int s_s, s_pos, s_repairs;
     __shared__ int s_nund;
@@ -537,26 +493,12 @@ __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p)
             for (int u = 0; u < n_und; ++u) {   // uniform; rare (test hook GYP_SYMBOL_TAU = 10: every millisecond)
                 const int ms = c0 + s_und[u];
                 const SpecIn in = p.spec[row + ms];
-                const double du = in.doppler * p.inv_fs;
-                const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
-                if (!have_code) {
-                    for (int k = tid; k < 2048; k += kScanThreads) s_chipf[k] = chipf[k];
-                    have_code = true;
-                    __syncthreads();
-                }
+                if (!have_code) { scan_stage_code(s_chipf, chipf, tid); have_code = true; }   // uniform
                 int lag = mod_n(in.code_phase, N) + p.rec_out[row + ms].peak_offset;   // (before any repair moves the offset: same lag)
                 lag = lag >= N ? lag - N : lag;
-                double acc[6];
-                exact_epl_generic<K, kScanThreads>(stream + (int64_t)ms * N, u0, du, lag, s_chipf, tid, acc);
-                const double re = wave_sum_last(acc[0]);
-                if ((tid & 63) == 63) part[tid >> 6][0] = re;
-                __syncthreads();
-                if (tid == 0) {
-                    double t = part[0][0];
-#pragma unroll
-                    for (int w = 1; w < kScanThreads / 64; ++w) t += part[w][0];
-                    p.rec_out[row + ms].pseudosymbol = t > 0.0 ? 1 : (t < 0.0 ? -1 : 0);
-                }
+                workgroup_exact_sums<K, kScanThreads, 1, false, false>(   // (Re of the coherent prompt value is all the pseudosymbol needs)
+                    stream + (int64_t)ms * N, p, in, ms, lag, s_chipf, tid, part,
+                    [&](const double (&re)[1]) { p.rec_out[row + ms].pseudosymbol = re[0] > 0.0 ? 1 : (re[0] < 0.0 ? -1 : 0); });
                 __syncthreads();
             }
         }
@@ -611,31 +553,8 @@ __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p)
             {   // repair: this millisecond's float64 sums for the lag the exact loop is at
                 const int ms = c0 + pos;
                 const SpecIn in = p.spec[row + ms];
-                const double du = in.doppler * p.inv_fs;
-                const double u0 = carrier_cycles(in.doppler, p.start_time[ms], in.carrier_phase);
-                if (!have_code) {   // uniform
-                    for (int k = tid; k < 2048; k += kScanThreads) s_chipf[k] = chipf[k];
-                    have_code = true;
-                    __syncthreads();
-                }
-                double acc[6];
-                exact_epl_generic<K, kScanThreads>(stream + (int64_t)ms * N, u0, du, mod_n(s_s, N), s_chipf, tid, acc);
-#pragma unroll
-                for (int v = 0; v < 6; ++v) acc[v] = wave_sum_last(acc[v]);
-                if ((tid & 63) == 63) {
-#pragma unroll
-                    for (int v = 0; v < 6; ++v) part[tid >> 6][v] = acc[v];
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    double ex[6];
-#pragma unroll
-                    for (int v = 0; v < 6; ++v) {
-                        double t = part[0][v];
-#pragma unroll
-                        for (int w = 1; w < kScanThreads / 64; ++w) t += part[w][v];
-                        ex[v] = t;
-                    }
+                if (!have_code) { scan_stage_code(s_chipf, chipf, tid); have_code = true; }   // uniform
+                workgroup_exact_sums<K, kScanThreads, 6, false, false>(stream + (int64_t)ms * N, p, in, ms, mod_n(s_s, N), s_chipf, tid, part, [&](const double (&ex)[6]) {
                     s_disc[pos] = dll_discriminator_exact(ex);
                     s_key[pos] = kSpecKeyRepaired;
                     if (p.rec_out) {   // the arg-max LAG stands; its index in the profile of the PRN rolled by s moves with s
@@ -648,7 +567,7 @@ __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p)
                     if (p.prof_delta && ms >= p.prof_from)
                         p.prof_delta[(int64_t)ch * p.prof_depth + (ms - p.prof_from)] = mod_n(s_s, N) - mod_n(in.code_phase, N);
                     ++s_repairs;
-                }
+                });
                 __syncthreads();
             }
         }
@@ -671,224 +590,6 @@ __global__ __launch_bounds__(kScanThreads) void dll_scan_kernel(DllScanParams p)
             if (p.hist_out) p.hist_out[ch] = x;
             if (p.final) { p.states[ch].dll_phase = s_a; p.states[ch].code_phase = s_s; }
         }
-    }
-}
-
-// End of a block under the round protocol (one workgroup per channel, main stream, behind the last verify kernels): the reports of
-// the last two rounds are consulted the way the tracking kernel would in two more rounds.  A channel whose every sub-block has
-// held takes the exact code loop's final state; any other one is handed to the transform kernel (bad / bad_from), which restarts
-// from ckpt[bad_from] -- where the channel never started that sub-block, its present state IS that checkpoint.
-struct SpecFinalizeParams {
-    SpecCtl* ctl;
-    const int32_t* trk;
-    const int32_t* fail;
-    ChanState* states;
-    ChanState* ckpt;
-    const DllExact* hist;
-    DllExact* exact;
-    int32_t* bad;
-    int32_t* bad_from;
-    int32_t* stats;      // [4] += {-, -, sub-block re-dos, channels handed to the transform kernel}
-    int32_t n_chan, n_sub, rounds;
-};
-__global__ __launch_bounds__(256) void spec_finalize_kernel(SpecFinalizeParams p) {
-    const int ch = blockIdx.x;
-    if (ch >= p.n_chan) return;
-    __shared__ int s_copy_to;
-    if (threadIdx.x == 0) {
-        SpecCtl c = p.ctl[ch];
-        for (int R = p.rounds; R < p.rounds + 2; ++R) {
-            if (c.dead || R < 2 || c.rb_round == R - 1) continue;
-            const int s = p.trk[(size_t)(R - 2) * p.n_chan + ch];
-            if (s >= 0 && p.fail[(size_t)(R - 2) * p.n_chan + ch] != kNoFail) { c.dead = 1; c.cursor = s; }
-        }
-        const bool ok = !c.dead && c.cursor >= p.n_sub;
-        p.bad[ch] = ok ? 0 : 1;
-        p.bad_from[ch] = ok ? kNoFail : c.cursor;
-        s_copy_to = -1;
-        if (ok) {
-            const DllExact x = p.hist[(size_t)p.n_sub * p.n_chan + ch];
-            p.states[ch].dll_phase = x.dll; p.states[ch].code_phase = x.code_phase;
-            p.exact[ch] = x;
-        } else {
-            atomicAdd(p.stats + 3, 1);
-            if (!c.dead) s_copy_to = c.cursor;   // ran out of rounds in front of a sub-block it never started
-        }
-        if (c.redos) atomicAdd(p.stats + 2, c.redos);
-        p.ctl[ch] = c;
-    }
-    __syncthreads();
-    if (s_copy_to >= 0) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(p.states + ch);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(p.ckpt + (size_t)s_copy_to * p.n_chan + ch);
-        for (int i = threadIdx.x; i < (int)(sizeof(ChanState) / 4); i += blockDim.x) dst[i] = src[i];
-    }
-}
-
-// {a, b, c, d} -> p[0..3] on the stream (telemetry headers: no host buffer has to outlive the call)
-// out[0] = how many of v[0 .. n) are non-zero (one wavefront)
-__global__ void count_nonzero_kernel(const int32_t* __restrict__ v, int32_t n, int32_t* __restrict__ out) {
-    int c = 0;
-    for (int i = threadIdx.x; i < n; i += 64) c += v[i] != 0 ? 1 : 0;
-    for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off, 64);
-    if (threadIdx.x == 0) out[0] = c;
-}
-__global__ void set4_kernel(int32_t* p, int32_t a, int32_t b, int32_t c, int32_t d) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { p[0] = a; p[1] = b; p[2] = c; p[3] = d; }
-}
-
-__global__ void bank_reset_kernel(ChanState* states, const gyp_chan_init* inits, int n_chan) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_chan) return;
-    ChanState* s = states + i;
-    const gyp_chan_init in = inits[i];
-    s->stream = in.stream; s->sat_id = in.sat_id;
-    s->doppler = in.doppler_hz; s->carrier_phase = in.carrier_phase;
-    s->dll_phase = (double)in.code_phase;   // tracker.py:224
-    s->last_watchdog_time = 0.0;
-    s->n_steps = 0;
-    s->code_phase = in.code_phase;
-    s->lost = 0;
-    s->win_centre1 = 0; s->pad0 = 0;
-    s->sums = LockSums{};
-}
-
-// acquisition.py:180-189 on a flat grid's records: per (stream, satellite) the FIRST bin holding the largest profile
-// maximum, with that profile's arg-max and strength (utils.py:111-116, float64 from the reduced record).
-__global__ void grid_best_bin_kernel(const gyp_cell* __restrict__ cells, int n_rows, int n_bins, int n_per_ms, gyp_best_bin* out) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n_rows) return;
-    const gyp_cell* c = cells + (int64_t)row * n_bins;
-    int best = 0;
-    float pk = c[0].peak;
-    for (int b = 1; b < n_bins; ++b)
-        if (c[b].peak > pk) { pk = c[b].peak; best = b; }
-    const gyp_cell w = c[best];
-    gyp_best_bin o;
-    o.bin = best; o.argmax = w.argmax; o.peak = w.peak; o.reserved = 0;
-    const double p = (double)w.peak;
-    o.strength = p / ((w.sum - (double)w.n_max * p) / (double)(n_per_ms - w.n_max));
-    out[row] = o;
-}
-
-// ---- the same selection with a float64 tie-break (r06) -------------------------------------------------------------------------
-// "Which bin holds the largest maximum" (acquisition.py:180-182) cannot always be decided from float32 cells: two bins of a row can
-// agree to ~1e-6 -- two bins at equal distance from the true Doppler do by construction -- and float32 magnitudes carry 3e-7.  As in
-// the 10-level search (acq_refine_kernel), every bin whose peak is within kGridTieBand of the row's maximum is re-evaluated in float64,
-// straight from the samples in the time domain, at its own arg-max lag:
-//     c_ms = sum_n x[ms, n] * exp(-2 pi i f t(ms, n)) * code[(n - lag) mod N]       V = sum_ms |c_ms|  (non-coherent)  or  |sum_ms c_ms|
-// -- the profile value the float64 reference compares -- and the first bin with the largest V wins.  Rows with one candidate (all but
-// ~1 %) are written by the first kernel and cost nothing more.
-constexpr float kGridTieBand = 2e-5f;
-struct GridRefineParams {
-    const cf* iq;
-    int64_t stream_stride;
-    int32_t n_ms, n_per_ms, k, n_sats, n_bins, n_rows, coherent;
-    const int32_t* sat_ids;        // [n_sats]
-    const double* doppler;         // [n_bins]
-    const gyp_cell* cells;         // [n_rows][n_bins], n_rows = n_streams x n_sats
-    gyp_best_bin* out;             // [n_rows]
-    const uint8_t* chips;          // [32][1023]
-    double inv_fs;
-    int32_t* cand;                 // work list: row * n_bins + bin of every candidate of every row with more than one
-    int32_t* n_cand;               // [0] length of cand, [1] rows with more than one candidate
-    int32_t* pend_rows;            // those rows ...
-    int32_t* pend_first;           // ... and where each one's candidates start in `cand` (contiguous, ascending bin)
-    double* partial;               // [cand][n_ms][2]: c_ms (re, im)
-};
-__global__ void grid_best_bin_select_kernel(GridRefineParams p) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= p.n_rows) return;
-    const gyp_cell* c = p.cells + (int64_t)row * p.n_bins;
-    int best = 0;
-    float pk = c[0].peak;
-    for (int b = 1; b < p.n_bins; ++b)
-        if (c[b].peak > pk) { pk = c[b].peak; best = b; }
-    const float floor_ = pk * (1.0f - kGridTieBand);
-    int n = 0;
-    for (int b = 0; b < p.n_bins; ++b) n += !(c[b].peak < floor_) ? 1 : 0;
-    const gyp_cell w = c[best];
-    gyp_best_bin o;
-    o.bin = best; o.argmax = w.argmax; o.peak = w.peak; o.reserved = n > 1 ? 1 : 0;     // reserved: 1 = decided by the float64 tie-break below
-    const double pd = (double)w.peak;
-    o.strength = pd / ((w.sum - (double)w.n_max * pd) / (double)(p.n_per_ms - w.n_max));
-    p.out[row] = o;
-    if (n > 1) {
-        const int at = atomicAdd(p.n_cand, n);
-        const int slot = atomicAdd(p.n_cand + 1, 1);
-        p.pend_rows[slot] = row; p.pend_first[slot] = at;
-        int k = 0;
-        for (int b = 0; b < p.n_bins; ++b)
-            if (!(c[b].peak < floor_)) p.cand[at + k++] = row * p.n_bins + b;
-    }
-}
-// grid (candidate slots, n_ms), 256 threads: c_ms of one candidate cell and millisecond (the arithmetic of acq_refine_kernel)
-__global__ __launch_bounds__(256) void grid_refine_kernel(GridRefineParams p) {
-    __shared__ double red_re[4], red_im[4];
-    const int n_cand = p.n_cand[0], ms = blockIdx.y;
-    for (int c = blockIdx.x; c < n_cand; c += gridDim.x) {
-        const int ci = p.cand[c], row = ci / p.n_bins, bin = ci - row * p.n_bins;
-        const int stream = row / p.n_sats, sat = p.sat_ids[row % p.n_sats];
-        const int n = p.n_per_ms, lag = p.cells[ci].argmax;
-        const uint8_t* code = p.chips + (sat - 1) * kChips;
-        const cf* block = p.iq + (int64_t)stream * p.stream_stride + (int64_t)ms * n;
-        const double f = p.doppler[bin], du = f * p.inv_fs;
-        double s_step, c_step;
-        sincospi(2.0 * (du * 256.0 - rint(du * 256.0)), &s_step, &c_step);     // exp(-2*pi*i*du*256) = (c, -s)
-        const double u = f * (((double)((int64_t)ms * n) + (double)threadIdx.x) * p.inv_fs);
-        double sn, cs;
-        sincospi(2.0 * (u - rint(u)), &sn, &cs);
-        double car_re = cs, car_im = -sn, acc_re = 0.0, acc_im = 0.0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            int cidx = i - lag;
-            cidx = cidx < 0 ? cidx + n : cidx;
-            const double sgn = code[cidx / p.k] ? 1.0 : -1.0;
-            const cf x = block[i];
-            acc_re += sgn * ((double)x.x * car_re - (double)x.y * car_im);
-            acc_im += sgn * ((double)x.x * car_im + (double)x.y * car_re);
-            const double nr = car_re * c_step + car_im * s_step;             // car *= (c_step - i*s_step)
-            car_im = car_im * c_step - car_re * s_step;
-            car_re = nr;
-        }
-        acc_re = wave_sum(acc_re);
-        acc_im = wave_sum(acc_im);
-        if ((threadIdx.x & 63) == 0) { red_re[threadIdx.x >> 6] = acc_re; red_im[threadIdx.x >> 6] = acc_im; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = p.partial + ((int64_t)c * p.n_ms + ms) * 2;
-            o[0] = (red_re[0] + red_re[1]) + (red_re[2] + red_re[3]);
-            o[1] = (red_im[0] + red_im[1]) + (red_im[2] + red_im[3]);
-        }
-        __syncthreads();
-    }
-}
-// one thread per pending row: its candidates sit contiguously in `cand` from pend_first on (ascending bin); the first bin with the largest float64 value wins
-__global__ void grid_best_bin_decide_kernel(GridRefineParams p) {
-    const int n_pend = p.n_cand[1], n_cand = p.n_cand[0];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pend; i += gridDim.x * blockDim.x) {
-        const int row = p.pend_rows[i], first = p.pend_first[i];
-        int best_bin = -1;
-        double best_v = -1.0;
-        for (int c = first; c < n_cand && p.cand[c] / p.n_bins == row; ++c) {
-            const double* q = p.partial + (int64_t)c * p.n_ms * 2;
-            double v;
-            if (p.coherent) {
-                double re = 0.0, im = 0.0;
-                for (int ms = 0; ms < p.n_ms; ++ms) { re += q[2 * ms]; im += q[2 * ms + 1]; }
-                v = sqrt(re * re + im * im);
-            } else {
-                v = 0.0;
-                for (int ms = 0; ms < p.n_ms; ++ms) v += sqrt(q[2 * ms] * q[2 * ms] + q[2 * ms + 1] * q[2 * ms + 1]);   // millisecond order, as utils.py:100-106 integrates
-            }
-            if (v > best_v) { best_v = v; best_bin = p.cand[c] - row * p.n_bins; }
-        }
-        if (best_bin < 0) continue;    // (every candidate's value NaN -- samples that are not numbers: the float32 selection of the first kernel stands)
-        const gyp_cell w = p.cells[(int64_t)row * p.n_bins + best_bin];
-        gyp_best_bin o;
-        o.bin = best_bin; o.argmax = w.argmax; o.peak = w.peak; o.reserved = 1;
-        const double pd = (double)w.peak;
-        o.strength = pd / ((w.sum - (double)w.n_max * pd) / (double)(p.n_per_ms - w.n_max));
-        p.out[row] = o;
     }
 }
 

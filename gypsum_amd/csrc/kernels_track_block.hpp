@@ -1347,21 +1347,14 @@ template <int K>
 __global__ __launch_bounds__(Geom<K>::kThreads, Geom<K>::kMinWavesPerSimd) void track_verify_kernel(TrackVerifyParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int N = K * kChips;
-    const int round_len = p.trk_round ? round_length(p.trk_round, p.n_chan, p.sub, p.n_ms) : p.ms_end - p.ms_begin;
+    const int round_len = unit_span(p);
     if (round_len == 0) return;   // a round in which no channel tracked anything: nothing to verify (uniform over the grid)
     const Smem sm = carve_smem<K>(smem_raw, p.tw_tables);
     __syncthreads();
     const int n_units = p.n_chan * round_len;
     for (int v = blockIdx.x; v < n_units; v += gridDim.x) {
-        const int u = xcd_contiguous(v, n_units);
-        int ms = p.ms_begin + u / p.n_chan;
-        const int ch = u % p.n_chan;   // the channels of a millisecond are neighbours: shared IQ
-        if (p.trk_round) {             // (uniform per unit)
-            const int sub = p.trk_round[ch];
-            if (sub < 0) continue;
-            ms = p.sub.begin(sub) + u / p.n_chan;
-            if (ms >= p.sub.end(sub, p.n_ms)) continue;
-        }
+        int ch, ms;
+        if (!unit_decode(p, xcd_contiguous(v, n_units), ch, ms)) continue;   // (uniform per unit)
         const SpecIn in = p.spec[(int64_t)ch * p.n_ms + ms];
         if (in.key < 0) continue;                                 // uniform: transform path in the tracking kernel, or not processed
         const ChanState* st = p.states + ch;

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 207: gyp_debug_disc_read added (the float64 discriminators of a bank's last throughput block); gyp_debug_set name no_exact_shared and
+/* 208: gyp_debug_set / gyp_debug_get name exact_prefetch removed (the software-prefetched form of dll_exact_wave_kernel it selected was
+ *      measured slower and is gone); the name is refused like any unknown one.  Nothing else changes.
+ * 207: gyp_debug_disc_read added (the float64 discriminators of a bank's last throughput block); gyp_debug_set name no_exact_shared and
  *      the read-only "last_exact_path".  Nothing that existed changes.
  * 206: recordings of 1-, 2- or 4-bit words packed into bytes, unpacked on the device: gyp_packing, gyp_packed_span,
  *      gyp_unpack_iq_dev, gyp_resample_packed_dev, gyp_ingest_open_packed.  Nothing that existed changes.
@@ -44,7 +46,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 207 /* 0.2.7 */
+#define GYP_VERSION 208 /* 0.2.8 */
 
 enum {
     GYP_OK = 0,
@@ -705,7 +707,6 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
  *   "track_chunk_ms" 0 | >= 20 (250)   launch length of the throughput tracking kernel (0: whole blocks)
  *   "resample_tile_samples" 1024..8192 (4096)  LDS budget of one resampler workgroup, in input samples; same output for any value
  *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring); same output for any value
- *   "exact_prefetch" 0/1 (0)    dll_exact_wave_kernel with its next window software-prefetched (A/B: measured slower, profiles/r04_exact_ab.txt)
  *   "no_exact_shared" 0/1 (0)   the exact code-loop sums behind the throughput tracking kernel fetch and convert a stream's samples once per
  *                               channel again (dll_exact_wave_kernel).  Default at 8 samples per chip, plain gyp_track_block(_dev) calls on the
  *                               throughput path: the channels are grouped by stream on the device and each (stream, millisecond) is staged once, as

@@ -1,5 +1,5 @@
 """Python statement of the speculative tracker's round protocol -- `spec_ctl_begin` / `track_verify_kernel`'s report /
-`spec_finalize_kernel` in gypsum_amd/csrc/kernels_track_block.hpp and kernels_dll_exact.hpp, `track_block_speculative` in
+`spec_finalize_kernel` in gypsum_amd/csrc/kernels_track_block.hpp and kernels_bank.hpp, `track_block_speculative` in
 gypsum_hip.hip -- with the tracking and the verification replaced by bookkeeping: a channel is a set of "bad" milliseconds (those
 whose window does not hold the profile's arg-max); tracking a sub-block with a millisecond on the forced-transform list makes
 that millisecond good.  tests/test_spec_rounds_model.py runs it over every small failure pattern and checks what the protocol

@@ -2,7 +2,7 @@
 # One GPU visit (through gpurun), steps chosen by name:
 #   gpurun --timeout 1500 -- 'bash tools/gpu_visit.sh <tag> step [step ...]'
 # r05 steps: locktests  locksurveys  n2  bench5
-# steps: probe64  quick  newtests  abexact  tests  bench  benchfast  kt  pmc  pmcgrid  surveys  single  singleab  rate16  prof16  survey16  find4092  lanes  phases  acqtl
+# steps: probe64  quick  newtests  tests  bench  benchfast  kt  pmc  pmcgrid  surveys  single  singleab  rate16  prof16  survey16  find4092  lanes  phases  acqtl
 set -u
 export GYP_TEST_HOOKS=1   # GypsumEngine forwards GYP_* switches (gyp_debug_set) only under this opt-in
 TAG=$1; shift
@@ -20,13 +20,6 @@ for step in "$@"; do
     newtests)
       timeout 900 python -m pytest tests/test_gpu_dll_exact.py tests/test_gpu_acq_lanes.py tests/test_gpu_end_to_end.py -x -q -m gpu > $O/pytest_new.log 2>&1
       echo "pytest rc=$?" >> $O/pytest_new.log; tail -25 $O/pytest_new.log ;;
-    abexact)
-      for v in 0 1 2 3; do
-        echo "== exact_prefetch $v"
-        GYP_EXACT_PREFETCH=$v timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 4 --warmup 1 2>/dev/null | python -c "
-import json,sys
-l=json.loads(sys.stdin.read()); print({k:l[k] for k in ('value','ms_per_step','acquire_ms_per_step','track_ms_per_step')}, l['track_kernels_ms_per_step'])"
-      done ;;
     quick)
       timeout 900 python -m pytest tests/test_gpu_dll_exact.py tests/test_gpu_parity.py tests/test_gpu_params.py -x -q -m gpu > $O/pytest_quick.log 2>&1
       echo "pytest rc=$?" >> $O/pytest_quick.log; tail -25 $O/pytest_quick.log ;;
