@@ -2953,8 +2953,7 @@ static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int
     g->halo_hi = d.taps / 2;
     g->sample_bytes = (size_t)(real ? 1 : 2) * wb;
     g->ms_bytes = (size_t)d.n_in * g->sample_bytes;   // total_ms: the input file's milliseconds, by the rule of gyp_ingest_open
-    g->host_block_bytes = ((size_t)block_ms * d.n_in + d.taps - 1) * g->sample_bytes;
-    g->raw_block_bytes = g->host_block_bytes;
+    ingest_set_block_bytes(g);
     return ingest_finish_open(ctx, g, path, out);
 }
 
@@ -2978,8 +2977,7 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
     g->block_ms = block_ms;
     g->depth = depth;
     g->ms_bytes = (size_t)n * 2 * wb;
-    g->host_block_bytes = (size_t)block_ms * g->ms_bytes;
-    g->raw_block_bytes = fmt != kFmtF32 ? g->host_block_bytes : 0;
+    ingest_set_block_bytes(g);
     return ingest_finish_open(ctx, g, path, out);
 }
 
@@ -3032,9 +3030,7 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
         g->halo_hi = d.taps / 2;
     }
     g->ms_bytes = 1;   // total_ms is counted in samples (ingest_finish_open)
-    const int64_t span = (int64_t)block_ms * g->in_n + g->halo_lo + g->halo_hi;
-    g->host_block_bytes = (size_t)((span * pk.sample_bits() + 7) / 8 + 1);
-    g->raw_block_bytes = g->host_block_bytes;
+    ingest_set_block_bytes(g);
     return ingest_finish_open(ctx, g, path, out);
 }
 

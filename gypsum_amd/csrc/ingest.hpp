@@ -292,6 +292,24 @@ struct gyp_ingest {
     int64_t dev_blocks = 0;          // uploads enqueued so far (device slot = index % depth)
 };
 
+// One ring slot's size from the handle's fields (rates, halo, packing and block_ms filled in): what the reader writes per block.
+//   packed:    the bytes covering block_ms * in_n + halo samples at any bit0, plus one;
+//   resampled: the block's input samples plus the T-1 halo, in file width;
+//   plain:     block_ms file milliseconds (float32 lands in the output slot directly: no device slot of raw words).
+static void ingest_set_block_bytes(gyp_ingest* g) {
+    if (g->packed) {
+        const int64_t span = (int64_t)g->block_ms * g->in_n + g->halo_lo + g->halo_hi;
+        g->host_block_bytes = (size_t)((span * g->pk.sample_bits() + 7) / 8 + 1);
+        g->raw_block_bytes = g->host_block_bytes;
+    } else if (g->resampled) {
+        g->host_block_bytes = ((size_t)g->block_ms * g->in_n + g->rs.taps - 1) * g->sample_bytes;
+        g->raw_block_bytes = g->host_block_bytes;
+    } else {
+        g->host_block_bytes = (size_t)g->block_ms * g->ms_bytes;
+        g->raw_block_bytes = g->fmt != kFmtF32 ? g->host_block_bytes : 0;
+    }
+}
+
 // A resampled block's input span with its halo; what lies outside the file's whole samples reads as zero.  0 or an errno.
 static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
     const size_t sb = g->sample_bytes;

@@ -1,0 +1,708 @@
+// Stand-alone driver for the host code of libgypsum_hip under ASan + UBSan or TSan (tests/test_host_sanitizers.py builds and runs it).
+//
+//     prog <scenario> <in_dir> <out_dir>
+//
+// One translation unit with the product: it includes gypsum_hip.hip itself, so the extern "C" entry points AND the static helpers
+// behind them are compiled with this program's sanitizer flags.  Inputs are little-endian binary files the pytest side wrote, results
+// are raw arrays it compares with numpy models or with the uninstrumented library.  No context is ever made and no entry point is given
+// a non-NULL one: nothing here initialises the GPU.
+#include "../../gypsum_amd/csrc/gypsum_hip.hip"
+
+#include <fstream>
+#include <iterator>
+
+#ifndef __has_feature
+#define __has_feature(x) 0
+#endif
+
+namespace drv {
+
+static std::string g_in, g_out;
+
+[[noreturn]] static void die(const std::string& what) {
+    std::fprintf(stderr, "driver: %s\n", what.c_str());
+    std::exit(2);
+}
+#define REQUIRE(cond)                                                                        \
+    do {                                                                                     \
+        if (!(cond)) drv::die(std::string(__FILE__) + ":" + std::to_string(__LINE__) + ": " #cond); \
+    } while (0)
+
+static std::vector<uint8_t> read_bytes(const std::string& name) {
+    std::ifstream f(g_in + "/" + name, std::ios::binary);
+    if (!f) die("cannot read " + name);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+template <class T>
+static std::vector<T> read_array(const std::string& name) {
+    const std::vector<uint8_t> b = read_bytes(name);
+    REQUIRE(b.size() % sizeof(T) == 0);
+    std::vector<T> v(b.size() / sizeof(T));
+    if (!b.empty()) std::memcpy(v.data(), b.data(), b.size());
+    return v;
+}
+static std::string in_path(const std::string& name) { return g_in + "/" + name; }
+
+// An output file under <out_dir>; everything is appended raw.
+struct Out {
+    FILE* f;
+    explicit Out(const std::string& name) : f(std::fopen((g_out + "/" + name).c_str(), "wb")) {
+        if (!f) die("cannot write " + name);
+    }
+    ~Out() { std::fclose(f); }
+    Out(const Out&) = delete;
+    void bytes(const void* p, size_t n) {
+        if (n && std::fwrite(p, 1, n, f) != n) die("short write");
+    }
+    template <class T>
+    void put(const T& v) { bytes(&v, sizeof(T)); }
+    void i64(int64_t v) { put(v); }
+    void line(const std::string& s) {
+        bytes(s.data(), s.size());
+        bytes("\n", 1);
+    }
+};
+
+// The log of blocks a reader handed out: rows (tag, first_ms, n_ms, n_bytes) in <name>.i64 and the bytes back to back in <name>.bin.
+struct BlockLog {
+    Out meta, data;
+    explicit BlockLog(const std::string& name) : meta(name + ".i64"), data(name + ".bin") {}
+    void block(int64_t tag, int64_t first, int64_t n_ms, const void* p, size_t n) {
+        meta.i64(tag);
+        meta.i64(first);
+        meta.i64(n_ms);
+        meta.i64((int64_t)n);
+        data.bytes(p, n);
+    }
+};
+
+static const int kWordBytes[4] = {4, 1, 2, 1};   // by GYP_FMT_*
+
+// One gyp_ingest_next_host call; logs the block (n_ms 0: a row without bytes).  Returns n_ms, or the error code.
+static int next_host(gyp_ingest* g, int fmt, int n, BlockLog& log, int64_t tag) {
+    const void* raw = nullptr;
+    int64_t first = -1;
+    int32_t n_ms = -1;
+    const int rc = gyp_ingest_next_host(g, &raw, &first, &n_ms);
+    if (rc != GYP_OK) return rc;
+    if (n_ms == 0) {
+        REQUIRE(raw == nullptr);
+        log.block(tag, -1, 0, nullptr, 0);
+        return 0;
+    }
+    log.block(tag, first, n_ms, raw, (size_t)n_ms * n * 2 * kWordBytes[fmt]);
+    return n_ms;
+}
+
+// --------------------------------------------------------------------------------------------------------- ingest-host
+// cases.i64 rows: file index, fmt, n, block_ms, depth, middle millisecond.  times.i64 rows: fs, first_ms.
+static void ingest_host() {
+    const std::vector<int64_t> cases = read_array<int64_t>("cases.i64");
+    BlockLog log("blocks");
+    Out info("info.i64");
+    for (size_t c = 0; c * 6 < cases.size(); ++c) {
+        const int64_t* k = &cases[c * 6];
+        const int fmt = (int)k[1], n = (int)k[2];
+        const std::string path = in_path("f" + std::to_string(k[0]) + "_" + std::to_string(fmt) + ".bin");
+        gyp_ingest* g = nullptr;
+        REQUIRE(gyp_ingest_open(nullptr, path.c_str(), fmt, (int64_t)n * 1000, n, (int32_t)k[3], (int32_t)k[4], &g) == GYP_OK && g);
+        const int64_t total = gyp_ingest_total_ms(g);
+        info.i64(total);
+        const int64_t tag = (int64_t)c * 4;
+        while (next_host(g, fmt, n, log, tag) > 0) {}
+        REQUIRE(next_host(g, fmt, n, log, tag + 1) == 0);   // past the end, twice
+        REQUIRE(next_host(g, fmt, n, log, tag + 1) == 0);
+        REQUIRE(gyp_ingest_seek(g, total) == GYP_OK);
+        REQUIRE(next_host(g, fmt, n, log, tag + 2) == 0);
+        REQUIRE(gyp_ingest_seek(g, k[5]) == GYP_OK);
+        next_host(g, fmt, n, log, tag + 3);
+        info.i64(gyp_ingest_seek(g, -1));
+        info.i64(gyp_ingest_seek(g, total + 1));
+        next_host(g, fmt, n, log, tag + 3);   // a refused seek leaves the reader where it was
+        const float inf = std::numeric_limits<float>::infinity();
+        for (float s : {0.0f, -1.0f, inf, std::numeric_limits<float>::quiet_NaN(), 0.01f}) info.i64(gyp_ingest_set_scale(g, s));
+        gyp_ingest_close(g);
+    }
+    info.i64(gyp_ingest_set_scale(nullptr, 1.0f));
+    info.i64(gyp_ingest_seek(nullptr, 0));
+    info.i64(gyp_ingest_total_ms(nullptr));
+    gyp_ingest_close(nullptr);
+    {   // the refusals of open
+        gyp_ingest* g = nullptr;
+        const std::string path = in_path("f0_0.bin");
+        info.i64(gyp_ingest_open(nullptr, in_path("missing").c_str(), 0, 2046000, 2046, 1, 3, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 0, 2046000, 2046, 1, 2, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 0, 2046000, 2046, 1, 65, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 0, 2046000, 2046, 0, 3, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 4, 2046000, 2046, 1, 3, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 0, 2046000, 2047, 1, 3, &g));
+        info.i64(gyp_ingest_open(nullptr, path.c_str(), 0, 2046000, 2046, 1, 3, nullptr));
+        REQUIRE(g == nullptr);
+    }
+    const std::vector<int64_t> times = read_array<int64_t>("times.i64");
+    Out t("times.f64");
+    for (size_t i = 0; i * 2 < times.size(); ++i) {
+        const int64_t fs = times[2 * i], first = times[2 * i + 1];
+        gyp_ingest* g = nullptr;
+        REQUIRE(gyp_ingest_open(nullptr, in_path("f2_0.bin").c_str(), 0, fs, (int32_t)(fs / 1000), 1, 3, &g) == GYP_OK);
+        double* start = (double*)std::malloc(40 * sizeof(double));   // exact sizes: one element too many is a report
+        double* end = (double*)std::malloc(40 * sizeof(double));
+        REQUIRE(gyp_ingest_times(g, first, 40, start, end) == GYP_OK);
+        t.bytes(start, 40 * sizeof(double));
+        t.bytes(end, 40 * sizeof(double));
+        REQUIRE(gyp_ingest_times(g, -1, 1, start, end) == GYP_E_BAD_ARG && gyp_ingest_times(g, 0, -1, start, end) == GYP_E_BAD_ARG &&
+                gyp_ingest_times(g, 0, 1, nullptr, end) == GYP_E_BAD_ARG && gyp_ingest_times(g, 0, 0, nullptr, nullptr) == GYP_OK);
+        std::free(start);
+        std::free(end);
+        gyp_ingest_close(g);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- ingest-races
+// The reader has filled its ring and waits for a slot (same translation unit: the counters are read under the handle's mutex).
+static void wait_ring_full(gyp_ingest* g) {
+    for (;;) {
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            if (g->eof || g->produced - g->released >= g->depth) return;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(200));
+    }
+}
+
+// rec.bin: float32 recording at 2.046 Msps (a few hundred ms).  seeks.i64: the milliseconds of the alternating seek / next calls.
+static void ingest_races() {
+    const int n = 2046, fmt = 0;
+    const std::string path = in_path("rec.bin");
+    BlockLog log("blocks");
+    Out info("info.i64");
+    auto open = [&](int block_ms, int depth) {
+        gyp_ingest* g = nullptr;
+        REQUIRE(gyp_ingest_open(nullptr, path.c_str(), fmt, 2046000, n, block_ms, depth, &g) == GYP_OK && g);
+        return g;
+    };
+    for (int i = 0; i < 50; ++i) gyp_ingest_close(open(1 + i % 7, 3 + i % 5));   // close directly after open
+    for (int i = 0; i < 20; ++i) {                                               // close while the reader waits on a full ring
+        gyp_ingest* g = open(1 + i % 3, 3);
+        wait_ring_full(g);
+        gyp_ingest_close(g);
+    }
+    {   // seek while the reader is reading a large block, and while it waits
+        gyp_ingest* g = open(200, 3);
+        const int64_t total = gyp_ingest_total_ms(g);
+        for (int i = 0; i < 60; ++i) {
+            REQUIRE(gyp_ingest_seek(g, (i * 37) % (total + 1)) == GYP_OK);   // the reader was started a moment ago: it is inside pread
+            if (i % 3 == 0) REQUIRE(next_host(g, fmt, n, log, 1) >= 0);
+            if (i % 10 == 9) wait_ring_full(g);
+        }
+        gyp_ingest_close(g);
+    }
+    {
+        gyp_ingest* g = open(4, 3);
+        for (int64_t ms : read_array<int64_t>("seeks.i64")) {
+            REQUIRE(gyp_ingest_seek(g, ms) == GYP_OK);
+            REQUIRE(next_host(g, fmt, n, log, 2) >= 0);
+        }
+        gyp_ingest_close(g);
+    }
+    {   // close at end of data
+        gyp_ingest* g = open(16, 64);
+        while (next_host(g, fmt, n, log, 3) > 0) {}
+        gyp_ingest_close(g);
+    }
+    {   // the file shrinks after open: the blocks read before stay good, the next one is GYP_E_IO
+        const std::string victim = in_path("shrinks.bin");
+        gyp_ingest* g = nullptr;
+        REQUIRE(gyp_ingest_open(nullptr, victim.c_str(), fmt, 2046000, n, 2, 3, &g) == GYP_OK && g);
+        wait_ring_full(g);   // blocks 0..2 = milliseconds 0..5 are in the ring
+        const int fd = ::open(victim.c_str(), O_WRONLY);
+        REQUIRE(fd >= 0 && ftruncate(fd, (off_t)6 * n * 8 + 24) == 0);
+        ::close(fd);
+        int rc = 0;
+        for (int i = 0; i < 3; ++i) REQUIRE((rc = next_host(g, fmt, n, log, 4)) == 2);
+        rc = next_host(g, fmt, n, log, 4);   // block 3 starts beyond the new end: pread returns 0
+        info.i64(rc);
+        Out("shrinks_error.txt").line(gyp_last_error(nullptr));
+        info.i64(next_host(g, fmt, n, log, 4));   // the error stays
+        REQUIRE(gyp_ingest_seek(g, 0) == GYP_OK);   // and a seek clears it
+        REQUIRE(next_host(g, fmt, n, log, 5) == 2);
+        gyp_ingest_close(g);
+    }
+    {   // two handles, two consumer threads, each with its own gyp_last_error(NULL)
+        std::string msg[2];
+        auto body = [&](int who) {
+            BlockLog mine("thread" + std::to_string(who));
+            gyp_ingest* g = open(who ? 3 : 5, who ? 3 : 8);
+            const int64_t total = gyp_ingest_total_ms(g);
+            for (int round = 0; round < 3; ++round) {
+                while (next_host(g, fmt, n, mine, 6 + who) > 0) {}
+                REQUIRE(gyp_ingest_seek(g, (total / 3) * round) == GYP_OK);
+            }
+            const int rc = who ? gyp_ingest_set_scale(g, -1.0f) : gyp_ingest_seek(g, total + 1);
+            REQUIRE(rc == GYP_E_BAD_ARG);
+            std::this_thread::sleep_for(std::chrono::milliseconds(5));   // (the other thread fails in the meantime)
+            msg[who] = gyp_last_error(nullptr);
+            gyp_ingest_close(g);
+        };
+        std::thread a(body, 0), b(body, 1);
+        a.join();
+        b.join();
+        Out m("thread_errors.txt");
+        m.line(msg[0]);
+        m.line(msg[1]);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- bits
+// plan.i64 rows: stream index, symbols per push, event capacity, reset mode (0 none, 1 gyp_bits_reset(channel) in mid-stream, 2 channel -1).
+// Stream k: s<k>.sym (int8), s<k>.start / s<k>.end (float64).  Then the block path on recs.bin (channel-major gyp_track_rec).
+static void put_state(gyp_bits* b, int32_t ch, Out& states) {
+    gyp_bits_state* st = (gyp_bits_state*)std::malloc(sizeof(gyp_bits_state));
+    REQUIRE(gyp_bits_get_state(b, ch, st) == GYP_OK);
+    states.bytes(st, sizeof(*st));
+    std::free(st);
+}
+static void bits() {
+    const std::vector<int64_t> plan = read_array<int64_t>("plan.i64");
+    Out events("events.bin"), cursors("cursors.i32"), states("states.bin"), counts("counts.i32");
+    for (size_t r = 0; r * 4 < plan.size(); ++r) {
+        const int64_t* k = &plan[r * 4];
+        const std::string s = "s" + std::to_string(k[0]);
+        const std::vector<int8_t> sym = read_array<int8_t>(s + ".sym");
+        const std::vector<double> start = read_array<double>(s + ".start"), end = read_array<double>(s + ".end");
+        const int32_t push = (int32_t)k[1], cap = (int32_t)k[2], channel = 1;
+        gyp_bits* b = nullptr;
+        REQUIRE(gyp_bits_create(3, &b) == GYP_OK && b);
+        const size_t total = sym.size(), mid = total / 2;
+        bool reset_done = k[3] == 0;
+        for (size_t at = 0; at < total; at += (size_t)push) {
+            const int32_t n = (int32_t)std::min<size_t>((size_t)push, total - at);
+            if (!reset_done && at >= mid) {
+                REQUIRE(gyp_bits_reset(b, k[3] == 2 ? -1 : channel) == GYP_OK);
+                reset_done = true;
+            }
+            // exact-size copies on the heap: a read or write one element out is a report
+            double* ts = (double*)std::malloc(n * sizeof(double));
+            double* te = (double*)std::malloc(n * sizeof(double));
+            int8_t* v = (int8_t*)std::malloc((size_t)n);
+            int32_t* cur = (int32_t*)std::malloc(n * sizeof(int32_t));
+            gyp_bit_event* ev = cap ? (gyp_bit_event*)std::malloc((size_t)cap * sizeof(gyp_bit_event)) : nullptr;
+            std::memcpy(ts, &start[at], n * sizeof(double));
+            std::memcpy(te, &end[at], n * sizeof(double));
+            std::memcpy(v, &sym[at], (size_t)n);
+            int32_t n_ev = -1;
+            REQUIRE(gyp_bits_push(b, channel, n, ts, ts, te, v, cur, ev, cap, &n_ev) == GYP_OK);
+            REQUIRE(n_ev >= 0 && n_ev <= cap);
+            counts.put(n_ev);
+            events.bytes(ev, (size_t)n_ev * sizeof(gyp_bit_event));
+            cursors.bytes(cur, n * sizeof(int32_t));
+            put_state(b, channel, states);
+            std::free(ts);
+            std::free(te);
+            std::free(v);
+            std::free(cur);
+            std::free(ev);
+        }
+        for (;;) {   // what the pushes left in the FIFO
+            gyp_bit_event* ev = (gyp_bit_event*)std::malloc(5 * sizeof(gyp_bit_event));
+            int32_t n_ev = -1;
+            REQUIRE(gyp_bits_drain(b, ev, 5, &n_ev) == GYP_OK);
+            counts.put(n_ev);
+            events.bytes(ev, (size_t)n_ev * sizeof(gyp_bit_event));
+            std::free(ev);
+            if (n_ev == 0) break;
+        }
+        put_state(b, 0, states);   // an untouched channel
+        gyp_bits_destroy(b);
+    }
+    // the block path: cuts.i64 = the millisecond cuts, recs.bin holds a status-1 record
+    const std::vector<int64_t> cuts = read_array<int64_t>("cuts.i64");
+    const std::vector<uint8_t> recs = read_bytes("recs.bin");
+    const std::vector<double> start = read_array<double>("block.start"), end = read_array<double>("block.end");
+    const int32_t n_ms = (int32_t)start.size();
+    REQUIRE(n_ms > 0 && recs.size() % ((size_t)n_ms * sizeof(gyp_track_rec)) == 0);
+    const int32_t n_chan = (int32_t)(recs.size() / ((size_t)n_ms * sizeof(gyp_track_rec)));
+    gyp_bits* b = nullptr;
+    REQUIRE(gyp_bits_create(n_chan, &b) == GYP_OK);
+    Out bev("block_events.bin"), bstates("block_states.bin"), bcounts("block_counts.i32");
+    for (size_t i = 0; i + 1 < cuts.size(); ++i) {
+        const int32_t a = (int32_t)cuts[i], len = (int32_t)(cuts[i + 1] - cuts[i]);
+        gyp_track_rec* part = (gyp_track_rec*)std::malloc((size_t)n_chan * len * sizeof(gyp_track_rec));
+        for (int32_t c = 0; c < n_chan; ++c)
+            std::memcpy(part + (size_t)c * len, recs.data() + ((size_t)c * n_ms + a) * sizeof(gyp_track_rec), (size_t)len * sizeof(gyp_track_rec));
+        double* ts = (double*)std::malloc(len * sizeof(double));
+        double* te = (double*)std::malloc(len * sizeof(double));
+        std::memcpy(ts, &start[a], len * sizeof(double));
+        std::memcpy(te, &end[a], len * sizeof(double));
+        const int32_t cap = i % 2 ? 3 : 1000;
+        gyp_bit_event* ev = (gyp_bit_event*)std::malloc((size_t)cap * sizeof(gyp_bit_event));
+        int32_t n_ev = -1;
+        REQUIRE(gyp_bits_push_block(b, part, n_chan, len, ts, te, ev, cap, &n_ev) == GYP_OK);
+        bcounts.put(n_ev);
+        bev.bytes(ev, (size_t)n_ev * sizeof(gyp_bit_event));
+        for (int32_t c = 0; c < n_chan; ++c) put_state(b, c, bstates);
+        std::free(part);
+        std::free(ts);
+        std::free(te);
+        std::free(ev);
+    }
+    Out rc("refusals.i64");
+    int32_t n_ev = 0;
+    gyp_bits_state st;
+    gyp_bits* refused = nullptr;
+    rc.i64(gyp_bits_create(0, &refused));
+    rc.i64(gyp_bits_create(-1, &refused));
+    rc.i64(gyp_bits_create(1, nullptr));
+    REQUIRE(refused == nullptr);
+    rc.i64(gyp_bits_reset(b, n_chan));
+    rc.i64(gyp_bits_reset(nullptr, 0));
+    rc.i64(gyp_bits_push(b, n_chan, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n_ev));
+    rc.i64(gyp_bits_push(b, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n_ev));
+    rc.i64(gyp_bits_push(nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n_ev));
+    rc.i64(gyp_bits_push_block(b, nullptr, n_chan + 1, 1, nullptr, nullptr, nullptr, 0, &n_ev));
+    rc.i64(gyp_bits_push_block(b, nullptr, 1, 1, nullptr, nullptr, nullptr, 0, &n_ev));
+    rc.i64(gyp_bits_drain(b, nullptr, -1, &n_ev));
+    rc.i64(gyp_bits_get_state(b, -1, &st));
+    rc.i64(gyp_bits_get_state(b, 0, nullptr));
+    gyp_bits_destroy(b);
+    gyp_bits_destroy(nullptr);
+}
+
+// --------------------------------------------------------------------------------------------------------- spans
+// cases.i64 rows: bits, real, order, samples_per_ms, file_bytes, first_sample, n_samples, file_samples if the static helper is to be
+// called too (the contract's arithmetic stays inside int64), else -1.
+static void spans() {
+    const std::vector<int64_t> cases = read_array<int64_t>("cases.i64");
+    Out pub("public.i64"), stat("static.i64");
+    for (size_t c = 0; c * 8 < cases.size(); ++c) {
+        const int64_t* k = &cases[c * 8];
+        gyp_packing p{};
+        p.bits = (int32_t)k[0];
+        p.real = (int32_t)k[1];
+        p.order = (int32_t)k[2];
+        for (int i = 0; i < 16; ++i) p.levels[i] = (float)i - 7.5f;
+        int64_t* o = (int64_t*)std::malloc(6 * sizeof(int64_t));
+        int32_t* bit0 = (int32_t*)std::malloc(sizeof(int32_t));
+        for (int i = 0; i < 6; ++i) o[i] = -777;
+        *bit0 = -777;
+        const int rc = gyp_packed_span(&p, (int32_t)k[3], k[4], k[5], k[6], &o[0], &o[1], &o[2], bit0, &o[3], &o[4], &o[5]);
+        REQUIRE(gyp_packed_span(&p, (int32_t)k[3], k[4], k[5], k[6], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == rc);
+        pub.i64(rc);
+        for (int i = 0; i < 6; ++i) pub.i64(o[i]);
+        pub.i64(*bit0);
+        std::free(o);
+        std::free(bit0);
+        PackedSpan sp;
+        if (k[7] >= 0) sp = packed_span(k[0] * (k[1] ? 1 : 2), k[7], k[5], k[6]);
+        stat.i64(sp.in_first);
+        stat.i64(sp.in_n);
+        stat.i64(sp.first_byte);
+        stat.i64(sp.n_bytes);
+        stat.i64(sp.bit0);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- designs
+// cases.i64 rows: kind (0 resampler, 1 down-converter), fs_in, fs_out, if_hz, taps.
+static void designs() {
+    const std::vector<int64_t> cases = read_array<int64_t>("cases.i64");
+    Out meta("meta.i64"), tables("tables.f32");
+    for (size_t c = 0; c * 5 < cases.size(); ++c) {
+        const int64_t* k = &cases[c * 5];
+        int32_t L = -1, T = -1;
+        const int rc = k[0] ? gyp_ddc_design(k[1], k[2], k[3], (int32_t)k[4], nullptr, &L, &T) : gyp_resample_design(k[1], k[2], (int32_t)k[4], nullptr, &L);
+        if (!k[0] && rc == GYP_OK) T = resample_taps((int32_t)k[4]);
+        meta.i64(rc);
+        meta.i64(L);
+        meta.i64(T);
+        if (rc != GYP_OK) {
+            REQUIRE(L == -1 && T == -1);
+            continue;
+        }
+        float* table = (float*)std::malloc((size_t)L * T * sizeof(float));   // exactly L x T: ASan sees a one-element overrun
+        int32_t L2 = -1, T2 = -1;
+        const int rc2 = k[0] ? gyp_ddc_design(k[1], k[2], k[3], (int32_t)k[4], table, &L2, &T2) : gyp_resample_design(k[1], k[2], (int32_t)k[4], table, &L2);
+        REQUIRE(rc2 == GYP_OK && L2 == L && (!k[0] || T2 == T));
+        REQUIRE((k[0] ? gyp_ddc_design(k[1], k[2], k[3], (int32_t)k[4], nullptr, nullptr, nullptr) : gyp_resample_design(k[1], k[2], (int32_t)k[4], nullptr, nullptr)) == GYP_OK);
+        tables.bytes(table, (size_t)L * T * sizeof(float));
+        std::free(table);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- misc
+static void misc() {
+    {
+        uint8_t* chips = (uint8_t*)std::malloc(32 * 1023);
+        REQUIRE(gyp_prn_chips(chips) == GYP_OK && gyp_prn_chips(nullptr) == GYP_E_BAD_ARG);
+        Out("prn_chips.u8").bytes(chips, 32 * 1023);
+        std::free(chips);
+        Out lanes("lanes.f32"), rc("lanes_rc.i64");
+        for (int sat : {1, 32, 0, 33}) {
+            float* t = (float*)std::malloc(32 * 64 * 2 * sizeof(float));
+            const int r = gyp_prn_spectrum_lane_layout(sat, t);
+            rc.i64(r);
+            if (r == GYP_OK) lanes.bytes(t, 32 * 64 * 2 * sizeof(float));
+            std::free(t);
+        }
+        rc.i64(gyp_prn_spectrum_lane_layout(1, nullptr));
+    }
+    {   // cells.bin: gyp_cell records; cells_n.i32: samples_per_ms of each
+        const std::vector<uint8_t> cells = read_bytes("cells.bin");
+        const std::vector<int32_t> n = read_array<int32_t>("cells_n.i32");
+        REQUIRE(cells.size() == n.size() * sizeof(gyp_cell));
+        Out s("strength.f64");
+        for (size_t i = 0; i < n.size(); ++i) {
+            gyp_cell* c = (gyp_cell*)std::malloc(sizeof(gyp_cell));
+            std::memcpy(c, cells.data() + i * sizeof(gyp_cell), sizeof(gyp_cell));
+            s.put(gyp_cell_strength(c, n[i]));
+            std::free(c);
+        }
+    }
+    {   // nav.i64 rows: seed, stream, sat, offset, ms
+        const std::vector<int64_t> nav = read_array<int64_t>("nav.i64");
+        Out o("nav_bits.i64");
+        for (size_t i = 0; i * 5 < nav.size(); ++i)
+            o.i64(gyp_synth_nav_bit((uint64_t)nav[5 * i], (int32_t)nav[5 * i + 1], (int32_t)nav[5 * i + 2], (int32_t)nav[5 * i + 3], nav[5 * i + 4]));
+    }
+    {
+        gyp_params* p = (gyp_params*)std::malloc(sizeof(gyp_params));
+        gyp_params_default(p);
+        gyp_params_default(nullptr);
+        Out("params.f64").bytes(p, sizeof(*p));
+        std::free(p);
+    }
+    {   // layout.i64: n_ms values then, after a -1, sub_ms values; every pair into a 33-int heap buffer
+        const std::vector<int64_t> in = read_array<int64_t>("layout.i64");
+        const size_t cut = std::find(in.begin(), in.end(), (int64_t)-1) - in.begin();
+        Out o("layout.i32");
+        for (size_t s = cut + 1; s < in.size(); ++s)
+            for (size_t i = 0; i < cut; ++i) {
+                int32_t* starts = (int32_t*)std::malloc(33 * sizeof(int32_t));
+                for (int j = 0; j < 33; ++j) starts[j] = -777;
+                o.put((int32_t)gyp_debug_spec_layout_for((int32_t)in[i], (int32_t)in[s], starts));
+                o.bytes(starts, 33 * sizeof(int32_t));
+                if (in[s] == 500) {
+                    int32_t* again = (int32_t*)std::malloc(33 * sizeof(int32_t));
+                    for (int j = 0; j < 33; ++j) again[j] = -777;
+                    (void)gyp_debug_spec_layout((int32_t)in[i], again);
+                    REQUIRE(std::memcmp(starts, again, 33 * sizeof(int32_t)) == 0);
+                    std::free(again);
+                }
+                std::free(starts);
+            }
+        int32_t one[33];
+        REQUIRE(gyp_debug_spec_layout_for(0, 500, one) == GYP_E_BAD_ARG && gyp_debug_spec_layout_for(-5, 500, one) == GYP_E_BAD_ARG &&
+                gyp_debug_spec_layout_for(100, 500, nullptr) == GYP_E_BAD_ARG);
+    }
+    {   // every entry point that needs a context, a bank or a handle refuses NULL and writes nothing
+        Out o("null_rc.i64");
+        uint8_t* buf = (uint8_t*)std::malloc(256);
+        std::memset(buf, 0x5a, 256);
+        void* vp = nullptr;
+        gyp_bank* bank = nullptr;
+        gyp_ingest* ing = nullptr;
+        gyp_packing pk{};
+        pk.bits = 2;
+        int32_t sat = 1;
+        double dop = 0.0;
+        float* f = (float*)buf;
+        gyp_ctx* none = nullptr;
+        gyp_bank* nobank = nullptr;
+        const int rcs[] = {
+            gyp_set_params(none, (gyp_params*)buf), gyp_get_params(none, (gyp_params*)buf), gyp_device_name(none, (char*)buf, 256), gyp_set_stream(none, nullptr),
+            gyp_sync(none), gyp_wait_for(none, none), gyp_timer_start(none), gyp_timer_stop(none, f), gyp_set_stream_format(none, 2046000, 2046),
+            gyp_malloc(none, 16, &vp), gyp_free(none, buf), gyp_memcpy_h2d(none, buf, buf, 16), gyp_memcpy_d2h(none, buf, buf, 16),
+            gyp_memcpy_d2h_async(none, buf, buf, 16),
+            gyp_correlate_cells_dev(none, f, 2046, 1, (gyp_cell_desc*)buf, 1, 0, (gyp_cell*)buf, nullptr),
+            gyp_correlate_cells(none, f, 1, 1, (gyp_cell_desc*)buf, 1, 0, (gyp_cell*)buf, nullptr),
+            gyp_correlate_grid_dev(none, f, 1, 2046, 1, &sat, 1, &dop, 1, 0, (gyp_cell*)buf),
+            gyp_correlate_grid(none, f, 1, 1, &sat, 1, &dop, 1, 0, (gyp_cell*)buf),
+            gyp_grid_best_bins_dev(none, (gyp_cell*)buf, 1, 1, (gyp_best_bin*)buf),
+            gyp_grid_best_bins_refined_dev(none, f, 1, 2046, 1, &sat, 1, &dop, 1, 0, (gyp_cell*)buf, (gyp_best_bin*)buf),
+            gyp_acquire_dev(none, f, 1, 2046, 1, &sat, 1, (gyp_acq_result*)buf), gyp_acquire(none, f, 1, 1, &sat, 1, (gyp_acq_result*)buf),
+            gyp_search_level_dev(none, f, 1, 2046, 1, &sat, 1, 0.0, 7000.0, (gyp_acq_result*)buf),
+            gyp_search_level(none, f, 1, 1, &sat, 1, 0.0, 7000.0, (gyp_acq_result*)buf),
+            gyp_track_step_dev(none, f, 2046, &dop, (gyp_chan_in*)buf, 1, (gyp_chan_out*)buf, nullptr),
+            gyp_track_step(none, f, 1, &dop, (gyp_chan_in*)buf, 1, (gyp_chan_out*)buf, nullptr),
+            gyp_bank_create(none, (gyp_chan_init*)buf, 1, &bank), gyp_bank_size(nobank), gyp_bank_set_channel(nobank, 0, (gyp_chan_init*)buf),
+            gyp_bank_drop_channel(nobank, 0), gyp_track_block_dev(nobank, f, 2046, 1, &dop, (gyp_track_rec*)buf),
+            gyp_track_block(nobank, f, 1, 1, &dop, (gyp_track_rec*)buf), gyp_bank_keep_profiles(nobank, 1),
+            gyp_bank_read_profiles(nobank, 0, f, &sat), gyp_bank_reset_dev(nobank, (gyp_chan_init*)buf),
+            gyp_bank_get_state(nobank, &dop, &dop, &sat, &sat), gyp_comm_init(none, 0, 1, nullptr), gyp_comm_destroy(none),
+            gyp_comm_info(none, &sat, &sat, &sat), gyp_allgather_dev(none, buf, buf, 16), gyp_host_alloc(none, 16, &vp), gyp_host_free(none, buf),
+            gyp_widen_iq_dev(none, GYP_FMT_I8, buf, 16, 1.0f, f), gyp_synth_iq_dev(none, f, 1, 2046, 1, (gyp_synth_sat*)buf, 1, 0.0f, 1),
+            gyp_debug_set(none, "no_pipe", 1.0), gyp_debug_get(none, "no_pipe", &dop), gyp_debug_track_profile(none, 1, (long long*)buf),
+            gyp_debug_track_timing(none, 1, f), gyp_debug_fft_bench(none, 4, 1, 1, f), gyp_debug_spec_read(nobank, f, 20, &sat),
+            gyp_debug_spec_redo_read(nobank, &sat), gyp_debug_dll_read(nobank, &sat), gyp_debug_disc_read(nobank, 1, &dop),
+            gyp_resample_iq_dev(none, GYP_FMT_I8, buf, 1, 16, 0, 16, 1.0f, 2048000, 32, 0, 1, 2046, f),
+            gyp_ddc_iq_dev(none, GYP_FMT_I8, buf, 1, 16, 0, 16, 1.0f, 16368000, 4092000, 64, 0, 1, 4092, f),
+            gyp_unpack_iq_dev(none, &pk, buf, 1, 16, 0, 16, 1.0f, 16, f),
+            gyp_resample_packed_dev(none, &pk, buf, 1, 16, 0, 0, 16, 1.0f, 2048000, 0, 32, 0, 1, 2046, f),
+            gyp_ingest_open_resampled(none, in_path("cells.bin").c_str(), GYP_FMT_I8, 2048000, 32, 1, 3, &ing),
+            gyp_ingest_open_ddc(none, in_path("cells.bin").c_str(), GYP_FMT_I8, 16368000, 4092000, 64, 1, 3, &ing),
+            gyp_ingest_open_packed(none, in_path("cells.bin").c_str(), &pk, 2048000, 0, 32, 1, 3, &ing),
+            gyp_device_locality(none, &sat, (char*)buf, 256), gyp_ingest_next_dev(nullptr, (const float**)&vp, (int64_t*)buf, &sat),
+            gyp_ingest_next_host(nullptr, (const void**)&vp, (int64_t*)buf, &sat),
+        };
+        for (int rc : rcs) o.i64(rc);
+        gyp_destroy(nullptr);
+        gyp_bank_destroy(nullptr);
+        bool untouched = vp == nullptr && bank == nullptr && ing == nullptr && sat == 1 && dop == 0.0;
+        for (int i = 0; i < 256; ++i) untouched = untouched && buf[i] == 0x5a;
+        o.i64(untouched ? 1 : 0);
+        std::free(buf);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- halo-readers
+// A handle as ingest_open_filtered / gyp_ingest_open_packed fill it in, without a context; sizes from the product's own helper; ring
+// slots of exactly host_block_bytes; the product's reader thread and take / release protocol.
+// cases.i64 rows: packed (0/1), fmt or bits, real, order, n_in, taps, block_ms, depth, file index, restart millisecond.
+static void halo_readers() {
+    const std::vector<int64_t> cases = read_array<int64_t>("cases.i64");
+    BlockLog log("blocks");
+    Out info("info.i64");
+    for (size_t c = 0; c * 10 < cases.size(); ++c) {
+        const int64_t* k = &cases[c * 10];
+        gyp_ingest* g = new gyp_ingest();
+        g->ctx = nullptr;
+        g->block_ms = (int32_t)k[6];
+        g->depth = (int32_t)k[7];
+        g->resampled = true;
+        g->real = k[2] != 0;
+        g->rs.taps = (int32_t)k[5];
+        g->rs.n_in = g->in_n = (int32_t)k[4];
+        g->halo_lo = g->rs.taps / 2 - 1;
+        g->halo_hi = g->rs.taps / 2;
+        if (k[0]) {
+            g->fmt = -1;
+            g->packed = true;
+            g->pk.bits = (int32_t)k[1];
+            g->pk.real = g->real;
+            g->pk.order = (int32_t)k[3];
+            g->ms_bytes = 1;
+        } else {
+            g->fmt = (int32_t)k[1];
+            g->sample_bytes = (size_t)(g->real ? 1 : 2) * ingest_word_bytes(g->fmt);
+            g->ms_bytes = (size_t)g->in_n * g->sample_bytes;
+        }
+        ingest_set_block_bytes(g);
+        const std::string path = in_path("h" + std::to_string(k[8]) + ".bin");
+        g->fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+        struct stat st;
+        REQUIRE(g->fd >= 0 && fstat(g->fd, &st) == 0);
+        g->total_ms = st.st_size > 0 ? (int64_t)((st.st_size - 1) / (off_t)g->ms_bytes) : 0;   // as ingest_finish_open counts them
+        if (g->sample_bytes) g->file_samples = (int64_t)(st.st_size / (off_t)g->sample_bytes);
+        if (g->packed) {
+            g->file_samples = (int64_t)st.st_size * 8 / g->pk.sample_bits();
+            g->total_ms = g->file_samples > 0 ? (g->file_samples - 1) / g->in_n : 0;
+        }
+        info.i64(g->total_ms);
+        info.i64(g->file_samples);
+        info.i64((int64_t)g->host_block_bytes);
+        g->host.assign(g->depth, nullptr);
+        g->host_first.assign(g->depth, 0);
+        g->host_ms.assign(g->depth, 0);
+        for (auto& p : g->host) REQUIRE((p = (uint8_t*)std::malloc(g->host_block_bytes)) != nullptr);   // no rounding up
+        auto consume = [&](int64_t tag) {
+            for (;;) {
+                ingest_release(g, g->taken);
+                int slot = -1;
+                int64_t first = -1;
+                int32_t n_ms = -1;
+                if (!ingest_take(g, &slot, &first, &n_ms, true)) break;
+                size_t n_bytes;
+                if (g->packed) n_bytes = (size_t)ingest_packed_span(g, first, n_ms).n_bytes;
+                else n_bytes = ((size_t)n_ms * g->in_n + g->halo_lo + g->halo_hi) * g->sample_bytes;
+                REQUIRE(n_bytes <= g->host_block_bytes);
+                log.block(tag, first, n_ms, g->host[slot], n_bytes);
+            }
+            REQUIRE(g->io_errno == 0);
+        };
+        ingest_start_reader(g, 0);
+        consume((int64_t)c * 2);
+        ingest_stop_reader(g);
+        if (k[9] <= g->total_ms) {
+            ingest_start_reader(g, k[9]);
+            consume((int64_t)c * 2 + 1);
+            ingest_stop_reader(g);
+        }
+        for (auto p : g->host) std::free(p);
+        ::close(g->fd);
+        delete g;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- small-parsers
+static void small_parsers() {
+    {   // cpulists.bin: strings, each closed by a NUL
+        const std::vector<uint8_t> all = read_bytes("cpulists.bin");
+        Out o("cpusets.bin");
+        for (size_t at = 0; at < all.size();) {
+            const std::string text((const char*)&all[at]);
+            at += text.size() + 1;
+            cpu_set_t* set = (cpu_set_t*)std::malloc(sizeof(cpu_set_t));
+            const bool any = parse_cpulist(text, set);
+            o.put((uint8_t)any);
+            for (int cpu = 0; cpu < CPU_SETSIZE; ++cpu) o.put((uint8_t)(CPU_ISSET(cpu, set) ? 1 : 0));
+            std::free(set);
+        }
+        o.put((int32_t)CPU_SETSIZE);
+    }
+    {
+        Out o("small_files.bin");
+        for (const char* name : {"missing", "empty", "big2000", "trailing"}) {
+            const std::string s = read_small_file(in_path(name));
+            o.put((int64_t)s.size());
+            o.bytes(s.data(), s.size());
+        }
+    }
+    {
+        Out o("round6.f64");
+        for (double x : read_array<double>("round6.f64")) o.put(round6(x));
+    }
+    {   // packings.bin: gyp_packing records; the refusal's text, or "ok"
+        const std::vector<uint8_t> all = read_bytes("packings.bin");
+        Out o("packings.txt");
+        for (size_t at = 0; at + sizeof(gyp_packing) <= all.size(); at += sizeof(gyp_packing)) {
+            gyp_packing* p = (gyp_packing*)std::malloc(sizeof(gyp_packing));
+            std::memcpy(p, &all[at], sizeof(gyp_packing));
+            PackedFormat f;
+            const char* why = packing_check(p, &f);
+            REQUIRE(packing_check(p, nullptr) == why);
+            o.line(why ? why : "ok " + std::to_string(f.bits) + " " + std::to_string((int)f.real) + " " + std::to_string(f.order) + " " + std::to_string(f.sample_bits()));
+            std::free(p);
+        }
+        o.line(packing_check(nullptr, nullptr));
+    }
+}
+
+}  // namespace drv
+
+int main(int argc, char** argv) {
+    if (argc != 4) drv::die("usage: prog <scenario> <in_dir> <out_dir>");
+    std::string san;
+#if __has_feature(address_sanitizer)
+    san += " address";
+#endif
+#if __has_feature(thread_sanitizer)
+    san += " thread";
+#endif
+#ifdef GYP_DRIVER_UBSAN
+    san += " undefined";
+#endif
+    std::printf("sanitizers:%s\n", san.c_str());
+    drv::g_in = argv[2];
+    drv::g_out = argv[3];
+    const std::pair<const char*, void (*)()> table[] = {
+        {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
+        {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
+    };
+    for (const auto& s : table)
+        if (std::string(argv[1]) == s.first) {
+            s.second();
+            std::fflush(stdout);
+            return 0;
+        }
+    drv::die(std::string("unknown scenario ") + argv[1]);
+}

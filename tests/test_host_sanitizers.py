@@ -1,0 +1,562 @@
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp) under ASan + UBSan and under TSan.
+
+tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
+(about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
+GPU: this file writes its inputs, the program writes raw arrays, and they are compared with numpy / big-integer models or with what the
+uninstrumented library returns through ctypes for the same calls.  A sanitizer report in this project's code is a bug.
+
+Nothing here is loaded into python under a sanitizer and nothing touches a GPU: the programs carry their own runtime, the
+environment is inherited as it is and only gains the variables below.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import errno
+import os
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import bits_scenarios
+import host_san_build
+from gypsum_amd import _lib
+from gypsum_amd.build import find_hipcc
+
+# measured: both programs build in 37 s side by side, the longest scenario takes 4 s; x2 for a loaded machine, rounded up
+pytestmark = pytest.mark.timeout(120)
+
+ASAN, TSAN = "asan_ubsan", "tsan"
+BOTH = [ASAN, TSAN]
+REPORT_WORDS = ("AddressSanitizer", "LeakSanitizer", "ThreadSanitizer", "runtime error:")
+N = 2046
+DTYPES = {0: np.float32, 1: np.int8, 2: np.int16, 3: np.uint8}      # GYP_FMT_*
+I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
+
+
+@pytest.fixture(scope="module")
+def programs():
+    try:
+        find_hipcc()
+    except RuntimeError as e:
+        pytest.skip(f"hipcc not found: {e}")
+    return {name: r["path"] for name, r in host_san_build.build().items()}
+
+
+def run(programs, which: str, scenario: str, tmp_path: Path) -> Path:
+    """One scenario in a fresh child process; returns the directory it wrote."""
+    out = tmp_path / f"out_{which}"
+    out.mkdir()
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", TSAN_OPTIONS="halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("ASAN_OPTIONS", None)
+    r = subprocess.run([str(programs[which]), scenario, str(tmp_path / "in"), str(out)], env=env, capture_output=True, text=True, timeout=60)
+    for word in REPORT_WORDS:
+        assert word not in r.stderr, f"{which} {scenario}:\n{r.stderr[-6000:]}"
+    assert r.returncode == 0, f"{which} {scenario}: exit {r.returncode}\n{r.stderr[-3000:]}"
+    assert r.stdout.splitlines()[0] == host_san_build.BANNER[which]
+    return out
+
+
+def indir(tmp_path: Path) -> Path:
+    d = tmp_path / "in"
+    d.mkdir()
+    return d
+
+
+def i64(rows) -> np.ndarray:
+    return np.array(rows, dtype="<i8")
+
+
+def blocks(out: Path, name: str = "blocks"):
+    """The driver's block log: (tag, first_ms, n_ms, bytes) per block handed out."""
+    meta = np.fromfile(out / f"{name}.i64", dtype="<i8").reshape(-1, 4)
+    blob = np.fromfile(out / f"{name}.bin", dtype=np.uint8)
+    ends = np.cumsum(meta[:, 3])
+    assert ends[-1] == len(blob) if len(meta) else len(blob) == 0
+    return [(int(t), int(f), int(n), blob[e - b:e]) for (t, f, n, b), e in zip(meta, ends)]
+
+
+def test_driver_never_makes_a_context():
+    text = host_san_build.DRIVER.read_text()
+    assert "gyp_create(" not in text
+    assert "LD_PRELOAD" not in text and "verify_asan_link_order" not in text
+
+
+# ------------------------------------------------------------------------------------------------------------ ingest-host
+def reader_sequence(total: int, block_ms: int, start: int = 0):
+    return [(f, min(block_ms, total - f)) for f in range(start, total, block_ms)]
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_ingest_host(programs, tmp_path, which):
+    d = indir(tmp_path)
+    rng = np.random.default_rng(11)
+    files = {}
+    for fmt, dt in DTYPES.items():
+        item = np.dtype(dt).itemsize
+        for idx, n_bytes in enumerate([0, 1, 2 * N * item, (2 * N + 1) * item, (23 * 2 * N + 2 * N - 1) * item]):
+            files[idx, fmt] = rng.integers(0, 256, n_bytes, dtype=np.uint8)
+            files[idx, fmt].tofile(d / f"f{idx}_{fmt}.bin")
+    cases = []
+    for (idx, fmt), data in files.items():
+        ms_bytes = 2 * N * np.dtype(DTYPES[fmt]).itemsize
+        total = (len(data) - 1) // ms_bytes if len(data) else 0
+        for block_ms in (1, 5):
+            for depth in (3, 64):
+                cases.append((idx, fmt, N, block_ms, depth, total // 2))
+    i64(cases).tofile(d / "cases.i64")
+    rates, firsts = (2_046_000, 8_184_000, 16_368_000, 49_104_000), (0, 1, 999, 12345, 3_599_000, 86_399_990)   # test_times_equal_python_round
+    i64([(fs, f) for fs in rates for f in firsts]).tofile(d / "times.i64")
+
+    out = run(programs, which, "ingest-host", tmp_path)
+    want_blocks, want_info = [], []
+    for c, (idx, fmt, _, block_ms, depth, mid) in enumerate(cases):
+        data = files[idx, fmt]
+        ms_bytes = 2 * N * np.dtype(DTYPES[fmt]).itemsize
+        total = (len(data) - 1) // ms_bytes if len(data) else 0
+        assert total == [0, 0, 0, 1, 23][idx]
+        seq = [(4 * c, f, n) for f, n in reader_sequence(total, block_ms)] + [(4 * c, -1, 0)]
+        seq += [(4 * c + 1, -1, 0)] * 2 + [(4 * c + 2, -1, 0)]
+        after = reader_sequence(total, block_ms, mid)[:2]
+        seq += [(4 * c + 3, f, n) for f, n in after] + [(4 * c + 3, -1, 0)] * (2 - len(after))
+        want_blocks += [(t, f, n, data[f * ms_bytes:(f + n) * ms_bytes] if n else data[:0]) for t, f, n in seq]
+        want_info += [total, -1, -1, -1, -1, -1, -1, -1 if fmt == 0 else 0]
+    want_info += [-1, -1, 0, _lib.GYP_E_IO, -1, -1, -1, -1, -2, -1]
+    got = blocks(out)
+    assert [(t, f, n) for t, f, n, _ in got] == [(t, f, n) for t, f, n, _ in want_blocks]
+    for (t, f, n, a), (_, _, _, b) in zip(got, want_blocks):
+        assert np.array_equal(a, b), (t, f, n)
+    assert np.fromfile(out / "info.i64", dtype="<i8").tolist() == want_info
+    times = np.fromfile(out / "times.f64", dtype="<f8").reshape(-1, 2, 40)
+    k = 0
+    for fs in rates:
+        n = fs // 1000
+        for first in firsts:
+            assert times[k, 0].tolist() == [round((first + i) * n / fs, 6) for i in range(40)]
+            assert times[k, 1].tolist() == [round((first + i + 1) * n / fs, 6) for i in range(40)]
+            k += 1
+
+
+# ------------------------------------------------------------------------------------------------------------ ingest-races
+@pytest.mark.parametrize("which", BOTH)
+def test_ingest_races(programs, tmp_path, which):
+    d = indir(tmp_path)
+    rng = np.random.default_rng(12)
+    ms_bytes = 2 * N * 4
+    total = 300
+    rec = rng.integers(0, 256, total * ms_bytes + 20, dtype=np.uint8)
+    rec.tofile(d / "rec.bin")
+    rec[:20 * ms_bytes + 4].tofile(d / "shrinks.bin")
+    seeks = np.random.default_rng(2026).integers(0, total + 1, 200)
+    i64(seeks).tofile(d / "seeks.i64")
+
+    out = run(programs, which, "ingest-races", tmp_path)
+
+    def one(tag, ms, block_ms, tot=total):
+        return (tag, ms, min(block_ms, tot - ms)) if ms < tot else (tag, -1, 0)
+
+    want = [one(1, (i * 37) % (total + 1), 200) for i in range(0, 60, 3)]
+    want += [one(2, int(ms), 4) for ms in seeks]
+    want += [(3, f, n) for f, n in reader_sequence(total, 16)] + [(3, -1, 0)]
+    want += [(4, 0, 2), (4, 2, 2), (4, 4, 2), (5, 0, 2)]
+    got = blocks(out)
+    assert [(t, f, n) for t, f, n, _ in got] == want
+    for t, f, n, data in got:      # every block handed out is the file's bytes
+        assert np.array_equal(data, rec[f * ms_bytes:(f + n) * ms_bytes]), (t, f, n)
+    assert np.fromfile(out / "info.i64", dtype="<i8").tolist() == [_lib.GYP_E_IO, _lib.GYP_E_IO]
+    assert (out / "shrinks_error.txt").read_text().strip() == "gyp_ingest: read failed: " + os.strerror(errno.EIO)
+    for who, block_ms in ((0, 5), (1, 3)):
+        want = []
+        for start in (0, 0, 100):
+            want += [(6 + who, f, n) for f, n in reader_sequence(total, block_ms, start)] + [(6 + who, -1, 0)]
+        got = blocks(out, f"thread{who}")
+        assert [(t, f, n) for t, f, n, _ in got] == want
+        for t, f, n, data in got:
+            assert np.array_equal(data, rec[f * ms_bytes:(f + n) * ms_bytes]), (who, f, n)
+    assert (out / "thread_errors.txt").read_text().splitlines() == ["gyp_ingest_seek: millisecond out of range",
+                                                                     "gyp_ingest_set_scale: scale must be positive and finite"]
+
+
+# ------------------------------------------------------------------------------------------------------------ bits
+def bits_plan():
+    names = sorted(bits_scenarios.scenarios())
+    # every stream in pushes of 1, 7 and 1000 symbols; capacities 0, 1 and ample crossed with 7 and 1000, in turn with 1 (a third of the calls)
+    return names, [(k, push, cap, {0: 1, 1: 2, 4096: 0}[cap]) for k in range(len(names)) for push in (1, 7, 1000)
+                   for cap in ((0, 1, 4096) if push > 1 else ((0, 1, 4096)[k % 3],))]
+
+
+def block_table(streams):
+    """3 channels x 1500 ms of gyp_track_rec: channel 1 loses lock at ms 700 (a status-1 record, status 2 after), channel 2 carries code phases."""
+    n_ms = 1500
+    recs = np.zeros((3, n_ms), dtype=_lib.TRACK_REC)
+    for c, name in enumerate(("clean_phase7", "clean_phase0", "noisy15")):
+        recs[c]["pseudosymbol"] = streams[name]["symbols"][:n_ms]
+    recs[1, 700]["status"] = 1
+    recs[1, 701:]["status"] = 2
+    recs[1, 700:]["pseudosymbol"] = 0
+    recs[2]["code_phase"] = (np.arange(n_ms) * 37) % 2046
+    return recs, streams["clean_phase7"]["start"][:n_ms].copy(), streams["clean_phase7"]["end"][:n_ms].copy(), [0, 1, 20, 21, 100, 777, 1000, n_ms]
+
+
+def bits_through_ctypes(streams, names, plan):
+    """The driver's calls, one for one, on the uninstrumented library (pinned to the reference by test_bits.py)."""
+    lib = _lib.load()
+    events, cursors, states, counts = [], [], [], []
+
+    def state(b, ch, into):
+        st = np.zeros(1, dtype=_lib.BITS_STATE)
+        assert lib.gyp_bits_get_state(b, ch, _lib.ptr(st)) == 0
+        into.append(st.tobytes())
+
+    for k, push, cap, reset in plan:
+        s = streams[names[k]]
+        sym, start, end = (np.ascontiguousarray(s[x]) for x in ("symbols", "start", "end"))
+        b = C.c_void_p()
+        assert lib.gyp_bits_create(3, C.byref(b)) == 0
+        total, reset_done = len(sym), reset == 0
+        ev = np.zeros(max(cap, 5), dtype=_lib.BIT_EVENT)
+        cur = np.zeros(push, dtype=np.int32)
+        n_ev = C.c_int32()
+        for at in range(0, total, push):
+            n = min(push, total - at)
+            if not reset_done and at >= total // 2:
+                assert lib.gyp_bits_reset(b, -1 if reset == 2 else 1) == 0
+                reset_done = True
+            ts, te = C.c_void_p(start.ctypes.data + 8 * at), C.c_void_p(end.ctypes.data + 8 * at)
+            assert lib.gyp_bits_push(b, 1, n, ts, ts, te, C.c_void_p(sym.ctypes.data + at), _lib.ptr(cur), _lib.ptr(ev) if cap else None, cap, C.byref(n_ev)) == 0
+            counts.append(n_ev.value)
+            events.append(ev[:n_ev.value].tobytes())
+            cursors.append(cur[:n].tobytes())
+            state(b, 1, states)
+        while True:
+            assert lib.gyp_bits_drain(b, _lib.ptr(ev), 5, C.byref(n_ev)) == 0
+            counts.append(n_ev.value)
+            events.append(ev[:n_ev.value].tobytes())
+            if n_ev.value == 0:
+                break
+        state(b, 0, states)
+        lib.gyp_bits_destroy(b)
+    recs, start, end, cuts = block_table(streams)
+    b = C.c_void_p()
+    assert lib.gyp_bits_create(3, C.byref(b)) == 0
+    bev, bstates, bcounts = [], [], []
+    n_ev = C.c_int32()
+    for i, (a, z) in enumerate(zip(cuts[:-1], cuts[1:])):
+        cap = 3 if i % 2 else 1000
+        ev = np.zeros(cap, dtype=_lib.BIT_EVENT)
+        part = np.ascontiguousarray(recs[:, a:z])
+        assert lib.gyp_bits_push_block(b, _lib.ptr(part), 3, z - a, _lib.ptr(np.ascontiguousarray(start[a:z])), _lib.ptr(np.ascontiguousarray(end[a:z])),
+                                       _lib.ptr(ev), cap, C.byref(n_ev)) == 0
+        bcounts.append(n_ev.value)
+        bev.append(ev[:n_ev.value].tobytes())
+        for c in range(3):
+            state(b, c, bstates)
+    lib.gyp_bits_destroy(b)
+    return [b"".join(x) for x in (events, cursors, states, bev, bstates)] + [counts, bcounts]
+
+
+def test_bits(programs, tmp_path):
+    d = indir(tmp_path)
+    streams = bits_scenarios.scenarios()
+    names, plan = bits_plan()
+    for k, name in enumerate(names):
+        for key, ext in (("symbols", "sym"), ("start", "start"), ("end", "end")):
+            np.ascontiguousarray(streams[name][key]).tofile(d / f"s{k}.{ext}")
+    i64(plan).tofile(d / "plan.i64")
+    recs, start, end, cuts = block_table(streams)
+    recs.tofile(d / "recs.bin")
+    start.tofile(d / "block.start")
+    end.tofile(d / "block.end")
+    i64(cuts).tofile(d / "cuts.i64")
+
+    out = run(programs, ASAN, "bits", tmp_path)
+    events, cursors, states, bev, bstates, counts, bcounts = bits_through_ctypes(streams, names, plan)
+    assert sum(counts) > 2000 and sum(bcounts) > 100                        # the FIFO, the drain and the block path all emitted bits
+    assert np.fromfile(out / "counts.i32", dtype="<i4").tolist() == counts
+    assert np.fromfile(out / "block_counts.i32", dtype="<i4").tolist() == bcounts
+    for name, want in (("events.bin", events), ("cursors.i32", cursors), ("states.bin", states), ("block_events.bin", bev), ("block_states.bin", bstates)):
+        assert (out / name).read_bytes() == want, name
+    lost = np.frombuffer(bstates, dtype=_lib.BITS_STATE).reshape(-1, 3)[-1]
+    assert [int(v) for v in lost["processed_pseudosymbol_count"]] == [1500, 700, 1500]
+    assert np.fromfile(out / "refusals.i64", dtype="<i8").tolist() == [-1] * 13
+
+
+# ------------------------------------------------------------------------------------------------------------ spans
+def span_model(bits, real, spm, file_bytes, first, n):
+    """include/gypsum_hip.h's contract of gyp_packed_span in Python integers: (rc, in_first, in_n, first_byte, n_bytes, file_samples,
+    total_ms, bit0); GYP_E_BAD_ARG, outputs untouched, where the contract's own arithmetic would leave int64."""
+    bad = (-1,) + (-777,) * 7
+    B = bits * (1 if real else 2)
+    if n < 0 or file_bytes < 0 or spm < 1:
+        return bad
+    file_samples = 8 * file_bytes // B
+    a, b = max(first, 0), min(first + n, file_samples)
+    if not all(I64_MIN <= v <= I64_MAX for v in (8 * file_bytes, first + n)):
+        return bad
+    total_ms = (file_samples - 1) // spm if file_samples > 0 else 0
+    if b <= a:                                       # no part inside the file: no byte arithmetic to do
+        return (0, 0, 0, 0, 0, file_samples, total_ms, 0)
+    if not all(I64_MIN <= v <= I64_MAX for v in (a * B, b * B + 7)):
+        return bad
+    first_byte = a * B // 8
+    return (0, a, b - a, first_byte, (b * B + 7) // 8 - first_byte, file_samples, total_ms, a * B % 8)
+
+
+def test_spans(programs, tmp_path):
+    d = indir(tmp_path)
+    cases, want = [], []
+    for bits in (1, 2, 4):
+        for real in (0, 1):
+            for order in (0, 1):
+                for file_bytes in (0, 1, 2, 4095, 4096, 2 ** 31, 2 ** 40, 2 ** 60):
+                    fsamp = 8 * file_bytes // (bits * (1 if real else 2))
+                    for first in (-2 ** 40, -1, 0, 1, fsamp - 1, fsamp, 2 ** 60):
+                        for n in (0, 1, 7, 2 ** 31, 2 ** 60):
+                            if first > I64_MAX:      # (the file_samples of a 2^60-byte file of 1-bit words: not an int64, cannot be asked)
+                                continue
+                            w = span_model(bits, real, N, file_bytes, first, n)
+                            cases.append((bits, real, order, N, file_bytes, first, n, fsamp if w[0] == 0 else -1))
+                            want.append(w)
+    assert len(cases) > 3000 and sum(w[0] == 0 for w in want) > 2000 and sum(w[0] != 0 for w in want) > 100
+    i64(cases).tofile(d / "cases.i64")
+    out = run(programs, ASAN, "spans", tmp_path)
+    pub = np.fromfile(out / "public.i64", dtype="<i8").reshape(-1, 8)
+    stat = np.fromfile(out / "static.i64", dtype="<i8").reshape(-1, 5)
+    for case, w, p, s in zip(cases, want, pub.tolist(), stat.tolist()):
+        assert tuple(p) == w, case
+        assert tuple(s) == ((w[1], w[2], w[3], w[4], w[7]) if w[0] == 0 else (0, 0, 0, 0, 0)), case
+    assert len(pub) == len(stat) == len(cases)
+
+
+# ------------------------------------------------------------------------------------------------------------ designs
+def design_cases():
+    """(kind, fs_in, fs_out, if_hz, taps, expected return code); kind 0 gyp_resample_design, 1 gyp_ddc_design."""
+    from ddc_model import TAPS as DDC_TAPS
+    from test_gpu_ddc import VALUE_CASES
+    from test_gpu_resample_edges import EDGE_PAIRS, TAPS as RS_TAPS
+    ok, arg, rate = 0, _lib.GYP_E_BAD_ARG, _lib.GYP_E_BAD_RATE
+    rows = [(0, fi, fo, 0, t, ok) for fi, fo in EDGE_PAIRS for t in (0, *RS_TAPS)]
+    rows += [(0, 2_048_000, 2_046_000, 0, t, arg) for t in (17, 96, 128, -16)]
+    rows += [(0, 1_000_000, 2_000_000, 0, 16, ok), (0, 1_000_000, 2_001_000, 0, 16, rate),          # ratio 2 and one kHz past it
+             (0, 4_000_000, 2_000_000, 0, 16, ok), (0, 4_001_000, 2_000_000, 0, 16, rate),          # ratio 0.5 and one kHz past it
+             (0, 2_046_000, 2_046_000, 0, 32, rate), (0, 2_048_500, 2_046_000, 0, 32, rate), (0, 2_048_000, 2_046_500, 0, 32, rate),
+             (0, 0, 2_046_000, 0, 32, rate), (0, 2_048_000, 0, 0, 32, rate), (0, -2_048_000, 2_046_000, 0, 32, rate)]
+    rows += [(1, fi, fo, f, t, ok) for fi, fo, f in VALUE_CASES for t in (0, *DDC_TAPS)]
+    rows += [(1, 16_368_000, 4_092_000, 4_092_000, t, arg) for t in (16, 24, 33, 256)]
+    rows += [(1, 16_368_000, 2_046_000, 4_092_000, 128, ok), (1, 16_369_000, 2_046_000, 4_092_000, 128, rate),      # 8 fs_out >= fs_in
+             (1, 16_368_000, 4_092_000, 1_841_400, 64, ok), (1, 16_368_000, 4_092_000, 1_841_399, 64, rate),        # 20 |if| >= 9 fs_out
+             (1, 16_368_000, 4_092_000, -1_841_400, 64, ok), (1, 16_368_000, 4_092_000, -1_841_399, 64, rate),
+             (1, 16_368_000, 4_092_000, 6_342_600, 64, ok), (1, 16_368_000, 4_092_000, 6_342_601, 64, rate),        # 20 |if| + 9 fs_out <= 10 fs_in
+             (1, 16_368_000, 4_092_000, -6_342_600, 64, ok), (1, 16_368_000, 4_092_000, -6_342_601, 64, rate),
+             (1, 16_368_000, 4_092_000, 0, 64, rate), (1, 2 ** 31, 2 ** 28, 2 ** 29, 64, rate), (1, 2_147_484_000, 268_436_000, 536_870_000, 64, rate),
+             (1, 16_368_500, 4_092_000, 4_092_000, 64, rate), (1, 16_368_000, 4_092_500, 4_092_000, 64, rate),
+             (1, 4_092_000, 8_184_000, 1_023_000, 64, rate), (1, 16_368_000, 4_092_000, 2 ** 40, 64, rate)]
+    return rows
+
+
+def test_designs(programs, tmp_path):
+    d = indir(tmp_path)
+    rows = design_cases()
+    i64([r[:5] for r in rows]).tofile(d / "cases.i64")
+    out = run(programs, ASAN, "designs", tmp_path)
+    meta = np.fromfile(out / "meta.i64", dtype="<i8").reshape(-1, 3)
+    tables = np.fromfile(out / "tables.f32", dtype=np.uint8)
+    lib = _lib.load()
+    at = 0
+    for (kind, fi, fo, f, taps, want_rc), (rc, L, T) in zip(rows, meta.tolist()):
+        assert rc == want_rc, (kind, fi, fo, f, taps)
+        n_phases, t_out = C.c_int32(-1), C.c_int32(-1)
+        if kind:
+            assert lib.gyp_ddc_design(fi, fo, f, taps, None, C.byref(n_phases), C.byref(t_out)) == rc
+        else:
+            assert lib.gyp_resample_design(fi, fo, taps, None, C.byref(n_phases)) == rc
+            t_out.value = (taps or 32) if rc == 0 else -1
+        assert (L, T) == (n_phases.value, t_out.value)
+        if rc:
+            continue
+        ref = np.zeros(L * T, dtype=np.float32)
+        assert (lib.gyp_ddc_design(fi, fo, f, taps, _lib.ptr(ref), None, None) if kind else lib.gyp_resample_design(fi, fo, taps, _lib.ptr(ref), None)) == 0
+        assert tables[at:at + 4 * L * T].tobytes() == ref.tobytes(), (kind, fi, fo, f, taps)
+        at += 4 * L * T
+    assert len(meta) == len(rows) and at == len(tables)
+
+
+# ------------------------------------------------------------------------------------------------------------ misc
+def test_misc(programs, tmp_path):
+    d = indir(tmp_path)
+    lib = _lib.load()
+    cells = np.zeros(6, dtype=_lib.CELL)
+    cells["peak"] = [1.5, 1.5, 2.0, 3.0, 0.0, 7.25]
+    cells["n_max"] = [N, N, 3, 1, N, 1]
+    cells["sum"] = [N * 1.5, 100.0, 6.0, 5000.0, 0.0, 7.25]          # 0/0, x/0, a zero mean, an ordinary profile, all zero, N - n_max = 0 below
+    cells_n = np.array([N, N, N, N, N, 1], dtype="<i4")
+    cells.tofile(d / "cells.bin")
+    cells_n.tofile(d / "cells_n.i32")
+    nav = [(seed, stream, sat, off, ms) for seed in (0, 1, 2 ** 63 + 5) for stream in (0, 3) for sat in (1, 32) for off in (0, 19)
+           for ms in (-2 ** 40, -21, -20, -1, 0, 19, 20, 2 ** 40, 2 ** 40 + 19)]
+    i64([tuple(v if v < 2 ** 63 else v - 2 ** 64 for v in row) for row in nav]).tofile(d / "nav.i64")
+    n_list, sub_list = list(range(1, 3001)) + [10 ** 6], [100, 167, 500, 2000, 99, 2001, 0]
+    i64(n_list + [-1] + sub_list).tofile(d / "layout.i64")      # (-1 closes the first list)
+
+    out = run(programs, ASAN, "misc", tmp_path)
+    chips = np.zeros(32 * 1023, dtype=np.uint8)
+    assert lib.gyp_prn_chips(_lib.ptr(chips)) == 0
+    assert (out / "prn_chips.u8").read_bytes() == chips.tobytes()
+    lanes = np.fromfile(out / "lanes.f32", dtype=np.float32).reshape(2, -1)
+    for row, sat in zip(lanes, (1, 32)):
+        ref = np.zeros(32 * 64 * 2, dtype=np.float32)
+        assert lib.gyp_prn_spectrum_lane_layout(sat, _lib.ptr(ref)) == 0
+        assert row.tobytes() == ref.tobytes()
+    assert np.fromfile(out / "lanes_rc.i64", dtype="<i8").tolist() == [0, 0, -1, -1, -1]
+    with np.errstate(all="ignore"):
+        pk = cells["peak"].astype(np.float64)
+        want = pk / ((cells["sum"] - cells["n_max"] * pk) / (cells_n - cells["n_max"]).astype(np.float64))
+    got = np.fromfile(out / "strength.f64", dtype="<f8")
+    assert np.array_equal(got, want, equal_nan=True) and np.isnan(got[0]) and got[1] == 0.0 and np.isinf(got[2])
+    assert np.fromfile(out / "nav_bits.i64", dtype="<i8").tolist() == [lib.gyp_synth_nav_bit(*row) for row in nav]
+    ref = np.zeros(1, dtype=_lib.PARAMS)
+    lib.gyp_params_default(_lib.ptr(ref))
+    assert (out / "params.f64").read_bytes() == ref.tobytes()
+    layout = np.fromfile(out / "layout.i32", dtype="<i4").reshape(len(sub_list), len(n_list), 34)
+    starts = np.zeros(33, dtype=np.int32)
+    for s, sub in enumerate(sub_list):
+        for i, n_ms in enumerate(n_list):
+            starts[:] = -777
+            n = lib.gyp_debug_spec_layout_for(n_ms, sub, _lib.ptr(starts))
+            assert layout[s, i, 0] == n and np.array_equal(layout[s, i, 1:], starts), (n_ms, sub)
+            if not 100 <= sub <= 2000:
+                assert n == -1 and (starts == -777).all()
+            else:
+                assert 1 <= n <= 32 and starts[0] == 0 and starts[n] == n_ms and (np.diff(starts[:n + 1]) > 0).all() and (starts[n + 1:] == -777).all()
+    null_rc = np.fromfile(out / "null_rc.i64", dtype="<i8").tolist()
+    assert len(null_rc) > 60 and null_rc[:-1] == [-1] * (len(null_rc) - 1) and null_rc[-1] == 1
+
+
+# ------------------------------------------------------------------------------------------------------------ halo-readers
+def halo_cases():
+    """(packed, fmt or bits, real, order, n_in, taps, block_ms, depth, file length in bytes) for the hand-built handles."""
+    kinds = [(0, fmt, real, 0) for fmt in DTYPES for real in (0, 1)] + [(1, bits, real, (bits + real) % 2) for bits in (1, 2, 4) for real in (0, 1)]
+    rows = []
+    for packed, what, real, order in kinds:
+        # bits per sample
+        B = what * (1 if real else 2) if packed else 8 * np.dtype(DTYPES[what]).itemsize * (1 if real else 2)
+        for n_in in (2048, 16368, 38192):
+            for taps in (16, 64, 128):
+                lengths = [0, (taps // 4 * B + 7) // 8 + (1 if B > 8 else 0), ((n_in + 1) * B + 7) // 8, 23 * n_in * B // 8 + 5 * max(B // 8, 1) + (B // 16 or 1)]
+                for block_ms in (1, 7):
+                    rows += [(packed, what, real, order, n_in, taps, block_ms, 3, length) for length in lengths]
+    return rows
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_halo_readers(programs, tmp_path, which):
+    d = indir(tmp_path)
+    rows = halo_cases()
+    blob = np.random.default_rng(13).integers(0, 256, max(r[8] for r in rows), dtype=np.uint8)
+    index = {length: i for i, length in enumerate(sorted({r[8] for r in rows}))}
+    for length, i in index.items():
+        blob[:length].tofile(d / f"h{i}.bin")
+    cases = []
+    for packed, what, real, order, n_in, taps, block_ms, depth, length in rows:
+        B = what * (1 if real else 2) if packed else 8 * np.dtype(DTYPES[what]).itemsize * (1 if real else 2)
+        file_samples = 8 * length // B
+        total = (file_samples - 1) // n_in if packed else ((length - 1) // (n_in * B // 8) if length else 0)
+        total = max(total, 0)
+        cases.append((packed, what, real, order, n_in, taps, block_ms, depth, index[length], total // 2, B, file_samples, total, length))
+    i64([c[:10] for c in cases]).tofile(d / "cases.i64")
+
+    out = run(programs, which, "halo-readers", tmp_path)
+    info = np.fromfile(out / "info.i64", dtype="<i8").reshape(-1, 3).tolist()
+    got = blocks(out)
+    at = 0
+    for c, (packed, what, real, order, n_in, taps, block_ms, depth, _, restart, B, file_samples, total, length) in enumerate(cases):
+        span = block_ms * n_in + taps - 1
+        slot_bytes = (span * B + 7) // 8 + 1 if packed else span * B // 8
+        assert info[c] == [total, file_samples, slot_bytes], cases[c]
+        data = blob[:length]
+        for tag, start in ((2 * c, 0), (2 * c + 1, restart)):
+            for first, n_ms in reader_sequence(total, block_ms, start):
+                t, f, n, raw = got[at]
+                at += 1
+                assert (t, f, n) == (tag, first, n_ms), cases[c]
+                s0, count = first * n_in - (taps // 2 - 1), n_ms * n_in + taps - 1
+                if packed:          # the covering bytes of the part inside the file, as they are in the file
+                    rc, _, _, first_byte, n_bytes, _, _, _ = span_model(what, real, n_in, length, s0, count)
+                    assert rc == 0
+                    want = data[first_byte:first_byte + n_bytes]
+                else:               # the zero-padded slice of the file's whole samples
+                    sb = B // 8
+                    want = np.zeros(count * sb, dtype=np.uint8)
+                    a, b = max(s0, 0), min(s0 + count, file_samples)
+                    if b > a:
+                        want[(a - s0) * sb:(b - s0) * sb] = data[a * sb:b * sb]
+                assert np.array_equal(raw, want), (cases[c], first)
+    assert at == len(got)
+
+
+# ------------------------------------------------------------------------------------------------------------ small-parsers
+def cpulist_model(text: str, setsize: int):
+    """ingest.hpp parse_cpulist on digits, '-' and ',': stop at the first malformed item, clip at CPU_SETSIZE."""
+    import re
+    cpus, p = set(), 0
+    while p < len(text):
+        m = re.compile(r"\d+").match(text, p)
+        if not m:
+            break
+        a = b = int(m.group())
+        p = m.end()
+        if text[p:p + 1] == "-":
+            m = re.compile(r"\d+").match(text, p + 1)
+            if not m or int(m.group()) < a:
+                break
+            b, p = int(m.group()), m.end()
+        cpus.update(range(a, min(b, setsize - 1) + 1))
+        if text[p:p + 1] != ",":
+            break
+        p += 1
+    return cpus
+
+
+def test_small_parsers(programs, tmp_path):
+    d = indir(tmp_path)
+    long_list = ",".join(f"{i}-{i + 1}" if i % 6 == 0 else str(i) for i in range(0, 2400, 3))
+    assert len(long_list) >= 5000
+    lists = ["0-31,128-159", "", "7", "3-1", "5,", "0-99999", "x", "1-", long_list, "0-3,9-8,12", "1023,1024,2", "4,,5"]
+    (d / "cpulists.bin").write_bytes(b"".join(s.encode() + b"\0" for s in lists))
+    (d / "empty").write_bytes(b"")
+    (d / "big2000").write_bytes(b"7" * 1999 + b"\n")
+    (d / "trailing").write_bytes(b"0-31,128-159 \n \n")
+    rates, firsts = (2_046_000, 8_184_000, 16_368_000, 49_104_000), (0, 1, 999, 12345, 3_599_000, 86_399_990)
+    xs = [(first + i) * (fs // 1000) / fs for fs in rates for first in firsts for i in range(41)] + [0.0, 1e-7, 86399.9999995]
+    np.array(xs, dtype="<f8").tofile(d / "round6.f64")
+    packs = np.zeros(12, dtype=_lib.PACKING)
+    packs["bits"] = [1, 2, 4, 3, 0, 8, 2, 2, 2, 2, 2, 1]
+    packs["real"] = [0, 1, 1, 0, 0, 0, 2, 0, 0, 0, 0, 1]
+    packs["order"] = [0, 1, 0, 0, 0, 0, 0, 2, 0, 0, 0, 1]
+    packs["reserved"] = [0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0]
+    packs["levels"][9][3] = np.nan
+    packs["levels"][10][0] = np.inf
+    packs["levels"][11][2:] = np.nan                 # entries >= 2^bits are ignored
+    packs.tofile(d / "packings.bin")
+
+    out = run(programs, ASAN, "small-parsers", tmp_path)
+    raw = (out / "cpusets.bin").read_bytes()
+    setsize = int(np.frombuffer(raw[-4:], dtype="<i4")[0])
+    sets = np.frombuffer(raw[:-4], dtype=np.uint8).reshape(len(lists), 1 + setsize)
+    for text, row in zip(lists, sets):
+        want = cpulist_model(text, setsize)
+        assert set(np.flatnonzero(row[1:]).tolist()) == want and row[0] == (1 if want else 0), text[:40]
+    assert cpulist_model("0-31,128-159", 1024) == set(range(32)) | set(range(128, 160)) and cpulist_model("1-", 1024) == set()
+    raw = (out / "small_files.bin").read_bytes()
+    got, at = [], 0
+    while at < len(raw):
+        n = int(np.frombuffer(raw[at:at + 8], dtype="<i8")[0])
+        got.append(raw[at + 8:at + 8 + n])
+        at += 8 + n
+    assert got == [b"", b"", b"7" * 1999, b"0-31,128-159"]
+    assert np.fromfile(out / "round6.f64", dtype="<f8").tolist() == [round(x, 6) for x in xs]
+    bad_bits, levels = "packing.bits must be 1, 2 or 4", "packing.levels[c] must be finite for every code c < 2^bits"
+    assert (out / "packings.txt").read_text().splitlines() == [
+        "ok 1 0 0 2", "ok 2 1 1 2", "ok 4 1 0 4", bad_bits, bad_bits, bad_bits, "packing.real must be 0 or 1",
+        "packing.order must be GYP_PACK_MSB_FIRST or GYP_PACK_LSB_FIRST", "packing.reserved must be 0", levels, levels, "ok 1 1 1 1", "packing is NULL"]
