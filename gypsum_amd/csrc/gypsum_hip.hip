@@ -13,11 +13,13 @@
 #include <dlfcn.h>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gypsum_hip.h"
 #include "kernels.hpp"
 #include "bit_integrator.hpp"
+#include "grid_plan.hpp"
 
 using namespace gyp;
 
@@ -136,7 +138,7 @@ struct gyp_ctx {
     int32_t* d_acq_witness = nullptr;   // [kAcqWitnessInts] gyp_debug_get("last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells", and "..._l<k>" per level): what the levels of
                                         // the last search on this context did (acq_init_kernel zeroes, the compact kernels add; read on request only)
     int acq_witness_lanes = 1;          // parts of that search: this context and the first acq_witness_lanes - 1 helpers
-    int last_grid_path = 0;       // gyp_debug_get("last_grid_path"): which cells kernel the last gyp_correlate_grid* call took (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
+    GridPlan last_grid_plan{};    // of the last gyp_correlate_grid* call; gyp_debug_get("last_grid_path") reads its path (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
     int grid_fused_waves = 12;    // gyp_debug_set("grid_fused_waves"): 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
     bool no_grid_fused = false;   // gyp_debug_set("no_grid_fused"): A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
     bool no_grid_parts = false;   // gyp_debug_set("no_grid_parts"): A/B switch: flat-grid work items take whole units (no branch runs + merge)
@@ -592,18 +594,36 @@ double gyp_cell_strength(const gyp_cell* c, int32_t samples_per_ms) {
 static int blocks_per_cu(int k) { return k > 8 ? 1 : 16 / k; }
 static int threads_for(int k) { return 64 * largest_divisor_up_to_8(k); }
 
-template <typename KernelT, typename ParamsT>
-static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds, hipStream_t stream) {
+// a launch with `lds` bytes of dynamic LDS (above 64 KB a kernel has to be given leave first)
+template <typename KernelT, typename... Args>
+static int launch_dyn(gyp_ctx* ctx, KernelT kernel, dim3 grid, dim3 threads, size_t lds, hipStream_t stream, const Args&... args) {
     HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads_for(k)), lds, stream, p);
+    hipLaunchKernelGGL(kernel, grid, threads, lds, stream, args...);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
+}
+template <typename KernelT, typename ParamsT>
+static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds, hipStream_t stream) {
+    return launch_dyn(ctx, kernel, dim3(grid), dim3(threads_for(k)), lds, stream, p);
 }
 template <typename KernelT, typename ParamsT>
 static int launch_k(gyp_ctx* ctx, KernelT kernel, int k, int grid, const ParamsT& p, size_t lds) {   // on the context's stream
     return launch_k(ctx, kernel, k, grid, p, lds, ctx->stream);
 }
 
+// The stream's samples per chip as a compile-time constant: f(std::integral_constant<int, K>) of the rate set by gyp_set_stream_format
+template <typename F>
+static int for_rate(gyp_ctx* ctx, F&& f) {
+    switch (ctx->k) {
+#define X(K) case K: return f(std::integral_constant<int, K>{});
+        GYP_FOR_EACH_RATE(X)
+#undef X
+    }
+    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+}
+// a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
+template <typename F>
+static auto for_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
 static int launch_cells(gyp_ctx* ctx, const CellsParams& p, int integration) {
     // gyp_debug_set "cells_cu_reserve" n: the correlation-cell launches of this context (acquisition levels, gyp_correlate_cells) size
@@ -619,13 +639,10 @@ static int launch_cells(gyp_ctx* ctx, const CellsParams& p, int integration) {
         return p.prof ? launch_k(ctx, corr_cells_pipe_kernel<8, true>, 8, grid1, p, lds_bytes_pipe<8>())
                       : launch_k(ctx, corr_cells_pipe_kernel<8, false>, 8, grid1, p, lds_bytes_pipe<8>());
     }
-    switch (ctx->k) {
-#define X(K) case K: return coh ? launch_k(ctx, corr_cells_kernel<K, true>, K, grid, p, lds_bytes<K>()) \
-                                : launch_k(ctx, corr_cells_kernel<K, false>, K, grid, p, lds_bytes<K>());
-        GYP_FOR_EACH_RATE(X)
-#undef X
-    }
-    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    return for_rate(ctx, [&](auto rate) {
+        constexpr int K = decltype(rate)::value;
+        return for_flag(coh, [&](auto c) { return launch_k(ctx, corr_cells_kernel<K, decltype(c)::value>, K, grid, p, lds_bytes<K>()); });
+    });
 }
 
 // A level's shared forward transforms (acquire_search): MODE 1 over the units, then MODE 2 over their cells.  Both walk device-side work
@@ -640,12 +657,10 @@ static int launch_cells_shared(gyp_ctx* ctx, const CellsParams& p_units, const C
 
 static int launch_track_step(gyp_ctx* ctx, const TrackStepParams& p) {
     const int grid = std::max(1, std::min(p.n_chan, ctx->n_cus * blocks_per_cu(ctx->k)) & ~7);
-    switch (ctx->k) {
-#define X(K) case K: return launch_k(ctx, track_step_kernel<K>, K, grid, p, lds_bytes<K>());
-        GYP_FOR_EACH_RATE(X)
-#undef X
-    }
-    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    return for_rate(ctx, [&](auto rate) {
+        constexpr int K = decltype(rate)::value;
+        return launch_k(ctx, track_step_kernel<K>, K, grid, p, lds_bytes<K>());
+    });
 }
 
 template <bool PROF>
@@ -660,12 +675,10 @@ static int launch_track_block_t(gyp_ctx* ctx, const TrackBlockParams& p_in, int 
         if (ctx->k == 16) return launch_k(ctx, track_block_kernel<16, PROF, 2>, 8, grid, p, lds_bytes_spec<16>());
         return launch_k(ctx, track_block_kernel<8, PROF, 2>, 8, grid, p, lds_bytes_spec<8>());
     }
-    switch (ctx->k) {
-#define X(K) case K: return launch_k(ctx, track_block_kernel<K, PROF, 0>, K, grid, p, lds_bytes<K>());
-        GYP_FOR_EACH_RATE(X)
-#undef X
-    }
-    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    return for_rate(ctx, [&](auto rate) {
+        constexpr int K = decltype(rate)::value;
+        return launch_k(ctx, track_block_kernel<K, PROF, 0>, K, grid, p, lds_bytes<K>());
+    });
 }
 // mode 0: throughput kernel; 2: latency form + speculation (at most one workgroup per CU)
 static int launch_track_block(gyp_ctx* ctx, const TrackBlockParams& p, int mode) {
@@ -706,14 +719,11 @@ static int launch_dll_exact(gyp_ctx* ctx, const DllExactParams& p, hipStream_t s
     // sized by the longest sub-block like launch_track_verify's, not by the whole block)
     const int n_units = p.n_chan * (p.trk_round ? p.sub.longest : p.ms_end - p.ms_begin);
     if (n_units <= 0) return GYP_OK;
-    switch (ctx->k) {
-#define X(K) case K: launch_dll_exact_k<K>(ctx, p, n_units, stream); break;
-        GYP_FOR_EACH_RATE(X)
-#undef X
-        default: return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
+    return for_rate(ctx, [&](auto rate) -> int {
+        launch_dll_exact_k<decltype(rate)::value>(ctx, p, n_units, stream);
+        HIP_TRY(ctx, hipGetLastError());
+        return GYP_OK;
+    });
 }
 // The same sums for the plain throughput call at 8 samples per chip: the channels are grouped by stream on the device, then one
 // workgroup per CU stages each (group, millisecond) once for all the group's channels (dll_exact_shared_kernel).
@@ -725,21 +735,14 @@ static int launch_dll_exact_shared(gyp_ctx* ctx, const DllExactParams& p, ExactG
     hipLaunchKernelGGL(exact_group_kernel, dim3((p.n_chan + 255) / 256), dim3(256), 0, stream, p.states, p.n_chan, groups, n_groups);
     DllExactSharedParams s;
     s.x = p; s.groups = groups; s.n_groups = n_groups;
-    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dll_exact_shared_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)exact_shared_lds_bytes<8>()));
-    hipLaunchKernelGGL(dll_exact_shared_kernel<8>, dim3(ctx->n_cus), dim3(kExactSharedThreads), exact_shared_lds_bytes<8>(), stream, s);
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
+    return launch_dyn(ctx, dll_exact_shared_kernel<8>, dim3(ctx->n_cus), dim3(kExactSharedThreads), exact_shared_lds_bytes<8>(), stream, s);
 }
 static int launch_dll_scan(gyp_ctx* ctx, const DllScanParams& p, hipStream_t stream) {
-    switch (ctx->k) {
-#define X(K) case K: hipLaunchKernelGGL(dll_scan_kernel<K>, dim3((unsigned)p.n_chan), dim3(kScanThreads), 0, stream, p); break;
-        GYP_FOR_EACH_RATE(X)
-#undef X
-        default: return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
+    return for_rate(ctx, [&](auto rate) -> int {
+        hipLaunchKernelGGL(dll_scan_kernel<decltype(rate)::value>, dim3((unsigned)p.n_chan), dim3(kScanThreads), 0, stream, p);
+        HIP_TRY(ctx, hipGetLastError());
+        return GYP_OK;
+    });
 }
 
 extern "C" {
@@ -820,6 +823,61 @@ int gyp_correlate_cells(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, i
 }
 
 // ---------------------------------------------------------------- flat search grid -----------------------
+}   // extern "C"
+static_assert(sizeof(cf) == kGridCfBytes && sizeof(GridPartial) == kGridPartialBytes && kChips == kGridChips, "grid_plan.hpp sizes the scratch by these");
+// 12 or 8 wavefronts per workgroup ("grid_fused_waves") as a compile-time constant
+template <typename F>
+static int for_waves(int waves, F&& f) { return waves == 8 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 12>{}); }
+
+// The launches of a planned flat grid (grid_plan.hpp): the fold stage, unless it is fused into the cells kernel, then the cells kernel
+template <int K>
+static int launch_grid(gyp_ctx* ctx, const GridParams& p, const GridPlan& pl, bool coh) {
+    hipStream_t stream = ctx->stream;
+    const int n_units = p.n_streams * p.n_bins, n_cells = n_units * p.n_sats, n_blk = coh ? 1 : p.n_ms;
+    const dim3 wgrid(pl.wgrid);
+    const size_t lds_units = 2 * kTablesBytes + (size_t)pl.waves * kXchWaveBytes + (size_t)pl.waves * 32 * sizeof(SatStat);   // paths 1 and 2
+    if constexpr (K <= 8) {
+        if (pl.path == 1)
+            return for_waves(pl.waves, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                return for_flag(coh, [&](auto c) {
+                    return launch_dyn(ctx, grid_cells_wave_fused_kernel<K, decltype(c)::value, W>, wgrid, dim3(64 * W), lds_units, stream, p);
+                });
+            });
+    }
+    if constexpr (K > 8) {   // wide rates: coalesced wipe-off into z, then the K-sample boxcar out of LDS tiles
+        cf* zbuf = (cf*)ctx->scratch[6];
+        const dim3 zgrid((unsigned)((K * kChips + 255) / 256), (unsigned)n_blk, (unsigned)n_units);
+        for_flag(coh, [&](auto c) { hipLaunchKernelGGL((grid_wipe_kernel<K, decltype(c)::value>), zgrid, dim3(256), 0, stream, p, zbuf); });
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(grid_boxcar_kernel<K>, dim3(8, (unsigned)n_blk, (unsigned)n_units), dim3(128), 0, stream, p, (const cf*)zbuf, n_blk);
+    } else {
+        const dim3 fgrid((unsigned)n_units, (unsigned)n_blk, (unsigned)Geom<K>::R);
+        for_flag(coh, [&](auto c) { hipLaunchKernelGGL((grid_fold_kernel<K, decltype(c)::value>), fgrid, dim3(threads_for(K)), 0, stream, p); });
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (pl.path == 2) {   // one wavefront per (unit, gs satellites, run of branches); runs are merged afterwards
+        const int rc = for_waves(pl.waves, [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            return launch_dyn(ctx, grid_cells_wave_shared_kernel<K, 32, W>, wgrid, dim3(64 * W), lds_units, stream, p, pl.gs);
+        });
+        if (rc || pl.parts == 1) return rc;
+        hipLaunchKernelGGL(grid_merge_parts_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, stream, p, n_cells);
+        HIP_TRY(ctx, hipGetLastError());
+        return GYP_OK;
+    }
+    if (pl.path == 4)   // a workgroup per cell
+        return for_flag(coh, [&](auto c) { return launch_k(ctx, grid_cells_kernel<K, decltype(c)::value>, K, pl.wgrid, p, lds_bytes<K>()); });
+    if constexpr (K % 2 == 0) {   // path 3: one wavefront per cell, with the next row prefetched or without barriers
+        if (pl.pipe) return launch_dyn(ctx, grid_cells_wave_pipe_kernel<K>, wgrid, dim3(512), 2 * kTablesBytes + 8 * kXchWaveBytes, stream, p);
+    }
+    if constexpr (K <= 8) {
+        if (!pl.pipe) return launch_dyn(ctx, grid_cells_wave_kernel<K>, wgrid, dim3(512), kTablesBytes + 8 * kXchWaveBytes, stream, p);
+    }
+    return fail(ctx, GYP_E_BAD_ARG, "flat grid: the plan names a kernel this rate does not have");
+}
+extern "C" {
+
 int gyp_correlate_grid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
                            const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host, int32_t n_bins,
                            int32_t integration, gyp_cell* out_dev) {
@@ -834,9 +892,12 @@ int gyp_correlate_grid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams,
     const int n_blk = coh ? 1 : n_ms;
     const int64_t n_units = (int64_t)n_streams * n_bins;
     if (n_units > 2147483647LL / 2 || n_blk > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_grid_dev: grid too large");
+    const GridPlan pl = grid_plan(GridShape{ctx->k, ctx->n_cus, n_units, n_sats, n_blk},
+                                  GridSwitches{ctx->no_pipe, ctx->no_shared_fwd, ctx->no_grid_fused, ctx->no_grid_parts, ctx->grid_fused_waves});
     int rc;
-    const size_t folded_bytes = (size_t)n_units * n_blk * ctx->k * 1024 * sizeof(cf);
-    if ((rc = ensure_scratch(ctx, 0, folded_bytes))) return rc;
+    if (pl.folded_bytes && (rc = ensure_scratch(ctx, 0, pl.folded_bytes))) return rc;
+    if (pl.z_bytes && (rc = ensure_scratch(ctx, 6, pl.z_bytes))) return rc;
+    if (pl.partial_bytes && (rc = ensure_scratch(ctx, 10, pl.partial_bytes))) return rc;
     if ((rc = ensure_scratch(ctx, 1, (size_t)n_sats * sizeof(int32_t) + 64))) return rc;
     if ((rc = ensure_scratch(ctx, 4, (size_t)n_bins * sizeof(double) + 64))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], sat_ids_host, (size_t)n_sats * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -853,132 +914,11 @@ int gyp_correlate_grid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams,
     p.replica_table = ctx->d_replicas;
     p.tw_tables = ctx->d_tw;
     p.inv_fs = 1.0 / (double)ctx->fs;
-    p.parts = 1; p.partial = nullptr;
-    const int n_cells = n_streams * n_sats * n_bins;
-    const int grid = std::max(1, std::min(n_cells, ctx->n_cus * blocks_per_cu(ctx->k)) & ~7);
-    switch (ctx->k) {
-#define X(K)                                                                                                                  \
-    case K: {                                                                                                                 \
-        /* r06: enough units to fill the chip's 2048 wavefront slots twice over, at most 32 satellites, at most 8 samples per chip: the     \
-           fold is fused into the cells kernel, one wavefront per (stream, bin) unit loops every satellite (no folded rows in HBM) */      \
-        if (K <= 8 && n_blk == 1 && n_sats >= 4 && n_sats <= 32 && n_units >= (int64_t)ctx->n_cus * 16 && !ctx->no_pipe &&                 \
-            !ctx->no_shared_fwd && !ctx->no_grid_fused) {                                                                             \
-            const int fw = ctx->grid_fused_waves == 8 ? 8 : 12;                                                                     \
-            const size_t lds = 2 * kTablesBytes + (size_t)fw * kXchWaveBytes + (size_t)fw * 32 * sizeof(SatStat);                       \
-            const int wgrid = std::max(1, std::min((int)((n_units + fw - 1) / fw), ctx->n_cus));                                       \
-            auto launch_fused = [&](auto kernel) -> int {                                                                             \
-                HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                hipLaunchKernelGGL(kernel, dim3(wgrid), dim3(64 * fw), lds, ctx->stream, p);                                           \
-                return GYP_OK;                                                                                                        \
-            };                                                                                                                        \
-            int rcf;                                                                                                                  \
-            if (fw == 12) rcf = coh ? launch_fused(grid_cells_wave_fused_kernel<(K <= 8 ? K : 8), true, 12>)                            \
-                                    : launch_fused(grid_cells_wave_fused_kernel<(K <= 8 ? K : 8), false, 12>);                          \
-            else rcf = coh ? launch_fused(grid_cells_wave_fused_kernel<(K <= 8 ? K : 8), true, 8>)                                      \
-                           : launch_fused(grid_cells_wave_fused_kernel<(K <= 8 ? K : 8), false, 8>);                                    \
-            if (rcf) return rcf;                                                                                                      \
-            HIP_TRY(ctx, hipGetLastError());                                                                                          \
-            ctx->last_grid_path = 1;                                                                                                  \
-            return GYP_OK;                                                                                                            \
-        }                                                                                                                             \
-        if (K > 8) { /* wide rates: coalesced wipe-off into z, then the K-sample boxcar out of LDS tiles */                 \
-            const size_t zbytes = (size_t)n_units * n_blk * (K * kChips) * sizeof(cf);                                         \
-            int rcz;                                                                                                           \
-            if ((rcz = ensure_scratch(ctx, 6, zbytes))) return rcz;                                                            \
-            cf* zbuf = (cf*)ctx->scratch[6];                                                                                    \
-            const dim3 wgrid((unsigned)((K * kChips + 255) / 256), (unsigned)n_blk, (unsigned)n_units);                        \
-            if (coh) hipLaunchKernelGGL((grid_wipe_kernel<K, true>), wgrid, dim3(256), 0, ctx->stream, p, zbuf);              \
-            else hipLaunchKernelGGL((grid_wipe_kernel<K, false>), wgrid, dim3(256), 0, ctx->stream, p, zbuf);                 \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-            hipLaunchKernelGGL(grid_boxcar_kernel<K>, dim3(8, (unsigned)n_blk, (unsigned)n_units), dim3(128), 0, ctx->stream,   \
-                               p, (const cf*)zbuf, n_blk);                                                                     \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-        } else {                                                                                                              \
-            const dim3 fgrid((unsigned)n_units, (unsigned)n_blk, (unsigned)Geom<K>::R);                                        \
-            if (coh) hipLaunchKernelGGL((grid_fold_kernel<K, true>), fgrid, dim3(threads_for(K)), 0, ctx->stream, p);         \
-            else hipLaunchKernelGGL((grid_fold_kernel<K, false>), fgrid, dim3(threads_for(K)), 0, ctx->stream, p);            \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-        }                                                                                                                     \
-        /* satellites per wavefront: more of them share a forward transform (1 + gs transforms per gs cells) but make fewer,   \
-           longer work items -- on a chip the grid does not fill (config 5 on one GPU, anything strong-scaled) the rounds decide */ \
-        /* r06: group size and branch runs are chosen TOGETHER -- cost = (1 + gs) transforms x (K / parts) branches per item x rounds of   \
-           the chip's 2048 wavefront slots -- with up to 32 satellites per wavefront and runs down to one branch (r05: gs <= 8, at most   \
-           16 runs, chosen one after the other: config 5 ran 19 rounds x 4 branches x 9 = 684 transform times, now 19 x 1 x 33 = 627) */  \
-        int gs_best = 1, parts_best = 1; double cost_best = 0;                                                                        \
-        {                                                                                                                             \
-            const double slots = ctx->n_cus * (ctx->grid_fused_waves == 8 ? 8.0 : 12.0);                                              \
-            cost_best = 2.0 * K * std::ceil((double)n_units * n_sats / slots);   /* one wavefront per cell: fwd + inv per branch */     \
-            for (int gs = 2; gs <= 32; gs *= 2) {                                                                                     \
-                if (gs / 2 >= n_sats) break;                                                                                          \
-                const double groups = (double)n_units * ((n_sats + gs - 1) / gs);                                                     \
-                for (int pp = 1; pp <= K; ++pp) {                                                                                     \
-                    if (K % pp || (pp > 1 && ctx->no_grid_parts)) continue;                                                            \
-                    const double t = (1.0 + gs) * (K / pp) * std::ceil(groups * pp / slots) + (pp > 1 ? 0.25 * (1.0 + gs) : 0.0); /* (+: a merge launch) */ \
-                    if (t < cost_best * (pp > 1 ? 0.97 : 1.0)) { cost_best = t; gs_best = gs; parts_best = pp; }                        \
-                }                                                                                                                     \
-            }                                                                                                                         \
-        }                                                                                                                             \
-        if (n_blk == 1 && gs_best > 1 && !ctx->no_pipe && !ctx->no_shared_fwd) { /* one wavefront per (unit, gs satellites) */ \
-            const int sw = ctx->grid_fused_waves == 8 ? 8 : 12;   /* wavefronts per workgroup ("grid_fused_waves") */               \
-            const size_t lds = 2 * kTablesBytes + (size_t)sw * kXchWaveBytes + (size_t)sw * 32 * sizeof(SatStat);                     \
-            int n_groups = n_units * ((n_sats + gs_best - 1) / gs_best);                                                       \
-            /* a chip the items do not fill runs a last round that is partly empty (config 5 on one GPU): a unit's K branches are cut     \
-               into `parts` runs -- the forward transforms stay shared -- so that the rounds are shorter and the last one costs less;     \
-               partial statistics are merged by grid_merge_parts_kernel */                                                             \
-            const int parts = parts_best;                                                                                             \
-            p.parts = parts;                                                                                                  \
-            if (parts > 1) {                                                                                                  \
-                int rcp;                                                                                                      \
-                if ((rcp = ensure_scratch(ctx, 10, (size_t)n_cells * parts * sizeof(GridPartial)))) return rcp;                  \
-                p.partial = (GridPartial*)ctx->scratch[10];                                                                     \
-                n_groups *= parts;                                                                                            \
-            }                                                                                                                 \
-            const int wgrid = std::max(1, std::min((n_groups + sw - 1) / sw, ctx->n_cus));                                     \
-            if (sw == 12) {                                                                                                   \
-                HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(grid_cells_wave_shared_kernel<K, 32, 12>),      \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
-                hipLaunchKernelGGL((grid_cells_wave_shared_kernel<K, 32, 12>), dim3(wgrid), dim3(768), lds, ctx->stream, p, gs_best); \
-            } else {                                                                                                          \
-                HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(grid_cells_wave_shared_kernel<K, 32, 8>),       \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
-                hipLaunchKernelGGL((grid_cells_wave_shared_kernel<K, 32, 8>), dim3(wgrid), dim3(512), lds, ctx->stream, p, gs_best); \
-            }                                                                                                                 \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-            if (parts > 1) {                                                                                                  \
-                hipLaunchKernelGGL(grid_merge_parts_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, ctx->stream, p, n_cells); \
-                HIP_TRY(ctx, hipGetLastError());                                                                              \
-            }                                                                                                                 \
-            ctx->last_grid_path = 2;                                                                                          \
-            return GYP_OK;                                                                                                    \
-        }                                                                                                                     \
-        if (n_blk == 1 && K % 2 == 0 && !ctx->no_pipe) { /* one wavefront per cell, 256 VGPRs, next row prefetched */              \
-            const size_t lds = 2 * kTablesBytes + 8 * kXchWaveBytes;                                                           \
-            const int wgrid = std::max(1, std::min((n_cells + 7) / 8, ctx->n_cus));                                            \
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(grid_cells_wave_pipe_kernel<(K % 2 == 0 ? K : 16)>),     \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-            hipLaunchKernelGGL(grid_cells_wave_pipe_kernel<(K % 2 == 0 ? K : 16)>, dim3(wgrid), dim3(512), lds, ctx->stream, p);     \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-            ctx->last_grid_path = 3;                                                                                          \
-            return GYP_OK;                                                                                                    \
-        }                                                                                                                     \
-        if (n_blk == 1 && K <= 8) { /* one wavefront per cell, no barriers */                                                \
-            const size_t lds = kTablesBytes + 8 * kXchWaveBytes;                                                               \
-            const int wgrid = std::max(1, std::min((n_cells + 7) / 8, ctx->n_cus * 2));                                        \
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(grid_cells_wave_kernel<K>),                         \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-            hipLaunchKernelGGL(grid_cells_wave_kernel<K>, dim3(wgrid), dim3(512), lds, ctx->stream, p);                        \
-            HIP_TRY(ctx, hipGetLastError());                                                                                  \
-            ctx->last_grid_path = 3;                                                                                          \
-            return GYP_OK;                                                                                                    \
-        }                                                                                                                     \
-        ctx->last_grid_path = 4;                                                                                              \
-        return coh ? launch_k(ctx, grid_cells_kernel<K, true>, K, grid, p, lds_bytes<K>())                                    \
-                   : launch_k(ctx, grid_cells_kernel<K, false>, K, grid, p, lds_bytes<K>());                                  \
-    }
-        GYP_FOR_EACH_RATE(X)
-#undef X
-    }
-    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    p.parts = pl.parts;
+    p.partial = pl.partial_bytes ? (GridPartial*)ctx->scratch[10] : nullptr;
+    if ((rc = for_rate(ctx, [&](auto rate) { return launch_grid<decltype(rate)::value>(ctx, p, pl, coh); }))) return rc;
+    ctx->last_grid_plan = pl;
+    return GYP_OK;
 }
 
 int gyp_correlate_grid(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
@@ -2129,7 +2069,7 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
     GYP_KNOB_BOOL("no_grid_fused", no_grid_fused)
     GYP_KNOB_NUM("grid_fused_waves", grid_fused_waves, int)
     if (is("last_grid_refined_rows")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_refined_rows; return GYP_OK; }
-    if (is("last_grid_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_path; return GYP_OK; }
+    if (is("last_grid_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_plan.path; return GYP_OK; }
     for (int w = 0; w < 3; ++w) {
         // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)
         static const char* const kWitness[3] = {"last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"};
@@ -2185,6 +2125,8 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
                                                 std::to_string(k.lo) + ", " + std::to_string(k.hi) + "]");
         if (std::strcmp(name, "track_chunk_ms") == 0 && value != 0.0 && value < 20.0)
             return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: track_chunk_ms must be 0 (whole blocks) or at least 20");
+        if (std::strcmp(name, "grid_fused_waves") == 0 && value != 8.0 && value != 12.0)
+            return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: grid_fused_waves must be 8 or 12");
         return debug_apply(ctx, name, value, true, nullptr);
     }
     return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);

@@ -677,6 +677,25 @@ static void small_parsers() {
     }
 }
 
+// --------------------------------------------------------------------------------------------------------- grid-plan
+// shapes.i64 rows: k, n_cus, n_units, n_sats, n_blk, switches (bit 0 no_pipe, 1 no_shared_fwd, 2 no_grid_fused, 3 no_grid_parts), fused_waves.
+// plans.i64 rows: GridPlan's members in their order.
+static void grid_plans() {
+    const std::vector<int64_t> shapes = read_array<int64_t>("shapes.i64");
+    REQUIRE(shapes.size() % 7 == 0);
+    std::vector<int64_t> plans;
+    plans.reserve(shapes.size() / 7 * 10);
+    for (size_t r = 0; r * 7 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 7];
+        const GridPlan pl = grid_plan(GridShape{(int)s[0], (int)s[1], s[2], (int)s[3], (int)s[4]},
+                                      GridSwitches{(s[5] & 1) != 0, (s[5] & 2) != 0, (s[5] & 4) != 0, (s[5] & 8) != 0, (int)s[6]});
+        for (int64_t v : {(int64_t)pl.path, (int64_t)pl.pipe, (int64_t)pl.waves, (int64_t)pl.gs, (int64_t)pl.parts, (int64_t)pl.wide_fold, (int64_t)pl.wgrid,
+                          (int64_t)pl.folded_bytes, (int64_t)pl.z_bytes, (int64_t)pl.partial_bytes})
+            plans.push_back(v);
+    }
+    Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+}
+
 }  // namespace drv
 
 int main(int argc, char** argv) {
@@ -697,6 +716,7 @@ int main(int argc, char** argv) {
     const std::pair<const char*, void (*)()> table[] = {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
+        {"grid-plan", drv::grid_plans},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

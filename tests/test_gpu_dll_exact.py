@@ -374,7 +374,7 @@ def test_debug_switches_are_range_checked(engine_factory):
     from gypsum_amd._lib import GypsumHipError
     eng = engine_factory(8_184_000, 8184)
     for name, bad_value in (("symbol_tau", -1.0), ("symbol_tau", float("nan")), ("track_chunk_ms", 1), ("acq_lanes", 0), ("acq_lanes", 2.5),
-                            ("no_spec", 2), ("no_such_switch", 1), ("exact_prefetch", 0)):
+                            ("no_spec", 2), ("no_such_switch", 1), ("exact_prefetch", 0), ("grid_fused_waves", 10)):
         with pytest.raises(GypsumHipError):
             eng.debug_set(name, bad_value)
     before = eng.debug_get("track_chunk_ms")

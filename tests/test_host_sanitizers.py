@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -560,3 +560,60 @@ def test_small_parsers(programs, tmp_path):
     assert (out / "packings.txt").read_text().splitlines() == [
         "ok 1 0 0 2", "ok 2 1 1 2", "ok 4 1 0 4", bad_bits, bad_bits, bad_bits, "packing.real must be 0 or 1",
         "packing.order must be GYP_PACK_MSB_FIRST or GYP_PACK_LSB_FIRST", "packing.reserved must be 0", levels, levels, "ok 1 1 1 1", "packing is NULL"]
+
+
+# ------------------------------------------------------------------------------------------------------------ grid-plan
+RATES = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 48)             # GYP_FOR_EACH_RATE
+NO_PIPE, NO_SHARED_FWD, NO_GRID_FUSED, NO_GRID_PARTS = 1, 2, 4, 8   # the switches column of shapes.i64
+# (k, n_units, n_sats, n_blk, switches, fused_waves, n_cus) -> (path, pipe, waves, gs, parts); None = not asserted.  gs is asserted on path 2 only.
+PLAN_LITERALS = [
+    ((2, 8192, 32, 1, 0, 12, 256), (1, None, 12, None, 1)),                      # cfg2
+    ((2, 8192, 32, 1, NO_GRID_FUSED, 12, 256), (2, None, 12, 16, 2)),
+    ((2, 4096, 32, 1, 0, 12, 256), (1, None, 12, None, 1)),                      # cfg4 on one GPU
+    ((8, 4095, 32, 1, 0, 12, 256), (2, None, 12, 16, 4)),
+    ((8, 4096, 32, 1, 0, 12, 256), (1, None, None, None, None)),
+    ((8, 4320, 3, 1, 0, 12, 256), (2, None, 12, 4, 2)),
+    ((48, 800, 32, 1, 0, 12, 256), (2, None, 12, 16, 48)),                       # cfg5
+    ((48, 800, 32, 1, 0, 8, 256), (2, None, 8, 16, 24)),
+    ((48, 800, 32, 1, NO_GRID_PARTS, 12, 256), (2, None, 12, 2, 1)),
+    ((48, 800, 32, 1, 0, 12, 304), (2, None, 12, 16, 24)),
+    ((1, 6, 11, 1, 0, 12, 256), (3, 0, None, None, None)),
+    *[((k, 6, 11, 1, 0, 12, 256), (2, None, 12, 2, k)) for k in (5, 8, 16, 48)],
+    ((48, 6, 11, 1, NO_GRID_PARTS, 12, 256), (3, 1, None, None, None)),
+    ((2, 6, 1, 1, 0, 12, 256), (3, 1, None, None, None)),
+    ((5, 6, 1, 1, 0, 12, 256), (3, 0, None, None, None)),
+    ((2, 6, 4, 10, 0, 12, 256), (4, None, None, None, None)),
+    ((8, 6, 11, 1, NO_PIPE, 12, 256), (3, 0, None, None, None)),
+    ((16, 6, 11, 1, NO_PIPE, 12, 256), (4, None, None, None, None)),
+    ((8, 8192, 32, 1, NO_SHARED_FWD, 12, 256), (3, 1, None, None, None)),
+    ((3, 8192, 32, 1, NO_SHARED_FWD, 12, 256), (3, 0, None, None, None)),
+    ((2, 8192, 33, 1, 0, 12, 256), (2, None, 12, 4, 1)),
+]
+
+
+def test_grid_plan(programs, tmp_path):
+    """grid_plan (csrc/grid_plan.hpp) against tests/grid_plan_model.py on every combination of the axes below, and on the shapes whose
+    plans are written out above."""
+    import grid_plan_model
+
+    d = indir(tmp_path)
+    axes = [RATES, (64, 256, 304), (1, 2, 3, 6, 20, 255, 800, 3200, 4095, 4096, 4320, 8192, 100000), range(1, 34), (1, 2, 10), range(16), (8, 12)]
+    sweep = np.stack([g.ravel() for g in np.meshgrid(*[np.array(a, dtype="<i8") for a in axes], indexing="ij")], axis=1)
+    literal = i64([(k, cus, units, sats, blk, sw, fw) for (k, units, sats, blk, sw, fw, cus), _ in PLAN_LITERALS])
+    shapes = np.concatenate([sweep, literal])
+    assert len(sweep) == 12 * 3 * 13 * 33 * 3 * 16 * 2
+    shapes.tofile(d / "shapes.i64")
+    out = run(programs, ASAN, "grid-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(shapes), len(grid_plan_model.FIELDS))
+    k, cus, units, sats, blk, sw, fw = shapes.T
+    want = grid_plan_model.grid_plan(k, cus, units, sats, blk, sw & NO_PIPE, sw & NO_SHARED_FWD, sw & NO_GRID_FUSED, sw & NO_GRID_PARTS, fw)
+    for col, field in enumerate(grid_plan_model.FIELDS):
+        bad = np.flatnonzero(got[:, col] != want[field])
+        assert len(bad) == 0, (field, len(bad), shapes[bad[0]].tolist(), int(got[bad[0], col]), int(want[field][bad[0]]))
+    plans = {f: got[:, c] for c, f in enumerate(grid_plan_model.FIELDS)}
+    assert np.array_equal(plans["folded_bytes"] == 0, plans["path"] == 1)
+    assert set(np.unique(plans["path"])) == {1, 2, 3, 4}
+    for row, (shape, expected) in zip(got[len(sweep):], PLAN_LITERALS):
+        for field, value in zip(("path", "pipe", "waves", "gs", "parts"), expected):
+            if value is not None:
+                assert row[grid_plan_model.FIELDS.index(field)] == value, (shape, field, row.tolist())
