@@ -51,6 +51,8 @@ BITS_STATE = np.dtype([("determined_bit_phase", "<i4"), ("previous_bit_phase_dec
                        ("last_emitted_bits_len", "<i4"), ("last_emitted_bits", "i1", (52,))], align=True)
 PACKING = np.dtype([("bits", "<i4"), ("real", "<i4"), ("order", "<i4"), ("reserved", "<i4"), ("levels", "<f4", (16,))], align=True)
 GYP_PACK_MSB_FIRST, GYP_PACK_LSB_FIRST = 0, 1
+IQ_STATS = np.dtype([("sum_re", "<f8"), ("sum_im", "<f8"), ("sum_sq", "<f8"), ("max_abs", "<f4"), ("n_clip", "<i4")], align=True)
+IQ_LEVEL = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("gain", "<f4"), ("reserved", "<i4")], align=True)
 GYP_BIT_ZERO, GYP_BIT_ONE, GYP_BIT_UNKNOWN = 0, 1, 2
 GYP_COMM_ID_BYTES = 128
 # sizeof() of every record the header declares, derived from the mirrors above (tests/test_abi_and_host.py compiles the
@@ -58,9 +60,10 @@ GYP_COMM_ID_BYTES = 128
 RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STATE.itemsize, "gyp_synth_sat": SYNTH_SAT.itemsize,
                 "gyp_cell_desc": CELL_DESC.itemsize, "gyp_cell": CELL.itemsize, "gyp_acq_result": ACQ_RESULT.itemsize,
                 "gyp_chan_in": CHAN_IN.itemsize, "gyp_chan_out": CHAN_OUT.itemsize, "gyp_best_bin": BEST_BIN.itemsize,
-                "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize}
+                "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize,
+                "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
-GYP_VERSION = 208
+GYP_VERSION = 209
 
 EXPORTS = (
     "gyp_version gyp_create gyp_destroy gyp_last_error gyp_device_name gyp_set_stream gyp_sync gyp_wait_for gyp_timer_start "
@@ -73,7 +76,8 @@ EXPORTS = (
     "gyp_bits_create gyp_bits_destroy gyp_bits_reset gyp_bits_push gyp_bits_push_block gyp_bits_drain gyp_bits_get_state "
     "gyp_ingest_open gyp_ingest_close gyp_ingest_total_ms gyp_ingest_set_scale gyp_ingest_seek gyp_ingest_next_host gyp_ingest_next_dev gyp_ingest_times "
     "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc "
-    "gyp_packed_span gyp_unpack_iq_dev gyp_resample_packed_dev gyp_ingest_open_packed"
+    "gyp_packed_span gyp_unpack_iq_dev gyp_resample_packed_dev gyp_ingest_open_packed "
+    "gyp_iq_stats_dev gyp_condition_iq_dev gyp_iq_level_from_stats gyp_ingest_set_level gyp_ingest_get_level gyp_ingest_calibrate"
 ).split()
 
 
@@ -195,6 +199,12 @@ def load() -> C.CDLL:
         "gyp_unpack_iq_dev": (C.c_int, [vp, vp, vp, i32, i64, i32, i64, C.c_float, i64, vp]),
         "gyp_resample_packed_dev": (C.c_int, [vp, vp, vp, i32, i64, i32, i64, i64, C.c_float, i64, i64, i32, i64, i32, i64, vp]),
         "gyp_ingest_open_packed": (C.c_int, [vp, C.c_char_p, vp, i64, i64, i32, i32, i32, C.POINTER(vp)]),
+        "gyp_iq_stats_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, C.c_float, vp]),
+        "gyp_condition_iq_dev": (C.c_int, [vp, vp, vp, i32, i64, i64, vp]),
+        "gyp_iq_level_from_stats": (C.c_int, [vp, i32, i32, i32, dbl, vp, vp]),
+        "gyp_ingest_set_level": (C.c_int, [vp, vp]),
+        "gyp_ingest_get_level": (C.c_int, [vp, vp, C.POINTER(i32)]),
+        "gyp_ingest_calibrate": (C.c_int, [vp, i64, i32, i32, dbl, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

@@ -195,11 +195,15 @@ class AntennaSampleProviderResampled(_CursorProvider):
 
     A recording of 1-, 2- or 4-bit packed words (`InputFileInfo.packed(...)`, or `packing=`, gypsum_amd.packing) is unpacked on
     the device (`gyp_ingest_open_packed`).  With a packing, and only then, `resample_to` may equal the input rate (an I,Q
-    recording at a supported rate, the default `resample_to` then): its words are only unpacked."""
+    recording at a supported rate, the default `resample_to` then): its words are only unpacked.
+
+    `level` (a gypsum_amd.level.IqLevel) or `calibrate` (a dict of `IqFileIngest.calibrate`'s arguments, `{}` for its defaults;
+    applied once after opening) removes a DC offset and normalises the amplitude of every sample served: what an offset-binary
+    uint8 recording needs before it can be acquired.  The two exclude each other."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
                  sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
-                 engine=None, device: int = 0, if_hz: int | None = None, packing=None) -> None:
+                 engine=None, device: int = 0, if_hz: int | None = None, packing=None, level=None, calibrate: dict | None = None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
         from .resample import default_ddc_rate, nearest_supported_rate
@@ -215,6 +219,8 @@ class AntennaSampleProviderResampled(_CursorProvider):
                 packing = getattr(info, "packing", None)
         if sample_rate is None:
             raise TypeError("sample_rate is required when no InputFileInfo is given")
+        if level is not None and calibrate is not None:
+            raise ValueError("level and calibrate exclude each other: a level is either given or measured")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
         self.if_hz = None if if_hz is None else int(if_hz)
@@ -246,6 +252,11 @@ class AntennaSampleProviderResampled(_CursorProvider):
                                         resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
             if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
                 self._ingest.set_scale(scale)
+        self.level = level
+        if level is not None:
+            self._ingest.set_level(level)
+        elif calibrate is not None:
+            self.level, self.measured = self._ingest.calibrate(**calibrate)
         self.total_ms = self._ingest.total_ms
         self._block_first_ms = 0
         self._block: np.ndarray | None = None    # [n_ms, N] complex64, downloaded

@@ -2702,6 +2702,78 @@ int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------------------
+// Level (kernels_level.hpp): per-millisecond statistics, y = (x - dc) * gain
+// ---------------------------------------------------------------------------------------------------------
+// Enqueue iq_stats_kernel on `stream`: one workgroup per (stream, millisecond) item over the widen kernel's persistent grid.
+static int stats_launch(gyp_ctx* ctx, hipStream_t stream, const float* iq, int32_t n_streams, int64_t stride, int32_t n_ms, int32_t n,
+                        float clip_level, gyp_iq_stats* out) {
+    const int64_t n_items = (int64_t)n_streams * n_ms;
+    const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
+    hipLaunchKernelGGL(iq_stats_kernel, dim3(grid), dim3(256), 0, stream, iq, stride, n_ms, n, n_items, clip_level, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+// Enqueue iq_condition_kernel on `stream`, kLevelStreams streams per launch (their levels are a kernel argument); the launches of
+// a call share the persistent grid's workgroups among their streams.
+static int condition_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride,
+                            int64_t n_samples, const gyp_iq_level* levels) {
+    const bool rows16 = n_streams == 1 || stride % 2 == 0;   // every row starts 16-byte aligned if the first one does
+    const int32_t vec4 = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0 && rows16;
+    const int64_t n_vec = vec4 ? (n_samples + 1) / 2 : n_samples;
+    for (int32_t s0 = 0; s0 < n_streams; s0 += kLevelStreams) {
+        const int32_t ns = std::min<int32_t>(kLevelStreams, n_streams - s0);
+        LevelArgs a{};
+        for (int32_t i = 0; i < kLevelStreams; ++i) a.v[i] = levels[s0 + std::min(i, ns - 1)];
+        const int64_t cap = std::max<int64_t>(1, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu / ns);
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_vec + 255) / 256, cap));
+        hipLaunchKernelGGL(iq_condition_kernel, dim3(grid, ns), dim3(256), 0, stream, in + 2 * s0 * stride, out + 2 * s0 * stride, stride,
+                           n_samples, a, vec4);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_iq_stats_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                     int32_t samples_per_ms, float clip_level, gyp_iq_stats* out_dev) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_stats_dev: ctx is NULL");
+    if (!iq_dev || !out_dev) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: iq_dev and out_dev must not be NULL");
+    if (n_streams < 1 || n_ms < 1 || samples_per_ms < 1)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: n_streams, n_ms and samples_per_ms must be >= 1");
+    if (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: stream_stride_samples must be >= n_ms * samples_per_ms");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return stats_launch(ctx, ctx->stream, iq_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, clip_level, out_dev);
+}
+
+int gyp_condition_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
+                         int64_t n_samples, const gyp_iq_level* levels_host) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_condition_iq_dev: ctx is NULL");
+    if (!in_dev || !out_dev || !levels_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_condition_iq_dev: in_dev, out_dev and levels_host must not be NULL");
+    if (n_streams < 1 || n_samples < 0 || (n_streams > 1 && stream_stride_samples < n_samples))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_condition_iq_dev: bad arguments (n_streams >= 1, n_samples >= 0, stream_stride_samples >= n_samples)");
+    for (int32_t s = 0; s < n_streams; ++s)
+        if (const char* why = level_check(&levels_host[s])) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_condition_iq_dev: ") + why);
+    if (n_samples == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return condition_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, n_samples, levels_host);
+}
+
+int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms, int32_t remove_dc, double target_rms,
+                            gyp_iq_level* level_out, double* measured_out4) {
+    if (!stats || !level_out) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_level_from_stats: stats and level_out must not be NULL");
+    if (n_ms < 1 || samples_per_ms < 1) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_level_from_stats: n_ms and samples_per_ms must be >= 1");
+    if (!(target_rms > 0.0) || !std::isfinite(target_rms))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_level_from_stats: target_rms must be positive and finite");
+    if (const char* why = level_from_stats(stats, n_ms, samples_per_ms, remove_dc, target_rms, level_out, measured_out4))
+        return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_iq_level_from_stats: ") + why);
+    return GYP_OK;
+}
+
+}  // extern "C"
 
 static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
@@ -2720,6 +2792,12 @@ static void ingest_free(gyp_ingest* g) {
     }
     if (g->fd >= 0) close(g->fd);
     delete g;
+}
+
+// A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
+static int ingest_condition(gyp_ingest* g, int d, int32_t n_ms) {
+    if (!g->level_on) return GYP_OK;
+    return condition_launch(g->ctx, g->copy_stream, g->dev_iq[d], g->dev_iq[d], 1, 0, (int64_t)n_ms * g->n, &g->level);
 }
 
 // Enqueue the upload (+ widening) of the reader's next block on the copy stream.  Returns 1 if a block was
@@ -2755,6 +2833,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
                            : unpack_launch(ctx, g->copy_stream, g->pk, g->dev_raw[d], 1, sp.n_bytes, sp.bit0, (int64_t)u->n_ms * g->n, g->scale,
                                            g->dev_iq[d], (int64_t)u->n_ms * g->n);
         if (rc) return rc;
+        if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
         HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
         g->in_flight.push_back(*u);
         ++g->dev_blocks;
@@ -2767,6 +2846,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
         if (const int rc = resample_launch(ctx, g->copy_stream, g->rs, g->fmt, g->dev_raw[d], 1, span, u->first_ms * g->in_n - g->halo_lo, span,
                                            g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n, g->if_hz))
             return rc;
+        if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
         HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
         g->in_flight.push_back(*u);
         ++g->dev_blocks;
@@ -2786,6 +2866,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
         }
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
     HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
     g->in_flight.push_back(*u);
     ++g->dev_blocks;
@@ -3016,6 +3097,7 @@ int gyp_ingest_seek(gyp_ingest* g, int64_t ms) {
         g->have_ahead = false;
     }
     ingest_start_reader(g, ms);
+    g->consumer_ms = ms;
     return GYP_OK;
 }
 
@@ -3025,6 +3107,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     *n_ms_out = 0;
     if (g->resampled) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
     if (g->packed) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
+    if (g->level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3035,6 +3118,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
         return GYP_OK;
     }
     *raw_out = g->host[slot];
+    g->consumer_ms = *first_ms_out + *n_ms_out;
     return GYP_OK;
 }
 
@@ -3068,6 +3152,7 @@ int gyp_ingest_next_dev(gyp_ingest* g, const float** iq_dev_out, int64_t* first_
     *iq_dev_out = g->dev_iq[d];
     *first_ms_out = cur.first_ms;
     *n_ms_out = cur.n_ms;
+    g->consumer_ms = cur.first_ms + cur.n_ms;
     return GYP_OK;
 }
 
@@ -3082,6 +3167,72 @@ int gyp_widen_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, uint64_t n_
         default: return fail(ctx, GYP_E_BAD_ARG, "gyp_widen_iq_dev: fmt must be GYP_FMT_I8, GYP_FMT_U8 or GYP_FMT_I16");
     }
     HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+int gyp_ingest_set_level(gyp_ingest* g, const gyp_iq_level* level) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_level: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_level: the handle was opened without a context (a level applies to device blocks)");
+    if (level)
+        if (const char* why = level_check(level)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_level: ") + why);
+    g->level_on = level != nullptr;
+    g->level = level ? *level : gyp_iq_level{0.0f, 0.0f, 1.0f, 0};
+    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old level: drop it and read it again
+}
+
+int gyp_ingest_get_level(const gyp_ingest* g, gyp_iq_level* out, int32_t* enabled_out) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: the handle was opened without a context (a level applies to device blocks)");
+    if (out) *out = g->level;
+    if (enabled_out) *enabled_out = g->level_on ? 1 : 0;
+    return GYP_OK;
+}
+
+int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
+                         gyp_iq_level* level_out, double* measured_out4) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_calibrate: handle is NULL");
+    gyp_ctx* ctx = g->ctx;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_calibrate: the handle was opened without a context (the statistics are taken on the device)");
+    if (n_ms < 1 || n_ms > 10000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_calibrate: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 10000");
+    if (!(target_rms > 0.0) || !std::isfinite(target_rms))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_calibrate: target_rms must be positive and finite");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gyp_iq_stats* d_stats = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d_stats, (size_t)n_ms * sizeof(gyp_iq_stats)));
+    const bool was_on = g->level_on;
+    const int64_t back_to = g->consumer_ms;
+    g->level_on = false;   // the blocks below are the handle's unconditioned output
+    std::vector<gyp_iq_stats> stats((size_t)n_ms);
+    gyp_iq_level level{};
+    auto measure = [&]() -> int {
+        if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
+        for (int32_t done = 0; done < n_ms;) {
+            const float* iq = nullptr;
+            int64_t first = 0;
+            int32_t count = 0;
+            if (const int rc = gyp_ingest_next_dev(g, &iq, &first, &count)) return rc;
+            if (count == 0 || first != first_ms + done) return fail(ctx, GYP_E_IO, "gyp_ingest_calibrate: the recording ended inside the range");
+            const int32_t take = std::min(count, n_ms - done);
+            if (const int rc = stats_launch(ctx, ctx->stream, iq, 1, 0, take, g->n, clip_level, d_stats + done)) return rc;
+            done += take;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (const char* why = level_from_stats(stats.data(), n_ms, g->n, remove_dc, target_rms, &level, measured_out4))
+            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_calibrate: ") + why);
+        return GYP_OK;
+    };
+    const int rc = measure();
+    const std::string why = ctx->err;
+    (void)hipStreamSynchronize(ctx->stream);   // nothing may still read d_stats or a block of the measurement
+    (void)hipFree(d_stats);
+    g->level_on = rc == GYP_OK ? true : was_on;
+    if (rc == GYP_OK) g->level = level;
+    const int rc_back = gyp_ingest_seek(g, back_to);
+    if (rc) return fail(ctx, rc, why);
+    if (rc_back) return rc_back;
+    if (level_out) *level_out = level;
     return GYP_OK;
 }
 

@@ -263,6 +263,12 @@ struct gyp_ingest {
     bool packed = false;
     PackedFormat pk{};
 
+    // level (gyp_ingest_set_level / gyp_ingest_calibrate): a constant of the handle; while it is on, every device block is conditioned
+    // in place on the copy stream behind whatever produced it
+    bool level_on = false;
+    gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
+    int64_t consumer_ms = 0;        // where the next block handed out starts (set_level and calibrate seek back to it)
+
     // host ring, filled by the reader thread
     std::vector<uint8_t*> host;
     std::vector<int64_t> host_first;

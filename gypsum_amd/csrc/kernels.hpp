@@ -21,6 +21,8 @@
 //                       arg-max from the full profile in parallel.
 //   resample_kernel     rational-rate resampler (fs_in -> the stream format): file-width words widened and filtered by a
 //                       polyphase FIR, one phase per lane, its taps in registers, the tile's input span in LDS.
+//   iq_stats_kernel / iq_condition_kernel   signal conditioning: per-millisecond DC / power / peak / clipping records in a fixed
+//                       float64 reduction order, and y = (x - dc) * gain in place behind whatever produced an ingest block.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -36,3 +38,4 @@
 #include "kernels_acq.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_resample.hpp"
+#include "kernels_level.hpp"

@@ -279,6 +279,51 @@ class GypsumEngine:
             d_out.free()
         return out if w.ndim > 1 else out[0]
 
+    def iq_stats_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, n_ms: int, samples_per_ms: int, clip_level: float,
+                     out_ptr: int) -> None:
+        """gyp_iq_stats_dev: one gyp_iq_stats record per (stream, millisecond) of complex64 samples in HBM (any samples_per_ms, no
+        stream format needed), stream-major into out_ptr.  Enqueued, not synchronised."""
+        self._check(self.lib.gyp_iq_stats_dev(self.ctx, C.c_void_p(iq_ptr), int(n_streams), int(stream_stride), int(n_ms),
+                                              int(samples_per_ms), float(clip_level), C.c_void_p(out_ptr)))
+
+    def condition_iq_dev(self, in_ptr: int, out_ptr: int, n_streams: int, stream_stride: int, n_samples: int, levels) -> None:
+        """gyp_condition_iq_dev: out = (in - dc) * gain in float32, stream s with levels[s] (gypsum_amd.level.IqLevel); out_ptr may
+        equal in_ptr.  Enqueued, not synchronised."""
+        from .level import level_records
+        recs = level_records(levels)
+        if len(recs) != int(n_streams):
+            raise ValueError(f"{len(recs)} levels for {n_streams} streams")
+        self._check(self.lib.gyp_condition_iq_dev(self.ctx, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n_streams), int(stream_stride),
+                                                  int(n_samples), ptr(recs)))
+
+    def iq_stats(self, iq: np.ndarray, samples_per_ms: int, clip_level: float = 0.0) -> np.ndarray:
+        """Host convenience: the per-millisecond records (gypsum_amd.level.STATS_DTYPE) of complex64 `iq` (2-D = one stream per
+        row), shape ([n_streams,] n_ms) over the whole milliseconds of samples_per_ms samples it holds."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        n_streams, n_ms = rows.shape[0], rows.shape[1] // int(samples_per_ms)
+        out = np.zeros((n_streams, n_ms), dtype=_lib.IQ_STATS)
+        if n_ms:
+            d_iq = self.alloc(rows.nbytes).upload(rows)
+            d_out = self.alloc(out.nbytes)
+            self.iq_stats_dev(d_iq.ptr.value, n_streams, rows.shape[1], n_ms, samples_per_ms, clip_level, d_out.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d_out.ptr, out.nbytes))
+            d_iq.free()
+            d_out.free()
+        return out if x.ndim > 1 else out[0]
+
+    def condition_iq(self, iq: np.ndarray, levels) -> np.ndarray:
+        """Host convenience: (iq - dc) * gain in float32 on the device, complex64 `iq` (2-D = one stream per row, one level each)."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        out = np.empty_like(rows)
+        if rows.size:
+            d = self.alloc(rows.nbytes).upload(rows)
+            self.condition_iq_dev(d.ptr.value, d.ptr.value, rows.shape[0], rows.shape[1], rows.shape[1], levels)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d.ptr, out.nbytes))
+            d.free()
+        return out if x.ndim > 1 else out[0]
+
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(_lib.GYP_COMM_ID_BYTES)
         rc = self.lib.gyp_comm_unique_id(buf)

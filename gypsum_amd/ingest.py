@@ -15,6 +15,9 @@ With `packing` (gypsum_amd.packing) the recording holds 1-, 2- or 4-bit words pa
 the device (`gyp_ingest_open_packed`): I,Q at the engine's rate (`resample_from_hz` None or equal to it) are only unpacked, I,Q at
 another rate are resampled, and a real packing (with `if_hz`) is down-converted.  The word type is then the packing's, so
 `sample_component_data_type` must be left out.
+
+`set_level` / `calibrate` (gypsum_amd.level) remove a DC offset and normalise the amplitude of every device block, whatever
+produced it: an RTL-SDR uint8 recording needs no rewrite on the host.
 """
 from __future__ import annotations
 
@@ -119,6 +122,33 @@ class IqFileIngest:
     def set_scale(self, scale: float) -> None:
         """Integer recordings: device samples = word * scale (default 1 = the reference's raw values)."""
         self._check(self._lib.gyp_ingest_set_scale(self._h, float(scale)))
+
+    def set_level(self, level) -> None:
+        """A gypsum_amd.level.IqLevel every device block is conditioned with from the next block handed out on: (x - dc) * gain behind
+        whatever produced the block, x = word * scale as without a level (gyp_ingest_set_level).  None switches it off."""
+        rec = None if level is None else level.record()
+        self._check(self._lib.gyp_ingest_set_level(self._h, _lib.ptr(rec)))
+
+    @property
+    def level(self):
+        """The installed IqLevel, or None while none is on."""
+        from .level import LEVEL_DTYPE, IqLevel
+        rec, on = np.zeros(1, dtype=LEVEL_DTYPE), C.c_int32()
+        self._check(self._lib.gyp_ingest_get_level(self._h, _lib.ptr(rec), C.byref(on)))
+        return IqLevel.from_record(rec) if on.value else None
+
+    def calibrate(self, first_ms: int = 0, n_ms: int = 100, target_rms: Optional[float] = None, remove_dc: bool = True,
+                  clip_level: float = 0.0):
+        """Measure output milliseconds [first_ms, first_ms + n_ms) of the handle's unconditioned output (word * scale, no level) on
+        the device and install the level that removes their mean (remove_dc) and brings the RMS of |x| to target_rms (default:
+        gypsum_amd.level.default_target_rms(N)).  Returns (IqLevel, measured) as gypsum_amd.level.level_from_stats does; the
+        cursor stays where it was, blocks handed out earlier are no longer valid (gyp_ingest_calibrate)."""
+        from .level import LEVEL_DTYPE, IqLevel, default_target_rms, measured_dict
+        rec, measured = np.zeros(1, dtype=LEVEL_DTYPE), np.zeros(4)
+        target = default_target_rms(self.n) if target_rms is None else float(target_rms)
+        self._check(self._lib.gyp_ingest_calibrate(self._h, int(first_ms), int(n_ms), int(bool(remove_dc)), target, float(clip_level),
+                                                   _lib.ptr(rec), _lib.ptr(measured)))
+        return IqLevel.from_record(rec), measured_dict(measured)
 
     def seek(self, ms: int) -> None:
         self._check(self._lib.gyp_ingest_seek(self._h, int(ms)))

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 208: gyp_debug_set / gyp_debug_get name exact_prefetch removed (the software-prefetched form of dll_exact_wave_kernel it selected was
+/* 209: signal conditioning on the device: gyp_iq_stats, gyp_iq_level, gyp_iq_stats_dev, gyp_condition_iq_dev, gyp_iq_level_from_stats,
+ *      gyp_ingest_set_level, gyp_ingest_get_level, gyp_ingest_calibrate.  Opt-in: nothing that existed changes.
+ * 208: gyp_debug_set / gyp_debug_get name exact_prefetch removed (the software-prefetched form of dll_exact_wave_kernel it selected was
  *      measured slower and is gone); the name is refused like any unknown one.  Nothing else changes.
  * 207: gyp_debug_disc_read added (the float64 discriminators of a bank's last throughput block); gyp_debug_set name no_exact_shared and
  *      the read-only "last_exact_path".  Nothing that existed changes.
@@ -46,7 +48,7 @@ extern "C" {
  * 201: gyp_debug_set / gyp_debug_get / gyp_debug_spec_redo_read / gyp_debug_spec_layout added (the library no longer reads GYP_* environment switches).
  * 200: gyp_chan_out carries the float64 early/late pair (80 bytes), gyp_track_rec::path_info, gyp_debug_track_profile writes
  * 16 values, gyp_params grew; a binding written against another value must not load the library (gypsum_amd/_lib.py checks). */
-#define GYP_VERSION 208 /* 0.2.8 */
+#define GYP_VERSION 209 /* 0.2.9 */
 
 enum {
     GYP_OK = 0,
@@ -492,7 +494,7 @@ typedef struct gyp_ingest gyp_ingest;
 #define GYP_FMT_F32 0   /* numpy float32, GNU Radio recordings (radio_input.py:41) */
 #define GYP_FMT_I8 1    /* numpy int8   (HackRF raw) */
 #define GYP_FMT_I16 2   /* numpy int16 */
-#define GYP_FMT_U8 3    /* numpy uint8  (RTL-SDR raw; no offset is removed, as np.fromfile would not) */
+#define GYP_FMT_U8 3    /* numpy uint8  (RTL-SDR raw; no offset is removed, as np.fromfile would not: gyp_ingest_set_level / _calibrate do) */
 
 /* ctx may be NULL: host-only reader (plain host buffers, gyp_ingest_next_host only).  n = samples per millisecond
  * (SampleProviderAttributes.samples_per_prn_transmission); block_ms >= 1; 3 <= depth <= 64. */
@@ -504,7 +506,8 @@ void gyp_ingest_close(gyp_ingest* ing);
 int64_t gyp_ingest_total_ms(const gyp_ingest* ing);
 /* Integer recordings only: device samples become word * scale (one float32 multiply) for blocks uploaded from now
  * on.  The default 1 keeps the reference's raw integer values; the tracking loops' fixed thresholds and gains
- * (tracker.py:157-203,246-262) assume GNU-Radio-like amplitudes, so an 8-bit front end wants about 1/100. */
+ * (tracker.py:157-203,246-262) assume GNU-Radio-like amplitudes, so an 8-bit front end wants about 1/100 -- or a level measured
+ * from the recording itself (gyp_ingest_calibrate, "level" below), which also removes an offset. */
 int gyp_ingest_set_scale(gyp_ingest* ing, float scale);
 /* Restart reading at millisecond `ms` (the provider's cursor / N). */
 int gyp_ingest_seek(gyp_ingest* ing, int64_t ms);
@@ -672,6 +675,81 @@ int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void
 int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* packing, int64_t fs_in_hz, int64_t if_hz, int32_t taps,
                            int32_t block_ms, int32_t depth, gyp_ingest** out);
 
+/* ---------------------------------------------------------------- level: DC offset and amplitude ------- */
+/* Offset-binary recordings (RTL-SDR uint8, zero at 128) carry a DC term far above the noise, and the tracking loops' fixed
+ * thresholds assume GNU-Radio-like amplitudes.  Three steps condition a recording on the device: measure per-millisecond
+ * statistics (gyp_iq_stats_dev), derive a level from them on the host (gyp_iq_level_from_stats), apply it (gyp_condition_iq_dev,
+ * or gyp_ingest_set_level / gyp_ingest_calibrate on an ingest handle).  Everything is opt-in: with none of these called every
+ * other entry point gives the bits it gave before.
+ *
+ * Statistics.  One record per (stream, millisecond), a pure function of that millisecond's samples: reduced in a fixed order with
+ * a fixed lane-to-sample mapping and a fixed tree (in-wave, then across waves through LDS), without floating-point atomics, so
+ * the same bits come out on every run and for every call shape -- other n_streams / n_ms, a sub-window of the same buffer,
+ * another grid size, whatever the rows' alignment.  Products and sums are single float64 roundings; for integer-valued samples
+ * with |v| < 2^15 every partial sum is an exact integer below 2^53 and the sums equal numpy's int64 sums.  Non-finite samples:
+ * the sums follow IEEE; max_abs and n_clip are unspecified. */
+typedef struct gyp_iq_stats {   /* one per (stream, millisecond): 32 bytes */
+    double sum_re, sum_im;      /* sum of Re x, Im x over the millisecond's samples, accumulated in float64 */
+    double sum_sq;              /* sum of (Re x)^2 + (Im x)^2, products and sums in float64 */
+    float  max_abs;             /* max over samples of max(|Re x|, |Im x|) */
+    int32_t n_clip;             /* COMPONENTS with |v| >= clip_level; 0 when clip_level <= 0 */
+} gyp_iq_stats;
+/* iq_dev: n_streams x n_ms x samples_per_ms complex64 samples, stream s at sample s * stream_stride_samples; any 8-byte aligned
+ * address and any stride (rows that start on 16 bytes are read 16 bytes at a time, the others 8).  samples_per_ms is an argument
+ * (>= 1), no stream format is needed: the function also works on data at a recording's own rate.  out_dev: n_streams x n_ms
+ * records, stream-major.  Enqueued on the context's stream.  GYP_E_BAD_ARG for NULL pointers, counts < 1, or a stride below
+ * n_ms * samples_per_ms when n_streams > 1. */
+int gyp_iq_stats_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                     int32_t samples_per_ms, float clip_level, gyp_iq_stats* out_dev);
+
+/* y_re = (x_re - dc_re) * gain, y_im = (x_im - dc_im) * gain: one float32 subtraction, then one float32 multiplication, each
+ * rounded to nearest -- what numpy computes for (x - dc) * g in float32.  The level {0, 0, 1} returns the input bits. */
+typedef struct gyp_iq_level {
+    float dc_re, dc_im;   /* finite */
+    float gain;           /* positive and finite */
+    int32_t reserved;     /* must be 0 */
+} gyp_iq_level;
+/* n_samples samples of each of n_streams streams (stream s at sample s * stream_stride_samples of both buffers), stream s with
+ * levels_host[s].  out_dev may equal in_dev; other overlaps are not allowed.  Alignment as for gyp_iq_stats_dev.  Enqueued on the
+ * context's stream; levels_host may be reused as soon as the call returns.  GYP_E_BAD_ARG for NULL pointers, n_streams < 1,
+ * n_samples < 0, a stride below n_samples when n_streams > 1, or a level that breaks the rules above. */
+int gyp_condition_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
+                         int64_t n_samples, const gyp_iq_level* levels_host);
+
+/* Host only (no GPU; errors through gyp_last_error(NULL)): the level that removes the mean (remove_dc != 0) and brings the RMS of
+ * |x| per complex sample to target_rms, from n_ms records of one stream.  Float64, in exactly this order, one rounding per
+ * operation (no contraction):
+ *     S_re, S_im, S_sq = the plain left-to-right sums of sum_re, sum_im, sum_sq over the records;  C = the int64 sum of n_clip
+ *     M = (double)n_ms * samples_per_ms;   m_re = S_re / M;   m_im = S_im / M;   P = S_sq / M
+ *     (d_re, d_im) = remove_dc ? (m_re, m_im) : (0, 0)
+ *     a = d_re * d_re;   b = d_im * d_im;   q = a + b;   V = P - q;   rms = sqrt(V);   g = target_rms / rms
+ * level_out = {(float)d_re, (float)d_im, (float)g, 0};  measured_out4 (may be NULL) = {m_re, m_im, rms, C / (2 M)}: the mean, the
+ * RMS about the removed offset and the share of clipped components.  GYP_E_BAD_ARG for NULL stats or level_out, n_ms < 1,
+ * samples_per_ms < 1, target_rms not positive and finite, V not positive and finite (a constant recording has no power to
+ * scale), or a level that float32 cannot hold. */
+int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms, int32_t remove_dc, double target_rms,
+                            gyp_iq_level* level_out, double* measured_out4);
+
+/* A level on an ingest handle (ctx required: a host-only handle returns GYP_E_BAD_ARG from all three, and gyp_ingest_next_host
+ * returns GYP_E_BAD_ARG while a level is on -- host blocks are raw file words, which a level does not define).  Where a level is
+ * on, every device block is conditioned in place on the upload stream, behind whatever produced it (the widen, unpack, resample
+ * or down-convert kernel, or the plain copy of a float32 recording): its samples are exactly gyp_condition_iq_dev of the samples
+ * the handle delivers without a level -- sample = word * scale as before, then the level.  The level is a constant of the handle,
+ * not a per-block estimate, so blocks, windows and seeks keep giving bit-identical samples.
+ * gyp_ingest_set_level (NULL: off) takes effect with the next block handed out: what was uploaded ahead is dropped and read
+ * again, as a seek to the consumer's position does. */
+int gyp_ingest_set_level(gyp_ingest* ing, const gyp_iq_level* level);
+int gyp_ingest_get_level(const gyp_ingest* ing, gyp_iq_level* out, int32_t* enabled_out);
+/* Measures output milliseconds [first_ms, first_ms + n_ms) of the handle, which must lie in [0, total_ms) with 1 <= n_ms <= 10000,
+ * and installs the level gyp_iq_level_from_stats derives.  What is measured is the handle's UNCONDITIONED output: the samples it
+ * delivers with its current scale (sample = word * scale) and without a level, whether or not one is installed.  The blocks are
+ * read through the handle's own path, gyp_iq_stats_dev (clip_level as given) runs on them and the records are combined in
+ * millisecond order, so the level does not depend on block_ms.  The cursor is put back where it was; the call synchronises, and
+ * blocks handed out earlier are no longer valid afterwards.  level_out / measured_out4 (either may be NULL) receive what
+ * gyp_iq_level_from_stats wrote.  On an error the handle keeps the level it had. */
+int gyp_ingest_calibrate(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
+                         gyp_iq_level* level_out, double* measured_out4);
+
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
  * with a message otherwise) and defaults:
@@ -706,7 +784,8 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
  *   "spec_debug" 0/1 (0)        per-ms window dump for gyp_debug_spec_read
  *   "track_chunk_ms" 0 | >= 20 (250)   launch length of the throughput tracking kernel (0: whole blocks)
  *   "resample_tile_samples" 1024..8192 (4096)  LDS budget of one resampler workgroup, in input samples; same output for any value
- *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring); same output for any value
+ *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring; the unpack,
+ *                               statistics and condition kernels follow it); same output for any value
  *   "no_exact_shared" 0/1 (0)   the exact code-loop sums behind the throughput tracking kernel fetch and convert a stream's samples once per
  *                               channel again (dll_exact_wave_kernel).  Default at 8 samples per chip, plain gyp_track_block(_dev) calls on the
  *                               throughput path: the channels are grouped by stream on the device and each (stream, millisecond) is staged once, as
