@@ -69,9 +69,13 @@ __device__ __forceinline__ double dll_discriminator_exact(const double (&ex)[6])
 
 // Carrier cycles at a chunk's first sample, f t0 + phi / 2 pi, reduced to a few cycles WITHOUT losing the fraction of f t0: the
 // product is ~2e5 cycles after 40 s and its rounding (3e-11 cycles) would turn every sum of the millisecond by 2e-10 rad.
+// ONE fma takes the nearest integer off the exact product.  (An earlier form read (prod - rint(prod)) + (fma(f, t0, -prod) + ...): the
+// compiler contracts prod - rint(prod) into that same exact fma, so the product's rounding error was added a second time -- up to half
+// an ulp of f t0, 1.5e-6 rad at one GPS week; tests/test_gpu_clocks.py found it.  Here rint() of the product
+// has nothing to contract with, and the fma is explicit.)
 __device__ __forceinline__ double carrier_cycles(double f, double t0, double phi) {
-    const double prod = f * t0, err = fma(f, t0, -prod);      // f t0 = prod + err exactly
-    return (prod - rint(prod)) + (err + phi * 0.15915494309189533577);
+    const double whole = rint(__dmul_rn(f, t0));              // |f t0 - whole| <= 1/2 + an ulp of f t0
+    return fma(f, t0, -whole) + phi * 0.15915494309189533577;
 }
 
 // One wavefront's share of the three sums -> red->expart[wave]; epl_finish* adds the wavefronts up after its barrier.

@@ -348,8 +348,9 @@ int gyp_bank_set_channel(gyp_bank* bank, int32_t index, const gyp_chan_init* ini
  * status-2 records for it until gyp_bank_set_channel revives the slot.  Synchronises the stream. */
 int gyp_bank_drop_channel(gyp_bank* bank, int32_t index);
 /* Advance every channel n_ms milliseconds.  iq_dev: n_streams x n_ms x N (stream stride given);
- * start_time_dev/end_time_dev: n_ms doubles (shared by all streams): chunk.start_time / chunk.end_time;
- * rec_out_dev: n_chan x n_ms records (channel-major), may be NULL.
+ * start_time_dev: n_ms doubles (shared by all streams): chunk.start_time of each millisecond, in seconds, any values up to one GPS
+ * week (they need not be gapless or increasing: the carrier is wiped off at start_time + n/fs and the watchdog runs on their
+ * differences; chunk.end_time is not read -- gyp_bits_push_block takes it); rec_out_dev: n_chan x n_ms records (channel-major), may be NULL.
  * The host form returns GYP_E_BAD_ARG when a channel's stream index is >= n_streams; for the _dev form the caller
  * guarantees that iq_dev holds (largest stream index + 1) streams.  Both return GYP_E_BAD_ARG when the context's stream
  * format is no longer the one the bank was created under.
