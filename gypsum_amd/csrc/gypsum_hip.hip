@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "bit_integrator.hpp"
 #include "grid_plan.hpp"
+#include "dev_mem.hpp"
 
 using namespace gyp;
 
@@ -114,77 +115,139 @@ static bool rate_supported(int k) {
 
 static thread_local std::string g_create_error;
 
+// Device buffers of the entry points on a context, one per role.  Each is reserved (Slack::grow) and used within one call, on the
+// context's stream; nothing is kept in them between calls.  A helper context (gyp_acquire_dev) has a set of its own.
+// Staging of the host-buffer entry points; only the wrappers that take host pointers use these, never a *_dev function:
+//   stage_iq       samples: gyp_correlate_cells, gyp_correlate_grid, gyp_search_level, gyp_acquire, gyp_track_step, gyp_track_block
+//   stage_in       descriptors: gyp_correlate_cells (gyp_cell_desc), gyp_track_step (gyp_chan_in)
+//   stage_out      results: gyp_correlate_cells, gyp_correlate_grid (gyp_cell), gyp_search_level, gyp_acquire (gyp_acq_result), gyp_track_step (gyp_chan_out), gyp_track_block (gyp_track_rec)
+//   stage_profile  optional profile rows: gyp_correlate_cells, gyp_track_step
+//   stage_times    start times: gyp_track_step (per stream), gyp_track_block (per millisecond)
+// Working buffers of the *_dev functions; no wrapper uses these:
+//   sat_ids, doppler          satellite ids and Doppler bins: gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev
+//   folded, z, grid_partial   gyp_correlate_grid_dev: folded rows, the wide rates' wiped-off samples, partial results of branch runs
+//   refine_list               gyp_grid_best_bins_refined_dev (refine_list_layout)
+//   partial64                 float64 per-millisecond sums: gyp_grid_best_bins_refined_dev, acquire_search
+//   acq_*                     acquire_search (gyp_acquire_dev, gyp_search_level_dev): search states, cell table, cell outputs, refined sums, float64 profiles, acq_book_layout, acq_units_layout, shared-forward spectra
+//   synth_scene, bench_sink   gyp_synth_iq_dev, gyp_debug_fft_bench
+// Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
+// wrapper calls another; of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
+// none calls another, and what acquire_search calls (correlate_cells_listed, gyp_correlate_cells_dev) uses no member.
+struct Scratch {
+    DevBuf<float> stage_iq, stage_profile, bench_sink;
+    DevBuf<uint8_t> stage_in, stage_out, refine_list, acq_book, acq_units;
+    DevBuf<double> stage_times, doppler, partial64, acq_refined, acq_profiles;
+    DevBuf<int32_t> sat_ids;
+    DevBuf<cf> folded, z, acq_spectra;
+    DevBuf<GridPartial> grid_partial;
+    DevBuf<AcqSearchState> acq_states;
+    DevBuf<gyp_cell_desc> acq_cells;
+    DevBuf<gyp_cell> acq_out;
+    DevBuf<gyp_synth_sat> synth_scene;
+};
+
+// The tables of the 32 C/A codes on the device (gyp_set_stream_format builds them whole, or not at all)
+struct CodeBufs {
+    DevBuf<cf> replicas, tw;    // [32][32][64]; tw1024[1024] ++ tw2048[1024] ++ ones[1024]
+    DevBuf<uint8_t> chips;      // [32][1023]: synthetic generator, float64 tie-breaks
+    DevBuf<uint16_t> ones, trans;   // [32][512]: positions of each code's 512 ones (float64 strength tie-break); [32][kMaxTrans]: chip transitions (float64 early/late boundary sums)
+    DevBuf<int32_t> ntrans;     // [32]
+    DevBuf<float> chipf;        // [32][2048]: +-1.0f codes, twice over (window correlations of the speculative tracker)
+};
+
 struct gyp_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    Stream own_stream;         // (declared before everything used on it: destroyed last)
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     int n_cus = 256;
     int n_xcd = 8;             // hipDeviceAttributeNumberOfXccs (workgroup b is dispatched to XCD b % n_xcd)
-    bool no_pipe = false;      // gyp_debug_set("no_pipe"): A/B switch back to the two-workgroups-per-CU cells kernel
-    int widen_wg_per_cu = 2;      // gyp_debug_set("widen_wg_per_cu"): workgroups per CU of the ingest widen kernel's persistent grid (1..8).  It runs on the
+    // A/B switches and test hooks: gyp_debug_set / gyp_debug_get by the names in kDebugSwitches below
+    bool no_pipe = false;      // A/B switch back to the two-workgroups-per-CU cells kernel
+    int widen_wg_per_cu = 2;      // workgroups per CU of the ingest widen kernel's persistent grid (1..8).  It runs on the
                                   // upload stream BESIDE the previous block's kernels: with 8 per CU (r02-r05) it took the chip at every launch boundary of the
                                   // trackers; 2 per CU leave them their slots -- int8-fed / resident 0.934-0.942 -> 0.949-0.953 (profiles/r06zi / r06zj_widen_grid.txt)
-    int resample_tile = 4096;     // gyp_debug_set("resample_tile_samples"): LDS budget of one resample_kernel tile, in input samples (32 KiB: five
+    int resample_tile = 4096;     // "resample_tile_samples": LDS budget of one resample_kernel tile, in input samples (32 KiB: five
                                   // workgroups per CU); same output for any value
-    std::vector<ResampleDesign> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps)
-    std::vector<std::pair<std::vector<float>, float*>> packed_levels;   // packed recordings: each level table met, in device memory
-    int track_chunk_ms = 250;     // gyp_debug_set("track_chunk_ms"): the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
-    float symbol_tau = 1e-4f;     // gyp_debug_set("symbol_tau"): |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
-    bool no_shared_fwd = false;   // gyp_debug_set("no_shared_fwd"): A/B switch: flat grids transform every cell's rows themselves again
-    bool no_acq_shared_fwd = false;   // gyp_debug_set("no_acq_shared_fwd"): A/B switch: acquisition levels transform every cell's rows themselves again
-    int cells_cu_reserve = 0;     // gyp_debug_set("cells_cu_reserve", n): CUs the correlation-cell launches leave free (see launch_cells)
+    std::vector<std::pair<ResampleDesign, DevBuf<float>>> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps), with the owner of its d_taps
+    std::vector<std::pair<std::vector<float>, DevBuf<float>>> packed_levels;   // packed recordings: each level table met, in device memory
+    int track_chunk_ms = 250;     // the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
+    float symbol_tau = 1e-4f;     // |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
+    bool no_shared_fwd = false;   // A/B switch: flat grids transform every cell's rows themselves again
+    bool no_acq_shared_fwd = false;   // A/B switch: acquisition levels transform every cell's rows themselves again
+    int cells_cu_reserve = 0;     // CUs the correlation-cell launches leave free (see launch_cells)
     int last_grid_refined_rows = 0;   // gyp_debug_get("last_grid_refined_rows"): rows the last gyp_grid_best_bins_refined_dev call decided in float64
-    int32_t* d_acq_witness = nullptr;   // [kAcqWitnessInts] gyp_debug_get("last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells", and "..._l<k>" per level): what the levels of
+    DevBuf<int32_t> acq_witness;        // [kAcqWitnessInts] gyp_debug_get("last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells", and "..._l<k>" per level): what the levels of
                                         // the last search on this context did (acq_init_kernel zeroes, the compact kernels add; read on request only)
     int acq_witness_lanes = 1;          // parts of that search: this context and the first acq_witness_lanes - 1 helpers
     GridPlan last_grid_plan{};    // of the last gyp_correlate_grid* call; gyp_debug_get("last_grid_path") reads its path (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
-    int grid_fused_waves = 12;    // gyp_debug_set("grid_fused_waves"): 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
-    bool no_grid_fused = false;   // gyp_debug_set("no_grid_fused"): A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
-    bool no_grid_parts = false;   // gyp_debug_set("no_grid_parts"): A/B switch: flat-grid work items take whole units (no branch runs + merge)
+    int grid_fused_waves = 12;    // 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
+    bool no_grid_fused = false;   // A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
+    bool no_grid_parts = false;   // A/B switch: flat-grid work items take whole units (no branch runs + merge)
     std::string err;
     // stream format
     int64_t fs = 0;
     int32_t n = 0;
     int k = 0;
-    cf* d_replicas = nullptr;  // [32][32][64]
-    cf* d_tw = nullptr;        // tw1024[1024] ++ tw2048[1024] ++ ones[1024]
-    uint8_t* d_chips = nullptr;  // [32][1023]: synthetic generator, float64 tie-breaks
-    uint16_t* d_ones = nullptr;  // [32][512]: positions of the 512 ones of each code (float64 strength tie-break)
-    uint16_t* d_trans = nullptr; // [32][kMaxTrans]: chip transitions (float64 early/late boundary sums)
-    int32_t* d_ntrans = nullptr; // [32]
-    float* d_chipf = nullptr;    // [32][2048]: +-1.0f codes, twice over (window correlations of the speculative tracker)
+    CodeBufs codes;
     // RCCL communicator (gyp_comm_init); the library is dlopen'ed on first use, libgypsum_hip does not link against it
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
     gyp_params params;
-    int spec_sub_ms = 0;         // gyp_debug_set("spec_sub_ms"): target length of a speculative block's sub-blocks (a failed verification costs one); 0 = by rate (spec_sub_ms_for)
-    bool spec_redo = true;       // gyp_debug_set("spec_redo"): 0 = A/B switch back to re-running a failed speculation on the throughput kernel
-    int prof_wave = 0;           // gyp_debug_set("prof_wave"): which wavefront of workgroup 0 stamps gyp_debug_track_profile's counters
-    bool no_exact_shared = false;   // gyp_debug_set("no_exact_shared"): A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
+    int spec_sub_ms = 0;         // target length of a speculative block's sub-blocks (a failed verification costs one); 0 = by rate (spec_sub_ms_for)
+    bool spec_redo = true;       // 0 = A/B switch back to re-running a failed speculation on the throughput kernel
+    int prof_wave = 0;           // which wavefront of workgroup 0 stamps gyp_debug_track_profile's counters
+    bool no_exact_shared = false;   // A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
     int last_exact_path = 0;     // gyp_debug_get("last_exact_path"): the exact-sums kernel of the last plain throughput call (0 none yet, 1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel)
-    bool no_spec = false;        // gyp_debug_set("no_spec"): A/B switch: lightly loaded banks use the throughput kernel too
-    int spec_fail_at = -1;       // gyp_debug_set("spec_fail_at", ms) (test hook): channel 0's verification is made to fail at that millisecond of a block
-    bool spec_debug = false;     // gyp_debug_set("spec_debug"): per-ms window dump of the speculative tracker (gyp_debug_spec_read)
-    double dll_prov_bias = 0.0;  // gyp_debug_set("dll_prov_bias", x) (test hook): added to the speculative kernel's PROVISIONAL discriminator, so
+    bool no_spec = false;        // A/B switch: lightly loaded banks use the throughput kernel too
+    int spec_fail_at = -1;       // (test hook): channel 0's verification is made to fail at that millisecond of a block
+    bool spec_debug = false;     // per-ms window dump of the speculative tracker (gyp_debug_spec_read)
+    double dll_prov_bias = 0.0;  // (test hook): added to the speculative kernel's PROVISIONAL discriminator, so
                                  // that dll_scan_kernel's repair path runs; results must not depend on it
-    long long* d_prof = nullptr; // debug: per-phase cycle counters of track_block workgroup 0
-    // gyp_debug_track_timing: HIP events around the three launches of the throughput tracking path (tracking kernel, exact sums, scan)
-    hipEvent_t ev_order = nullptr;   // gyp_wait_for(waiter, this): recorded on this context's stream
+    DevBuf<long long> prof;      // gyp_debug_track_profile: per-phase cycle counters of track_block workgroup 0
+    Event ev_order;              // gyp_wait_for(waiter, this): recorded on this context's stream
     static constexpr int kMaxAcqLanes = 4;
     gyp_ctx* helper[kMaxAcqLanes - 1] = {};   // gyp_acquire_dev: the other parts of a multi-stream scan run here (own stream, scratch, tables)
-    int acq_lanes = 2;               // gyp_debug_set("acq_lanes")
+    int acq_lanes = 2;
     bool is_helper = false;
-    bool no_acq_split = false;       // gyp_debug_set("no_acq_split"): A/B switch
+    bool no_acq_split = false;       // A/B switch
+    // gyp_debug_track_timing: HIP events around the three launches of the throughput tracking path (tracking kernel, exact sums, scan)
     bool time_track = false;
-    bool track_timed = false;
-    int track_launches = 0;     // launches of the tracking kernel behind the last timed call   // the events below have been recorded since timing was switched on (the speculative path records none)
-    hipEvent_t ev_track[4] = {nullptr, nullptr, nullptr, nullptr};
-    // growable scratch for the host-buffer entry points and the acquisition driver
-    static constexpr int kScratchSlots = 13;
-    void* scratch[kScratchSlots] = {};
-    size_t scratch_cap[kScratchSlots] = {};
+    bool track_timed = false;   // the events below have been recorded since timing was switched on (the speculative path records none)
+    int track_launches = 0;     // launches of the tracking kernel behind the last timed call
+    Event ev_track[4];
+    Scratch scratch;
 };
+
+// Every switch of gyp_debug_set / gyp_debug_get: name, range, integral or not, whether the helper contexts of a multi-stream scan run
+// under the caller's value (acquire_helper), getter, setter.  The read-only "last_*" values are in debug_read_only.
+struct DebugSwitch { const char* name; double lo, hi; bool integral, inherited; double (*get)(const gyp_ctx&); void (*set)(gyp_ctx&, double); };
+#define GYP_SWITCH(NAME, FIELD, LO, HI, INTEGRAL, INHERITED) \
+    {NAME, LO, HI, INTEGRAL, INHERITED, [](const gyp_ctx& c) { return (double)c.FIELD; }, [](gyp_ctx& c, double v) { c.FIELD = static_cast<decltype(c.FIELD)>(v); }}
+static const DebugSwitch kDebugSwitches[] = {
+    GYP_SWITCH("no_pipe", no_pipe, 0, 1, true, true),
+    GYP_SWITCH("no_shared_fwd", no_shared_fwd, 0, 1, true, true),
+    GYP_SWITCH("no_acq_shared_fwd", no_acq_shared_fwd, 0, 1, true, true),
+    GYP_SWITCH("no_acq_split", no_acq_split, 0, 1, true, false),
+    GYP_SWITCH("no_spec", no_spec, 0, 1, true, true),
+    GYP_SWITCH("spec_debug", spec_debug, 0, 1, true, false),
+    GYP_SWITCH("acq_lanes", acq_lanes, 1, gyp_ctx::kMaxAcqLanes, true, false),
+    GYP_SWITCH("track_chunk_ms", track_chunk_ms, 0, 1e6, true, true),   // (and not 1..19: gyp_debug_set)
+    GYP_SWITCH("widen_wg_per_cu", widen_wg_per_cu, 1, 8, true, false),
+    GYP_SWITCH("symbol_tau", symbol_tau, 0, 100, false, true),
+    GYP_SWITCH("dll_prov_bias", dll_prov_bias, -1e6, 1e6, false, false),
+    GYP_SWITCH("spec_fail_at", spec_fail_at, -1, 2147483647.0, true, false),
+    GYP_SWITCH("spec_redo", spec_redo, 0, 1, true, false),
+    GYP_SWITCH("spec_sub_ms", spec_sub_ms, 0, 2000, true, false),
+    GYP_SWITCH("no_exact_shared", no_exact_shared, 0, 1, true, false),
+    GYP_SWITCH("prof_wave", prof_wave, 0, 7, true, false),
+    GYP_SWITCH("no_grid_parts", no_grid_parts, 0, 1, true, false),
+    GYP_SWITCH("no_grid_fused", no_grid_fused, 0, 1, true, false),
+    GYP_SWITCH("grid_fused_waves", grid_fused_waves, 8, 12, true, false),   // (8 or 12: gyp_debug_set)
+    GYP_SWITCH("cells_cu_reserve", cells_cu_reserve, 0, 128, true, true),
+    GYP_SWITCH("resample_tile_samples", resample_tile, 1024, 8192, true, false),
+};
+#undef GYP_SWITCH
 
 struct gyp_bank {
     gyp_ctx* ctx = nullptr;
@@ -192,33 +255,26 @@ struct gyp_bank {
     int64_t fs = 0;              // the stream format the bank was created under
     int n = 0;
     std::vector<int32_t> stream_of;   // host copy of each channel's stream index
-    ChanState* d_states = nullptr;
+    Stream verify_stream;        // (declared before everything used on it: destroyed last)
+    Event ev_spec, ev_verify, ev_vring[3];
+    DevBuf<ChanState> states;
     // speculative block tracking: state checkpoint, per-(channel, ms) hand-over records, failed-verification flags
-    ChanState* d_ckpt = nullptr;
-    SpecIn* d_spec = nullptr;
-    double* d_disc = nullptr;    // [n_chan][n_ms] exact discriminators from the verify pass (dll_scan_kernel's input)
-    DllExact* d_dllx = nullptr;  // [n_chan] the exactly re-integrated code loop between sub-blocks
-    ExactGroup* d_groups = nullptr;  // [n_chan] + one int32 counter behind them: dll_exact_shared_kernel's channel groups (exact_group_kernel, every call)
-    int last_n_ms = 0;           // row length of d_spec / d_disc in the last throughput call (gyp_debug_disc_read)
-    size_t spec_cap = 0;         // in records
-    int32_t* d_bad = nullptr;
-    int32_t* d_bad_from = nullptr;   // per channel: first verify sub-block that failed
-    DllExact* d_hist = nullptr;      // [ckpt_cap + 1][n_chan] the exact code loop at the sub-block starts
-    int ckpt_cap = 0;                // sub-blocks d_ckpt / d_hist have room for (sized by the n_sub in use, grown on demand)
+    DevBuf<ChanState> ckpt;      // [sub-blocks][n_chan]: as many sub-blocks as the longest layout so far (18 KB per channel and sub-block)
+    DevBuf<SpecIn> spec;         // [n_chan][n_ms]
+    DevBuf<double> disc;         // [n_chan][n_ms] exact discriminators from the verify pass (dll_scan_kernel's input)
+    DevBuf<DllExact> dllx;       // [n_chan] the exactly re-integrated code loop between sub-blocks
+    DevBuf<ExactGroup> groups;   // [n_chan] + one int32 counter behind them: dll_exact_shared_kernel's channel groups (exact_group_kernel, every call)
+    int last_n_ms = 0;           // row length of spec / disc in the last throughput call (gyp_debug_disc_read)
+    DevBuf<int32_t> bad, bad_from;   // per channel: verification failed; the first verify sub-block that failed
+    DevBuf<DllExact> hist;       // [sub-blocks + 1][n_chan] the exact code loop at the sub-block starts
     // round protocol of the speculative tracker (SpecCtl, kernels_track_block.hpp)
-    SpecCtl* d_ctl = nullptr;        // [n_chan]
-    int32_t* d_trk = nullptr;        // [rounds_cap][n_chan]
-    int32_t* d_fail = nullptr;       // [rounds_cap][n_chan]
-    int rounds_cap = 0;
-    int32_t* d_redo_stats = nullptr; // [4] of the last block: sub-blocks, rounds, sub-block re-dos, channels finished by the transform kernel
-    hipEvent_t ev_vring[3] = {nullptr, nullptr, nullptr};
-    float* d_dbg = nullptr;      // GYP_SPEC_DEBUG: per-ms window dump of the last block
-    size_t dbg_cap = 0;
-    hipStream_t verify_stream = nullptr;
-    hipEvent_t ev_spec = nullptr, ev_verify = nullptr;
+    DevBuf<SpecCtl> ctl;         // [n_chan]
+    DevBuf<int32_t> trk, fail;   // [rounds][n_chan]
+    DevBuf<int32_t> redo_stats;  // [4] of the last block: sub-blocks, rounds, sub-block re-dos, channels finished by the transform kernel
+    DevBuf<float> dbg;           // GYP_SPEC_DEBUG: per-ms window dump of the last block
     // gyp_bank_keep_profiles: the last call's trailing prompt profiles (tracker.py:154,308-309)
-    float* d_prof_tail = nullptr;    // [n_chan][prof_depth][n]
-    int32_t* d_prof_delta = nullptr; // [n_chan][prof_depth] exact - provisional code phase (repaired milliseconds only)
+    DevBuf<float> prof_tail;     // [n_chan][prof_depth][n]
+    DevBuf<int32_t> prof_delta;  // [n_chan][prof_depth] exact - provisional code phase (repaired milliseconds only)
     int prof_depth = 0;
     int prof_rows = 0;               // rows valid after the last gyp_track_block(_dev)
 };
@@ -298,18 +354,29 @@ static int fail(gyp_ctx* ctx, int code, const std::string& msg) {
             return fail(ctx, GYP_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
-static int ensure_scratch(gyp_ctx* ctx, int slot, size_t bytes) {
-    if (ctx->scratch_cap[slot] >= bytes) return GYP_OK;
-    if (ctx->scratch[slot]) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(ctx->scratch[slot]));
-        ctx->scratch[slot] = nullptr;
-        ctx->scratch_cap[slot] = 0;
-    }
-    const size_t cap = bytes + bytes / 4 + 4096;
-    HIP_TRY(ctx, hipMalloc(&ctx->scratch[slot], cap));
-    ctx->scratch_cap[slot] = cap;
+static const char* const kNoFormat = "gyp_set_stream_format has not been called";
+static int need_format(gyp_ctx* ctx) { return ctx->k ? GYP_OK : fail(ctx, GYP_E_NO_FORMAT, kNoFormat); }
+static int check_sat_ids(gyp_ctx* ctx, const int32_t* ids, int n) {
+    for (int i = 0; i < n; ++i) if (ids[i] < 1 || ids[i] > 32) return fail(ctx, GYP_E_BAD_ARG, "satellite id out of range");
     return GYP_OK;
+}
+// n_streams * n_ms milliseconds of complex64 samples, in floats
+static size_t iq_floats(const gyp_ctx* ctx, int64_t n_streams, int64_t n_ms) { return (size_t)n_streams * n_ms * ctx->n * 2; }
+static const uint8_t* as_bytes(const void* p) { return static_cast<const uint8_t*>(p); }
+// The tail of a host-buffer entry point: the staged results (and profile rows) copied back; returns when they have arrived.
+static int stage_back(gyp_ctx* ctx, void* out_host, size_t out_bytes, float* profile_host = nullptr, size_t n_prof = 0) {
+    if (out_host) HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch.stage_out.get(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (profile_host) HIP_TRY(ctx, hipMemcpyAsync(profile_host, ctx->scratch.stage_profile.get(), n_prof * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GYP_OK;
+}
+// A channel's state at the start of tracking: the acquisition's values, fresh loop state and histories
+static ChanState fresh_chan_state(const gyp_chan_init& in) {
+    ChanState s;
+    std::memset(&s, 0, sizeof(s));
+    s.stream = in.stream; s.sat_id = in.sat_id; s.doppler = in.doppler_hz; s.carrier_phase = in.carrier_phase;
+    s.code_phase = in.code_phase; s.dll_phase = (double)in.code_phase;  // tracker.py:224
+    return s;
 }
 
 extern "C" {
@@ -378,13 +445,12 @@ int gyp_create(int device_ordinal, gyp_ctx** out) {
     // (no GYP_* environment variable is read here or anywhere else in the library except GYP_RCCL_LIB, a deployment's library path:
     // the A/B switches and test hooks below are set through gyp_debug_set by whoever wants them)
     gyp_params_default(&ctx->params);
-    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+    if (ctx->own_stream.create(hipStreamNonBlocking) != hipSuccess || ctx->ev0.create(hipEventDefault) != hipSuccess || ctx->ev1.create(hipEventDefault) != hipSuccess) {
         delete ctx;
         return fail(nullptr, GYP_E_HIP, "stream/event creation failed");
     }
-    ctx->stream = ctx->own_stream;
-    if (hipMalloc((void**)&ctx->d_acq_witness, kAcqWitnessInts * sizeof(int32_t)) != hipSuccess || hipMemset(ctx->d_acq_witness, 0, kAcqWitnessInts * sizeof(int32_t)) != hipSuccess) {
+    ctx->stream = ctx->own_stream.get();
+    if (ctx->acq_witness.reserve(kAcqWitnessInts, Slack::exact) != hipSuccess || hipMemset(ctx->acq_witness.get(), 0, kAcqWitnessInts * sizeof(int32_t)) != hipSuccess) {
         gyp_destroy(ctx);
         return fail(nullptr, GYP_E_HIP, "gyp_create: no device memory for the acquisition counters");
     }
@@ -397,26 +463,8 @@ void gyp_destroy(gyp_ctx* ctx) {
     for (auto& h : ctx->helper) if (h) { gyp_destroy(h); h = nullptr; }
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < gyp_ctx::kScratchSlots; ++i)
-        if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
-    if (ctx->d_replicas) (void)hipFree(ctx->d_replicas);
-    if (ctx->d_tw) (void)hipFree(ctx->d_tw);
-    if (ctx->d_chips) (void)hipFree(ctx->d_chips);
-    if (ctx->d_ones) (void)hipFree(ctx->d_ones);
-    if (ctx->d_trans) (void)hipFree(ctx->d_trans);
-    if (ctx->d_ntrans) (void)hipFree(ctx->d_ntrans);
-    if (ctx->d_chipf) (void)hipFree(ctx->d_chipf);
-    if (ctx->d_prof) (void)hipFree(ctx->d_prof);
-    if (ctx->d_acq_witness) (void)hipFree(ctx->d_acq_witness);
-    for (auto& d : ctx->resample_designs) if (d.d_taps) (void)hipFree(d.d_taps);
-    for (auto& l : ctx->packed_levels) (void)hipFree(l.second);
-    for (int i = 0; i < 4; ++i) if (ctx->ev_track[i]) (void)hipEventDestroy(ctx->ev_track[i]);
-    if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;   // the members release what they hold: buffers and events first, the stream last
 }
 
 int gyp_device_name(gyp_ctx* ctx, char* out, int cap) {
@@ -429,7 +477,7 @@ int gyp_device_name(gyp_ctx* ctx, char* out, int cap) {
 
 int gyp_set_stream(gyp_ctx* ctx, void* hip_stream) {
     if (!ctx) return GYP_E_BAD_ARG;
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.get();
     return GYP_OK;
 }
 
@@ -442,23 +490,23 @@ int gyp_sync(gyp_ctx* ctx) {
 int gyp_wait_for(gyp_ctx* ctx, gyp_ctx* other) {
     if (!ctx || !other) return GYP_E_BAD_ARG;
     if (ctx == other) return GYP_OK;
-    if (!other->ev_order) HIP_TRY(ctx, hipEventCreateWithFlags(&other->ev_order, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(other->ev_order, other->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, other->ev_order, 0));
+    HIP_TRY(ctx, other->ev_order.create(hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(other->ev_order.get(), other->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, other->ev_order.get(), 0));
     return GYP_OK;
 }
 
 int gyp_timer_start(gyp_ctx* ctx) {
     if (!ctx) return GYP_E_BAD_ARG;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0.get(), ctx->stream));
     return GYP_OK;
 }
 
 int gyp_timer_stop(gyp_ctx* ctx, float* elapsed_ms) {
     if (!ctx || !elapsed_ms) return GYP_E_BAD_ARG;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    HIP_TRY(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1.get(), ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1.get()));
+    HIP_TRY(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0.get(), ctx->ev1.get()));
     return GYP_OK;
 }
 
@@ -486,7 +534,8 @@ int gyp_set_stream_format(gyp_ctx* ctx, int64_t fs_hz, int32_t samples_per_ms) {
     if (!rate_supported(k))
         return fail(ctx, GYP_E_BAD_RATE, "supported multiples of 1.023 MHz: 1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 48");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_replicas) {
+    if (!ctx->codes.replicas.get()) {   // built into a local: the context gets the tables whole or, after a failure, not at all (the next call tries again)
+        CodeBufs t;
         std::vector<uint8_t> chips(32 * kChips);
         if (make_prn_chips(chips.data()) != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, "PRN self-check against IS-GPS-200 markers failed");
         std::vector<float> rep(32 * 32 * 64 * 2);
@@ -504,12 +553,6 @@ int gyp_set_stream_format(gyp_ctx* ctx, int64_t fs_hz, int32_t samples_per_ms) {
             tw[(1024 + n) * 2 + 0] = (float)std::cos(a);
             tw[(1024 + n) * 2 + 1] = (float)std::sin(a);
         }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_replicas, rep.size() * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tw, tw.size() * sizeof(float)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_replicas, rep.data(), rep.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chips, chips.size()));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_chips, chips.data(), chips.size(), hipMemcpyHostToDevice));
         std::vector<uint16_t> ones(32 * 512);   // every C/A code has exactly 512 ones (balanced Gold codes)
         for (int sv = 0; sv < 32; ++sv) {
             int k1 = 0;
@@ -517,8 +560,6 @@ int gyp_set_stream_format(gyp_ctx* ctx, int64_t fs_hz, int32_t samples_per_ms) {
                 if (chips[(size_t)sv * kChips + m] && k1 < 512) ones[(size_t)sv * 512 + k1++] = (uint16_t)m;
             if (k1 != 512) return fail(ctx, GYP_E_BAD_ARG, "a generated C/A code does not have 512 ones");
         }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ones, ones.size() * sizeof(uint16_t)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_ones, ones.data(), ones.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         // chip transitions m (chip[m-1] != chip[m], indices mod 1023) with the sign of chip[m-1] - chip[m] as +-1 codes,
         // and the +-1 codes themselves laid out twice so that chip[(j - q) mod 1023] is chipf[j - q + 1023]
         std::vector<uint16_t> trans((size_t)32 * kMaxTrans, 0);
@@ -534,12 +575,18 @@ int gyp_set_stream_format(gyp_ctx* ctx, int64_t fs_hz, int32_t samples_per_ms) {
             ntrans[sv] = nt;
             for (int i = 0; i < 2048; ++i) chipf[(size_t)sv * 2048 + i] = c[i % kChips] ? 1.0f : -1.0f;
         }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_trans, trans.size() * sizeof(uint16_t)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_trans, trans.data(), trans.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ntrans, ntrans.size() * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_ntrans, ntrans.data(), ntrans.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chipf, chipf.size() * sizeof(float)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_chipf, chipf.data(), chipf.size() * sizeof(float), hipMemcpyHostToDevice));
+        const auto put = [&](auto& buf, const auto& host, size_t count) -> hipError_t {   // (count in the buffer's elements)
+            const hipError_t e = buf.reserve(count, Slack::exact);
+            return e != hipSuccess ? e : hipMemcpy(buf.get(), host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice);
+        };
+        HIP_TRY(ctx, put(t.replicas, rep, rep.size() / 2));
+        HIP_TRY(ctx, put(t.tw, tw, tw.size() / 2));
+        HIP_TRY(ctx, put(t.chips, chips, chips.size()));
+        HIP_TRY(ctx, put(t.ones, ones, ones.size()));
+        HIP_TRY(ctx, put(t.trans, trans, trans.size()));
+        HIP_TRY(ctx, put(t.ntrans, ntrans, ntrans.size()));
+        HIP_TRY(ctx, put(t.chipf, chipf, chipf.size()));
+        ctx->codes = std::move(t);
     }
     ctx->fs = fs_hz;
     ctx->n = samples_per_ms;
@@ -619,7 +666,7 @@ static int for_rate(gyp_ctx* ctx, F&& f) {
         GYP_FOR_EACH_RATE(X)
 #undef X
     }
-    return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    return fail(ctx, GYP_E_NO_FORMAT, kNoFormat);
 }
 // a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
 template <typename F>
@@ -760,10 +807,10 @@ static CellsParams cells_params(gyp_ctx* ctx, const float* iq_dev, int64_t strea
     p.n_cells = n_cells;
     p.out = out_dev;
     p.profile_out = profile_out_dev;
-    p.replica_table = ctx->d_replicas;
-    p.tw_tables = ctx->d_tw;
+    p.replica_table = ctx->codes.replicas.get();
+    p.tw_tables = ctx->codes.tw.get();
     p.inv_fs = 1.0 / (double)ctx->fs;
-    p.prof = ctx->d_prof;
+    p.prof = ctx->prof.get();
     p.prof_wave = std::min(ctx->prof_wave, 7);
     p.order = order_dev;
     p.n_active = n_active_dev;
@@ -775,7 +822,7 @@ static int correlate_cells_listed(gyp_ctx* ctx, const float* iq_dev, int64_t str
                                   const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
                                   gyp_cell* out_dev, float* profile_out_dev, const int32_t* order_dev, const int32_t* n_active_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !cells_dev || !out_dev || n_ms < 0 || n_cells < 0 || (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells_dev: bad argument");
     if (n_cells == 0) return GYP_OK;
@@ -794,7 +841,7 @@ int gyp_correlate_cells(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, i
                         const gyp_cell_desc* cells_host, int32_t n_cells, int32_t integration,
                         gyp_cell* out_host, float* profile_out_host) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_host || !cells_host || !out_host || n_streams <= 0 || n_ms < 0 || n_cells < 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells: bad argument");
     for (int i = 0; i < n_cells; ++i)
@@ -802,28 +849,53 @@ int gyp_correlate_cells(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, i
             cells_host[i].tap_index >= ctx->n)
             return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells: cell descriptor out of range");
     if (n_cells == 0) return GYP_OK;
-    const size_t iq_bytes = (size_t)n_streams * n_ms * ctx->n * 8;
-    int rc;
-    if ((rc = ensure_scratch(ctx, 0, iq_bytes ? iq_bytes : 8))) return rc;
-    if ((rc = ensure_scratch(ctx, 1, (size_t)n_cells * sizeof(gyp_cell_desc)))) return rc;
-    if ((rc = ensure_scratch(ctx, 2, (size_t)n_cells * sizeof(gyp_cell)))) return rc;
-    const size_t prof_bytes = (size_t)n_cells * ctx->n * (integration == GYP_COHERENT ? 8 : 4);
-    if (profile_out_host && (rc = ensure_scratch(ctx, 3, prof_bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], cells_host, (size_t)n_cells * sizeof(gyp_cell_desc), hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_correlate_cells_dev(ctx, (const float*)ctx->scratch[0], (int64_t)n_ms * ctx->n, n_ms,
-                                 (const gyp_cell_desc*)ctx->scratch[1], n_cells, integration, (gyp_cell*)ctx->scratch[2],
-                                 profile_out_host ? (float*)ctx->scratch[3] : nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch[2], (size_t)n_cells * sizeof(gyp_cell), hipMemcpyDeviceToHost, ctx->stream));
-    if (profile_out_host)
-        HIP_TRY(ctx, hipMemcpyAsync(profile_out_host, ctx->scratch[3], prof_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    Scratch& sc = ctx->scratch;
+    const size_t n_iq = iq_floats(ctx, n_streams, n_ms), out_bytes = (size_t)n_cells * sizeof(gyp_cell);
+    const size_t n_prof = profile_out_host ? (size_t)n_cells * ctx->n * (integration == GYP_COHERENT ? 2 : 1) : 0;
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.stage_profile.reserve(n_prof, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, n_iq, ctx->stream, n_iq ? 0 : 2));
+    HIP_TRY(ctx, upload(sc.stage_in, as_bytes(cells_host), (size_t)n_cells * sizeof(gyp_cell_desc), ctx->stream));
+    if (const int rc = gyp_correlate_cells_dev(ctx, sc.stage_iq.get(), (int64_t)n_ms * ctx->n, n_ms, (const gyp_cell_desc*)sc.stage_in.get(), n_cells,
+                                               integration, (gyp_cell*)sc.stage_out.get(), profile_out_host ? sc.stage_profile.get() : nullptr))
+        return rc;
+    return stage_back(ctx, out_host, out_bytes, profile_out_host, n_prof);
 }
 
 // ---------------------------------------------------------------- flat search grid -----------------------
 }   // extern "C"
+// The three scratch buffers that hold several arrays: one layout each, giving the size on a null base and the pointers on the buffer.
+static size_t refine_list_layout(void* base, size_t n_rows, size_t n_cells, GridRefineParams* p) {   // Scratch::refine_list
+    Carve c(base);
+    p->n_cand = c.take<int32_t>(4);            // [0] candidates, [1] pending rows
+    p->pend_rows = c.take<int32_t>(n_rows); p->pend_first = c.take<int32_t>(n_rows);
+    p->cand = c.take<int32_t>(n_cells);
+    return c.bytes();
+}
+struct AcqBook {        // acquire_search's bookkeeping (Scratch::acq_book)
+    gyp_cell* prev_out;                       // the previous level's records
+    int32_t *reuse, *order, *cand;            // reuse map, the level's work list, the tie-break's candidate list
+    int32_t *n_active, *n_cand, *n_pend;      // their lengths; candidates of the tie-break in n_cand[0], pending cross-level pairs in n_cand[1] = n_pend[0]
+    size_t bytes;
+};
+static AcqBook acq_book_layout(void* base, size_t n_cells) {
+    Carve c(base);
+    AcqBook b;
+    b.prev_out = c.take<gyp_cell>(n_cells);
+    b.reuse = c.take<int32_t>(n_cells); b.order = c.take<int32_t>(n_cells); b.cand = c.take<int32_t>(n_cells);
+    b.n_active = c.take<int32_t>(1); b.n_cand = c.take<int32_t>(1); b.n_pend = c.take<int32_t>(1);   // three counters at the start of a 64-byte tail
+    c.take<int32_t>(13);
+    b.bytes = c.bytes();
+    return b;
+}
+static size_t acq_units_layout(void* base, size_t max_units, size_t n_cells, AcqUnits* u) {   // Scratch::acq_units
+    Carve c(base);
+    u->unit_cell = c.take<int32_t>(max_units);
+    u->sh_cell = c.take<int32_t>(n_cells); u->sh_unit = c.take<int32_t>(n_cells);
+    u->counts = c.take<int32_t>(4);
+    return c.bytes();
+}
+
 static_assert(sizeof(cf) == kGridCfBytes && sizeof(GridPartial) == kGridPartialBytes && kChips == kGridChips, "grid_plan.hpp sizes the scratch by these");
 // 12 or 8 wavefronts per workgroup ("grid_fused_waves") as a compile-time constant
 template <typename F>
@@ -846,7 +918,7 @@ static int launch_grid(gyp_ctx* ctx, const GridParams& p, const GridPlan& pl, bo
             });
     }
     if constexpr (K > 8) {   // wide rates: coalesced wipe-off into z, then the K-sample boxcar out of LDS tiles
-        cf* zbuf = (cf*)ctx->scratch[6];
+        cf* zbuf = ctx->scratch.z.get();
         const dim3 zgrid((unsigned)((K * kChips + 255) / 256), (unsigned)n_blk, (unsigned)n_units);
         for_flag(coh, [&](auto c) { hipLaunchKernelGGL((grid_wipe_kernel<K, decltype(c)::value>), zgrid, dim3(256), 0, stream, p, zbuf); });
         HIP_TRY(ctx, hipGetLastError());
@@ -882,41 +954,38 @@ int gyp_correlate_grid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams,
                            const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host, int32_t n_bins,
                            int32_t integration, gyp_cell* out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !sat_ids_host || !doppler_hz_host || !out_dev || n_streams <= 0 || n_ms <= 0 || n_sats <= 0 || n_bins <= 0 ||
         (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_grid_dev: bad argument");
-    for (int i = 0; i < n_sats; ++i)
-        if (sat_ids_host[i] < 1 || sat_ids_host[i] > 32) return fail(ctx, GYP_E_BAD_ARG, "satellite id out of range");
+    if (const int rc = check_sat_ids(ctx, sat_ids_host, n_sats)) return rc;
     const bool coh = integration == GYP_COHERENT;
     const int n_blk = coh ? 1 : n_ms;
     const int64_t n_units = (int64_t)n_streams * n_bins;
     if (n_units > 2147483647LL / 2 || n_blk > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_grid_dev: grid too large");
     const GridPlan pl = grid_plan(GridShape{ctx->k, ctx->n_cus, n_units, n_sats, n_blk},
                                   GridSwitches{ctx->no_pipe, ctx->no_shared_fwd, ctx->no_grid_fused, ctx->no_grid_parts, ctx->grid_fused_waves});
-    int rc;
-    if (pl.folded_bytes && (rc = ensure_scratch(ctx, 0, pl.folded_bytes))) return rc;
-    if (pl.z_bytes && (rc = ensure_scratch(ctx, 6, pl.z_bytes))) return rc;
-    if (pl.partial_bytes && (rc = ensure_scratch(ctx, 10, pl.partial_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 1, (size_t)n_sats * sizeof(int32_t) + 64))) return rc;
-    if ((rc = ensure_scratch(ctx, 4, (size_t)n_bins * sizeof(double) + 64))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], sat_ids_host, (size_t)n_sats * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4], doppler_hz_host, (size_t)n_bins * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.folded.reserve(pl.folded_bytes / sizeof(cf), Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.z.reserve(pl.z_bytes / sizeof(cf), Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.grid_partial.reserve(pl.partial_bytes / sizeof(GridPartial), Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.sat_ids, sat_ids_host, (size_t)n_sats, ctx->stream, 16));
+    HIP_TRY(ctx, upload(sc.doppler, doppler_hz_host, (size_t)n_bins, ctx->stream, 8));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host arrays may be temporaries
     GridParams p;
     p.iq = reinterpret_cast<const cf*>(iq_dev);
     p.stream_stride = stream_stride_samples;
     p.n_ms = n_ms; p.n_streams = n_streams; p.n_sats = n_sats; p.n_bins = n_bins;
-    p.sat_ids = (const int32_t*)ctx->scratch[1];
-    p.doppler = (const double*)ctx->scratch[4];
-    p.folded = (cf*)ctx->scratch[0];
+    p.sat_ids = sc.sat_ids.get();
+    p.doppler = sc.doppler.get();
+    p.folded = sc.folded.get();
     p.out = out_dev;
-    p.replica_table = ctx->d_replicas;
-    p.tw_tables = ctx->d_tw;
+    p.replica_table = ctx->codes.replicas.get();
+    p.tw_tables = ctx->codes.tw.get();
     p.inv_fs = 1.0 / (double)ctx->fs;
     p.parts = pl.parts;
-    p.partial = pl.partial_bytes ? (GridPartial*)ctx->scratch[10] : nullptr;
-    if ((rc = for_rate(ctx, [&](auto rate) { return launch_grid<decltype(rate)::value>(ctx, p, pl, coh); }))) return rc;
+    p.partial = pl.partial_bytes ? sc.grid_partial.get() : nullptr;
+    if (const int rc = for_rate(ctx, [&](auto rate) { return launch_grid<decltype(rate)::value>(ctx, p, pl, coh); })) return rc;
     ctx->last_grid_plan = pl;
     return GYP_OK;
 }
@@ -924,26 +993,22 @@ int gyp_correlate_grid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams,
 int gyp_correlate_grid(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                        int32_t n_sats, const double* doppler_hz_host, int32_t n_bins, int32_t integration, gyp_cell* out_host) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0 || n_bins <= 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_grid: bad argument");
-    const size_t iq_bytes = (size_t)n_streams * n_ms * ctx->n * 8;
+    Scratch& sc = ctx->scratch;
     const size_t out_bytes = (size_t)n_streams * n_sats * n_bins * sizeof(gyp_cell);
-    int rc;
-    if ((rc = ensure_scratch(ctx, 5, iq_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 2, out_bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_correlate_grid_dev(ctx, (const float*)ctx->scratch[5], n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats,
-                                doppler_hz_host, n_bins, integration, (gyp_cell*)ctx->scratch[2]);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch[2], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    if (const int rc = gyp_correlate_grid_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, doppler_hz_host,
+                                              n_bins, integration, (gyp_cell*)sc.stage_out.get()))
+        return rc;
+    return stage_back(ctx, out_host, out_bytes);
 }
 
 int gyp_grid_best_bins_dev(gyp_ctx* ctx, const gyp_cell* cells_dev, int32_t n_rows, int32_t n_bins, gyp_best_bin* out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!cells_dev || !out_dev || n_rows < 0 || n_bins <= 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_grid_best_bins_dev: bad argument");
     if (n_rows == 0) return GYP_OK;
     hipLaunchKernelGGL(grid_best_bin_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, ctx->stream, cells_dev, n_rows, n_bins, ctx->n, out_dev);
@@ -955,33 +1020,26 @@ int gyp_grid_best_bins_refined_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_
                                    const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host, int32_t n_bins, int32_t integration,
                                    const gyp_cell* cells_dev, gyp_best_bin* out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !sat_ids_host || !doppler_hz_host || !cells_dev || !out_dev || n_streams <= 0 || n_ms <= 0 || n_sats <= 0 || n_bins <= 0 ||
         (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_grid_best_bins_refined_dev: bad argument");
-    for (int i = 0; i < n_sats; ++i)
-        if (sat_ids_host[i] < 1 || sat_ids_host[i] > 32) return fail(ctx, GYP_E_BAD_ARG, "satellite id out of range");
+    if (const int rc = check_sat_ids(ctx, sat_ids_host, n_sats)) return rc;
     const int64_t n_rows = (int64_t)n_streams * n_sats, n_cells = n_rows * n_bins;
     if (n_cells > 2147483647LL / 2) return fail(ctx, GYP_E_BAD_ARG, "gyp_grid_best_bins_refined_dev: grid too large");
-    int rc;
-    // scratch: the ids and bins (slots 1 / 4 as in gyp_correlate_grid_dev), the work list + counters + pending rows, the per-ms sums
-    if ((rc = ensure_scratch(ctx, 1, (size_t)n_sats * sizeof(int32_t) + 64))) return rc;
-    if ((rc = ensure_scratch(ctx, 4, (size_t)n_bins * sizeof(double) + 64))) return rc;
-    if ((rc = ensure_scratch(ctx, 8, (size_t)(n_cells + 2 * n_rows + 4) * sizeof(int32_t)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], sat_ids_host, (size_t)n_sats * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4], doppler_hz_host, (size_t)n_bins * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    Scratch& sc = ctx->scratch;
     GridRefineParams p;
+    HIP_TRY(ctx, sc.refine_list.reserve(refine_list_layout(nullptr, (size_t)n_rows, (size_t)n_cells, &p), Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.sat_ids, sat_ids_host, (size_t)n_sats, ctx->stream, 16));
+    HIP_TRY(ctx, upload(sc.doppler, doppler_hz_host, (size_t)n_bins, ctx->stream, 8));
     p.iq = reinterpret_cast<const cf*>(iq_dev);
     p.stream_stride = stream_stride_samples;
     p.n_ms = n_ms; p.n_per_ms = ctx->n; p.k = ctx->k; p.n_sats = n_sats; p.n_bins = n_bins; p.n_rows = (int32_t)n_rows;
     p.coherent = integration == GYP_COHERENT ? 1 : 0;
-    p.sat_ids = (const int32_t*)ctx->scratch[1];
-    p.doppler = (const double*)ctx->scratch[4];
-    p.cells = cells_dev; p.out = out_dev; p.chips = ctx->d_chips; p.inv_fs = 1.0 / (double)ctx->fs;
-    p.n_cand = (int32_t*)ctx->scratch[8];
-    p.pend_rows = p.n_cand + 4;
-    p.pend_first = p.pend_rows + n_rows;
-    p.cand = p.pend_first + n_rows;
+    p.sat_ids = sc.sat_ids.get();
+    p.doppler = sc.doppler.get();
+    p.cells = cells_dev; p.out = out_dev; p.chips = ctx->codes.chips.get(); p.inv_fs = 1.0 / (double)ctx->fs;
+    refine_list_layout(sc.refine_list.get(), (size_t)n_rows, (size_t)n_cells, &p);
     HIP_TRY(ctx, hipMemsetAsync(p.n_cand, 0, 4 * sizeof(int32_t), ctx->stream));
     p.partial = nullptr;
     hipLaunchKernelGGL(grid_best_bin_select_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, p);
@@ -993,8 +1051,8 @@ int gyp_grid_best_bins_refined_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->last_grid_refined_rows = counts[1];
     if (counts[0] == 0) return GYP_OK;
-    if ((rc = ensure_scratch(ctx, 9, (size_t)counts[0] * n_ms * 2 * sizeof(double)))) return rc;
-    p.partial = (double*)ctx->scratch[9];
+    HIP_TRY(ctx, sc.partial64.reserve((size_t)counts[0] * n_ms * 2, Slack::grow, ctx->stream));
+    p.partial = sc.partial64.get();
     hipLaunchKernelGGL(grid_refine_kernel, dim3((unsigned)std::min(counts[0], 65535), (unsigned)n_ms), dim3(256), 0, ctx->stream, p);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(grid_best_bin_decide_kernel, dim3((unsigned)std::min((counts[1] + 63) / 64, 1024)), dim3(64), 0, ctx->stream, p);
@@ -1008,40 +1066,31 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
                           const int32_t* sat_ids_host, int32_t n_sats, double center0, double spread0, bool single_level,
                           gyp_acq_result* out_dev, int stream_base = 0) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !sat_ids_host || !out_dev || n_streams <= 0 || n_sats <= 0 || n_ms <= 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_acquire_dev / gyp_search_level_dev: bad argument");
-    for (int i = 0; i < n_sats; ++i)
-        if (sat_ids_host[i] < 1 || sat_ids_host[i] > 32) return fail(ctx, GYP_E_BAD_ARG, "satellite id out of range");
+    if (const int rc = check_sat_ids(ctx, sat_ids_host, n_sats)) return rc;
     if (n_sats > 32) return fail(ctx, GYP_E_BAD_ARG, "at most 32 satellites per search");
     const int n_states = n_streams * n_sats;
     int rc;
     const size_t n_cells = (size_t)n_states * kMaxBins;
-    if ((rc = ensure_scratch(ctx, 4, (size_t)n_states * sizeof(AcqSearchState)))) return rc;
-    if ((rc = ensure_scratch(ctx, 1, n_cells * sizeof(gyp_cell_desc)))) return rc;
-    if ((rc = ensure_scratch(ctx, 2, n_cells * sizeof(gyp_cell)))) return rc;
-    if ((rc = ensure_scratch(ctx, 3, n_cells * sizeof(double)))) return rc;
-    // previous level's records, reuse map, the level's work list, the tie-break's candidate list, their lengths
-    if ((rc = ensure_scratch(ctx, 8, n_cells * (sizeof(gyp_cell) + 3 * sizeof(int32_t)) + 64))) return rc;
-    gyp_cell* d_prev_out = (gyp_cell*)ctx->scratch[8];
-    int32_t* d_reuse = (int32_t*)(d_prev_out + n_cells);
-    int32_t* d_order = d_reuse + n_cells;
-    int32_t* d_cand = d_order + n_cells;
-    int32_t* d_n_active = d_cand + n_cells;
-    int32_t* d_n_cand = d_n_active + 1;      // [0] candidates of the tie-break, [1] pending cross-level pairs
-    int32_t* d_n_pend = d_n_cand + 1;
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.acq_states.reserve((size_t)n_states, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_cells.reserve(n_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_out.reserve(n_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_refined.reserve(n_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_book.reserve(acq_book_layout(nullptr, n_cells).bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.partial64.reserve(n_cells * (size_t)n_ms, Slack::grow, ctx->stream));   // per-ms magnitudes of the candidates
+    // float64 profile rows of the (rare) cross-level near-ties: written whole by acq_exact_profile_kernel
+    HIP_TRY(ctx, sc.acq_profiles.reserve((size_t)n_states * 2 * ctx->n, Slack::grow, ctx->stream));
+    const AcqBook book = acq_book_layout(sc.acq_book.get(), n_cells);
+    gyp_cell* d_prev_out = book.prev_out;
+    int32_t *d_reuse = book.reuse, *d_order = book.order, *d_cand = book.cand, *d_n_active = book.n_active, *d_n_cand = book.n_cand, *d_n_pend = book.n_pend;
     int32_t* d_pend = d_reuse;               // the reuse map is consumed by acq_reuse_kernel before acq_reduce_kernel fills this
-    if ((rc = ensure_scratch(ctx, 9, n_cells * (size_t)n_ms * sizeof(double)))) return rc;   // per-ms magnitudes of the candidates
-    double* d_partial = (double*)ctx->scratch[9];
-    const size_t profile_bytes = (size_t)n_states * 2 * ctx->n * sizeof(double);
-    const void* profiles_before = ctx->scratch[7];
-    if ((rc = ensure_scratch(ctx, 7, profile_bytes))) return rc;
-    double* d_profiles = (double*)ctx->scratch[7];
-    (void)profiles_before;   // float64 profile rows of the (rare) cross-level near-ties: written whole by acq_exact_profile_kernel
-    double* d_refined = (double*)ctx->scratch[3];
-    AcqSearchState* d_states = (AcqSearchState*)ctx->scratch[4];
-    gyp_cell_desc* d_cells = (gyp_cell_desc*)ctx->scratch[1];
-    gyp_cell* d_out = (gyp_cell*)ctx->scratch[2];
+    double *d_partial = sc.partial64.get(), *d_profiles = sc.acq_profiles.get(), *d_refined = sc.acq_refined.get();
+    AcqSearchState* d_states = sc.acq_states.get();
+    gyp_cell_desc* d_cells = sc.acq_cells.get();
+    gyp_cell* d_out = sc.acq_out.get();
     // Shared forward transforms (K == 8, the pipelined path): the first three levels of a scan put every satellite of a stream on the
     // same Doppler bins -- range(-7000, 7000, 700) for all at level 1, multiples of 350 and 175 Hz at levels 2 and 3 -- so the
     // wipe-off and the 8 forward transforms of a (stream, bin) unit are run once (corr_cells_pipe_kernel MODE 1) and read back by
@@ -1056,13 +1105,10 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         const size_t want = std::min<size_t>((size_t)1 << 30, (size_t)n_streams * 3 * kMaxBins * unit_bytes);
         units.max_units = (int32_t)std::min<size_t>(n_cells, want / unit_bytes);
         if (units.max_units > 0) {
-            if ((rc = ensure_scratch(ctx, 11, (size_t)units.max_units * unit_bytes))) return rc;
-            if ((rc = ensure_scratch(ctx, 12, ((size_t)units.max_units + 2 * n_cells + 4) * sizeof(int32_t)))) return rc;
-            d_spectra = (cf*)ctx->scratch[11];
-            units.unit_cell = (int32_t*)ctx->scratch[12];
-            units.sh_cell = units.unit_cell + units.max_units;
-            units.sh_unit = units.sh_cell + n_cells;
-            units.counts = units.sh_unit + n_cells;
+            HIP_TRY(ctx, sc.acq_spectra.reserve((size_t)units.max_units * (unit_bytes / sizeof(cf)), Slack::grow, ctx->stream));
+            HIP_TRY(ctx, sc.acq_units.reserve(acq_units_layout(nullptr, (size_t)units.max_units, n_cells, &units), Slack::grow, ctx->stream));
+            d_spectra = sc.acq_spectra.get();
+            acq_units_layout(sc.acq_units.get(), (size_t)units.max_units, n_cells, &units);
         }
     }
     const int tpb = 64, nblk = (n_states + tpb - 1) / tpb;
@@ -1070,7 +1116,7 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         AcqSatList sl;
         for (int i = 0; i < 32; ++i) sl.id[i] = i < n_sats ? sat_ids_host[i] : 0;
         hipLaunchKernelGGL(acq_init_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, n_sats, sl, center0, spread0,
-                           ctx->d_acq_witness);   // acquisition.py:78-79
+                           ctx->acq_witness.get());   // acquisition.py:78-79
     }
     int level = 0;
     for (double spread = spread0; single_level ? spread == spread0 : spread >= ctx->params.acq_min_spread_hz; spread /= 2.0, ++level) {  // acquisition.py:81,89
@@ -1079,7 +1125,7 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         const bool shared = d_spectra && spread * 4.0 >= ctx->params.acq_initial_spread_hz;   // levels 1-3 of a scan
         if (shared) {
             hipLaunchKernelGGL(acq_compact_units_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells,
-                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units, ctx->d_acq_witness, level);
+                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units, ctx->acq_witness.get(), level);
             CellsParams pu = cells_params(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, d_out, nullptr, units.unit_cell,
                                           units.counts);
             pu.prof = nullptr;
@@ -1091,7 +1137,7 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
             if ((rc = launch_cells_shared(ctx, pu, pc))) return rc;
         } else {
             hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand,
-                               ctx->d_acq_witness, level);
+                               ctx->acq_witness.get(), level);
         }
         rc = correlate_cells_listed(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, GYP_NON_COHERENT, d_out, nullptr,
                                     d_order, d_n_active);
@@ -1108,7 +1154,7 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         rp.cells = d_cells;
         rp.out = d_out;
         rp.refined = d_refined;
-        rp.chips = ctx->d_chips;
+        rp.chips = ctx->codes.chips.get();
         rp.inv_fs = 1.0 / (double)ctx->fs;
         rp.cand = d_cand; rp.n_cand = d_n_cand; rp.partial = d_partial;
         // normally one or two candidates per (stream, satellite): 2 n_states slots x n_ms blocks, strided beyond that
@@ -1118,7 +1164,7 @@ static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         // cross-level near-ties in strength: float64 profiles for the (few) pending pairs, else immediate exits
         ExactParams ep;
         ep.iq = rp.iq; ep.stream_stride = stream_stride_samples; ep.n_ms = n_ms; ep.n_per_ms = ctx->n; ep.k = ctx->k; ep.n_states = n_states;
-        ep.states = d_states; ep.ones = ctx->d_ones; ep.inv_fs = rp.inv_fs; ep.profiles = d_profiles;
+        ep.states = d_states; ep.ones = ctx->codes.ones.get(); ep.inv_fs = rp.inv_fs; ep.profiles = d_profiles;
         ep.pend = d_pend; ep.n_pend = d_n_pend;
         // (pending pairs are rare -- about one acquisition in a hundred: a short z grid whose blocks walk the states)
         hipLaunchKernelGGL(acq_exact_profile_kernel, dim3((unsigned)(ctx->k * kExactSplit), 2, (unsigned)std::min(n_states, 32)), dim3(1024), 0, ctx->stream, ep);
@@ -1156,8 +1202,8 @@ static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
         if (gyp_set_stream_format(h, ctx->fs, ctx->n) != GYP_OK) return nullptr;
     h->params = ctx->params;
     // the helper runs under the caller's switches (it never read an environment of its own)
-    h->no_pipe = ctx->no_pipe; h->no_shared_fwd = ctx->no_shared_fwd; h->no_acq_shared_fwd = ctx->no_acq_shared_fwd; h->symbol_tau = ctx->symbol_tau; h->cells_cu_reserve = ctx->cells_cu_reserve;
-    h->track_chunk_ms = ctx->track_chunk_ms; h->no_spec = ctx->no_spec;
+    for (const DebugSwitch& k : kDebugSwitches)
+        if (k.inherited) k.set(*h, k.get(*ctx));
     return h;
 }
 
@@ -1208,49 +1254,42 @@ int gyp_search_level_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, i
     return acquire_search(ctx, iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, true, out_dev);
 }
 
+}   // extern "C"
+// gyp_search_level / gyp_acquire: the samples staged, `search(iq_dev, out_dev)`, the results copied back
+template <typename F>
+static int search_staged(gyp_ctx* ctx, const char* who, const float* iq_host, int32_t n_streams, int32_t n_ms, int32_t n_sats,
+                         gyp_acq_result* out_host, F&& search) {
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad argument");
+    Scratch& sc = ctx->scratch;
+    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_acq_result);
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    if (const int rc = search(sc.stage_iq.get(), (gyp_acq_result*)sc.stage_out.get())) return rc;
+    return stage_back(ctx, out_host, out_bytes);
+}
+extern "C" {
+
 int gyp_search_level(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                      int32_t n_sats, double center_hz, double spread_hz, gyp_acq_result* out_host) {
-    if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_search_level: bad argument");
-    const size_t iq_bytes = (size_t)n_streams * n_ms * ctx->n * 8;
-    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_acq_result);
-    int rc;
-    if ((rc = ensure_scratch(ctx, 0, iq_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 5, out_bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_search_level_dev(ctx, (const float*)ctx->scratch[0], n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats,
-                              center_hz, spread_hz, (gyp_acq_result*)ctx->scratch[5]);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch[5], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    return search_staged(ctx, "gyp_search_level", iq_host, n_streams, n_ms, n_sats, out_host, [&](const float* iq_dev, gyp_acq_result* out_dev) {
+        return gyp_search_level_dev(ctx, iq_dev, n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, out_dev);
+    });
 }
 
 int gyp_acquire(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                 int32_t n_sats, gyp_acq_result* out_host) {
-    if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_acquire: bad argument");
-    const size_t iq_bytes = (size_t)n_streams * n_ms * ctx->n * 8;
-    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_acq_result);
-    int rc;
-    if ((rc = ensure_scratch(ctx, 0, iq_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 5, out_bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_acquire_dev(ctx, (const float*)ctx->scratch[0], n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats,
-                         (gyp_acq_result*)ctx->scratch[5]);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch[5], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    return search_staged(ctx, "gyp_acquire", iq_host, n_streams, n_ms, n_sats, out_host, [&](const float* iq_dev, gyp_acq_result* out_dev) {
+        return gyp_acquire_dev(ctx, iq_dev, n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, out_dev);
+    });
 }
 
 // ---------------------------------------------------------------- tracking: explicit millisecond ----------
 int gyp_track_step_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, const double* start_time_dev,
                        const gyp_chan_in* chans_dev, int32_t n_chan, gyp_chan_out* out_dev, float* profile_out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !start_time_dev || !chans_dev || !out_dev || n_chan < 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_track_step_dev: bad argument");
     if (n_chan == 0) return GYP_OK;
     TrackStepParams p;
@@ -1261,63 +1300,49 @@ int gyp_track_step_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_
     p.n_chan = n_chan;
     p.out = out_dev;
     p.profile_out = profile_out_dev;
-    p.replica_table = ctx->d_replicas;
-    p.tw_tables = ctx->d_tw;
+    p.replica_table = ctx->codes.replicas.get();
+    p.tw_tables = ctx->codes.tw.get();
     p.inv_fs = 1.0 / (double)ctx->fs;
-    p.trans = ctx->d_trans;
-    p.n_trans = ctx->d_ntrans;
-    p.chipf = ctx->d_chipf;
+    p.trans = ctx->codes.trans.get();
+    p.n_trans = ctx->codes.ntrans.get();
+    p.chipf = ctx->codes.chipf.get();
     return launch_track_step(ctx, p);
 }
 
 int gyp_track_step(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, const double* start_time_host,
                    const gyp_chan_in* chans_host, int32_t n_chan, gyp_chan_out* out_host, float* profile_out_host) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!iq_host || !start_time_host || !chans_host || !out_host || n_streams <= 0 || n_chan < 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_track_step: bad argument");
     for (int i = 0; i < n_chan; ++i)
         if (chans_host[i].stream < 0 || chans_host[i].stream >= n_streams || chans_host[i].sat_id < 1 || chans_host[i].sat_id > 32)
             return fail(ctx, GYP_E_BAD_ARG, "gyp_track_step: channel descriptor out of range");
     if (n_chan == 0) return GYP_OK;
-    const size_t iq_bytes = (size_t)n_streams * ctx->n * 8;
-    int rc;
-    if ((rc = ensure_scratch(ctx, 0, iq_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 1, (size_t)n_chan * sizeof(gyp_chan_in)))) return rc;
-    if ((rc = ensure_scratch(ctx, 2, (size_t)n_chan * sizeof(gyp_chan_out)))) return rc;
-    if ((rc = ensure_scratch(ctx, 4, (size_t)n_streams * sizeof(double)))) return rc;
-    if (profile_out_host && (rc = ensure_scratch(ctx, 3, (size_t)n_chan * ctx->n * 4))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], chans_host, (size_t)n_chan * sizeof(gyp_chan_in), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4], start_time_host, (size_t)n_streams * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_track_step_dev(ctx, (const float*)ctx->scratch[0], ctx->n, (const double*)ctx->scratch[4], (const gyp_chan_in*)ctx->scratch[1],
-                            n_chan, (gyp_chan_out*)ctx->scratch[2], profile_out_host ? (float*)ctx->scratch[3] : nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch[2], (size_t)n_chan * sizeof(gyp_chan_out), hipMemcpyDeviceToHost, ctx->stream));
-    if (profile_out_host)
-        HIP_TRY(ctx, hipMemcpyAsync(profile_out_host, ctx->scratch[3], (size_t)n_chan * ctx->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    Scratch& sc = ctx->scratch;
+    const size_t out_bytes = (size_t)n_chan * sizeof(gyp_chan_out), n_prof = profile_out_host ? (size_t)n_chan * ctx->n : 0;
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.stage_profile.reserve(n_prof, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, 1), ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_in, as_bytes(chans_host), (size_t)n_chan * sizeof(gyp_chan_in), ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_times, start_time_host, (size_t)n_streams, ctx->stream));
+    if (const int rc = gyp_track_step_dev(ctx, sc.stage_iq.get(), ctx->n, sc.stage_times.get(), (const gyp_chan_in*)sc.stage_in.get(), n_chan,
+                                          (gyp_chan_out*)sc.stage_out.get(), profile_out_host ? sc.stage_profile.get() : nullptr))
+        return rc;
+    return stage_back(ctx, out_host, out_bytes, profile_out_host, n_prof);
 }
 
 // ---------------------------------------------------------------- tracking: device-resident loops --------
 int gyp_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_chan, gyp_bank** out) {
     if (!ctx || !out) return GYP_E_BAD_ARG;
     *out = nullptr;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!chans_host || n_chan <= 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_create: bad argument");
     std::vector<ChanState> init((size_t)n_chan);
     for (int i = 0; i < n_chan; ++i) {
         if (chans_host[i].stream < 0 || chans_host[i].sat_id < 1 || chans_host[i].sat_id > 32)
             return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_create: channel descriptor out of range");
-        ChanState& s = init[i];
-        std::memset(&s, 0, sizeof(s));
-        s.stream = chans_host[i].stream;
-        s.sat_id = chans_host[i].sat_id;
-        s.doppler = chans_host[i].doppler_hz;
-        s.carrier_phase = chans_host[i].carrier_phase;
-        s.code_phase = chans_host[i].code_phase;
-        s.dll_phase = (double)chans_host[i].code_phase;  // tracker.py:224
+        init[i] = fresh_chan_state(chans_host[i]);
     }
     gyp_bank* b = new gyp_bank();
     b->ctx = ctx;
@@ -1325,10 +1350,9 @@ int gyp_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_cha
     b->fs = ctx->fs;
     b->n = ctx->n;
     for (int i = 0; i < n_chan; ++i) b->stream_of.push_back(chans_host[i].stream);
-    hipError_t e = hipMalloc((void**)&b->d_states, init.size() * sizeof(ChanState));
-    if (e == hipSuccess) e = hipMemcpy(b->d_states, init.data(), init.size() * sizeof(ChanState), hipMemcpyHostToDevice);
+    hipError_t e = b->states.reserve(init.size(), Slack::exact);
+    if (e == hipSuccess) e = hipMemcpy(b->states.get(), init.data(), init.size() * sizeof(ChanState), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (b->d_states) (void)hipFree(b->d_states);
         delete b;
         return fail(ctx, GYP_E_HIP, std::string("gyp_bank_create: ") + hipGetErrorString(e));
     }
@@ -1339,27 +1363,8 @@ int gyp_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_cha
 void gyp_bank_destroy(gyp_bank* bank) {
     if (!bank) return;
     (void)hipStreamSynchronize(bank->ctx->stream);
-    if (bank->d_states) (void)hipFree(bank->d_states);
-    if (bank->d_ckpt) (void)hipFree(bank->d_ckpt);
-    if (bank->d_spec) (void)hipFree(bank->d_spec);
-    if (bank->d_disc) (void)hipFree(bank->d_disc);
-    if (bank->d_dllx) (void)hipFree(bank->d_dllx);
-    if (bank->d_groups) (void)hipFree(bank->d_groups);
-    if (bank->d_bad) (void)hipFree(bank->d_bad);
-    if (bank->d_bad_from) (void)hipFree(bank->d_bad_from);
-    if (bank->d_hist) (void)hipFree(bank->d_hist);
-    if (bank->d_ctl) (void)hipFree(bank->d_ctl);
-    if (bank->d_trk) (void)hipFree(bank->d_trk);
-    if (bank->d_fail) (void)hipFree(bank->d_fail);
-    if (bank->d_redo_stats) (void)hipFree(bank->d_redo_stats);
-    for (auto& e : bank->ev_vring) if (e) (void)hipEventDestroy(e);
-    if (bank->d_dbg) (void)hipFree(bank->d_dbg);
-    if (bank->d_prof_tail) (void)hipFree(bank->d_prof_tail);
-    if (bank->d_prof_delta) (void)hipFree(bank->d_prof_delta);
-    if (bank->verify_stream) { (void)hipStreamSynchronize(bank->verify_stream); (void)hipStreamDestroy(bank->verify_stream); }
-    if (bank->ev_spec) (void)hipEventDestroy(bank->ev_spec);
-    if (bank->ev_verify) (void)hipEventDestroy(bank->ev_verify);
-    delete bank;
+    if (bank->verify_stream.get()) (void)hipStreamSynchronize(bank->verify_stream.get());
+    delete bank;   // the members release what they hold: buffers and events first, the verify stream last
 }
 
 int gyp_bank_size(const gyp_bank* bank) { return bank ? bank->n_chan : GYP_E_BAD_ARG; }
@@ -1369,17 +1374,9 @@ int gyp_bank_set_channel(gyp_bank* bank, int32_t index, const gyp_chan_init* in)
     gyp_ctx* ctx = bank->ctx;
     if (!in || index < 0 || index >= bank->n_chan || in->stream < 0 || in->sat_id < 1 || in->sat_id > 32)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_set_channel: bad argument");
-    std::vector<ChanState> one(1);
-    ChanState& s = one[0];
-    std::memset(&s, 0, sizeof(s));
-    s.stream = in->stream;
-    s.sat_id = in->sat_id;
-    s.doppler = in->doppler_hz;
-    s.carrier_phase = in->carrier_phase;
-    s.code_phase = in->code_phase;
-    s.dll_phase = (double)in->code_phase;  // tracker.py:224
+    const ChanState s = fresh_chan_state(*in);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(bank->d_states + index, &s, sizeof(ChanState), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(bank->states.get() + index, &s, sizeof(ChanState), hipMemcpyHostToDevice));
     bank->stream_of[index] = in->stream;
     return GYP_OK;
 }
@@ -1390,7 +1387,7 @@ int gyp_bank_drop_channel(gyp_bank* bank, int32_t index) {
     if (index < 0 || index >= bank->n_chan) return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_drop_channel: index out of range");
     const int32_t one = 1;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(reinterpret_cast<char*>(bank->d_states + index) + offsetof(ChanState, lost), &one, sizeof(one),
+    HIP_TRY(ctx, hipMemcpy(reinterpret_cast<char*>(bank->states.get() + index) + offsetof(ChanState, lost), &one, sizeof(one),
                            hipMemcpyHostToDevice));
     return GYP_OK;
 }
@@ -1398,29 +1395,18 @@ int gyp_bank_drop_channel(gyp_bank* bank, int32_t index) {
 // Buffers of the exact code loop (hand-over records, float64 discriminators, the loop's state), any tracking path.
 static int ensure_dll_buffers(gyp_bank* bank, size_t n_rec) {
     gyp_ctx* ctx = bank->ctx;
-    if (!bank->d_dllx) HIP_TRY(ctx, hipMalloc((void**)&bank->d_dllx, (size_t)bank->n_chan * sizeof(DllExact)));
-    if (!bank->d_groups) HIP_TRY(ctx, hipMalloc((void**)&bank->d_groups, ((size_t)bank->n_chan + 1) * sizeof(ExactGroup)));
-    if (bank->spec_cap < n_rec) {
-        if (bank->d_spec) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (bank->verify_stream) HIP_TRY(ctx, hipStreamSynchronize(bank->verify_stream));
-            HIP_TRY(ctx, hipFree(bank->d_spec));
-            HIP_TRY(ctx, hipFree(bank->d_disc));
-            bank->d_spec = nullptr;
-            bank->d_disc = nullptr;
-            bank->spec_cap = 0;
-        }
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_spec, n_rec * sizeof(SpecIn)));
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_disc, n_rec * sizeof(double)));
-        bank->spec_cap = n_rec;
-    }
+    const hipStream_t s0 = ctx->stream, s1 = bank->verify_stream.get();
+    HIP_TRY(ctx, bank->dllx.reserve((size_t)bank->n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->groups.reserve((size_t)bank->n_chan + 1, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->spec.reserve(n_rec, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->disc.reserve(n_rec, Slack::exact, s0, s1));
     return GYP_OK;
 }
 static DllExactParams dll_exact_params(gyp_bank* bank, const TrackBlockParams& p) {
     gyp_ctx* ctx = bank->ctx;
     DllExactParams x;
     x.iq = p.iq; x.stream_stride = p.stream_stride; x.n_ms = p.n_ms; x.ms_begin = 0; x.ms_end = p.n_ms; x.start_time = p.start_time;
-    x.states = bank->d_states; x.n_chan = bank->n_chan; x.spec = bank->d_spec; x.disc_out = bank->d_disc; x.chipf = ctx->d_chipf;
+    x.states = bank->states.get(); x.n_chan = bank->n_chan; x.spec = bank->spec.get(); x.disc_out = bank->disc.get(); x.chipf = ctx->codes.chipf.get();
     x.inv_fs = p.inv_fs; x.only_if = nullptr; x.from_sub = nullptr; x.sub = SubLayout::none(); x.trk_round = nullptr;
     return x;
 }
@@ -1428,11 +1414,11 @@ static DllScanParams dll_scan_params(gyp_bank* bank, const TrackBlockParams& p) 
     gyp_ctx* ctx = bank->ctx;
     DllScanParams d;
     d.iq = p.iq; d.stream_stride = p.stream_stride; d.n_ms = p.n_ms; d.ms_begin = 0; d.ms_end = p.n_ms; d.start_time = p.start_time;
-    d.states = bank->d_states; d.ckpt = nullptr; d.n_chan = bank->n_chan; d.spec = bank->d_spec; d.disc = bank->d_disc;
-    d.rec_out = p.rec_out; d.exact = bank->d_dllx; d.bad = nullptr; d.only_bad = 0; d.chipf = ctx->d_chipf;
+    d.states = bank->states.get(); d.ckpt = nullptr; d.n_chan = bank->n_chan; d.spec = bank->spec.get(); d.disc = bank->disc.get();
+    d.rec_out = p.rec_out; d.exact = bank->dllx.get(); d.bad = nullptr; d.only_bad = 0; d.chipf = ctx->codes.chipf.get();
     d.inv_fs = p.inv_fs; d.dll_gain = p.lp.dll_gain; d.dll_modulus = p.lp.dll_modulus; d.n_samples = p.lp.n_samples;
     d.first = 1; d.final = 1; d.from_sub = nullptr; d.sub = SubLayout::none(); d.hist_out = nullptr;
-    d.prof_delta = p.prof_tail ? bank->d_prof_delta : nullptr; d.prof_from = p.prof_from; d.prof_depth = p.prof_depth;
+    d.prof_delta = p.prof_tail ? bank->prof_delta.get() : nullptr; d.prof_from = p.prof_from; d.prof_depth = p.prof_depth;
     d.symbol_tau = ctx->symbol_tau;
     d.trk_round = nullptr; d.hist = nullptr;
     return d;
@@ -1446,11 +1432,11 @@ static int track_block_throughput(gyp_bank* bank, TrackBlockParams p, const int3
     int rc;
     if ((rc = ensure_dll_buffers(bank, (size_t)bank->n_chan * p.n_ms))) return rc;
     p.ms_begin = 0; p.ms_end = p.n_ms;
-    p.spec_out = bank->d_spec; p.exact0 = bank->d_dllx; p.dbg = nullptr;
+    p.spec_out = bank->spec.get(); p.exact0 = bank->dllx.get(); p.dbg = nullptr;
     p.only_if = only_if; p.restore_from = restore_from;
     p.from_sub = from_sub; p.exact_hist = exact_hist; p.sub = sub;
     const bool timed = ctx->time_track && !only_if;
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[0], ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[0].get(), ctx->stream));
     // The channels of a stream are independent workgroups that read the same samples; nothing keeps them within an L2's worth
     // (~11 ms of an XCD's resident streams) of each other, and over a 1000-ms launch they drift apart: FETCH_SIZE per
     // millisecond is 1.24x the algorithmic bytes for launches of <= 250 ms and 2.6x for 1000 ms (profiles/r03_drift.txt).  A
@@ -1469,22 +1455,22 @@ static int track_block_throughput(gyp_bank* bank, TrackBlockParams p, const int3
         if (b0 > 0) q.exact0 = nullptr;          // the code loop's state before the BLOCK is what dll_scan_kernel starts from
         if ((rc = launch_track_block(ctx, q, 0))) return rc;
     }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[1], ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[1].get(), ctx->stream));
     DllExactParams x = dll_exact_params(bank, p);
     x.only_if = only_if; x.from_sub = from_sub; x.sub = sub;
     bank->last_n_ms = p.n_ms;
     if (!only_if && !from_sub && exact_shared_applies(ctx, bank->n_chan)) {
-        if ((rc = launch_dll_exact_shared(ctx, x, bank->d_groups, ctx->stream))) return rc;
+        if ((rc = launch_dll_exact_shared(ctx, x, bank->groups.get(), ctx->stream))) return rc;
         ctx->last_exact_path = 2;
     } else {
         if ((rc = launch_dll_exact(ctx, x, ctx->stream))) return rc;
         if (!only_if && !from_sub) ctx->last_exact_path = ctx->k <= 8 ? 1 : 3;
     }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[2], ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[2].get(), ctx->stream));
     DllScanParams d = dll_scan_params(bank, p);
     d.bad = only_if; d.only_bad = only_if ? 1 : 0; d.from_sub = from_sub; d.sub = sub;
     if ((rc = launch_dll_scan(ctx, d, ctx->stream))) return rc;
-    if (timed) { HIP_TRY(ctx, hipEventRecord(ctx->ev_track[3], ctx->stream)); ctx->track_timed = true; }
+    if (timed) { HIP_TRY(ctx, hipEventRecord(ctx->ev_track[3].get(), ctx->stream)); ctx->track_timed = true; }
     return GYP_OK;
 }
 
@@ -1530,54 +1516,40 @@ static SubLayout spec_layout(int n_ms, int n_sub) {
 }
 static int ensure_spec_buffers(gyp_bank* bank, int n_sub, int rounds) {
     gyp_ctx* ctx = bank->ctx;
-    // each resource under its own check: a HIP failure part way through leaves what exists in place for the retry (and for gyp_bank_destroy)
-    if (!bank->d_bad) HIP_TRY(ctx, hipMalloc((void**)&bank->d_bad, (size_t)bank->n_chan * sizeof(int32_t)));
-    if (!bank->d_bad_from) HIP_TRY(ctx, hipMalloc((void**)&bank->d_bad_from, (size_t)bank->n_chan * sizeof(int32_t)));
-    if (!bank->d_ctl) HIP_TRY(ctx, hipMalloc((void**)&bank->d_ctl, (size_t)bank->n_chan * sizeof(SpecCtl)));
-    if (!bank->d_redo_stats) {
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_redo_stats, 4 * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMemset(bank->d_redo_stats, 0, 4 * sizeof(int32_t)));
+    const size_t n_chan = (size_t)bank->n_chan;
+    // each resource under its own check: a HIP failure part way through leaves what exists in place for the retry
+    HIP_TRY(ctx, bank->verify_stream.create(hipStreamNonBlocking));
+    const hipStream_t s0 = ctx->stream, s1 = bank->verify_stream.get();
+    HIP_TRY(ctx, bank->bad.reserve(n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->bad_from.reserve(n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->ctl.reserve(n_chan, Slack::exact, s0, s1));
+    if (!bank->redo_stats.get()) {
+        HIP_TRY(ctx, bank->redo_stats.reserve(4, Slack::exact));
+        HIP_TRY(ctx, hipMemset(bank->redo_stats.get(), 0, 4 * sizeof(int32_t)));
     }
-    if (!bank->verify_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&bank->verify_stream, hipStreamNonBlocking));
-    if (!bank->ev_spec) HIP_TRY(ctx, hipEventCreateWithFlags(&bank->ev_spec, hipEventDisableTiming));
-    if (!bank->ev_verify) HIP_TRY(ctx, hipEventCreateWithFlags(&bank->ev_verify, hipEventDisableTiming));
-    for (auto& e : bank->ev_vring)
-        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (bank->ckpt_cap < n_sub) {   // state checkpoints (18 KB per channel and sub-block): as many as this block uses
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(bank->verify_stream));
-        if (bank->d_ckpt) { HIP_TRY(ctx, hipFree(bank->d_ckpt)); bank->d_ckpt = nullptr; }
-        if (bank->d_hist) { HIP_TRY(ctx, hipFree(bank->d_hist)); bank->d_hist = nullptr; }
-        bank->ckpt_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_ckpt, (size_t)n_sub * bank->n_chan * sizeof(ChanState)));
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_hist, (size_t)(n_sub + 1) * bank->n_chan * sizeof(DllExact)));
-        bank->ckpt_cap = n_sub;
-    }
-    if (bank->rounds_cap < rounds) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(bank->verify_stream));
-        if (bank->d_trk) { HIP_TRY(ctx, hipFree(bank->d_trk)); bank->d_trk = nullptr; }
-        if (bank->d_fail) { HIP_TRY(ctx, hipFree(bank->d_fail)); bank->d_fail = nullptr; }
-        bank->rounds_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_trk, (size_t)rounds * bank->n_chan * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&bank->d_fail, (size_t)rounds * bank->n_chan * sizeof(int32_t)));
-        bank->rounds_cap = rounds;
-    }
+    HIP_TRY(ctx, bank->ev_spec.create(hipEventDisableTiming));
+    HIP_TRY(ctx, bank->ev_verify.create(hipEventDisableTiming));
+    for (Event& e : bank->ev_vring) HIP_TRY(ctx, e.create(hipEventDisableTiming));
+    // state checkpoints and code-loop history: as many sub-blocks as this block uses; the round tables: as many rounds
+    HIP_TRY(ctx, bank->ckpt.reserve((size_t)n_sub * n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->hist.reserve((size_t)(n_sub + 1) * n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->trk.reserve((size_t)rounds * n_chan, Slack::exact, s0, s1));
+    HIP_TRY(ctx, bank->fail.reserve((size_t)rounds * n_chan, Slack::exact, s0, s1));
     return GYP_OK;
 }
 static TrackVerifyParams verify_params(gyp_bank* bank, const TrackBlockParams& p) {
     gyp_ctx* ctx = bank->ctx;
     TrackVerifyParams v;
     v.iq = p.iq; v.stream_stride = p.stream_stride; v.n_ms = p.n_ms; v.ms_begin = 0; v.ms_end = p.n_ms; v.start_time = p.start_time;
-    v.states = bank->d_states; v.n_chan = bank->n_chan; v.spec = bank->d_spec; v.rec_out = p.rec_out; v.bad = bank->d_bad;
-    v.bad_from = bank->d_bad_from; v.sub_index = 0; v.force_fail_ms = ctx->spec_fail_at;
-    v.replica_table = ctx->d_replicas; v.tw_tables = ctx->d_tw; v.inv_fs = p.inv_fs; v.tie_tol = 4e-6f;
+    v.states = bank->states.get(); v.n_chan = bank->n_chan; v.spec = bank->spec.get(); v.rec_out = p.rec_out; v.bad = bank->bad.get();
+    v.bad_from = bank->bad_from.get(); v.sub_index = 0; v.force_fail_ms = ctx->spec_fail_at;
+    v.replica_table = ctx->codes.replicas.get(); v.tw_tables = ctx->codes.tw.get(); v.inv_fs = p.inv_fs; v.tie_tol = 4e-6f;
     v.trk_round = nullptr; v.fail_round = nullptr; v.sub = SubLayout::none();
     return v;
 }
 static int spec_prepare(gyp_bank* bank, TrackBlockParams& p, size_t n_rec) {
     gyp_ctx* ctx = bank->ctx;
-    p.spec_out = bank->d_spec;
+    p.spec_out = bank->spec.get();
     p.exact0 = nullptr;
     p.from_sub = nullptr; p.exact_hist = nullptr; p.sub = SubLayout::none();
     // gyp_params::spec_confidence_kappa is quoted for 8184 lags: the chance that some noise lag beats a peak of kappa x the sample
@@ -1591,12 +1563,8 @@ static int spec_prepare(gyp_bank* bank, TrackBlockParams& p, size_t n_rec) {
     const double kappa_rate = std::log((double)ctx->n / 8184.0) + (ctx->k == 2 ? -5.0 : 0.0);
     p.spec_kappa = (float)std::max(0.0, ctx->params.spec_confidence_kappa + (ctx->params.spec_confidence_kappa > 0.0 ? kappa_rate : 0.0));
     if (ctx->spec_debug) {
-        if (bank->dbg_cap < n_rec * 20) {
-            if (bank->d_dbg) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); HIP_TRY(ctx, hipFree(bank->d_dbg)); }
-            HIP_TRY(ctx, hipMalloc((void**)&bank->d_dbg, n_rec * 20 * sizeof(float)));
-            bank->dbg_cap = n_rec * 20;
-        }
-        p.dbg = bank->d_dbg;
+        HIP_TRY(ctx, bank->dbg.reserve(n_rec * 20, Slack::exact, ctx->stream));
+        p.dbg = bank->dbg.get();
     }
     return GYP_OK;
 }
@@ -1608,7 +1576,7 @@ struct VerifyStreamGuard {
     bool armed = true;
     ~VerifyStreamGuard() {
         if (!armed) return;
-        (void)hipStreamSynchronize(bank->verify_stream);
+        (void)hipStreamSynchronize(bank->verify_stream.get());
         (void)hipStreamSynchronize(bank->ctx->stream);
     }
 };
@@ -1623,43 +1591,43 @@ static int track_block_speculative_rerun(gyp_bank* bank, TrackBlockParams p) {
     const int n_sub = lay.n;
     if ((rc = ensure_spec_buffers(bank, n_sub, 1))) return rc;
     if ((rc = ensure_dll_buffers(bank, n_rec))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(bank->d_bad, 0, (size_t)bank->n_chan * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->d_bad_from, 0x7fffffff, (size_t)bank->n_chan, ctx->stream));
-    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->d_redo_stats, n_sub, n_sub, 0, 0);
+    HIP_TRY(ctx, hipMemsetAsync(bank->bad.get(), 0, (size_t)bank->n_chan * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->bad_from.get(), 0x7fffffff, (size_t)bank->n_chan, ctx->stream));
+    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->redo_stats.get(), n_sub, n_sub, 0, 0);
     if ((rc = spec_prepare(bank, p, n_rec))) return rc;
     VerifyStreamGuard join_on_error{bank};
     TrackVerifyParams v = verify_params(bank, p);
     DllExactParams x = dll_exact_params(bank, p);
     DllScanParams d = dll_scan_params(bank, p);
-    d.ckpt = bank->d_ckpt; d.bad = bank->d_bad; d.only_bad = 0;
+    d.ckpt = bank->ckpt.get(); d.bad = bank->bad.get(); d.only_bad = 0;
     for (int j = 0; j < n_sub; ++j) {
         const int b0 = lay.begin(j);
-        HIP_TRY(ctx, hipMemcpyAsync(bank->d_ckpt + (size_t)j * bank->n_chan, bank->d_states, (size_t)bank->n_chan * sizeof(ChanState),
+        HIP_TRY(ctx, hipMemcpyAsync(bank->ckpt.get() + (size_t)j * bank->n_chan, bank->states.get(), (size_t)bank->n_chan * sizeof(ChanState),
                                     hipMemcpyDeviceToDevice, ctx->stream));
         p.ms_begin = b0;
         p.ms_end = lay.end(j, p.n_ms);
         if ((rc = launch_track_block(ctx, p, 2))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_spec, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream, bank->ev_spec, 0));
+        HIP_TRY(ctx, hipEventRecord(bank->ev_spec.get(), ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream.get(), bank->ev_spec.get(), 0));
         v.ms_begin = p.ms_begin;
         v.ms_end = p.ms_end;
         v.sub_index = j;
-        if ((rc = launch_track_verify(ctx, v, bank->verify_stream))) return rc;
+        if ((rc = launch_track_verify(ctx, v, bank->verify_stream.get()))) return rc;
         x.ms_begin = p.ms_begin; x.ms_end = p.ms_end;
-        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream))) return rc;
+        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream.get()))) return rc;
         d.ms_begin = p.ms_begin; d.ms_end = p.ms_end; d.first = b0 == 0 ? 1 : 0; d.final = p.ms_end == p.n_ms ? 1 : 0;
-        d.hist_out = p.ms_end < p.n_ms ? bank->d_hist + (size_t)(j + 1) * bank->n_chan : nullptr;
-        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream))) return rc;
+        d.hist_out = p.ms_end < p.n_ms ? bank->hist.get() + (size_t)(j + 1) * bank->n_chan : nullptr;
+        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream.get()))) return rc;
     }
-    HIP_TRY(ctx, hipEventRecord(bank->ev_verify, bank->verify_stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify, 0));
+    HIP_TRY(ctx, hipEventRecord(bank->ev_verify.get(), bank->verify_stream.get()));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify.get(), 0));
     join_on_error.armed = false;
     // gyp_debug_spec_redo_read's out4[3]: how many channels the transform kernel finishes (the round protocol's spec_finalize_kernel counts its own)
-    hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(64), 0, ctx->stream, bank->d_bad, bank->n_chan, bank->d_redo_stats + 3);
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(64), 0, ctx->stream, bank->bad.get(), bank->n_chan, bank->redo_stats.get() + 3);
     // channels whose window maximum was not the global one somewhere (any count is handled): again from the checkpoint of the
     // sub-block in which that happened, through the transform kernel, their code loop re-integrated behind it
     p.dbg = nullptr;
-    return track_block_throughput(bank, p, bank->d_bad, bank->d_ckpt, bank->d_bad_from, bank->d_hist, lay);
+    return track_block_throughput(bank, p, bank->bad.get(), bank->ckpt.get(), bank->bad_from.get(), bank->hist.get(), lay);
 }
 
 // Speculative block tracking (8.184 / 2.046 Msps, at most one channel per CU) under the round protocol (SpecCtl,
@@ -1683,50 +1651,50 @@ static int track_block_speculative(gyp_bank* bank, TrackBlockParams p) {
     int rc;
     if ((rc = ensure_spec_buffers(bank, n_sub_used, rounds))) return rc;
     if ((rc = ensure_dll_buffers(bank, n_rec))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(bank->d_ctl, 0, (size_t)bank->n_chan * sizeof(SpecCtl), ctx->stream));   // cursor 0, nothing forced (rb_round 0 only ever matters for R = 1, which consults nothing)
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->d_fail, 0x7fffffff, (size_t)rounds * bank->n_chan, ctx->stream));
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->d_trk, 0xffffffff, (size_t)rounds * bank->n_chan, ctx->stream));
-    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->d_redo_stats, n_sub_used, rounds, 0, 0);
+    HIP_TRY(ctx, hipMemsetAsync(bank->ctl.get(), 0, (size_t)bank->n_chan * sizeof(SpecCtl), ctx->stream));   // cursor 0, nothing forced (rb_round 0 only ever matters for R = 1, which consults nothing)
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->fail.get(), 0x7fffffff, (size_t)rounds * bank->n_chan, ctx->stream));
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->trk.get(), 0xffffffff, (size_t)rounds * bank->n_chan, ctx->stream));
+    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->redo_stats.get(), n_sub_used, rounds, 0, 0);
     if ((rc = spec_prepare(bank, p, n_rec))) return rc;
     VerifyStreamGuard join_on_error{bank};
-    p.ctl = bank->d_ctl; p.trk = bank->d_trk; p.fail = bank->d_fail; p.ckpt = bank->d_ckpt;
-    p.n_sub = n_sub_used; p.sub = lay; p.exact_hist = bank->d_hist;
+    p.ctl = bank->ctl.get(); p.trk = bank->trk.get(); p.fail = bank->fail.get(); p.ckpt = bank->ckpt.get();
+    p.n_sub = n_sub_used; p.sub = lay; p.exact_hist = bank->hist.get();
     p.ms_begin = 0; p.ms_end = p.n_ms;
     TrackVerifyParams v = verify_params(bank, p);
     v.bad = nullptr; v.bad_from = nullptr; v.sub = lay;
     DllExactParams x = dll_exact_params(bank, p);
     x.sub = lay;
     DllScanParams d = dll_scan_params(bank, p);
-    d.ckpt = bank->d_ckpt; d.bad = nullptr; d.only_bad = 0; d.first = 0; d.final = 0; d.hist_out = nullptr;
-    d.sub = lay; d.hist = bank->d_hist;
+    d.ckpt = bank->ckpt.get(); d.bad = nullptr; d.only_bad = 0; d.first = 0; d.final = 0; d.hist_out = nullptr;
+    d.sub = lay; d.hist = bank->hist.get();
     for (int R = 0; R < rounds; ++R) {
-        if (R >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_vring[(R - 2) % 3], 0));   // round R - 2's reports are in
+        if (R >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_vring[(R - 2) % 3].get(), 0));   // round R - 2's reports are in
         p.round = R;
         if ((rc = launch_track_block(ctx, p, 2))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_spec, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream, bank->ev_spec, 0));
-        v.trk_round = bank->d_trk + (size_t)R * bank->n_chan;
-        v.fail_round = bank->d_fail + (size_t)R * bank->n_chan;
-        if ((rc = launch_track_verify(ctx, v, bank->verify_stream))) return rc;
+        HIP_TRY(ctx, hipEventRecord(bank->ev_spec.get(), ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream.get(), bank->ev_spec.get(), 0));
+        v.trk_round = bank->trk.get() + (size_t)R * bank->n_chan;
+        v.fail_round = bank->fail.get() + (size_t)R * bank->n_chan;
+        if ((rc = launch_track_verify(ctx, v, bank->verify_stream.get()))) return rc;
         x.trk_round = v.trk_round;
-        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream))) return rc;
+        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream.get()))) return rc;
         d.trk_round = v.trk_round;
-        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_vring[R % 3], bank->verify_stream));
+        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream.get()))) return rc;
+        HIP_TRY(ctx, hipEventRecord(bank->ev_vring[R % 3].get(), bank->verify_stream.get()));
     }
-    HIP_TRY(ctx, hipEventRecord(bank->ev_verify, bank->verify_stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify, 0));
+    HIP_TRY(ctx, hipEventRecord(bank->ev_verify.get(), bank->verify_stream.get()));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify.get(), 0));
     join_on_error.armed = false;
     SpecFinalizeParams f;
-    f.ctl = bank->d_ctl; f.trk = bank->d_trk; f.fail = bank->d_fail; f.states = bank->d_states; f.ckpt = bank->d_ckpt; f.hist = bank->d_hist;
-    f.exact = bank->d_dllx; f.bad = bank->d_bad; f.bad_from = bank->d_bad_from; f.stats = bank->d_redo_stats;
+    f.ctl = bank->ctl.get(); f.trk = bank->trk.get(); f.fail = bank->fail.get(); f.states = bank->states.get(); f.ckpt = bank->ckpt.get(); f.hist = bank->hist.get();
+    f.exact = bank->dllx.get(); f.bad = bank->bad.get(); f.bad_from = bank->bad_from.get(); f.stats = bank->redo_stats.get();
     f.n_chan = bank->n_chan; f.n_sub = n_sub_used; f.rounds = rounds;
     hipLaunchKernelGGL(spec_finalize_kernel, dim3((unsigned)bank->n_chan), dim3(256), 0, ctx->stream, f);
     HIP_TRY(ctx, hipGetLastError());
     // channels the rounds did not finish (out of forced-transform slots or of rounds): the transform kernel, from their last good checkpoint
     p.dbg = nullptr;
     p.ctl = nullptr; p.trk = nullptr; p.fail = nullptr; p.ckpt = nullptr; p.n_sub = 0; p.round = 0;
-    return track_block_throughput(bank, p, bank->d_bad, bank->d_ckpt, bank->d_bad_from, bank->d_hist, lay);
+    return track_block_throughput(bank, p, bank->bad.get(), bank->ckpt.get(), bank->bad_from.get(), bank->hist.get(), lay);
 }
 
 int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
@@ -1738,23 +1706,22 @@ int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stri
         return fail(ctx, GYP_E_BAD_ARG, "gyp_track_block: the bank was created for " + std::to_string(bank->fs) + " Hz / " + std::to_string(bank->n) +
                                             " samples per ms, the context is now set to " + std::to_string(ctx->fs) + " / " + std::to_string(ctx->n));
     if (n_ms == 0) return GYP_OK;
-    TrackBlockParams p;
+    TrackBlockParams p{};   // (what is not set below is null / 0: no work list, no checkpoints, no rounds, no kept profiles)
     p.iq = reinterpret_cast<const cf*>(iq_dev);
     p.stream_stride = stream_stride_samples;
     p.n_ms = n_ms;
-    p.ms_begin = 0;
     p.ms_end = n_ms;
     p.start_time = start_time_dev;
-    p.states = bank->d_states;
+    p.states = bank->states.get();
     p.n_chan = bank->n_chan;
     p.rec_out = rec_out_dev;
-    p.replica_table = ctx->d_replicas;
-    p.tw_tables = ctx->d_tw;
+    p.replica_table = ctx->codes.replicas.get();
+    p.tw_tables = ctx->codes.tw.get();
     p.inv_fs = 1.0 / (double)ctx->fs;
     p.fs = (double)ctx->fs;
-    p.prof = ctx->d_prof;
+    p.prof = ctx->prof.get();
     p.prof_wave = ctx->prof_wave;
-    p.codes = CodeTables{ctx->d_trans, ctx->d_ntrans, ctx->d_chipf};
+    p.codes = CodeTables{ctx->codes.trans.get(), ctx->codes.ntrans.get(), ctx->codes.chipf.get()};
     {
         const gyp_params& g = ctx->params;
         // tracker.py:227-244: alpha = 4 zeta B dt, beta = 4 B^2 dt with zeta = 1/sqrt(2), dt = 1/fs, in the reference's order
@@ -1765,20 +1732,13 @@ int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stri
                           std::tan(g.lock_rotation_max_deg * M_PI / 180.0),
                           g.watchdog_period_s, g.watchdog_drop_below, g.watchdog_nudge_below, g.watchdog_nudge_hz, (double)ctx->n};
     }
-    p.spec_out = nullptr;
-    p.exact0 = nullptr;
     p.spec_kappa = (float)ctx->params.spec_confidence_kappa;
     p.prov_bias = ctx->dll_prov_bias;
-    p.only_if = nullptr;
-    p.restore_from = nullptr;
-    p.from_sub = nullptr; p.exact_hist = nullptr; p.sub = SubLayout::none();
-    p.dbg = nullptr;
-    p.prof_tail = nullptr; p.prof_from = 0; p.prof_depth = 0;
-    p.ctl = nullptr; p.trk = nullptr; p.fail = nullptr; p.ckpt = nullptr; p.round = 0; p.n_sub = 0;
+    p.sub = SubLayout::none();
     if (bank->prof_depth > 0) {   // profiles kept: the transform kernel forms every millisecond's full profile anyway
         bank->prof_rows = std::min(bank->prof_depth, (int)n_ms);
-        p.prof_tail = bank->d_prof_tail; p.prof_from = n_ms - bank->prof_rows; p.prof_depth = bank->prof_depth;
-        HIP_TRY(ctx, hipMemsetAsync(bank->d_prof_delta, 0, (size_t)bank->n_chan * bank->prof_depth * sizeof(int32_t), ctx->stream));
+        p.prof_tail = bank->prof_tail.get(); p.prof_from = n_ms - bank->prof_rows; p.prof_depth = bank->prof_depth;
+        HIP_TRY(ctx, hipMemsetAsync(bank->prof_delta.get(), 0, (size_t)bank->n_chan * bank->prof_depth * sizeof(int32_t), ctx->stream));
         return track_block_throughput(bank, p, nullptr, nullptr);
     }
     const bool light = (ctx->k == 8 || ctx->k == 2 || ctx->k == 16) && p.n_chan <= ctx->n_cus && !ctx->no_pipe;   // one workgroup per CU anyway
@@ -1792,16 +1752,16 @@ int gyp_bank_keep_profiles(gyp_bank* bank, int32_t depth) {
     if (depth < 0 || depth > 4096) return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_keep_profiles: depth must be in 0..4096");
     if (depth == bank->prof_depth) return GYP_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (bank->d_prof_tail) { hipFree(bank->d_prof_tail); bank->d_prof_tail = nullptr; }
-    if (bank->d_prof_delta) { hipFree(bank->d_prof_delta); bank->d_prof_delta = nullptr; }
+    HIP_TRY(ctx, bank->prof_tail.reset());
+    HIP_TRY(ctx, bank->prof_delta.reset());
     bank->prof_depth = 0; bank->prof_rows = 0;
     if (depth == 0) return GYP_OK;
     const size_t rows = (size_t)bank->n_chan * depth;
-    if (hipMalloc((void**)&bank->d_prof_tail, rows * bank->n * sizeof(float)) != hipSuccess) {
+    if (bank->prof_tail.reserve(rows * bank->n, Slack::exact) != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, GYP_E_NOMEM, "gyp_bank_keep_profiles: " + std::to_string(rows * bank->n * sizeof(float)) + " bytes of profile rows do not fit");
     }
-    HIP_TRY(ctx, hipMalloc((void**)&bank->d_prof_delta, rows * sizeof(int32_t)));
+    HIP_TRY(ctx, bank->prof_delta.reserve(rows, Slack::exact));
     bank->prof_depth = depth;
     return GYP_OK;
 }
@@ -1816,8 +1776,8 @@ int gyp_bank_read_profiles(gyp_bank* bank, int32_t channel, float* out, int32_t*
     std::vector<float> raw((size_t)rows * n);
     std::vector<int32_t> delta(rows);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(raw.data(), bank->d_prof_tail + (size_t)channel * bank->prof_depth * n, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(delta.data(), bank->d_prof_delta + (size_t)channel * bank->prof_depth, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(raw.data(), bank->prof_tail.get() + (size_t)channel * bank->prof_depth * n, raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(delta.data(), bank->prof_delta.get() + (size_t)channel * bank->prof_depth, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int r = 0; r < rows; ++r) {
         // the row is roll(c0, -s_provisional); the reference's is roll(c0, -s_exact): out[k] = row[(k + s_exact - s_provisional) mod n]
         const int d = ((delta[r] % n) + n) % n;
@@ -1838,20 +1798,15 @@ int gyp_track_block(gyp_bank* bank, const float* iq_host, int32_t n_streams, int
             return fail(ctx, GYP_E_BAD_ARG, "gyp_track_block: channel " + std::to_string(c) + " reads stream " +
                                                 std::to_string(bank->stream_of[c]) + " but only " + std::to_string(n_streams) + " were passed");
     if (n_ms == 0) return GYP_OK;
-    const size_t iq_bytes = (size_t)n_streams * n_ms * ctx->n * 8;
-    const size_t rec_bytes = (size_t)bank->n_chan * n_ms * sizeof(gyp_track_rec);
-    int rc;
-    if ((rc = ensure_scratch(ctx, 0, iq_bytes))) return rc;
-    if ((rc = ensure_scratch(ctx, 4, (size_t)n_ms * sizeof(double)))) return rc;
-    if (rec_out_host && (rc = ensure_scratch(ctx, 5, rec_bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0], iq_host, iq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4], start_time_host, (size_t)n_ms * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gyp_track_block_dev(bank, (const float*)ctx->scratch[0], (int64_t)n_ms * ctx->n, n_ms, (const double*)ctx->scratch[4],
-                             rec_out_host ? (gyp_track_rec*)ctx->scratch[5] : nullptr);
-    if (rc) return rc;
-    if (rec_out_host) HIP_TRY(ctx, hipMemcpyAsync(rec_out_host, ctx->scratch[5], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    Scratch& sc = ctx->scratch;
+    const size_t rec_bytes = rec_out_host ? (size_t)bank->n_chan * n_ms * sizeof(gyp_track_rec) : 0;
+    HIP_TRY(ctx, sc.stage_out.reserve(rec_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_times, start_time_host, (size_t)n_ms, ctx->stream));
+    if (const int rc = gyp_track_block_dev(bank, sc.stage_iq.get(), (int64_t)n_ms * ctx->n, n_ms, sc.stage_times.get(),
+                                           rec_out_host ? (gyp_track_rec*)sc.stage_out.get() : nullptr))
+        return rc;
+    return stage_back(ctx, rec_out_host, rec_bytes);
 }
 
 // ---------------------------------------------------------------- multi-GPU: one all-gather over RCCL ------
@@ -1940,8 +1895,8 @@ int gyp_debug_spec_read(gyp_bank* bank, float* out, int32_t n_floats, int32_t* b
     if (!bank) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (out && bank->d_dbg) HIP_TRY(ctx, hipMemcpy(out, bank->d_dbg, std::min((size_t)n_floats, bank->dbg_cap) * sizeof(float), hipMemcpyDeviceToHost));
-    if (bad_out && bank->d_bad) HIP_TRY(ctx, hipMemcpy(bad_out, bank->d_bad, (size_t)bank->n_chan * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out && bank->dbg.get()) HIP_TRY(ctx, hipMemcpy(out, bank->dbg.get(), std::min((size_t)n_floats, bank->dbg.capacity()) * sizeof(float), hipMemcpyDeviceToHost));
+    if (bad_out && bank->bad.get()) HIP_TRY(ctx, hipMemcpy(bad_out, bank->bad.get(), (size_t)bank->n_chan * sizeof(int32_t), hipMemcpyDeviceToHost));
     return GYP_OK;
 }
 
@@ -1957,9 +1912,9 @@ int gyp_debug_spec_redo_read(gyp_bank* bank, int32_t* out4) {
     if (!bank || !out4) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
     out4[0] = out4[1] = out4[2] = out4[3] = 0;
-    if (!bank->d_redo_stats) return GYP_OK;   // the bank has not tracked a block on the speculative path
+    if (!bank->redo_stats.get()) return GYP_OK;   // the bank has not tracked a block on the speculative path
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(out4, bank->d_redo_stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out4, bank->redo_stats.get(), 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return GYP_OK;
 }
 
@@ -1969,8 +1924,8 @@ int gyp_debug_dll_read(gyp_bank* bank, int32_t* repairs_out) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<DllExact> x((size_t)bank->n_chan);
     for (int i = 0; i < bank->n_chan; ++i) repairs_out[i] = 0;
-    if (!bank->d_dllx) return GYP_OK;          // the bank has not tracked a block yet
-    HIP_TRY(ctx, hipMemcpy(x.data(), bank->d_dllx, x.size() * sizeof(DllExact), hipMemcpyDeviceToHost));
+    if (!bank->dllx.get()) return GYP_OK;          // the bank has not tracked a block yet
+    HIP_TRY(ctx, hipMemcpy(x.data(), bank->dllx.get(), x.size() * sizeof(DllExact), hipMemcpyDeviceToHost));
     for (int i = 0; i < bank->n_chan; ++i) repairs_out[i] = x[i].repairs;
     return GYP_OK;
 }
@@ -1978,13 +1933,13 @@ int gyp_debug_dll_read(gyp_bank* bank, int32_t* repairs_out) {
 int gyp_debug_disc_read(gyp_bank* bank, int32_t n_ms, double* disc_out) {
     if (!bank) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
-    if (!disc_out || n_ms <= 0 || n_ms != bank->last_n_ms || !bank->d_disc || !bank->d_spec)
+    if (!disc_out || n_ms <= 0 || n_ms != bank->last_n_ms || !bank->disc.get() || !bank->spec.get())
         return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_disc_read: n_ms must be the length of the bank's last block on the throughput path");
     const size_t n_rec = (size_t)bank->n_chan * n_ms;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<SpecIn> spec(n_rec);
-    HIP_TRY(ctx, hipMemcpy(disc_out, bank->d_disc, n_rec * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(spec.data(), bank->d_spec, n_rec * sizeof(SpecIn), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(disc_out, bank->disc.get(), n_rec * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(spec.data(), bank->spec.get(), n_rec * sizeof(SpecIn), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n_rec; ++i)
         if (spec[i].key == kSpecKeyLost) disc_out[i] = 0.0;   // not processed: the pass wrote nothing there
     return GYP_OK;
@@ -1994,7 +1949,7 @@ int gyp_bank_reset_dev(gyp_bank* bank, const gyp_chan_init* inits_dev) {
     if (!bank) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
     if (!inits_dev) return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_reset_dev: bad argument");
-    hipLaunchKernelGGL(bank_reset_kernel, dim3((bank->n_chan + 63) / 64), dim3(64), 0, ctx->stream, bank->d_states, inits_dev, bank->n_chan);
+    hipLaunchKernelGGL(bank_reset_kernel, dim3((bank->n_chan + 63) / 64), dim3(64), 0, ctx->stream, bank->states.get(), inits_dev, bank->n_chan);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
@@ -2004,7 +1959,7 @@ int gyp_bank_get_state(gyp_bank* bank, double* doppler_hz, double* carrier_phase
     gyp_ctx* ctx = bank->ctx;
     std::vector<ChanState> host((size_t)bank->n_chan);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(host.data(), bank->d_states, host.size() * sizeof(ChanState), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(host.data(), bank->states.get(), host.size() * sizeof(ChanState), hipMemcpyDeviceToHost));
     for (int i = 0; i < bank->n_chan; ++i) {
         if (doppler_hz) doppler_hz[i] = host[i].doppler;
         if (carrier_phase) carrier_phase[i] = host[i].carrier_phase;
@@ -2018,16 +1973,14 @@ int gyp_bank_get_state(gyp_bank* bank, double* doppler_hz, double* carrier_phase
 int gyp_synth_iq_dev(gyp_ctx* ctx, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
                      const gyp_synth_sat* sats_host, int32_t n_sats, float noise_sigma, uint64_t seed) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
+    if (const int rc = need_format(ctx)) return rc;
     if (!out_dev || !sats_host || n_streams <= 0 || n_ms <= 0 || n_ms > 65535 || n_sats < 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_synth_iq_dev: bad argument (n_ms must be 1..65535)");
     for (int i = 0; i < n_streams * n_sats; ++i)
         if (sats_host[i].sat_id < 1 || sats_host[i].sat_id > 32 || sats_host[i].code_phase < 0 || sats_host[i].code_phase >= ctx->n)
             return fail(ctx, GYP_E_BAD_ARG, "gyp_synth_iq_dev: satellite descriptor out of range");
-    int rc;
-    const size_t bytes = (size_t)std::max(1, n_streams * n_sats) * sizeof(gyp_synth_sat);
-    if ((rc = ensure_scratch(ctx, 1, bytes))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1], sats_host, (size_t)n_streams * n_sats * sizeof(gyp_synth_sat), hipMemcpyHostToDevice, ctx->stream));
+    const size_t n_scene = (size_t)n_streams * n_sats;
+    HIP_TRY(ctx, upload(ctx->scratch.synth_scene, sats_host, n_scene, ctx->stream, n_scene ? 0 : 1));
     SynthParams p;
     p.out = reinterpret_cast<cf*>(out_dev);
     p.stream_stride = stream_stride_samples;
@@ -2035,41 +1988,26 @@ int gyp_synth_iq_dev(gyp_ctx* ctx, float* out_dev, int32_t n_streams, int64_t st
     p.n_per_ms = ctx->n;
     p.k = ctx->k;
     p.n_sats = n_sats;
-    p.sats = (const gyp_synth_sat*)ctx->scratch[1];
-    p.chips = ctx->d_chips;
+    p.sats = ctx->scratch.synth_scene.get();
+    p.chips = ctx->codes.chips.get();
     p.sigma = noise_sigma;
     p.seed = seed;
     p.inv_fs = 1.0 / (double)ctx->fs;
     hipLaunchKernelGGL(synth_iq_kernel, dim3((ctx->n + 255) / 256, n_ms, n_streams), dim3(256), 0, ctx->stream, p);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // sats_host may be a temporary; scratch[1] is reused by other calls
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // sats_host may be a temporary
     return GYP_OK;
 }
 
 // A/B switches and test hooks of a context, by name.  The library reads no environment variable for them (a stray variable in
-// a deployment must not change the speed path): whoever wants one says so through this call.  Values are range-checked.
-namespace {
-struct DebugKnob { const char* name; double lo, hi; bool integral; };
-const DebugKnob kDebugKnobs[] = {
-    {"no_pipe", 0, 1, true}, {"no_shared_fwd", 0, 1, true}, {"no_acq_shared_fwd", 0, 1, true}, {"no_acq_split", 0, 1, true}, {"no_spec", 0, 1, true},
-    {"spec_debug", 0, 1, true}, {"acq_lanes", 1, gyp_ctx::kMaxAcqLanes, true}, {"track_chunk_ms", 0, 1e6, true}, {"widen_wg_per_cu", 1, 8, true},
-    {"symbol_tau", 0, 100, false}, {"dll_prov_bias", -1e6, 1e6, false}, {"spec_fail_at", -1, 2147483647.0, true},
-    {"spec_redo", 0, 1, true}, {"spec_sub_ms", 0, 2000, true}, {"no_exact_shared", 0, 1, true}, {"prof_wave", 0, 7, true}, {"no_grid_parts", 0, 1, true}, {"no_grid_fused", 0, 1, true}, {"grid_fused_waves", 8, 12, true}, {"cells_cu_reserve", 0, 128, true},
-    {"resample_tile_samples", 1024, 8192, true},
-};
-}  // namespace
-static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, double* out) {
+// a deployment must not change the speed path): whoever wants one says so through this call.  Values are range-checked (kDebugSwitches).
+
+// The values gyp_debug_get reads and nobody sets (what the last call of its kind did): GYP_OK, GYP_E_HIP, or GYP_E_BAD_ARG if `name` is none.
+static int debug_read_only(gyp_ctx* ctx, const char* name, double* out) {
     auto is = [&](const char* n) { return std::strcmp(name, n) == 0; };
-#define GYP_KNOB_BOOL(N, FIELD) if (is(N)) { if (set) ctx->FIELD = v != 0.0; else *out = ctx->FIELD ? 1.0 : 0.0; return GYP_OK; }
-#define GYP_KNOB_NUM(N, FIELD, T) if (is(N)) { if (set) ctx->FIELD = (T)v; else *out = (double)ctx->FIELD; return GYP_OK; }
-    GYP_KNOB_BOOL("no_pipe", no_pipe)
-    GYP_KNOB_BOOL("no_shared_fwd", no_shared_fwd)
-    GYP_KNOB_BOOL("no_acq_shared_fwd", no_acq_shared_fwd)
-    GYP_KNOB_BOOL("no_grid_parts", no_grid_parts)
-    GYP_KNOB_BOOL("no_grid_fused", no_grid_fused)
-    GYP_KNOB_NUM("grid_fused_waves", grid_fused_waves, int)
-    if (is("last_grid_refined_rows")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_refined_rows; return GYP_OK; }
-    if (is("last_grid_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_grid_plan.path; return GYP_OK; }
+    if (is("last_grid_refined_rows")) { *out = (double)ctx->last_grid_refined_rows; return GYP_OK; }
+    if (is("last_grid_path")) { *out = (double)ctx->last_grid_plan.path; return GYP_OK; }
+    if (is("last_exact_path")) { *out = (double)ctx->last_exact_path; return GYP_OK; }
     for (int w = 0; w < 3; ++w) {
         // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)
         static const char* const kWitness[3] = {"last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"};
@@ -2082,58 +2020,44 @@ static int debug_apply(gyp_ctx* ctx, const char* name, double v, bool set, doubl
             if (k < 1 || k > kAcqWitnessLevels || !end || *end != 0) continue;
             at = 3 * (int)k + w;
         }
-        if (set) return GYP_E_BAD_ARG;
         // the one place the counters are waited for and copied: this context's part of the last search plus the helpers' parts
         long long total = 0;
         for (int i = 0; i < ctx->acq_witness_lanes; ++i) {
             gyp_ctx* c = i == 0 ? ctx : ctx->helper[i - 1];
-            if (!c || !c->d_acq_witness) continue;
+            if (!c || !c->acq_witness.get()) continue;
             int32_t v = 0;
             if (hipStreamSynchronize(c->stream) != hipSuccess) return GYP_E_HIP;
-            if (hipMemcpy(&v, c->d_acq_witness + at, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return GYP_E_HIP;
+            if (hipMemcpy(&v, c->acq_witness.get() + at, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return GYP_E_HIP;
             total += v;
         }
         *out = (double)total;
         return GYP_OK;
     }
-    GYP_KNOB_NUM("cells_cu_reserve", cells_cu_reserve, int)
-    GYP_KNOB_BOOL("no_acq_split", no_acq_split)
-    GYP_KNOB_BOOL("no_spec", no_spec)
-    GYP_KNOB_BOOL("spec_debug", spec_debug)
-    GYP_KNOB_BOOL("spec_redo", spec_redo)
-    GYP_KNOB_NUM("spec_sub_ms", spec_sub_ms, int)
-    GYP_KNOB_NUM("acq_lanes", acq_lanes, int)
-    GYP_KNOB_NUM("track_chunk_ms", track_chunk_ms, int)
-    GYP_KNOB_NUM("widen_wg_per_cu", widen_wg_per_cu, int)
-    GYP_KNOB_NUM("symbol_tau", symbol_tau, float)
-    GYP_KNOB_NUM("dll_prov_bias", dll_prov_bias, double)
-    GYP_KNOB_NUM("spec_fail_at", spec_fail_at, int)
-    GYP_KNOB_BOOL("no_exact_shared", no_exact_shared)
-    if (is("last_exact_path")) { if (set) return GYP_E_BAD_ARG; *out = (double)ctx->last_exact_path; return GYP_OK; }
-    GYP_KNOB_NUM("prof_wave", prof_wave, int)
-    GYP_KNOB_NUM("resample_tile_samples", resample_tile, int)
-#undef GYP_KNOB_BOOL
-#undef GYP_KNOB_NUM
     return GYP_E_BAD_ARG;
+}
+static const DebugSwitch* debug_switch(const char* name) {
+    for (const DebugSwitch& k : kDebugSwitches)
+        if (std::strcmp(name, k.name) == 0) return &k;
+    return nullptr;
 }
 int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
     if (!ctx || !name) return GYP_E_BAD_ARG;
-    for (const DebugKnob& k : kDebugKnobs) {
-        if (std::strcmp(name, k.name) != 0) continue;
-        if (!std::isfinite(value) || value < k.lo || value > k.hi || (k.integral && value != std::floor(value)))
-            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be " + (k.integral ? "an integer " : "") + "in [" +
-                                                std::to_string(k.lo) + ", " + std::to_string(k.hi) + "]");
-        if (std::strcmp(name, "track_chunk_ms") == 0 && value != 0.0 && value < 20.0)
-            return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: track_chunk_ms must be 0 (whole blocks) or at least 20");
-        if (std::strcmp(name, "grid_fused_waves") == 0 && value != 8.0 && value != 12.0)
-            return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: grid_fused_waves must be 8 or 12");
-        return debug_apply(ctx, name, value, true, nullptr);
-    }
-    return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);
+    const DebugSwitch* k = debug_switch(name);
+    if (!k) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);
+    if (!std::isfinite(value) || value < k->lo || value > k->hi || (k->integral && value != std::floor(value)))
+        return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be " + (k->integral ? "an integer " : "") + "in [" +
+                                            std::to_string(k->lo) + ", " + std::to_string(k->hi) + "]");
+    if (std::strcmp(name, "track_chunk_ms") == 0 && value != 0.0 && value < 20.0)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: track_chunk_ms must be 0 (whole blocks) or at least 20");
+    if (std::strcmp(name, "grid_fused_waves") == 0 && value != 8.0 && value != 12.0)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: grid_fused_waves must be 8 or 12");
+    k->set(*ctx, value);
+    return GYP_OK;
 }
 int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
-    const int rc = debug_apply(ctx, name, 0.0, false, out);
+    if (const DebugSwitch* k = debug_switch(name)) { *out = k->get(*ctx); return GYP_OK; }
+    const int rc = debug_read_only(ctx, name, out);
     if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");
     if (rc != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_get: no such switch: ") + name);
     return GYP_OK;
@@ -2141,27 +2065,27 @@ int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
 
 int gyp_debug_track_profile(gyp_ctx* ctx, int enable, long long* out8) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (enable && !ctx->d_prof) {
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_prof, 16 * sizeof(long long)));
-        HIP_TRY(ctx, hipMemset(ctx->d_prof, 0, 16 * sizeof(long long)));
+    if (enable && !ctx->prof.get()) {
+        HIP_TRY(ctx, ctx->prof.reserve(16, Slack::exact));
+        HIP_TRY(ctx, hipMemset(ctx->prof.get(), 0, 16 * sizeof(long long)));
     }
-    if (out8 && ctx->d_prof) {
+    if (out8 && ctx->prof.get()) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipMemcpy(out8, ctx->d_prof, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out8, ctx->prof.get(), 16 * sizeof(long long), hipMemcpyDeviceToHost));
     }
-    if (!enable && ctx->d_prof) { HIP_TRY(ctx, hipFree(ctx->d_prof)); ctx->d_prof = nullptr; }
+    if (!enable) HIP_TRY(ctx, ctx->prof.reset());
     return GYP_OK;
 }
 
 int gyp_debug_track_timing(gyp_ctx* ctx, int enable, float* out4) {
     if (!ctx) return GYP_E_BAD_ARG;
-    if (enable && !ctx->ev_track[0])
-        for (int i = 0; i < 4; ++i) HIP_TRY(ctx, hipEventCreate(&ctx->ev_track[i]));
+    if (enable)
+        for (Event& e : ctx->ev_track) HIP_TRY(ctx, e.create(hipEventDefault));
     if (out4) {
         out4[0] = out4[1] = out4[2] = out4[3] = 0.0f;   // (a bank on the speculative path: no per-kernel split, zeros)
         if (ctx->time_track && ctx->track_timed) {
-            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_track[3]));
-            for (int i = 0; i < 3; ++i) HIP_TRY(ctx, hipEventElapsedTime(out4 + i, ctx->ev_track[i], ctx->ev_track[i + 1]));
+            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_track[3].get()));
+            for (int i = 0; i < 3; ++i) HIP_TRY(ctx, hipEventElapsedTime(out4 + i, ctx->ev_track[i].get(), ctx->ev_track[i + 1].get()));
             out4[3] = (float)ctx->track_launches;
         }
     }
@@ -2172,27 +2096,27 @@ int gyp_debug_track_timing(gyp_ctx* ctx, int enable, float* out4) {
 
 int gyp_debug_fft_bench(gyp_ctx* ctx, int waves_per_wg, int wgs, int iters, float* ms_out) {
     if (!ctx || !ms_out) return GYP_E_BAD_ARG;
-    if (!ctx->k) return fail(ctx, GYP_E_NO_FORMAT, "gyp_set_stream_format has not been called");
-    int rc;
-    if ((rc = ensure_scratch(ctx, 3, (size_t)wgs * 1024 * 4))) return rc;
-    float* sink = (float*)ctx->scratch[3];
+    if (const int rc = need_format(ctx)) return rc;
+    HIP_TRY(ctx, ctx->scratch.bench_sink.reserve((size_t)wgs * 1024, Slack::grow, ctx->stream));
+    float* sink = ctx->scratch.bench_sink.get();
     for (int rep = 0; rep < 2; ++rep) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0.get(), ctx->stream));
+        const auto bench = [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            return launch_dyn(ctx, fft_bench_kernel<W>, dim3(wgs), dim3(64 * W), lds_bytes<W>(), ctx->stream, ctx->codes.tw.get(), ctx->codes.replicas.get(), iters, sink);
+        };
+        int rc;
         switch (waves_per_wg) {
-            case 1: HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fft_bench_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<1>()));
-                    hipLaunchKernelGGL(fft_bench_kernel<1>, dim3(wgs), dim3(64), lds_bytes<1>(), ctx->stream, ctx->d_tw, ctx->d_replicas, iters, sink); break;
-            case 2: HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fft_bench_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<2>()));
-                    hipLaunchKernelGGL(fft_bench_kernel<2>, dim3(wgs), dim3(128), lds_bytes<2>(), ctx->stream, ctx->d_tw, ctx->d_replicas, iters, sink); break;
-            case 4: HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fft_bench_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<4>()));
-                    hipLaunchKernelGGL(fft_bench_kernel<4>, dim3(wgs), dim3(256), lds_bytes<4>(), ctx->stream, ctx->d_tw, ctx->d_replicas, iters, sink); break;
-            case 8: HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fft_bench_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<8>()));
-                    hipLaunchKernelGGL(fft_bench_kernel<8>, dim3(wgs), dim3(512), lds_bytes<8>(), ctx->stream, ctx->d_tw, ctx->d_replicas, iters, sink); break;
+            case 1: rc = bench(std::integral_constant<int, 1>{}); break;
+            case 2: rc = bench(std::integral_constant<int, 2>{}); break;
+            case 4: rc = bench(std::integral_constant<int, 4>{}); break;
+            case 8: rc = bench(std::integral_constant<int, 8>{}); break;
             default: return fail(ctx, GYP_E_BAD_ARG, "waves_per_wg must be 1, 2, 4 or 8");
         }
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-        HIP_TRY(ctx, hipEventElapsedTime(ms_out, ctx->ev0, ctx->ev1));
+        if (rc) return rc;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1.get(), ctx->stream));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1.get()));
+        HIP_TRY(ctx, hipEventElapsedTime(ms_out, ctx->ev0.get(), ctx->ev1.get()));
     }
     return GYP_OK;
 }
@@ -2340,10 +2264,10 @@ int gyp_bits_get_state(const gyp_bits* bits, int32_t channel, gyp_bits_state* ou
 // ---------------------------------------------------------------------------------------------------------
 // Resampler (kernels_resample.hpp): fs_in recordings -> the stream format
 // ---------------------------------------------------------------------------------------------------------
-// The design for (fs_in, the context's rate, T, input kind), built and uploaded on first use.  A copy: the context owns d_taps.
+// The design for (fs_in, the context's rate, T, input kind), built and uploaded on first use.  A copy: the context owns d_taps' memory.
 static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool real, ResampleDesign* out, const char* who) {
-    for (const ResampleDesign& d : ctx->resample_designs)
-        if (d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T && d.real == real) {
+    for (const auto& cached : ctx->resample_designs)
+        if (const ResampleDesign& d = cached.first; d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T && d.real == real) {
             *out = d;
             return GYP_OK;
         }
@@ -2364,20 +2288,19 @@ static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool r
         for (int32_t j = 0; j < T; ++j) cols[(size_t)j * d.L + p] = rows[(size_t)row * T + j];
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMalloc((void**)&d.d_taps, cols.size() * sizeof(float)));
+    DevBuf<float> taps;
+    HIP_TRY(ctx, taps.reserve(cols.size(), Slack::exact));
+    d.d_taps = taps.get();
     const hipError_t e = hipMemcpyAsync(d.d_taps, cols.data(), cols.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `cols` is a temporary
-    if (e2 != hipSuccess) {
-        (void)hipFree(d.d_taps);
-        return fail(ctx, GYP_E_HIP, std::string(who) + ": table upload: " + hipGetErrorString(e2));
-    }
-    ctx->resample_designs.push_back(d);
+    if (e2 != hipSuccess) return fail(ctx, GYP_E_HIP, std::string(who) + ": table upload: " + hipGetErrorString(e2));
+    ctx->resample_designs.emplace_back(d, std::move(taps));
     *out = d;
     return GYP_OK;
 }
 
 static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, ResampleDesign* out, const char* who) {
-    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": " + kNoFormat);
     const int32_t T = resample_taps(taps);
     if (!T) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (32), 16, 24, 32, 48 or 64");
     if (!resample_rates_ok(fs_in, ctx->fs))
@@ -2390,7 +2313,7 @@ static const char* const kDdcRateRule = ": rates must be whole kHz with fs_in < 
                                         "20 |if| >= 9 fs_out and 20 |if| + 9 fs_out <= 10 fs_in";
 
 static int ddc_get_design(gyp_ctx* ctx, int64_t fs_in, int64_t if_hz, int32_t taps, ResampleDesign* out, const char* who) {
-    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": " + kNoFormat);
     if (taps && !ddc_taps(taps, 0, 0)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (auto), 32, 48, 64, 96 or 128");
     if (!ddc_rates_ok(fs_in, ctx->fs, if_hz)) return fail(ctx, GYP_E_BAD_RATE, std::string(who) + kDdcRateRule);
     return resample_cached_design(ctx, fs_in, ddc_taps(taps, fs_in, ctx->fs), true, out, who);
@@ -2501,20 +2424,17 @@ static int packed_levels_dev(gyp_ctx* ctx, const PackedFormat& pk, const float**
     const std::vector<float> key(pk.levels.v, pk.levels.v + 16);
     for (const auto& l : ctx->packed_levels)
         if (std::memcmp(l.first.data(), key.data(), sizeof(pk.levels.v)) == 0) {
-            *out = l.second;
+            *out = l.second.get();
             return GYP_OK;
         }
-    float* d = nullptr;
+    DevBuf<float> d;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMalloc((void**)&d, sizeof(pk.levels.v)));
-    const hipError_t e = hipMemcpyAsync(d, key.data(), sizeof(pk.levels.v), hipMemcpyHostToDevice, ctx->stream);
+    HIP_TRY(ctx, d.reserve(key.size(), Slack::exact));
+    const hipError_t e = hipMemcpyAsync(d.get(), key.data(), sizeof(pk.levels.v), hipMemcpyHostToDevice, ctx->stream);
     const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `key` is a temporary
-    if (e2 != hipSuccess) {
-        (void)hipFree(d);
-        return fail(ctx, GYP_E_HIP, std::string("packed level table upload: ") + hipGetErrorString(e2));
-    }
-    ctx->packed_levels.emplace_back(key, d);
-    *out = d;
+    if (e2 != hipSuccess) return fail(ctx, GYP_E_HIP, std::string("packed level table upload: ") + hipGetErrorString(e2));
+    *out = d.get();
+    ctx->packed_levels.emplace_back(key, std::move(d));
     return GYP_OK;
 }
 
@@ -2779,25 +2699,26 @@ static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
     if (g->ctx) {
         (void)hipSetDevice(g->ctx->device);
-        if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
-        for (auto p : g->dev_raw) if (p) (void)hipFree(p);
-        for (auto p : g->dev_iq) if (p) (void)hipFree(p);
-        for (auto e : g->uploaded) if (e) (void)hipEventDestroy(e);
-        for (auto e : g->ready) if (e) (void)hipEventDestroy(e);
-        if (g->consumer_mark) (void)hipEventDestroy(g->consumer_mark);
-        if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
-        for (auto p : g->host) if (p) (void)hipHostFree(p);
-    } else {
-        for (auto p : g->host) std::free(p);
+        if (g->copy_stream.get()) (void)hipStreamSynchronize(g->copy_stream.get());
     }
     if (g->fd >= 0) close(g->fd);
-    delete g;
+    delete g;   // the members release what they hold: the rings and events first, the copy stream last
+}
+
+// Enqueue ingest_widen_kernel on `stream`: n_words int8, uint8 or int16 words (fmt) -> float32 * scale
+static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, const void* raw, size_t n_words, float scale, float* out) {
+    const dim3 grid((unsigned)std::min<size_t>((n_words / 16 + 255) / 256 + 1, (size_t)ctx->n_cus * ctx->widen_wg_per_cu));
+    switch (fmt) {
+        case kFmtI8: hipLaunchKernelGGL(ingest_widen_kernel<int8_t>, grid, dim3(256), 0, stream, (const int8_t*)raw, out, n_words, scale); break;
+        case kFmtU8: hipLaunchKernelGGL(ingest_widen_kernel<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t*)raw, out, n_words, scale); break;
+        default: hipLaunchKernelGGL(ingest_widen_kernel<int16_t>, grid, dim3(256), 0, stream, (const int16_t*)raw, out, n_words, scale); break;
+    }
 }
 
 // A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
 static int ingest_condition(gyp_ingest* g, int d, int32_t n_ms) {
     if (!g->level_on) return GYP_OK;
-    return condition_launch(g->ctx, g->copy_stream, g->dev_iq[d], g->dev_iq[d], 1, 0, (int64_t)n_ms * g->n, &g->level);
+    return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * g->n, &g->level);
 }
 
 // Enqueue the upload (+ widening) of the reader's next block on the copy stream.  Returns 1 if a block was
@@ -2807,7 +2728,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     // keep fewer than `depth` host slots tied up in uploads: retire the oldest first
     while ((int)g->in_flight.size() >= g->depth - 1) {
         const gyp_ingest::Upload& f = g->in_flight.front();
-        HIP_TRY(ctx, hipEventSynchronize(g->uploaded[f.block % g->depth]));
+        HIP_TRY(ctx, hipEventSynchronize(g->uploaded[f.block % g->depth].get()));
         ingest_release(g, f.block + 1);
         g->in_flight.pop_front();
     }
@@ -2821,53 +2742,40 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     const int d = (int)(u->block % g->depth);
     // the device slot may hold an older block: everything the consumer has enqueued so far drains first (that is
     // the kernels of block k-1 when block k+1 is uploaded ahead, so the upload still overlaps block k's kernels)
-    HIP_TRY(ctx, hipEventRecord(g->consumer_mark, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(g->copy_stream, g->consumer_mark, 0));
+    HIP_TRY(ctx, hipEventRecord(g->consumer_mark.get(), ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(g->copy_stream.get(), g->consumer_mark.get(), 0));
+    uint8_t* raw = g->dev_raw[d].get();
+    float* iq = g->dev_iq[d].get();
+    const int64_t out_n = (int64_t)u->n_ms * g->n;
     if (g->packed) {   // the bytes covering the block's samples (halo included), unpacked / resampled / down-converted into the output slot
         const PackedSpan sp = ingest_packed_span(g, u->first_ms, u->n_ms);
-        if (sp.n_bytes) HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)sp.n_bytes, hipMemcpyHostToDevice, g->copy_stream));
-        HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
+        if (sp.n_bytes) HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)sp.n_bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
+        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
         const int rc = g->resampled
-                           ? resample_launch_packed(ctx, g->copy_stream, g->rs, g->pk, g->dev_raw[d], 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n,
-                                                    g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n, g->if_hz)
-                           : unpack_launch(ctx, g->copy_stream, g->pk, g->dev_raw[d], 1, sp.n_bytes, sp.bit0, (int64_t)u->n_ms * g->n, g->scale,
-                                           g->dev_iq[d], (int64_t)u->n_ms * g->n);
+                           ? resample_launch_packed(ctx, g->copy_stream.get(), g->rs, g->pk, raw, 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n,
+                                                    g->scale, u->first_ms, u->n_ms, iq, out_n, g->if_hz)
+                           : unpack_launch(ctx, g->copy_stream.get(), g->pk, raw, 1, sp.n_bytes, sp.bit0, out_n, g->scale, iq, out_n);
         if (rc) return rc;
-        if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
-        HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
-        g->in_flight.push_back(*u);
-        ++g->dev_blocks;
-        return 1;
-    }
-    if (g->resampled) {   // the block's input span (halo included) in file width, resampled into the output slot
+    } else if (g->resampled) {   // the block's input span (halo included) in file width, resampled into the output slot
         const int64_t span = (int64_t)u->n_ms * g->in_n + g->halo_lo + g->halo_hi;
-        HIP_TRY(ctx, hipMemcpyAsync(g->dev_raw[d], g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream));
-        HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
-        if (const int rc = resample_launch(ctx, g->copy_stream, g->rs, g->fmt, g->dev_raw[d], 1, span, u->first_ms * g->in_n - g->halo_lo, span,
-                                           g->scale, u->first_ms, u->n_ms, g->dev_iq[d], (int64_t)u->n_ms * g->n, g->if_hz))
+        HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
+        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
+        if (const int rc = resample_launch(ctx, g->copy_stream.get(), g->rs, g->fmt, raw, 1, span, u->first_ms * g->in_n - g->halo_lo, span,
+                                           g->scale, u->first_ms, u->n_ms, iq, out_n, g->if_hz))
             return rc;
-        if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
-        HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
-        g->in_flight.push_back(*u);
-        ++g->dev_blocks;
-        return 1;
-    }
-    const size_t bytes = (size_t)u->n_ms * g->ms_bytes;
-    const size_t words = (size_t)u->n_ms * g->n * 2;
-    void* dst = g->fmt == kFmtF32 ? (void*)g->dev_iq[d] : (void*)g->dev_raw[d];
-    HIP_TRY(ctx, hipMemcpyAsync(dst, g->host[slot], bytes, hipMemcpyHostToDevice, g->copy_stream));
-    HIP_TRY(ctx, hipEventRecord(g->uploaded[d], g->copy_stream));
-    if (g->fmt != kFmtF32) {
-        const int grid = (int)std::min<size_t>((words / 16 + 255) / 256 + 1, (size_t)ctx->n_cus * ctx->widen_wg_per_cu);
-        switch (g->fmt) {
-            case kFmtI8: hipLaunchKernelGGL(ingest_widen_kernel<int8_t>, dim3(grid), dim3(256), 0, g->copy_stream, (const int8_t*)dst, g->dev_iq[d], words, g->scale); break;
-            case kFmtU8: hipLaunchKernelGGL(ingest_widen_kernel<uint8_t>, dim3(grid), dim3(256), 0, g->copy_stream, (const uint8_t*)dst, g->dev_iq[d], words, g->scale); break;
-            default: hipLaunchKernelGGL(ingest_widen_kernel<int16_t>, dim3(grid), dim3(256), 0, g->copy_stream, (const int16_t*)dst, g->dev_iq[d], words, g->scale); break;
+    } else {   // file-width words, widened on the device (float32 lands in the output slot directly)
+        const size_t bytes = (size_t)u->n_ms * g->ms_bytes;
+        const size_t words = (size_t)u->n_ms * g->n * 2;
+        void* dst = g->fmt == kFmtF32 ? (void*)iq : (void*)raw;
+        HIP_TRY(ctx, hipMemcpyAsync(dst, g->host[slot], bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
+        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
+        if (g->fmt != kFmtF32) {
+            widen_launch(ctx, g->copy_stream.get(), g->fmt, dst, words, g->scale, iq);
+            HIP_TRY(ctx, hipGetLastError());
         }
-        HIP_TRY(ctx, hipGetLastError());
     }
     if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
-    HIP_TRY(ctx, hipEventRecord(g->ready[d], g->copy_stream));
+    HIP_TRY(ctx, hipEventRecord(g->ready[d].get(), g->copy_stream.get()));
     g->in_flight.push_back(*u);
     ++g->dev_blocks;
     return 1;
@@ -2879,10 +2787,6 @@ static double round6(double x) {
     std::snprintf(buf, sizeof buf, "%.6f", x);
     return std::strtod(buf, nullptr);
 }
-
-extern "C" {
-
-}  // extern "C"
 
 // Opens the file and allocates the rings of a handle whose rates and sizes are filled in; frees it on failure.
 static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp_ingest** out) {
@@ -2903,15 +2807,16 @@ static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp
     (void)posix_fadvise(g->fd, 0, 0, POSIX_FADV_SEQUENTIAL);
     const size_t block_bytes = g->host_block_bytes;
     g->host.assign(depth, nullptr);
+    g->host_mem.resize(depth);
     g->host_first.assign(depth, 0);
     g->host_ms.assign(depth, 0);
     int rc = GYP_OK;
     auto setup = [&]() -> int {
         if (!ctx) {
-            for (auto& p : g->host) {
+            for (int i = 0; i < depth; ++i) {
                 void* m = nullptr;
                 if (posix_memalign(&m, 4096, block_bytes)) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open: out of memory");
-                p = (uint8_t*)m;
+                g->host[i] = g->host_mem[i].adopt(m);
             }
             return GYP_OK;
         }
@@ -2919,23 +2824,24 @@ static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp
         g->locality = device_locality(ctx->device);
         {
             ScopedAffinity on_the_gpus_node(g->locality);   // pinned pages land on the node of the thread that allocates them
-            for (auto& p : g->host) {
-                HIP_TRY(ctx, hipHostMalloc((void**)&p, block_bytes, hipHostMallocDefault));
-                std::memset(p, 0, block_bytes);              // first touch, still on that node
+            for (int i = 0; i < depth; ++i) {
+                HIP_TRY(ctx, g->host_mem[i].alloc(block_bytes));
+                g->host[i] = g->host_mem[i].get();
+                std::memset(g->host[i], 0, block_bytes);     // first touch, still on that node
             }
         }
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking));
-        g->dev_raw.assign(depth, nullptr);
-        g->dev_iq.assign(depth, nullptr);
-        g->uploaded.assign(depth, nullptr);
-        g->ready.assign(depth, nullptr);
+        HIP_TRY(ctx, g->copy_stream.create(hipStreamNonBlocking));
+        g->dev_raw.resize(depth);
+        g->dev_iq.resize(depth);
+        g->uploaded.resize(depth);
+        g->ready.resize(depth);
         for (int i = 0; i < depth; ++i) {
-            if (g->raw_block_bytes) HIP_TRY(ctx, hipMalloc((void**)&g->dev_raw[i], g->raw_block_bytes));
-            HIP_TRY(ctx, hipMalloc((void**)&g->dev_iq[i], (size_t)g->block_ms * g->n * 2 * sizeof(float)));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&g->uploaded[i], hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&g->ready[i], hipEventDisableTiming));
+            HIP_TRY(ctx, g->dev_raw[i].reserve(g->raw_block_bytes, Slack::exact));
+            HIP_TRY(ctx, g->dev_iq[i].reserve((size_t)g->block_ms * g->n * 2, Slack::exact));
+            HIP_TRY(ctx, g->uploaded[i].create(hipEventDisableTiming));
+            HIP_TRY(ctx, g->ready[i].create(hipEventDisableTiming));
         }
-        HIP_TRY(ctx, hipEventCreateWithFlags(&g->consumer_mark, hipEventDisableTiming));
+        HIP_TRY(ctx, g->consumer_mark.create(hipEventDisableTiming));
         return GYP_OK;
     };
     if ((rc = setup())) {
@@ -3025,7 +2931,7 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
     if (pk.real != (if_hz != 0)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": real words need if_hz != 0, I,Q words if_hz = 0");
     if (!path || block_ms < 1 || depth < 3 || depth > 64)
         return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (path, block_ms >= 1, 3 <= depth <= 64)");
-    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": gyp_set_stream_format has not been called");
+    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": " + kNoFormat);
     const bool native = !pk.real && fs_in_hz == ctx->fs;
     const float* levels = nullptr;   // uploaded now, not on the copy stream's first block
     if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
@@ -3092,7 +2998,7 @@ int gyp_ingest_seek(gyp_ingest* g, int64_t ms) {
     if (ms < 0 || ms > g->total_ms) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_seek: millisecond out of range");
     ingest_stop_reader(g);
     if (g->ctx) {
-        HIP_TRY(g->ctx, hipStreamSynchronize(g->copy_stream));
+        HIP_TRY(g->ctx, hipStreamSynchronize(g->copy_stream.get()));
         g->in_flight.clear();
         g->have_ahead = false;
     }
@@ -3143,13 +3049,13 @@ int gyp_ingest_next_dev(gyp_ingest* g, const float** iq_dev_out, int64_t* first_
     if (rc < 0) return rc;
     g->have_ahead = rc == 1;
     const int d = (int)(cur.block % g->depth);
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, g->ready[d], 0));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, g->ready[d].get(), 0));
     // hand back host slots whose upload has finished
-    while (!g->in_flight.empty() && hipEventQuery(g->uploaded[g->in_flight.front().block % g->depth]) == hipSuccess) {
+    while (!g->in_flight.empty() && hipEventQuery(g->uploaded[g->in_flight.front().block % g->depth].get()) == hipSuccess) {
         ingest_release(g, g->in_flight.front().block + 1);
         g->in_flight.pop_front();
     }
-    *iq_dev_out = g->dev_iq[d];
+    *iq_dev_out = g->dev_iq[d].get();
     *first_ms_out = cur.first_ms;
     *n_ms_out = cur.n_ms;
     g->consumer_ms = cur.first_ms + cur.n_ms;
@@ -3159,13 +3065,9 @@ int gyp_ingest_next_dev(gyp_ingest* g, const float** iq_dev_out, int64_t* first_
 int gyp_widen_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, uint64_t n_words, float scale, float* out_dev) {
     if (!ctx || !raw_dev || !out_dev) return ctx ? fail(ctx, GYP_E_BAD_ARG, "gyp_widen_iq_dev: bad argument") : GYP_E_BAD_ARG;
     if (n_words == 0) return GYP_OK;
-    const int grid = (int)std::min<uint64_t>((n_words / 16 + 255) / 256 + 1, (uint64_t)ctx->n_cus * ctx->widen_wg_per_cu);
-    switch (fmt) {
-        case GYP_FMT_I8: hipLaunchKernelGGL(ingest_widen_kernel<int8_t>, dim3(grid), dim3(256), 0, ctx->stream, (const int8_t*)raw_dev, out_dev, (size_t)n_words, scale); break;
-        case GYP_FMT_U8: hipLaunchKernelGGL(ingest_widen_kernel<uint8_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*)raw_dev, out_dev, (size_t)n_words, scale); break;
-        case GYP_FMT_I16: hipLaunchKernelGGL(ingest_widen_kernel<int16_t>, dim3(grid), dim3(256), 0, ctx->stream, (const int16_t*)raw_dev, out_dev, (size_t)n_words, scale); break;
-        default: return fail(ctx, GYP_E_BAD_ARG, "gyp_widen_iq_dev: fmt must be GYP_FMT_I8, GYP_FMT_U8 or GYP_FMT_I16");
-    }
+    if (fmt != GYP_FMT_I8 && fmt != GYP_FMT_U8 && fmt != GYP_FMT_I16)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_widen_iq_dev: fmt must be GYP_FMT_I8, GYP_FMT_U8 or GYP_FMT_I16");
+    widen_launch(ctx, ctx->stream, fmt, raw_dev, (size_t)n_words, scale, out_dev);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
@@ -3198,8 +3100,9 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     if (!(target_rms > 0.0) || !std::isfinite(target_rms))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_calibrate: target_rms must be positive and finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    gyp_iq_stats* d_stats = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_stats, (size_t)n_ms * sizeof(gyp_iq_stats)));
+    DevBuf<gyp_iq_stats> stats_dev;
+    HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
+    gyp_iq_stats* d_stats = stats_dev.get();
     const bool was_on = g->level_on;
     const int64_t back_to = g->consumer_ms;
     g->level_on = false;   // the blocks below are the handle's unconditioned output
@@ -3226,7 +3129,7 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     const int rc = measure();
     const std::string why = ctx->err;
     (void)hipStreamSynchronize(ctx->stream);   // nothing may still read d_stats or a block of the measurement
-    (void)hipFree(d_stats);
+    (void)stats_dev.reset();
     g->level_on = rc == GYP_OK ? true : was_on;
     if (rc == GYP_OK) g->level = level;
     const int rc_back = gyp_ingest_seek(g, back_to);

@@ -271,6 +271,7 @@ struct gyp_ingest {
 
     // host ring, filled by the reader thread
     std::vector<uint8_t*> host;
+    std::vector<PinnedBuf> host_mem;   // owns what `host` points to (empty where the caller supplied and frees the blocks)
     std::vector<int64_t> host_first;
     std::vector<int32_t> host_ms;
     std::thread reader;
@@ -282,11 +283,11 @@ struct gyp_ingest {
     int io_errno = 0;
 
     // device ring
-    hipStream_t copy_stream = nullptr;
-    std::vector<uint8_t*> dev_raw;   // file-width words (unused for float32: the upload lands in dev_iq directly)
-    std::vector<float*> dev_iq;
-    std::vector<hipEvent_t> uploaded, ready;
-    hipEvent_t consumer_mark = nullptr;
+    Stream copy_stream;              // (declared before everything used on it: destroyed last)
+    std::vector<DevBuf<uint8_t>> dev_raw;   // file-width words (unused for float32: the upload lands in dev_iq directly)
+    std::vector<DevBuf<float>> dev_iq;
+    std::vector<Event> uploaded, ready;
+    Event consumer_mark;
     struct Upload {
         int64_t block, first_ms;
         int32_t n_ms;
@@ -316,6 +317,17 @@ static void ingest_set_block_bytes(gyp_ingest* g) {
     }
 }
 
+// pread until `want` bytes from file offset `at` are in: 0, or an errno (EIO: the file shrank under us).
+static int pread_fully(int fd, uint8_t* buf, size_t want, size_t at) {
+    for (size_t got = 0; got < want;) {
+        const ssize_t r = pread(fd, buf + got, want - got, (off_t)(at + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return r < 0 ? errno : EIO;
+        got += (size_t)r;
+    }
+    return 0;
+}
+
 // A resampled block's input span with its halo; what lies outside the file's whole samples reads as zero.  0 or an errno.
 static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
     const size_t sb = g->sample_bytes;
@@ -328,18 +340,7 @@ static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int
     }
     std::memset(buf, 0, (size_t)(a - s0) * sb);
     std::memset(buf + (size_t)(b - s0) * sb, 0, (size_t)(s0 + count - b) * sb);
-    const size_t want = (size_t)(b - a) * sb;
-    size_t got = 0;
-    while (got < want) {
-        const ssize_t r = pread(g->fd, buf + (size_t)(a - s0) * sb + got, want - got, (off_t)((size_t)a * sb + got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return errno;
-        }
-        if (r == 0) return EIO;   // file shrank under us
-        got += (size_t)r;
-    }
-    return 0;
+    return pread_fully(g->fd, buf + (size_t)(a - s0) * sb, (size_t)(b - a) * sb, (size_t)a * sb);
 }
 
 // A packed block's span: its input samples with the halo, the part inside the file, and the bytes covering that part.
@@ -350,17 +351,7 @@ static PackedSpan ingest_packed_span(const gyp_ingest* g, int64_t first, int32_t
 // A packed block: the bytes covering its samples, as they are in the file.  0 or an errno.
 static int ingest_read_packed(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
     const PackedSpan sp = ingest_packed_span(g, first, n_ms);
-    size_t got = 0;
-    while (got < (size_t)sp.n_bytes) {
-        const ssize_t r = pread(g->fd, buf + got, (size_t)sp.n_bytes - got, (off_t)((size_t)sp.first_byte + got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return errno;
-        }
-        if (r == 0) return EIO;   // file shrank under us
-        got += (size_t)r;
-    }
-    return 0;
+    return pread_fully(g->fd, buf, (size_t)sp.n_bytes, (size_t)sp.first_byte);
 }
 
 static void ingest_reader_main(gyp_ingest* g) {
@@ -381,22 +372,10 @@ static void ingest_reader_main(gyp_ingest* g) {
             }
             slot = (int)(g->produced % g->depth);
         }
-        size_t want = g->resampled || g->packed ? 0 : (size_t)n_ms * g->ms_bytes, got = 0;
-        int err = g->packed ? ingest_read_packed(g, g->host[slot], first, n_ms)
-                  : g->resampled ? ingest_read_resampled(g, g->host[slot], first, n_ms) : 0;
-        while (got < want) {
-            const ssize_t r = pread(g->fd, g->host[slot] + got, want - got, (off_t)((size_t)first * g->ms_bytes + got));
-            if (r < 0) {
-                if (errno == EINTR) continue;
-                err = errno;
-                break;
-            }
-            if (r == 0) {   // file shrank under us
-                err = EIO;
-                break;
-            }
-            got += (size_t)r;
-        }
+        uint8_t* buf = g->host[slot];
+        const int err = g->packed ? ingest_read_packed(g, buf, first, n_ms)
+                        : g->resampled ? ingest_read_resampled(g, buf, first, n_ms)
+                                       : pread_fully(g->fd, buf, (size_t)n_ms * g->ms_bytes, (size_t)first * g->ms_bytes);
         std::lock_guard<std::mutex> lk(g->mu);
         if (err) {
             g->io_errno = err;

@@ -696,6 +696,107 @@ static void grid_plans() {
     Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
 }
 
+// --------------------------------------------------------------------------------------------------------- dev-mem
+// The owners of dev_mem.hpp on a host without a device (every allocation fails), the scratch layouts, the table of debug switches on a
+// context that lives on the stack.  No kernel is launched and no context is made through gyp_create.
+template <class T>
+static int64_t offset_of(const T* p, const void* base) { return (int64_t)((const uint8_t*)p - (const uint8_t*)base); }
+static void dev_mem() {
+    {
+        DevBuf<float> a;
+        REQUIRE(a.reserve(0, Slack::grow) == hipSuccess && a.get() == nullptr && a.capacity() == 0);   // enough already: nothing is asked of HIP
+        REQUIRE(a.reserve(100, Slack::grow) != hipSuccess);
+        REQUIRE(a.get() == nullptr && a.capacity() == 0);
+        REQUIRE(a.reserve(7, Slack::exact, (hipStream_t) nullptr, (hipStream_t) nullptr) != hipSuccess);   // again, after the failure
+        REQUIRE(a.get() == nullptr && a.capacity() == 0);
+        DevBuf<float> b(std::move(a));
+        DevBuf<float> c;
+        c = std::move(b);
+        REQUIRE(a.get() == nullptr && b.get() == nullptr && c.get() == nullptr && c.capacity() == 0);
+        float* host = (float*)std::malloc(4 * sizeof(float));
+        REQUIRE(upload(c, host, 4, nullptr) != hipSuccess && c.get() == nullptr && c.capacity() == 0);
+        std::free(host);
+        REQUIRE(c.release() == nullptr && c.reset() == hipSuccess);
+        std::vector<DevBuf<uint8_t>> ring(3);
+        for (auto& r : ring) REQUIRE(r.reserve(4096, Slack::exact) != hipSuccess && r.get() == nullptr);
+        ring.resize(40);   // moved
+        Event e;
+        Stream s;
+        if (e.create(hipEventDisableTiming) != hipSuccess) REQUIRE(e.get() == nullptr);
+        if (s.create(hipStreamNonBlocking) != hipSuccess) REQUIRE(s.get() == nullptr);
+        Event e2(std::move(e));
+        Stream s2(std::move(s));
+        REQUIRE(e.get() == nullptr && s.get() == nullptr);
+        PinnedBuf p;
+        p.adopt(std::malloc(100));
+        REQUIRE(p.get() != nullptr);
+        std::memset(p.get(), 1, 100);
+        PinnedBuf q(std::move(p));
+        REQUIRE(p.get() == nullptr && q.get()[99] == 1);
+        PinnedBuf pinned;
+        if (pinned.alloc(64) != hipSuccess) REQUIRE(pinned.get() == nullptr);
+    }
+    {   // layouts.i64: n_cells, n_rows, max_units.  carve.i64: per layout the offsets of its arrays in their order, then its size
+        const std::vector<int64_t> in = read_array<int64_t>("layouts.i64");
+        REQUIRE(in.size() == 3);
+        const size_t n_cells = (size_t)in[0], n_rows = (size_t)in[1], max_units = (size_t)in[2];
+        Out o("carve.i64");
+        void* base = nullptr;
+        REQUIRE(posix_memalign(&base, 256, 1 << 20) == 0);
+        const AcqBook b0 = acq_book_layout(nullptr, n_cells), b = acq_book_layout(base, n_cells);
+        REQUIRE(b0.prev_out == nullptr && b0.n_pend == nullptr && b0.bytes == b.bytes);
+        REQUIRE(b.bytes == n_cells * (sizeof(gyp_cell) + 3 * sizeof(int32_t)) + 64);   // the size this buffer was always given
+        REQUIRE((uint8_t*)(b.prev_out + n_cells) <= (uint8_t*)b.reuse && b.reuse + n_cells <= b.order && b.order + n_cells <= b.cand &&
+                b.cand + n_cells <= b.n_active && b.n_active + 1 <= b.n_cand && b.n_cand + 1 <= b.n_pend && (uint8_t*)(b.n_pend + 1) <= (uint8_t*)base + b.bytes);
+        for (int64_t v : {offset_of(b.prev_out, base), offset_of(b.reuse, base), offset_of(b.order, base), offset_of(b.cand, base),
+                          offset_of(b.n_active, base), offset_of(b.n_cand, base), offset_of(b.n_pend, base), (int64_t)b.bytes})
+            o.i64(v);
+        const size_t n_grid = n_rows * 7;   // a refine call's cells: rows x bins
+        GridRefineParams r{}, r0{};
+        const size_t rb = refine_list_layout(base, n_rows, n_grid, &r);
+        REQUIRE(refine_list_layout(nullptr, n_rows, n_grid, &r0) == rb && r0.cand == nullptr && rb == (n_grid + 2 * n_rows + 4) * sizeof(int32_t));
+        REQUIRE(r.n_cand + 4 <= r.pend_rows && r.pend_rows + n_rows <= r.pend_first && r.pend_first + n_rows <= r.cand &&
+                (uint8_t*)(r.cand + n_grid) <= (uint8_t*)base + rb);
+        for (int64_t v : {offset_of(r.n_cand, base), offset_of(r.pend_rows, base), offset_of(r.pend_first, base), offset_of(r.cand, base), (int64_t)rb}) o.i64(v);
+        AcqUnits u{}, u0{};
+        const size_t ub = acq_units_layout(base, max_units, n_cells, &u);
+        REQUIRE(acq_units_layout(nullptr, max_units, n_cells, &u0) == ub && u0.unit_cell == nullptr && ub == (max_units + 2 * n_cells + 4) * sizeof(int32_t));
+        REQUIRE(u.unit_cell + max_units <= u.sh_cell && u.sh_cell + n_cells <= u.sh_unit && u.sh_unit + n_cells <= u.counts &&
+                (uint8_t*)(u.counts + 4) <= (uint8_t*)base + ub);
+        for (int64_t v : {offset_of(u.unit_cell, base), offset_of(u.sh_cell, base), offset_of(u.sh_unit, base), offset_of(u.counts, base), (int64_t)ub}) o.i64(v);
+        std::free(base);
+    }
+    {   // switches.txt: name, lo, hi, integral, inherited, default of every row
+        Out o("switches.txt");
+        gyp_ctx ctx;
+        for (const DebugSwitch& k : kDebugSwitches) {
+            size_t same = 0;
+            for (const DebugSwitch& other : kDebugSwitches) same += std::strcmp(k.name, other.name) == 0;
+            REQUIRE(same == 1);
+            double def = -777.0, got = -777.0;
+            REQUIRE(gyp_debug_get(&ctx, k.name, &def) == GYP_OK && k.lo <= def && def <= k.hi);
+            o.line(std::string(k.name) + " " + std::to_string(k.lo) + " " + std::to_string(k.hi) + " " + std::to_string((int)k.integral) + " " +
+                   std::to_string((int)k.inherited) + " " + std::to_string(def));
+            for (double v : {k.hi, k.lo}) {   // set, then get
+                REQUIRE(gyp_debug_set(&ctx, k.name, v) == GYP_OK && gyp_debug_get(&ctx, k.name, &got) == GYP_OK && got == v);
+            }
+            const double inf = std::numeric_limits<double>::infinity();
+            for (double v : {k.lo - 1.0, k.hi + 1.0, inf, -inf, std::numeric_limits<double>::quiet_NaN(), k.integral ? k.lo + 0.5 : inf}) {   // refused: the field stays
+                REQUIRE(gyp_debug_set(&ctx, k.name, v) == GYP_E_BAD_ARG && gyp_debug_get(&ctx, k.name, &got) == GYP_OK && got == k.lo);
+                REQUIRE(std::string(gyp_last_error(&ctx)).find(std::string("gyp_debug_set: ") + k.name + " must be ") == 0);
+            }
+            REQUIRE(gyp_debug_set(&ctx, k.name, def) == GYP_OK);
+        }
+        double got = 0.0;   // the two extra rules
+        REQUIRE(gyp_debug_set(&ctx, "track_chunk_ms", 19.0) == GYP_E_BAD_ARG && gyp_debug_set(&ctx, "track_chunk_ms", 20.0) == GYP_OK &&
+                gyp_debug_get(&ctx, "track_chunk_ms", &got) == GYP_OK && got == 20.0);
+        REQUIRE(gyp_debug_set(&ctx, "grid_fused_waves", 10.0) == GYP_E_BAD_ARG && gyp_debug_get(&ctx, "grid_fused_waves", &got) == GYP_OK && got == 12.0);
+        REQUIRE(gyp_debug_set(&ctx, "no_such_switch", 1.0) == GYP_E_BAD_ARG && gyp_debug_set(&ctx, "last_grid_path", 1.0) == GYP_E_BAD_ARG);
+        REQUIRE(gyp_debug_get(&ctx, "last_grid_path", &got) == GYP_OK && got == 0.0 && gyp_debug_get(&ctx, "last_exact_path", &got) == GYP_OK &&
+                gyp_debug_get(&ctx, "no_such_switch", &got) == GYP_E_BAD_ARG);
+    }
+}
+
 }  // namespace drv
 
 int main(int argc, char** argv) {
@@ -716,7 +817,7 @@ int main(int argc, char** argv) {
     const std::pair<const char*, void (*)()> table[] = {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
-        {"grid-plan", drv::grid_plans},
+        {"grid-plan", drv::grid_plans}, {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

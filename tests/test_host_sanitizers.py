@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -617,3 +617,36 @@ def test_grid_plan(programs, tmp_path):
         for field, value in zip(("path", "pipe", "waves", "gs", "parts"), expected):
             if value is not None:
                 assert row[grid_plan_model.FIELDS.index(field)] == value, (shape, field, row.tolist())
+
+
+# ------------------------------------------------------------------------------------------------------------ dev-mem
+# Byte offsets of the sub-arrays of the two scratch buffers that hold several arrays, and each buffer's size, for n_cells = 56,
+# n_rows = 3 (x 7 bins = 21 grid cells), max_units = 5; from the pointer arithmetic these buffers were carved with by hand:
+#   acquisition's bookkeeping: gyp_cell prev_out[n_cells] (32 bytes each), then int32 reuse[n_cells], order[n_cells], cand[n_cells],
+#     n_active, n_cand, n_pend; n_cells * (32 + 3 * 4) + 64 bytes
+#   the refine list: int32 n_cand[4], pend_rows[n_rows], pend_first[n_rows], cand[n_cells]; (n_cells + 2 n_rows + 4) * 4 bytes
+#   the shared-forward unit lists: int32 unit_cell[max_units], sh_cell[n_cells], sh_unit[n_cells], counts[4]; (max_units + 2 n_cells + 4) * 4 bytes
+CARVE_LITERALS = [0, 1792, 2016, 2240, 2464, 2468, 2472, 2528,
+                  0, 16, 28, 40, 124,
+                  0, 20, 244, 468, 484]
+INHERITED_SWITCHES = {"no_pipe", "no_shared_fwd", "no_acq_shared_fwd", "symbol_tau", "cells_cu_reserve", "track_chunk_ms", "no_spec"}
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_dev_mem(programs, tmp_path, which):
+    """The owners of dev_mem.hpp where every allocation fails (no device), the scratch layouts against the offsets above, and every row
+    of the table of debug switches on a context on the stack (the driver checks ranges, set / get and refusals itself)."""
+    d = indir(tmp_path)
+    i64([56, 3, 5]).tofile(d / "layouts.i64")
+    out = run(programs, which, "dev-mem", tmp_path)
+    assert np.fromfile(out / "carve.i64", dtype="<i8").tolist() == CARVE_LITERALS
+    rows = [line.split() for line in (out / "switches.txt").read_text().splitlines()]
+    names = [r[0] for r in rows]
+    assert len(rows) == 21 and len(set(names)) == len(names)
+    for name, lo, hi, integral, inherited, default in rows:
+        assert float(lo) <= float(default) <= float(hi), name
+    assert {r[0] for r in rows if r[4] == "1"} == INHERITED_SWITCHES
+    by_name = {r[0]: r for r in rows}
+    assert [float(x) for x in by_name["grid_fused_waves"][1:3]] == [8.0, 12.0] and float(by_name["grid_fused_waves"][5]) == 12.0
+    assert [float(x) for x in by_name["track_chunk_ms"][1:3]] == [0.0, 1e6] and float(by_name["track_chunk_ms"][5]) == 250.0
+    assert by_name["symbol_tau"][3] == "0" and by_name["dll_prov_bias"][3] == "0" and sum(r[3] == "0" for r in rows) == 2
