@@ -53,6 +53,10 @@ PACKING = np.dtype([("bits", "<i4"), ("real", "<i4"), ("order", "<i4"), ("reserv
 GYP_PACK_MSB_FIRST, GYP_PACK_LSB_FIRST = 0, 1
 IQ_STATS = np.dtype([("sum_re", "<f8"), ("sum_im", "<f8"), ("sum_sq", "<f8"), ("max_abs", "<f4"), ("n_clip", "<i4")], align=True)
 IQ_LEVEL = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("gain", "<f4"), ("reserved", "<i4")], align=True)
+TONE_REC = np.dtype([("re", "<f8"), ("im", "<f8")], align=True)
+NOTCH_TONES = np.dtype([("count", "<i4"), ("reserved", "<i4"), ("freq_hz", "<i8", (8,))], align=True)
+GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
+GYP_NOTCH_MAX_TONES = 8
 GYP_BIT_ZERO, GYP_BIT_ONE, GYP_BIT_UNKNOWN = 0, 1, 2
 GYP_COMM_ID_BYTES = 128
 # sizeof() of every record the header declares, derived from the mirrors above (tests/test_abi_and_host.py compiles the
@@ -61,7 +65,8 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_cell_desc": CELL_DESC.itemsize, "gyp_cell": CELL.itemsize, "gyp_acq_result": ACQ_RESULT.itemsize,
                 "gyp_chan_in": CHAN_IN.itemsize, "gyp_chan_out": CHAN_OUT.itemsize, "gyp_best_bin": BEST_BIN.itemsize,
                 "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize,
-                "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize}
+                "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize,
+                "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -77,7 +82,8 @@ EXPORTS = (
     "gyp_ingest_open gyp_ingest_close gyp_ingest_total_ms gyp_ingest_set_scale gyp_ingest_seek gyp_ingest_next_host gyp_ingest_next_dev gyp_ingest_times "
     "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc "
     "gyp_packed_span gyp_unpack_iq_dev gyp_resample_packed_dev gyp_ingest_open_packed "
-    "gyp_iq_stats_dev gyp_condition_iq_dev gyp_iq_level_from_stats gyp_ingest_set_level gyp_ingest_get_level gyp_ingest_calibrate"
+    "gyp_iq_stats_dev gyp_condition_iq_dev gyp_iq_level_from_stats gyp_ingest_set_level gyp_ingest_get_level gyp_ingest_calibrate "
+    "gyp_iq_tones_dev gyp_notch_iq_dev gyp_tones_find gyp_tone_refine gyp_ingest_set_notches gyp_ingest_get_notches gyp_ingest_find_tones"
 ).split()
 
 
@@ -205,6 +211,13 @@ def load() -> C.CDLL:
         "gyp_ingest_set_level": (C.c_int, [vp, vp]),
         "gyp_ingest_get_level": (C.c_int, [vp, vp, C.POINTER(i32)]),
         "gyp_ingest_calibrate": (C.c_int, [vp, i64, i32, i32, dbl, C.c_float, vp, vp]),
+        "gyp_iq_tones_dev": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i64, vp, i32, i32, vp]),
+        "gyp_notch_iq_dev": (C.c_int, [vp, vp, vp, i32, i64, i64, i32, i32, i64, vp]),
+        "gyp_tones_find": (C.c_int, [vp, i32, dbl, dbl, i32, i32, vp]),
+        "gyp_tone_refine": (C.c_int, [vp, i32, dbl, C.POINTER(dbl)]),
+        "gyp_ingest_set_notches": (C.c_int, [vp, vp, i32]),
+        "gyp_ingest_get_notches": (C.c_int, [vp, vp, C.POINTER(i32)]),
+        "gyp_ingest_find_tones": (C.c_int, [vp, i64, i32, dbl, i32, i32, vp, vp, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

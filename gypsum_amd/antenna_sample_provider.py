@@ -199,11 +199,16 @@ class AntennaSampleProviderResampled(_CursorProvider):
 
     `level` (a gypsum_amd.level.IqLevel) or `calibrate` (a dict of `IqFileIngest.calibrate`'s arguments, `{}` for its defaults;
     applied once after opening) removes a DC offset and normalises the amplitude of every sample served: what an offset-binary
-    uint8 recording needs before it can be acquired.  The two exclude each other."""
+    uint8 recording needs before it can be acquired.  The two exclude each other.
+
+    `notches` (a list of whole Hz) or `find_tones` (True, or a dict of `IqFileIngest.find_tones`'s arguments; applied once after
+    opening) removes CW interference from every sample served (gypsum_amd.notch); the two exclude each other.  The chain is
+    producer -> notches -> level, and tones are found and installed BEFORE `calibrate` measures: its level is the notched output's."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
                  sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
-                 engine=None, device: int = 0, if_hz: int | None = None, packing=None, level=None, calibrate: dict | None = None) -> None:
+                 engine=None, device: int = 0, if_hz: int | None = None, packing=None, level=None, calibrate: dict | None = None,
+                 notches=None, find_tones=None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
         from .resample import default_ddc_rate, nearest_supported_rate
@@ -221,6 +226,8 @@ class AntennaSampleProviderResampled(_CursorProvider):
             raise TypeError("sample_rate is required when no InputFileInfo is given")
         if level is not None and calibrate is not None:
             raise ValueError("level and calibrate exclude each other: a level is either given or measured")
+        if notches is not None and find_tones:
+            raise ValueError("notches and find_tones exclude each other: tones are either given or found")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
         self.if_hz = None if if_hz is None else int(if_hz)
@@ -252,6 +259,12 @@ class AntennaSampleProviderResampled(_CursorProvider):
                                         resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
             if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
                 self._ingest.set_scale(scale)
+        self.tones = None                        # [(Hz, dB over the median), ...] where find_tones ran
+        if notches is not None:
+            self._ingest.set_notches(notches)
+        elif find_tones:
+            self.tones = self._ingest.find_tones(**(find_tones if isinstance(find_tones, dict) else {}))
+        self.notches = self._ingest.notches
         self.level = level
         if level is not None:
             self._ingest.set_level(level)

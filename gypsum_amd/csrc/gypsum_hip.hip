@@ -171,6 +171,8 @@ struct gyp_ctx {
                                   // workgroups per CU); same output for any value
     std::vector<std::pair<ResampleDesign, DevBuf<float>>> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps), with the owner of its d_taps
     std::vector<std::pair<std::vector<float>, DevBuf<float>>> packed_levels;   // packed recordings: each level table met, in device memory
+    bool notch_no_lds = false;    // A/B switch: iq_notch_kernel keeps the residual in the output buffer at every rate (same bits)
+    DevBuf<int64_t> tone_freqs;   // gyp_iq_tones_dev: the call's frequencies (f mod fs) in device memory
     int track_chunk_ms = 250;     // the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
     float symbol_tau = 1e-4f;     // |Re peak| / |peak| below which the pseudosymbol is decided in float64 (test hook: 10 = always)
     bool no_shared_fwd = false;   // A/B switch: flat grids transform every cell's rows themselves again
@@ -2040,8 +2042,15 @@ static const DebugSwitch* debug_switch(const char* name) {
         if (std::strcmp(name, k.name) == 0) return &k;
     return nullptr;
 }
+// "notch_no_lds" 0/1, set and read like a row of kDebugSwitches (whose rows the host driver of the sanitizer tests enumerates)
+static bool debug_is_notch_switch(const char* name) { return std::strcmp(name, "notch_no_lds") == 0; }
 int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
     if (!ctx || !name) return GYP_E_BAD_ARG;
+    if (debug_is_notch_switch(name)) {
+        if (value != 0.0 && value != 1.0) return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: notch_no_lds must be 0 or 1");
+        ctx->notch_no_lds = value != 0.0;
+        return GYP_OK;
+    }
     const DebugSwitch* k = debug_switch(name);
     if (!k) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);
     if (!std::isfinite(value) || value < k->lo || value > k->hi || (k->integral && value != std::floor(value)))
@@ -2056,6 +2065,7 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
 }
 int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
+    if (debug_is_notch_switch(name)) { *out = ctx->notch_no_lds ? 1.0 : 0.0; return GYP_OK; }
     if (const DebugSwitch* k = debug_switch(name)) { *out = k->get(*ctx); return GYP_OK; }
     const int rc = debug_read_only(ctx, name, out);
     if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");
@@ -2695,6 +2705,127 @@ int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t sam
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------------------
+// Notch (kernels_notch.hpp): complex amplitudes of tones per block, their per-millisecond projection out of the samples
+// ---------------------------------------------------------------------------------------------------------
+static bool tone_rate_ok(int64_t fs_hz) { return fs_hz >= 1000 && fs_hz < ((int64_t)1 << 31); }
+static ToneMix tone_mix(int64_t fs_hz) { return ToneMix{fs_hz, 4.0 / (double)fs_hz, 0.5 / (double)fs_hz}; }
+
+// Enqueue iq_tones_kernel on the context's stream for frequencies already in device memory (f mod fs each).
+static int tones_launch(gyp_ctx* ctx, const float* iq, int32_t n_streams, int64_t stride, int64_t first_index, int32_t n_blocks,
+                        int32_t block_samples, int64_t fs_hz, const int64_t* freqs_dev, int32_t n_freq, int32_t window, gyp_tone_rec* out) {
+    const int64_t n_items = (int64_t)n_streams * n_blocks * n_freq;
+    const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * 8);
+    hipLaunchKernelGGL(iq_tones_kernel, dim3(grid), dim3(256), 0, ctx->stream, reinterpret_cast<const float2*>(iq), stride, first_index,
+                       n_blocks, block_samples, freqs_dev, n_freq, tone_mix(fs_hz), window, n_items, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+
+// The call's frequencies as f mod fs in the context's table.  Waits for the copy: the host array is the caller's.
+static int tones_upload_freqs(gyp_ctx* ctx, const int64_t* freqs_hz, int32_t n_freq, int64_t fs_hz) {
+    std::vector<int64_t> r((size_t)n_freq);
+    for (int32_t k = 0; k < n_freq; ++k) r[(size_t)k] = tone_mod(freqs_hz[k], fs_hz);
+    HIP_TRY(ctx, upload(ctx->tone_freqs, r.data(), r.size(), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GYP_OK;
+}
+
+// Enqueue iq_notch_kernel on `stream`, kNotchStreams streams per launch (their tone lists are a kernel argument): one workgroup per
+// (stream, millisecond) over the widen kernel's persistent grid.  The lists have passed notch_check.
+static int notch_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride, int64_t first_index,
+                        int32_t n_ms, int32_t n, int64_t fs_hz, const gyp_notch_tones* tones) {
+    const bool lds = n <= kNotchLdsSamples && !ctx->notch_no_lds;
+    const size_t lds_bytes = lds ? (size_t)n * sizeof(float2) : 0;
+    for (int32_t s0 = 0; s0 < n_streams; s0 += kNotchStreams) {
+        const int32_t ns = std::min<int32_t>(kNotchStreams, n_streams - s0);
+        NotchArgs a{};
+        for (int32_t i = 0; i < ns; ++i) {
+            a.count[i] = tones[s0 + i].count;
+            for (int32_t k = 0; k < a.count[i]; ++k) a.f[i][k] = tone_mod(tones[s0 + i].freq_hz[k], fs_hz);
+        }
+        const int64_t n_items = (int64_t)ns * n_ms;
+        const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
+        const float2* src = reinterpret_cast<const float2*>(in) + s0 * stride;
+        float2* dst = reinterpret_cast<float2*>(out) + s0 * stride;
+        const int rc = lds ? launch_dyn(ctx, iq_notch_kernel<true>, dim3(grid), dim3(kNotchThreads), lds_bytes, stream, src, dst, stride,
+                                        first_index, n_ms, n, n_items, tone_mix(fs_hz), a)
+                           : launch_dyn(ctx, iq_notch_kernel<false>, dim3(grid), dim3(kNotchThreads), 0, stream, src, dst, stride,
+                                        first_index, n_ms, n, n_items, tone_mix(fs_hz), a);
+        if (rc) return rc;
+    }
+    return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_iq_tones_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_sample_index,
+                     int32_t n_blocks, int32_t block_samples, int64_t fs_hz, const int64_t* freqs_hz_host, int32_t n_freq, int32_t window,
+                     gyp_tone_rec* out_dev) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_tones_dev: ctx is NULL");
+    if (!iq_dev || !out_dev || !freqs_hz_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: iq_dev, freqs_hz_host and out_dev must not be NULL");
+    if (n_streams < 1 || n_blocks < 1 || block_samples < 1 || n_freq < 1 || first_sample_index < 0)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: n_streams, n_blocks, block_samples and n_freq must be >= 1, first_sample_index >= 0");
+    if (n_streams > 1 && stream_stride_samples < (int64_t)n_blocks * block_samples)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: stream_stride_samples must be >= n_blocks * block_samples");
+    if (!tone_rate_ok(fs_hz)) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: fs_hz must lie in [1000, 2^31)");
+    if (window != GYP_WINDOW_RECT && window != GYP_WINDOW_HANN)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: window must be GYP_WINDOW_RECT or GYP_WINDOW_HANN");
+    for (int32_t k = 0; k < n_freq; ++k) {
+        const int64_t f = freqs_hz_host[k];
+        if (f <= -fs_hz || f >= fs_hz || 2 * (f < 0 ? -f : f) >= fs_hz)
+            return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: every frequency must satisfy |f| < fs / 2");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (const int rc = tones_upload_freqs(ctx, freqs_hz_host, n_freq, fs_hz)) return rc;
+    return tones_launch(ctx, iq_dev, n_streams, stream_stride_samples, first_sample_index, n_blocks, block_samples, fs_hz,
+                        ctx->tone_freqs.get(), n_freq, window, out_dev);
+}
+
+int gyp_notch_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
+                     int64_t first_sample_index, int32_t n_ms, int32_t samples_per_ms, int64_t fs_hz, const gyp_notch_tones* tones_host) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_notch_iq_dev: ctx is NULL");
+    if (!in_dev || !out_dev || !tones_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: in_dev, out_dev and tones_host must not be NULL");
+    if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || first_sample_index < 0 ||
+        (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, samples_per_ms >= 1, first_sample_index >= 0, "
+                                        "stream_stride_samples >= n_ms * samples_per_ms)");
+    if (!tone_rate_ok(fs_hz)) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: fs_hz must lie in [1000, 2^31)");
+    for (int32_t s = 0; s < n_streams; ++s) {
+        if (tones_host[s].reserved != 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: tones.reserved must be 0");
+        if (const char* why = notch_check(tones_host[s].freq_hz, tones_host[s].count, fs_hz))
+            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_notch_iq_dev: ") + why);
+    }
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return notch_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, first_sample_index, n_ms, samples_per_ms, fs_hz,
+                        tones_host);
+}
+
+int gyp_tones_find(const double* power, int32_t n_freq, double freq_step_hz, double threshold_over_median, int32_t min_separation_bins,
+                   int32_t max_tones, int32_t* out_bins) {
+    if (!power || (!out_bins && max_tones > 0)) return fail(nullptr, GYP_E_BAD_ARG, "gyp_tones_find: power and out_bins must not be NULL");
+    if (n_freq < 1 || min_separation_bins < 1 || max_tones < 0)
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_tones_find: n_freq and min_separation_bins must be >= 1, max_tones >= 0");
+    if (!(freq_step_hz > 0.0) || !std::isfinite(freq_step_hz) || !(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_tones_find: freq_step_hz and threshold_over_median must be positive and finite");
+    const char* why = nullptr;
+    const int32_t n = tones_find(power, n_freq, threshold_over_median, min_separation_bins, max_tones, out_bins, &why);
+    if (n < 0) return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_tones_find: ") + why);
+    return n;
+}
+
+int gyp_tone_refine(const gyp_tone_rec* records, int32_t n_blocks, double block_seconds, double* delta_hz_out) {
+    if (!records || !delta_hz_out) return fail(nullptr, GYP_E_BAD_ARG, "gyp_tone_refine: records and delta_hz_out must not be NULL");
+    if (n_blocks < 2) return fail(nullptr, GYP_E_BAD_ARG, "gyp_tone_refine: n_blocks must be >= 2");
+    if (!(block_seconds > 0.0) || !std::isfinite(block_seconds))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_tone_refine: block_seconds must be positive and finite");
+    *delta_hz_out = tone_refine(records, n_blocks, block_seconds);
+    return GYP_OK;
+}
+
+}  // extern "C"
+
 static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
     if (g->ctx) {
@@ -2716,7 +2847,11 @@ static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, co
 }
 
 // A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
-static int ingest_condition(gyp_ingest* g, int d, int32_t n_ms) {
+static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms) {
+    if (g->notches.count > 0)   // chain order: producer -> notches -> level
+        if (const int rc = notch_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, first_ms * g->n, n_ms,
+                                        g->n, g->fs, &g->notches))
+            return rc;
     if (!g->level_on) return GYP_OK;
     return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * g->n, &g->level);
 }
@@ -2774,7 +2909,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
             HIP_TRY(ctx, hipGetLastError());
         }
     }
-    if (const int lrc = ingest_condition(g, d, u->n_ms)) return lrc;
+    if (const int lrc = ingest_condition(g, d, u->first_ms, u->n_ms)) return lrc;
     HIP_TRY(ctx, hipEventRecord(g->ready[d].get(), g->copy_stream.get()));
     g->in_flight.push_back(*u);
     ++g->dev_blocks;
@@ -3014,6 +3149,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     if (g->resampled) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
     if (g->packed) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
     if (g->level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    if (g->notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3136,6 +3272,157 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     if (rc) return fail(ctx, rc, why);
     if (rc_back) return rc_back;
     if (level_out) *level_out = level;
+    return GYP_OK;
+}
+
+int gyp_ingest_set_notches(gyp_ingest* g, const int64_t* freqs_hz, int32_t n) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_notches: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_notches: the handle was opened without a context (notches apply to device blocks)");
+    if (!freqs_hz) n = 0;
+    if (const char* why = notch_check(freqs_hz, n, g->fs)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_notches: ") + why);
+    gyp_notch_tones t{};
+    t.count = n;
+    for (int32_t i = 0; i < n; ++i) t.freq_hz[i] = freqs_hz[i];
+    g->notches = t;
+    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old list: drop it and read it again
+}
+
+int gyp_ingest_get_notches(const gyp_ingest* g, int64_t* freqs_out8, int32_t* n_out) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: the handle was opened without a context (notches apply to device blocks)");
+    if (freqs_out8)
+        for (int32_t i = 0; i < g->notches.count; ++i) freqs_out8[i] = g->notches.freq_hz[i];
+    if (n_out) *n_out = g->notches.count;
+    return GYP_OK;
+}
+
+int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double threshold, int32_t max_tones, int32_t install,
+                          int64_t* freqs_out, double* power_db_out, int32_t* n_out) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_tones: handle is NULL");
+    gyp_ctx* ctx = g->ctx;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_tones: the handle was opened without a context (the scan runs on the device)");
+    if (!n_out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: n_out is NULL");
+    *n_out = 0;
+    if (n_ms < 1 || n_ms > 1000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 1000");
+    if (!(threshold > 0.0) || !std::isfinite(threshold) || max_tones < 1 || max_tones > GYP_NOTCH_MAX_TONES)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: threshold must be positive and finite, 1 <= max_tones <= 8");
+    const int64_t fs = g->fs, total = (int64_t)n_ms * g->n, first_index = first_ms * g->n;
+    if (!tone_rate_ok(fs) || total < kScanBlock)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: the range must hold at least 1024 samples at a rate in [1000, 2^31) Hz");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    constexpr int32_t n_grid = 2 * kScanHalf + 1;
+    const int32_t n_scan = (int32_t)(total / kScanBlock), n_fine = (int32_t)(total / kScanFine);
+    DevBuf<float> iq_all;
+    DevBuf<gyp_tone_rec> recs_dev;
+    HIP_TRY(ctx, iq_all.reserve((size_t)total * 2, Slack::exact));
+    HIP_TRY(ctx, recs_dev.reserve(std::max<size_t>((size_t)n_scan * n_grid, (size_t)n_fine * GYP_NOTCH_MAX_TONES), Slack::exact));
+    const bool level_was_on = g->level_on;
+    const gyp_notch_tones notches_were = g->notches;
+    const int64_t back_to = g->consumer_ms;
+    g->level_on = false;          // the blocks below are the producer's output: no notches, no level
+    g->notches = gyp_notch_tones{};
+    std::vector<gyp_tone_rec> recs;
+    std::vector<int64_t> found;
+    std::vector<double> found_db;
+    // records of `freqs` over n_blocks blocks of block_samples samples of the gathered range, block-major, in `recs`
+    auto measure = [&](const std::vector<int64_t>& freqs, int32_t n_blocks, int32_t block_samples, int32_t window) -> int {
+        if (const int rc = tones_upload_freqs(ctx, freqs.data(), (int32_t)freqs.size(), fs)) return rc;
+        if (const int rc = tones_launch(ctx, iq_all.get(), 1, 0, first_index, n_blocks, block_samples, fs, ctx->tone_freqs.get(),
+                                        (int32_t)freqs.size(), window, recs_dev.get()))
+            return rc;
+        recs.resize((size_t)n_blocks * freqs.size());
+        HIP_TRY(ctx, hipMemcpyAsync(recs.data(), recs_dev.get(), recs.size() * sizeof(gyp_tone_rec), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return GYP_OK;
+    };
+    // one refinement step of every tone found: the phase slope over blocks of block_samples samples, rounded to whole Hz
+    auto refine = [&](int32_t n_blocks, int32_t block_samples, int32_t window) -> int {
+        if (const int rc = measure(found, n_blocks, block_samples, window)) return rc;
+        std::vector<gyp_tone_rec> col((size_t)n_blocks);
+        for (size_t t = 0; t < found.size(); ++t) {
+            for (int32_t b = 0; b < n_blocks; ++b) col[(size_t)b] = recs[(size_t)b * found.size() + t];
+            const double delta = tone_refine(col.data(), n_blocks, (double)block_samples / (double)fs);
+            const int64_t f = found[t] + (int64_t)std::llrint(delta);
+            if (2 * (f < 0 ? -f : f) < fs) found[t] = f;
+        }
+        return GYP_OK;
+    };
+    auto search = [&]() -> int {
+        if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
+        for (int32_t done = 0; done < n_ms;) {
+            const float* iq = nullptr;
+            int64_t first = 0;
+            int32_t count = 0;
+            if (const int rc = gyp_ingest_next_dev(g, &iq, &first, &count)) return rc;
+            if (count == 0 || first != first_ms + done) return fail(ctx, GYP_E_IO, "gyp_ingest_find_tones: the recording ended inside the range");
+            const int32_t take = std::min(count, n_ms - done);
+            HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * g->n, iq, (size_t)take * g->n * 2 * sizeof(float),
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+            done += take;
+        }
+        // 1. the scan
+        std::vector<int64_t> grid((size_t)n_grid);
+        for (int32_t k = 0; k < n_grid; ++k) grid[(size_t)k] = scan_freq(k - kScanHalf, fs);
+        if (const int rc = measure(grid, n_scan, kScanBlock, GYP_WINDOW_HANN)) return rc;
+        std::vector<double> power((size_t)n_grid, 0.0);
+        for (int32_t b = 0; b < n_scan; ++b)
+            for (int32_t k = 0; k < n_grid; ++k) {
+                const gyp_tone_rec& r = recs[(size_t)b * n_grid + k];
+                power[(size_t)k] += r.re * r.re + r.im * r.im;
+            }
+        for (double& p : power) p /= (double)n_scan;
+        // 2. candidates, without the offset at 0 Hz and without what the window leaks from it and from stronger tones
+        constexpr int32_t kMaxCand = 256;
+        int32_t cand[kMaxCand];
+        const char* why = nullptr;
+        double median = 0.0;
+        const int32_t min_sep = (int32_t)((kNotchMinSeparationHz * kScanDiv + fs - 1) / fs) + 2;
+        const int32_t n_cand = tones_find(power.data(), n_grid, threshold, min_sep, kMaxCand, cand, &why, &median);
+        if (n_cand < 0) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_find_tones: the scan's spectrum: ") + why);
+        std::vector<int32_t> kept;
+        for (int32_t c = 0; c < n_cand && (int32_t)kept.size() < max_tones; ++c) {
+            const int32_t k = cand[c];
+            if (std::abs(k - kScanHalf) < 4) continue;
+            bool leak = power[(size_t)k] <= 4.0 * power[(size_t)kScanHalf] * scan_leakage(k - kScanHalf);
+            for (const int32_t j : kept) leak = leak || power[(size_t)k] <= 4.0 * power[(size_t)j] * scan_leakage(k - j);
+            if (!leak) kept.push_back(k);
+        }
+        for (const int32_t k : kept) {
+            found.push_back(grid[(size_t)k]);
+            found_db.push_back(10.0 * std::log10(power[(size_t)k] / median));
+        }
+        if (found.empty()) return GYP_OK;
+        // 3. refinement
+        // (Hann on the short blocks: behind a rectangular window of 64 samples an offset-binary file's offset or a stronger tone
+        // leaks into a weak tone's records at -30 dB and below and bends its phase slope)
+        if (const int rc = refine(n_fine, kScanFine, GYP_WINDOW_HANN)) return rc;
+        if (n_ms >= 2)
+            if (const int rc = refine(n_ms, g->n, GYP_WINDOW_RECT)) return rc;
+        return notch_check(found.data(), (int32_t)found.size(), fs)
+                   ? fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
+                   : GYP_OK;
+    };
+    const int rc = search();
+    const std::string why = ctx->err;
+    (void)hipStreamSynchronize(ctx->stream);   // nothing may still read the buffers or a block of the search
+    (void)iq_all.reset();
+    (void)recs_dev.reset();
+    g->level_on = level_was_on;
+    g->notches = notches_were;
+    if (rc == GYP_OK && install) {
+        g->notches = gyp_notch_tones{};
+        g->notches.count = (int32_t)found.size();
+        for (size_t t = 0; t < found.size(); ++t) g->notches.freq_hz[t] = found[t];
+    }
+    const int rc_back = gyp_ingest_seek(g, back_to);
+    if (rc) return fail(ctx, rc, why);
+    if (rc_back) return rc_back;
+    for (size_t t = 0; t < found.size(); ++t) {
+        if (freqs_out) freqs_out[t] = found[t];
+        if (power_db_out) power_db_out[t] = found_db[t];
+    }
+    *n_out = (int32_t)found.size();
     return GYP_OK;
 }
 

@@ -267,6 +267,9 @@ struct gyp_ingest {
     // in place on the copy stream behind whatever produced it
     bool level_on = false;
     gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
+    // notches (gyp_ingest_set_notches / gyp_ingest_find_tones): constants of the handle too; every device block is notched in place
+    // on the copy stream between its producer and the level
+    gyp_notch_tones notches{};
     int64_t consumer_ms = 0;        // where the next block handed out starts (set_level and calibrate seek back to it)
 
     // host ring, filled by the reader thread

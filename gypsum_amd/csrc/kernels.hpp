@@ -23,6 +23,8 @@
 //                       polyphase FIR, one phase per lane, its taps in registers, the tile's input span in LDS.
 //   iq_stats_kernel / iq_condition_kernel   signal conditioning: per-millisecond DC / power / peak / clipping records in a fixed
 //                       float64 reduction order, and y = (x - dc) * gain in place behind whatever produced an ingest block.
+//   iq_tones_kernel / iq_notch_kernel   narrowband interference: complex amplitudes of tones per block in a fixed float64 reduction
+//                       order (spectrum scan, refinement), and their per-millisecond sequential projection out of the samples.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -39,3 +41,4 @@
 #include "kernels_misc.hpp"
 #include "kernels_resample.hpp"
 #include "kernels_level.hpp"
+#include "kernels_notch.hpp"

@@ -324,6 +324,57 @@ class GypsumEngine:
             d.free()
         return out if x.ndim > 1 else out[0]
 
+    def iq_tones_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, first_sample_index: int, n_blocks: int, block_samples: int,
+                     fs_hz: int, freqs_hz, window: int, out_ptr: int) -> None:
+        """gyp_iq_tones_dev: one gyp_tone_rec per (stream, block, frequency) of complex64 samples in HBM, stream-major, then block, then
+        frequency, into out_ptr.  Enqueued, not synchronised."""
+        f = np.ascontiguousarray(freqs_hz, dtype=np.int64).reshape(-1)
+        self._check(self.lib.gyp_iq_tones_dev(self.ctx, C.c_void_p(iq_ptr), int(n_streams), int(stream_stride), int(first_sample_index),
+                                              int(n_blocks), int(block_samples), int(fs_hz), ptr(f), len(f), int(window), C.c_void_p(out_ptr)))
+
+    def notch_iq_dev(self, in_ptr: int, out_ptr: int, n_streams: int, stream_stride: int, first_sample_index: int, n_ms: int,
+                     samples_per_ms: int, fs_hz: int, tones) -> None:
+        """gyp_notch_iq_dev: the tones of stream s (gypsum_amd.notch.notch_records) projected out of every millisecond, in list order;
+        out_ptr may equal in_ptr.  Enqueued, not synchronised."""
+        from .notch import notch_records
+        recs = notch_records(tones, n_streams)
+        if len(recs) != int(n_streams):
+            raise ValueError(f"{len(recs)} tone lists for {n_streams} streams")
+        self._check(self.lib.gyp_notch_iq_dev(self.ctx, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n_streams), int(stream_stride),
+                                              int(first_sample_index), int(n_ms), int(samples_per_ms), int(fs_hz), ptr(recs)))
+
+    def iq_tones(self, iq: np.ndarray, fs_hz: int, freqs_hz, block_samples: int, window: int = 0, first_sample_index: int = 0) -> np.ndarray:
+        """Host convenience: the records (gypsum_amd.notch.TONE_DTYPE) of complex64 `iq` (2-D = one stream per row), shape
+        ([n_streams,] n_blocks, n_freq) over the whole blocks of block_samples samples it holds."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.int64).reshape(-1)
+        n_streams, n_blocks = rows.shape[0], rows.shape[1] // int(block_samples)
+        out = np.zeros((n_streams, n_blocks, len(f)), dtype=_lib.TONE_REC)
+        if out.size:
+            d_iq = self.alloc(rows.nbytes).upload(rows)
+            d_out = self.alloc(out.nbytes)
+            self.iq_tones_dev(d_iq.ptr.value, n_streams, rows.shape[1], first_sample_index, n_blocks, block_samples, fs_hz, f, window,
+                              d_out.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d_out.ptr, out.nbytes))
+            d_iq.free()
+            d_out.free()
+        return out if x.ndim > 1 else out[0]
+
+    def notch_iq(self, iq: np.ndarray, fs_hz: int, samples_per_ms: int, tones, first_sample_index: int = 0) -> np.ndarray:
+        """Host convenience: complex64 `iq` (2-D = one stream per row, one tone list each or one for all) with the tones projected out
+        of every whole millisecond on the device; a trailing part of a millisecond is returned as it is."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        out = rows.copy()
+        n_ms = rows.shape[1] // int(samples_per_ms)
+        if n_ms:
+            d = self.alloc(rows.nbytes).upload(rows)
+            self.notch_iq_dev(d.ptr.value, d.ptr.value, rows.shape[0], rows.shape[1], first_sample_index, n_ms, samples_per_ms, fs_hz, tones)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d.ptr, out.nbytes))
+            d.free()
+        return out if x.ndim > 1 else out[0]
+
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(_lib.GYP_COMM_ID_BYTES)
         rc = self.lib.gyp_comm_unique_id(buf)

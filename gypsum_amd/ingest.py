@@ -18,6 +18,9 @@ another rate are resampled, and a real packing (with `if_hz`) is down-converted.
 
 `set_level` / `calibrate` (gypsum_amd.level) remove a DC offset and normalise the amplitude of every device block, whatever
 produced it: an RTL-SDR uint8 recording needs no rewrite on the host.
+
+`set_notches` / `find_tones` (gypsum_amd.notch) remove narrowband (CW) interference from every device block, between whatever
+produced it and the level: `calibrate` then measures the notched output.
 """
 from __future__ import annotations
 
@@ -149,6 +152,29 @@ class IqFileIngest:
         self._check(self._lib.gyp_ingest_calibrate(self._h, int(first_ms), int(n_ms), int(bool(remove_dc)), target, float(clip_level),
                                                    _lib.ptr(rec), _lib.ptr(measured)))
         return IqLevel.from_record(rec), measured_dict(measured)
+
+    def set_notches(self, freqs_hz) -> None:
+        """Tones (whole Hz, at most 8, |f| < fs / 2, 4000 Hz apart) projected out of every device block from the next block handed
+        out on, between whatever produced the block and the level (gyp_ingest_set_notches).  None or an empty list switches them off."""
+        f = np.zeros(0, dtype=np.int64) if freqs_hz is None else np.ascontiguousarray(freqs_hz, dtype=np.int64).reshape(-1)
+        self._check(self._lib.gyp_ingest_set_notches(self._h, _lib.ptr(f) if len(f) else None, len(f)))
+
+    @property
+    def notches(self):
+        """The installed tones in Hz, in the order they are removed (empty: none)."""
+        f, n = np.zeros(_lib.GYP_NOTCH_MAX_TONES, dtype=np.int64), C.c_int32()
+        self._check(self._lib.gyp_ingest_get_notches(self._h, _lib.ptr(f), C.byref(n)))
+        return [int(x) for x in f[:n.value]]
+
+    def find_tones(self, first_ms: int = 0, n_ms: int = 10, threshold: float = 16.0, max_tones: int = 8, install: bool = True):
+        """Scan output milliseconds [first_ms, first_ms + n_ms) of the handle's output (no notches, no level) for CW tones on the
+        device: a Hann spectrum over +-0.45 fs on a grid of fs / 2048, its local maxima `threshold` times above the median, each
+        refined to a whole Hz.  Returns [(Hz, dB over the median), ...], strongest first, and installs them (install) as set_notches
+        does; the cursor stays where it was, blocks handed out earlier are no longer valid (gyp_ingest_find_tones)."""
+        f, db, n = np.zeros(_lib.GYP_NOTCH_MAX_TONES, dtype=np.int64), np.zeros(_lib.GYP_NOTCH_MAX_TONES), C.c_int32()
+        self._check(self._lib.gyp_ingest_find_tones(self._h, int(first_ms), int(n_ms), float(threshold), int(max_tones), int(bool(install)),
+                                                    _lib.ptr(f), _lib.ptr(db), C.byref(n)))
+        return [(int(f[i]), float(db[i])) for i in range(n.value)]
 
     def seek(self, ms: int) -> None:
         self._check(self._lib.gyp_ingest_seek(self._h, int(ms)))

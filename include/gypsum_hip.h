@@ -28,7 +28,10 @@
 extern "C" {
 #endif
 
-/* 209: signal conditioning on the device: gyp_iq_stats, gyp_iq_level, gyp_iq_stats_dev, gyp_condition_iq_dev, gyp_iq_level_from_stats,
+/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband
+ *      interference on the device: gyp_tone_rec, gyp_notch_tones, gyp_iq_tones_dev, gyp_notch_iq_dev, gyp_tones_find, gyp_tone_refine,
+ *      gyp_ingest_set_notches, gyp_ingest_get_notches, gyp_ingest_find_tones; gyp_debug_set name notch_no_lds.  Opt-in.
+ * 209: signal conditioning on the device: gyp_iq_stats, gyp_iq_level, gyp_iq_stats_dev, gyp_condition_iq_dev, gyp_iq_level_from_stats,
  *      gyp_ingest_set_level, gyp_ingest_get_level, gyp_ingest_calibrate.  Opt-in: nothing that existed changes.
  * 208: gyp_debug_set / gyp_debug_get name exact_prefetch removed (the software-prefetched form of dll_exact_wave_kernel it selected was
  *      measured slower and is gone); the name is refused like any unknown one.  Nothing else changes.
@@ -751,6 +754,110 @@ int gyp_ingest_get_level(const gyp_ingest* ing, gyp_iq_level* out, int32_t* enab
 int gyp_ingest_calibrate(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
                          gyp_iq_level* level_out, double* measured_out4);
 
+/* ---------------------------------------------------------------- notch: narrowband (CW) interference -- */
+/* A CW spur inside the band (a harmonic of an RTL-SDR's 28.8 MHz reference, a USB or clock spur, a jammer) far above the noise
+ * jams every Doppler bin.  The level above removes one frequency, 0 Hz; these calls find and remove tones at any whole number of
+ * Hz with |f| < fs / 2.  Everything is opt-in: with none of them called every other entry point gives the bits it gave before.
+ *
+ * Phase.  theta(i) = 2 pi ((f i) mod fs) / fs, i the ABSOLUTE index of the sample in its stream (first_sample_index + its offset
+ * in the buffer), reduced in integers; the device uses the float32 pair (cos theta, sin theta) of the down-converter's mixer,
+ * within 2^-22 of exact at any index and a pure function of (f, i).  fs_hz must lie in [1000, 2^31).
+ *
+ * Measurement (gyp_iq_tones_dev).  For each (stream, block b, frequency f) one record
+ *     A = (sum_n w[n] x[i0 + n] e^(-j theta(i0 + n))) / sum_n w[n],       i0 = first_sample_index + b * block_samples
+ * over the block's block_samples samples, w = 1 (GYP_WINDOW_RECT) or w[n] = sin^2(pi (n + 1) / (B + 1)) (GYP_WINDOW_HANN: nonzero
+ * on every sample; its sum is (B + 1) / 2, which is what the device divides by).  Products and sums are float64 over the float32
+ * mixer value: per sample (x_re c - x_im s', x_re s' + x_im c) with s' = -sin theta (the four products are exact, the difference
+ * and the sum one rounding each), times w[n] (Hann only), added to the owning thread's accumulator.  Thread t of 256 owns samples
+ * n = t, t + 256, ...; the partial sums are reduced by a fixed tree (in-wave, then across the wavefronts through LDS), without
+ * floating-point atomics and without contraction, as the statistics above: the same record bits for every grid size, every
+ * sub-window of the same buffer (same absolute indices) and every row alignment. */
+typedef struct gyp_tone_rec {   /* 16 bytes */
+    double re, im;
+} gyp_tone_rec;
+#define GYP_WINDOW_RECT 0
+#define GYP_WINDOW_HANN 1
+#define GYP_NOTCH_MAX_TONES 8
+/* iq_dev: complex64, stream s at sample s * stream_stride_samples, any 8-byte aligned address; no stream format is needed.
+ * freqs_hz_host: n_freq whole Hz, |f| < fs / 2 (copied before the call returns).  out_dev: n_streams x n_blocks x n_freq records,
+ * stream-major, then block, then frequency.  Enqueued on the context's stream (the call waits for the upload of the frequency
+ * list).  GYP_E_BAD_ARG for NULL pointers, counts < 1, first_sample_index < 0, a stride below n_blocks * block_samples when
+ * n_streams > 1, an fs_hz or a frequency out of range, or a window that is neither of the two. */
+int gyp_iq_tones_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_sample_index,
+                     int32_t n_blocks, int32_t block_samples, int64_t fs_hz, const int64_t* freqs_hz_host, int32_t n_freq, int32_t window,
+                     gyp_tone_rec* out_dev);
+
+/* Removal.  Per (stream, millisecond of samples_per_ms samples) and for the stream's tones t = 0 .. count-1 IN LIST ORDER -- a
+ * sequential projection:
+ *     A_t = the rectangular measurement above over the millisecond, taken on the residual y_(t-1) that tones 0 .. t-1 left
+ *           (y_(-1) = x; 1024 threads: thread t owns samples t, t + 1024, ...), then a = ((float)Re A_t, (float)Im A_t)
+ *     y_t = y_(t-1) - a e^(+j theta_t) in float32:  p_re = a_re c - a_im s,  p_im = a_re s + a_im c  (four products, then the
+ *           difference and the sum), y_re = y_re - p_re, y_im = y_im - p_im: one float32 rounding per operation, no contraction.
+ * The amplitude is a per-millisecond estimate, the frequencies are constants of the call: the same samples come out for every
+ * n_streams / n_ms split, window and grid size.  A tone 50 Hz off its listed frequency is still suppressed by about 20 dB
+ * (|1 - sinc|-like residual of a one-millisecond projection); re-run gyp_ingest_find_tones for recordings that drift further.
+ * The projection also takes the part of the wanted signal that lies on the tone: 1 / samples_per_ms of the power per tone.
+ * An empty list returns the input bits.  out_dev may equal in_dev; other overlaps are not allowed. */
+typedef struct gyp_notch_tones {   /* one per stream: 72 bytes */
+    int32_t count;                 /* 0 .. GYP_NOTCH_MAX_TONES */
+    int32_t reserved;              /* must be 0 */
+    int64_t freq_hz[GYP_NOTCH_MAX_TONES];   /* |f| < fs / 2, pairwise at least 4000 Hz apart (over 1 ms closer tones are far from orthogonal) */
+} gyp_notch_tones;
+/* Enqueued on the context's stream; tones_host (n_streams records) may be reused as soon as the call returns.  GYP_E_BAD_ARG for
+ * NULL pointers, n_streams < 1, n_ms < 0, samples_per_ms < 1, first_sample_index < 0, a stride below n_ms * samples_per_ms when
+ * n_streams > 1, fs_hz out of range, or a tone list that breaks the rules above (count > 8, |f| >= fs / 2, two tones closer than
+ * 4000 Hz, reserved != 0). */
+int gyp_notch_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
+                     int64_t first_sample_index, int32_t n_ms, int32_t samples_per_ms, int64_t fs_hz, const gyp_notch_tones* tones_host);
+
+/* Host only (no GPU; errors through gyp_last_error(NULL)).  The tones of a power spectrum power[0 .. n_freq) whose bins are
+ * freq_step_hz apart: bin k is a candidate if power[k] >= threshold_over_median * median(power) (the median of numpy: the mean of
+ * the two middle values for an even count), power[k] > 0, power[k] > power[k-1] (or k = 0) and power[k] >= power[k+1] (or
+ * k = n_freq - 1) -- of equal neighbours the lowest bin is the maximum.  Candidates are taken strongest first, of equal powers
+ * the lowest bin first; one that lies closer than min_separation_bins to a bin already taken is dropped; at most max_tones are
+ * written to out_bins.  Returns their number (>= 0), or GYP_E_BAD_ARG for NULL pointers, n_freq < 1, a power that is negative or
+ * not finite, a threshold or freq_step_hz that is not positive and finite, min_separation_bins < 1 or max_tones < 0. */
+int gyp_tones_find(const double* power, int32_t n_freq, double freq_step_hz, double threshold_over_median, int32_t min_separation_bins,
+                   int32_t max_tones, int32_t* out_bins);
+/* Host only.  The frequency offset of a tone from the frequency its records were measured at (n_blocks >= 2 consecutive blocks
+ * of block_seconds each), as the phase slope: float64, in exactly this order, one rounding per operation:
+ *     S = sum over b = 0 .. n_blocks-2, left to right, of A[b+1] conj(A[b]):
+ *         c_re = A[b+1].re A[b].re + A[b+1].im A[b].im,   c_im = A[b+1].im A[b].re - A[b+1].re A[b].im
+ *     *delta_hz_out = atan2(S_im, S_re) / (6.283185307179586 * block_seconds)
+ * Valid for |delta| < 1 / (2 block_seconds).  GYP_E_BAD_ARG for NULL pointers, n_blocks < 2 or block_seconds not positive and finite. */
+int gyp_tone_refine(const gyp_tone_rec* records, int32_t n_blocks, double block_seconds, double* delta_hz_out);
+
+/* Notches on an ingest handle (ctx required: a host-only handle returns GYP_E_BAD_ARG from all of these, and gyp_ingest_next_host
+ * returns GYP_E_BAD_ARG while notches are on).  CHAIN ORDER of a handle: producer (widen / unpack / resample / down-convert /
+ * copy) -> notches -> level.  Every device block is notched in place on the upload stream exactly as gyp_notch_iq_dev would, at
+ * the handle's output rate and with first_sample_index = the block's first millisecond * N, and conditioned with the level
+ * afterwards.  gyp_ingest_calibrate therefore measures the NOTCHED output when notches are installed, and only then: a level
+ * measured under a 40 dB jammer is useless, so find and install the tones first.
+ * gyp_ingest_set_notches (n = 0 or freqs_hz NULL: off) follows gyp_ingest_set_level: it takes effect with the next block handed
+ * out, and what was uploaded ahead is dropped and read again.  gyp_ingest_get_notches writes up to 8 frequencies and their count. */
+int gyp_ingest_set_notches(gyp_ingest* ing, const int64_t* freqs_hz, int32_t n);
+int gyp_ingest_get_notches(const gyp_ingest* ing, int64_t* freqs_out8, int32_t* n_out);
+/* Finds the tones in output milliseconds [first_ms, first_ms + n_ms) of the handle (inside [0, total_ms), 1 <= n_ms <= 1000).
+ * What is searched is the handle's output WITHOUT notches and without a level, read through the handle's own path into one
+ * buffer, so the result does not depend on block_ms; the cursor is put back, the call synchronises, and blocks handed out
+ * earlier are no longer valid afterwards.  Steps:
+ *   1. scan: gyp_iq_tones_dev with Hann blocks of 1024 samples at the 1843 frequencies round(k fs / 2048) Hz, |k| <= 921
+ *      (+-0.45 fs); the spectrum is the mean over the blocks, in block order, of re^2 + im^2 per frequency (float64);
+ *   2. gyp_tones_find on it with `threshold` over the median and a separation of ceil(4000 / (fs / 2048)) + 2 grid points (the refinement
+ *      moves a tone by less than one, so refined tones stay 4000 Hz apart) and up to 256 candidates.  A
+ *      candidate is then dropped if it lies within 4 grid points of 0 Hz (the offset is the level's to remove:
+ *      gyp_ingest_calibrate) or if its power is at most 4 times what the Hann window leaks there from 0 Hz or from a stronger
+ *      tone already kept (bound: (pi x (x^2 - 1))^-2 of the peak at x = distance / 2 grid points >= 2); the strongest max_tones
+ *      (<= 8) remain, strongest first;
+ *   3. each is refined twice with gyp_tone_refine and rounded to whole Hz after each step: on Hann blocks of 64 samples (range
+ *      +-fs / 128; Hann, so that the offset and stronger tones do not leak into a weak tone's records), then on rectangular
+ *      blocks of one millisecond (needs n_ms >= 2; skipped otherwise).
+ * freqs_out / power_db_out (room for max_tones; either may be NULL) receive the frequencies and 10 log10(power / median) of the
+ * scan; *n_out their number.  With install != 0 the tones are installed as gyp_ingest_set_notches does (none found: notches off).
+ * On an error the handle keeps the notches it had. */
+int gyp_ingest_find_tones(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, double threshold, int32_t max_tones, int32_t install,
+                          int64_t* freqs_out, double* power_db_out, int32_t* n_out);
+
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
  * with a message otherwise) and defaults:
@@ -785,6 +892,8 @@ int gyp_ingest_calibrate(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int32_
  *   "spec_debug" 0/1 (0)        per-ms window dump for gyp_debug_spec_read
  *   "track_chunk_ms" 0 | >= 20 (250)   launch length of the throughput tracking kernel (0: whole blocks)
  *   "resample_tile_samples" 1024..8192 (4096)  LDS budget of one resampler workgroup, in input samples; same output for any value
+ *   "notch_no_lds" 0/1 (0)      gyp_notch_iq_dev and the ingest's notches keep the millisecond's residual in the output buffer (the
+ *                               form rates above 16.384 Msps take) instead of LDS; same samples bit for bit
  *   "widen_wg_per_cu" 1..8 (2)  workgroups per CU of the widen kernel's persistent grid (gyp_widen_iq_dev, the ingest ring; the unpack,
  *                               statistics and condition kernels follow it); same output for any value
  *   "no_exact_shared" 0/1 (0)   the exact code-loop sums behind the throughput tracking kernel fetch and convert a stream's samples once per
