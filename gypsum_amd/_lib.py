@@ -55,6 +55,10 @@ IQ_STATS = np.dtype([("sum_re", "<f8"), ("sum_im", "<f8"), ("sum_sq", "<f8"), ("
 IQ_LEVEL = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("gain", "<f4"), ("reserved", "<i4")], align=True)
 TONE_REC = np.dtype([("re", "<f8"), ("im", "<f8")], align=True)
 NOTCH_TONES = np.dtype([("count", "<i4"), ("reserved", "<i4"), ("freq_hz", "<i8", (8,))], align=True)
+QUALITY_SUMS = np.dtype([("n_used", "<i4"), ("n_locked", "<i4"), ("n_groups", "<i4"), ("reserved", "<i4"), ("sum_p2", "<f8"),
+                         ("sum_p4", "<f8"), ("sum_np", "<f8"), ("sum_pl", "<f8")], align=True)
+QUALITY = np.dtype([("cn0_m2m4_dbhz", "<f8"), ("cn0_nwpr_dbhz", "<f8"), ("phase_lock", "<f8"), ("locked_share", "<f8"),
+                    ("n_used", "<i4"), ("n_groups", "<i4")], align=True)
 GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
 GYP_NOTCH_MAX_TONES = 8
 GYP_BIT_ZERO, GYP_BIT_ONE, GYP_BIT_UNKNOWN = 0, 1, 2
@@ -66,7 +70,8 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_chan_in": CHAN_IN.itemsize, "gyp_chan_out": CHAN_OUT.itemsize, "gyp_best_bin": BEST_BIN.itemsize,
                 "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize,
                 "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize,
-                "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize}
+                "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize,
+                "gyp_quality_sums": QUALITY_SUMS.itemsize, "gyp_quality": QUALITY.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -83,7 +88,8 @@ EXPORTS = (
     "gyp_resample_design gyp_resample_iq_dev gyp_ingest_open_resampled gyp_ddc_design gyp_ddc_iq_dev gyp_ingest_open_ddc "
     "gyp_packed_span gyp_unpack_iq_dev gyp_resample_packed_dev gyp_ingest_open_packed "
     "gyp_iq_stats_dev gyp_condition_iq_dev gyp_iq_level_from_stats gyp_ingest_set_level gyp_ingest_get_level gyp_ingest_calibrate "
-    "gyp_iq_tones_dev gyp_notch_iq_dev gyp_tones_find gyp_tone_refine gyp_ingest_set_notches gyp_ingest_get_notches gyp_ingest_find_tones"
+    "gyp_iq_tones_dev gyp_notch_iq_dev gyp_tones_find gyp_tone_refine gyp_ingest_set_notches gyp_ingest_get_notches gyp_ingest_find_tones "
+    "gyp_track_quality_dev gyp_track_quality gyp_quality_from_sums"
 ).split()
 
 
@@ -218,6 +224,9 @@ def load() -> C.CDLL:
         "gyp_ingest_set_notches": (C.c_int, [vp, vp, i32]),
         "gyp_ingest_get_notches": (C.c_int, [vp, vp, C.POINTER(i32)]),
         "gyp_ingest_find_tones": (C.c_int, [vp, i64, i32, dbl, i32, i32, vp, vp, C.POINTER(i32)]),
+        "gyp_track_quality_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, vp, vp]),
+        "gyp_track_quality": (C.c_int, [vp, vp, i32, i64, i32, i32, vp, vp]),
+        "gyp_quality_from_sums": (C.c_int, [vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

@@ -123,6 +123,8 @@ static thread_local std::string g_create_error;
 //   stage_out      results: gyp_correlate_cells, gyp_correlate_grid (gyp_cell), gyp_search_level, gyp_acquire (gyp_acq_result), gyp_track_step (gyp_chan_out), gyp_track_block (gyp_track_rec)
 //   stage_profile  optional profile rows: gyp_correlate_cells, gyp_track_step
 //   stage_times    start times: gyp_track_step (per stream), gyp_track_block (per millisecond)
+//   quality_recs, quality_sums   tracking records in, sums out: gyp_track_quality (roles of its own: its input is the kind of record
+//                  stage_out holds for gyp_track_block)
 // Working buffers of the *_dev functions; no wrapper uses these:
 //   sat_ids, doppler          satellite ids and Doppler bins: gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev
 //   folded, z, grid_partial   gyp_correlate_grid_dev: folded rows, the wide rates' wiped-off samples, partial results of branch runs
@@ -144,6 +146,8 @@ struct Scratch {
     DevBuf<gyp_cell_desc> acq_cells;
     DevBuf<gyp_cell> acq_out;
     DevBuf<gyp_synth_sat> synth_scene;
+    DevBuf<gyp_track_rec> quality_recs;
+    DevBuf<gyp_quality_sums> quality_sums;
 };
 
 // The tables of the 32 C/A codes on the device (gyp_set_stream_format builds them whole, or not at all)
@@ -2821,6 +2825,77 @@ int gyp_tone_refine(const gyp_tone_rec* records, int32_t n_blocks, double block_
     if (!(block_seconds > 0.0) || !std::isfinite(block_seconds))
         return fail(nullptr, GYP_E_BAD_ARG, "gyp_tone_refine: block_seconds must be positive and finite");
     *delta_hz_out = tone_refine(records, n_blocks, block_seconds);
+    return GYP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Signal quality (kernels_quality.hpp): per (channel, window) sums of tracking records, the figures derived from them
+// ---------------------------------------------------------------------------------------------------------
+// GYP_E_BAD_ARG's reason, or nullptr if the call can be launched.
+static const char* quality_check(const void* recs, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms, int32_t window_ms,
+                                 const int32_t* bit_offset, const void* out) {
+    if (!recs || !out) return "the records and the output must not be NULL";
+    if (n_chan < 1 || n_ms < 1 || window_ms < 1) return "n_chan, n_ms and window_ms must be >= 1";
+    if (n_chan > 1 && chan_stride_recs < n_ms) return "chan_stride_recs must be >= n_ms";
+    if (bit_offset)
+        for (int32_t c = 0; c < n_chan; ++c)
+            if (bit_offset[c] < -1 || bit_offset[c] >= kGroupMs) return "every bit offset must lie in -1 .. 19";
+    return nullptr;
+}
+
+// Enqueue track_quality_kernel on the context's stream, kQualityChans channels per launch (their bit offsets are a kernel
+// argument): one wavefront per (channel, window).  The arguments have passed quality_check.
+static int quality_launch(gyp_ctx* ctx, const gyp_track_rec* recs, int32_t n_chan, int64_t stride, int32_t n_ms, int32_t window_ms,
+                          const int32_t* bit_offset, gyp_quality_sums* out) {
+    const int32_t n_win = (int32_t)(((int64_t)n_ms + window_ms - 1) / window_ms);
+    for (int32_t c0 = 0; c0 < n_chan; c0 += kQualityChans) {
+        const int32_t nc = std::min<int32_t>(kQualityChans, n_chan - c0);
+        QualityArgs a;
+        for (int32_t i = 0; i < kQualityChans; ++i) a.bit_offset[i] = (int8_t)(bit_offset && i < nc ? bit_offset[c0 + i] : -1);
+        const int64_t n_items = (int64_t)nc * n_win;
+        const int grid = (int)std::min<int64_t>((n_items + 3) / 4, (int64_t)ctx->n_cus * 64);
+        hipLaunchKernelGGL(track_quality_kernel, dim3(grid), dim3(256), 0, ctx->stream, recs + (int64_t)c0 * stride, stride, n_ms, window_ms,
+                           n_win, n_items, a, out + (int64_t)c0 * n_win);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_track_quality_dev(gyp_ctx* ctx, const gyp_track_rec* recs_dev, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
+                          int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_dev) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_track_quality_dev: ctx is NULL");
+    if (const char* why = quality_check(recs_dev, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_dev))
+        return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_track_quality_dev: ") + why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return quality_launch(ctx, recs_dev, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_dev);
+}
+
+int gyp_track_quality(gyp_ctx* ctx, const gyp_track_rec* recs_host, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
+                      int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_host) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_track_quality: ctx is NULL");
+    if (const char* why = quality_check(recs_host, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_host))
+        return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_track_quality: ") + why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Scratch& sc = ctx->scratch;
+    const size_t n_recs = (size_t)(n_chan - 1) * (size_t)chan_stride_recs + (size_t)n_ms;
+    const size_t n_out = (size_t)n_chan * (size_t)(((int64_t)n_ms + window_ms - 1) / window_ms);
+    HIP_TRY(ctx, upload(sc.quality_recs, recs_host, n_recs, ctx->stream));
+    HIP_TRY(ctx, sc.quality_sums.reserve(n_out, Slack::grow, ctx->stream));
+    if (const int rc = quality_launch(ctx, sc.quality_recs.get(), n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, sc.quality_sums.get()))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, sc.quality_sums.get(), n_out * sizeof(gyp_quality_sums), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GYP_OK;
+}
+
+int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* out) {
+    if (!sums || !out) return fail(nullptr, GYP_E_BAD_ARG, "gyp_quality_from_sums: sums and out must not be NULL");
+    if (n < 1) return fail(nullptr, GYP_E_BAD_ARG, "gyp_quality_from_sums: n must be >= 1");
+    quality_from_sums(sums, n, out);
     return GYP_OK;
 }
 

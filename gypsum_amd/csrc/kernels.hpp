@@ -25,6 +25,8 @@
 //                       float64 reduction order, and y = (x - dc) * gain in place behind whatever produced an ingest block.
 //   iq_tones_kernel / iq_notch_kernel   narrowband interference: complex amplitudes of tones per block in a fixed float64 reduction
 //                       order (spectrum scan, refinement), and their per-millisecond sequential projection out of the samples.
+//   track_quality_kernel   signal quality: per (channel, window) sums of a block's tracking records -- peak moments, lock count,
+//                       narrow/wide-band power ratios of 20-ms groups -- one wavefront each, in a fixed float64 reduction order.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -42,3 +44,4 @@
 #include "kernels_resample.hpp"
 #include "kernels_level.hpp"
 #include "kernels_notch.hpp"
+#include "kernels_quality.hpp"

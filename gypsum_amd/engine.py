@@ -375,6 +375,27 @@ class GypsumEngine:
             d.free()
         return out if x.ndim > 1 else out[0]
 
+    def track_quality_dev(self, rec_ptr: int, n_chan: int, chan_stride: int, n_ms: int, window_ms: int, out_ptr: int,
+                          bit_offsets=None) -> None:
+        """gyp_track_quality_dev: one gyp_quality_sums record per (channel, window of window_ms records) of tracking records in HBM,
+        channel-major into out_ptr; bit_offsets: per channel -1..19, None = no groups.  Enqueued, not synchronised."""
+        from .quality import bit_offset_records
+        b = bit_offset_records(bit_offsets, n_chan)
+        self._check(self.lib.gyp_track_quality_dev(self.ctx, C.c_void_p(rec_ptr), int(n_chan), int(chan_stride), int(n_ms),
+                                                   int(window_ms), ptr(b), C.c_void_p(out_ptr)))
+
+    def track_quality(self, records: np.ndarray, window_ms: int, bit_offsets=None) -> np.ndarray:
+        """Host convenience (gyp_track_quality): the sums (gypsum_amd.quality.SUMS_DTYPE) of `records` (TRACK_REC, 2-D = one channel
+        per row), shape ([n_chan,] ceil(n_ms / window_ms))."""
+        from .quality import bit_offset_records
+        r = np.ascontiguousarray(records, dtype=TRACK_REC)
+        rows = r if r.ndim > 1 else r.reshape(1, -1)
+        n_chan, n_ms = rows.shape
+        b = bit_offset_records(bit_offsets, n_chan)
+        out = np.zeros((n_chan, -(-n_ms // int(window_ms)) if int(window_ms) > 0 else 0), dtype=_lib.QUALITY_SUMS)
+        self._check(self.lib.gyp_track_quality(self.ctx, ptr(rows), n_chan, n_ms, n_ms, int(window_ms), ptr(b), ptr(out)))
+        return out if r.ndim > 1 else out[0]
+
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(_lib.GYP_COMM_ID_BYTES)
         rc = self.lib.gyp_comm_unique_id(buf)
@@ -561,6 +582,12 @@ class ChannelBank:
         e = self.engine
         e._check(e.lib.gyp_track_block_dev(self.handle, C.c_void_p(iq_ptr), stream_stride, n_ms,
                                            C.c_void_p(start_times_ptr), C.c_void_p(rec_ptr or None)))
+
+    def quality_dev(self, rec_ptr: int, n_ms: int, window_ms: int, out_ptr: int, bit_offsets=None, chan_stride: Optional[int] = None) -> None:
+        """The signal-quality sums of the records track_block_dev left at rec_ptr (n_chan rows of n_ms, or chan_stride apart): one
+        gyp_quality_sums per (channel, window) into out_ptr, on the same stream behind the tracking kernels.  Not synchronised."""
+        self.engine.track_quality_dev(rec_ptr, self.n_chan, n_ms if chan_stride is None else chan_stride, n_ms, window_ms, out_ptr,
+                                      bit_offsets)
 
     def set_channel(self, index: int, init) -> None:
         """(Re)start one slot from an acquisition result (fresh loop state and histories)."""

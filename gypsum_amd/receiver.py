@@ -133,10 +133,15 @@ class BatchedGpsReceiver:
     knows (0 for a fresh tracker): every block is cut so that such a millisecond is its LAST one, the dropped satellite
     is back in the search list before the next millisecond, and the re-scan `step()` would run then (receiver.py:158-163,
     when the scan period has already passed) happens at the same millisecond here.
+
+    `quality_window_ms=W` (default None: nothing new runs) adds signal quality: every W records of a tracked satellite, counted
+    from its acquisition, `signal_quality[satellite_id]` gains (first record, QUALITY record, QUALITY_SUMS record) -- C/N0 by two
+    estimators, phase lock, share of locked milliseconds (gypsum_amd.quality) -- the same entries for every `block_ms`.
     """
 
     def __init__(self, antenna_samples_provider: AntennaSampleProvider,
-                 only_acquire_satellite_ids: Optional[List[GpsSatelliteId]] = None, block_ms: int = 250, device: int = 0) -> None:
+                 only_acquire_satellite_ids: Optional[List[GpsSatelliteId]] = None, block_ms: int = 250, device: int = 0,
+                 quality_window_ms: Optional[int] = None) -> None:
         from .engine import default_engine
         from .navigation_bit_intergrator import NavigationBitIntegratorBank
         from ._lib import CHAN_INIT
@@ -166,6 +171,15 @@ class BatchedGpsReceiver:
         for k in range(32):
             self._bank.drop_channel(k)
         self._bits = NavigationBitIntegratorBank(32)
+        # Signal quality (gypsum_amd.quality), opt-in: per satellite the (first record since its acquisition, QUALITY, QUALITY_SUMS)
+        # of every complete window of quality_window_ms records in which the channel was tracked
+        self.signal_quality: Dict[GpsSatelliteId, List[Any]] = {}
+        self._quality = None
+        if quality_window_ms is not None:
+            from .quality import QualityMonitor
+            self._quality = QualityMonitor(self._engine, 32, int(quality_window_ms))
+            self._q_starts: List[List[float]] = [[] for _ in range(32)]   # start_of_pseudosymbol of each slot's records since its reset
+            self._q_bit_start: List[Optional[int]] = [None] * 32          # record (since the reset) that starts a decided bit
 
     # the provider's clock: round(cursor / fs, 6) after `k` whole chunks (antenna_sample_provider.py:88-96)
     def _time_after(self, k: int) -> float:
@@ -211,6 +225,9 @@ class BatchedGpsReceiver:
             self._bank.set_channel(slot, (0, sid.id, float(r.doppler_shift), float(r.carrier_wave_phase_shift),
                                           int(r.prn_phase_shift), 0))
             self._bits.reset(slot)                           # a new pipeline starts with a new integrator (pipeline.py:70)
+            if self._quality is not None:
+                self._quality.reset(slot)
+                self._q_starts[slot], self._q_bit_start[slot] = [], None
             self._last_watchdog[sid] = 0.0                   # a new tracker's watchdog clock starts at 0 (tracker.py:222)
             self.tracked_satellite_ids_to_tracking_params[sid] = GpsSatelliteTrackingParameters(
                 satellite=self.satellites_by_id[sid], current_doppler_shift=r.doppler_shift,
@@ -219,6 +236,36 @@ class BatchedGpsReceiver:
             self.emitted_pseudosymbols.setdefault(sid, [])
         acquired = [r.satellite_id for r in results]
         self.satellite_ids_eligible_for_acquisition = [s for s in self.satellite_ids_eligible_for_acquisition if s not in acquired]
+
+    def _push_with_quality(self, rec: np.ndarray, t0: np.ndarray, t1: np.ndarray) -> List[Any]:
+        """push_block_events of the block, cut where a tracked channel completes a quality window: the integrators see the same
+        pseudosymbols in the same order and emit the same events, and a window is evaluated with the bit phase known when its last
+        record had been integrated -- so `signal_quality` does not depend on block_ms.  A channel's bit offset comes from its most
+        recent bit event whose value is not UNKNOWN: the record that bit's first pseudosymbol came from."""
+        from .tracker import BitValue, _DLL_MODULUS, ONE_MILLISECOND
+        q, W, length = self._quality, self._quality.window_ms, rec.shape[1]
+        tracked = [sid.id - 1 for sid in self.tracked_satellite_ids_to_tracking_params]
+        cuts = {0, length}
+        for c in tracked:
+            cuts.update(range(W - q.seen(c) % W, length, W))
+        cuts = sorted(cuts)
+        out = []
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            seg = np.ascontiguousarray(rec[:, a:b])
+            for c in tracked:
+                delay = (seg[c]["code_phase"].astype(np.int64) / _DLL_MODULUS) * ONE_MILLISECOND
+                self._q_starts[c].extend((t0[a:b] + delay).tolist())
+            for c, ev in self._bits.push_block_events(seg, t0[a:b], t1[a:b]):
+                out.append((c, ev))
+                if ev.bit_value != BitValue.UNKNOWN:
+                    tail = np.asarray(self._q_starts[c][-4096:])
+                    self._q_bit_start[c] = len(self._q_starts[c]) - len(tail) + int(np.argmin(np.abs(tail - ev.receiver_timestamp)))
+            # relative to the segment's first record, which is record q.seen(c) of the channel
+            offsets = [-1 if self._q_bit_start[c] is None else (self._q_bit_start[c] - q.seen(c)) % 20 for c in range(32)]
+            for (c, first, quality), sums in zip(q.push(seg, offsets), q.last_sums):
+                if quality["n_used"] > 0:
+                    self.signal_quality.setdefault(GpsSatelliteId(c + 1), []).append((first, quality, sums))
+        return out
 
     def run(self, n_ms: int) -> Dict[GpsSatelliteId, List[Any]]:
         """Advance `n_ms` milliseconds (fewer if the provider runs dry; NoMoreSamplesError if it is already dry).
@@ -253,7 +300,7 @@ class BatchedGpsReceiver:
             t1 = np.array([self._time_after(i + k + 1) for k in range(length)])
             if self.tracked_satellite_ids_to_tracking_params:
                 rec = self._bank.track_block(iq, 1, length, t0)
-                for c, ev in self._bits.push_block_events(rec, t0, t1):
+                for c, ev in (self._bits.push_block_events(rec, t0, t1) if self._quality is None else self._push_with_quality(rec, t0, t1)):
                     events.setdefault(GpsSatelliteId(c + 1), []).append(ev)
                 state = self._bank.state()
                 for sid in list(self.tracked_satellite_ids_to_tracking_params):

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband
+/* 209 (additions, as below): signal quality per tracked channel on the device: gyp_quality_sums, gyp_quality, gyp_track_quality_dev,
+ *      gyp_track_quality, gyp_quality_from_sums.  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband
  *      interference on the device: gyp_tone_rec, gyp_notch_tones, gyp_iq_tones_dev, gyp_notch_iq_dev, gyp_tones_find, gyp_tone_refine,
  *      gyp_ingest_set_notches, gyp_ingest_get_notches, gyp_ingest_find_tones; gyp_debug_set name notch_no_lds.  Opt-in.
  * 209: signal conditioning on the device: gyp_iq_stats, gyp_iq_level, gyp_iq_stats_dev, gyp_condition_iq_dev, gyp_iq_level_from_stats,
@@ -857,6 +859,73 @@ int gyp_ingest_get_notches(const gyp_ingest* ing, int64_t* freqs_out8, int32_t* 
  * On an error the handle keeps the notches it had. */
 int gyp_ingest_find_tones(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, double threshold, int32_t max_tones, int32_t install,
                           int64_t* freqs_out, double* power_db_out, int32_t* n_out);
+
+/* ---------------------------------------------------------------- signal quality: C/N0 and carrier lock -- */
+/* A receiver reports a carrier-to-noise density per tracked satellite.  gyp_track_rec carries the raw prompt peak and the
+ * reference's `locked` flag, whose fixed thresholds depend on the recording's amplitude; C/N0 does not depend on scale, and says
+ * what a level or a notch bought.  Two steps: the device reduces a block's records to sums per (channel, window)
+ * (gyp_track_quality_dev, on records that are still in HBM behind gyp_track_block_dev), the host turns sums into figures
+ * (gyp_quality_from_sums).  Everything is opt-in: with none of these called every other entry point gives the bits it gave before.
+ *
+ * Windows.  Window w of window_ms = W records covers records [w W, min((w + 1) W, n_ms)) of each channel; n_win = ceil(n_ms / W);
+ * the output is n_chan x n_win records, channel-major.  A record is USED iff status != 2 (status 1 is the millisecond that
+ * raised: its peak is real).
+ *
+ * Per record, float64 without contraction:  p2 = (double)re (double)re + (double)im (double)im  (both products exact, the sum one
+ * rounding),  p4 = p2 p2.
+ *
+ * Groups (narrow-band / wide-band power, Van Dierendonck).  For a channel with bit offset b in 0..19, group g >= 0 is the 20
+ * records starting at call-relative index b + 20 g.  A group belongs to the window that contains all 20 of its records; one that
+ * straddles a window edge or the end of the call belongs to no window.  In record order:  sI = sum (double)re,  sQ = sum
+ * (double)im,  WBP = sum p2;  then  NBP = sI sI + sQ sQ,  NBD = sI sI - sQ sQ.  The group is VALID iff all 20 records are used,
+ * WBP > 0 and NBP > 0; a valid group contributes NBP / WBP and NBD / NBP (IEEE float64 divisions).  b = -1: no groups (n_groups = 0
+ * and both sums 0.0).
+ *
+ * Order.  One 64-lane wavefront owns a (channel, window).  Lane l adds the used records l, l + 64, ... of the window, in that
+ * order, to its accumulators, and owns the window's groups l, l + 64, ... (numbered from the window's first group) in that order;
+ * the lanes are reduced by a fixed tree -- lane l takes lane l + 32, 16, 8, 4, 2, 1 -- and lane 0 writes.  No atomics.
+ * INVARIANCE: a record is a pure function of its window's records and of the position of the bit edges in it.  The same bits come
+ * out for every n_chan split and every chan_stride_recs, and for a call on the sub-range that starts at record w0 W with the bit
+ * offsets shifted to (b - w0 W) mod 20.  Non-finite peaks: the sums follow IEEE, the counts are unspecified. */
+typedef struct gyp_quality_sums {   /* one per (channel, window): 48 bytes */
+    int32_t n_used;      /* records of the window with status != 2 */
+    int32_t n_locked;    /* of those, records with locked != 0 */
+    int32_t n_groups;    /* valid 20-ms groups */
+    int32_t reserved;    /* written 0 */
+    double sum_p2;       /* sum of p2 = re*re + im*im over the used records */
+    double sum_p4;       /* sum of p2*p2 */
+    double sum_np;       /* sum over valid groups of NBP / WBP */
+    double sum_pl;       /* sum over valid groups of NBD / NBP */
+} gyp_quality_sums;
+/* recs_dev: n_chan rows of n_ms records, channel c at record c * chan_stride_recs (gyp_track_block_dev's output: stride n_ms).
+ * bit_offset_host: n_chan values in -1..19, or NULL for all -1; they travel as a kernel argument and may be reused as soon as the
+ * call returns.  out_dev: n_chan x ceil(n_ms / window_ms) records.  No stream format is needed.  Enqueued on the context's
+ * stream.  GYP_E_BAD_ARG for NULL pointers, n_chan < 1, n_ms < 1, window_ms < 1, a stride below n_ms when n_chan > 1, or a bit
+ * offset outside -1..19. */
+int gyp_track_quality_dev(gyp_ctx* ctx, const gyp_track_rec* recs_dev, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
+                          int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_dev);
+/* The same for records and results in host memory (recs_host spans (n_chan - 1) * chan_stride_recs + n_ms records); synchronous. */
+int gyp_track_quality(gyp_ctx* ctx, const gyp_track_rec* recs_host, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
+                      int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_host);
+
+/* Host only (no GPU; errors through gyp_last_error(NULL)): the figures of n >= 1 records combined -- consecutive windows of one
+ * channel, say.  Counts are added as integers, S2, S4, Snp, Spl are the plain left-to-right sums of sum_p2, sum_p4, sum_np, sum_pl.
+ * Float64, in exactly this order, one rounding per operation (no contraction).  An estimate that is not defined is NaN: a value,
+ * not an error.
+ *   Moments (M2M4; needs no bit phase).  NaN if n_used < 2.  n = (double)n_used;  M2 = S2 / n;  M4 = S4 / n;  a = M2 M2;  t = a + a;
+ *     d = t - M4;  NaN if !(d > 0);  Pd = sqrt(d);  Pn = M2 - Pd;  NaN if !(Pn > 0);  cn0_m2m4_dbhz = 10 log10((Pd / Pn) 1000.0).
+ *     Assumes a constant-modulus signal in complex Gaussian noise.
+ *   NWPR.  NaN if n_groups < 1.  G = (double)n_groups;  mu = Snp / G;  NaN if !(mu > 1 && mu < 20);
+ *     cn0_nwpr_dbhz = 10 log10(((mu - 1) / (20 - mu)) 1000.0).  Assumes groups that lie inside one data bit: a wrong bit offset
+ *     biases it low.
+ *   phase_lock = Spl / G: about +1 when the carrier is phase locked, about 0 when it is not; NaN without groups.
+ *   locked_share = (double)n_locked / (double)n_used; NaN if n_used = 0.
+ * Both C/N0 figures are per 1 ms prompt, hence the factor 1000 (dB-Hz).  GYP_E_BAD_ARG for NULL pointers or n < 1. */
+typedef struct gyp_quality {   /* 40 bytes */
+    double cn0_m2m4_dbhz, cn0_nwpr_dbhz, phase_lock, locked_share;
+    int32_t n_used, n_groups;
+} gyp_quality;
+int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* out);
 
 /* A/B switches and test hooks of a context, by name.  The library reads NO environment variable for them (only GYP_RCCL_LIB,
  * a deployment's library path): a stray variable must not change the speed path.  Names, value ranges (checked; GYP_E_BAD_ARG
