@@ -2923,22 +2923,25 @@ static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, co
 
 // A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
 static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms) {
-    if (g->notches.count > 0)   // chain order: producer -> notches -> level
-        if (const int rc = notch_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, first_ms * g->n, n_ms,
-                                        g->n, g->fs, &g->notches))
+    const int32_t n = g->src.n;
+    if (g->cond.notches.count > 0)   // chain order: producer -> notches -> level
+        if (const int rc = notch_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, first_ms * n, n_ms, n,
+                                        g->fs, &g->cond.notches))
             return rc;
-    if (!g->level_on) return GYP_OK;
-    return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * g->n, &g->level);
+    if (!g->cond.level_on) return GYP_OK;
+    return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * n, &g->cond.level);
 }
 
 // Enqueue the upload (+ widening) of the reader's next block on the copy stream.  Returns 1 if a block was
 // enqueued, 0 if none is available (end of data, or not yet read and !wait), negative on error.
 static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait) {
     gyp_ctx* ctx = g->ctx;
+    const IngestSource& src = g->src;
+    const hipStream_t copy = g->copy_stream.get();
     // keep fewer than `depth` host slots tied up in uploads: retire the oldest first
-    while ((int)g->in_flight.size() >= g->depth - 1) {
+    while ((int)g->in_flight.size() >= src.depth - 1) {
         const gyp_ingest::Upload& f = g->in_flight.front();
-        HIP_TRY(ctx, hipEventSynchronize(g->uploaded[f.block % g->depth].get()));
+        HIP_TRY(ctx, hipEventSynchronize(g->uploaded[f.block % src.depth].get()));
         ingest_release(g, f.block + 1);
         g->in_flight.pop_front();
     }
@@ -2949,43 +2952,41 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     }
     u->host_slot = slot;
     u->block = g->taken - 1;
-    const int d = (int)(u->block % g->depth);
+    const int d = (int)(u->block % src.depth);
     // the device slot may hold an older block: everything the consumer has enqueued so far drains first (that is
     // the kernels of block k-1 when block k+1 is uploaded ahead, so the upload still overlaps block k's kernels)
     HIP_TRY(ctx, hipEventRecord(g->consumer_mark.get(), ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(g->copy_stream.get(), g->consumer_mark.get(), 0));
-    uint8_t* raw = g->dev_raw[d].get();
+    HIP_TRY(ctx, hipStreamWaitEvent(copy, g->consumer_mark.get(), 0));
     float* iq = g->dev_iq[d].get();
-    const int64_t out_n = (int64_t)u->n_ms * g->n;
-    if (g->packed) {   // the bytes covering the block's samples (halo included), unpacked / resampled / down-converted into the output slot
-        const PackedSpan sp = ingest_packed_span(g, u->first_ms, u->n_ms);
-        if (sp.n_bytes) HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)sp.n_bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
-        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
-        const int rc = g->resampled
-                           ? resample_launch_packed(ctx, g->copy_stream.get(), g->rs, g->pk, raw, 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n,
-                                                    g->scale, u->first_ms, u->n_ms, iq, out_n, g->if_hz)
-                           : unpack_launch(ctx, g->copy_stream.get(), g->pk, raw, 1, sp.n_bytes, sp.bit0, out_n, g->scale, iq, out_n);
-        if (rc) return rc;
-    } else if (g->resampled) {   // the block's input span (halo included) in file width, resampled into the output slot
-        const int64_t span = (int64_t)u->n_ms * g->in_n + g->halo_lo + g->halo_hi;
-        HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)span * g->sample_bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
-        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
-        if (const int rc = resample_launch(ctx, g->copy_stream.get(), g->rs, g->fmt, raw, 1, span, u->first_ms * g->in_n - g->halo_lo, span,
-                                           g->scale, u->first_ms, u->n_ms, iq, out_n, g->if_hz))
-            return rc;
-    } else {   // file-width words, widened on the device (float32 lands in the output slot directly)
-        const size_t bytes = (size_t)u->n_ms * g->ms_bytes;
-        const size_t words = (size_t)u->n_ms * g->n * 2;
-        void* dst = g->fmt == kFmtF32 ? (void*)iq : (void*)raw;
-        HIP_TRY(ctx, hipMemcpyAsync(dst, g->host[slot], bytes, hipMemcpyHostToDevice, g->copy_stream.get()));
-        HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), g->copy_stream.get()));
-        if (g->fmt != kFmtF32) {
-            widen_launch(ctx, g->copy_stream.get(), g->fmt, dst, words, g->scale, iq);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+    // the slot as the reader filled it, in file width (float32 at the output rate lands in the output slot directly); the host slot
+    // is free again as soon as the copy is through, so `uploaded` stands directly behind it, ahead of the producer
+    void* raw = src.raw_block_bytes ? (void*)g->dev_raw[d].get() : (void*)iq;
+    const IngestSpan sp = ingest_span(src, g->file_samples, u->first_ms, u->n_ms);
+    if (sp.slot_bytes()) HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)sp.slot_bytes(), hipMemcpyHostToDevice, copy));
+    HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), copy));
+    const int64_t out_n = (int64_t)u->n_ms * src.n;
+    int rc = GYP_OK;
+    switch (src.kind) {   // the producer: file-width words -> complex64 in the output slot
+        case SourceKind::plain:
+            if (src.fmt != kFmtF32) {
+                widen_launch(ctx, copy, src.fmt, raw, (size_t)out_n * 2, g->scale, iq);
+                HIP_TRY(ctx, hipGetLastError());
+            }
+            break;
+        case SourceKind::filtered:   // the whole window, zero-padded: the buffer's sample 0 is input sample s0
+            rc = resample_launch(ctx, copy, src.rs, src.fmt, raw, 1, sp.count, sp.s0, sp.count, g->scale, u->first_ms, u->n_ms, iq, out_n, src.if_hz);
+            break;
+        case SourceKind::packed_native:
+            rc = unpack_launch(ctx, copy, src.pk, raw, 1, sp.n_bytes, sp.bit0, out_n, g->scale, iq, out_n);
+            break;
+        case SourceKind::packed_filtered:   // the window's part inside the file: the buffer's sample 0 is input sample in_first
+            rc = resample_launch_packed(ctx, copy, src.rs, src.pk, raw, 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n, g->scale, u->first_ms,
+                                        u->n_ms, iq, out_n, src.if_hz);
+            break;
     }
+    if (rc) return rc;
     if (const int lrc = ingest_condition(g, d, u->first_ms, u->n_ms)) return lrc;
-    HIP_TRY(ctx, hipEventRecord(g->ready[d].get(), g->copy_stream.get()));
+    HIP_TRY(ctx, hipEventRecord(g->ready[d].get(), copy));
     g->in_flight.push_back(*u);
     ++g->dev_blocks;
     return 1;
@@ -2998,29 +2999,18 @@ static double round6(double x) {
     return std::strtod(buf, nullptr);
 }
 
-// Opens the file and allocates the rings of a handle whose rates and sizes are filled in; frees it on failure.
-static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp_ingest** out) {
-    const int32_t depth = g->depth;
-    g->fd = open(path, O_RDONLY | O_CLOEXEC);
-    struct stat st;
-    if (g->fd < 0 || fstat(g->fd, &st) != 0) {
-        const std::string why = std::strerror(errno);
+// Makes the handle of a described source: opens and measures the file, allocates the rings, starts the reader.  `who` is the entry
+// point's name in the out-of-memory message.
+static int ingest_finish_open(gyp_ctx* ctx, const IngestSource& src, int64_t fs, const char* path, gyp_ingest** out, const std::string& who) {
+    gyp_ingest* g = new (std::nothrow) gyp_ingest(ctx, fs, src);
+    if (!g) return fail(ctx, GYP_E_NOMEM, who + ": out of memory");
+    if (const int e = ingest_open_file(g, path)) {
         ingest_free(g);
-        return fail(ctx, GYP_E_IO, std::string("gyp_ingest_open: ") + path + ": " + why);
+        return fail(ctx, GYP_E_IO, std::string("gyp_ingest_open: ") + path + ": " + std::strerror(e));
     }
-    g->total_ms = st.st_size > 0 ? (int64_t)((st.st_size - 1) / (off_t)g->ms_bytes) : 0;
-    if (g->sample_bytes) g->file_samples = (int64_t)(st.st_size / (off_t)g->sample_bytes);
-    if (g->packed) {   // counted in samples (gyp_packed_span)
-        g->file_samples = (int64_t)st.st_size * 8 / g->pk.sample_bits();
-        g->total_ms = g->file_samples > 0 ? (g->file_samples - 1) / g->in_n : 0;
-    }
-    (void)posix_fadvise(g->fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-    const size_t block_bytes = g->host_block_bytes;
-    g->host.assign(depth, nullptr);
+    const int32_t depth = src.depth;
+    const size_t block_bytes = src.host_block_bytes;
     g->host_mem.resize(depth);
-    g->host_first.assign(depth, 0);
-    g->host_ms.assign(depth, 0);
-    int rc = GYP_OK;
     auto setup = [&]() -> int {
         if (!ctx) {
             for (int i = 0; i < depth; ++i) {
@@ -3046,15 +3036,15 @@ static int ingest_finish_open(gyp_ctx* ctx, gyp_ingest* g, const char* path, gyp
         g->uploaded.resize(depth);
         g->ready.resize(depth);
         for (int i = 0; i < depth; ++i) {
-            HIP_TRY(ctx, g->dev_raw[i].reserve(g->raw_block_bytes, Slack::exact));
-            HIP_TRY(ctx, g->dev_iq[i].reserve((size_t)g->block_ms * g->n * 2, Slack::exact));
+            HIP_TRY(ctx, g->dev_raw[i].reserve(src.raw_block_bytes, Slack::exact));
+            HIP_TRY(ctx, g->dev_iq[i].reserve((size_t)src.block_ms * src.n * 2, Slack::exact));
             HIP_TRY(ctx, g->uploaded[i].create(hipEventDisableTiming));
             HIP_TRY(ctx, g->ready[i].create(hipEventDisableTiming));
         }
         HIP_TRY(ctx, g->consumer_mark.create(hipEventDisableTiming));
         return GYP_OK;
     };
-    if ((rc = setup())) {
+    if (const int rc = setup()) {
         ingest_free(g);
         return rc;
     }
@@ -3075,25 +3065,46 @@ static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int
         return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (format, block_ms >= 1, 3 <= depth <= 64)");
     ResampleDesign d;
     if (const int rc = real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who)) return rc;
-    gyp_ingest* g = new (std::nothrow) gyp_ingest();
-    if (!g) return fail(ctx, GYP_E_NOMEM, std::string(who) + ": out of memory");
-    g->ctx = ctx;
-    g->fmt = fmt;
-    g->fs = d.fs_out;
-    g->n = d.n_out;
-    g->block_ms = block_ms;
-    g->depth = depth;
-    g->resampled = true;
-    g->real = real;
-    g->if_hz = if_hz;
-    g->rs = d;
-    g->in_n = d.n_in;
-    g->halo_lo = d.taps / 2 - 1;
-    g->halo_hi = d.taps / 2;
-    g->sample_bytes = (size_t)(real ? 1 : 2) * wb;
-    g->ms_bytes = (size_t)d.n_in * g->sample_bytes;   // total_ms: the input file's milliseconds, by the rule of gyp_ingest_open
-    ingest_set_block_bytes(g);
-    return ingest_finish_open(ctx, g, path, out);
+    return ingest_finish_open(ctx, ingest_describe(fmt, nullptr, d, if_hz, block_ms, depth), d.fs_out, path, out, who);
+}
+
+// One measurement over the handle's own device blocks of [first_ms, first_ms + n_ms) with the level put aside, and with
+// suspend_notches the notches too (gyp_ingest_calibrate, gyp_ingest_find_tones).  per_block(iq_dev, ms done, ms to take) is called
+// for the blocks in order; after(next) does what follows the walk (downloads, host arithmetic, further launches on the context's
+// stream) and may write the conditioning to install into `next`, which starts as the one found.  Then, whatever happened and in
+// this order: the error text is saved (the seek overwrites ctx->err), the context's stream is synchronised (nothing may still read
+// a block or a temporary), release() lets the caller's temporaries go, the conditioning becomes `next` on success and what it was
+// otherwise, the cursor goes back to where it was, and the first error is reported with its own message.
+template <class PerBlock, class After, class Release>
+static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, bool suspend_notches, const char* who, PerBlock per_block,
+                                After after, Release release) {
+    gyp_ctx* ctx = g->ctx;
+    const Conditioning before = g->cond;
+    const int64_t back_to = g->consumer_ms;
+    Conditioning next = before;
+    g->cond.level_on = false;
+    if (suspend_notches) g->cond.notches = gyp_notch_tones{};
+    auto measure = [&]() -> int {
+        if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
+        for (int32_t done = 0; done < n_ms;) {
+            const float* iq = nullptr;
+            int64_t first = 0;
+            int32_t count = 0;
+            if (const int rc = gyp_ingest_next_dev(g, &iq, &first, &count)) return rc;
+            if (count == 0 || first != first_ms + done) return fail(ctx, GYP_E_IO, std::string(who) + ": the recording ended inside the range");
+            const int32_t take = std::min(count, n_ms - done);
+            if (const int rc = per_block(iq, done, take)) return rc;
+            done += take;
+        }
+        return after(next);
+    };
+    const int rc = measure();
+    const std::string why = ctx->err;
+    (void)hipStreamSynchronize(ctx->stream);
+    release();
+    g->cond = rc == GYP_OK ? next : before;
+    const int rc_back = gyp_ingest_seek(g, back_to);
+    return rc ? fail(ctx, rc, why) : rc_back;
 }
 
 extern "C" {
@@ -3107,17 +3118,7 @@ int gyp_ingest_open(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_hz, 
         return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_open: bad arguments (format, fs, n, block_ms >= 1, 3 <= depth <= 64)");
     if ((int64_t)n != fs_hz / 1000)   // antenna_sample_provider.py:135
         return fail(ctx, GYP_E_BAD_RATE, "gyp_ingest_open: n must be fs // 1000");
-    gyp_ingest* g = new (std::nothrow) gyp_ingest();
-    if (!g) return fail(ctx, GYP_E_NOMEM, "gyp_ingest_open: out of memory");
-    g->ctx = ctx;
-    g->fmt = fmt;
-    g->fs = fs_hz;
-    g->n = n;
-    g->block_ms = block_ms;
-    g->depth = depth;
-    g->ms_bytes = (size_t)n * 2 * wb;
-    ingest_set_block_bytes(g);
-    return ingest_finish_open(ctx, g, path, out);
+    return ingest_finish_open(ctx, ingest_describe(fmt, nullptr, ingest_unfiltered(n), 0, block_ms, depth), fs_hz, path, out, "gyp_ingest_open");
 }
 
 int gyp_ingest_open_resampled(gyp_ctx* ctx, const char* path, int32_t fmt, int64_t fs_in_hz, int32_t taps, int32_t block_ms,
@@ -3145,32 +3146,11 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
     const bool native = !pk.real && fs_in_hz == ctx->fs;
     const float* levels = nullptr;   // uploaded now, not on the copy stream's first block
     if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
-    ResampleDesign d;
+    ResampleDesign d = ingest_unfiltered((int32_t)(ctx->fs / 1000));
     if (!native)
         if (const int rc = pk.real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who))
             return rc;
-    gyp_ingest* g = new (std::nothrow) gyp_ingest();
-    if (!g) return fail(ctx, GYP_E_NOMEM, std::string(who) + ": out of memory");
-    g->ctx = ctx;
-    g->fmt = -1;   // no file-width word format: set_scale applies
-    g->fs = ctx->fs;
-    g->n = (int32_t)(ctx->fs / 1000);
-    g->block_ms = block_ms;
-    g->depth = depth;
-    g->packed = true;
-    g->pk = pk;
-    g->resampled = !native;
-    g->real = pk.real;
-    g->if_hz = if_hz;
-    g->in_n = native ? g->n : d.n_in;
-    if (!native) {
-        g->rs = d;
-        g->halo_lo = d.taps / 2 - 1;
-        g->halo_hi = d.taps / 2;
-    }
-    g->ms_bytes = 1;   // total_ms is counted in samples (ingest_finish_open)
-    ingest_set_block_bytes(g);
-    return ingest_finish_open(ctx, g, path, out);
+    return ingest_finish_open(ctx, ingest_describe(0, &pk, d, if_hz, block_ms, depth), ctx->fs, path, out, who);
 }
 
 int gyp_device_locality(gyp_ctx* ctx, int32_t* numa_node_out, char* cpulist_out, int32_t cap) {
@@ -3198,7 +3178,7 @@ int64_t gyp_ingest_total_ms(const gyp_ingest* ing) { return ing ? ing->total_ms 
 int gyp_ingest_set_scale(gyp_ingest* g, float scale) {
     if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_scale: handle is NULL");
     if (!(scale > 0.0f) || !std::isfinite(scale)) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_set_scale: scale must be positive and finite");
-    if (g->fmt == kFmtF32) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_set_scale: float32 recordings are uploaded as they are");
+    if (!g->src.packed() && g->src.fmt == kFmtF32) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_set_scale: float32 recordings are uploaded as they are");
     g->scale = scale;
     return GYP_OK;
 }
@@ -3221,10 +3201,10 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     if (!g || !raw_out || !first_ms_out || !n_ms_out) return fail(g ? g->ctx : nullptr, GYP_E_BAD_ARG, "gyp_ingest_next_host: NULL argument");
     *raw_out = nullptr;
     *n_ms_out = 0;
-    if (g->resampled) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
-    if (g->packed) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
-    if (g->level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
-    if (g->notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    if (g->src.filtered()) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
+    if (g->src.packed()) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
+    if (g->cond.level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    if (g->cond.notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3259,10 +3239,10 @@ int gyp_ingest_next_dev(gyp_ingest* g, const float** iq_dev_out, int64_t* first_
     const int rc = ingest_enqueue_upload(g, &g->ahead, false);
     if (rc < 0) return rc;
     g->have_ahead = rc == 1;
-    const int d = (int)(cur.block % g->depth);
+    const int d = (int)(cur.block % g->src.depth);
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, g->ready[d].get(), 0));
     // hand back host slots whose upload has finished
-    while (!g->in_flight.empty() && hipEventQuery(g->uploaded[g->in_flight.front().block % g->depth].get()) == hipSuccess) {
+    while (!g->in_flight.empty() && hipEventQuery(g->uploaded[g->in_flight.front().block % g->src.depth].get()) == hipSuccess) {
         ingest_release(g, g->in_flight.front().block + 1);
         g->in_flight.pop_front();
     }
@@ -3288,16 +3268,16 @@ int gyp_ingest_set_level(gyp_ingest* g, const gyp_iq_level* level) {
     if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_level: the handle was opened without a context (a level applies to device blocks)");
     if (level)
         if (const char* why = level_check(level)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_level: ") + why);
-    g->level_on = level != nullptr;
-    g->level = level ? *level : gyp_iq_level{0.0f, 0.0f, 1.0f, 0};
+    g->cond.level_on = level != nullptr;
+    g->cond.level = level ? *level : gyp_iq_level{0.0f, 0.0f, 1.0f, 0};
     return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old level: drop it and read it again
 }
 
 int gyp_ingest_get_level(const gyp_ingest* g, gyp_iq_level* out, int32_t* enabled_out) {
     if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: handle is NULL");
     if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: the handle was opened without a context (a level applies to device blocks)");
-    if (out) *out = g->level;
-    if (enabled_out) *enabled_out = g->level_on ? 1 : 0;
+    if (out) *out = g->cond.level;
+    if (enabled_out) *enabled_out = g->cond.level_on ? 1 : 0;
     return GYP_OK;
 }
 
@@ -3314,38 +3294,24 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     DevBuf<gyp_iq_stats> stats_dev;
     HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
     gyp_iq_stats* d_stats = stats_dev.get();
-    const bool was_on = g->level_on;
-    const int64_t back_to = g->consumer_ms;
-    g->level_on = false;   // the blocks below are the handle's unconditioned output
+    const int32_t n = g->src.n;
     std::vector<gyp_iq_stats> stats((size_t)n_ms);
     gyp_iq_level level{};
-    auto measure = [&]() -> int {
-        if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
-        for (int32_t done = 0; done < n_ms;) {
-            const float* iq = nullptr;
-            int64_t first = 0;
-            int32_t count = 0;
-            if (const int rc = gyp_ingest_next_dev(g, &iq, &first, &count)) return rc;
-            if (count == 0 || first != first_ms + done) return fail(ctx, GYP_E_IO, "gyp_ingest_calibrate: the recording ended inside the range");
-            const int32_t take = std::min(count, n_ms - done);
-            if (const int rc = stats_launch(ctx, ctx->stream, iq, 1, 0, take, g->n, clip_level, d_stats + done)) return rc;
-            done += take;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (const char* why = level_from_stats(stats.data(), n_ms, g->n, remove_dc, target_rms, &level, measured_out4))
-            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_calibrate: ") + why);
-        return GYP_OK;
-    };
-    const int rc = measure();
-    const std::string why = ctx->err;
-    (void)hipStreamSynchronize(ctx->stream);   // nothing may still read d_stats or a block of the measurement
-    (void)stats_dev.reset();
-    g->level_on = rc == GYP_OK ? true : was_on;
-    if (rc == GYP_OK) g->level = level;
-    const int rc_back = gyp_ingest_seek(g, back_to);
-    if (rc) return fail(ctx, rc, why);
-    if (rc_back) return rc_back;
+    // the level is put aside: the blocks measured are the handle's output without it (notches stay)
+    const int rc = ingest_measure_range(
+        g, first_ms, n_ms, false, "gyp_ingest_calibrate",
+        [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ctx->stream, iq, 1, 0, take, n, clip_level, d_stats + done); },
+        [&](Conditioning& next) -> int {
+            HIP_TRY(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (const char* why = level_from_stats(stats.data(), n_ms, n, remove_dc, target_rms, &level, measured_out4))
+                return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_calibrate: ") + why);
+            next.level_on = true;
+            next.level = level;
+            return GYP_OK;
+        },
+        [&] { (void)stats_dev.reset(); });
+    if (rc) return rc;
     if (level_out) *level_out = level;
     return GYP_OK;
 }
@@ -3358,7 +3324,7 @@ int gyp_ingest_set_notches(gyp_ingest* g, const int64_t* freqs_hz, int32_t n) {
     gyp_notch_tones t{};
     t.count = n;
     for (int32_t i = 0; i < n; ++i) t.freq_hz[i] = freqs_hz[i];
-    g->notches = t;
+    g->cond.notches = t;
     return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old list: drop it and read it again
 }
 
@@ -3366,8 +3332,8 @@ int gyp_ingest_get_notches(const gyp_ingest* g, int64_t* freqs_out8, int32_t* n_
     if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: handle is NULL");
     if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: the handle was opened without a context (notches apply to device blocks)");
     if (freqs_out8)
-        for (int32_t i = 0; i < g->notches.count; ++i) freqs_out8[i] = g->notches.freq_hz[i];
-    if (n_out) *n_out = g->notches.count;
+        for (int32_t i = 0; i < g->cond.notches.count; ++i) freqs_out8[i] = g->cond.notches.freq_hz[i];
+    if (n_out) *n_out = g->cond.notches.count;
     return GYP_OK;
 }
 
@@ -3382,7 +3348,8 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 1000");
     if (!(threshold > 0.0) || !std::isfinite(threshold) || max_tones < 1 || max_tones > GYP_NOTCH_MAX_TONES)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: threshold must be positive and finite, 1 <= max_tones <= 8");
-    const int64_t fs = g->fs, total = (int64_t)n_ms * g->n, first_index = first_ms * g->n;
+    const int32_t n = g->src.n;
+    const int64_t fs = g->fs, total = (int64_t)n_ms * n, first_index = first_ms * n;
     if (!tone_rate_ok(fs) || total < kScanBlock)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: the range must hold at least 1024 samples at a rate in [1000, 2^31) Hz");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3392,11 +3359,6 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
     DevBuf<gyp_tone_rec> recs_dev;
     HIP_TRY(ctx, iq_all.reserve((size_t)total * 2, Slack::exact));
     HIP_TRY(ctx, recs_dev.reserve(std::max<size_t>((size_t)n_scan * n_grid, (size_t)n_fine * GYP_NOTCH_MAX_TONES), Slack::exact));
-    const bool level_was_on = g->level_on;
-    const gyp_notch_tones notches_were = g->notches;
-    const int64_t back_to = g->consumer_ms;
-    g->level_on = false;          // the blocks below are the producer's output: no notches, no level
-    g->notches = gyp_notch_tones{};
     std::vector<gyp_tone_rec> recs;
     std::vector<int64_t> found;
     std::vector<double> found_db;
@@ -3423,19 +3385,12 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         }
         return GYP_OK;
     };
+    // the blocks gathered are the producer's output: no notches, no level
+    auto gather = [&](const float* iq, int32_t done, int32_t take) -> int {
+        HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        return GYP_OK;
+    };
     auto search = [&]() -> int {
-        if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
-        for (int32_t done = 0; done < n_ms;) {
-            const float* iq = nullptr;
-            int64_t first = 0;
-            int32_t count = 0;
-            if (const int rc = gyp_ingest_next_dev(g, &iq, &first, &count)) return rc;
-            if (count == 0 || first != first_ms + done) return fail(ctx, GYP_E_IO, "gyp_ingest_find_tones: the recording ended inside the range");
-            const int32_t take = std::min(count, n_ms - done);
-            HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * g->n, iq, (size_t)take * g->n * 2 * sizeof(float),
-                                        hipMemcpyDeviceToDevice, ctx->stream));
-            done += take;
-        }
         // 1. the scan
         std::vector<int64_t> grid((size_t)n_grid);
         for (int32_t k = 0; k < n_grid; ++k) grid[(size_t)k] = scan_freq(k - kScanHalf, fs);
@@ -3473,26 +3428,25 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         // leaks into a weak tone's records at -30 dB and below and bends its phase slope)
         if (const int rc = refine(n_fine, kScanFine, GYP_WINDOW_HANN)) return rc;
         if (n_ms >= 2)
-            if (const int rc = refine(n_ms, g->n, GYP_WINDOW_RECT)) return rc;
+            if (const int rc = refine(n_ms, n, GYP_WINDOW_RECT)) return rc;
         return notch_check(found.data(), (int32_t)found.size(), fs)
                    ? fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
                    : GYP_OK;
     };
-    const int rc = search();
-    const std::string why = ctx->err;
-    (void)hipStreamSynchronize(ctx->stream);   // nothing may still read the buffers or a block of the search
-    (void)iq_all.reset();
-    (void)recs_dev.reset();
-    g->level_on = level_was_on;
-    g->notches = notches_were;
-    if (rc == GYP_OK && install) {
-        g->notches = gyp_notch_tones{};
-        g->notches.count = (int32_t)found.size();
-        for (size_t t = 0; t < found.size(); ++t) g->notches.freq_hz[t] = found[t];
-    }
-    const int rc_back = gyp_ingest_seek(g, back_to);
-    if (rc) return fail(ctx, rc, why);
-    if (rc_back) return rc_back;
+    auto search_and_install = [&](Conditioning& next) -> int {
+        if (const int rc = search()) return rc;
+        if (install) {
+            next.notches = gyp_notch_tones{};
+            next.notches.count = (int32_t)found.size();
+            for (size_t t = 0; t < found.size(); ++t) next.notches.freq_hz[t] = found[t];
+        }
+        return GYP_OK;
+    };
+    if (const int rc = ingest_measure_range(g, first_ms, n_ms, true, "gyp_ingest_find_tones", gather, search_and_install, [&] {
+            (void)iq_all.reset();
+            (void)recs_dev.reset();
+        }))
+        return rc;
     for (size_t t = 0; t < found.size(); ++t) {
         if (freqs_out) freqs_out[t] = found[t];
         if (power_db_out) power_db_out[t] = found_db[t];
@@ -3505,9 +3459,9 @@ int gyp_ingest_times(const gyp_ingest* g, int64_t first_ms, int32_t n_ms, double
     if (!g || n_ms < 0 || first_ms < 0 || (n_ms > 0 && (!start_out || !end_out)))
         return fail(g ? g->ctx : nullptr, GYP_E_BAD_ARG, "gyp_ingest_times: bad arguments");
     for (int32_t i = 0; i < n_ms; ++i) {
-        const int64_t cursor = (first_ms + i) * g->n;
+        const int64_t cursor = (first_ms + i) * g->src.n;
         start_out[i] = round6((double)cursor / (double)g->fs);
-        end_out[i] = round6((double)(cursor + g->n) / (double)g->fs);
+        end_out[i] = round6((double)(cursor + g->src.n) / (double)g->fs);
     }
     return GYP_OK;
 }

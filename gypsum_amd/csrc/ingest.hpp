@@ -235,41 +235,121 @@ static PackedSpan packed_span(int64_t B, int64_t file_samples, int64_t first, in
     return sp;
 }
 
-struct gyp_ingest {
-    gyp_ctx* ctx = nullptr;   // null: host-only (no pinned memory, no device ring)
-    int fd = -1;
-    int32_t fmt = kFmtF32;
-    float scale = 1.0f;       // integer formats only: sample = word * scale (1 = the reference's raw values)
-    int64_t fs = 0;
-    int32_t n = 0, block_ms = 0, depth = 0;
-    size_t ms_bytes = 0;
-    int64_t total_ms = 0;     // milliseconds the reference provider delivers before NoMoreSamplesError
-    std::string err;
-    HostLocality locality;    // the GPU's NUMA node: the pinned ring is allocated there and the reader thread runs there
-    size_t host_block_bytes = 0, raw_block_bytes = 0;   // one ring slot on the host / of file-width words on the device (0: none)
+// ---------------------------------------------------------------------------------------------------------
+// The handle.  Everything below is host code without a HIP call: what the file holds, where a block's samples lie in it, how many
+// milliseconds it has, the reader thread and the take / release protocol.  What launches or copies is in gypsum_hip.hip.
+// ---------------------------------------------------------------------------------------------------------
+// What the file holds and how the device turns it into the stream format:
+//   plain            I,Q words at the output rate, widened (float32: uploaded as they are)              gyp_ingest_open
+//   filtered         I,Q or real words at another rate, resampled / down-converted from if_hz           gyp_ingest_open_resampled / _ddc
+//   packed_native    packed I,Q words at the output rate, unpacked                                      gyp_ingest_open_packed
+//   packed_filtered  packed I,Q or real words at another rate, resampled / down-converted               gyp_ingest_open_packed
+enum class SourceKind : int32_t { plain, filtered, packed_native, packed_filtered };
 
-    // resampled handles (gyp_ingest_open_resampled): n / fs are the OUTPUT rate, ms_bytes the input file's millisecond.  A block
-    // of output milliseconds [first, first + n_ms) is read as input samples first*in_n - halo_lo .. (first+n_ms)*in_n + halo_hi - 1,
-    // zero outside the file's whole samples, and resampled where the widen kernel runs otherwise.
-    bool resampled = false;
-    bool real = false;        // gyp_ingest_open_ddc: one real word per sample, mixed down from if_hz (the mixer index is the file index)
+// One handle's source, built by ingest_describe at open and never written afterwards: the reader thread reads it without the lock.
+// A block of output milliseconds [first, first + n_ms) needs input samples first*in_n - halo_lo .. (first+n_ms)*in_n + halo_hi - 1
+// (ingest_span); an unfiltered source has in_n == n and no halo.
+struct IngestSource {
+    SourceKind kind = SourceKind::plain;
+    int32_t fmt = kFmtF32;    // the words of plain and filtered sources
+    PackedFormat pk{};        // the words of packed sources
+    bool real = false;        // one real word per sample, mixed down from if_hz (the mixer index is the file index)
     int64_t if_hz = 0;
-    ResampleDesign rs{};
-    int32_t in_n = 0, halo_lo = 0, halo_hi = 0;
-    size_t sample_bytes = 0;
-    int64_t file_samples = 0;
-    // packed handles (gyp_ingest_open_packed): words of pk.bits bits; a block reads the bytes covering its samples (halo included
-    // when resampled), which the upload stream unpacks, resamples or down-converts.  in_n is the input millisecond either way.
-    bool packed = false;
-    PackedFormat pk{};
+    ResampleDesign rs{};      // filtered sources
+    int32_t n = 0, in_n = 0;  // samples per millisecond of the output and of the file
+    int32_t halo_lo = 0, halo_hi = 0;
+    int64_t sample_bits = 0;  // one input sample in the file
+    int32_t block_ms = 0, depth = 0;
+    size_t host_block_bytes = 0, raw_block_bytes = 0;   // one ring slot on the host / of file-width words on the device (0: none)
+    bool packed() const { return kind == SourceKind::packed_native || kind == SourceKind::packed_filtered; }
+    bool filtered() const { return kind == SourceKind::filtered || kind == SourceKind::packed_filtered; }
+};
 
-    // level (gyp_ingest_set_level / gyp_ingest_calibrate): a constant of the handle; while it is on, every device block is conditioned
-    // in place on the copy stream behind whatever produced it
-    bool level_on = false;
+// A block's input samples [s0, s0 + count), their part inside the file with the bytes that cover it (PackedSpan; a width that is a
+// multiple of 8 has bit0 == 0), and what a ring slot holds for it: pad_lo zero bytes, the n_bytes of the file, pad_hi zero bytes.
+// Word formats pad to the whole window (the kernel indexes from s0); packed blocks are the file's bytes as they are (the kernel
+// is given in_first and bit0).
+struct IngestSpan : PackedSpan {
+    int64_t s0 = 0, count = 0, pad_lo = 0, pad_hi = 0;
+    int64_t slot_bytes() const { return pad_lo + n_bytes + pad_hi; }
+};
+static IngestSpan ingest_span(const IngestSource& s, int64_t file_samples, int64_t first_ms, int32_t n_ms) {
+    IngestSpan sp;
+    sp.s0 = first_ms * s.in_n - s.halo_lo;
+    sp.count = (int64_t)n_ms * s.in_n + s.halo_lo + s.halo_hi;
+    static_cast<PackedSpan&>(sp) = packed_span(s.sample_bits, file_samples, sp.s0, sp.count);
+    if (!s.packed()) {
+        const int64_t sample_bytes = s.sample_bits / 8;
+        sp.pad_lo = (sp.in_n ? sp.in_first - sp.s0 : sp.count) * sample_bytes;
+        sp.pad_hi = sp.count * sample_bytes - sp.pad_lo - sp.n_bytes;
+    }
+    return sp;
+}
+
+// The source of a file of `fmt` words (pk null) or of `pk` packed words, filtered by design d (taps, n_in, n_out, real) or, with
+// d.taps == 0, at the output rate already (n_in == n_out).  A filter of T taps reaches T/2 - 1 samples back and T/2 ahead.
+// A ring slot holds the largest block: block_ms milliseconds with the halo, for packed words at any bit0, plus one byte.
+static IngestSource ingest_describe(int32_t fmt, const PackedFormat* pk, const ResampleDesign& d, int64_t if_hz, int32_t block_ms, int32_t depth) {
+    IngestSource s;
+    const bool filtered = d.taps > 0;
+    s.kind = pk ? (filtered ? SourceKind::packed_filtered : SourceKind::packed_native) : (filtered ? SourceKind::filtered : SourceKind::plain);
+    s.fmt = fmt;
+    if (pk) s.pk = *pk;
+    s.real = d.real;
+    s.if_hz = if_hz;
+    s.rs = d;
+    s.n = d.n_out;
+    s.in_n = d.n_in;
+    if (filtered) {
+        s.halo_lo = d.taps / 2 - 1;
+        s.halo_hi = d.taps / 2;
+    }
+    s.sample_bits = pk ? pk->sample_bits() : (int64_t)8 * ingest_word_bytes(fmt) * (d.real ? 1 : 2);
+    s.block_ms = block_ms;
+    s.depth = depth;
+    s.host_block_bytes = (size_t)((ingest_span(s, 0, 0, block_ms).count * s.sample_bits + 7) / 8 + (pk ? 1 : 0));
+    // (float32 at the output rate lands in the output slot directly: no device slot of raw words)
+    s.raw_block_bytes = s.kind == SourceKind::plain && fmt == kFmtF32 ? 0 : s.host_block_bytes;
+    return s;
+}
+// The design of a source that is not filtered: n samples per millisecond in and out.
+static ResampleDesign ingest_unfiltered(int32_t n) {
+    ResampleDesign d;
+    d.n_in = d.n_out = n;
+    return d;
+}
+
+// A file's whole samples, and the milliseconds the reference provider delivers from it before NoMoreSamplesError: it stops one
+// word short of the end, so word formats count (bytes - 1) / millisecond bytes; packed files count in samples (gyp_packed_span).
+struct IngestExtent {
+    int64_t total_ms = 0, file_samples = 0;
+};
+static IngestExtent ingest_extent(const IngestSource& s, int64_t file_bytes) {
+    IngestExtent e;
+    e.file_samples = file_bytes * 8 / s.sample_bits;
+    if (s.packed()) e.total_ms = e.file_samples > 0 ? (e.file_samples - 1) / s.in_n : 0;
+    else e.total_ms = file_bytes > 0 ? (file_bytes - 1) / (s.in_n * s.sample_bits / 8) : 0;
+    return e;
+}
+
+// What is applied in place to every device block behind its producer, on the copy stream: notches, then the level.  One value, so
+// that a measurement can put it aside and back whole (ingest_measure_range).
+struct Conditioning {
+    bool level_on = false;     // gyp_ingest_set_level / gyp_ingest_calibrate
     gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
-    // notches (gyp_ingest_set_notches / gyp_ingest_find_tones): constants of the handle too; every device block is notched in place
-    // on the copy stream between its producer and the level
-    gyp_notch_tones notches{};
+    gyp_notch_tones notches{};   // gyp_ingest_set_notches / gyp_ingest_find_tones
+};
+
+struct gyp_ingest {
+    gyp_ingest(gyp_ctx* c, int64_t fs_hz, const IngestSource& s) : ctx(c), fs(fs_hz), src(s) {}
+    gyp_ctx* const ctx;       // null: host-only (no pinned memory, no device ring)
+    const int64_t fs;         // the output rate
+    const IngestSource src;
+    int fd = -1;
+    float scale = 1.0f;       // integer and packed words only: sample = word * scale (1 = the reference's raw values)
+    int64_t total_ms = 0, file_samples = 0;   // ingest_extent of the file as it was at open
+    HostLocality locality;    // the GPU's NUMA node: the pinned ring is allocated there and the reader thread runs there
+    Conditioning cond;
     int64_t consumer_ms = 0;        // where the next block handed out starts (set_level and calibrate seek back to it)
 
     // host ring, filled by the reader thread
@@ -302,22 +382,19 @@ struct gyp_ingest {
     int64_t dev_blocks = 0;          // uploads enqueued so far (device slot = index % depth)
 };
 
-// One ring slot's size from the handle's fields (rates, halo, packing and block_ms filled in): what the reader writes per block.
-//   packed:    the bytes covering block_ms * in_n + halo samples at any bit0, plus one;
-//   resampled: the block's input samples plus the T-1 halo, in file width;
-//   plain:     block_ms file milliseconds (float32 lands in the output slot directly: no device slot of raw words).
-static void ingest_set_block_bytes(gyp_ingest* g) {
-    if (g->packed) {
-        const int64_t span = (int64_t)g->block_ms * g->in_n + g->halo_lo + g->halo_hi;
-        g->host_block_bytes = (size_t)((span * g->pk.sample_bits() + 7) / 8 + 1);
-        g->raw_block_bytes = g->host_block_bytes;
-    } else if (g->resampled) {
-        g->host_block_bytes = ((size_t)g->block_ms * g->in_n + g->rs.taps - 1) * g->sample_bytes;
-        g->raw_block_bytes = g->host_block_bytes;
-    } else {
-        g->host_block_bytes = (size_t)g->block_ms * g->ms_bytes;
-        g->raw_block_bytes = g->fmt != kFmtF32 ? g->host_block_bytes : 0;
-    }
+// Opens the file, measures it and sizes the (still empty) host ring's tables.  0 or an errno.
+static int ingest_open_file(gyp_ingest* g, const char* path) {
+    g->fd = open(path, O_RDONLY | O_CLOEXEC);
+    struct stat st;
+    if (g->fd < 0 || fstat(g->fd, &st) != 0) return errno;
+    const IngestExtent e = ingest_extent(g->src, (int64_t)st.st_size);
+    g->total_ms = e.total_ms;
+    g->file_samples = e.file_samples;
+    (void)posix_fadvise(g->fd, 0, 0, POSIX_FADV_SEQUENTIAL);
+    g->host.assign(g->src.depth, nullptr);
+    g->host_first.assign(g->src.depth, 0);
+    g->host_ms.assign(g->src.depth, 0);
+    return 0;
 }
 
 // pread until `want` bytes from file offset `at` are in: 0, or an errno (EIO: the file shrank under us).
@@ -331,54 +408,31 @@ static int pread_fully(int fd, uint8_t* buf, size_t want, size_t at) {
     return 0;
 }
 
-// A resampled block's input span with its halo; what lies outside the file's whole samples reads as zero.  0 or an errno.
-static int ingest_read_resampled(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
-    const size_t sb = g->sample_bytes;
-    const int64_t s0 = first * g->in_n - g->halo_lo;
-    const int64_t count = (int64_t)n_ms * g->in_n + g->halo_lo + g->halo_hi;
-    const int64_t a = std::max<int64_t>(s0, 0), b = std::min<int64_t>(s0 + count, g->file_samples);
-    if (b <= a) {
-        std::memset(buf, 0, (size_t)count * sb);
-        return 0;
-    }
-    std::memset(buf, 0, (size_t)(a - s0) * sb);
-    std::memset(buf + (size_t)(b - s0) * sb, 0, (size_t)(s0 + count - b) * sb);
-    return pread_fully(g->fd, buf + (size_t)(a - s0) * sb, (size_t)(b - a) * sb, (size_t)a * sb);
-}
-
-// A packed block's span: its input samples with the halo, the part inside the file, and the bytes covering that part.
-static PackedSpan ingest_packed_span(const gyp_ingest* g, int64_t first, int32_t n_ms) {
-    return packed_span(g->pk.sample_bits(), g->file_samples, first * g->in_n - g->halo_lo, (int64_t)n_ms * g->in_n + g->halo_lo + g->halo_hi);
-}
-
-// A packed block: the bytes covering its samples, as they are in the file.  0 or an errno.
-static int ingest_read_packed(gyp_ingest* g, uint8_t* buf, int64_t first, int32_t n_ms) {
-    const PackedSpan sp = ingest_packed_span(g, first, n_ms);
-    return pread_fully(g->fd, buf, (size_t)sp.n_bytes, (size_t)sp.first_byte);
-}
-
 static void ingest_reader_main(gyp_ingest* g) {
+    const int32_t depth = g->src.depth;
     for (;;) {
         int slot;
         int64_t first;
         int32_t n_ms;
         {
             std::unique_lock<std::mutex> lk(g->mu);
-            g->cv.wait(lk, [&] { return g->stop || (!g->eof && g->produced - g->released < g->depth); });
+            g->cv.wait(lk, [&] { return g->stop || (!g->eof && g->produced - g->released < depth); });
             if (g->stop) return;
             first = g->cursor_ms;
-            n_ms = (int32_t)std::min<int64_t>(g->block_ms, g->total_ms - first);
+            n_ms = (int32_t)std::min<int64_t>(g->src.block_ms, g->total_ms - first);
             if (n_ms <= 0) {
                 g->eof = true;
                 g->cv.notify_all();
                 continue;
             }
-            slot = (int)(g->produced % g->depth);
+            slot = (int)(g->produced % depth);
         }
+        // the slot's content, whatever the kind: zeros where the span says, then the file's bytes
         uint8_t* buf = g->host[slot];
-        const int err = g->packed ? ingest_read_packed(g, buf, first, n_ms)
-                        : g->resampled ? ingest_read_resampled(g, buf, first, n_ms)
-                                       : pread_fully(g->fd, buf, (size_t)n_ms * g->ms_bytes, (size_t)first * g->ms_bytes);
+        const IngestSpan sp = ingest_span(g->src, g->file_samples, first, n_ms);
+        std::memset(buf, 0, (size_t)sp.pad_lo);
+        std::memset(buf + sp.pad_lo + sp.n_bytes, 0, (size_t)sp.pad_hi);
+        const int err = pread_fully(g->fd, buf + sp.pad_lo, (size_t)sp.n_bytes, (size_t)sp.first_byte);
         std::lock_guard<std::mutex> lk(g->mu);
         if (err) {
             g->io_errno = err;
@@ -419,7 +473,7 @@ static bool ingest_take(gyp_ingest* g, int* slot, int64_t* first, int32_t* n_ms,
     std::unique_lock<std::mutex> lk(g->mu);
     if (wait) g->cv.wait(lk, [&] { return g->produced > g->taken || g->eof; });
     if (g->produced <= g->taken) return false;
-    *slot = (int)(g->taken % g->depth);
+    *slot = (int)(g->taken % g->src.depth);
     *first = g->host_first[*slot];
     *n_ms = g->host_ms[*slot];
     ++g->taken;
@@ -431,3 +485,4 @@ static void ingest_release(gyp_ingest* g, int64_t up_to_block /* exclusive */) {
     if (up_to_block > g->released) g->released = up_to_block;
     g->cv.notify_all();
 }
+

@@ -41,12 +41,16 @@ class IqFileIngest:
                  depth: int = 4, engine=None, resample_from_hz: Optional[int] = None, taps: Optional[int] = None,
                  if_hz: Optional[int] = None, packing=None) -> None:
         self.packing = packing
-        if packing is not None:
-            self._open_packed(path, samples_per_second, sample_component_data_type, block_ms, depth, engine, resample_from_hz, taps, if_hz)
-            return
-        self.dtype = np.dtype(np.float32 if sample_component_data_type is None else sample_component_data_type)
-        if self.dtype not in _FORMATS:
-            raise ValueError(f"unsupported sample component type {self.dtype} (float32, int8, int16, uint8)")
+        if packing is None:
+            self.dtype = np.dtype(np.float32 if sample_component_data_type is None else sample_component_data_type)
+            if self.dtype not in _FORMATS:
+                raise ValueError(f"unsupported sample component type {self.dtype} (float32, int8, int16, uint8)")
+        else:
+            if sample_component_data_type is not None:
+                raise ValueError("a packed recording's words are given by its packing: leave sample_component_data_type out")
+            if engine is None:
+                raise ValueError("packed recordings are unpacked on the device: pass an engine")
+            self.dtype = None
         self._lib = _lib.load()
         self.engine = engine
         self.path = Path(path)
@@ -54,16 +58,18 @@ class IqFileIngest:
         self.n = self.fs // 1000
         self.block_ms = int(block_ms)
         self._h = C.c_void_p()
-        ctx = engine.ctx if engine is not None else None
         self.resample_from_hz = None if resample_from_hz is None else int(resample_from_hz)
         self.if_hz = None if if_hz is None else int(if_hz)
+        if packing is not None:
+            self._open_packed(taps, depth)
+            return
+        ctx = engine.ctx if engine is not None else None
         if self.if_hz is not None and self.resample_from_hz is None:
             raise ValueError("if_hz needs resample_from_hz (the real recording's sample rate)")
         if self.resample_from_hz is not None:
             if engine is None:
                 raise ValueError("resampling runs on the device: pass an engine")
-            if engine.fs is not None and engine.fs != self.fs:
-                raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({engine.fs})")
+            self._check_output_rate()
             if self.if_hz is not None:   # taps None: the down-converter's automatic choice
                 rc = self._lib.gyp_ingest_open_ddc(ctx, str(self.path).encode(), _FORMATS[self.dtype], self.resample_from_hz, self.if_hz,
                                                    int(taps or 0), self.block_ms, int(depth), C.byref(self._h))
@@ -75,29 +81,20 @@ class IqFileIngest:
                                            int(depth), C.byref(self._h))
         self._check(rc)
 
-    def _open_packed(self, path, samples_per_second, dtype, block_ms, depth, engine, resample_from_hz, taps, if_hz) -> None:
-        if dtype is not None:
-            raise ValueError("a packed recording's words are given by its packing: leave sample_component_data_type out")
-        if engine is None:
-            raise ValueError("packed recordings are unpacked on the device: pass an engine")
-        self.dtype = None
-        self._lib = _lib.load()
-        self.engine = engine
-        self.path = Path(path)
-        self.fs = int(samples_per_second)
-        self.n = self.fs // 1000
-        self.block_ms = int(block_ms)
-        self._h = C.c_void_p()
-        if engine.fs is not None and engine.fs != self.fs:
-            raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({engine.fs})")
-        self.resample_from_hz = self.fs if resample_from_hz is None else int(resample_from_hz)
-        self.if_hz = None if if_hz is None else int(if_hz)
+    def _check_output_rate(self) -> None:
+        if self.engine.fs is not None and self.engine.fs != self.fs:
+            raise ValueError(f"samples_per_second ({self.fs}) is the output rate and must be the engine's stream format ({self.engine.fs})")
+
+    def _open_packed(self, taps, depth) -> None:
+        self._check_output_rate()
+        if self.resample_from_hz is None:
+            self.resample_from_hz = self.fs
         if self.packing.real and self.if_hz is None:
             raise ValueError("a real packing needs if_hz (the recording's intermediate frequency)")
         if not self.packing.real and self.if_hz is not None:
             raise ValueError("if_hz is for real packings (an I,Q packing has no intermediate frequency)")
         self._record = self.packing.record()
-        rc = self._lib.gyp_ingest_open_packed(engine.ctx, str(self.path).encode(), _lib.ptr(self._record), self.resample_from_hz,
+        rc = self._lib.gyp_ingest_open_packed(self.engine.ctx, str(self.path).encode(), _lib.ptr(self._record), self.resample_from_hz,
                                               int(self.if_hz or 0), int(taps or 0), self.block_ms, int(depth), C.byref(self._h))
         self._check(rc)
 

@@ -164,7 +164,7 @@ static void wait_ring_full(gyp_ingest* g) {
     for (;;) {
         {
             std::lock_guard<std::mutex> lk(g->mu);
-            if (g->eof || g->produced - g->released >= g->depth) return;
+            if (g->eof || g->produced - g->released >= g->src.depth) return;
         }
         std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
@@ -555,55 +555,31 @@ static void misc() {
 }
 
 // --------------------------------------------------------------------------------------------------------- halo-readers
-// A handle as ingest_open_filtered / gyp_ingest_open_packed fill it in, without a context; sizes from the product's own helper; ring
-// slots of exactly host_block_bytes; the product's reader thread and take / release protocol.
-// cases.i64 rows: packed (0/1), fmt or bits, real, order, n_in, taps, block_ms, depth, file index, restart millisecond.
+// Handles of all four kinds without a context, described, measured and sized by the product (ingest_describe, ingest_open_file,
+// ingest_span); ring slots of exactly host_block_bytes; the product's reader thread and take / release protocol.
+// cases.i64 rows: packed (0/1), fmt or bits, real, order, n_in, taps (0: not filtered), block_ms, depth, file index, restart millisecond.
+// spans.i64 rows, one per block handed out: s0, count, in_first, in_n, first_byte, bit0, n_bytes, pad_lo, pad_hi.
 static void halo_readers() {
     const std::vector<int64_t> cases = read_array<int64_t>("cases.i64");
     BlockLog log("blocks");
-    Out info("info.i64");
+    Out info("info.i64"), spans("spans.i64");
     for (size_t c = 0; c * 10 < cases.size(); ++c) {
         const int64_t* k = &cases[c * 10];
-        gyp_ingest* g = new gyp_ingest();
-        g->ctx = nullptr;
-        g->block_ms = (int32_t)k[6];
-        g->depth = (int32_t)k[7];
-        g->resampled = true;
-        g->real = k[2] != 0;
-        g->rs.taps = (int32_t)k[5];
-        g->rs.n_in = g->in_n = (int32_t)k[4];
-        g->halo_lo = g->rs.taps / 2 - 1;
-        g->halo_hi = g->rs.taps / 2;
-        if (k[0]) {
-            g->fmt = -1;
-            g->packed = true;
-            g->pk.bits = (int32_t)k[1];
-            g->pk.real = g->real;
-            g->pk.order = (int32_t)k[3];
-            g->ms_bytes = 1;
-        } else {
-            g->fmt = (int32_t)k[1];
-            g->sample_bytes = (size_t)(g->real ? 1 : 2) * ingest_word_bytes(g->fmt);
-            g->ms_bytes = (size_t)g->in_n * g->sample_bytes;
-        }
-        ingest_set_block_bytes(g);
-        const std::string path = in_path("h" + std::to_string(k[8]) + ".bin");
-        g->fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
-        struct stat st;
-        REQUIRE(g->fd >= 0 && fstat(g->fd, &st) == 0);
-        g->total_ms = st.st_size > 0 ? (int64_t)((st.st_size - 1) / (off_t)g->ms_bytes) : 0;   // as ingest_finish_open counts them
-        if (g->sample_bytes) g->file_samples = (int64_t)(st.st_size / (off_t)g->sample_bytes);
-        if (g->packed) {
-            g->file_samples = (int64_t)st.st_size * 8 / g->pk.sample_bits();
-            g->total_ms = g->file_samples > 0 ? (g->file_samples - 1) / g->in_n : 0;
-        }
+        ResampleDesign d;
+        d.taps = (int32_t)k[5];
+        d.real = k[2] != 0;
+        d.n_in = d.n_out = (int32_t)k[4];
+        PackedFormat pk;
+        pk.bits = (int32_t)k[1];
+        pk.real = d.real;
+        pk.order = (int32_t)k[3];
+        gyp_ingest* g = new gyp_ingest(nullptr, 0, ingest_describe(k[0] ? 0 : (int32_t)k[1], k[0] ? &pk : nullptr, d, 0, (int32_t)k[6], (int32_t)k[7]));
+        const IngestSource& src = g->src;
+        REQUIRE(ingest_open_file(g, in_path("h" + std::to_string(k[8]) + ".bin").c_str()) == 0);
         info.i64(g->total_ms);
         info.i64(g->file_samples);
-        info.i64((int64_t)g->host_block_bytes);
-        g->host.assign(g->depth, nullptr);
-        g->host_first.assign(g->depth, 0);
-        g->host_ms.assign(g->depth, 0);
-        for (auto& p : g->host) REQUIRE((p = (uint8_t*)std::malloc(g->host_block_bytes)) != nullptr);   // no rounding up
+        info.i64((int64_t)src.host_block_bytes);
+        for (auto& p : g->host) REQUIRE((p = (uint8_t*)std::malloc(src.host_block_bytes)) != nullptr);   // no rounding up
         auto consume = [&](int64_t tag) {
             for (;;) {
                 ingest_release(g, g->taken);
@@ -611,11 +587,10 @@ static void halo_readers() {
                 int64_t first = -1;
                 int32_t n_ms = -1;
                 if (!ingest_take(g, &slot, &first, &n_ms, true)) break;
-                size_t n_bytes;
-                if (g->packed) n_bytes = (size_t)ingest_packed_span(g, first, n_ms).n_bytes;
-                else n_bytes = ((size_t)n_ms * g->in_n + g->halo_lo + g->halo_hi) * g->sample_bytes;
-                REQUIRE(n_bytes <= g->host_block_bytes);
-                log.block(tag, first, n_ms, g->host[slot], n_bytes);
+                const IngestSpan sp = ingest_span(src, g->file_samples, first, n_ms);
+                for (int64_t v : {sp.s0, sp.count, sp.in_first, sp.in_n, sp.first_byte, (int64_t)sp.bit0, sp.n_bytes, sp.pad_lo, sp.pad_hi}) spans.i64(v);
+                REQUIRE((size_t)sp.slot_bytes() <= src.host_block_bytes);
+                log.block(tag, first, n_ms, g->host[slot], (size_t)sp.slot_bytes());
             }
             REQUIRE(g->io_errno == 0);
         };
@@ -628,8 +603,7 @@ static void halo_readers() {
             ingest_stop_reader(g);
         }
         for (auto p : g->host) std::free(p);
-        ::close(g->fd);
-        delete g;
+        ingest_free(g);
     }
 }
 

@@ -13,7 +13,7 @@ from gypsum_amd import _lib
 from gypsum_amd.antenna_sample_provider import AntennaSampleProviderResampled
 from gypsum_amd.engine import GypsumEngine
 from gypsum_amd.ingest import IqFileIngest
-from gypsum_amd.level import default_target_rms, level_from_stats
+from gypsum_amd.level import IqLevel, default_target_rms, level_from_stats
 from gypsum_amd.notch import TONE_DTYPE, as_complex
 from oracle import gypsum_oracle as orc
 
@@ -440,6 +440,48 @@ def test_the_level_is_measured_behind_the_notches(eng, scene_files):
         assert _same(_drain(eng, ing)[1], eng.condition_iq(notched, level))
     finally:
         ing.close()
+
+
+def test_a_failed_measurement_restores_the_level_the_notches_and_the_cursor(eng, tmp_path):
+    """An error past the point where calibrate / find_tones have switched the conditioning off: a float32 recording (uploaded as it
+    is) with one NaN word in millisecond 6 makes the statistics and the scan's spectrum not finite.  After each failed call the level
+    and the notches are the installed ones, and the blocks handed out afterwards are those of a twin handle nothing was asked of."""
+    fs, n, n_ms = model.SCENE_FS, model.SCENE_N, 12
+    words = np.random.default_rng(6).standard_normal((n_ms * n + 1) * 2).astype(np.float32)
+    words[2 * (6 * n + 100)] = np.nan
+    path = tmp_path / "nan.f32"
+    words.tofile(path)
+    level, tones = IqLevel(0.25, -0.5, 2.0), [100_000, -300_000]
+    subject, twin = (IqFileIngest(path, fs, np.float32, block_ms=2, depth=3, engine=eng) for _ in range(2))
+
+    def block(ing):
+        f, count, dev = ing.next_device_block()
+        buf = np.empty(count * n, dtype=np.complex64)
+        eng._check(eng.lib.gyp_memcpy_d2h(eng.ctx, _lib.ptr(buf), _lib.C.c_void_p(dev), buf.nbytes))
+        return f, count, buf.view(np.uint32)
+
+    try:
+        for ing in (subject, twin):
+            assert ing.total_ms == n_ms
+            ing.set_level(level)
+            ing.set_notches(tones)
+        first = [block(ing) for ing in (subject, twin)]
+        assert first[0][:2] == first[1][:2] == (0, 2) and _same(first[0][2], first[1][2])
+        for call, text in ((subject.calibrate, "gyp_ingest_calibrate"), (subject.find_tones, "the scan's spectrum")):
+            with pytest.raises(_lib.GypsumHipError, match=text) as e:
+                call(first_ms=4, n_ms=4)
+            assert e.value.code == BAD
+            assert subject.level == level and subject.notches == tones
+        found = subject.find_tones(first_ms=0, n_ms=4, install=False)                 # no NaN there: returns normally
+        assert isinstance(found, list) and subject.level == level and subject.notches == tones
+        for want_first in range(2, n_ms, 2):
+            a, b = block(subject), block(twin)
+            assert a[:2] == b[:2] == (want_first, 2) and _same(a[2], b[2]), want_first
+        assert subject.next_device_block() is None and twin.next_device_block() is None
+        assert np.isnan(words[2 * 6 * n:2 * 7 * n]).sum() == 1
+    finally:
+        subject.close()
+        twin.close()
 
 
 def test_the_provider_finds_and_installs_the_tones_before_it_calibrates(eng, tmp_path):

@@ -435,14 +435,18 @@ def test_misc(programs, tmp_path):
 
 # ------------------------------------------------------------------------------------------------------------ halo-readers
 def halo_cases():
-    """(packed, fmt or bits, real, order, n_in, taps, block_ms, depth, file length in bytes) for the hand-built handles."""
-    kinds = [(0, fmt, real, 0) for fmt in DTYPES for real in (0, 1)] + [(1, bits, real, (bits + real) % 2) for bits in (1, 2, 4) for real in (0, 1)]
+    """(packed, fmt or bits, real, order, n_in, taps, block_ms, depth, file length in bytes) for the context-free handles of all four
+    kinds: filtered words and filtered packed words at every tap count, and (taps 0: no halo, n_in = n) plain words and native packed words."""
+    filtered, unfiltered = (16, 64, 128), (0,)
+    kinds = [(0, fmt, real, 0, filtered) for fmt in DTYPES for real in (0, 1)]
+    kinds += [(1, bits, real, (bits + real) % 2, filtered) for bits in (1, 2, 4) for real in (0, 1)]
+    kinds += [(0, fmt, 0, 0, unfiltered) for fmt in DTYPES] + [(1, bits, 0, bits % 2, unfiltered) for bits in (1, 2, 4)]
     rows = []
-    for packed, what, real, order in kinds:
+    for packed, what, real, order, tap_counts in kinds:
         # bits per sample
         B = what * (1 if real else 2) if packed else 8 * np.dtype(DTYPES[what]).itemsize * (1 if real else 2)
         for n_in in (2048, 16368, 38192):
-            for taps in (16, 64, 128):
+            for taps in tap_counts:
                 lengths = [0, (taps // 4 * B + 7) // 8 + (1 if B > 8 else 0), ((n_in + 1) * B + 7) // 8, 23 * n_in * B // 8 + 5 * max(B // 8, 1) + (B // 16 or 1)]
                 for block_ms in (1, 7):
                     rows += [(packed, what, real, order, n_in, taps, block_ms, 3, length) for length in lengths]
@@ -469,18 +473,28 @@ def test_halo_readers(programs, tmp_path, which):
     out = run(programs, which, "halo-readers", tmp_path)
     info = np.fromfile(out / "info.i64", dtype="<i8").reshape(-1, 3).tolist()
     got = blocks(out)
+    spans = np.fromfile(out / "spans.i64", dtype="<i8").reshape(-1, 9).tolist()
+    assert len(spans) == len(got)
     at = 0
     for c, (packed, what, real, order, n_in, taps, block_ms, depth, _, restart, B, file_samples, total, length) in enumerate(cases):
-        span = block_ms * n_in + taps - 1
+        halo_lo, halo_hi = (taps // 2 - 1, taps // 2) if taps else (0, 0)
+        span = block_ms * n_in + halo_lo + halo_hi
         slot_bytes = (span * B + 7) // 8 + 1 if packed else span * B // 8
         assert info[c] == [total, file_samples, slot_bytes], cases[c]
         data = blob[:length]
         for tag, start in ((2 * c, 0), (2 * c + 1, restart)):
             for first, n_ms in reader_sequence(total, block_ms, start):
                 t, f, n, raw = got[at]
+                s0, count = first * n_in - halo_lo, n_ms * n_in + halo_lo + halo_hi
+                # the span function's numbers: the window, its part [a, b) inside the file, the bytes covering that part, the zero-fill
+                a, b = max(s0, 0), min(s0 + count, file_samples)
+                inside = [a, b - a, a * B // 8, a * B % 8, (b * B + 7) // 8 - a * B // 8] if b > a else [0, 0, 0, 0, 0]
+                pad_lo = 0 if packed else ((a - s0) if b > a else count) * B // 8
+                pad_hi = 0 if packed else count * B // 8 - pad_lo - inside[4]
+                assert spans[at] == [s0, count, *inside, pad_lo, pad_hi], (cases[c], first)
+                assert len(raw) == pad_lo + inside[4] + pad_hi <= slot_bytes
                 at += 1
                 assert (t, f, n) == (tag, first, n_ms), cases[c]
-                s0, count = first * n_in - (taps // 2 - 1), n_ms * n_in + taps - 1
                 if packed:          # the covering bytes of the part inside the file, as they are in the file
                     rc, _, _, first_byte, n_bytes, _, _, _ = span_model(what, real, n_in, length, s0, count)
                     assert rc == 0
@@ -493,6 +507,8 @@ def test_halo_readers(programs, tmp_path, which):
                         want[(a - s0) * sb:(b - s0) * sb] = data[a * sb:b * sb]
                 assert np.array_equal(raw, want), (cases[c], first)
     assert at == len(got)
+    cols = np.array(spans)      # the cases reach: a halo before sample 0, one past the end, a part that starts inside a byte
+    assert (cols[:, 7] > 0).any() and (cols[:, 8] > 0).any() and (cols[:, 5] != 0).any() and (cols[:, 0] < 0).any()
 
 
 # ------------------------------------------------------------------------------------------------------------ small-parsers
