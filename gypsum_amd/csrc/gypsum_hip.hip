@@ -206,6 +206,7 @@ struct gyp_ctx {
     bool no_exact_shared = false;   // A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
     int last_exact_path = 0;     // gyp_debug_get("last_exact_path"): the exact-sums kernel of the last plain throughput call (0 none yet, 1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel)
     bool no_spec = false;        // A/B switch: lightly loaded banks use the throughput kernel too
+    bool track_finish_all = false;   // A/B switch: every wavefront of the throughput tracking kernel merges the millisecond's profile again (same bits)
     int spec_fail_at = -1;       // (test hook): channel 0's verification is made to fail at that millisecond of a block
     bool spec_debug = false;     // per-ms window dump of the speculative tracker (gyp_debug_spec_read)
     double dll_prov_bias = 0.0;  // (test hook): added to the speculative kernel's PROVISIONAL discriminator, so
@@ -254,6 +255,13 @@ static const DebugSwitch kDebugSwitches[] = {
     GYP_SWITCH("resample_tile_samples", resample_tile, 1024, 8192, true, false),
 };
 #undef GYP_SWITCH
+// The 0 / 1 switches added since the sanitizer tests' host driver pinned the rows of kDebugSwitches (it enumerates them and counts them):
+// set, read and range-checked like a row of the table; `inherited` as there (acquire_helper).
+struct DebugFlag { const char* name; bool gyp_ctx::*field; bool inherited; };
+static const DebugFlag kDebugFlags[] = {
+    {"notch_no_lds", &gyp_ctx::notch_no_lds, false},
+    {"track_finish_all", &gyp_ctx::track_finish_all, true},
+};
 
 struct gyp_bank {
     gyp_ctx* ctx = nullptr;
@@ -1210,6 +1218,8 @@ static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
     // the helper runs under the caller's switches (it never read an environment of its own)
     for (const DebugSwitch& k : kDebugSwitches)
         if (k.inherited) k.set(*h, k.get(*ctx));
+    for (const DebugFlag& f : kDebugFlags)
+        if (f.inherited) h->*(f.field) = ctx->*(f.field);
     return h;
 }
 
@@ -1727,6 +1737,7 @@ int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stri
     p.fs = (double)ctx->fs;
     p.prof = ctx->prof.get();
     p.prof_wave = ctx->prof_wave;
+    p.finish_all = ctx->track_finish_all ? 1 : 0;
     p.codes = CodeTables{ctx->codes.trans.get(), ctx->codes.ntrans.get(), ctx->codes.chipf.get()};
     {
         const gyp_params& g = ctx->params;
@@ -2046,13 +2057,16 @@ static const DebugSwitch* debug_switch(const char* name) {
         if (std::strcmp(name, k.name) == 0) return &k;
     return nullptr;
 }
-// "notch_no_lds" 0/1, set and read like a row of kDebugSwitches (whose rows the host driver of the sanitizer tests enumerates)
-static bool debug_is_notch_switch(const char* name) { return std::strcmp(name, "notch_no_lds") == 0; }
+static const DebugFlag* debug_flag(const char* name) {
+    for (const DebugFlag& f : kDebugFlags)
+        if (std::strcmp(name, f.name) == 0) return &f;
+    return nullptr;
+}
 int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
     if (!ctx || !name) return GYP_E_BAD_ARG;
-    if (debug_is_notch_switch(name)) {
-        if (value != 0.0 && value != 1.0) return fail(ctx, GYP_E_BAD_ARG, "gyp_debug_set: notch_no_lds must be 0 or 1");
-        ctx->notch_no_lds = value != 0.0;
+    if (const DebugFlag* f = debug_flag(name)) {
+        if (value != 0.0 && value != 1.0) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be 0 or 1");
+        ctx->*(f->field) = value != 0.0;
         return GYP_OK;
     }
     const DebugSwitch* k = debug_switch(name);
@@ -2069,7 +2083,7 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
 }
 int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
-    if (debug_is_notch_switch(name)) { *out = ctx->notch_no_lds ? 1.0 : 0.0; return GYP_OK; }
+    if (const DebugFlag* f = debug_flag(name)) { *out = ctx->*(f->field) ? 1.0 : 0.0; return GYP_OK; }
     if (const DebugSwitch* k = debug_switch(name)) { *out = k->get(*ctx); return GYP_OK; }
     const int rc = debug_read_only(ctx, name, out);
     if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");

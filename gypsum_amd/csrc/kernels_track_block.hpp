@@ -240,6 +240,7 @@ struct TrackBlockParams {
     double fs;
     long long* prof;           // optional: per-phase cycle counters of workgroup 0 (debug)
     int32_t prof_wave;         // ... as seen by this wavefront's lane 0 (gyp_debug_set "prof_wave")
+    int32_t finish_all;        // throughput form, single-round rates: 1 = every wavefront merges the millisecond's profile again (gyp_debug_set "track_finish_all", A/B)
     CodeTables codes;
     LoopParams lp;
     // speculative mode (MODE 2)
@@ -309,6 +310,29 @@ struct MsMeasure {
     bool strength_pending;
     int path_info;    // gyp_track_rec::path_info
 };
+
+// The throughput kernel's PROVISIONAL discriminator from the transform's float32 taps at s -+ 1 (tracker.py:297): it only has to
+// keep int(self.phase) right for all but about one millisecond in a million -- the loop is re-integrated from float64 sums
+// afterwards and those milliseconds repaired (dll_scan_kernel).  bias: the test hook "dll_prov_bias".
+__device__ __forceinline__ double prov_disc(cf early, cf late, double bias) {
+    return (((double)early.x * (double)early.x + (double)early.y * (double)early.y) -
+            ((double)late.x * (double)late.x + (double)late.y * (double)late.y)) / 2.0 + bias;
+}
+// A single-round millisecond's measurement, every calling thread merging the published candidates for itself (epl_collect_wave).
+template <int K>
+__device__ __forceinline__ void measure_all(RedScratch* red, double bias, MsMeasure& m) {
+    const EplResult r = epl_collect_wave<K>(red);
+    m.peak = r.peak; m.peak_mag = r.best.v; m.key = r.best.key; m.sum = r.sum; m.n_max = r.n_max;
+    m.disc = prov_disc(r.early, r.late, bias);
+}
+// The measurement out of the candidates the wavefronts of a single-round millisecond have published (epl_round_wave), for
+// the calling wavefront alone: peak, arg-max and count of equal maxima, and with_sum the float64 sum of the profile.
+template <int W>
+__device__ __forceinline__ void measure_merged(const RedScratch* red, int lane, bool with_sum, MsMeasure& m) {
+    const WaveMerge g = epl_merge_lanes<W>(red, lane);
+    m.peak = g.peak; m.peak_mag = __builtin_amdgcn_sqrtf(g.v); m.key = g.key; m.n_max = g.n_max;
+    if (with_sum) m.sum = epl_sum_ordered<W>(red);
+}
 
 // tracker.py:297-303 code loop, :246-262 Costas loop with the is_locked() bandwidth switch, :346-389 histories and
 // circularity watchdog, for one millisecond of one channel; executed by wavefront 0 (all lanes, uniform values; the
@@ -1207,16 +1231,19 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
                 }
                 float* prof_row = (PROF && p.prof_tail && ms >= p.prof_from)
                                       ? p.prof_tail + ((int64_t)ch * p.prof_depth + (ms - p.prof_from)) * N : nullptr;   // uniform
-                const EplResult r = track_ms<K, false, PRE>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, nullptr, pre);
-                if (prof) t_b = (long long)__builtin_readcyclecounter();
-                m.peak = r.peak; m.peak_mag = r.best.v; m.key = r.best.key; m.sum = r.sum; m.n_max = r.n_max;
                 m.strength_pending = false;
                 m.path_info = 0;
-                // PROVISIONAL discriminator from the transform's float32 taps at s -+ 1 (tracker.py:297): it only has to keep
-                // int(self.phase) right for all but about one millisecond in a million -- the loop is re-integrated from
-                // float64 sums afterwards and those milliseconds repaired (dll_scan_kernel)
-                m.disc = (((double)r.early.x * (double)r.early.x + (double)r.early.y * (double)r.early.y) -
-                          ((double)r.late.x * (double)r.late.x + (double)r.late.y * (double)r.late.y)) / 2.0 + p.prov_bias;
+                if constexpr (Geom<K>::R > 1) {
+                    const EplResult r = track_ms<K, false, PRE>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, nullptr, pre);
+                    if (prof) t_b = (long long)__builtin_readcyclecounter();
+                    m.peak = r.peak; m.peak_mag = r.best.v; m.key = r.best.key; m.sum = r.sum; m.n_max = r.n_max;
+                    m.disc = prov_disc(r.early, r.late, p.prov_bias);
+                } else {
+                    track_ms_publish<K, PRE>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, pre);
+                    __syncthreads();   // candidates and taps published
+                    if (prof) t_b = (long long)__builtin_readcyclecounter();
+                    // (the merged profile is finished in the update phase, by the wavefronts that use it: measure_merged)
+                }
                 if (prof) t_c = (long long)__builtin_readcyclecounter();
             }
         }
@@ -1241,7 +1268,18 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
             RedScratch* red = launder_lds(sm.red);
             constexpr int kW = Geom<K>::W;          // (rates whose workgroup has fewer than three wavefronts double up)
             constexpr int kLeaveWave = 3;   // the wavefront that fetches the next millisecond's leaving ring entries
+            // Single-round rates: the millisecond's candidates and taps are published, not merged yet.  Wavefront 0 merges them for the
+            // peak, the record wavefront for the whole measurement, the code-loop wavefront reads its two taps; the others go straight
+            // on to the barrier below.  Every thread merging for itself behind the publishing barrier, as epl_finish_wave does, cost
+            // each of the eight wavefronts ~120 VALU instructions a millisecond.  finish_all (gyp_debug_set "track_finish_all", A/B)
+            // is that form again: every wavefront runs epl_collect_wave, the ones that need nothing of it included.
+            constexpr bool kSingle = Geom<K>::R == 1;
+            constexpr int kRecWave = kW >= 3 ? 2 : 0, kDllWave = kW >= 2 ? 1 : 0;
+            const bool narrow = kSingle && !p.finish_all;   // (uniform)
             if (wave == 0 && !GYP_EXPERIMENT_SKIP_UPDATE) {
+                if constexpr (kSingle) {
+                    if (narrow) measure_merged<kW>(red, lane, kRecWave == 0, m); else measure_all<K>(red, p.prov_bias, m);
+                }
                 const long long u0_ = prof ? (long long)__builtin_readcyclecounter() : 0;
                 if (GYP_EXPERIMENT_LEAVE_PF && kW >= 4 && red->leave_for_ms[ms & 1] == ms) {
                     const double* ln = red->leave_next[ms & 1];    // (filled during millisecond ms - 1; this millisecond's fetch goes to the other slot)
@@ -1254,8 +1292,25 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
                 costas_update<K, false>(red->kc, st, red, t0, lane, m, leave);
                 if (prof) { tp[6] += u1_ - u0_; tp[8] += (long long)__builtin_readcyclecounter() - u1_; }
             }
-            if (wave == (kW >= 2 ? 1 : 0)) dll_update(red, m.disc, lane, red->kc.lp);
-            if (wave == (kW >= 3 ? 2 : 0)) spec_record_fields<K>(red, m, lane);
+            if (wave == kDllWave) {
+                if constexpr (kSingle) {
+                    if (narrow) m.disc = prov_disc(make_float2(red->taps[0], red->taps[1]), make_float2(red->taps[2], red->taps[3]), p.prov_bias);
+                    else if (kDllWave != 0 || GYP_EXPERIMENT_SKIP_UPDATE) measure_all<K>(red, p.prov_bias, m);
+                }
+                dll_update(red, m.disc, lane, red->kc.lp);
+            }
+            if (wave == kRecWave) {
+                if constexpr (kSingle && (kRecWave != 0 || GYP_EXPERIMENT_SKIP_UPDATE)) {
+                    if (narrow) measure_merged<kW>(red, lane, true, m); else measure_all<K>(red, p.prov_bias, m);
+                }
+                spec_record_fields<K>(red, m, lane);
+            }
+            if constexpr (kSingle && kW > 3) {
+                if (!narrow && wave > 2) {   // the A/B form's idle wavefronts: the same merge, for nobody
+                    measure_all<K>(red, p.prov_bias, m);
+                    asm volatile("" ::"v"(m.peak.x), "v"(m.peak.y), "v"(m.peak_mag), "v"(m.key), "v"(m.sum), "v"(m.n_max), "v"(m.disc));
+                }
+            }
             if (GYP_EXPERIMENT_LEAVE_PF && kW >= 4 && wave == kLeaveWave && ms + 1 < ms_last) {
                 // what fetch_leaving will want in the next millisecond's update (positions follow from the step count: the prologue
                 // derives them the same way), asked for now: the load's latency passes under wavefront 0's update and the next

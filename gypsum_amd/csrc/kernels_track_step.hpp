@@ -227,10 +227,10 @@ __device__ __forceinline__ void epl_round_wave(const cf (&c)[16], int s, int pro
         red->cand[wave] = wc;
     }
 }
+// The merge of the W published candidates, every thread for itself (after the barrier that publishes them).
 template <int K, bool WANT_EX = false>
-__device__ __forceinline__ EplResult epl_finish_wave(RedScratch* red) {
+__device__ __forceinline__ EplResult epl_collect_wave(RedScratch* red) {
     constexpr int W = Geom<K>::W;
-    __syncthreads();   // candidates and taps published
     WaveCand g = red->cand[0];
     double sum = g.sum;
 #pragma unroll
@@ -252,6 +252,54 @@ __device__ __forceinline__ EplResult epl_finish_wave(RedScratch* red) {
     r.sum = sum;
     r.n_max = n_max;
     return r;
+}
+template <int K, bool WANT_EX = false>
+__device__ __forceinline__ EplResult epl_finish_wave(RedScratch* red) {
+    __syncthreads();   // candidates and taps published
+    return epl_collect_wave<K, WANT_EX>(red);
+}
+
+// epl_collect_wave's merge for a caller in which only some wavefronts consume it (the throughput block kernel), as
+// straight-line code: lane l holds candidate l mod 8, a row reduction (three DPP steps) leaves the winner -- largest v,
+// ties to the lowest key -- in every lane, the counts of the candidates equal to it are added the same way (integers:
+// any order), and the winner's complex value comes out of the lane that holds it.  Same bits as the chain of scalar
+// branches above: wave_profile publishes no NaN (fmaxf drops them), keys of different wavefronts differ, and where
+// they do not (a wavefront without a single valid value) the lowest wavefront wins here as there.
+struct WaveMerge {
+    float v;       // the winner's |c|^2
+    int key;
+    cf peak;       // uniform (scalar registers)
+    int n_max;
+};
+template <int W>
+__device__ __forceinline__ WaveMerge epl_merge_lanes(const RedScratch* red, int lane) {
+    static_assert(W >= 1 && W <= 8, "one candidate per lane of a half row");
+    constexpr int G = W > 4 ? 8 : (W > 2 ? 4 : (W > 1 ? 2 : 1));   // lanes per copy of the candidate list
+    const int w = lane & (G - 1);
+    const bool on = G == W || w < W;
+    const WaveCand c = red->cand[on ? w : 0];
+    const Best mine{on ? c.v : -2.0f, on ? c.key : 0x7fffffff};   // (below wave_profile's -1 of a wavefront of NaNs)
+    Best g = mine;
+    if constexpr (G > 1) g = best_step<kDppXor1>(g);
+    if constexpr (G > 2) g = best_step<kDppXor2>(g);
+    if constexpr (G > 4) g = best_step<kDppHalfMirror>(g);
+    int n = (on && c.v == g.v) ? c.cnt : 0;
+    if constexpr (G > 1) n += dpp_i<kDppXor1>(n);
+    if constexpr (G > 2) n += dpp_i<kDppXor2>(n);
+    if constexpr (G > 4) n += dpp_i<kDppHalfMirror>(n);
+    const int L = __builtin_ctzll(__ballot(mine.v == g.v && mine.key == g.key));   // (never empty: g is some lane's pair)
+    WaveMerge m;
+    m.v = g.v; m.key = g.key; m.n_max = n;
+    m.peak = make_float2(readlane_f(c.re, L), readlane_f(c.im, L));
+    return m;
+}
+// The float64 sum of the profile, added in wavefront order like epl_collect_wave's (uniform LDS reads).
+template <int W>
+__device__ __forceinline__ double epl_sum_ordered(const RedScratch* red) {
+    double sum = red->cand[0].sum;
+#pragma unroll
+    for (int w = 1; w < W; ++w) sum += red->cand[w].sum;
+    return sum;
 }
 
 template <int K, bool WANT_EX = false>
@@ -316,6 +364,18 @@ __device__ __forceinline__ EplResult track_ms(const cf* __restrict__ block, doub
     }
     generic_ex();
     return epl_finish<K, WANT_EX>(ls, sm.red, launder(threadIdx.x));
+}
+
+// The single-round track_ms up to, and not including, the barrier that publishes the candidates and the taps: for a caller
+// that takes the barrier itself and then merges only on the wavefronts that use the result (epl_merge_lanes).
+template <int K, bool HAVE_PRE = false>
+__device__ __forceinline__ void track_ms_publish(const cf* __restrict__ block, double u0, double du, const CarrierSteps& cs,
+                                                 int code_phase, int probe, const Smem& sm, const cf* __restrict__ rep, float* profile_row,
+                                                 typename PreSamples<K>::type& pre) {
+    static_assert(Geom<K>::R == 1, "single round only");
+    cf c[16];
+    correlate_round<K, HAVE_PRE>(block, 0, u0, du, cs, sm, rep, c, pre);
+    epl_round_wave<K>(c, mod_n(code_phase, K * kChips), probe, sm.red, profile_row, launder(threadIdx.x));
 }
 
 template <int K, bool WANT_EX = false>

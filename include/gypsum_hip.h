@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-/* 209 (additions, as below): signal quality per tracked channel on the device: gyp_quality_sums, gyp_quality, gyp_track_quality_dev,
+/* 209 (addition; the number stays): gyp_debug_set name track_finish_all (A/B: the throughput tracking kernel's all-wavefront finish).
+ * 209 (additions, as below): signal quality per tracked channel on the device: gyp_quality_sums, gyp_quality, gyp_track_quality_dev,
  *      gyp_track_quality, gyp_quality_from_sums.  Opt-in.
  * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband
  *      interference on the device: gyp_tone_rec, gyp_notch_tones, gyp_iq_tones_dev, gyp_notch_iq_dev, gyp_tones_find, gyp_tone_refine,
@@ -972,6 +973,11 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
  *                               speculative tracker's rounds and its re-runs keep the per-channel kernels either way
  *   "last_exact_path" (read only, gyp_debug_get)  the exact-sums kernel of the context's last plain throughput call: 0 none yet,
  *                               1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel (more than 8 samples per chip)
+ *   "track_finish_all" 0/1 (0)  the throughput tracking kernel at up to 8 samples per chip: every wavefront of a channel's workgroup merges the
+ *                               millisecond's profile candidates for itself again.  Default: only the wavefronts that use the merged
+ *                               profile do (the Costas loop's and the record's), in straight-line code, and the code loop's reads its two
+ *                               taps; same records, states and dumps bit for bit.  Rates above 8 samples per chip ignore it; the helper
+ *                               contexts of a split scan inherit it
  *   "prof_wave" 0..7 (0)        which wavefront of workgroup 0 stamps the counters of gyp_debug_track_profile
  *   "symbol_tau" 0..100 (1e-4)  |Re peak| / |peak| below which dll_scan_kernel decides the pseudosymbol in float64 (test: 10 = always)
  *   "dll_prov_bias" (0)         test hook: added to the PROVISIONAL discriminator so that the repair path runs; results must not change
