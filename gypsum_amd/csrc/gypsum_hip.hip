@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "bit_integrator.hpp"
 #include "grid_plan.hpp"
+#include "track_plan.hpp"
 #include "dev_mem.hpp"
 
 using namespace gyp;
@@ -200,11 +201,12 @@ struct gyp_ctx {
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
     gyp_params params;
-    int spec_sub_ms = 0;         // target length of a speculative block's sub-blocks (a failed verification costs one); 0 = by rate (spec_sub_ms_for)
+    int spec_sub_ms = 0;         // target length of a speculative block's sub-blocks (a failed verification costs one); 0 = by rate (spec_sub_ms_for, track_plan.hpp)
     bool spec_redo = true;       // 0 = A/B switch back to re-running a failed speculation on the throughput kernel
     int prof_wave = 0;           // which wavefront of workgroup 0 stamps gyp_debug_track_profile's counters
     bool no_exact_shared = false;   // A/B switch: the throughput path's exact sums fetch and convert the samples per channel again (dll_exact_wave_kernel)
     int last_exact_path = 0;     // gyp_debug_get("last_exact_path"): the exact-sums kernel of the last plain throughput call (0 none yet, 1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel)
+    TrackPlan last_track_plan{};   // of the last gyp_track_block_dev call; gyp_debug_get("last_track_flow") reads its flow (0 none yet, 1 throughput kernel, 2 speculative with the re-run at the end, 3 round protocol)
     bool no_spec = false;        // A/B switch: lightly loaded banks use the throughput kernel too
     bool track_finish_all = false;   // A/B switch: every wavefront of the throughput tracking kernel merges the millisecond's profile again (same bits)
     int spec_fail_at = -1;       // (test hook): channel 0's verification is made to fail at that millisecond of a block
@@ -788,7 +790,6 @@ static int launch_dll_exact(gyp_ctx* ctx, const DllExactParams& p, hipStream_t s
 }
 // The same sums for the plain throughput call at 8 samples per chip: the channels are grouped by stream on the device, then one
 // workgroup per CU stages each (group, millisecond) once for all the group's channels (dll_exact_shared_kernel).
-static bool exact_shared_applies(const gyp_ctx* ctx, int n_chan) { return ctx->k == 8 && !ctx->no_exact_shared && n_chan <= kExactGroupMaxChan; }
 static int launch_dll_exact_shared(gyp_ctx* ctx, const DllExactParams& p, ExactGroup* groups, hipStream_t stream) {
     if (p.n_chan <= 0 || p.ms_end <= p.ms_begin) return GYP_OK;
     int32_t* n_groups = reinterpret_cast<int32_t*>(groups + p.n_chan);
@@ -1408,6 +1409,8 @@ int gyp_bank_drop_channel(gyp_bank* bank, int32_t index) {
     return GYP_OK;
 }
 
+// Block tracking (gyp_track_block_dev): track_plan says what the call runs, track_param_set builds every kernel's parameters once, and
+// the flow states per launch only what differs (span_of, round_of, rerun_of).
 // Buffers of the exact code loop (hand-over records, float64 discriminators, the loop's state), any tracking path.
 static int ensure_dll_buffers(gyp_bank* bank, size_t n_rec) {
     gyp_ctx* ctx = bank->ctx;
@@ -1418,121 +1421,118 @@ static int ensure_dll_buffers(gyp_bank* bank, size_t n_rec) {
     HIP_TRY(ctx, bank->disc.reserve(n_rec, Slack::exact, s0, s1));
     return GYP_OK;
 }
-static DllExactParams dll_exact_params(gyp_bank* bank, const TrackBlockParams& p) {
+
+// The parameters of the four kernels behind a gyp_track_block_dev call (tracking, verification, exact sums, scan).
+struct TrackParamSet { TrackBlockParams trk; TrackVerifyParams ver; DllExactParams sums; DllScanParams scan; };
+// The channels the throughput kernel re-runs behind a speculative block: their flags, the checkpoints, each one's first sub-block, the exact code loop at the sub-block starts, the sub-blocks.
+struct TrackRerun { const int32_t* bad; const ChanState* ckpt; const int32_t* bad_from; const DllExact* hist; SubLayout sub; };
+
+// The set as launches over the whole block, every channel, need it (a plain throughput call's).  The bank's buffers have been reserved.
+static TrackParamSet track_param_set(gyp_bank* bank, const TrackPlan& plan, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
+                                     const double* start_time_dev, gyp_track_rec* rec_out_dev) {
     gyp_ctx* ctx = bank->ctx;
-    DllExactParams x;
-    x.iq = p.iq; x.stream_stride = p.stream_stride; x.n_ms = p.n_ms; x.ms_begin = 0; x.ms_end = p.n_ms; x.start_time = p.start_time;
-    x.states = bank->states.get(); x.n_chan = bank->n_chan; x.spec = bank->spec.get(); x.disc_out = bank->disc.get(); x.chipf = ctx->codes.chipf.get();
-    x.inv_fs = p.inv_fs; x.only_if = nullptr; x.from_sub = nullptr; x.sub = SubLayout::none(); x.trk_round = nullptr;
-    return x;
-}
-static DllScanParams dll_scan_params(gyp_bank* bank, const TrackBlockParams& p) {
-    gyp_ctx* ctx = bank->ctx;
-    DllScanParams d;
-    d.iq = p.iq; d.stream_stride = p.stream_stride; d.n_ms = p.n_ms; d.ms_begin = 0; d.ms_end = p.n_ms; d.start_time = p.start_time;
-    d.states = bank->states.get(); d.ckpt = nullptr; d.n_chan = bank->n_chan; d.spec = bank->spec.get(); d.disc = bank->disc.get();
-    d.rec_out = p.rec_out; d.exact = bank->dllx.get(); d.bad = nullptr; d.only_bad = 0; d.chipf = ctx->codes.chipf.get();
-    d.inv_fs = p.inv_fs; d.dll_gain = p.lp.dll_gain; d.dll_modulus = p.lp.dll_modulus; d.n_samples = p.lp.n_samples;
-    d.first = 1; d.final = 1; d.from_sub = nullptr; d.sub = SubLayout::none(); d.hist_out = nullptr;
+    TrackParamSet s{};   // (what is not set below is null / 0: no work list, no checkpoints, no rounds, no kept profiles)
+    const auto block = [&](auto& x) -> auto& {   // the fields all four have
+        x.iq = reinterpret_cast<const cf*>(iq_dev); x.stream_stride = stream_stride_samples; x.n_ms = n_ms; x.ms_begin = 0; x.ms_end = n_ms;
+        x.start_time = start_time_dev; x.states = bank->states.get(); x.n_chan = bank->n_chan; x.inv_fs = 1.0 / (double)ctx->fs;
+        x.sub = SubLayout::none();
+        return x;
+    };
+    TrackBlockParams& p = block(s.trk);
+    p.rec_out = rec_out_dev; p.replica_table = ctx->codes.replicas.get(); p.tw_tables = ctx->codes.tw.get(); p.fs = (double)ctx->fs;
+    p.prof = ctx->prof.get(); p.prof_wave = ctx->prof_wave; p.finish_all = ctx->track_finish_all ? 1 : 0;
+    p.codes = CodeTables{ctx->codes.trans.get(), ctx->codes.ntrans.get(), ctx->codes.chipf.get()};
+    const gyp_params& g = ctx->params;
+    // tracker.py:227-244: alpha = 4 zeta B dt, beta = 4 B^2 dt with zeta = 1/sqrt(2), dt = 1/fs, in the reference's order
+    const double dt = 1.0 / (double)ctx->fs, bl = g.pll_bandwidth_locked_hz, bu = g.pll_bandwidth_unlocked_hz;
+    p.lp = LoopParams{g.dll_gain, g.dll_phase_modulus, 4.0 * (1.0 / std::sqrt(2.0)) * bl * dt, 4.0 * (bl * bl) * dt,
+                      4.0 * (1.0 / std::sqrt(2.0)) * bu * dt, 4.0 * (bu * bu) * dt,
+                      g.lock_error_variance_max, g.lock_i_variance_max, g.lock_rotation_max_deg,
+                      std::tan(g.lock_rotation_max_deg * M_PI / 180.0),
+                      g.watchdog_period_s, g.watchdog_drop_below, g.watchdog_nudge_below, g.watchdog_nudge_hz, (double)ctx->n};
+    p.spec_out = bank->spec.get(); p.spec_kappa = plan.spec_kappa; p.prov_bias = ctx->dll_prov_bias;
+    p.exact0 = plan.flow == 1 ? bank->dllx.get() : nullptr;   // the throughput kernel leaves the code loop's state before the block here for dll_scan_kernel
+    p.dbg = plan.flow != 1 && ctx->spec_debug ? bank->dbg.get() : nullptr;
+    if (bank->prof_depth > 0) { p.prof_tail = bank->prof_tail.get(); p.prof_from = n_ms - bank->prof_rows; p.prof_depth = bank->prof_depth; }
+    TrackVerifyParams& v = block(s.ver);
+    v.spec = bank->spec.get(); v.rec_out = rec_out_dev; v.sub_index = 0; v.force_fail_ms = ctx->spec_fail_at;
+    v.replica_table = ctx->codes.replicas.get(); v.tw_tables = ctx->codes.tw.get(); v.tie_tol = 4e-6f;
+    DllExactParams& x = block(s.sums);
+    x.spec = bank->spec.get(); x.disc_out = bank->disc.get(); x.chipf = ctx->codes.chipf.get();
+    DllScanParams& d = block(s.scan);
+    d.spec = bank->spec.get(); d.disc = bank->disc.get(); d.rec_out = rec_out_dev; d.exact = bank->dllx.get(); d.only_bad = 0;
+    d.chipf = ctx->codes.chipf.get(); d.dll_gain = p.lp.dll_gain; d.dll_modulus = p.lp.dll_modulus; d.n_samples = p.lp.n_samples;
+    d.first = 1; d.final = 1; d.symbol_tau = ctx->symbol_tau;
     d.prof_delta = p.prof_tail ? bank->prof_delta.get() : nullptr; d.prof_from = p.prof_from; d.prof_depth = p.prof_depth;
-    d.symbol_tau = ctx->symbol_tau;
-    d.trk_round = nullptr; d.hist = nullptr;
-    return d;
+    return s;
+}
+// The launches cover [b, e) of every channel: sub-block j of flow 2, whose verification flags the channels that fail it and whose scan
+// starts from the checkpoints -- or a chunk of the throughput kernel, which uses the tracking part alone.
+static TrackParamSet span_of(const TrackParamSet& base, const gyp_bank* bank, int j, int b, int e) {
+    TrackParamSet s = base;
+    s.trk.ms_begin = s.ver.ms_begin = s.sums.ms_begin = s.scan.ms_begin = b;
+    s.trk.ms_end = s.ver.ms_end = s.sums.ms_end = s.scan.ms_end = e;
+    if (b > 0) s.trk.exact0 = nullptr;          // the code loop's state before the BLOCK is what dll_scan_kernel starts from
+    s.scan.bad = s.ver.bad = bank->bad.get(); s.ver.bad_from = bank->bad_from.get(); s.ver.sub_index = j;
+    s.scan.ckpt = bank->ckpt.get(); s.scan.first = b == 0 ? 1 : 0; s.scan.final = e == s.trk.n_ms ? 1 : 0;
+    s.scan.hist_out = bank->hist.get() && e < s.trk.n_ms ? bank->hist.get() + (size_t)(j + 1) * bank->n_chan : nullptr;
+    return s;
+}
+// Round R of the round protocol: every channel takes its own next sub-block (row R of the round tables; the spans are not used).
+static TrackParamSet round_of(const TrackParamSet& base, const gyp_bank* bank, const TrackPlan& plan, int R) {
+    TrackParamSet s = base;
+    s.trk.ctl = bank->ctl.get(); s.trk.trk = bank->trk.get(); s.trk.fail = bank->fail.get(); s.trk.ckpt = bank->ckpt.get();
+    s.trk.n_sub = plan.layout.n; s.trk.round = R; s.trk.exact_hist = bank->hist.get();
+    s.trk.sub = s.ver.sub = s.sums.sub = s.scan.sub = plan.layout;
+    s.ver.trk_round = s.sums.trk_round = s.scan.trk_round = bank->trk.get() + (size_t)R * bank->n_chan;
+    s.ver.fail_round = bank->fail.get() + (size_t)R * bank->n_chan;
+    s.scan.ckpt = bank->ckpt.get(); s.scan.hist = bank->hist.get(); s.scan.first = 0; s.scan.final = 0;
+    return s;
+}
+// The re-run of the channels whose speculation failed verification: only they run, each from the checkpoint of the sub-block in which
+// that happened, and the scan takes ONLY them.
+static TrackParamSet rerun_of(const TrackParamSet& base, const gyp_bank* bank, const TrackRerun& r) {
+    TrackParamSet s = base;
+    s.trk.exact0 = bank->dllx.get(); s.trk.dbg = nullptr;
+    s.trk.only_if = s.sums.only_if = s.scan.bad = r.bad; s.scan.only_bad = 1;
+    s.trk.restore_from = r.ckpt; s.trk.exact_hist = r.hist;
+    s.trk.from_sub = s.sums.from_sub = s.scan.from_sub = r.bad_from;
+    s.trk.sub = s.sums.sub = s.scan.sub = r.sub;
+    return s;
 }
 
-// The throughput tracking kernel with its code loop re-integrated exactly behind it (same stream).  only_if / restore_from: the
-// re-run of channels whose speculation failed verification.
-static int track_block_throughput(gyp_bank* bank, TrackBlockParams p, const int32_t* only_if, const ChanState* restore_from,
-                                  const int32_t* from_sub = nullptr, const DllExact* exact_hist = nullptr, SubLayout sub = SubLayout::none()) {
+// The throughput tracking kernel with its code loop re-integrated exactly behind it (same stream).  rerun: behind a speculative
+// block, for the channels whose speculation failed verification; null for a plain call.
+static int track_block_throughput(gyp_bank* bank, const TrackParamSet& base, const TrackPlan& plan, const TrackRerun* rerun = nullptr) {
     gyp_ctx* ctx = bank->ctx;
+    const TrackParamSet s = rerun ? rerun_of(base, bank, *rerun) : base;
+    const int n_ms = s.trk.n_ms;
     int rc;
-    if ((rc = ensure_dll_buffers(bank, (size_t)bank->n_chan * p.n_ms))) return rc;
-    p.ms_begin = 0; p.ms_end = p.n_ms;
-    p.spec_out = bank->spec.get(); p.exact0 = bank->dllx.get(); p.dbg = nullptr;
-    p.only_if = only_if; p.restore_from = restore_from;
-    p.from_sub = from_sub; p.exact_hist = exact_hist; p.sub = sub;
-    const bool timed = ctx->time_track && !only_if;
+    const bool timed = ctx->time_track && !rerun;
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[0].get(), ctx->stream));
-    // The channels of a stream are independent workgroups that read the same samples; nothing keeps them within an L2's worth
-    // (~11 ms of an XCD's resident streams) of each other, and over a 1000-ms launch they drift apart: FETCH_SIZE per
-    // millisecond is 1.24x the algorithmic bytes for launches of <= 250 ms and 2.6x for 1000 ms (profiles/r03_drift.txt).  A
-    // launch boundary is a rendezvous: long blocks go through in chunks (the loop state travels in ChanState anyway, and a block
-    // gives the same records however it is cut).  r03-r05: 500 ms (1.3-1.5x).  How far the workgroups of a stream drift depends on
-    // their relative pace, and with the staging instructions of r06's gain correction 500-ms launches counted 2.0x at an unchanged
-    // kernel time (profiles/r06_experiments.txt item 9).  r06: 250 ms -- 1.29x, the same 58.6 ms of tracking kernels per
-    // 1536-channel x 1000-ms step (125 ms: 1.23x), resident throughput unchanged; the price is a host-fed pipeline's overlap --
-    // the chip drains at every boundary and the upload stream's widen kernel takes it whole: int8-fed 0.960 -> 0.938 of the
-    // resident rate (profiles/r06zf_chunk_sweep.txt, r06zf_chunk_legs.txt).
-    const int chunk = (only_if || ctx->track_chunk_ms <= 0) ? p.n_ms : ctx->track_chunk_ms;
-    ctx->track_launches = (p.n_ms + chunk - 1) / chunk;
-    for (int b0 = 0; b0 < p.n_ms; b0 += chunk) {
-        TrackBlockParams q = p;
-        q.ms_begin = b0; q.ms_end = std::min(p.n_ms, b0 + chunk);
-        if (b0 > 0) q.exact0 = nullptr;          // the code loop's state before the BLOCK is what dll_scan_kernel starts from
-        if ((rc = launch_track_block(ctx, q, 0))) return rc;
-    }
+    ctx->track_launches = plan.launches;
+    for (int b0 = 0; b0 < n_ms; b0 += plan.chunk_ms)   // a launch boundary is a rendezvous of a stream's channels (track_plan)
+        if ((rc = launch_track_block(ctx, span_of(s, bank, 0, b0, std::min(n_ms, b0 + plan.chunk_ms)).trk, 0))) return rc;
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[1].get(), ctx->stream));
-    DllExactParams x = dll_exact_params(bank, p);
-    x.only_if = only_if; x.from_sub = from_sub; x.sub = sub;
-    bank->last_n_ms = p.n_ms;
-    if (!only_if && !from_sub && exact_shared_applies(ctx, bank->n_chan)) {
-        if ((rc = launch_dll_exact_shared(ctx, x, bank->groups.get(), ctx->stream))) return rc;
-        ctx->last_exact_path = 2;
-    } else {
-        if ((rc = launch_dll_exact(ctx, x, ctx->stream))) return rc;
-        if (!only_if && !from_sub) ctx->last_exact_path = ctx->k <= 8 ? 1 : 3;
-    }
+    bank->last_n_ms = n_ms;
+    if ((rc = plan.exact_path == 2 ? launch_dll_exact_shared(ctx, s.sums, bank->groups.get(), ctx->stream) : launch_dll_exact(ctx, s.sums, ctx->stream))) return rc;
+    if (!rerun) ctx->last_exact_path = plan.exact_path;
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_track[2].get(), ctx->stream));
-    DllScanParams d = dll_scan_params(bank, p);
-    d.bad = only_if; d.only_bad = only_if ? 1 : 0; d.from_sub = from_sub; d.sub = sub;
-    if ((rc = launch_dll_scan(ctx, d, ctx->stream))) return rc;
+    if ((rc = launch_dll_scan(ctx, s.scan, ctx->stream))) return rc;
     if (timed) { HIP_TRY(ctx, hipEventRecord(ctx->ev_track[3].get(), ctx->stream)); ctx->track_timed = true; }
     return GYP_OK;
 }
 
-// Speculative block tracking (8.184 / 2.046 Msps, at most one channel per CU): the tracking kernel advances on window maxima
-// (track_block_kernel MODE 2) in sub-blocks; each sub-block's full profiles are verified by track_verify_kernel on a second
-// stream while the next sub-block is being tracked, and its code loop is re-integrated there (dll_exact + dll_scan); channels
-// that failed verification are re-run from the checkpoint by the transform kernel.  Everything is enqueued; nothing
-// synchronises with the host.
-// Sub-blocks of a speculative block: the last sub-block's verification trails the tracking, and a failed verification costs a
-// sub-block (more, shorter ones for long blocks); each round re-reads the channel state and the tables (~20 us).
-static constexpr int kMaxSub = 20;
-static int spec_sub_ms_for(const gyp_ctx* ctx) { return ctx->spec_sub_ms >= 100 ? ctx->spec_sub_ms : (ctx->k == 2 ? 167 : 500); }
-static int spec_sub_blocks(int n_ms, int sub_ms = 500) {   // sub_ms: target sub-block length (gyp_debug_set "spec_sub_ms"; 500 by default)
-    const int cap = sub_ms == 500 ? kMaxSub : kMaxSubBlocks - 2;   // (a layout ends with two more, shrinking, sub-blocks: SubLayout holds 32)
-    return n_ms >= 2048 ? std::min(cap, std::max(4, n_ms / sub_ms)) : (n_ms >= 256 ? 4 : 1);
-}
-// ... and their lengths: equal ones, except that a block of sub-blocks of >= 160 ms ends with three shrinking ones (0.56, 0.34 and
-// 0.20 of the usual length) in place of its last one (SubLayout: only the last sub-block's verification is not hidden behind tracking;
-// each piece is ~0.6 of the one before because round R waits for the verification of round R - 2, which takes about half as long
-// as the tracking of the same milliseconds at 16.368 Msps and a third at 8.184).
-static SubLayout spec_layout(int n_ms, int n_sub) {
-    SubLayout l = SubLayout::none();
-    const int len = (n_ms + n_sub - 1) / n_sub;
-    int at = 0;
-    auto push = [&](int piece) {
-        if (piece <= 0 || at >= n_ms || l.n >= kMaxSubBlocks) return;
-        piece = std::min(piece, n_ms - at);
-        l.start[l.n++] = at;
-        l.longest = std::max(l.longest, piece);
-        at += piece;
-    };
-    if (n_sub > 1 && len >= 160) {
-        const int t1 = (56 * len + 99) / 100, t2 = (34 * len + 99) / 100, t3 = std::max(32, len / 5);
-        const int body = n_ms - (t1 + t2 + t3), piece = (body + n_sub - 2) / (n_sub - 1);
-        for (int j = 0; j < n_sub - 1; ++j) push(piece);
-        push(t1); push(t2);
-        push(n_ms - at);
-    } else {
-        for (int j = 0; j < n_sub; ++j) push(len);
-    }
-    for (int i = l.n; i <= kMaxSubBlocks; ++i) l.start[i] = n_ms;
-    return l;
-}
-static int ensure_spec_buffers(gyp_bank* bank, int n_sub, int rounds) {
+// Speculative block tracking (track_plan.hpp; everything is enqueued, nothing synchronises with the host).
+//   flow 2, r03 form: every sub-block's verification trails its tracking on the verify stream; channels that failed one are re-run from
+//   that sub-block's checkpoint by the TRANSFORM kernel afterwards.
+//   flow 3, the round protocol (SpecCtl, kernels_track_block.hpp): round R's tracking launch on the context's stream, its verify /
+//   exact-sums / scan launches on the verify stream behind it, launch R + 2 waiting for the verify kernels of round R.
+// The prologue: the buffers, the tables of the flow cleared, gyp_debug_spec_redo_read's counters set.
+static int spec_begin(gyp_bank* bank, const TrackPlan& plan, int n_ms) {
     gyp_ctx* ctx = bank->ctx;
-    const size_t n_chan = (size_t)bank->n_chan;
+    const size_t n_chan = (size_t)bank->n_chan, n_rec = n_chan * n_ms;
+    const int n_sub = plan.layout.n, rounds = plan.rounds;
     // each resource under its own check: a HIP failure part way through leaves what exists in place for the retry
     HIP_TRY(ctx, bank->verify_stream.create(hipStreamNonBlocking));
     const hipStream_t s0 = ctx->stream, s1 = bank->verify_stream.get();
@@ -1551,38 +1551,30 @@ static int ensure_spec_buffers(gyp_bank* bank, int n_sub, int rounds) {
     HIP_TRY(ctx, bank->hist.reserve((size_t)(n_sub + 1) * n_chan, Slack::exact, s0, s1));
     HIP_TRY(ctx, bank->trk.reserve((size_t)rounds * n_chan, Slack::exact, s0, s1));
     HIP_TRY(ctx, bank->fail.reserve((size_t)rounds * n_chan, Slack::exact, s0, s1));
-    return GYP_OK;
-}
-static TrackVerifyParams verify_params(gyp_bank* bank, const TrackBlockParams& p) {
-    gyp_ctx* ctx = bank->ctx;
-    TrackVerifyParams v;
-    v.iq = p.iq; v.stream_stride = p.stream_stride; v.n_ms = p.n_ms; v.ms_begin = 0; v.ms_end = p.n_ms; v.start_time = p.start_time;
-    v.states = bank->states.get(); v.n_chan = bank->n_chan; v.spec = bank->spec.get(); v.rec_out = p.rec_out; v.bad = bank->bad.get();
-    v.bad_from = bank->bad_from.get(); v.sub_index = 0; v.force_fail_ms = ctx->spec_fail_at;
-    v.replica_table = ctx->codes.replicas.get(); v.tw_tables = ctx->codes.tw.get(); v.inv_fs = p.inv_fs; v.tie_tol = 4e-6f;
-    v.trk_round = nullptr; v.fail_round = nullptr; v.sub = SubLayout::none();
-    return v;
-}
-static int spec_prepare(gyp_bank* bank, TrackBlockParams& p, size_t n_rec) {
-    gyp_ctx* ctx = bank->ctx;
-    p.spec_out = bank->spec.get();
-    p.exact0 = nullptr;
-    p.from_sub = nullptr; p.exact_hist = nullptr; p.sub = SubLayout::none();
-    // gyp_params::spec_confidence_kappa is quoted for 8184 lags: the chance that some noise lag beats a peak of kappa x the sample
-    // energy is (number of lags) x exp(-kappa), so a rate with fewer lags reaches the same risk at a lower threshold (2.046 Msps:
-    // 20 -> 18.6, which moves ~5 % of its milliseconds from the in-kernel transform path to the fast path; 16.368 Msps: 20.7)
-    // r06, 2.046 Msps only: a further -5 (20 -> 13.6) together with sub-blocks of ~167 ms instead of ~500 (spec_sub_ms_for).  At two
-    // samples per chip a millisecond that fails the test runs its transforms on TWO of the workgroup's eight wavefronts (~15 us against
-    // 2.9 on the fast path), and a verification that fails costs its channel one short sub-block: measured on five scenes / seeds at
-    // a N = 18..41, sigma = 6 a (tools/kappa_sweep.py, profiles/r06_experiments.txt item 2): 180-205 x -> 217-245 x real time, SURVEY d2's
-    // cfg2 scene 316 -> 320 x.  8.184 / 16.368 Msps: no difference within the noise of the measurement, left alone.
-    const double kappa_rate = std::log((double)ctx->n / 8184.0) + (ctx->k == 2 ? -5.0 : 0.0);
-    p.spec_kappa = (float)std::max(0.0, ctx->params.spec_confidence_kappa + (ctx->params.spec_confidence_kappa > 0.0 ? kappa_rate : 0.0));
-    if (ctx->spec_debug) {
-        HIP_TRY(ctx, bank->dbg.reserve(n_rec * 20, Slack::exact, ctx->stream));
-        p.dbg = bank->dbg.get();
+    if (const int rc = ensure_dll_buffers(bank, n_rec)) return rc;
+    if (plan.flow == 2) {
+        HIP_TRY(ctx, hipMemsetAsync(bank->bad.get(), 0, n_chan * sizeof(int32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->bad_from.get(), 0x7fffffff, n_chan, ctx->stream));
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(bank->ctl.get(), 0, n_chan * sizeof(SpecCtl), ctx->stream));   // cursor 0, nothing forced (rb_round 0 only ever matters for R = 1, which consults nothing)
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->fail.get(), 0x7fffffff, (size_t)rounds * n_chan, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->trk.get(), 0xffffffff, (size_t)rounds * n_chan, ctx->stream));
     }
+    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->redo_stats.get(), n_sub, plan.flow == 3 ? rounds : n_sub, 0, 0);
+    if (ctx->spec_debug) HIP_TRY(ctx, bank->dbg.reserve(n_rec * 20, Slack::exact, ctx->stream));
     return GYP_OK;
+}
+// One step: the tracking launch on the context's stream; its verification, exact sums and scan behind it on the verify stream.
+static int spec_step(gyp_bank* bank, const TrackParamSet& s) {
+    gyp_ctx* ctx = bank->ctx;
+    const hipStream_t vs = bank->verify_stream.get();
+    int rc;
+    if ((rc = launch_track_block(ctx, s.trk, 2))) return rc;
+    HIP_TRY(ctx, hipEventRecord(bank->ev_spec.get(), ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(vs, bank->ev_spec.get(), 0));
+    if ((rc = launch_track_verify(ctx, s.ver, vs))) return rc;
+    if ((rc = launch_dll_exact(ctx, s.sums, vs))) return rc;
+    return launch_dll_scan(ctx, s.scan, vs);
 }
 
 // An error between the first launch on the verify stream and the join leaves work enqueued there that reads the caller's IQ and writes
@@ -1597,120 +1589,44 @@ struct VerifyStreamGuard {
     }
 };
 
-// r03 form (blocks of one sub-block, or gyp_debug_set "spec_redo" 0): every sub-block's verification trails its tracking on the
-// verify stream; channels that failed one are re-run from that sub-block's checkpoint by the TRANSFORM kernel afterwards.
-static int track_block_speculative_rerun(gyp_bank* bank, TrackBlockParams p) {
+static int track_block_speculative(gyp_bank* bank, const TrackParamSet& base, const TrackPlan& plan) {
     gyp_ctx* ctx = bank->ctx;
-    const size_t n_rec = (size_t)bank->n_chan * p.n_ms;
+    const SubLayout& lay = plan.layout;
+    const hipStream_t vs = bank->verify_stream.get();
     int rc;
-    const SubLayout lay = spec_layout(p.n_ms, spec_sub_blocks(p.n_ms, spec_sub_ms_for(ctx)));
-    const int n_sub = lay.n;
-    if ((rc = ensure_spec_buffers(bank, n_sub, 1))) return rc;
-    if ((rc = ensure_dll_buffers(bank, n_rec))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(bank->bad.get(), 0, (size_t)bank->n_chan * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->bad_from.get(), 0x7fffffff, (size_t)bank->n_chan, ctx->stream));
-    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->redo_stats.get(), n_sub, n_sub, 0, 0);
-    if ((rc = spec_prepare(bank, p, n_rec))) return rc;
     VerifyStreamGuard join_on_error{bank};
-    TrackVerifyParams v = verify_params(bank, p);
-    DllExactParams x = dll_exact_params(bank, p);
-    DllScanParams d = dll_scan_params(bank, p);
-    d.ckpt = bank->ckpt.get(); d.bad = bank->bad.get(); d.only_bad = 0;
-    for (int j = 0; j < n_sub; ++j) {
-        const int b0 = lay.begin(j);
-        HIP_TRY(ctx, hipMemcpyAsync(bank->ckpt.get() + (size_t)j * bank->n_chan, bank->states.get(), (size_t)bank->n_chan * sizeof(ChanState),
-                                    hipMemcpyDeviceToDevice, ctx->stream));
-        p.ms_begin = b0;
-        p.ms_end = lay.end(j, p.n_ms);
-        if ((rc = launch_track_block(ctx, p, 2))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_spec.get(), ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream.get(), bank->ev_spec.get(), 0));
-        v.ms_begin = p.ms_begin;
-        v.ms_end = p.ms_end;
-        v.sub_index = j;
-        if ((rc = launch_track_verify(ctx, v, bank->verify_stream.get()))) return rc;
-        x.ms_begin = p.ms_begin; x.ms_end = p.ms_end;
-        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream.get()))) return rc;
-        d.ms_begin = p.ms_begin; d.ms_end = p.ms_end; d.first = b0 == 0 ? 1 : 0; d.final = p.ms_end == p.n_ms ? 1 : 0;
-        d.hist_out = p.ms_end < p.n_ms ? bank->hist.get() + (size_t)(j + 1) * bank->n_chan : nullptr;
-        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream.get()))) return rc;
+    if (plan.flow == 2) {
+        for (int j = 0; j < lay.n; ++j) {
+            HIP_TRY(ctx, hipMemcpyAsync(bank->ckpt.get() + (size_t)j * bank->n_chan, bank->states.get(), (size_t)bank->n_chan * sizeof(ChanState),
+                                        hipMemcpyDeviceToDevice, ctx->stream));
+            if ((rc = spec_step(bank, span_of(base, bank, j, lay.begin(j), lay.end(j, base.trk.n_ms))))) return rc;
+        }
+    } else {
+        for (int R = 0; R < plan.rounds; ++R) {
+            if (R >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_vring[(R - 2) % 3].get(), 0));   // round R - 2's reports are in
+            if ((rc = spec_step(bank, round_of(base, bank, plan, R)))) return rc;
+            HIP_TRY(ctx, hipEventRecord(bank->ev_vring[R % 3].get(), vs));
+        }
     }
-    HIP_TRY(ctx, hipEventRecord(bank->ev_verify.get(), bank->verify_stream.get()));
+    // the epilogue: the context's stream joins the verify stream, and the throughput kernel takes the channels the speculation did not finish
+    HIP_TRY(ctx, hipEventRecord(bank->ev_verify.get(), vs));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify.get(), 0));
     join_on_error.armed = false;
-    // gyp_debug_spec_redo_read's out4[3]: how many channels the transform kernel finishes (the round protocol's spec_finalize_kernel counts its own)
-    hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(64), 0, ctx->stream, bank->bad.get(), bank->n_chan, bank->redo_stats.get() + 3);
-    // channels whose window maximum was not the global one somewhere (any count is handled): again from the checkpoint of the
-    // sub-block in which that happened, through the transform kernel, their code loop re-integrated behind it
-    p.dbg = nullptr;
-    return track_block_throughput(bank, p, bank->bad.get(), bank->ckpt.get(), bank->bad_from.get(), bank->hist.get(), lay);
-}
-
-// Speculative block tracking (8.184 / 2.046 Msps, at most one channel per CU) under the round protocol (SpecCtl,
-// kernels_track_block.hpp): round R's tracking launch on the context's stream, its verify / exact-sums / scan launches on the
-// verify stream behind it, launch R + 2 waiting for the verify kernels of round R.  Everything is enqueued; nothing
-// synchronises with the host.
-static int track_block_speculative(gyp_bank* bank, TrackBlockParams p) {
-    gyp_ctx* ctx = bank->ctx;
-    const SubLayout lay = spec_layout(p.n_ms, spec_sub_blocks(p.n_ms, spec_sub_ms_for(ctx)));
-    const int n_sub_used = lay.n;
-    // The rounds couple the tracking launches to the verify launches two rounds back, so the verify kernels must keep up beside the
-    // tracking -- on the CUs the channels leave free, one workgroup per CU (launch_track_verify).  That holds for a receiver's bank
-    // (12 channels: verify 0.4 ms per 500-ms round against 2 ms of tracking) and up to about two streams; beyond, the verify launches
-    // become the bottleneck (tools/mid_bank_probe.sh: 48 channels 5.5 against 4.7 ms per 1000 ms, 252 channels 109 against 16), and
-    // those banks keep r03's flow, in which nothing waits for the verification until the end of the block.
-    constexpr int kMaxRoundProtocolChannels = 24;
-    if (n_sub_used == 1 || !ctx->spec_redo || bank->n_chan > kMaxRoundProtocolChannels) return track_block_speculative_rerun(bank, p);
-    const size_t n_rec = (size_t)bank->n_chan * p.n_ms;
-    // a re-do costs its channel two rounds: room for three of them behind the last sub-block, then the transform kernel takes over
-    const int rounds = n_sub_used + 2 + (n_sub_used >= 8 ? 6 : 2);
-    int rc;
-    if ((rc = ensure_spec_buffers(bank, n_sub_used, rounds))) return rc;
-    if ((rc = ensure_dll_buffers(bank, n_rec))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(bank->ctl.get(), 0, (size_t)bank->n_chan * sizeof(SpecCtl), ctx->stream));   // cursor 0, nothing forced (rb_round 0 only ever matters for R = 1, which consults nothing)
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->fail.get(), 0x7fffffff, (size_t)rounds * bank->n_chan, ctx->stream));
-    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bank->trk.get(), 0xffffffff, (size_t)rounds * bank->n_chan, ctx->stream));
-    hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, ctx->stream, bank->redo_stats.get(), n_sub_used, rounds, 0, 0);
-    if ((rc = spec_prepare(bank, p, n_rec))) return rc;
-    VerifyStreamGuard join_on_error{bank};
-    p.ctl = bank->ctl.get(); p.trk = bank->trk.get(); p.fail = bank->fail.get(); p.ckpt = bank->ckpt.get();
-    p.n_sub = n_sub_used; p.sub = lay; p.exact_hist = bank->hist.get();
-    p.ms_begin = 0; p.ms_end = p.n_ms;
-    TrackVerifyParams v = verify_params(bank, p);
-    v.bad = nullptr; v.bad_from = nullptr; v.sub = lay;
-    DllExactParams x = dll_exact_params(bank, p);
-    x.sub = lay;
-    DllScanParams d = dll_scan_params(bank, p);
-    d.ckpt = bank->ckpt.get(); d.bad = nullptr; d.only_bad = 0; d.first = 0; d.final = 0; d.hist_out = nullptr;
-    d.sub = lay; d.hist = bank->hist.get();
-    for (int R = 0; R < rounds; ++R) {
-        if (R >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_vring[(R - 2) % 3].get(), 0));   // round R - 2's reports are in
-        p.round = R;
-        if ((rc = launch_track_block(ctx, p, 2))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_spec.get(), ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(bank->verify_stream.get(), bank->ev_spec.get(), 0));
-        v.trk_round = bank->trk.get() + (size_t)R * bank->n_chan;
-        v.fail_round = bank->fail.get() + (size_t)R * bank->n_chan;
-        if ((rc = launch_track_verify(ctx, v, bank->verify_stream.get()))) return rc;
-        x.trk_round = v.trk_round;
-        if ((rc = launch_dll_exact(ctx, x, bank->verify_stream.get()))) return rc;
-        d.trk_round = v.trk_round;
-        if ((rc = launch_dll_scan(ctx, d, bank->verify_stream.get()))) return rc;
-        HIP_TRY(ctx, hipEventRecord(bank->ev_vring[R % 3].get(), bank->verify_stream.get()));
+    if (plan.flow == 2) {
+        // gyp_debug_spec_redo_read's out4[3]: how many channels the transform kernel finishes (the round protocol's spec_finalize_kernel counts its own)
+        hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(64), 0, ctx->stream, bank->bad.get(), bank->n_chan, bank->redo_stats.get() + 3);
+    } else {
+        SpecFinalizeParams f;
+        f.ctl = bank->ctl.get(); f.trk = bank->trk.get(); f.fail = bank->fail.get(); f.states = bank->states.get(); f.ckpt = bank->ckpt.get(); f.hist = bank->hist.get();
+        f.exact = bank->dllx.get(); f.bad = bank->bad.get(); f.bad_from = bank->bad_from.get(); f.stats = bank->redo_stats.get();
+        f.n_chan = bank->n_chan; f.n_sub = lay.n; f.rounds = plan.rounds;
+        hipLaunchKernelGGL(spec_finalize_kernel, dim3((unsigned)bank->n_chan), dim3(256), 0, ctx->stream, f);
+        HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(bank->ev_verify.get(), bank->verify_stream.get()));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, bank->ev_verify.get(), 0));
-    join_on_error.armed = false;
-    SpecFinalizeParams f;
-    f.ctl = bank->ctl.get(); f.trk = bank->trk.get(); f.fail = bank->fail.get(); f.states = bank->states.get(); f.ckpt = bank->ckpt.get(); f.hist = bank->hist.get();
-    f.exact = bank->dllx.get(); f.bad = bank->bad.get(); f.bad_from = bank->bad_from.get(); f.stats = bank->redo_stats.get();
-    f.n_chan = bank->n_chan; f.n_sub = n_sub_used; f.rounds = rounds;
-    hipLaunchKernelGGL(spec_finalize_kernel, dim3((unsigned)bank->n_chan), dim3(256), 0, ctx->stream, f);
-    HIP_TRY(ctx, hipGetLastError());
-    // channels the rounds did not finish (out of forced-transform slots or of rounds): the transform kernel, from their last good checkpoint
-    p.dbg = nullptr;
-    p.ctl = nullptr; p.trk = nullptr; p.fail = nullptr; p.ckpt = nullptr; p.n_sub = 0; p.round = 0;
-    return track_block_throughput(bank, p, bank->bad.get(), bank->ckpt.get(), bank->bad_from.get(), bank->hist.get(), lay);
+    // flow 2: channels whose window maximum was not the global one somewhere (any count is handled), from the checkpoint of the sub-block in which that
+    // happened; flow 3: channels the rounds did not finish (out of forced-transform slots or of rounds), from their last good checkpoint
+    const TrackRerun rerun{bank->bad.get(), bank->ckpt.get(), bank->bad_from.get(), bank->hist.get(), lay};
+    return track_block_throughput(bank, base, plan, &rerun);
 }
 
 int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
@@ -1722,45 +1638,15 @@ int gyp_track_block_dev(gyp_bank* bank, const float* iq_dev, int64_t stream_stri
         return fail(ctx, GYP_E_BAD_ARG, "gyp_track_block: the bank was created for " + std::to_string(bank->fs) + " Hz / " + std::to_string(bank->n) +
                                             " samples per ms, the context is now set to " + std::to_string(ctx->fs) + " / " + std::to_string(ctx->n));
     if (n_ms == 0) return GYP_OK;
-    TrackBlockParams p{};   // (what is not set below is null / 0: no work list, no checkpoints, no rounds, no kept profiles)
-    p.iq = reinterpret_cast<const cf*>(iq_dev);
-    p.stream_stride = stream_stride_samples;
-    p.n_ms = n_ms;
-    p.ms_end = n_ms;
-    p.start_time = start_time_dev;
-    p.states = bank->states.get();
-    p.n_chan = bank->n_chan;
-    p.rec_out = rec_out_dev;
-    p.replica_table = ctx->codes.replicas.get();
-    p.tw_tables = ctx->codes.tw.get();
-    p.inv_fs = 1.0 / (double)ctx->fs;
-    p.fs = (double)ctx->fs;
-    p.prof = ctx->prof.get();
-    p.prof_wave = ctx->prof_wave;
-    p.finish_all = ctx->track_finish_all ? 1 : 0;
-    p.codes = CodeTables{ctx->codes.trans.get(), ctx->codes.ntrans.get(), ctx->codes.chipf.get()};
-    {
-        const gyp_params& g = ctx->params;
-        // tracker.py:227-244: alpha = 4 zeta B dt, beta = 4 B^2 dt with zeta = 1/sqrt(2), dt = 1/fs, in the reference's order
-        const double dt = 1.0 / (double)ctx->fs, bl = g.pll_bandwidth_locked_hz, bu = g.pll_bandwidth_unlocked_hz;
-        p.lp = LoopParams{g.dll_gain, g.dll_phase_modulus, 4.0 * (1.0 / std::sqrt(2.0)) * bl * dt, 4.0 * (bl * bl) * dt,
-                          4.0 * (1.0 / std::sqrt(2.0)) * bu * dt, 4.0 * (bu * bu) * dt,
-                          g.lock_error_variance_max, g.lock_i_variance_max, g.lock_rotation_max_deg,
-                          std::tan(g.lock_rotation_max_deg * M_PI / 180.0),
-                          g.watchdog_period_s, g.watchdog_drop_below, g.watchdog_nudge_below, g.watchdog_nudge_hz, (double)ctx->n};
-    }
-    p.spec_kappa = (float)ctx->params.spec_confidence_kappa;
-    p.prov_bias = ctx->dll_prov_bias;
-    p.sub = SubLayout::none();
-    if (bank->prof_depth > 0) {   // profiles kept: the transform kernel forms every millisecond's full profile anyway
+    const TrackPlan plan = ctx->last_track_plan = track_plan(TrackShape{ctx->k, ctx->n, ctx->n_cus, bank->n_chan, n_ms, bank->prof_depth > 0},
+                                      TrackSwitches{ctx->no_pipe, ctx->no_spec, ctx->spec_redo, ctx->spec_sub_ms, ctx->track_chunk_ms, ctx->no_exact_shared, ctx->params.spec_confidence_kappa});
+    if (bank->prof_depth > 0) {
         bank->prof_rows = std::min(bank->prof_depth, (int)n_ms);
-        p.prof_tail = bank->prof_tail.get(); p.prof_from = n_ms - bank->prof_rows; p.prof_depth = bank->prof_depth;
         HIP_TRY(ctx, hipMemsetAsync(bank->prof_delta.get(), 0, (size_t)bank->n_chan * bank->prof_depth * sizeof(int32_t), ctx->stream));
-        return track_block_throughput(bank, p, nullptr, nullptr);
     }
-    const bool light = (ctx->k == 8 || ctx->k == 2 || ctx->k == 16) && p.n_chan <= ctx->n_cus && !ctx->no_pipe;   // one workgroup per CU anyway
-    if (light && !ctx->no_spec) return track_block_speculative(bank, p);
-    return track_block_throughput(bank, p, nullptr, nullptr);
+    if (const int rc = plan.flow == 1 ? ensure_dll_buffers(bank, (size_t)bank->n_chan * n_ms) : spec_begin(bank, plan, n_ms)) return rc;
+    const TrackParamSet set = track_param_set(bank, plan, iq_dev, stream_stride_samples, n_ms, start_time_dev, rec_out_dev);
+    return plan.flow == 1 ? track_block_throughput(bank, set, plan) : track_block_speculative(bank, set, plan);
 }
 
 int gyp_bank_keep_profiles(gyp_bank* bank, int32_t depth) {
@@ -1920,7 +1806,7 @@ int gyp_debug_spec_read(gyp_bank* bank, float* out, int32_t n_floats, int32_t* b
 int gyp_debug_spec_layout(int32_t n_ms, int32_t* starts_out) { return gyp_debug_spec_layout_for(n_ms, 500, starts_out); }
 int gyp_debug_spec_layout_for(int32_t n_ms, int32_t sub_ms, int32_t* starts_out) {
     if (n_ms <= 0 || sub_ms < 100 || sub_ms > 2000 || !starts_out) return GYP_E_BAD_ARG;
-    const SubLayout l = spec_layout(n_ms, spec_sub_blocks(n_ms, sub_ms));
+    const SubLayout l = spec_layout(n_ms, sub_ms);
     for (int i = 0; i <= l.n; ++i) starts_out[i] = l.start[i];
     return l.n;
 }
@@ -2024,6 +1910,7 @@ static int debug_read_only(gyp_ctx* ctx, const char* name, double* out) {
     auto is = [&](const char* n) { return std::strcmp(name, n) == 0; };
     if (is("last_grid_refined_rows")) { *out = (double)ctx->last_grid_refined_rows; return GYP_OK; }
     if (is("last_grid_path")) { *out = (double)ctx->last_grid_plan.path; return GYP_OK; }
+    if (is("last_track_flow")) { *out = (double)ctx->last_track_plan.flow; return GYP_OK; }
     if (is("last_exact_path")) { *out = (double)ctx->last_exact_path; return GYP_OK; }
     for (int w = 0; w < 3; ++w) {
         // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)

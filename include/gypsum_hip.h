@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-/* 209 (addition; the number stays): gyp_debug_set name track_finish_all (A/B: the throughput tracking kernel's all-wavefront finish).
+/* 209 (addition; the number stays): gyp_debug_get's read-only "last_track_flow" (what the last gyp_track_block(_dev) call ran).
+ * 209 (addition; the number stays): gyp_debug_set name track_finish_all (A/B: the throughput tracking kernel's all-wavefront finish).
  * 209 (additions, as below): signal quality per tracked channel on the device: gyp_quality_sums, gyp_quality, gyp_track_quality_dev,
  *      gyp_track_quality, gyp_quality_from_sums.  Opt-in.
  * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband
@@ -973,6 +974,9 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
  *                               speculative tracker's rounds and its re-runs keep the per-channel kernels either way
  *   "last_exact_path" (read only, gyp_debug_get)  the exact-sums kernel of the context's last plain throughput call: 0 none yet,
  *                               1 dll_exact_wave_kernel, 2 dll_exact_shared_kernel, 3 dll_exact_block_kernel (more than 8 samples per chip)
+ *   "last_track_flow" (read only, gyp_debug_get)  what the context's last gyp_track_block(_dev) call ran: 0 none yet, 1 the throughput
+ *                               kernel, 2 the speculative tracker with the failed channels re-run at the end of the block, 3 the speculative
+ *                               tracker under the round protocol
  *   "track_finish_all" 0/1 (0)  the throughput tracking kernel at up to 8 samples per chip: every wavefront of a channel's workgroup merges the
  *                               millisecond's profile candidates for itself again.  Default: only the wavefronts that use the merged
  *                               profile do (the Costas loop's and the record's), in straight-line code, and the code loop's reads its two

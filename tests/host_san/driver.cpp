@@ -670,6 +670,29 @@ static void grid_plans() {
     Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
 }
 
+// --------------------------------------------------------------------------------------------------------- track-plan
+// shapes.i64 rows: k, n, n_cus, n_chan, n_ms, keep_profiles, switches (bit 0 no_pipe, 1 no_spec, 2 spec_redo, 3 no_exact_shared), spec_sub_ms,
+// track_chunk_ms, spec_confidence_kappa.  plans.i64 rows: flow, rounds, chunk_ms, launches, exact_path, the bits of spec_kappa, the layout's n,
+// longest and all of start[].
+static void track_plans() {
+    const std::vector<int64_t> shapes = read_array<int64_t>("shapes.i64");
+    REQUIRE(shapes.size() % 10 == 0);
+    std::vector<int64_t> plans;
+    plans.reserve(shapes.size() / 10 * (9 + kMaxSubBlocks));
+    for (size_t r = 0; r * 10 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 10];
+        const TrackPlan pl = track_plan(TrackShape{(int)s[0], (int)s[1], (int)s[2], (int)s[3], (int)s[4], s[5] != 0},
+                                        TrackSwitches{(s[6] & 1) != 0, (s[6] & 2) != 0, (s[6] & 4) != 0, (int)s[7], (int)s[8], (s[6] & 8) != 0, (double)s[9]});
+        uint32_t kappa_bits;
+        std::memcpy(&kappa_bits, &pl.spec_kappa, sizeof(kappa_bits));
+        for (int64_t v : {(int64_t)pl.flow, (int64_t)pl.rounds, (int64_t)pl.chunk_ms, (int64_t)pl.launches, (int64_t)pl.exact_path, (int64_t)kappa_bits,
+                          (int64_t)pl.layout.n, (int64_t)pl.layout.longest})
+            plans.push_back(v);
+        for (int32_t v : pl.layout.start) plans.push_back(v);
+    }
+    Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+}
+
 // --------------------------------------------------------------------------------------------------------- dev-mem
 // The owners of dev_mem.hpp on a host without a device (every allocation fails), the scratch layouts, the table of debug switches on a
 // context that lives on the stack.  No kernel is launched and no context is made through gyp_create.
@@ -768,6 +791,7 @@ static void dev_mem() {
         REQUIRE(gyp_debug_set(&ctx, "no_such_switch", 1.0) == GYP_E_BAD_ARG && gyp_debug_set(&ctx, "last_grid_path", 1.0) == GYP_E_BAD_ARG);
         REQUIRE(gyp_debug_get(&ctx, "last_grid_path", &got) == GYP_OK && got == 0.0 && gyp_debug_get(&ctx, "last_exact_path", &got) == GYP_OK &&
                 gyp_debug_get(&ctx, "no_such_switch", &got) == GYP_E_BAD_ARG);
+        REQUIRE(gyp_debug_set(&ctx, "last_track_flow", 1.0) == GYP_E_BAD_ARG && gyp_debug_get(&ctx, "last_track_flow", &got) == GYP_OK && got == 0.0);
     }
 }
 
@@ -791,7 +815,7 @@ int main(int argc, char** argv) {
     const std::pair<const char*, void (*)()> table[] = {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
-        {"grid-plan", drv::grid_plans}, {"dev-mem", drv::dev_mem},
+        {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

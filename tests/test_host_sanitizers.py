@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -633,6 +633,70 @@ def test_grid_plan(programs, tmp_path):
         for field, value in zip(("path", "pipe", "waves", "gs", "parts"), expected):
             if value is not None:
                 assert row[grid_plan_model.FIELDS.index(field)] == value, (shape, field, row.tolist())
+
+
+# ------------------------------------------------------------------------------------------------------------ track-plan
+T_NO_PIPE, T_NO_SPEC, T_SPEC_REDO, T_NO_EXACT_SHARED = 1, 2, 4, 8      # the switches column of the track-plan scenario's shapes.i64
+# Read off the host code as it stood before track_plan.hpp, by hand: (k, n_cus, n_chan, n_ms, switches) with spec_sub_ms 0, track_chunk_ms 250,
+# no kept profiles, kappa 20 -> {field: value}; "lengths" are the sub-blocks' lengths, "starts" their first milliseconds.
+TRACK_LITERALS = [
+    ((8, 256, 12, 1000, T_SPEC_REDO), {"flow": 3, "starts": [0, 242, 484, 726, 866, 951], "rounds": 10}),
+    ((8, 256, 12, 2500, T_SPEC_REDO), {"flow": 3, "lengths": [488, 488, 488, 488, 280, 170, 98], "rounds": 11}),
+    ((8, 256, 12, 200, T_SPEC_REDO), {"flow": 2, "n": 1}),
+    ((8, 256, 25, 1000, T_SPEC_REDO), {"flow": 2, "n": 6}),
+    ((8, 256, 12, 1000, T_SPEC_REDO | T_NO_SPEC), {"flow": 1, "chunk_ms": 250, "launches": 4, "exact_path": 2}),
+    ((8, 256, 12, 1000, T_SPEC_REDO | T_NO_SPEC | T_NO_EXACT_SHARED), {"flow": 1, "chunk_ms": 250, "launches": 4, "exact_path": 1}),
+    ((8, 256, 257, 1000, T_SPEC_REDO), {"flow": 1}),
+    ((16, 256, 12, 1000, T_SPEC_REDO | T_NO_SPEC), {"flow": 1, "exact_path": 3}),
+    *[((4, 256, 12, 1000, sw), {"flow": 1}) for sw in range(16)],
+]
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_track_plan(programs, tmp_path, which):
+    """track_plan (csrc/track_plan.hpp) against tests/track_plan_model.py on every combination of the axes below and on the shapes whose
+    plans are written out above; the layout of every speculative row is also what gyp_debug_spec_layout_for returns."""
+    import track_plan_model as model
+
+    d = indir(tmp_path)
+    # k, n_cus, n_chan, n_ms, keep_profiles, switches, spec_sub_ms, track_chunk_ms, kappa
+    axes = [(1, 2, 4, 8, 16), (8, 256), (1, 12, 24, 25, 256, 257, 1536), (1, 19, 255, 256, 300, 1000, 2047, 2048, 2500, 12000), (0, 1), range(16),
+            (0, 50, 100, 167, 500, 2000), (0, 20, 250), (0, 20)]
+    sweep = np.stack([g.ravel() for g in np.meshgrid(*[np.array(a, dtype="<i8") for a in axes], indexing="ij")], axis=1)
+    assert len(sweep) == 5 * 2 * 7 * 10 * 2 * 16 * 6 * 3 * 2
+    literal = i64([(k, cus, chan, n_ms, 0, sw, 0, 250, 20) for (k, cus, chan, n_ms, sw), _ in TRACK_LITERALS])
+    rows = np.concatenate([sweep, literal])
+    k, cus, chan, n_ms, keep, sw, sub_ms, chunk, kappa = rows.T
+    np.stack([k, 1023 * k, cus, chan, n_ms, keep, sw, sub_ms, chunk, kappa], axis=1).astype("<i8").tofile(d / "shapes.i64")
+    out = run(programs, which, "track-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(rows), len(model.FIELDS))
+    want = model.track_plans(k, 1023 * k, cus, chan, n_ms, keep, sw & T_NO_PIPE, sw & T_NO_SPEC, sw & T_SPEC_REDO, sub_ms, chunk, sw & T_NO_EXACT_SHARED, kappa)
+    for col, field in enumerate(model.FIELDS):
+        bad = np.flatnonzero(got[:, col] != want[:, col])
+        assert len(bad) == 0, (field, len(bad), rows[bad[0]].tolist(), int(got[bad[0], col]), int(want[bad[0], col]))
+    plans = {f: got[:, c] for c, f in enumerate(model.FIELDS)}
+    assert set(np.unique(plans["flow"])) == {1, 2, 3} and set(np.unique(plans["exact_path"])) == {1, 2, 3}
+    assert np.array_equal(plans["n"] == 0, plans["flow"] == 1) and np.array_equal(plans["rounds"] > 1, plans["flow"] == 3)
+    assert (plans["launches"][plans["flow"] != 1] == 1).all() and plans["launches"].max() == 600
+    # the library's own layout call, for every (block length, target sub-block length) a speculative row has
+    lib = _lib.load()
+    spec = plans["flow"] != 1
+    target = np.where(sub_ms >= 100, sub_ms, np.where(k == 2, 167, 500))
+    starts = np.zeros(33, dtype=np.int32)
+    pairs = np.unique(np.stack([n_ms, target], axis=1)[spec], axis=0)
+    assert len(pairs) == 10 * 4 + 1                  # (the sweep's, and the 200-ms block written out above)
+    for block, sub in pairs.tolist():
+        n = lib.gyp_debug_spec_layout_for(block, sub, _lib.ptr(starts))
+        assert n >= 1
+        same = got[spec & (n_ms == block) & (target == sub)]
+        assert (same[:, 6] == n).all() and (same[:, 8:9 + n] == starts[:n + 1]).all() and (same[:, 9 + n:] == block).all(), (block, sub)
+        assert (same[:, 7] == np.diff(starts[:n + 1]).max()).all(), (block, sub)
+    for row, (shape, expected) in zip(got[len(sweep):], TRACK_LITERALS):
+        plan = dict(zip(model.FIELDS, row.tolist()))
+        first = [plan[f"start{i}"] for i in range(plan["n"] + 1)]
+        plan["starts"], plan["lengths"] = first[:-1], np.diff(first).tolist()
+        for field, value in expected.items():
+            assert plan[field] == value, (shape, field, plan[field])
 
 
 # ------------------------------------------------------------------------------------------------------------ dev-mem
