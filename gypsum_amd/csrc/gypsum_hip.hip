@@ -21,6 +21,7 @@
 #include "bit_integrator.hpp"
 #include "grid_plan.hpp"
 #include "track_plan.hpp"
+#include "acq_plan.hpp"
 #include "dev_mem.hpp"
 
 using namespace gyp;
@@ -131,11 +132,11 @@ static thread_local std::string g_create_error;
 //   folded, z, grid_partial   gyp_correlate_grid_dev: folded rows, the wide rates' wiped-off samples, partial results of branch runs
 //   refine_list               gyp_grid_best_bins_refined_dev (refine_list_layout)
 //   partial64                 float64 per-millisecond sums: gyp_grid_best_bins_refined_dev, acquire_search
-//   acq_*                     acquire_search (gyp_acquire_dev, gyp_search_level_dev): search states, cell table, cell outputs, refined sums, float64 profiles, acq_book_layout, acq_units_layout, shared-forward spectra
+//   acq_*                     acquire_search (gyp_acquire_dev, gyp_search_level_dev), sized by its AcqPlan and reserved in acq_reserve: search states, cell table, cell outputs, refined sums, float64 profiles, acq_book_layout, acq_units_layout, shared-forward spectra
 //   synth_scene, bench_sink   gyp_synth_iq_dev, gyp_debug_fft_bench
 // Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
 // wrapper calls another; of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
-// none calls another, and what acquire_search calls (correlate_cells_listed, gyp_correlate_cells_dev) uses no member.
+// none calls another, and what acquire_search calls (launch_cells, launch_cells_shared, gyp_correlate_cells_dev) uses no member.
 struct Scratch {
     DevBuf<float> stage_iq, stage_profile, bench_sink;
     DevBuf<uint8_t> stage_in, stage_out, refine_list, acq_book, acq_units;
@@ -186,7 +187,8 @@ struct gyp_ctx {
     int last_grid_refined_rows = 0;   // gyp_debug_get("last_grid_refined_rows"): rows the last gyp_grid_best_bins_refined_dev call decided in float64
     DevBuf<int32_t> acq_witness;        // [kAcqWitnessInts] gyp_debug_get("last_acq_units" / "last_acq_shared_cells" / "last_acq_unshared_cells", and "..._l<k>" per level): what the levels of
                                         // the last search on this context did (acq_init_kernel zeroes, the compact kernels add; read on request only)
-    int acq_witness_lanes = 1;          // parts of that search: this context and the first acq_witness_lanes - 1 helpers
+    AcqPlan last_acq_plan{};            // of that search (a split scan's: the whole scan's); gyp_debug_get("last_acq_levels" / "last_acq_shared_levels" / "last_acq_lanes") read it.  lanes: the
+                                        // parts it actually went through in -- this context and the first lanes - 1 helpers (0 none yet)
     GridPlan last_grid_plan{};    // of the last gyp_correlate_grid* call; gyp_debug_get("last_grid_path") reads its path (1 fused, 2 shared forward, 3 one wavefront per cell, 4 workgroup per cell)
     int grid_fused_waves = 12;    // 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
     bool no_grid_fused = false;   // A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
@@ -215,7 +217,6 @@ struct gyp_ctx {
                                  // that dll_scan_kernel's repair path runs; results must not depend on it
     DevBuf<long long> prof;      // gyp_debug_track_profile: per-phase cycle counters of track_block workgroup 0
     Event ev_order;              // gyp_wait_for(waiter, this): recorded on this context's stream
-    static constexpr int kMaxAcqLanes = 4;
     gyp_ctx* helper[kMaxAcqLanes - 1] = {};   // gyp_acquire_dev: the other parts of a multi-stream scan run here (own stream, scratch, tables)
     int acq_lanes = 2;
     bool is_helper = false;
@@ -240,7 +241,7 @@ static const DebugSwitch kDebugSwitches[] = {
     GYP_SWITCH("no_acq_split", no_acq_split, 0, 1, true, false),
     GYP_SWITCH("no_spec", no_spec, 0, 1, true, true),
     GYP_SWITCH("spec_debug", spec_debug, 0, 1, true, false),
-    GYP_SWITCH("acq_lanes", acq_lanes, 1, gyp_ctx::kMaxAcqLanes, true, false),
+    GYP_SWITCH("acq_lanes", acq_lanes, 1, kMaxAcqLanes, true, false),
     GYP_SWITCH("track_chunk_ms", track_chunk_ms, 0, 1e6, true, true),   // (and not 1..19: gyp_debug_set)
     GYP_SWITCH("widen_wg_per_cu", widen_wg_per_cu, 1, 8, true, false),
     GYP_SWITCH("symbol_tau", symbol_tau, 0, 100, false, true),
@@ -833,23 +834,16 @@ static CellsParams cells_params(gyp_ctx* ctx, const float* iq_dev, int64_t strea
     p.unit_of = nullptr;
     return p;
 }
-static int correlate_cells_listed(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
-                                  const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
-                                  gyp_cell* out_dev, float* profile_out_dev, const int32_t* order_dev, const int32_t* n_active_dev) {
+extern "C" {
+int gyp_correlate_cells_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
+                            const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
+                            gyp_cell* out_dev, float* profile_out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
     if (const int rc = need_format(ctx)) return rc;
     if (!iq_dev || !cells_dev || !out_dev || n_ms < 0 || n_cells < 0 || (integration != GYP_COHERENT && integration != GYP_NON_COHERENT))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_cells_dev: bad argument");
     if (n_cells == 0) return GYP_OK;
-    return launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, n_ms, cells_dev, n_cells, out_dev, profile_out_dev, order_dev,
-                                          n_active_dev), integration);
-}
-extern "C" {
-int gyp_correlate_cells_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t n_ms,
-                            const gyp_cell_desc* cells_dev, int32_t n_cells, int32_t integration,
-                            gyp_cell* out_dev, float* profile_out_dev) {
-    return correlate_cells_listed(ctx, iq_dev, stream_stride_samples, n_ms, cells_dev, n_cells, integration, out_dev, profile_out_dev,
-                                  nullptr, nullptr);
+    return launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, n_ms, cells_dev, n_cells, out_dev, profile_out_dev, nullptr, nullptr), integration);
 }
 
 int gyp_correlate_cells(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms,
@@ -890,6 +884,7 @@ static size_t refine_list_layout(void* base, size_t n_rows, size_t n_cells, Grid
 struct AcqBook {        // acquire_search's bookkeeping (Scratch::acq_book)
     gyp_cell* prev_out;                       // the previous level's records
     int32_t *reuse, *order, *cand;            // reuse map, the level's work list, the tie-break's candidate list
+    int32_t* pend;                            // = reuse: the reuse map is consumed by acq_reuse_kernel before acq_reduce_kernel fills this with the pending states
     int32_t *n_active, *n_cand, *n_pend;      // their lengths; candidates of the tie-break in n_cand[0], pending cross-level pairs in n_cand[1] = n_pend[0]
     size_t bytes;
 };
@@ -897,7 +892,7 @@ static AcqBook acq_book_layout(void* base, size_t n_cells) {
     Carve c(base);
     AcqBook b;
     b.prev_out = c.take<gyp_cell>(n_cells);
-    b.reuse = c.take<int32_t>(n_cells); b.order = c.take<int32_t>(n_cells); b.cand = c.take<int32_t>(n_cells);
+    b.pend = b.reuse = c.take<int32_t>(n_cells); b.order = c.take<int32_t>(n_cells); b.cand = c.take<int32_t>(n_cells);
     b.n_active = c.take<int32_t>(1); b.n_cand = c.take<int32_t>(1); b.n_pend = c.take<int32_t>(1);   // three counters at the start of a 64-byte tail
     c.take<int32_t>(13);
     b.bytes = c.bytes();
@@ -1077,135 +1072,137 @@ int gyp_grid_best_bins_refined_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_
 
 // ---------------------------------------------------------------- acquisition ----------------------------
 // acquisition.py:70-152 from (center, spread) down to min_spread -- or exactly one level -- for every (stream, satellite).
-static int acquire_search(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
-                          const int32_t* sat_ids_host, int32_t n_sats, double center0, double spread0, bool single_level,
-                          gyp_acq_result* out_dev, int stream_base = 0) {
+// The host path is plan -> parameter set -> begin / level / finish: acq_plan (acq_plan.hpp) says what the search runs and how large its
+// scratch is, acq_param_set builds every kernel's parameters once, and each step is the list of its launches.
+
+// The arguments of one search: a call's own, or one part of a split scan (its streams of the caller's buffers, from stream_base on)
+struct AcqCall { const float* iq_dev; int32_t n_streams; int64_t stream_stride; int32_t n_ms; const int32_t* sat_ids_host; int32_t n_sats; gyp_acq_result* out_dev; int stream_base; };
+// ... checked and planned, for both entry points and for each part of a scan.  split: a scan that may go through in parts (gyp_acquire_dev);
+// a part, a single level and a helper's search are planned whole
+static int plan_search(gyp_ctx* ctx, const AcqCall& c, const AcqSearch& q, bool split, AcqPlan* pl) {
     if (!ctx) return GYP_E_BAD_ARG;
     if (const int rc = need_format(ctx)) return rc;
-    if (!iq_dev || !sat_ids_host || !out_dev || n_streams <= 0 || n_sats <= 0 || n_ms <= 0)
+    if (!c.iq_dev || !c.sat_ids_host || !c.out_dev || c.n_streams <= 0 || c.n_sats <= 0 || c.n_ms <= 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_acquire_dev / gyp_search_level_dev: bad argument");
-    if (const int rc = check_sat_ids(ctx, sat_ids_host, n_sats)) return rc;
-    if (n_sats > 32) return fail(ctx, GYP_E_BAD_ARG, "at most 32 satellites per search");
-    const int n_states = n_streams * n_sats;
-    int rc;
-    const size_t n_cells = (size_t)n_states * kMaxBins;
+    if (const int rc = check_sat_ids(ctx, c.sat_ids_host, c.n_sats)) return rc;
+    if (c.n_sats > 32) return fail(ctx, GYP_E_BAD_ARG, "at most 32 satellites per search");
+    *pl = acq_plan(AcqShape{ctx->k, ctx->n, c.n_streams, c.n_sats, c.n_ms}, q,
+                   AcqLevels{ctx->params.acq_initial_spread_hz, ctx->params.acq_min_spread_hz, ctx->params.acq_bins_per_spread},
+                   AcqSwitches{ctx->no_pipe, ctx->no_acq_shared_fwd, ctx->no_acq_split || !split, ctx->is_helper, ctx->acq_lanes});
+    if (!pl->fits) return fail(ctx, GYP_E_BAD_ARG, "gyp_acquire_dev / gyp_search_level_dev: search too large (at most 65535 ms, and 2^31 - 1 cells at 28 per stream and satellite)");
+    return GYP_OK;
+}
+static int acq_reserve(gyp_ctx* ctx, const AcqPlan& pl) {
     Scratch& sc = ctx->scratch;
-    HIP_TRY(ctx, sc.acq_states.reserve((size_t)n_states, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.acq_cells.reserve(n_cells, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.acq_out.reserve(n_cells, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.acq_refined.reserve(n_cells, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.acq_book.reserve(acq_book_layout(nullptr, n_cells).bytes, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.partial64.reserve(n_cells * (size_t)n_ms, Slack::grow, ctx->stream));   // per-ms magnitudes of the candidates
-    // float64 profile rows of the (rare) cross-level near-ties: written whole by acq_exact_profile_kernel
-    HIP_TRY(ctx, sc.acq_profiles.reserve((size_t)n_states * 2 * ctx->n, Slack::grow, ctx->stream));
-    const AcqBook book = acq_book_layout(sc.acq_book.get(), n_cells);
-    gyp_cell* d_prev_out = book.prev_out;
-    int32_t *d_reuse = book.reuse, *d_order = book.order, *d_cand = book.cand, *d_n_active = book.n_active, *d_n_cand = book.n_cand, *d_n_pend = book.n_pend;
-    int32_t* d_pend = d_reuse;               // the reuse map is consumed by acq_reuse_kernel before acq_reduce_kernel fills this
-    double *d_partial = sc.partial64.get(), *d_profiles = sc.acq_profiles.get(), *d_refined = sc.acq_refined.get();
-    AcqSearchState* d_states = sc.acq_states.get();
-    gyp_cell_desc* d_cells = sc.acq_cells.get();
-    gyp_cell* d_out = sc.acq_out.get();
-    // Shared forward transforms (K == 8, the pipelined path): the first three levels of a scan put every satellite of a stream on the
-    // same Doppler bins -- range(-7000, 7000, 700) for all at level 1, multiples of 350 and 175 Hz at levels 2 and 3 -- so the
-    // wipe-off and the 8 forward transforms of a (stream, bin) unit are run once (corr_cells_pipe_kernel MODE 1) and read back by
-    // each of its satellites (MODE 2).  From level 4 on every satellite has a grid of its own: no unit to speak of.  The spectra
-    // take 128 KiB per unit-millisecond: room for 3 * kMaxBins units per stream (level 3 needs ~70 at most), capped at 1 GiB; units
-    // beyond the room stay on the unshared kernel.
-    const bool can_share = ctx->k == 8 && !ctx->no_pipe && !ctx->no_acq_shared_fwd;
-    AcqUnits units = {};
-    cf* d_spectra = nullptr;
-    if (can_share) {
-        const size_t unit_bytes = (size_t)n_ms * kSpecUnitMs * sizeof(cf);
-        const size_t want = std::min<size_t>((size_t)1 << 30, (size_t)n_streams * 3 * kMaxBins * unit_bytes);
-        units.max_units = (int32_t)std::min<size_t>(n_cells, want / unit_bytes);
-        if (units.max_units > 0) {
-            HIP_TRY(ctx, sc.acq_spectra.reserve((size_t)units.max_units * (unit_bytes / sizeof(cf)), Slack::grow, ctx->stream));
-            HIP_TRY(ctx, sc.acq_units.reserve(acq_units_layout(nullptr, (size_t)units.max_units, n_cells, &units), Slack::grow, ctx->stream));
-            d_spectra = sc.acq_spectra.get();
-            acq_units_layout(sc.acq_units.get(), (size_t)units.max_units, n_cells, &units);
-        }
+    HIP_TRY(ctx, sc.acq_states.reserve(pl.states, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_cells.reserve(pl.cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_out.reserve(pl.out, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_refined.reserve(pl.refined, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_book.reserve(acq_book_layout(nullptr, pl.cells).bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.partial64.reserve(pl.partial64, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.acq_profiles.reserve(pl.profiles, Slack::grow, ctx->stream));   // written whole by acq_exact_profile_kernel
+    if (pl.max_units > 0) {
+        AcqUnits sized;
+        HIP_TRY(ctx, sc.acq_spectra.reserve(pl.spectra, Slack::grow, ctx->stream));
+        HIP_TRY(ctx, sc.acq_units.reserve(acq_units_layout(nullptr, (size_t)pl.max_units, pl.cells, &sized), Slack::grow, ctx->stream));
     }
-    const int tpb = 64, nblk = (n_states + tpb - 1) / tpb;
-    {
-        AcqSatList sl;
-        for (int i = 0; i < 32; ++i) sl.id[i] = i < n_sats ? sat_ids_host[i] : 0;
-        hipLaunchKernelGGL(acq_init_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, n_sats, sl, center0, spread0,
-                           ctx->acq_witness.get());   // acquisition.py:78-79
+    return GYP_OK;
+}
+
+// Every kernel's parameters of one search, built once from the context, the plan and the reserved scratch: no level changes any of them
+struct AcqParamSet {
+    AcqSearchState* states; gyp_cell_desc* cells; gyp_cell* out; double* refined;   // Scratch::acq_states, acq_cells, acq_out, acq_refined
+    int cells_per_stream;
+    AcqBook book;
+    AcqUnits units;
+    CellsParams cells_units, cells_shared, cells_listed;   // MODE 1 over the units, MODE 2 over their cells; the level's work list
+    RefineParams refine;
+    ExactParams exact;
+};
+static AcqParamSet acq_param_set(gyp_ctx* ctx, const AcqCall& c, const AcqPlan& pl) {
+    Scratch& sc = ctx->scratch;
+    AcqParamSet s{};
+    s.states = sc.acq_states.get(); s.cells = sc.acq_cells.get(); s.out = sc.acq_out.get(); s.refined = sc.acq_refined.get();
+    s.cells_per_stream = c.n_sats * kMaxBins;
+    s.book = acq_book_layout(sc.acq_book.get(), pl.cells);
+    s.cells_listed = cells_params(ctx, c.iq_dev, c.stream_stride, c.n_ms, s.cells, pl.n_cells, s.out, nullptr, s.book.order, s.book.n_active);
+    s.units.max_units = pl.max_units;
+    if (pl.max_units > 0) {
+        acq_units_layout(sc.acq_units.get(), (size_t)pl.max_units, pl.cells, &s.units);
+        s.cells_units = s.cells_listed;
+        s.cells_units.order = s.units.unit_cell; s.cells_units.n_active = s.units.counts; s.cells_units.prof = nullptr; s.cells_units.spectra = sc.acq_spectra.get();
+        s.cells_shared = s.cells_units;
+        s.cells_shared.order = s.units.sh_cell; s.cells_shared.n_active = s.units.counts + 1; s.cells_shared.unit_of = s.units.sh_unit;
     }
-    int level = 0;
-    for (double spread = spread0; single_level ? spread == spread0 : spread >= ctx->params.acq_min_spread_hz; spread /= 2.0, ++level) {  // acquisition.py:81,89
-        hipLaunchKernelGGL(acq_plan_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_cells, d_reuse, ctx->params.acq_bins_per_spread,
-                           ctx->params.acq_reuse_level_records != 0.0 ? 1 : 0);
-        const bool shared = d_spectra && spread * 4.0 >= ctx->params.acq_initial_spread_hz;   // levels 1-3 of a scan
-        if (shared) {
-            hipLaunchKernelGGL(acq_compact_units_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells,
-                               n_sats * kMaxBins, d_order, d_n_active, d_n_cand, units, ctx->acq_witness.get(), level);
-            CellsParams pu = cells_params(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, d_out, nullptr, units.unit_cell,
-                                          units.counts);
-            pu.prof = nullptr;
-            pu.spectra = d_spectra;
-            CellsParams pc = pu;
-            pc.order = units.sh_cell;
-            pc.n_active = units.counts + 1;
-            pc.unit_of = units.sh_unit;
-            if ((rc = launch_cells_shared(ctx, pu, pc))) return rc;
-        } else {
-            hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const gyp_cell_desc*)d_cells, (int)n_cells, d_order, d_n_active, d_n_cand,
-                               ctx->acq_witness.get(), level);
-        }
-        rc = correlate_cells_listed(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, (int32_t)n_cells, GYP_NON_COHERENT, d_out, nullptr,
-                                    d_order, d_n_active);
-        if (rc) return rc;
-        hipLaunchKernelGGL(acq_reuse_kernel, dim3((unsigned)n_states), dim3(64), 0, ctx->stream, (const int32_t*)d_reuse, d_out, d_prev_out,
-                           (const AcqSearchState*)d_states, d_refined, d_cand, d_n_cand, n_states);
-        RefineParams rp;
-        rp.iq = reinterpret_cast<const cf*>(iq_dev);
-        rp.stream_stride = stream_stride_samples;
-        rp.n_ms = n_ms;
-        rp.n_per_ms = ctx->n;
-        rp.k = ctx->k;
-        rp.states = d_states;
-        rp.cells = d_cells;
-        rp.out = d_out;
-        rp.refined = d_refined;
-        rp.chips = ctx->codes.chips.get();
-        rp.inv_fs = 1.0 / (double)ctx->fs;
-        rp.cand = d_cand; rp.n_cand = d_n_cand; rp.partial = d_partial;
-        // normally one or two candidates per (stream, satellite): 2 n_states slots x n_ms blocks, strided beyond that
-        hipLaunchKernelGGL(acq_refine_kernel, dim3((unsigned)std::min<size_t>(n_cells, 2 * (size_t)n_states), (unsigned)n_ms), dim3(256), 0, ctx->stream, rp);
-        hipLaunchKernelGGL(acq_refine_sum_kernel, dim3((unsigned)((n_states + 63) / 64)), dim3(64), 0, ctx->stream, rp);
-        hipLaunchKernelGGL(acq_reduce_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_out, d_refined, ctx->n, d_pend, d_n_pend);
-        // cross-level near-ties in strength: float64 profiles for the (few) pending pairs, else immediate exits
-        ExactParams ep;
-        ep.iq = rp.iq; ep.stream_stride = stream_stride_samples; ep.n_ms = n_ms; ep.n_per_ms = ctx->n; ep.k = ctx->k; ep.n_states = n_states;
-        ep.states = d_states; ep.ones = ctx->codes.ones.get(); ep.inv_fs = rp.inv_fs; ep.profiles = d_profiles;
-        ep.pend = d_pend; ep.n_pend = d_n_pend;
-        // (pending pairs are rare -- about one acquisition in a hundred: a short z grid whose blocks walk the states)
-        hipLaunchKernelGGL(acq_exact_profile_kernel, dim3((unsigned)(ctx->k * kExactSplit), 2, (unsigned)std::min(n_states, 32)), dim3(1024), 0, ctx->stream, ep);
-        hipLaunchKernelGGL(acq_exact_decide_kernel, dim3((unsigned)std::min(n_states, 32)), dim3(256), 0, ctx->stream, ep);
+    RefineParams& rp = s.refine;
+    rp.iq = reinterpret_cast<const cf*>(c.iq_dev); rp.stream_stride = c.stream_stride; rp.n_ms = c.n_ms; rp.n_per_ms = ctx->n; rp.k = ctx->k;
+    rp.states = s.states; rp.cells = s.cells; rp.out = s.out; rp.refined = s.refined;
+    rp.chips = ctx->codes.chips.get(); rp.inv_fs = 1.0 / (double)ctx->fs;
+    rp.cand = s.book.cand; rp.n_cand = s.book.n_cand; rp.partial = sc.partial64.get();
+    ExactParams& ep = s.exact;   // cross-level near-ties in strength: float64 profiles for the (few) pending pairs, else immediate exits
+    ep.iq = rp.iq; ep.stream_stride = c.stream_stride; ep.n_ms = c.n_ms; ep.n_per_ms = ctx->n; ep.k = ctx->k; ep.n_states = pl.n_states;
+    ep.states = s.states; ep.ones = ctx->codes.ones.get(); ep.inv_fs = rp.inv_fs; ep.profiles = sc.acq_profiles.get();
+    ep.pend = s.book.pend; ep.n_pend = s.book.n_pend;
+    return s;
+}
+
+static void acq_begin(gyp_ctx* ctx, const AcqCall& c, const AcqSearch& q, const AcqParamSet& s, const AcqPlan& pl) {
+    AcqSatList sl;
+    for (int i = 0; i < 32; ++i) sl.id[i] = i < c.n_sats ? c.sat_ids_host[i] : 0;
+    hipLaunchKernelGGL(acq_init_kernel, dim3(pl.nblk), dim3(pl.tpb), 0, ctx->stream, s.states, pl.n_states, c.n_sats, sl, q.center0, q.spread0,
+                       ctx->acq_witness.get());   // acquisition.py:78-79
+}
+static int acq_level(gyp_ctx* ctx, const AcqParamSet& s, const AcqPlan& pl, int level) {
+    const dim3 per_state(pl.nblk), tpb(pl.tpb);
+    const AcqBook& b = s.book;
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(acq_plan_kernel, per_state, tpb, 0, st, s.states, pl.n_states, s.cells, b.reuse, pl.bins_per_spread,
+                       ctx->params.acq_reuse_level_records != 0.0 ? 1 : 0);
+    if (level < pl.shared_levels) {
+        hipLaunchKernelGGL(acq_compact_units_kernel, dim3(1), dim3(1024), 0, st, (const gyp_cell_desc*)s.cells, pl.n_cells, s.cells_per_stream,
+                           b.order, b.n_active, b.n_cand, s.units, ctx->acq_witness.get(), level);
+        if (const int rc = launch_cells_shared(ctx, s.cells_units, s.cells_shared)) return rc;
+    } else {
+        hipLaunchKernelGGL(acq_compact_kernel, dim3(1), dim3(1024), 0, st, (const gyp_cell_desc*)s.cells, pl.n_cells, b.order, b.n_active, b.n_cand,
+                           ctx->acq_witness.get(), level);
     }
-    if (single_level) {
-        hipLaunchKernelGGL(acq_finish_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, (const gyp_cell*)nullptr, out_dev, stream_base);
-        HIP_TRY(ctx, hipGetLastError());
-        return GYP_OK;
+    if (const int rc = launch_cells(ctx, s.cells_listed, GYP_NON_COHERENT)) return rc;
+    hipLaunchKernelGGL(acq_reuse_kernel, dim3((unsigned)pl.n_states), dim3(64), 0, st, (const int32_t*)b.reuse, s.out, b.prev_out,
+                       (const AcqSearchState*)s.states, s.refined, b.cand, b.n_cand, pl.n_states);
+    hipLaunchKernelGGL(acq_refine_kernel, dim3((unsigned)pl.refine_x, (unsigned)pl.refine_y), dim3(256), 0, st, s.refine);
+    hipLaunchKernelGGL(acq_refine_sum_kernel, per_state, dim3(64), 0, st, s.refine);
+    hipLaunchKernelGGL(acq_reduce_kernel, per_state, tpb, 0, st, s.states, pl.n_states, s.out, s.refined, ctx->n, b.pend, b.n_pend);
+    hipLaunchKernelGGL(acq_exact_profile_kernel, dim3((unsigned)(ctx->k * kExactSplit), 2, (unsigned)pl.exact_z), dim3(1024), 0, st, s.exact);
+    hipLaunchKernelGGL(acq_exact_decide_kernel, dim3((unsigned)pl.exact_z), dim3(256), 0, st, s.exact);
+    return GYP_OK;
+}
+// The coherent pass over every state's best bin (acquisition.py:91-152) -- a single level reports its bin as it is
+static int acq_finish(gyp_ctx* ctx, const AcqCall& c, const AcqSearch& q, const AcqParamSet& s, const AcqPlan& pl) {
+    const gyp_cell* coherent = nullptr;
+    if (!q.single_level) {
+        hipLaunchKernelGGL(acq_plan_coherent_kernel, dim3(pl.nblk), dim3(pl.tpb), 0, ctx->stream, s.states, pl.n_states, s.cells);
+        if (const int rc = gyp_correlate_cells_dev(ctx, c.iq_dev, c.stream_stride, c.n_ms, s.cells, pl.n_states, GYP_COHERENT, s.out, nullptr)) return rc;
+        coherent = s.out;
     }
-    hipLaunchKernelGGL(acq_plan_coherent_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_cells);
-    rc = gyp_correlate_cells_dev(ctx, iq_dev, stream_stride_samples, n_ms, d_cells, n_states, GYP_COHERENT, d_out, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(acq_finish_kernel, dim3(nblk), dim3(tpb), 0, ctx->stream, d_states, n_states, d_out, out_dev, stream_base);
+    hipLaunchKernelGGL(acq_finish_kernel, dim3(pl.nblk), dim3(pl.tpb), 0, ctx->stream, s.states, pl.n_states, coherent, c.out_dev, c.stream_base);
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
 
+static int acquire_search(gyp_ctx* ctx, const AcqCall& c, const AcqSearch& q) {
+    AcqPlan pl;
+    if (const int rc = plan_search(ctx, c, q, false, &pl)) return rc;
+    ctx->last_acq_plan = pl;
+    if (const int rc = acq_reserve(ctx, pl)) return rc;
+    const AcqParamSet set = acq_param_set(ctx, c, pl);
+    acq_begin(ctx, c, q, set, pl);
+    for (int level = 0; level < pl.n_levels; ++level)
+        if (const int rc = acq_level(ctx, set, pl, level)) return rc;
+    return acq_finish(ctx, c, q, set, pl);
+}
 
-// A scan is ten levels of one big correlation launch each plus eight small bookkeeping launches (the tie-breaks, the reductions:
-// ~3 ms of a 13-stream scan during which the chip is almost empty, profiles/r03y_acq_timeline.txt) and the big launches end in
-// a ragged last round of workgroups.  Streams are searched independently of each other, so a scan of several streams goes
-// through in parts on several HIP streams -- the others on helper contexts of their own (own scratch and tables): one part's
-// big launch fills the chip while another part is in its small ones.  Same results bit for bit.
+// The other parts of a multi-stream scan (AcqPlan::lanes) run on helper contexts of their own
 static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
-    if (ctx->is_helper || ctx->no_acq_split) return nullptr;
     if (!ctx->helper[which]) {
         gyp_ctx* h = nullptr;
         if (gyp_create(ctx->device, &h) != GYP_OK) return nullptr;
@@ -1226,34 +1223,32 @@ static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
 
 int gyp_acquire_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples,
                     int32_t n_ms, const int32_t* sat_ids_host, int32_t n_sats, gyp_acq_result* out_dev) {
-    if (!ctx) return GYP_E_BAD_ARG;
-    int lanes = (ctx->k && iq_dev && out_dev && n_sats > 0 && !ctx->is_helper && !ctx->no_acq_split)
-                    ? std::max(1, std::min(ctx->acq_lanes, n_streams / 2)) : 1;
-    gyp_ctx* lane_ctx[gyp_ctx::kMaxAcqLanes] = {ctx};
-    for (int i = 1; i < lanes; ++i)
-        if (!(lane_ctx[i] = acquire_helper(ctx, i - 1))) { lanes = 1; break; }
-    ctx->acq_witness_lanes = lanes;
-    if (lanes == 1)
-        return acquire_search(ctx, iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, 0.0,
-                              ctx->params.acq_initial_spread_hz, false, out_dev);
+    const AcqCall call{iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, out_dev, 0};
+    const AcqSearch scan{0.0, ctx ? ctx->params.acq_initial_spread_hz : 0.0, false};
+    AcqPlan pl;
+    if (const int rc = plan_search(ctx, call, scan, true, &pl)) return rc;
+    gyp_ctx* lane_ctx[kMaxAcqLanes] = {ctx};
+    for (int i = 1; i < pl.lanes; ++i)
+        if (!(lane_ctx[i] = acquire_helper(ctx, i - 1))) pl.lanes = 1;   // no helper: the whole scan on this context
+    if (pl.lanes == 1) return acquire_search(ctx, call, scan);
     int rc = GYP_OK;
     std::string why;
     // (a failure of gyp_wait_for(helper, ctx) leaves its text in the helper: everything is reported through the caller's context)
-    for (int i = 1; i < lanes && !rc; ++i)
+    for (int i = 1; i < pl.lanes && !rc; ++i)
         if ((rc = gyp_wait_for(lane_ctx[i], ctx))) why = "gyp_acquire_dev: ordering a helper stream behind the caller's: " + lane_ctx[i]->err;   // the samples may still be on their way on this context's stream
-    int s0 = 0, enqueued = 0;
-    for (int i = 0; i < lanes && !rc; ++i) {
-        const int cnt = (n_streams - s0) / (lanes - i);           // remaining streams spread evenly over the remaining lanes
+    int enqueued = 0;
+    for (int i = 0; i < pl.lanes && !rc; ++i) {
+        const int s0 = pl.lane_first[i];
         gyp_ctx* c = lane_ctx[i];
-        rc = acquire_search(c, iq_dev + (int64_t)s0 * stream_stride_samples * 2, cnt, stream_stride_samples, n_ms, sat_ids_host, n_sats,
-                            0.0, ctx->params.acq_initial_spread_hz, false, out_dev + (size_t)s0 * n_sats, s0);
+        rc = acquire_search(c, AcqCall{iq_dev + (int64_t)s0 * stream_stride_samples * 2, pl.lane_streams[i], stream_stride_samples, n_ms, sat_ids_host, n_sats,
+                                       out_dev + (size_t)s0 * n_sats, s0}, scan);
         if (rc) why = c == ctx ? ctx->err : std::string("part of the scan on a helper stream: ") + c->err;
         enqueued = i + 1;   // (a part that failed half way may have launches in flight too)
-        s0 += cnt;
     }
+    ctx->last_acq_plan = pl;   // the scan's, with the parts it went through in (this context's own part has left its plan here)
     // Join every helper that may have work in flight -- ALSO on failure: the caller is entitled to free or overwrite iq_dev /
     // out_dev as soon as its own stream has passed this point, error or not.
-    for (int i = 1; i < std::max(enqueued, rc ? lanes : 0); ++i) {
+    for (int i = 1; i < std::max(enqueued, rc ? pl.lanes : 0); ++i) {
         const int rj = gyp_wait_for(ctx, lane_ctx[i]);            // whatever follows on this context's stream sees every part
         if (rj && !rc) { rc = rj; why = "gyp_acquire_dev: joining a helper stream: " + ctx->err; }
         if (rj) (void)hipStreamSynchronize(lane_ctx[i]->stream);  // the event path failed: wait for the helper on the host instead
@@ -1267,8 +1262,7 @@ int gyp_search_level_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, i
     const int step = (int)(spread_hz / ctx->params.acq_bins_per_spread);
     if (!(spread_hz > 0) || step < 1 || ((int)(center_hz + spread_hz) - (int)(center_hz - spread_hz) + step - 1) / step > kMaxBins)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_search_level_dev: the level must have between 1 and 28 Doppler bins");
-    ctx->acq_witness_lanes = 1;
-    return acquire_search(ctx, iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, true, out_dev);
+    return acquire_search(ctx, AcqCall{iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, out_dev, 0}, AcqSearch{center_hz, spread_hz, true});
 }
 
 }   // extern "C"
@@ -1912,6 +1906,9 @@ static int debug_read_only(gyp_ctx* ctx, const char* name, double* out) {
     if (is("last_grid_path")) { *out = (double)ctx->last_grid_plan.path; return GYP_OK; }
     if (is("last_track_flow")) { *out = (double)ctx->last_track_plan.flow; return GYP_OK; }
     if (is("last_exact_path")) { *out = (double)ctx->last_exact_path; return GYP_OK; }
+    if (is("last_acq_lanes")) { *out = (double)ctx->last_acq_plan.lanes; return GYP_OK; }
+    if (is("last_acq_levels")) { *out = (double)ctx->last_acq_plan.n_levels; return GYP_OK; }
+    if (is("last_acq_shared_levels")) { *out = (double)ctx->last_acq_plan.shared_levels; return GYP_OK; }
     for (int w = 0; w < 3; ++w) {
         // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)
         static const char* const kWitness[3] = {"last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"};
@@ -1926,7 +1923,7 @@ static int debug_read_only(gyp_ctx* ctx, const char* name, double* out) {
         }
         // the one place the counters are waited for and copied: this context's part of the last search plus the helpers' parts
         long long total = 0;
-        for (int i = 0; i < ctx->acq_witness_lanes; ++i) {
+        for (int i = 0; i < ctx->last_acq_plan.lanes; ++i) {
             gyp_ctx* c = i == 0 ? ctx : ctx->helper[i - 1];
             if (!c || !c->acq_witness.get()) continue;
             int32_t v = 0;

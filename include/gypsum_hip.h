@@ -28,7 +28,10 @@
 extern "C" {
 #endif
 
-/* 209 (addition; the number stays): gyp_debug_get's read-only "last_track_flow" (what the last gyp_track_block(_dev) call ran).
+/* 209 (additions; the number stays): gyp_debug_get's read-only "last_acq_lanes", "last_acq_levels", "last_acq_shared_levels" (what the last
+ *      search ran).  gyp_acquire_dev and gyp_search_level_dev refuse, with GYP_E_BAD_ARG, a search of more than 65535 ms or of more than
+ *      2^31 - 1 cells (28 per stream and satellite) before anything runs; such a search never worked.
+ * 209 (addition; the number stays): gyp_debug_get's read-only "last_track_flow" (what the last gyp_track_block(_dev) call ran).
  * 209 (addition; the number stays): gyp_debug_set name track_finish_all (A/B: the throughput tracking kernel's all-wavefront finish).
  * 209 (additions, as below): signal quality per tracked channel on the device: gyp_quality_sums, gyp_quality, gyp_track_quality_dev,
  *      gyp_track_quality, gyp_quality_from_sums.  Opt-in.
@@ -977,6 +980,11 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
  *   "last_track_flow" (read only, gyp_debug_get)  what the context's last gyp_track_block(_dev) call ran: 0 none yet, 1 the throughput
  *                               kernel, 2 the speculative tracker with the failed channels re-run at the end of the block, 3 the speculative
  *                               tracker under the round protocol
+ *   "last_acq_lanes", "last_acq_levels", "last_acq_shared_levels" (read only, gyp_debug_get)  what the context's last gyp_acquire(_dev) /
+ *                               gyp_search_level(_dev) call ran (0 none yet): the parts it actually went through in (this context and that many
+ *                               helper contexts less one; 1 for a single level), its levels (10 with the default parameters, 1 for a single
+ *                               level), and how many of the first of them went through the shared-forward kernels (3 of a scan at 8 samples
+ *                               per chip; 0 at other rates, with "no_pipe" or "no_acq_shared_fwd" 1 and beyond 8192 ms)
  *   "track_finish_all" 0/1 (0)  the throughput tracking kernel at up to 8 samples per chip: every wavefront of a channel's workgroup merges the
  *                               millisecond's profile candidates for itself again.  Default: only the wavefronts that use the merged
  *                               profile do (the Costas loop's and the record's), in straight-line code, and the code loop's reads its two

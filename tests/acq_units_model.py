@@ -1,5 +1,5 @@
 """CPU model of the shared-forward planner of the acquisition search (acq_plan_kernel and acq_compact_units_kernel,
-kernels_acq.hpp; the room for units as acquire_search computes it, gypsum_hip.hip): the level's active cells -- the level's bins,
+kernels_acq.hpp; the room for units is acq_plan_model's, the restatement of acq_plan.hpp): the level's active cells -- the level's bins,
 minus the bins whose records the previous level already holds -- grouped by exact (stream, Doppler) equality; a unit of two or more
 cells gets one forward pass, units are numbered in the order of their first cell and those beyond the spectra buffer's room stay on
 the unshared kernel.  Plain Python over lists: the CPU tests check it against hand counts (test_acq_units_plan.py), the GPU tests
@@ -8,9 +8,10 @@ from __future__ import annotations
 
 import numpy as np
 
+import acq_plan_model
+
 MAX_BINS = 28           # kMaxBins
 N_SATS = 32
-SPEC_UNIT_BYTES = 131072   # one unit-millisecond of spectra: 8 branches x 2048 complex64 (kSpecUnitMs * sizeof(cf))
 
 
 def level_bins(center: float, spread: float, bins_per_spread: float = 10.0) -> list[int]:
@@ -65,11 +66,9 @@ def _check_partition(cells, units, sh_cell, sh_unit, order):
 
 
 def max_units_for(n_streams: int, n_sats: int, n_ms: int) -> int:
-    """Units the spectra buffer of a search of n_streams x n_sats states over n_ms milliseconds has room for (acquire_search):
-    3 * 28 = 84 per stream, 1 GiB at most, never more than there are cells."""
-    unit_bytes = n_ms * SPEC_UNIT_BYTES
-    n_cells = n_streams * n_sats * MAX_BINS
-    return min(n_cells, min(2 ** 30, n_streams * 84 * unit_bytes) // unit_bytes)
+    """Units the spectra buffer of a search of n_streams x n_sats states over n_ms milliseconds has room for (acq_plan.hpp, restated
+    in acq_plan_model.py): 3 * 28 = 84 per stream, 1 GiB at most, never more than there are cells."""
+    return acq_plan_model.acq_plan(8, 8184, n_streams, n_sats, n_ms)["max_units"]
 
 
 def expected_counts(levels, max_units: int, n_sats: int = N_SATS):

@@ -693,6 +693,33 @@ static void track_plans() {
     Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
 }
 
+// --------------------------------------------------------------------------------------------------------- acq-plan
+// shapes.i64 rows: k, n, n_streams, n_sats, n_ms, switches (bit 0 no_pipe, 1 no_acq_shared_fwd, 2 no_acq_split, 3 is_helper), acq_lanes, single_level,
+// then the bits of four float64: spread0, acq_initial_spread_hz, acq_min_spread_hz, acq_bins_per_spread.  plans.i64 rows: AcqPlan's members in
+// their order (bins_per_spread as its bits).
+static void acq_plans() {
+    const std::vector<int64_t> shapes = read_array<int64_t>("shapes.i64");
+    REQUIRE(shapes.size() % 12 == 0);
+    std::vector<int64_t> plans;
+    plans.reserve(shapes.size() / 12 * (20 + 2 * kMaxAcqLanes));
+    for (size_t r = 0; r * 12 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 12];
+        double real[4];
+        std::memcpy(real, s + 8, sizeof(real));
+        const AcqPlan pl = acq_plan(AcqShape{(int)s[0], (int)s[1], (int)s[2], (int)s[3], (int)s[4]}, AcqSearch{0.0, real[0], s[7] != 0}, AcqLevels{real[1], real[2], real[3]},
+                                    AcqSwitches{(s[5] & 1) != 0, (s[5] & 2) != 0, (s[5] & 4) != 0, (s[5] & 8) != 0, (int)s[6]});
+        int64_t bins_bits;
+        std::memcpy(&bins_bits, &pl.bins_per_spread, sizeof(bins_bits));
+        for (int64_t v : {(int64_t)pl.fits, (int64_t)pl.n_states, (int64_t)pl.n_cells, (int64_t)pl.n_levels, (int64_t)pl.shared_levels, bins_bits, (int64_t)pl.max_units,
+                          (int64_t)pl.states, (int64_t)pl.cells, (int64_t)pl.out, (int64_t)pl.refined, (int64_t)pl.partial64, (int64_t)pl.profiles, (int64_t)pl.spectra,
+                          (int64_t)pl.tpb, (int64_t)pl.nblk, (int64_t)pl.refine_x, (int64_t)pl.refine_y, (int64_t)pl.exact_z, (int64_t)pl.lanes})
+            plans.push_back(v);
+        for (int v : pl.lane_first) plans.push_back(v);
+        for (int v : pl.lane_streams) plans.push_back(v);
+    }
+    Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+}
+
 // --------------------------------------------------------------------------------------------------------- dev-mem
 // The owners of dev_mem.hpp on a host without a device (every allocation fails), the scratch layouts, the table of debug switches on a
 // context that lives on the stack.  No kernel is launched and no context is made through gyp_create.
@@ -792,6 +819,24 @@ static void dev_mem() {
         REQUIRE(gyp_debug_get(&ctx, "last_grid_path", &got) == GYP_OK && got == 0.0 && gyp_debug_get(&ctx, "last_exact_path", &got) == GYP_OK &&
                 gyp_debug_get(&ctx, "no_such_switch", &got) == GYP_E_BAD_ARG);
         REQUIRE(gyp_debug_set(&ctx, "last_track_flow", 1.0) == GYP_E_BAD_ARG && gyp_debug_get(&ctx, "last_track_flow", &got) == GYP_OK && got == 0.0);
+        for (const char* name : {"last_acq_lanes", "last_acq_levels", "last_acq_shared_levels"})
+            REQUIRE(gyp_debug_set(&ctx, name, 1.0) == GYP_E_BAD_ARG && gyp_debug_get(&ctx, name, &got) == GYP_OK && got == 0.0);
+    }
+    {   // a search that does not fit is refused before anything is planned into the context, reserved or launched (gyp_create's parameters and a
+        // stream format by hand: no tables)
+        gyp_ctx ctx;
+        gyp_params_default(&ctx.params);
+        ctx.fs = 8184000; ctx.n = 8184; ctx.k = 8;
+        float iq = 0.0f;
+        gyp_acq_result res{};
+        const std::vector<int32_t> sats(33, 1);
+        auto too_large = [&](int rc) { return rc == GYP_E_BAD_ARG && std::string(gyp_last_error(&ctx)).find("search too large") != std::string::npos && ctx.last_acq_plan.lanes == 0; };
+        REQUIRE(too_large(gyp_acquire_dev(&ctx, &iq, 1, 8184, 65536, sats.data(), 1, &res)));
+        REQUIRE(too_large(gyp_search_level_dev(&ctx, &iq, 1, 8184, 65536, sats.data(), 1, 0.0, 7000.0, &res)));
+        REQUIRE(too_large(gyp_acquire_dev(&ctx, &iq, 2739138, 8184, 10, sats.data(), 28, &res)));
+        REQUIRE(too_large(gyp_search_level_dev(&ctx, &iq, 2739138, 8184, 10, sats.data(), 28, 0.0, 7000.0, &res)));
+        REQUIRE(gyp_acquire_dev(&ctx, &iq, 1, 8184, 0, sats.data(), 1, &res) == GYP_E_BAD_ARG && std::string(gyp_last_error(&ctx)) == "gyp_acquire_dev / gyp_search_level_dev: bad argument");
+        REQUIRE(gyp_acquire_dev(&ctx, &iq, 8, 8184, 10, sats.data(), 33, &res) == GYP_E_BAD_ARG && ctx.helper[0] == nullptr);   // refused before a helper is made
     }
 }
 
@@ -815,7 +860,7 @@ int main(int argc, char** argv) {
     const std::pair<const char*, void (*)()> table[] = {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
-        {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"dev-mem", drv::dev_mem},
+        {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -695,6 +695,82 @@ def test_track_plan(programs, tmp_path, which):
         plan = dict(zip(model.FIELDS, row.tolist()))
         first = [plan[f"start{i}"] for i in range(plan["n"] + 1)]
         plan["starts"], plan["lengths"] = first[:-1], np.diff(first).tolist()
+        for field, value in expected.items():
+            assert plan[field] == value, (shape, field, plan[field])
+
+
+# ------------------------------------------------------------------------------------------------------------ acq-plan
+A_NO_PIPE, A_NO_SHARED_FWD, A_NO_SPLIT, A_IS_HELPER = 1, 2, 4, 8      # the switches column of the acq-plan scenario's shapes.i64
+# Read off the host code as it stood before acq_plan.hpp, by hand (acquire_search's level loop, `can_share`, the room formula and
+# `spread * 4 >= acq_initial_spread_hz`; gyp_acquire_dev's `max(1, min(acq_lanes, n_streams / 2))` and `(n_streams - s0) / (lanes - i)`):
+# (k, n_streams, n_sats, n_ms, switches, acq_lanes, single_level, spread0) with the default gyp_params -> {field: value}; "parts" are the
+# parts' stream counts.  The two limits behind "fits" are new: cells are indexed in int32 (2^31 - 1 >= 28 n_streams n_sats) and
+# acq_refine_kernel's grid has n_ms rows of blocks (65535 at the most).  2 739 137 streams x 28 satellites is the largest search of 28
+# satellites that fits (2 147 483 408 cells; one stream more makes 2 147 484 192), so the round 2 739 000 x 28 (2 147 376 000) still does.
+ACQ_LITERALS = [
+    ((8, 1, 32, 10, 0, 2, 0, 7000.0), {"fits": 1, "n_levels": 10, "shared_levels": 3, "max_units": 84, "lanes": 1, "parts": [1]}),
+    ((8, 13, 32, 10, 0, 2, 0, 7000.0), {"max_units": 819, "lanes": 2, "parts": [6, 7], "n_levels": 10, "shared_levels": 3}),      # the 1 GiB cap
+    ((8, 13, 32, 10, 0, 4, 0, 7000.0), {"lanes": 4, "parts": [3, 3, 3, 4]}),
+    ((8, 5, 32, 10, 0, 4, 0, 7000.0), {"lanes": 2, "parts": [2, 3]}),
+    ((8, 4, 32, 40, 0, 2, 0, 7000.0), {"max_units": 204, "lanes": 2, "parts": [2, 2]}),
+    ((8, 4, 32, 40, A_NO_SPLIT, 2, 0, 7000.0), {"max_units": 204, "lanes": 1, "parts": [4]}),
+    ((8, 4, 32, 40, A_IS_HELPER, 2, 0, 7000.0), {"lanes": 1, "parts": [4]}),
+    ((8, 1, 32, 8192, 0, 2, 0, 7000.0), {"max_units": 1, "shared_levels": 3}),
+    ((8, 1, 32, 8193, 0, 2, 0, 7000.0), {"max_units": 0, "shared_levels": 0, "n_levels": 10, "spectra": 0}),
+    ((4, 1, 32, 10, 0, 2, 0, 7000.0), {"max_units": 0, "shared_levels": 0, "n_levels": 10}),
+    ((8, 1, 32, 10, A_NO_PIPE, 2, 0, 7000.0), {"max_units": 0, "shared_levels": 0, "n_levels": 10}),
+    ((8, 1, 32, 10, A_NO_SHARED_FWD, 2, 0, 7000.0), {"max_units": 0, "shared_levels": 0}),
+    ((8, 1, 32, 10, 0, 2, 1, 1750.0), {"n_levels": 1, "shared_levels": 1, "lanes": 1}),
+    ((8, 1, 32, 10, 0, 2, 1, 1749.0), {"n_levels": 1, "shared_levels": 0}),
+    ((8, 1, 32, 65535, 0, 2, 0, 7000.0), {"fits": 1, "refine_y": 65535}),
+    ((8, 1, 32, 65536, 0, 2, 0, 7000.0), {"fits": 0, "n_levels": 0, "lanes": 0}),
+    ((8, 2_739_000, 28, 10, 0, 2, 0, 7000.0), {"fits": 1, "n_cells": 2_147_376_000}),
+    ((8, 2_739_137, 28, 10, 0, 2, 0, 7000.0), {"fits": 1, "n_cells": 2_147_483_408}),
+    ((8, 2_739_138, 28, 10, 0, 2, 0, 7000.0), {"fits": 0, "n_cells": 0}),
+    ((8, 2_739_000, 32, 10, 0, 2, 0, 7000.0), {"fits": 0}),
+]
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_acq_plan(programs, tmp_path, which):
+    """acq_plan (csrc/acq_plan.hpp) against tests/acq_plan_model.py on every combination of the axes below and on the searches whose
+    plans are written out above."""
+    import acq_plan_model as model
+
+    d = indir(tmp_path)
+    # k, n_streams, n_sats, n_ms, switches, acq_lanes, single_level, spread0, min_spread
+    axes = [(1, 2, 4, 8, 16), (1, 2, 3, 4, 5, 13, 64), (1, 2, 31, 32), (1, 2, 10, 40, 8192, 8193, 65535, 65536), range(16), (1, 2, 3, 4), (0, 1),
+            (7000.0, 1750.0, 1749.0, 10.0), (10.0, 437.5)]
+    sweep = np.stack([g.ravel() for g in np.meshgrid(*[np.array(a, dtype=np.float64) for a in axes], indexing="ij")], axis=1)
+    assert len(sweep) == 5 * 7 * 4 * 8 * 16 * 4 * 2 * 4 * 2
+    literal = np.array([shape + (10.0,) for shape, _ in ACQ_LITERALS], dtype=np.float64)
+    rows = np.concatenate([sweep, literal])
+    k, streams, sats, n_ms, sw, lanes, single = rows[:, :7].astype(np.int64).T
+    spread0, min_spread = rows[:, 7].copy(), rows[:, 8].copy()
+    initial, bins = np.full(len(rows), 7000.0), np.full(len(rows), 10.0)
+    shapes = np.stack([k, 1023 * k, streams, sats, n_ms, sw, lanes, single, *(x.view(np.int64) for x in (spread0, initial, min_spread, bins))], axis=1)
+    shapes.astype("<i8").tofile(d / "shapes.i64")
+    out = run(programs, which, "acq-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(rows), len(model.FIELDS))
+    (d / "shapes.i64").unlink()                          # (a few hundred megabytes between them)
+    (out / "plans.i64").unlink()
+    want = model.acq_plans(k, 1023 * k, streams, sats, n_ms, spread0, single, initial, min_spread, bins, sw & A_NO_PIPE, sw & A_NO_SHARED_FWD,
+                           sw & A_NO_SPLIT, sw & A_IS_HELPER, lanes)
+    for col, field in enumerate(model.FIELDS):
+        bad = np.flatnonzero(got[:, col] != want[:, col])
+        assert len(bad) == 0, (field, len(bad), rows[bad[0]].tolist(), int(got[bad[0], col]), int(want[bad[0], col]))
+    plans = {f: got[:, c] for c, f in enumerate(model.FIELDS)}
+    fits = plans["fits"] == 1
+    assert np.array_equal(fits[:len(sweep)], n_ms[:len(sweep)] <= 65535) and (got[~fits] == 0).all()      # (in the sweep the milliseconds alone decide)
+    # levels: 7000 Hz down to 10 Hz 10 and to 437.5 Hz 5; 1750 and 1749 Hz down to 10 Hz 8, to 437.5 Hz 3 and 2 (437.25 is below); 10 Hz 1 and 0
+    assert set(np.unique(plans["n_levels"][fits])) == {0, 1, 2, 3, 5, 8, 10} and set(np.unique(plans["shared_levels"])) == {0, 1, 3}
+    assert set(np.unique(plans["lanes"][fits])) == {1, 2, 3, 4} and (plans["shared_levels"] <= plans["n_levels"]).all()
+    total = sum(plans[f"lane_streams{i}"] for i in range(model.MAX_LANES))
+    assert np.array_equal(total[fits], streams[fits]) and (plans["lane_streams0"][fits] >= np.minimum(streams[fits], 2)).all()
+    assert np.array_equal(plans["shared_levels"] > 0, fits & (plans["max_units"] > 0) & (spread0 * 4.0 >= 7000.0) & ((single == 1) | (spread0 >= min_spread)))
+    for row, (shape, expected) in zip(got[len(sweep):], ACQ_LITERALS):
+        plan = dict(zip(model.FIELDS, row.tolist()))
+        plan["parts"] = [plan[f"lane_streams{i}"] for i in range(plan["lanes"])]
         for field, value in expected.items():
             assert plan[field] == value, (shape, field, plan[field])
 
