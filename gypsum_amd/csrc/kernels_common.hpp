@@ -179,7 +179,7 @@ struct RedScratch {
     // speculative tracker under the round protocol (SpecCtl, kernels_track_block.hpp): what this channel does in this launch
     int32_t ctl_sub, ctl_restore, ctl_nforce, ctl_pad;
     int32_t force_ms[8];   // milliseconds of the block that take the transform path whatever the window says (a verification failed there)
-    // throughput kernel (GYP_EXPERIMENT_LEAVE_PF, kernels_track_block.hpp): the ring entries leaving the lock windows in the NEXT
+    // throughput kernel (the leave-prefetch of track_block_kernel, kernels_track_block.hpp): the ring entries leaving the lock windows in the NEXT
     // millisecond's update, fetched by an idle wavefront during this one's
     // Double-buffered by the parity of the millisecond: in millisecond ms wavefront 0 reads slot ms & 1 while the fetching
     // wavefront fills slot (ms + 1) & 1 in the same barrier interval -- the two never touch the same words.

@@ -3,16 +3,6 @@
 #pragma once
 #include "kernels_track_step.hpp"
 
-#ifndef GYP_EXPERIMENT_LEAVE_PF
-// 1 (default since r05; 0 for an A/B build): the throughput kernel's ring entries that leave the lock windows in the NEXT millisecond's
-// update are fetched during this one's by an otherwise idle wavefront and handed over through LDS, so that the serial section (wavefront
-// 0's Costas / lock-detector update, which the other seven wavefronts wait for) no longer starts with three global-memory latencies:
-// track_block_kernel<8, false, 0> 29.51 -> 29.30 ms per 500-ms launch (rocprofv3, 82 launches each; profiles/r05_experiments.txt item 5)
-#define GYP_EXPERIMENT_LEAVE_PF 1
-#endif
-#ifndef GYP_EXPERIMENT_SKIP_UPDATE
-#define GYP_EXPERIMENT_SKIP_UPDATE 0   // 1 (development builds only): the throughput kernel without its Costas / lock-detector update -- how much of the kernel's time the serial update costs
-#endif
 namespace gyp {
 
 // ---------------------------------------------------------------------------------------------------------
@@ -881,6 +871,78 @@ __device__ __attribute__((noinline)) EplResult spec_transform_path(const Smem& s
     }
 }
 
+// ---- track_block_kernel's prologue and epilogue, piece by piece ------------------------------------------------
+// (Every helper takes Smem, SpecLds and TrackBlockParams by const reference and reads sm.red->... itself: an LDS pointer
+// handed over as a plain pointer parameter loses its address space, and the compiler answers with null checks and 64-bit
+// flat address arithmetic -- 100-130 instructions in every MODE 2 instantiation.)
+
+// A channel's state to or from a checkpoint, by the whole workgroup.
+template <int THREADS>
+__device__ __forceinline__ void chan_state_copy(ChanState* dst_, const ChanState* src_) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(src_);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(dst_);
+    for (int i = threadIdx.x; i < (int)(sizeof(ChanState) / 4); i += THREADS) dst[i] = src[i];
+    __threadfence();
+    __syncthreads();
+}
+// LDS of the speculative form behind the throughput form's: tw2048 where it fits, the SpecLds tables, and tw1024 where
+// carve_smem keeps none in LDS.
+template <int K>
+__device__ __forceinline__ SpecLds spec_carve(char* smem_raw, const TrackBlockParams& p, Smem& sm) {
+    SpecLds sl{};
+    if (kSpecTw2048InLds<K>) {
+        cf* tw2048 = reinterpret_cast<cf*>(smem_raw + lds_bytes<K>());
+        for (int i = threadIdx.x; i < 1024; i += kSpecThreads) tw2048[i] = p.tw_tables[1024 + i];
+        sm.tw2048 = tw2048;
+        sm.ones = nullptr;
+    }
+    char* b = smem_raw + lds_bytes<K>() + (kSpecTw2048InLds<K> ? kTablesBytes : 0);
+    sl.chipf = reinterpret_cast<float*>(b); b += kSpecChipBytes;
+    sl.ein_part = reinterpret_cast<float*>(b); b += kSpecEinBytes;
+    sl.fin = reinterpret_cast<double*>(b); b += kSpecFinBytes;
+    sl.win = reinterpret_cast<cf*>(b); b += kSpecWinBytes;
+    if constexpr (!kTw1024InLds<K>) {
+        cf* tw1024 = reinterpret_cast<cf*>(b);
+        for (int i = threadIdx.x; i < 1024; i += kSpecThreads) tw1024[i] = p.tw_tables[i];
+        sm.tw1024 = tw1024;
+    }
+    return sl;
+}
+// Loop state lives in LDS between milliseconds (RedScratch::dstate / istate / steps / loop) and is re-read where
+// it is needed, so that no wavefront carries it in registers across the transforms.  Thread 0, before the first millisecond.
+template <int K, bool SPEC>
+__device__ __forceinline__ void loop_state_load(const TrackBlockParams& p, const ChanState* st, const Smem& sm, int ms_first, int ms_last) {
+    constexpr int N = K * kChips;
+    sm.red->kc.lp = p.lp; sm.red->kc.inv_fs = p.inv_fs;
+    LoopState ls;
+    ls.dll_phase = st->dll_phase; ls.last_watchdog = st->last_watchdog_time; ls.n_steps = st->n_steps; ls.sums = st->sums;
+    ls.pos_e = (int)(ls.n_steps % kLockWindow); ls.pos_p = (int)(ls.n_steps % kPeakHistory);
+    ls.pos_refresh = (int)(ls.n_steps % kLockRefresh); ls.pad = 0;
+    sm.red->loop = ls;
+    sm.red->dstate[0] = st->doppler; sm.red->dstate[1] = st->carrier_phase;
+    sm.red->istate[0] = st->code_phase; sm.red->istate[1] = st->lost;
+    sm.red->istate[2] = st->win_centre1 > 0 ? st->win_centre1 - 1 : mod_n(st->code_phase, N);   // speculative window centre
+    sm.red->steps = tracking_steps<K>(st->doppler * p.inv_fs);   // the same expression as after an update: a block gives
+                                                                    // the same records however it is cut into launches
+    sm.red->cc[0].nf = st->doppler; sm.red->cc[0].nphi = st->carrier_phase;
+    sm.red->cc[0].rot1 = sm.red->steps.rot1;
+    sm.red->cc[0].pad = (double)carrier_amp<K>(sm.red->steps.rot1);
+    sm.red->cc[0].step = carrier_from_cycles_fast(st->doppler * p.inv_fs * (double)(K * kSpecThreads));
+    sm.red->cand_sel = 0; sm.red->rec_sel = 0;
+    sm.red->defer = 0;
+    if (SPEC && ms_first < ms_last) sm.red->t0_next = p.start_time[ms_first];
+}
+// ... and back into the channel's state, by thread 0 behind the last millisecond.
+template <bool SPEC>
+__device__ __forceinline__ void loop_state_store(ChanState* st, const Smem& sm) {
+    st->doppler = SPEC ? sm.red->cc[sm.red->cand_sel].nf : sm.red->dstate[0];
+    st->carrier_phase = SPEC ? sm.red->cc[sm.red->cand_sel].nphi : sm.red->dstate[1];
+    st->code_phase = sm.red->istate[0]; st->lost = sm.red->istate[1];
+    st->win_centre1 = SPEC ? sm.red->istate[2] + 1 : 0;
+    const LoopState ls = sm.red->loop;
+    st->dll_phase = ls.dll_phase; st->n_steps = ls.n_steps; st->last_watchdog_time = ls.last_watchdog;
+    st->sums = ls.sums;
+}
 // MODE 0: throughput form (several workgroups per CU).  MODE 2: the latency form for at most one workgroup per CU (the
 // next millisecond's samples requested a phase early, both twiddle tables in LDS) with speculation: the millisecond's
 // prompt correlation is evaluated only at the 8 lags around the previous peak lag, directly from the staged rows; if the
@@ -890,9 +952,9 @@ __device__ __attribute__((noinline)) EplResult spec_transform_path(const Smem& s
 // pairs in parallel afterwards.  Otherwise the millisecond takes the transform path right here, from the same rows.
 template <int K, bool PROF, int MODE = 0>
 __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 : Geom<K>::kMinWavesPerSimd) void track_block_kernel(TrackBlockParams p) {
-    static_assert(MODE == 0 || MODE == 2, "r01's non-speculative latency variant (MODE 1) is gone: superseded by MODE 2");
-    constexpr bool LAT = MODE == 2, SPEC = MODE == 2;
-    static_assert(!LAT || kSpecRate<K>, "the speculative form exists for K = 2, 8 and 16");
+    static_assert(MODE == 0 || MODE == 2, "MODE == 0 || MODE == 2");
+    constexpr bool SPEC = MODE == 2;
+    static_assert(!SPEC || kSpecRate<K>, "the speculative form exists for K = 2, 8 and 16");
     constexpr int kThreadsHere = SPEC ? kSpecThreads : Geom<K>::kThreads;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int N = K * kChips;
@@ -915,24 +977,7 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
     }
     Smem sm = carve_smem<K>(smem_raw, p.tw_tables);
     SpecLds sl{};
-    if (LAT && kSpecTw2048InLds<K>) {
-        cf* tw2048 = reinterpret_cast<cf*>(smem_raw + lds_bytes<K>());
-        for (int i = threadIdx.x; i < 1024; i += kThreadsHere) tw2048[i] = p.tw_tables[1024 + i];
-        sm.tw2048 = tw2048;
-        sm.ones = nullptr;
-    }
-    if (SPEC) {
-        char* b = smem_raw + lds_bytes<K>() + (kSpecTw2048InLds<K> ? kTablesBytes : 0);
-        sl.chipf = reinterpret_cast<float*>(b); b += kSpecChipBytes;
-        sl.ein_part = reinterpret_cast<float*>(b); b += kSpecEinBytes;
-        sl.fin = reinterpret_cast<double*>(b); b += kSpecFinBytes;
-        sl.win = reinterpret_cast<cf*>(b); b += kSpecWinBytes;
-        if constexpr (!kTw1024InLds<K>) {
-            cf* tw1024 = reinterpret_cast<cf*>(b);
-            for (int i = threadIdx.x; i < 1024; i += kThreadsHere) tw1024[i] = p.tw_tables[i];
-            sm.tw1024 = tw1024;
-        }
-    }
+    if constexpr (SPEC) sl = spec_carve<K>(smem_raw, p, sm);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     if ((int)blockIdx.x >= p.n_chan) return;
@@ -952,11 +997,7 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
             ms_last = p.sub.end(sub, p.n_ms);
             // the sub-block's checkpoint: taken now, or -- a verification failed in here two rounds ago -- gone back to
             ChanState* ck = p.ckpt + (size_t)sub * p.n_chan + ch;
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(restore ? ck : st);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(restore ? st : ck);
-            for (int i = threadIdx.x; i < (int)(sizeof(ChanState) / 4); i += kThreadsHere) dst[i] = src[i];
-            __threadfence();
-            __syncthreads();
+            chan_state_copy<kThreadsHere>(restore ? st : ck, restore ? ck : st);
             if (restore && sub > 0 && p.exact_hist && threadIdx.x == 0) {   // (the checkpoint carries the provisional code loop)
                 const DllExact x = p.exact_hist[(size_t)sub * p.n_chan + ch];
                 st->dll_phase = x.dll; st->code_phase = x.code_phase;
@@ -968,11 +1009,7 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
     if (p.restore_from) {   // re-run of a channel whose speculation failed verification: back to the checkpoint before the failure
         const int j = p.from_sub ? min(p.from_sub[ch], p.sub.sub_of(p.n_ms - 1)) : 0;
         ms_first = p.from_sub ? p.sub.begin(j) : p.ms_begin;
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(p.restore_from + (size_t)j * p.n_chan + ch);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(st);
-        for (int i = threadIdx.x; i < (int)(sizeof(ChanState) / 4); i += kThreadsHere) dst[i] = src[i];
-        __threadfence();
-        __syncthreads();
+        chan_state_copy<kThreadsHere>(st, p.restore_from + (size_t)j * p.n_chan + ch);
         if (j > 0 && p.exact_hist && threadIdx.x == 0) {   // (the checkpoint carries the serial kernel's provisional code loop)
             const DllExact x = p.exact_hist[(size_t)j * p.n_chan + ch];
             st->dll_phase = x.dll; st->code_phase = x.code_phase;
@@ -988,28 +1025,7 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
         const float* src = p.codes.chipf + sat_index * 2048;
         for (int i = threadIdx.x; i < 2048; i += kThreadsHere) sl.chipf[i] = src[i];
     }
-    // Loop state lives in LDS between milliseconds (RedScratch::dstate / istate / steps / loop) and is re-read where
-    // it is needed, so that no wavefront carries it in registers across the transforms.
-    if (threadIdx.x == 0) {
-        sm.red->kc.lp = p.lp; sm.red->kc.inv_fs = p.inv_fs;
-        LoopState ls;
-        ls.dll_phase = st->dll_phase; ls.last_watchdog = st->last_watchdog_time; ls.n_steps = st->n_steps; ls.sums = st->sums;
-        ls.pos_e = (int)(ls.n_steps % kLockWindow); ls.pos_p = (int)(ls.n_steps % kPeakHistory);
-        ls.pos_refresh = (int)(ls.n_steps % kLockRefresh); ls.pad = 0;
-        sm.red->loop = ls;
-        sm.red->dstate[0] = st->doppler; sm.red->dstate[1] = st->carrier_phase;
-        sm.red->istate[0] = st->code_phase; sm.red->istate[1] = st->lost;
-        sm.red->istate[2] = st->win_centre1 > 0 ? st->win_centre1 - 1 : mod_n(st->code_phase, N);   // speculative window centre
-        sm.red->steps = tracking_steps<K>(st->doppler * p.inv_fs);   // the same expression as after an update: a block gives
-                                                                        // the same records however it is cut into launches
-        sm.red->cc[0].nf = st->doppler; sm.red->cc[0].nphi = st->carrier_phase;
-        sm.red->cc[0].rot1 = sm.red->steps.rot1;
-        sm.red->cc[0].pad = (double)carrier_amp<K>(sm.red->steps.rot1);
-        sm.red->cc[0].step = carrier_from_cycles_fast(st->doppler * p.inv_fs * (double)(K * kSpecThreads));
-        sm.red->cand_sel = 0; sm.red->rec_sel = 0;
-        sm.red->defer = 0;
-        if (SPEC && ms_first < ms_last) sm.red->t0_next = p.start_time[ms_first];
-    }
+    if (threadIdx.x == 0) loop_state_load<K, SPEC>(p, st, sm, ms_first, ms_last);
     __syncthreads();
     if (p.exact0 && threadIdx.x == 0) {
         DllExact x; x.dll = st->dll_phase; x.code_phase = st->code_phase; x.repairs = 0;
@@ -1020,30 +1036,19 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
     long long t_last = 0;
     // speculative mode: tp[6 + i] accumulates the cycles between stamp i-1 and stamp i of workgroup 0's thread 0
 #define GYP_STAMP(i) do { if (prof) { const long long now_ = (long long)__builtin_readcyclecounter(); tp[6 + (i)] += now_ - t_last; t_last = now_; } } while (0)
-    OwnSamples<LAT ? K : 1, LAT ? kSpecThreads : 64> smp;   // LAT: the next millisecond's raw samples
-    // Throughput form, halo-free staging: the next millisecond's raw samples are requested while the loop update runs -- by
-    // wavefronts 1.. before they wait at the millisecond's last barrier, by wavefront 0 behind its update (so the 2 x K sample
-    // registers are never live across the update's own register needs) -- instead of at the top of the millisecond with every
-    // wavefront waiting for them.
-    // (Both forms measured and switched off: at the 128-register budget the allocator parks the requested samples in scratch
-    // memory between the request and the wipe-off -- 78 ms per launch against 58 -- and a TOUCH of one dword per 64-byte line of
-    // the next millisecond, to pull the lines into L2 / L1 under the update, costs more in extra address traffic than the
-    // latency it hides -- 60.1 against 58.4.  With two workgroups per CU the other workgroup already covers the wait.)
-    constexpr bool PRE = false;
-    constexpr bool TOUCH = false;
-    float touch = 0.f;
-    typename PreSamples<K>::type pre;
-    if constexpr (PRE) {
-        if (ms_first < ms_last && !sm.red->istate[1]) stage_fetch_own<K>(stream + (int64_t)ms_first * N, pre, launder(threadIdx.x));
-    }
+    OwnSamples<SPEC ? K : 1, SPEC ? kSpecThreads : 64> smp;   // SPEC: the next millisecond's raw samples
+    // Throughput form, the next millisecond's samples asked for during the loop update: both ways measured, both lost.
+    // PRE (requested into registers, HAVE_PRE): parked in scratch memory at the 128-register budget, 78 ms per launch against 58.
+    // TOUCH (one dword per 64-byte line read instead): 60.1 ms against 58.4; the CU's other workgroup already covers the wait.
+    typename PreSamples<K>::type pre;   // (never filled: track_ms / track_ms_publish take it, HAVE_PRE = false)
     // K = 16: a thread's two chips are 32 samples = 64 registers.  Held from one millisecond's staging to the next they push the
     // kernel past its 256 registers, and a spill is worse than slow here: its reload queues BEHIND the sample requests (vector
     // memory returns in order).  So only the first chip's samples are requested a phase early; the second chip's are requested
     // at the top of the staging and arrive under the first chip's wipe-off (not quite: ~1500 cycles of their latency show at the
     // staging barrier.  Measured and not kept: requesting them at the end of the loop update instead (20 spills, 7.97 us per ms-step
     // against 7.08); touching one dword per line of them a phase early so that they wait in L2 (7.16-7.48).
-    constexpr bool SPLIT = LAT && K > 8;
-    if constexpr (LAT) {
+    constexpr bool SPLIT = SPEC && K > 8;
+    if constexpr (SPEC) {
         if (ms_first < ms_last) {
             if constexpr (SPLIT) stage_fetch_chip<K, kSpecThreads>(stream + (int64_t)ms_first * N, 0, smp.w[0], launder(threadIdx.x));
             else stage_fetch_own<K>(stream + (int64_t)ms_first * N, smp, launder(threadIdx.x));
@@ -1052,16 +1057,13 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
     WinCache wcache;
     wcache.q = -1; wcache.qe = -1; wcache.ql = -1;
     bool have_prev = false;   // speculative mode: the previous millisecond's record (and possibly its histories) await completion
-    const int64_t n_first = GYP_EXPERIMENT_LEAVE_PF ? launder_lds(sm.red)->loop.n_steps : 0;   // (uniform: steps taken before this launch)
-    if (GYP_EXPERIMENT_LEAVE_PF && threadIdx.x == 0) { sm.red->leave_for_ms[0] = -1; sm.red->leave_for_ms[1] = -1; }
+    const int64_t n_first = launder_lds(sm.red)->loop.n_steps;   // (uniform: steps taken before this launch)
+    if (threadIdx.x == 0) { sm.red->leave_for_ms[0] = -1; sm.red->leave_for_ms[1] = -1; }
     for (int ms = ms_first; ms < ms_last; ++ms) {   // ([ms_first, ms_last) == [p.ms_begin, p.ms_end) except in a re-run from a later checkpoint and under the round protocol)
         gyp_track_rec* rec = p.rec_out ? p.rec_out + (int64_t)ch * p.n_ms + ms : nullptr;
         // (speculative mode: a load issued here would be waited for -- a few hundred cycles -- by the first carrier of the
         // wipe-off; wavefront 5 fetched the value into LDS during the previous millisecond's loop updates)
         const double t0 = SPEC ? launder_lds(sm.red)->t0_next : p.start_time[launder(ms)];
-        if constexpr (TOUCH) {   // (never true: it only keeps the touched values -- and the wait for them -- in the program)
-            if (touch == 1.2345e38f && p.dbg) p.dbg[0] = touch;
-        }
         if (!SPEC && have_prev) {   // the previous millisecond's record (complete since the barrier that ended it)
             if (wave == (Geom<K>::W >= 2 ? 1 : 0)) {
                 rec_flush(sm.red, rec ? rec - 1 : nullptr, lane);
@@ -1234,12 +1236,12 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
                 m.strength_pending = false;
                 m.path_info = 0;
                 if constexpr (Geom<K>::R > 1) {
-                    const EplResult r = track_ms<K, false, PRE>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, nullptr, pre);
+                    const EplResult r = track_ms<K, false, false>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, nullptr, pre);
                     if (prof) t_b = (long long)__builtin_readcyclecounter();
                     m.peak = r.peak; m.peak_mag = r.best.v; m.key = r.best.key; m.sum = r.sum; m.n_max = r.n_max;
                     m.disc = prov_disc(r.early, r.late, p.prov_bias);
                 } else {
-                    track_ms_publish<K, PRE>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, pre);
+                    track_ms_publish<K, false>(block, u0, du, cs, code_phase, mod_n(code_phase, N), sm, rep, prof_row, pre);
                     __syncthreads();   // candidates and taps published
                     if (prof) t_b = (long long)__builtin_readcyclecounter();
                     // (the merged profile is finished in the update phase, by the wavefronts that use it: measure_merged)
@@ -1276,12 +1278,12 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
             constexpr bool kSingle = Geom<K>::R == 1;
             constexpr int kRecWave = kW >= 3 ? 2 : 0, kDllWave = kW >= 2 ? 1 : 0;
             const bool narrow = kSingle && !p.finish_all;   // (uniform)
-            if (wave == 0 && !GYP_EXPERIMENT_SKIP_UPDATE) {
+            if (wave == 0) {
                 if constexpr (kSingle) {
                     if (narrow) measure_merged<kW>(red, lane, kRecWave == 0, m); else measure_all<K>(red, p.prov_bias, m);
                 }
                 const long long u0_ = prof ? (long long)__builtin_readcyclecounter() : 0;
-                if (GYP_EXPERIMENT_LEAVE_PF && kW >= 4 && red->leave_for_ms[ms & 1] == ms) {
+                if (kW >= 4 && red->leave_for_ms[ms & 1] == ms) {
                     const double* ln = red->leave_next[ms & 1];    // (filled during millisecond ms - 1; this millisecond's fetch goes to the other slot)
                     leave[0] = ln[0]; leave[1] = ln[1]; leave[2] = ln[2];
                 } else {
@@ -1295,12 +1297,12 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
             if (wave == kDllWave) {
                 if constexpr (kSingle) {
                     if (narrow) m.disc = prov_disc(make_float2(red->taps[0], red->taps[1]), make_float2(red->taps[2], red->taps[3]), p.prov_bias);
-                    else if (kDllWave != 0 || GYP_EXPERIMENT_SKIP_UPDATE) measure_all<K>(red, p.prov_bias, m);
+                    else if (kDllWave != 0) measure_all<K>(red, p.prov_bias, m);
                 }
                 dll_update(red, m.disc, lane, red->kc.lp);
             }
             if (wave == kRecWave) {
-                if constexpr (kSingle && (kRecWave != 0 || GYP_EXPERIMENT_SKIP_UPDATE)) {
+                if constexpr (kSingle && kRecWave != 0) {
                     if (narrow) measure_merged<kW>(red, lane, true, m); else measure_all<K>(red, p.prov_bias, m);
                 }
                 spec_record_fields<K>(red, m, lane);
@@ -1311,7 +1313,12 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
                     asm volatile("" ::"v"(m.peak.x), "v"(m.peak.y), "v"(m.peak_mag), "v"(m.key), "v"(m.sum), "v"(m.n_max), "v"(m.disc));
                 }
             }
-            if (GYP_EXPERIMENT_LEAVE_PF && kW >= 4 && wave == kLeaveWave && ms + 1 < ms_last) {
+            if (kW >= 4 && wave == kLeaveWave && ms + 1 < ms_last) {
+                // The ring entries that leave the lock windows in the NEXT millisecond's update are fetched during this one's by an
+                // otherwise idle wavefront and handed over through LDS, so that the serial section (wavefront 0's Costas / lock-detector
+                // update, which the other seven wavefronts wait for) does not start with three global-memory latencies:
+                // track_block_kernel<8, false, 0> 29.51 -> 29.30 ms per 500-ms launch (rocprofv3, 82 launches each;
+                // profiles/r05_experiments.txt item 5).
                 // what fetch_leaving will want in the next millisecond's update (positions follow from the step count: the prologue
                 // derives them the same way), asked for now: the load's latency passes under wavefront 0's update and the next
                 // millisecond's transforms instead of at the head of the serial section
@@ -1324,22 +1331,12 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
                 }
                 if (lane == 0) { double* ln = red->leave_next[(ms + 1) & 1]; ln[0] = e; ln[1] = pr_; ln[2] = pi_; red->leave_for_ms[(ms + 1) & 1] = ms + 1; }
             }
-            if constexpr (PRE) {   // (wavefront 0 gets here behind its update; a channel the watchdog has just dropped asks for samples nobody uses)
-                if (ms + 1 < ms_last) stage_fetch_own<K>(stream + (int64_t)(ms + 1) * N, pre, launder(threadIdx.x));
-            }
-            if constexpr (TOUCH) {
-                if (ms + 1 < ms_last) {
-                    const cf* nb = stream + (int64_t)(ms + 1) * N;
-                    const int t_ = launder(threadIdx.x);
-                    touch = nb[K * t_].x + nb[K * min(t_ + Geom<K>::kThreads, kChips - 1)].x;
-                }
-            }
             have_prev = true;
         }
         asm volatile("; MARK_UPDATE_END");
         long long t_d = prof ? (long long)__builtin_readcyclecounter() : 0;
         GYP_STAMP(9);
-        if constexpr (SPEC || PRE || TOUCH) lds_barrier(); else __syncthreads();   // (LDS traffic only: the sample requests / touches stay in flight)
+        if constexpr (SPEC) lds_barrier(); else __syncthreads();   // (LDS traffic only: the sample requests stay in flight)
         if (SPEC) have_prev = true;   // the record is flushed by wavefront 1 in the next window phase (or after the loop)
         if (prof) {
             const long long t_e = (long long)__builtin_readcyclecounter();
@@ -1355,15 +1352,7 @@ __global__ __launch_bounds__(MODE ? kSpecThreads : Geom<K>::kThreads, MODE ? 2 :
         gyp_track_rec* last = p.rec_out ? p.rec_out + (int64_t)ch * p.n_ms + (ms_last - 1) : nullptr;
         rec_flush(sm.red, last, lane);
     }
-    if (threadIdx.x == 0) {
-        st->doppler = SPEC ? sm.red->cc[sm.red->cand_sel].nf : sm.red->dstate[0];
-        st->carrier_phase = SPEC ? sm.red->cc[sm.red->cand_sel].nphi : sm.red->dstate[1];
-        st->code_phase = sm.red->istate[0]; st->lost = sm.red->istate[1];
-        st->win_centre1 = SPEC ? sm.red->istate[2] + 1 : 0;
-        const LoopState ls = sm.red->loop;
-        st->dll_phase = ls.dll_phase; st->n_steps = ls.n_steps; st->last_watchdog_time = ls.last_watchdog;
-        st->sums = ls.sums;
-    }
+    if (threadIdx.x == 0) loop_state_store<SPEC>(st, sm);
     if (prof) for (int i = 0; i < 16; ++i) p.prof[i] = tp[i];
 }
 

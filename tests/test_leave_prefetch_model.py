@@ -1,5 +1,5 @@
 """CPU restatement of the ring arithmetic behind r05's leave-prefetch in the throughput tracking kernel (csrc/kernels_track_block.hpp,
-GYP_EXPERIMENT_LEAVE_PF): wavefront 3 fetches, during millisecond ms, the ring entries that costas_update's fetch_leaving will want in
+the end of track_block_kernel's update phase): wavefront 3 fetches, during millisecond ms, the ring entries that costas_update's fetch_leaving will want in
 millisecond ms + 1, from positions it derives from the STEP COUNT alone (n1 = n_first + (ms - ms_first) + 1).  That is only right if the
 incrementally updated positions of the loop state (pos_e, pos_p) always equal n % 250 and n % 1000 -- the prologue derives them that way at
 every launch -- and if the entry read a millisecond early is not written in between.  Both are checked here for every launch cut."""
