@@ -176,7 +176,7 @@ struct gyp_ctx {
     int resample_tile = 4096;     // "resample_tile_samples": LDS budget of one resample_kernel tile, in input samples (32 KiB: five
                                   // workgroups per CU); same output for any value
     std::vector<std::pair<ResampleDesign, DevBuf<float>>> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps), with the owner of its d_taps
-    std::vector<std::pair<std::vector<float>, DevBuf<float>>> packed_levels;   // packed recordings: each level table met, in device memory
+    std::vector<std::pair<PackedLevels, DevBuf<float>>> packed_levels;   // packed recordings: each level table met, in device memory
     bool notch_no_lds = false;    // A/B switch: iq_notch_kernel keeps the residual in the output buffer at every rate (same bits)
     DevBuf<int64_t> tone_freqs;   // gyp_iq_tones_dev: the call's frequencies (f mod fs) in device memory
     int track_chunk_ms = 250;     // the throughput tracking kernel's launch length (0: whole blocks; r03-r05: 500)
@@ -2177,22 +2177,18 @@ int gyp_bits_get_state(const gyp_bits* bits, int32_t channel, gyp_bits_state* ou
 // Resampler (kernels_resample.hpp): fs_in recordings -> the stream format
 // ---------------------------------------------------------------------------------------------------------
 // The design for (fs_in, the context's rate, T, input kind), built and uploaded on first use.  A copy: the context owns d_taps' memory.
-static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool real, ResampleDesign* out, const char* who) {
+static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool real, ResampleDesign* out) {
     for (const auto& cached : ctx->resample_designs)
         if (const ResampleDesign& d = cached.first; d.fs_in == fs_in && d.fs_out == ctx->fs && d.taps == T && d.real == real) {
             *out = d;
             return GYP_OK;
         }
     ResampleDesign d;
+    static_cast<ResampleRatio&>(d) = resample_ratio(fs_in, ctx->fs);
     d.fs_in = fs_in;
     d.fs_out = ctx->fs;
     d.taps = T;
     d.real = real;
-    d.n_in = (int32_t)(fs_in / 1000);
-    d.n_out = (int32_t)(ctx->fs / 1000);
-    d.g = (int32_t)resample_gcd(d.n_in, d.n_out);
-    d.L = d.n_out / d.g;
-    d.M = d.n_in / d.g;
     std::vector<float> rows((size_t)d.L * T), cols((size_t)d.L * T);
     resample_design_rows(fs_in, ctx->fs, T, d.L, rows.data());
     for (int32_t p = 0; p < d.L; ++p) {   // the kernel's layout: column p holds phase p's taps (design row p*M mod L)
@@ -2201,44 +2197,62 @@ static int resample_cached_design(gyp_ctx* ctx, int64_t fs_in, int32_t T, bool r
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<float> taps;
-    HIP_TRY(ctx, taps.reserve(cols.size(), Slack::exact));
+    HIP_TRY(ctx, upload(taps, cols.data(), cols.size(), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `cols` is a temporary
     d.d_taps = taps.get();
-    const hipError_t e = hipMemcpyAsync(d.d_taps, cols.data(), cols.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `cols` is a temporary
-    if (e2 != hipSuccess) return fail(ctx, GYP_E_HIP, std::string(who) + ": table upload: " + hipGetErrorString(e2));
     ctx->resample_designs.emplace_back(d, std::move(taps));
     *out = d;
     return GYP_OK;
 }
 
-static int resample_get_design(gyp_ctx* ctx, int64_t fs_in, int32_t taps, ResampleDesign* out, const char* who) {
-    if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": " + kNoFormat);
-    const int32_t T = resample_taps(taps);
-    if (!T) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (32), 16, 24, 32, 48 or 64");
-    if (!resample_rates_ok(fs_in, ctx->fs))
-        return fail(ctx, GYP_E_BAD_RATE, std::string(who) + ": fs_in must be a positive multiple of 1000 Hz, differ from the stream format's rate "
-                                                            "and lie within a factor 2 of it");
-    return resample_cached_design(ctx, fs_in, T, false, out, who);
-}
-
+static const char* const kResampleTapsRule = ": taps must be 0 (32), 16, 24, 32, 48 or 64";
+static const char* const kDdcTapsRule = ": taps must be 0 (auto), 32, 48, 64, 96 or 128";
 static const char* const kDdcRateRule = ": rates must be whole kHz with fs_in < 2^31 Hz and 8 fs_out >= fs_in, and the IF must satisfy "
                                         "20 |if| >= 9 fs_out and 20 |if| + 9 fs_out <= 10 fs_in";
 
-static int ddc_get_design(gyp_ctx* ctx, int64_t fs_in, int64_t if_hz, int32_t taps, ResampleDesign* out, const char* who) {
+// The design that takes fs_in recordings to the context's rate: the resampler's (I,Q words), or with `real` the down-converter's
+// (real words at if_hz).  Refuses in this order: no stream format, the tap count, the rates.
+static int filter_design(gyp_ctx* ctx, int64_t fs_in, bool real, int64_t if_hz, int32_t taps, ResampleDesign* out, const char* who) {
     if (!ctx->fs) return fail(ctx, GYP_E_NO_FORMAT, std::string(who) + ": " + kNoFormat);
-    if (taps && !ddc_taps(taps, 0, 0)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": taps must be 0 (auto), 32, 48, 64, 96 or 128");
-    if (!ddc_rates_ok(fs_in, ctx->fs, if_hz)) return fail(ctx, GYP_E_BAD_RATE, std::string(who) + kDdcRateRule);
-    return resample_cached_design(ctx, fs_in, ddc_taps(taps, fs_in, ctx->fs), true, out, who);
+    if (real ? taps && !ddc_taps(taps, 0, 0) : !resample_taps(taps))
+        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + (real ? kDdcTapsRule : kResampleTapsRule));
+    if (real ? !ddc_rates_ok(fs_in, ctx->fs, if_hz) : !resample_rates_ok(fs_in, ctx->fs))
+        return fail(ctx, GYP_E_BAD_RATE, std::string(who) + (real ? kDdcRateRule : ": fs_in must be a positive multiple of 1000 Hz, differ from the "
+                                                                                   "stream format's rate and lie within a factor 2 of it"));
+    return resample_cached_design(ctx, fs_in, real ? ddc_taps(taps, fs_in, ctx->fs) : resample_taps(taps), real, out);
 }
 
+// One call of the sample path, by name: the words, the window of them the caller holds, the scale, the output window.
+struct RawWindow {
+    const void* raw;        // stream 0's words
+    int64_t stride;         // between streams: in SAMPLES for word formats, in BYTES for packed ones
+    int64_t first, n;       // the buffer holds input samples first .. first+n-1 (the unpacker: samples 0 .. n-1); zeros outside
+    int32_t bit0;           // packed words: the buffer's sample 0 starts bit0 bits into its first byte; else 0
+};
+struct OutWindow {
+    float* iq;              // stream 0's complex64 samples
+    int64_t stride;         // between streams, in samples
+    int64_t first_ms;       // output milliseconds first_ms .. first_ms+n_ms-1 (the unpacker: in.n samples) ...
+    int32_t n_ms, n_streams;   // ... of n_streams streams
+};
+struct SampleRequest {
+    int32_t fmt;            // GYP_FMT_* words, unless ...
+    const PackedFormat* pk; // ... set: packed words of this format
+    int64_t if_hz;          // real words (the design's kind says so) are mixed down from it; I,Q words: 0
+    float scale;
+    RawWindow in;
+    OutWindow out;
+};
+
 template <class S, int TT>
-static void resample_launch_one(dim3 grid, size_t lds, hipStream_t stream, const void* raw, int64_t in_stride, int64_t raw_first,
-                                int64_t raw_n, const typename S::Params& prm, const ResampleDesign& d, int64_t p_first, int64_t n_periods,
-                                int32_t np_tile, int32_t pc_tile, int32_t n_pchunks, float* out, int64_t out_stride) {
+static void resample_launch_one(hipStream_t stream, const ResampleDesign& d, const SampleRequest& rq, const ResampleTiling& tl,
+                                const typename S::Params& prm) {
     S stage;
     static_cast<typename S::Params&>(stage) = prm;
-    hipLaunchKernelGGL((resample_kernel<S, TT>), grid, dim3(256), lds, stream, (const typename S::Word*)raw, in_stride, raw_first, raw_n,
-                       stage, d.d_taps, d.L, d.M, p_first, n_periods, np_tile, pc_tile, n_pchunks, (float2*)out, out_stride);
+    const dim3 grid((unsigned)tl.n_tiles, (unsigned)rq.out.n_streams);
+    hipLaunchKernelGGL((resample_kernel<S, TT>), grid, dim3(256), (size_t)tl.lds_samples * sizeof(float2), stream, (const typename S::Word*)rq.in.raw,
+                       rq.in.stride, rq.in.first, rq.in.n, stage, d.d_taps, d.L, d.M, tl.p_first, tl.n_periods, tl.np_tile, tl.pc_tile,
+                       tl.n_pchunks, (float2*)rq.out.iq, rq.out.stride);
 }
 
 // The tap counts each policy is instantiated for: the resampler's 16..64, the down-converter's 32..128.
@@ -2282,156 +2296,105 @@ static void resample_launch_bits(int32_t bits, int32_t T, const A&... a) {
     }
 }
 
-// resample_kernel's launch shape for output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.
-struct ResampleShape {
-    dim3 grid;
-    size_t lds;
-    int64_t p_first, n_periods;
-    int32_t np_tile, pc_tile, n_pchunks;
-};
-static int resample_shape(gyp_ctx* ctx, const ResampleDesign& d, int32_t n_streams, int64_t first_ms, int32_t n_ms, int32_t TS, ResampleShape* sh) {
-    const int64_t n_periods = (int64_t)n_ms * d.g;
-    const int32_t T = d.taps;
-    int32_t np_tile = 1, pc_tile = d.L, n_pchunks = 1;
-    size_t lds_samples;
-    if (d.M + T - 1 <= TS) {      // whole periods: as many as fit
-        np_tile = (int32_t)std::min<int64_t>(std::max(1, (TS - T + 1) / d.M), n_periods);
-        lds_samples = (size_t)np_tile * d.M + T - 1;
-    } else {                      // one period, its phases in chunks whose span fits
-        pc_tile = (int32_t)std::max<int64_t>(1, (int64_t)(TS - T - 1) * d.L / d.M);
-        n_pchunks = (d.L + pc_tile - 1) / pc_tile;
-        lds_samples = (size_t)TS;
-    }
-    const int64_t n_tiles = (n_periods + np_tile - 1) / np_tile * n_pchunks;
-    if (n_tiles > INT32_MAX || n_streams > 65535) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample: launch too large (split it)");
-    *sh = ResampleShape{dim3((unsigned)n_tiles, (unsigned)n_streams), lds_samples * sizeof(float2), first_ms * d.g, n_periods, np_tile,
-                        pc_tile, n_pchunks};
-    return GYP_OK;
-}
-
-// Enqueue resample_kernel on `stream`: output milliseconds first_ms .. first_ms+n_ms-1 of n_streams streams.  A real design (the
-// down-converter's) stages real words mixed down from if_hz; in_stride / raw_first / raw_n count samples either way.
-static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, int32_t fmt, const void* raw, int32_t n_streams,
-                           int64_t in_stride, int64_t raw_first, int64_t raw_n, float scale, int64_t first_ms, int32_t n_ms,
-                           float* out, int64_t out_stride, int64_t if_hz = 0) {
-    ResampleShape sh;
-    if (const int rc = resample_shape(ctx, d, n_streams, first_ms, n_ms, ctx->resample_tile, &sh)) return rc;
-    const int32_t T = d.taps;
-    if (d.real) {
-        const int64_t fs = d.fs_in;
-        const int64_t f = (if_hz % fs + fs) % fs;
-        resample_launch_fmt<StageReal>(fmt, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n,
-                                       StageRealParams{scale, fs, f, 4.0 / (double)fs, 0.5 / (double)fs}, d, sh.p_first, sh.n_periods,
-                                       sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
-    } else {
-        resample_launch_fmt<StageIQ>(fmt, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n, StageIQParams{scale}, d, sh.p_first,
-                                     sh.n_periods, sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
-}
-
 // The packing's level table in device memory: uploaded on first use and cached on the context (which frees it), like a design.
 static int packed_levels_dev(gyp_ctx* ctx, const PackedFormat& pk, const float** out) {
-    const std::vector<float> key(pk.levels.v, pk.levels.v + 16);
     for (const auto& l : ctx->packed_levels)
-        if (std::memcmp(l.first.data(), key.data(), sizeof(pk.levels.v)) == 0) {
+        if (std::memcmp(l.first.v, pk.levels.v, sizeof(pk.levels.v)) == 0) {
             *out = l.second.get();
             return GYP_OK;
         }
     DevBuf<float> d;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, d.reserve(key.size(), Slack::exact));
-    const hipError_t e = hipMemcpyAsync(d.get(), key.data(), sizeof(pk.levels.v), hipMemcpyHostToDevice, ctx->stream);
-    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;   // `key` is a temporary
-    if (e2 != hipSuccess) return fail(ctx, GYP_E_HIP, std::string("packed level table upload: ") + hipGetErrorString(e2));
+    HIP_TRY(ctx, upload(d, pk.levels.v, 16, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `pk` may be the caller's temporary
     *out = d.get();
-    ctx->packed_levels.emplace_back(key, std::move(d));
+    ctx->packed_levels.emplace_back(pk.levels, std::move(d));
     return GYP_OK;
 }
 
-// resample_launch on packed words: in_stride counts bytes, and the buffer's sample 0 (input sample raw_first) starts bit0 bits
-// into its first byte.  The design's kind (real or not) matches pk.real.
-static int resample_launch_packed(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, const PackedFormat& pk, const void* raw,
-                                  int32_t n_streams, int64_t in_stride, int32_t bit0, int64_t raw_first, int64_t raw_n, float scale,
-                                  int64_t first_ms, int32_t n_ms, float* out, int64_t out_stride, int64_t if_hz) {
-    ResampleShape sh;
-    // the 16-entry level table takes 64 bytes of LDS beside the tile: the tile gives up 8 samples, so five workgroups still fit a
-    // CU (the tile's shape does not change an output's bits)
-    if (const int rc = resample_shape(ctx, d, n_streams, first_ms, n_ms, ctx->resample_tile - 8, &sh)) return rc;
-    const float* levels = nullptr;
-    if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
-    const int32_t T = d.taps;
-    if (d.real) {
-        const int64_t fs = d.fs_in;
-        StageRealPackedParams prm;
-        static_cast<StagePackedParams&>(prm) = StagePackedParams{levels, scale, pk.order, bit0};
-        prm.fs = fs;
-        prm.f = (if_hz % fs + fs) % fs;
-        prm.q_scale = 4.0 / (double)fs;
-        prm.y_scale = 0.5 / (double)fs;
-        resample_launch_bits<StageRealPacked>(pk.bits, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n, prm, d, sh.p_first,
-                                              sh.n_periods, sh.np_tile, sh.pc_tile, sh.n_pchunks, out, out_stride);
+// Enqueue resample_kernel on `stream` for a request that has passed resample_check (n_ms >= 1).  The staging policy follows the
+// words (rq.pk, rq.fmt) and the design's kind, which matches the packing's: a real design stages real words mixed down from if_hz.
+static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesign& d, const SampleRequest& rq) {
+    const ResampleTiling tl = resample_tiling(d, d.taps, rq.out.n_streams, rq.out.first_ms, rq.out.n_ms, ctx->resample_tile - (rq.pk ? 8 : 0));
+    if (!tl.fits) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample: launch too large (split it)");
+    const MixerParams mix = mixer_params(d.fs_in, rq.if_hz);
+    if (!rq.pk) {
+        if (d.real) resample_launch_fmt<StageReal>(rq.fmt, d.taps, stream, d, rq, tl, StageRealParams{rq.scale, mix.fs, mix.f, mix.q_scale, mix.y_scale});
+        else resample_launch_fmt<StageIQ>(rq.fmt, d.taps, stream, d, rq, tl, StageIQParams{rq.scale});
     } else {
-        resample_launch_bits<StageIQPacked>(pk.bits, T, sh.grid, sh.lds, stream, raw, in_stride, raw_first, raw_n,
-                                            StagePackedParams{levels, scale, pk.order, bit0}, d, sh.p_first, sh.n_periods, sh.np_tile,
-                                            sh.pc_tile, sh.n_pchunks, out, out_stride);
+        const float* levels = nullptr;
+        if (const int rc = packed_levels_dev(ctx, *rq.pk, &levels)) return rc;
+        const StagePackedParams words{levels, rq.scale, rq.pk->order, rq.in.bit0};
+        if (d.real) resample_launch_bits<StageRealPacked>(rq.pk->bits, d.taps, stream, d, rq, tl, StageRealPackedParams{words, mix.fs, mix.f, mix.q_scale, mix.y_scale});
+        else resample_launch_bits<StageIQPacked>(rq.pk->bits, d.taps, stream, d, rq, tl, words);
     }
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
 
-// Enqueue ingest_unpack_kernel on `stream` (packed I,Q words at their own rate).
-static int unpack_launch(gyp_ctx* ctx, hipStream_t stream, const PackedFormat& pk, const void* raw, int32_t n_streams, int64_t in_stride,
-                         int32_t bit0, int64_t n_samples, float scale, float* out, int64_t out_stride) {
-    const int64_t kS = 64 / pk.bits;
-    const int64_t n_items = (n_samples + kS - 1) / kS * n_streams;
+// Enqueue ingest_unpack_kernel on `stream` (packed I,Q words at their own rate): the request's in.n samples of every stream.
+static int unpack_launch(gyp_ctx* ctx, hipStream_t stream, const SampleRequest& rq) {
+    const PackedFormat& pk = *rq.pk;
+    const int64_t kS = 64 / pk.bits, n_samples = rq.in.n;
+    const int64_t n_items = (n_samples + kS - 1) / kS * rq.out.n_streams;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu));
-    const int32_t vec4 = ((uintptr_t)out & 15u) == 0 && out_stride % 2 == 0;   // every row starts 16-byte aligned
+    const int32_t vec4 = ((uintptr_t)rq.out.iq & 15u) == 0 && rq.out.stride % 2 == 0;   // every row starts 16-byte aligned
     const float* levels = nullptr;
     if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
-    const uint8_t* r = (const uint8_t*)raw;
-    float2* o = (float2*)out;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, (const uint8_t*)rq.in.raw, rq.in.stride, rq.in.bit0, n_samples, rq.out.n_streams,
+                           levels, rq.scale, pk.order, (float2*)rq.out.iq, rq.out.stride, vec4);
+    };
     switch (pk.bits) {
-        case 1: hipLaunchKernelGGL(ingest_unpack_kernel<1>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
-        case 2: hipLaunchKernelGGL(ingest_unpack_kernel<2>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
-        default: hipLaunchKernelGGL(ingest_unpack_kernel<4>, dim3(grid), dim3(256), 0, stream, r, in_stride, bit0, n_samples, n_streams, levels, scale, pk.order, o, out_stride, vec4); break;
+        case 1: launch(ingest_unpack_kernel<1>); break;
+        case 2: launch(ingest_unpack_kernel<2>); break;
+        default: launch(ingest_unpack_kernel<4>); break;
     }
     HIP_TRY(ctx, hipGetLastError());
     return GYP_OK;
 }
 
-// The checks common to the packed device entries: the buffer holds bit0 + n * B bits per stream, bit0 a sample edge below 8.
-static bool packed_buffer_ok(const PackedFormat& pk, int64_t in_stride_bytes, int32_t bit0, int64_t n_samples) {
+// A packed buffer holds bit0 + n * B bits per stream, bit0 a sample edge below 8 (the unpacker's entry asks this too).
+static bool packed_window_ok(const PackedFormat& pk, const RawWindow& in) {
     const int64_t B = pk.sample_bits();
-    if (bit0 < 0 || bit0 >= 8 || bit0 % B || n_samples < 0 || in_stride_bytes < 0) return false;
-    if (n_samples > (INT64_MAX - 8) / B / 2 || in_stride_bytes > INT64_MAX / 16) return false;
-    return in_stride_bytes * 8 >= bit0 + n_samples * B;
+    if (in.bit0 < 0 || in.bit0 >= 8 || in.bit0 % B || in.n < 0 || in.stride < 0) return false;
+    if (in.n > (INT64_MAX - 8) / B / 2 || in.stride > INT64_MAX / 16) return false;
+    return in.stride * 8 >= in.bit0 + in.n * B;
 }
 
-// The argument checks and the launch of gyp_resample_iq_dev / gyp_ddc_iq_dev, on the context's stream.
-static int resample_iq_checked(gyp_ctx* ctx, const ResampleDesign& d, const char* who, int32_t fmt, const void* raw_dev, int32_t n_streams,
-                               int64_t in_stride_samples, int64_t raw_first_sample, int64_t raw_n_samples, float scale, int64_t if_hz,
-                               int64_t first_ms, int32_t n_ms, int64_t out_stride_samples, float* out_dev) {
-    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || raw_n_samples < 0 || in_stride_samples < raw_n_samples ||
-        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
-        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, "
-                                                           "in_stride >= raw_n_samples >= 0, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
-    if (n_ms == 0) return GYP_OK;
+// GYP_E_BAD_ARG's reason, or nullptr if the request can be launched with design d (n_ms == 0: there is nothing to launch).
+static const char* resample_check(const ResampleDesign& d, const SampleRequest& rq) {
+    const RawWindow& in = rq.in;
+    const bool rest_ok = rq.out.n_streams >= 1 && rq.out.n_ms >= 0 && rq.out.first_ms >= 0 && rq.out.stride >= (int64_t)rq.out.n_ms * d.n_out &&
+                         std::isfinite(rq.scale) && (in.n <= 0 || in.raw) && (rq.out.n_ms <= 0 || rq.out.iq);
+    if (!rq.pk)
+        return rest_ok && in.n >= 0 && in.stride >= in.n ? nullptr
+                                                         : "bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, in_stride >= raw_n_samples >= 0, "
+                                                           "out_stride >= n_ms * N_out, finite scale, non-NULL buffers)";
+    return rest_ok && packed_window_ok(*rq.pk, in) ? nullptr
+                                                   : "bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, raw_n_samples >= 0, 0 <= bit0 < 8 a multiple of "
+                                                     "the sample's bits, 8 in_stride_bytes >= bit0 + raw_n_samples * sample bits, out_stride >= n_ms * N_out, "
+                                                     "finite scale, non-NULL buffers)";
+}
+
+// The three resampling device entries behind their own first checks: the design, the argument check, the launch on the context's stream.
+static int resample_dev(gyp_ctx* ctx, const char* who, int64_t fs_in_hz, bool real, int32_t taps, const SampleRequest& rq) {
+    ResampleDesign d;
+    if (const int rc = filter_design(ctx, fs_in_hz, real, rq.if_hz, taps, &d, who)) return rc;
+    if (const char* why = resample_check(d, rq)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why);
+    if (rq.out.n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return resample_launch(ctx, ctx->stream, d, fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples, scale,
-                           first_ms, n_ms, out_dev, out_stride_samples, if_hz);
+    return resample_launch(ctx, ctx->stream, d, rq);
 }
 
 extern "C" {
 
 int gyp_resample_design(int64_t fs_in_hz, int64_t fs_out_hz, int32_t taps, float* table_out, int32_t* n_phases_out) {
     const int32_t T = resample_taps(taps);
-    if (!T) return fail(nullptr, GYP_E_BAD_ARG, "gyp_resample_design: taps must be 0 (32), 16, 24, 32, 48 or 64");
+    if (!T) return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_resample_design") + kResampleTapsRule);
     if (!resample_rates_ok(fs_in_hz, fs_out_hz))
         return fail(nullptr, GYP_E_BAD_RATE, "gyp_resample_design: rates must be positive multiples of 1000 Hz, differ, and lie within a factor 2");
-    const int64_t n_out = fs_out_hz / 1000;
-    const int32_t L = (int32_t)(n_out / resample_gcd(fs_in_hz / 1000, n_out));
+    const int32_t L = resample_ratio(fs_in_hz, fs_out_hz).L;
     if (n_phases_out) *n_phases_out = L;
     if (table_out) resample_design_rows(fs_in_hz, fs_out_hz, T, L, table_out);
     return GYP_OK;
@@ -2442,19 +2405,19 @@ int gyp_resample_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t 
                         int32_t n_ms, int64_t out_stride_samples, float* out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
     if (!ingest_word_bytes(fmt)) return fail(ctx, GYP_E_BAD_ARG, "gyp_resample_iq_dev: fmt must be one of GYP_FMT_*");
-    ResampleDesign d;
-    if (const int rc = resample_get_design(ctx, fs_in_hz, taps, &d, "gyp_resample_iq_dev")) return rc;
-    return resample_iq_checked(ctx, d, "gyp_resample_iq_dev", fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples,
-                               scale, 0, first_ms, n_ms, out_stride_samples, out_dev);
+    SampleRequest rq{};
+    rq.fmt = fmt, rq.scale = scale;
+    rq.in = RawWindow{raw_dev, in_stride_samples, raw_first_sample, raw_n_samples, 0};
+    rq.out = OutWindow{out_dev, out_stride_samples, first_ms, n_ms, n_streams};
+    return resample_dev(ctx, "gyp_resample_iq_dev", fs_in_hz, false, taps, rq);
 }
 
 int gyp_ddc_design(int64_t fs_in_hz, int64_t fs_out_hz, int64_t if_hz, int32_t taps, float* table_out, int32_t* n_phases_out,
                    int32_t* taps_out) {
-    if (taps && !ddc_taps(taps, 0, 0)) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ddc_design: taps must be 0 (auto), 32, 48, 64, 96 or 128");
+    if (taps && !ddc_taps(taps, 0, 0)) return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_ddc_design") + kDdcTapsRule);
     if (!ddc_rates_ok(fs_in_hz, fs_out_hz, if_hz)) return fail(nullptr, GYP_E_BAD_RATE, std::string("gyp_ddc_design") + kDdcRateRule);
     const int32_t T = ddc_taps(taps, fs_in_hz, fs_out_hz);
-    const int64_t n_out = fs_out_hz / 1000;
-    const int32_t L = (int32_t)(n_out / resample_gcd(fs_in_hz / 1000, n_out));
+    const int32_t L = resample_ratio(fs_in_hz, fs_out_hz).L;
     if (n_phases_out) *n_phases_out = L;
     if (taps_out) *taps_out = T;
     if (table_out) resample_design_rows(fs_in_hz, fs_out_hz, T, L, table_out);
@@ -2466,10 +2429,11 @@ int gyp_ddc_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, int32_t n_str
                    int64_t out_stride_samples, float* out_dev) {
     if (!ctx) return GYP_E_BAD_ARG;
     if (!ingest_word_bytes(fmt)) return fail(ctx, GYP_E_BAD_ARG, "gyp_ddc_iq_dev: fmt must be one of GYP_FMT_*");
-    ResampleDesign d;
-    if (const int rc = ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, "gyp_ddc_iq_dev")) return rc;
-    return resample_iq_checked(ctx, d, "gyp_ddc_iq_dev", fmt, raw_dev, n_streams, in_stride_samples, raw_first_sample, raw_n_samples,
-                               scale, if_hz, first_ms, n_ms, out_stride_samples, out_dev);
+    SampleRequest rq{};
+    rq.fmt = fmt, rq.if_hz = if_hz, rq.scale = scale;
+    rq.in = RawWindow{raw_dev, in_stride_samples, raw_first_sample, raw_n_samples, 0};
+    rq.out = OutWindow{out_dev, out_stride_samples, first_ms, n_ms, n_streams};
+    return resample_dev(ctx, "gyp_ddc_iq_dev", fs_in_hz, true, taps, rq);
 }
 
 int gyp_packed_span(const gyp_packing* packing, int32_t samples_per_ms, int64_t file_bytes, int64_t first_sample, int64_t n_samples,
@@ -2499,14 +2463,18 @@ int gyp_unpack_iq_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_
     PackedFormat pk;
     if (const char* why = packing_check(packing, &pk)) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_unpack_iq_dev: ") + why);
     if (pk.real) return fail(ctx, GYP_E_BAD_ARG, "gyp_unpack_iq_dev: real words are down-converted (gyp_resample_packed_dev), not unpacked");
-    if (n_streams < 1 || n_streams > 65535 || !packed_buffer_ok(pk, in_stride_bytes, bit0, n_samples) || out_stride_samples < n_samples ||
-        !std::isfinite(scale) || (n_samples > 0 && (!raw_dev || !out_dev)))
+    SampleRequest rq{};
+    rq.pk = &pk, rq.scale = scale;
+    rq.in = RawWindow{raw_dev, in_stride_bytes, 0, n_samples, bit0};
+    rq.out = OutWindow{out_dev, out_stride_samples, 0, 0, n_streams};
+    if (n_streams < 1 || n_streams > 65535 || !packed_window_ok(pk, rq.in) || out_stride_samples < n_samples || !std::isfinite(scale) ||
+        (n_samples > 0 && (!raw_dev || !out_dev)))
         return fail(ctx, GYP_E_BAD_ARG, "gyp_unpack_iq_dev: bad arguments (1 <= n_streams <= 65535, n_samples >= 0, 0 <= bit0 < 8 a multiple "
                                         "of the sample's bits, 8 in_stride_bytes >= bit0 + n_samples * sample bits, out_stride >= n_samples, "
                                         "finite scale, non-NULL buffers)");
     if (n_samples == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return unpack_launch(ctx, ctx->stream, pk, raw_dev, n_streams, in_stride_bytes, bit0, n_samples, scale, out_dev, out_stride_samples);
+    return unpack_launch(ctx, ctx->stream, rq);
 }
 
 int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void* raw_dev, int32_t n_streams, int64_t in_stride_bytes,
@@ -2518,18 +2486,11 @@ int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void
     if (const char* why = packing_check(packing, &pk)) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why);
     if (pk.real != (if_hz != 0))
         return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": real words need if_hz != 0, I,Q words if_hz = 0");
-    ResampleDesign d;
-    if (const int rc = pk.real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who))
-        return rc;
-    if (n_streams < 1 || n_ms < 0 || first_ms < 0 || !packed_buffer_ok(pk, in_stride_bytes, bit0, raw_n_samples) ||
-        out_stride_samples < (int64_t)n_ms * d.n_out || !std::isfinite(scale) || (raw_n_samples > 0 && !raw_dev) || (n_ms > 0 && !out_dev))
-        return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (n_streams >= 1, n_ms >= 0, first_ms >= 0, raw_n_samples >= 0, "
-                                                           "0 <= bit0 < 8 a multiple of the sample's bits, 8 in_stride_bytes >= bit0 + "
-                                                           "raw_n_samples * sample bits, out_stride >= n_ms * N_out, finite scale, non-NULL buffers)");
-    if (n_ms == 0) return GYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return resample_launch_packed(ctx, ctx->stream, d, pk, raw_dev, n_streams, in_stride_bytes, bit0, raw_first_sample, raw_n_samples, scale,
-                                  first_ms, n_ms, out_dev, out_stride_samples, if_hz);
+    SampleRequest rq{};
+    rq.pk = &pk, rq.if_hz = if_hz, rq.scale = scale;
+    rq.in = RawWindow{raw_dev, in_stride_bytes, raw_first_sample, raw_n_samples, bit0};
+    rq.out = OutWindow{out_dev, out_stride_samples, first_ms, n_ms, n_streams};
+    return resample_dev(ctx, who, fs_in_hz, pk.real, taps, rq);
 }
 
 }  // extern "C"
@@ -2611,7 +2572,10 @@ int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t sam
 // Notch (kernels_notch.hpp): complex amplitudes of tones per block, their per-millisecond projection out of the samples
 // ---------------------------------------------------------------------------------------------------------
 static bool tone_rate_ok(int64_t fs_hz) { return fs_hz >= 1000 && fs_hz < ((int64_t)1 << 31); }
-static ToneMix tone_mix(int64_t fs_hz) { return ToneMix{fs_hz, 4.0 / (double)fs_hz, 0.5 / (double)fs_hz}; }
+static ToneMix tone_mix(int64_t fs_hz) {
+    const MixerParams m = mixer_params(fs_hz, 0);
+    return ToneMix{m.fs, m.q_scale, m.y_scale};
+}
 
 // Enqueue iq_tones_kernel on the context's stream for frequencies already in device memory (f mod fs each).
 static int tones_launch(gyp_ctx* ctx, const float* iq, int32_t n_streams, int64_t stride, int64_t first_index, int32_t n_blocks,
@@ -2830,6 +2794,27 @@ static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms
     return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * n, &g->cond.level);
 }
 
+// The producer of a block, on the copy stream: file-width words in `raw` (the span's slot) -> complex64 in the output slot `iq`.
+static int ingest_produce(gyp_ingest* g, const IngestSpan& sp, const gyp_ingest::Upload& u, const void* raw, float* iq) {
+    gyp_ctx* ctx = g->ctx;
+    const IngestSource& src = g->src;
+    const hipStream_t copy = g->copy_stream.get();
+    const int64_t out_n = (int64_t)u.n_ms * src.n;
+    if (src.kind == SourceKind::plain) {
+        if (src.fmt == kFmtF32) return GYP_OK;   // uploaded as it is
+        widen_launch(ctx, copy, src.fmt, raw, (size_t)out_n * 2, g->scale, iq);
+        HIP_TRY(ctx, hipGetLastError());
+        return GYP_OK;
+    }
+    SampleRequest rq{};
+    rq.fmt = src.fmt, rq.pk = src.packed() ? &src.pk : nullptr, rq.if_hz = src.if_hz, rq.scale = g->scale;
+    // word formats: the whole window, zero-padded (the buffer's sample 0 is input sample s0).  Packed words: the window's part inside
+    // the file (sample 0 is input sample in_first); a block at the output rate lies inside it whole (in_n == out_n)
+    rq.in = src.packed() ? RawWindow{raw, sp.n_bytes, sp.in_first, sp.in_n, sp.bit0} : RawWindow{raw, sp.count, sp.s0, sp.count, 0};
+    rq.out = OutWindow{iq, out_n, u.first_ms, u.n_ms, 1};
+    return src.filtered() ? resample_launch(ctx, copy, src.rs, rq) : unpack_launch(ctx, copy, rq);
+}
+
 // Enqueue the upload (+ widening) of the reader's next block on the copy stream.  Returns 1 if a block was
 // enqueued, 0 if none is available (end of data, or not yet read and !wait), negative on error.
 static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait) {
@@ -2862,27 +2847,7 @@ static int ingest_enqueue_upload(gyp_ingest* g, gyp_ingest::Upload* u, bool wait
     const IngestSpan sp = ingest_span(src, g->file_samples, u->first_ms, u->n_ms);
     if (sp.slot_bytes()) HIP_TRY(ctx, hipMemcpyAsync(raw, g->host[slot], (size_t)sp.slot_bytes(), hipMemcpyHostToDevice, copy));
     HIP_TRY(ctx, hipEventRecord(g->uploaded[d].get(), copy));
-    const int64_t out_n = (int64_t)u->n_ms * src.n;
-    int rc = GYP_OK;
-    switch (src.kind) {   // the producer: file-width words -> complex64 in the output slot
-        case SourceKind::plain:
-            if (src.fmt != kFmtF32) {
-                widen_launch(ctx, copy, src.fmt, raw, (size_t)out_n * 2, g->scale, iq);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-            break;
-        case SourceKind::filtered:   // the whole window, zero-padded: the buffer's sample 0 is input sample s0
-            rc = resample_launch(ctx, copy, src.rs, src.fmt, raw, 1, sp.count, sp.s0, sp.count, g->scale, u->first_ms, u->n_ms, iq, out_n, src.if_hz);
-            break;
-        case SourceKind::packed_native:
-            rc = unpack_launch(ctx, copy, src.pk, raw, 1, sp.n_bytes, sp.bit0, out_n, g->scale, iq, out_n);
-            break;
-        case SourceKind::packed_filtered:   // the window's part inside the file: the buffer's sample 0 is input sample in_first
-            rc = resample_launch_packed(ctx, copy, src.rs, src.pk, raw, 1, sp.n_bytes, sp.bit0, sp.in_first, sp.in_n, g->scale, u->first_ms,
-                                        u->n_ms, iq, out_n, src.if_hz);
-            break;
-    }
-    if (rc) return rc;
+    if (const int rc = ingest_produce(g, sp, *u, raw, iq)) return rc;
     if (const int lrc = ingest_condition(g, d, u->first_ms, u->n_ms)) return lrc;
     HIP_TRY(ctx, hipEventRecord(g->ready[d].get(), copy));
     g->in_flight.push_back(*u);
@@ -2962,7 +2927,7 @@ static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int
     if (!path || !wb || block_ms < 1 || depth < 3 || depth > 64)
         return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad arguments (format, block_ms >= 1, 3 <= depth <= 64)");
     ResampleDesign d;
-    if (const int rc = real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who)) return rc;
+    if (const int rc = filter_design(ctx, fs_in_hz, real, if_hz, taps, &d, who)) return rc;
     return ingest_finish_open(ctx, ingest_describe(fmt, nullptr, d, if_hz, block_ms, depth), d.fs_out, path, out, who);
 }
 
@@ -3046,8 +3011,7 @@ int gyp_ingest_open_packed(gyp_ctx* ctx, const char* path, const gyp_packing* pa
     if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
     ResampleDesign d = ingest_unfiltered((int32_t)(ctx->fs / 1000));
     if (!native)
-        if (const int rc = pk.real ? ddc_get_design(ctx, fs_in_hz, if_hz, taps, &d, who) : resample_get_design(ctx, fs_in_hz, taps, &d, who))
-            return rc;
+        if (const int rc = filter_design(ctx, fs_in_hz, pk.real, if_hz, taps, &d, who)) return rc;
     return ingest_finish_open(ctx, ingest_describe(0, &pk, d, if_hz, block_ms, depth), ctx->fs, path, out, who);
 }
 

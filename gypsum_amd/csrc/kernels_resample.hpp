@@ -28,23 +28,16 @@
 #include <cstdint>
 #include <vector>
 
-// One cached design: the taps in the kernel's layout, [T][L] with column p = phase p's taps (design row p*M mod L).
-struct ResampleDesign {
+#include "resample_plan.hpp"   // the host side's ratio, tiling and mixer constants
+
+// One cached design: the ratio of its rates (n_in, n_out, g, L, M) and the taps in the kernel's layout, [T][L] with column p =
+// phase p's taps (design row p*M mod L).
+struct ResampleDesign : gyp::ResampleRatio {
     int64_t fs_in = 0, fs_out = 0;
     int32_t taps = 0;
     bool real = false;   // the down-converter's (real words at an IF); the cache key includes it
-    int32_t n_in = 0, n_out = 0, g = 0, L = 0, M = 0;
     float* d_taps = nullptr;
 };
-
-static inline int64_t resample_gcd(int64_t a, int64_t b) {
-    while (b) {
-        const int64_t t = a % b;
-        a = b;
-        b = t;
-    }
-    return a;
-}
 
 // taps: 0 -> 32; otherwise one of 16, 24, 32, 48, 64.  Returns 0 if not allowed.
 static inline int32_t resample_taps(int32_t taps) {

@@ -720,6 +720,36 @@ static void acq_plans() {
     Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
 }
 
+// --------------------------------------------------------------------------------------------------------- resample-plan
+// shapes.i64 rows: fs_in, fs_out (Hz), taps, n_streams, first_ms, n_ms, tile_samples.  plans.i64 rows: ResampleRatio's members, then
+// ResampleTiling's, in their order.  mixers.i64 rows: fs, f_hz -> mixed.i64 rows: MixerParams' members (the two scales as their bits).
+static void resample_plans() {
+    const std::vector<int64_t> shapes = read_array<int64_t>("shapes.i64");
+    REQUIRE(shapes.size() % 7 == 0);
+    std::vector<int64_t> plans;
+    plans.reserve(shapes.size() / 7 * 13);
+    for (size_t r = 0; r * 7 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 7];
+        const ResampleRatio q = resample_ratio(s[0], s[1]);
+        const ResampleTiling t = resample_tiling(q, (int32_t)s[2], (int32_t)s[3], s[4], (int32_t)s[5], (int32_t)s[6]);
+        for (int64_t v : {(int64_t)q.n_in, (int64_t)q.n_out, (int64_t)q.g, (int64_t)q.L, (int64_t)q.M, (int64_t)t.fits, t.n_tiles, t.lds_samples, t.p_first,
+                          t.n_periods, (int64_t)t.np_tile, (int64_t)t.pc_tile, (int64_t)t.n_pchunks})
+            plans.push_back(v);
+    }
+    Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+    const std::vector<int64_t> mixers = read_array<int64_t>("mixers.i64");
+    Out mixed("mixed.i64");
+    for (size_t r = 0; r * 2 < mixers.size(); ++r) {
+        const MixerParams m = mixer_params(mixers[2 * r], mixers[2 * r + 1]);
+        const ToneMix tone = tone_mix(m.fs);   // the tone kernels' constants come from the same function
+        REQUIRE(tone.fs == m.fs && tone.q_scale == m.q_scale && tone.y_scale == m.y_scale);
+        int64_t bits[2];
+        std::memcpy(&bits[0], &m.q_scale, 8);
+        std::memcpy(&bits[1], &m.y_scale, 8);
+        for (int64_t v : {m.fs, m.f, bits[0], bits[1]}) mixed.i64(v);
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------- dev-mem
 // The owners of dev_mem.hpp on a host without a device (every allocation fails), the scratch layouts, the table of debug switches on a
 // context that lives on the stack.  No kernel is launched and no context is made through gyp_create.
@@ -860,7 +890,8 @@ int main(int argc, char** argv) {
     const std::pair<const char*, void (*)()> table[] = {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
-        {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"dev-mem", drv::dev_mem},
+        {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"resample-plan", drv::resample_plans},
+        {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

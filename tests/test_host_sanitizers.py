@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, resample_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -24,7 +24,8 @@ import host_san_build
 from gypsum_amd import _lib
 from gypsum_amd.build import find_hipcc
 
-# measured: both programs build in 37 s side by side, the longest scenario takes 4 s; x2 for a loaded machine, rounded up
+# measured: both programs build in 37 s side by side, the longest scenario with its model (resample-plan under TSan, 5 million rows)
+# takes 24 s; x2 for a loaded machine, rounded up
 pytestmark = pytest.mark.timeout(120)
 
 ASAN, TSAN = "asan_ubsan", "tsan"
@@ -773,6 +774,125 @@ def test_acq_plan(programs, tmp_path, which):
         plan["parts"] = [plan[f"lane_streams{i}"] for i in range(plan["lanes"])]
         for field, value in expected.items():
             assert plan[field] == value, (shape, field, plan[field])
+
+
+# ------------------------------------------------------------------------------------------------------------ resample-plan
+RESAMPLE_TAPS, DDC_TAPS = (16, 24, 32, 48, 64), (32, 48, 64, 96, 128)
+TILE_BUDGETS = (1016, 1024, 4088, 4096, 8184, 8192)          # "resample_tile_samples" at its ends and its default, and 8 less (packed words)
+# Worked out by hand from resample_shape as it stood before resample_plan.hpp: (n_in kHz, n_out kHz, T, budget, n_ms, first_ms) ->
+# (np_tile, pc_tile, n_pchunks, lds_samples, n_tiles, p_first, n_periods).  4000 -> 4092: g 4, L 1023, M 1000; 16368 -> 4092: g 4092,
+# L 1, M 4; 38192 -> 8184: g 2728, L 3, M 14; 2048 -> 2046: g 2, L 1023, M 1024.
+RESAMPLE_LITERALS = [
+    ((4000, 4092, 32, 4096, 5, 3), (4, 1023, 1, 4031, 5, 12, 20)),
+    ((4000, 4092, 32, 1024, 5, 3), (1, 1013, 2, 1024, 40, 12, 20)),
+    ((4000, 4092, 32, 4088, 5, 3), (4, 1023, 1, 4031, 5, 12, 20)),       # the packed budget: the same plan as 4096
+    ((4000, 4092, 32, 1031, 1, 0), (1, 1023, 1, 1031, 4, 0, 4)),         # M + T - 1: a whole period just fits
+    ((4000, 4092, 32, 1030, 1, 0), (1, 1019, 2, 1030, 8, 0, 4)),         # one sample less: chunks
+    ((16368, 4092, 64, 4096, 1, 0), (1008, 1, 1, 4095, 5, 0, 4092)),
+    ((38192, 8184, 96, 4096, 2, 7), (285, 3, 1, 4085, 20, 19096, 5456)),
+    ((2048, 2046, 16, 4096, 1, 0), (2, 1023, 1, 2063, 1, 0, 2)),
+]
+# the refusal's edges: (n_in, n_out, T, budget, n_ms, n_streams) -> (fits, n_tiles)
+RESAMPLE_EDGES = [
+    ((16368, 4092, 128, 1024, 117_555_312, 1), (1, 2_147_483_646)),
+    ((16368, 4092, 128, 1024, 117_555_313, 1), (0, 0)),
+    ((2048, 2046, 32, 4096, 1, 65535), (1, 1)),
+    ((2048, 2046, 32, 4096, 1, 65536), (0, 0)),
+]
+MIXER_ROWS = [(16_368_000, 4_092_000), (16_368_000, -4_092_000), (16_368_000, -1), (38_192_000, -9_548_001), (2_147_483_000, -2_147_483_000),
+              (5_000_000, -12_345_678), (1000, 0), (2_046_000, 2_046_000)]
+
+
+def resample_sweep():
+    """Rows (n_in, n_out, T, n_streams, first_ms, n_ms, budget): every stream rate; the resampler's input rates N_out/2 .. 2 N_out and
+    the down-converter's N_out .. 8 N_out -- both ends, the neighbours of N_out and 61 rates in between, and at 1.023 and 2.046 Msps
+    every kHz; every tap count; the six budgets and the two at the branch, M + T - 1 and M + T - 2; n_ms 1, 2, 9, 250 (first_ms goes
+    with n_ms); n_streams 1, 2, 65535, 65536."""
+    ms = np.array([(1, 0), (2, 7), (9, 3), (250, 1_000_000)])                   # (n_ms, first_ms)
+
+    def cross(n_out, n_in, taps, streams):
+        t, i = np.meshgrid(np.array(taps), n_in, indexing="ij")
+        pairs = np.stack([i.ravel(), np.full(i.size, n_out), t.ravel()], axis=1).astype(np.int64)
+        M = pairs[:, 0] // np.gcd(pairs[:, 0], pairs[:, 1])
+        budgets = np.concatenate([np.broadcast_to(np.array(TILE_BUDGETS), (len(pairs), 6)), (M + pairs[:, 2] - 1)[:, None], (M + pairs[:, 2] - 2)[:, None]], axis=1)
+        p, b, m, s = (x.ravel() for x in np.meshgrid(np.arange(len(pairs)), np.arange(8), np.arange(4), np.arange(len(streams)), indexing="ij"))
+        return np.stack([pairs[p, 0], pairs[p, 1], pairs[p, 2], np.array(streams)[s], ms[m, 1], ms[m, 0], budgets[p, b]], axis=1)
+
+    rows = []
+    for k in RATES:
+        n_out = 1023 * k
+        for taps, lo, hi in ((RESAMPLE_TAPS, -(-n_out // 2), 2 * n_out), (DDC_TAPS, n_out, 8 * n_out)):
+            allowed = lambda n_in: n_in[(n_in >= lo) & (n_in <= hi) & ((n_in != n_out) | (lo == n_out))]      # (the resampler refuses equal rates)
+            some = np.unique(np.r_[np.linspace(lo, hi, 61).astype(np.int64), lo + 1, hi - 1, n_out - 1, n_out + 1, n_out + 2])
+            rows.append(cross(n_out, allowed(some), taps, (1, 2, 65535, 65536)))
+            if k <= 2:   # every kHz: the grid's height plays no part in the tiling, so these go with one stream
+                rows.append(cross(n_out, allowed(np.setdiff1d(np.arange(lo, hi + 1), some)), taps, (1,)))
+    return np.concatenate(rows)
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_resample_plan(programs, tmp_path, which):
+    """resample_ratio and resample_tiling (csrc/resample_plan.hpp) against tests/resample_plan_model.py on the sweep above, the plans
+    written out above, and for every plan that fits what makes it correct: the span resample_kernel stages for a tile (its own formula,
+    model.tile_span) never exceeds the LDS reserved, on the first tile of every phase chunk and on the last (the widest: a tile holds
+    np_tile periods, or fewer at the end), and the tiles cover [p_first, p_first + n_periods) x [0, L) exactly once.  mixer_params
+    against Python integers."""
+    import resample_plan_model as model
+
+    d = indir(tmp_path)
+    sweep = resample_sweep()
+    literal = i64([(n_in, n_out, T, 1, first, n_ms, budget) for (n_in, n_out, T, budget, n_ms, first), _ in RESAMPLE_LITERALS])
+    edges = i64([(n_in, n_out, T, n_streams, 0, n_ms, budget) for (n_in, n_out, T, budget, n_ms, n_streams), _ in RESAMPLE_EDGES])
+    rows = np.concatenate([sweep, literal, edges])
+    n_in, n_out, T, n_streams, first_ms, n_ms, budget = rows.T
+    np.stack([n_in * 1000, n_out * 1000, T, n_streams, first_ms, n_ms, budget], axis=1).astype("<i8").tofile(d / "shapes.i64")
+    i64(MIXER_ROWS).tofile(d / "mixers.i64")
+    out = run(programs, which, "resample-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(rows), len(model.RATIO_FIELDS) + len(model.FIELDS))
+    (d / "shapes.i64").unlink()
+    (out / "plans.i64").unlink()
+    ratio = model.resample_ratio(n_in * 1000, n_out * 1000)
+    for col, field in enumerate(model.RATIO_FIELDS):
+        assert np.array_equal(got[:, col], ratio[field]), field
+    want = model.resample_tilings(n_in, n_out, T, n_streams, first_ms, n_ms, budget)
+    tiling = got[:, len(model.RATIO_FIELDS):]
+    for col, field in enumerate(model.FIELDS):
+        bad = np.flatnonzero(tiling[:, col] != want[:, col])
+        assert len(bad) == 0, (field, len(bad), rows[bad[0]].tolist(), int(tiling[bad[0], col]), int(want[bad[0], col]))
+    plan = {f: tiling[:, c] for c, f in enumerate(model.FIELDS)}
+    fits = plan["fits"] == 1
+    assert np.array_equal(fits[:len(sweep)], n_streams[:len(sweep)] <= 65535) and (tiling[~fits] == 0).all()   # (in the sweep the streams alone decide)
+    # the invariant, on every row that fits (none is excused)
+    g, L, M = ratio["g"][fits], ratio["L"][fits], ratio["M"][fits]
+    ok = {f: v[fits] for f, v in plan.items()}
+    period_tiles = -(-ok["n_periods"] // ok["np_tile"])
+    assert np.array_equal(ok["n_tiles"], period_tiles * ok["n_pchunks"])                       # one tile per (period tile, chunk)
+    assert np.array_equal(ok["p_first"], first_ms[fits] * g) and np.array_equal(ok["n_periods"], n_ms[fits] * g)
+    # np_tile periods a tile, the last one the rest: [p_first, p_first + n_periods) once; pc_tile phases a chunk, the last the rest: [0, L) once
+    assert (ok["np_tile"] >= 1).all() and ((period_tiles - 1) * ok["np_tile"] < ok["n_periods"]).all()
+    assert (ok["pc_tile"] >= 1).all() and ((ok["n_pchunks"] - 1) * ok["pc_tile"] < L).all() and (ok["n_pchunks"] * ok["pc_tile"] >= L).all()
+    worst, taps = np.zeros(fits.sum(), dtype=np.int64), T[fits]
+    has = np.arange(len(worst))                                                                 # the plans that have a chunk `chunk`
+    for chunk in range(int(ok["n_pchunks"].max())):
+        has = has[ok["n_pchunks"][has] > chunk]
+        sub = {f: v[has] for f, v in ok.items()}
+        for tile in (np.full(len(has), chunk), (period_tiles[has] - 1) * sub["n_pchunks"] + chunk):       # this chunk of the first and of the last period tile
+            worst[has] = np.maximum(worst[has], model.tile_span(sub, L[has], M[has], taps[has], tile))
+    over = np.flatnonzero(worst > ok["lds_samples"])
+    assert len(over) == 0, (len(over), rows[fits][over[0]].tolist(), int(worst[over[0]]), int(ok["lds_samples"][over[0]]))
+    assert (worst >= taps).all()
+    assert {1, 2} <= set(np.unique(ok["n_pchunks"]).tolist()) and (ok["np_tile"] > 1).any()    # both branches were swept
+    for row, (shape, expected) in zip(tiling[len(sweep):], RESAMPLE_LITERALS):
+        p = dict(zip(model.FIELDS, row.tolist()))
+        assert p["fits"] == 1 and (p["np_tile"], p["pc_tile"], p["n_pchunks"], p["lds_samples"], p["n_tiles"], p["p_first"], p["n_periods"]) == expected, (shape, p)
+    for row, (shape, expected) in zip(tiling[len(sweep) + len(literal):], RESAMPLE_EDGES):
+        assert (row[0], row[1]) == expected and (expected[0] or not row.any()), (shape, row.tolist())
+    mixed = np.fromfile(out / "mixed.i64", dtype="<i8").reshape(len(MIXER_ROWS), 4)
+    for (fs, f_hz), (got_fs, got_f, q_bits, y_bits) in zip(MIXER_ROWS, mixed.tolist()):
+        f, q, y = model.mixer_params(fs, f_hz)
+        assert got_fs == fs and got_f == f and 0 <= got_f < fs, (fs, f_hz, got_f)
+        assert q_bits == np.float64(q).view(np.int64) and y_bits == np.float64(y).view(np.int64), (fs, f_hz)
+        assert q == 4.0 / fs and y == 0.5 / fs
 
 
 # ------------------------------------------------------------------------------------------------------------ dev-mem
