@@ -203,15 +203,20 @@ class AntennaSampleProviderResampled(_CursorProvider):
 
     `notches` (a list of whole Hz) or `find_tones` (True, or a dict of `IqFileIngest.find_tones`'s arguments; applied once after
     opening) removes CW interference from every sample served (gypsum_amd.notch); the two exclude each other.  The chain is
-    producer -> notches -> level, and tones are found and installed BEFORE `calibrate` measures: its level is the notched output's."""
+    producer -> notches -> level, and tones are found and installed BEFORE `calibrate` measures: its level is the notched output's.
+
+    `blank` (a gypsum_amd.blanker.Blanker) or `find_pulses` (True, or a dict of `IqFileIngest.find_pulses`'s arguments; applied once
+    after opening) blanks pulsed interference in every sample served (gypsum_amd.blanker); the two exclude each other.  The blanker
+    stands in front of the notches and runs FIRST: tones and level are then measured on the blanked output.  Where `find_pulses`
+    names no guard it is half the filter's taps (at most 64): a T-tap resampler or down-converter smears a pulse over T samples."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
                  sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
                  engine=None, device: int = 0, if_hz: int | None = None, packing=None, level=None, calibrate: dict | None = None,
-                 notches=None, find_tones=None) -> None:
+                 notches=None, find_tones=None, blank=None, find_pulses=None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
-        from .resample import default_ddc_rate, nearest_supported_rate
+        from .resample import DEFAULT_TAPS, ddc_design, default_ddc_rate, nearest_supported_rate
 
         if hasattr(path, "sdr_sample_rate"):
             info = path
@@ -228,6 +233,8 @@ class AntennaSampleProviderResampled(_CursorProvider):
             raise ValueError("level and calibrate exclude each other: a level is either given or measured")
         if notches is not None and find_tones:
             raise ValueError("notches and find_tones exclude each other: tones are either given or found")
+        if blank is not None and find_pulses:
+            raise ValueError("blank and find_pulses exclude each other: a blanker is either given or measured")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
         self.if_hz = None if if_hz is None else int(if_hz)
@@ -259,6 +266,20 @@ class AntennaSampleProviderResampled(_CursorProvider):
                                         resample_from_hz=self.input_sample_rate, taps=taps, if_hz=self.if_hz)
             if np.dtype(sample_component_data_type) != np.dtype(np.float32) and scale != 1.0:
                 self._ingest.set_scale(scale)
+        self.blanker, self.pulses = blank, None  # pulses: {"median", "threshold"} where find_pulses ran
+        if blank is not None:
+            self._ingest.set_blanker(blank)
+        elif find_pulses:
+            args = dict(find_pulses) if isinstance(find_pulses, dict) else {}
+            if "guard" not in args:
+                if self.if_hz is not None:
+                    filter_taps = ddc_design(self.input_sample_rate, self.sample_rate, self.if_hz, int(taps or 0)).shape[1]
+                elif packing is not None and not packing.real and self.input_sample_rate == self.sample_rate:
+                    filter_taps = 8                  # only unpacked: the blanker's own default guard of 4
+                else:
+                    filter_taps = int(taps or DEFAULT_TAPS)
+                args["guard"] = min(filter_taps // 2, 64)
+            self.blanker, self.pulses = self._ingest.find_pulses(**args)
         self.tones = None                        # [(Hz, dB over the median), ...] where find_tones ran
         if notches is not None:
             self._ingest.set_notches(notches)

@@ -2763,6 +2763,93 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------------------
+// Blanker (kernels_blank.hpp): per-millisecond pulse blanking, the power histogram its threshold comes from
+// ---------------------------------------------------------------------------------------------------------
+// Enqueue iq_blank_kernel on `stream`, kBlankStreams streams per launch (their blankers are a kernel argument): one workgroup per
+// (stream, millisecond) over the widen kernel's persistent grid.  The blankers have passed blanker_check; counts may be null.
+static int blank_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride, int32_t n_ms,
+                        int32_t n, const gyp_blanker* blankers, int32_t* counts) {
+    for (int32_t s0 = 0; s0 < n_streams; s0 += kBlankStreams) {
+        const int32_t ns = std::min<int32_t>(kBlankStreams, n_streams - s0);
+        BlankArgs a{};
+        for (int32_t i = 0; i < kBlankStreams; ++i) a.v[i] = blankers[s0 + std::min(i, ns - 1)];
+        const int64_t n_items = (int64_t)ns * n_ms;
+        const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
+        const float2* src = reinterpret_cast<const float2*>(in) + s0 * stride;
+        float2* dst = reinterpret_cast<float2*>(out) + s0 * stride;
+        int32_t* cnt = counts ? counts + (int64_t)s0 * n_ms : nullptr;
+        if (in == out)   // in place: only blanked samples are stored
+            hipLaunchKernelGGL(iq_blank_kernel<false>, dim3(grid), dim3(kBlankThreads), 0, stream, src, dst, stride, n_ms, n, n_items, a, cnt);
+        else
+            hipLaunchKernelGGL(iq_blank_kernel<true>, dim3(grid), dim3(kBlankThreads), 0, stream, src, dst, stride, n_ms, n, n_items, a, cnt);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return GYP_OK;
+}
+
+// Zero the histograms and enqueue iq_power_hist_kernel on `stream`, kBlankStreams streams per launch; the launches of a call share
+// the persistent grid's workgroups among their streams.  centres: 2 floats per stream, or null for 0.
+static int hist_launch(gyp_ctx* ctx, hipStream_t stream, const float* iq, int32_t n_streams, int64_t stride, int64_t n_samples,
+                       const float* centres, uint32_t* hist) {
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)n_streams * GYP_POWER_HIST_BINS * sizeof(uint32_t), stream));
+    for (int32_t s0 = 0; s0 < n_streams; s0 += kBlankStreams) {
+        const int32_t ns = std::min<int32_t>(kBlankStreams, n_streams - s0);
+        HistArgs a{};
+        for (int32_t i = 0; i < ns; ++i) a.c[i] = centres ? make_float2(centres[2 * (s0 + i)], centres[2 * (s0 + i) + 1]) : make_float2(0.f, 0.f);
+        const int64_t cap = std::max<int64_t>(1, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu / ns);
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_samples / 2 + 255) / 256, cap));
+        hipLaunchKernelGGL(iq_power_hist_kernel, dim3(grid, ns), dim3(256), 0, stream, reinterpret_cast<const float2*>(iq) + s0 * stride, stride,
+                           n_samples, a, hist + (int64_t)s0 * GYP_POWER_HIST_BINS);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return GYP_OK;
+}
+
+extern "C" {
+
+int gyp_blank_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                     int32_t samples_per_ms, const gyp_blanker* blankers_host, int32_t* counts_out_dev) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_iq_dev: ctx is NULL");
+    if (!in_dev || !out_dev || !blankers_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_blank_iq_dev: in_dev, out_dev and blankers_host must not be NULL");
+    if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || samples_per_ms > kBlankMaxSamples ||
+        (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_blank_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
+                                        "stream_stride_samples >= n_ms * samples_per_ms)");
+    for (int32_t s = 0; s < n_streams; ++s)
+        if (const char* why = blanker_check(&blankers_host[s])) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_blank_iq_dev: ") + why);
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return blank_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, blankers_host, counts_out_dev);
+}
+
+int gyp_iq_power_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t n_samples,
+                          const float* centers_host, uint32_t* hist_out_dev) {
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: ctx is NULL");
+    if (!iq_dev || !hist_out_dev) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: iq_dev and hist_out_dev must not be NULL");
+    if (n_streams < 1 || n_samples < 1 || (n_streams > 1 && stream_stride_samples < n_samples))
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: bad arguments (n_streams >= 1, n_samples >= 1, stream_stride_samples >= n_samples)");
+    if (centers_host)
+        for (int32_t i = 0; i < 2 * n_streams; ++i)
+            if (!std::isfinite(centers_host[i])) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: every centre must be finite");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return hist_launch(ctx, ctx->stream, iq_dev, n_streams, stream_stride_samples, n_samples, centers_host, hist_out_dev);
+}
+
+int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
+                        gyp_blanker* blanker_out, double* measured_out2) {
+    if (!hist || !blanker_out) return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_from_hist: hist and blanker_out must not be NULL");
+    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_from_hist: threshold_over_median must be positive and finite");
+    if (!std::isfinite(center_re) || !std::isfinite(center_im)) return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_from_hist: the centre must be finite");
+    if (guard < 0 || guard > kBlankMaxGuard) return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_from_hist: guard must lie in 0 .. 64");
+    if (const char* why = blank_from_hist(hist, center_re, center_im, threshold_over_median, guard, blanker_out, measured_out2))
+        return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_blank_from_hist: ") + why);
+    return GYP_OK;
+}
+
+}  // extern "C"
+
 static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
     if (g->ctx) {
@@ -2786,7 +2873,12 @@ static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, co
 // A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
 static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms) {
     const int32_t n = g->src.n;
-    if (g->cond.notches.count > 0)   // chain order: producer -> notches -> level
+    g->slot_blanked[d] = g->cond.blank_on ? 1 : 0;
+    if (g->cond.blank_on)   // chain order: producer -> blanker -> notches -> level
+        if (const int rc = blank_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, n_ms, n, &g->cond.blanker,
+                                        g->dev_blanked[d].get()))
+            return rc;
+    if (g->cond.notches.count > 0)
         if (const int rc = notch_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, first_ms * n, n_ms, n,
                                         g->fs, &g->cond.notches))
             return rc;
@@ -2898,7 +2990,10 @@ static int ingest_finish_open(gyp_ctx* ctx, const IngestSource& src, int64_t fs,
         g->dev_iq.resize(depth);
         g->uploaded.resize(depth);
         g->ready.resize(depth);
+        g->dev_blanked.resize(depth);
+        g->slot_blanked.assign(depth, 0);
         for (int i = 0; i < depth; ++i) {
+            HIP_TRY(ctx, g->dev_blanked[i].reserve((size_t)src.block_ms, Slack::exact));
             HIP_TRY(ctx, g->dev_raw[i].reserve(src.raw_block_bytes, Slack::exact));
             HIP_TRY(ctx, g->dev_iq[i].reserve((size_t)src.block_ms * src.n * 2, Slack::exact));
             HIP_TRY(ctx, g->uploaded[i].create(hipEventDisableTiming));
@@ -2931,22 +3026,23 @@ static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int
     return ingest_finish_open(ctx, ingest_describe(fmt, nullptr, d, if_hz, block_ms, depth), d.fs_out, path, out, who);
 }
 
-// One measurement over the handle's own device blocks of [first_ms, first_ms + n_ms) with the level put aside, and with
-// suspend_notches the notches too (gyp_ingest_calibrate, gyp_ingest_find_tones).  per_block(iq_dev, ms done, ms to take) is called
+// One measurement over the handle's own device blocks of [first_ms, first_ms + n_ms) with the level put aside (gyp_ingest_calibrate),
+// the notches too (gyp_ingest_find_tones) or the whole conditioning (gyp_ingest_find_pulses).  per_block(iq_dev, ms done, ms to take) is called
 // for the blocks in order; after(next) does what follows the walk (downloads, host arithmetic, further launches on the context's
 // stream) and may write the conditioning to install into `next`, which starts as the one found.  Then, whatever happened and in
 // this order: the error text is saved (the seek overwrites ctx->err), the context's stream is synchronised (nothing may still read
 // a block or a temporary), release() lets the caller's temporaries go, the conditioning becomes `next` on success and what it was
 // otherwise, the cursor goes back to where it was, and the first error is reported with its own message.
 template <class PerBlock, class After, class Release>
-static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, bool suspend_notches, const char* who, PerBlock per_block,
+static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, Suspend suspend, const char* who, PerBlock per_block,
                                 After after, Release release) {
     gyp_ctx* ctx = g->ctx;
     const Conditioning before = g->cond;
     const int64_t back_to = g->consumer_ms;
     Conditioning next = before;
     g->cond.level_on = false;
-    if (suspend_notches) g->cond.notches = gyp_notch_tones{};
+    if (suspend != Suspend::level) g->cond.notches = gyp_notch_tones{};
+    if (suspend == Suspend::all) g->cond.blank_on = false;
     auto measure = [&]() -> int {
         if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
         for (int32_t done = 0; done < n_ms;) {
@@ -3053,6 +3149,8 @@ int gyp_ingest_seek(gyp_ingest* g, int64_t ms) {
         HIP_TRY(g->ctx, hipStreamSynchronize(g->copy_stream.get()));
         g->in_flight.clear();
         g->have_ahead = false;
+        g->last_slot = -1;   // (gyp_ingest_last_blanked: the slots are about to be refilled)
+        g->last_n_ms = 0;
     }
     ingest_start_reader(g, ms);
     g->consumer_ms = ms;
@@ -3067,6 +3165,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     if (g->src.packed()) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
     if (g->cond.level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->cond.notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    if (g->cond.blank_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a blanker is on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3112,6 +3211,8 @@ int gyp_ingest_next_dev(gyp_ingest* g, const float** iq_dev_out, int64_t* first_
     *first_ms_out = cur.first_ms;
     *n_ms_out = cur.n_ms;
     g->consumer_ms = cur.first_ms + cur.n_ms;
+    g->last_slot = d;
+    g->last_n_ms = cur.n_ms;
     return GYP_OK;
 }
 
@@ -3159,9 +3260,9 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     const int32_t n = g->src.n;
     std::vector<gyp_iq_stats> stats((size_t)n_ms);
     gyp_iq_level level{};
-    // the level is put aside: the blocks measured are the handle's output without it (notches stay)
+    // the level is put aside: the blocks measured are the handle's output without it (blanker and notches stay)
     const int rc = ingest_measure_range(
-        g, first_ms, n_ms, false, "gyp_ingest_calibrate",
+        g, first_ms, n_ms, Suspend::level, "gyp_ingest_calibrate",
         [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ctx->stream, iq, 1, 0, take, n, clip_level, d_stats + done); },
         [&](Conditioning& next) -> int {
             HIP_TRY(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
@@ -3247,7 +3348,7 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         }
         return GYP_OK;
     };
-    // the blocks gathered are the producer's output: no notches, no level
+    // the blocks gathered are the producer's output behind the blanker, where one is on: no notches, no level
     auto gather = [&](const float* iq, int32_t done, int32_t take) -> int {
         HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         return GYP_OK;
@@ -3304,7 +3405,7 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         }
         return GYP_OK;
     };
-    if (const int rc = ingest_measure_range(g, first_ms, n_ms, true, "gyp_ingest_find_tones", gather, search_and_install, [&] {
+    if (const int rc = ingest_measure_range(g, first_ms, n_ms, Suspend::level_notches, "gyp_ingest_find_tones", gather, search_and_install, [&] {
             (void)iq_all.reset();
             (void)recs_dev.reset();
         }))
@@ -3314,6 +3415,112 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
         if (power_db_out) power_db_out[t] = found_db[t];
     }
     *n_out = (int32_t)found.size();
+    return GYP_OK;
+}
+
+int gyp_ingest_set_blanker(gyp_ingest* g, const gyp_blanker* blanker) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: the handle was opened without a context (a blanker applies to device blocks)");
+    if (blanker) {
+        if (const char* why = blanker_check(blanker)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_blanker: ") + why);
+        if (g->src.n > kBlankMaxSamples) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: the blanker takes at most 65536 samples per millisecond");
+    }
+    g->cond.blank_on = blanker != nullptr;
+    g->cond.blanker = blanker ? *blanker : gyp_blanker{0.0f, 0.0f, 1.0f, 0};
+    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old blanker: drop it and read it again
+}
+
+int gyp_ingest_get_blanker(const gyp_ingest* g, gyp_blanker* out, int32_t* enabled_out) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_blanker: handle is NULL");
+    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_blanker: the handle was opened without a context (a blanker applies to device blocks)");
+    if (out) *out = g->cond.blanker;
+    if (enabled_out) *enabled_out = g->cond.blank_on ? 1 : 0;
+    return GYP_OK;
+}
+
+int gyp_ingest_find_pulses(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double threshold_over_median, int32_t guard,
+                           int32_t install, gyp_blanker* blanker_out, double* measured_out2) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: handle is NULL");
+    gyp_ctx* ctx = g->ctx;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the handle was opened without a context (the histogram is taken on the device)");
+    if (n_ms < 1 || n_ms > 1000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 1000");
+    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median) || guard < 0 || guard > kBlankMaxGuard)
+        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: threshold_over_median must be positive and finite, 0 <= guard <= 64");
+    const int32_t n = g->src.n;
+    if (n > kBlankMaxSamples) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the blanker takes at most 65536 samples per millisecond");
+    const int64_t total = (int64_t)n_ms * n;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<float> iq_all;
+    DevBuf<gyp_iq_stats> stats_dev;
+    DevBuf<uint32_t> hist_dev;
+    HIP_TRY(ctx, iq_all.reserve((size_t)total * 2, Slack::exact));
+    HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
+    HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
+    gyp_blanker found{};
+    // the blocks gathered are the producer's output: no blanker, no notches, no level
+    auto gather = [&](const float* iq, int32_t done, int32_t take) -> int {
+        HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        return GYP_OK;
+    };
+    auto derive = [&](Conditioning& next) -> int {
+        float centre[2] = {0.0f, 0.0f};
+        if (remove_dc) {   // the mean as gyp_iq_level_from_stats takes it
+            std::vector<gyp_iq_stats> stats((size_t)n_ms);
+            if (const int rc = stats_launch(ctx, ctx->stream, iq_all.get(), 1, 0, n_ms, n, 0.0f, stats_dev.get())) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(stats.data(), stats_dev.get(), stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            double S_re = 0.0, S_im = 0.0;
+            for (const gyp_iq_stats& r : stats) {
+                S_re += r.sum_re;
+                S_im += r.sum_im;
+            }
+            const double M = (double)n_ms * n;
+            centre[0] = (float)(S_re / M);
+            centre[1] = (float)(S_im / M);
+            if (!std::isfinite(centre[0]) || !std::isfinite(centre[1]))
+                return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the range's mean is not finite");
+        }
+        std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
+        if (const int rc = hist_launch(ctx, ctx->stream, iq_all.get(), 1, 0, total, centre, hist_dev.get())) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(hist.data(), hist_dev.get(), hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (const char* why = blank_from_hist(hist.data(), centre[0], centre[1], threshold_over_median, guard, &found, measured_out2))
+            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_find_pulses: ") + why);
+        if (install) {
+            next.blank_on = true;
+            next.blanker = found;
+        }
+        return GYP_OK;
+    };
+    if (const int rc = ingest_measure_range(g, first_ms, n_ms, Suspend::all, "gyp_ingest_find_pulses", gather, derive, [&] {
+            (void)iq_all.reset();
+            (void)stats_dev.reset();
+            (void)hist_dev.reset();
+        }))
+        return rc;
+    if (blanker_out) *blanker_out = found;
+    return GYP_OK;
+}
+
+int gyp_ingest_last_blanked(gyp_ingest* g, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
+    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: handle is NULL");
+    gyp_ctx* ctx = g->ctx;
+    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: the handle was opened without a context (a blanker applies to device blocks)");
+    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: n_ms_out is NULL, or cap > 0 without counts_out");
+    *n_ms_out = g->last_n_ms;
+    const int32_t take = std::min(cap, g->last_n_ms);
+    if (take <= 0 || g->last_slot < 0) return GYP_OK;
+    const int d = g->last_slot;
+    if (!g->slot_blanked[d]) {
+        std::fill(counts_out, counts_out + take, 0);
+        return GYP_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
+    HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
+    HIP_TRY(ctx, hipMemcpyAsync(counts_out, g->dev_blanked[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
     return GYP_OK;
 }
 

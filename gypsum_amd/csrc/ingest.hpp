@@ -332,13 +332,17 @@ static IngestExtent ingest_extent(const IngestSource& s, int64_t file_bytes) {
     return e;
 }
 
-// What is applied in place to every device block behind its producer, on the copy stream: notches, then the level.  One value, so
-// that a measurement can put it aside and back whole (ingest_measure_range).
+// What is applied in place to every device block behind its producer, on the copy stream: the blanker, then the notches, then the
+// level.  One value, so that a measurement can put it aside and back whole (ingest_measure_range).
 struct Conditioning {
     bool level_on = false;     // gyp_ingest_set_level / gyp_ingest_calibrate
     gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
     gyp_notch_tones notches{};   // gyp_ingest_set_notches / gyp_ingest_find_tones
+    bool blank_on = false;     // gyp_ingest_set_blanker / gyp_ingest_find_pulses
+    gyp_blanker blanker{0.0f, 0.0f, 1.0f, 0};
 };
+// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); everything (gyp_ingest_find_pulses).
+enum class Suspend : int32_t { level, level_notches, all };
 
 struct gyp_ingest {
     gyp_ingest(gyp_ctx* c, int64_t fs_hz, const IngestSource& s) : ctx(c), fs(fs_hz), src(s) {}
@@ -369,6 +373,11 @@ struct gyp_ingest {
     Stream copy_stream;              // (declared before everything used on it: destroyed last)
     std::vector<DevBuf<uint8_t>> dev_raw;   // file-width words (unused for float32: the upload lands in dev_iq directly)
     std::vector<DevBuf<float>> dev_iq;
+    std::vector<DevBuf<int32_t>> dev_blanked;   // per slot: the blanker's count per millisecond of the slot's block (block_ms words)
+    std::vector<uint8_t> slot_blanked;       // per slot: the block in it went through the blanker
+    Stream counts_stream;            // gyp_ingest_last_blanked's download (made by its first call: it must not wait for anything else)
+    int last_slot = -1;              // the device slot of the block most recently handed out (-1: none since open / seek)
+    int32_t last_n_ms = 0;
     std::vector<Event> uploaded, ready;
     Event consumer_mark;
     struct Upload {

@@ -26,6 +26,9 @@
 //                       float64 reduction order, and y = (x - dc) * gain in place behind whatever produced an ingest block.
 //   iq_tones_kernel / iq_notch_kernel   narrowband interference: complex amplitudes of tones per block in a fixed float64 reduction
 //                       order (spectrum scan, refinement), and their per-millisecond sequential projection out of the samples.
+//   iq_blank_kernel / iq_power_hist_kernel   pulsed interference: per millisecond the hit bits of a power threshold through
+//                       __ballot into LDS, dilated by the guard and applied (in place only the blanked samples are stored), and
+//                       the eighth-octave histogram of the power the threshold is derived from, in integer atomics.
 //   track_quality_kernel   signal quality: per (channel, window) sums of a block's tracking records -- peak moments, lock count,
 //                       narrow/wide-band power ratios of 20-ms groups -- one wavefront each, in a fixed float64 reduction order.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
@@ -45,4 +48,5 @@
 #include "kernels_resample.hpp"
 #include "kernels_level.hpp"
 #include "kernels_notch.hpp"
+#include "kernels_blank.hpp"
 #include "kernels_quality.hpp"

@@ -376,6 +376,63 @@ class GypsumEngine:
             d.free()
         return out if x.ndim > 1 else out[0]
 
+    def blank_iq_dev(self, in_ptr: int, out_ptr: int, n_streams: int, stream_stride: int, n_ms: int, samples_per_ms: int, blankers,
+                     counts_ptr: int = 0) -> None:
+        """gyp_blank_iq_dev: per millisecond, every sample whose power about the centre reaches the threshold and `guard` samples on
+        either side become the centre, stream s with blankers[s] (gypsum_amd.blanker.Blanker); out_ptr may equal in_ptr; counts_ptr
+        (0: none) receives n_streams x n_ms int32 counts of blanked samples.  Enqueued, not synchronised."""
+        from .blanker import blanker_records
+        recs = blanker_records(blankers, n_streams)
+        if len(recs) != max(1, int(n_streams)):   # (a count below 1 is the library's to refuse)
+            raise ValueError(f"{len(recs)} blankers for {n_streams} streams")
+        self._check(self.lib.gyp_blank_iq_dev(self.ctx, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n_streams), int(stream_stride),
+                                              int(n_ms), int(samples_per_ms), ptr(recs), C.c_void_p(counts_ptr or None)))
+
+    def power_hist_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, n_samples: int, centers, hist_ptr: int) -> None:
+        """gyp_iq_power_hist_dev: n_streams x 2048 uint32 counts of the samples' power about centers[s] (pairs of floats; None: 0) in
+        eighth-octave bins into hist_ptr, which is zeroed first.  Enqueued, not synchronised."""
+        c = None if centers is None else np.ascontiguousarray(centers, dtype=np.float32).reshape(-1)
+        if c is not None and len(c) != 2 * int(n_streams):
+            raise ValueError(f"{len(c)} centre components for {n_streams} streams")
+        self._check(self.lib.gyp_iq_power_hist_dev(self.ctx, C.c_void_p(iq_ptr), int(n_streams), int(stream_stride), int(n_samples),
+                                                   ptr(c), C.c_void_p(hist_ptr)))
+
+    def blank_iq(self, iq: np.ndarray, samples_per_ms: int, blankers):
+        """Host convenience: (complex64 `iq` blanked over its whole milliseconds on the device, int32 counts [[n_streams,] n_ms]);
+        2-D = one stream per row, one blanker each or one for all; a trailing part of a millisecond is returned as it is."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        out = rows.copy()
+        n_ms = rows.shape[1] // int(samples_per_ms)
+        counts = np.zeros((rows.shape[0], n_ms), dtype=np.int32)
+        if n_ms:
+            d = self.alloc(rows.nbytes).upload(rows)
+            d_counts = self.alloc(counts.nbytes)
+            self.blank_iq_dev(d.ptr.value, d.ptr.value, rows.shape[0], rows.shape[1], n_ms, samples_per_ms, blankers, d_counts.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d.ptr, out.nbytes))
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(counts), d_counts.ptr, counts.nbytes))
+            d.free()
+            d_counts.free()
+        return (out, counts) if x.ndim > 1 else (out[0], counts[0])
+
+    def power_hist(self, iq: np.ndarray, centers=None) -> np.ndarray:
+        """Host convenience: the uint32 histogram(s) [[n_streams,] 2048] of complex64 `iq` (2-D = one stream per row) about `centers`
+        (one complex number or (re, im) pair per stream; None: 0)."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        if centers is not None:
+            c = np.asarray(centers)
+            centers = np.stack([c.real, c.imag], axis=-1) if np.iscomplexobj(c) else c
+        out = np.zeros((rows.shape[0], _lib.GYP_POWER_HIST_BINS), dtype=np.uint32)
+        if rows.shape[1]:
+            d_iq = self.alloc(rows.nbytes).upload(rows)
+            d_out = self.alloc(out.nbytes)
+            self.power_hist_dev(d_iq.ptr.value, rows.shape[0], rows.shape[1], rows.shape[1], centers, d_out.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d_out.ptr, out.nbytes))
+            d_iq.free()
+            d_out.free()
+        return out if x.ndim > 1 else out[0]
+
     def track_quality_dev(self, rec_ptr: int, n_chan: int, chan_stride: int, n_ms: int, window_ms: int, out_ptr: int,
                           bit_offsets=None) -> None:
         """gyp_track_quality_dev: one gyp_quality_sums record per (channel, window of window_ms records) of tracking records in HBM,

@@ -21,6 +21,9 @@ produced it: an RTL-SDR uint8 recording needs no rewrite on the host.
 
 `set_notches` / `find_tones` (gypsum_amd.notch) remove narrowband (CW) interference from every device block, between whatever
 produced it and the level: `calibrate` then measures the notched output.
+
+`set_blanker` / `find_pulses` (gypsum_amd.blanker) blank pulsed (wideband) interference in every device block, in front of the
+notches: `find_tones` and `calibrate` then measure the blanked output, and `last_blanked` counts what each block lost.
 """
 from __future__ import annotations
 
@@ -172,6 +175,40 @@ class IqFileIngest:
         self._check(self._lib.gyp_ingest_find_tones(self._h, int(first_ms), int(n_ms), float(threshold), int(max_tones), int(bool(install)),
                                                     _lib.ptr(f), _lib.ptr(db), C.byref(n)))
         return [(int(f[i]), float(db[i])) for i in range(n.value)]
+
+    def set_blanker(self, blanker) -> None:
+        """A gypsum_amd.blanker.Blanker every device block is blanked with from the next block handed out on, between whatever
+        produced the block and the notches (gyp_ingest_set_blanker).  None switches it off."""
+        rec = None if blanker is None else blanker.record()
+        self._check(self._lib.gyp_ingest_set_blanker(self._h, _lib.ptr(rec)))
+
+    @property
+    def blanker(self):
+        """The installed Blanker, or None while none is on."""
+        from .blanker import BLANKER_DTYPE, Blanker
+        rec, on = np.zeros(1, dtype=BLANKER_DTYPE), C.c_int32()
+        self._check(self._lib.gyp_ingest_get_blanker(self._h, _lib.ptr(rec), C.byref(on)))
+        return Blanker.from_record(rec) if on.value else None
+
+    def find_pulses(self, first_ms: int = 0, n_ms: int = 10, threshold_over_median: float = 16.0, guard: int = 4, remove_dc: bool = True,
+                    install: bool = True):
+        """Measure output milliseconds [first_ms, first_ms + n_ms) of the handle's output (no blanker, no notches, no level) on the
+        device -- their mean as the centre (remove_dc; else 0), the histogram of the power about it -- and derive the blanker whose
+        threshold is sqrt(threshold_over_median x the median power).  Returns (Blanker, measured) as
+        gypsum_amd.blanker.blanker_from_hist does and installs it (install) as set_blanker does; the cursor stays where it was,
+        blocks handed out earlier are no longer valid (gyp_ingest_find_pulses)."""
+        from .blanker import BLANKER_DTYPE, Blanker, measured_dict
+        rec, measured = np.zeros(1, dtype=BLANKER_DTYPE), np.zeros(2)
+        self._check(self._lib.gyp_ingest_find_pulses(self._h, int(first_ms), int(n_ms), int(bool(remove_dc)), float(threshold_over_median),
+                                                     int(guard), int(bool(install)), _lib.ptr(rec), _lib.ptr(measured)))
+        return Blanker.from_record(rec), measured_dict(measured)
+
+    def last_blanked(self) -> np.ndarray:
+        """int32 counts of blanked samples per millisecond of the block most recently handed out by next_device_block (empty
+        before the first block and after a seek; zeros while no blanker is on).  Waits for that block only (gyp_ingest_last_blanked)."""
+        counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
+        self._check(self._lib.gyp_ingest_last_blanked(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
+        return counts[:n_ms.value]
 
     def seek(self, ms: int) -> None:
         self._check(self._lib.gyp_ingest_seek(self._h, int(ms)))

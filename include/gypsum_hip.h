@@ -28,7 +28,10 @@
 extern "C" {
 #endif
 
-/* 209 (additions; the number stays): gyp_debug_get's read-only "last_acq_lanes", "last_acq_levels", "last_acq_shared_levels" (what the last
+/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): pulsed (wideband)
+ *      interference on the device: gyp_blanker, GYP_POWER_HIST_BINS, gyp_blank_iq_dev, gyp_iq_power_hist_dev, gyp_blank_from_hist,
+ *      gyp_ingest_set_blanker, gyp_ingest_get_blanker, gyp_ingest_find_pulses, gyp_ingest_last_blanked.  Opt-in.
+ * 209 (additions; the number stays): gyp_debug_get's read-only "last_acq_lanes", "last_acq_levels", "last_acq_shared_levels" (what the last
  *      search ran).  gyp_acquire_dev and gyp_search_level_dev refuse, with GYP_E_BAD_ARG, a search of more than 65535 ms or of more than
  *      2^31 - 1 cells (28 per stream and satellite) before anything runs; such a search never worked.
  * 209 (addition; the number stays): gyp_debug_get's read-only "last_track_flow" (what the last gyp_track_block(_dev) call ran).
@@ -757,7 +760,9 @@ int gyp_ingest_get_level(const gyp_ingest* ing, gyp_iq_level* out, int32_t* enab
  * read through the handle's own path, gyp_iq_stats_dev (clip_level as given) runs on them and the records are combined in
  * millisecond order, so the level does not depend on block_ms.  The cursor is put back where it was; the call synchronises, and
  * blocks handed out earlier are no longer valid afterwards.  level_out / measured_out4 (either may be NULL) receive what
- * gyp_iq_level_from_stats wrote.  On an error the handle keeps the level it had. */
+ * gyp_iq_level_from_stats wrote.  On an error the handle keeps the level it had.
+ * With a blanker installed ("blanker" below), and only then, what is measured is the BLANKED output (and, as before, the notched
+ * one where notches are installed): the chain is producer -> blanker -> notches -> level, and an RMS taken under pulses is useless. */
 int gyp_ingest_calibrate(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
                          gyp_iq_level* level_out, double* measured_out4);
 
@@ -861,9 +866,95 @@ int gyp_ingest_get_notches(const gyp_ingest* ing, int64_t* freqs_out8, int32_t* 
  *      blocks of one millisecond (needs n_ms >= 2; skipped otherwise).
  * freqs_out / power_db_out (room for max_tones; either may be NULL) receive the frequencies and 10 log10(power / median) of the
  * scan; *n_out their number.  With install != 0 the tones are installed as gyp_ingest_set_notches does (none found: notches off).
- * On an error the handle keeps the notches it had. */
+ * On an error the handle keeps the notches it had.
+ * With a blanker installed ("blanker" below), and only then, what is searched is the BLANKED output, still without notches and
+ * without a level: the blanker stands in front of the notches, and a per-millisecond projection taken under pulses is useless. */
 int gyp_ingest_find_tones(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, double threshold, int32_t max_tones, int32_t install,
                           int64_t* freqs_out, double* power_db_out, int32_t* n_out);
+
+/* ---------------------------------------------------------------- blanker: pulsed interference ---------- */
+/* Wideband pulses (radar, DME-like bursts, ignition noise, a neighbouring transmitter keying up, ADC saturation bursts) are
+ * broadband, so a notch does nothing to them, and brief, so an RMS-based level is wrong in both directions: the pulses inflate
+ * the RMS and the gain that follows crushes the satellites.  A pulse blanker replaces the samples of a pulse by the recording's
+ * centre.  Three steps: a histogram of the power about the centre on the device (gyp_iq_power_hist_dev), a threshold from its
+ * median on the host (gyp_blank_from_hist), the blanking (gyp_blank_iq_dev, or gyp_ingest_set_blanker / gyp_ingest_find_pulses
+ * on an ingest handle).  Everything is opt-in: with none of these called every other entry point gives the bits it gave before.
+ *
+ * Decision.  Per (stream, millisecond of samples_per_ms samples), a pure function of that millisecond's samples.  In float32, one
+ * rounding per operation, no contraction:
+ *     dx = re - center_re;  dy = im - center_im;  a = dx dx;  b = dy dy;  p = a + b;  t2 = threshold threshold
+ * Sample i is a HIT iff p >= t2 (equality is a hit; a NaN p is not).  Sample i is BLANKED iff some hit j of the SAME millisecond
+ * has |i - j| <= guard.  A blanked sample becomes exactly (center_re, center_im); every other sample keeps its bits.
+ * Guards do not cross millisecond edges, so blocks, windows, seeks and call shapes give identical samples, as the notch's
+ * per-millisecond estimate does.  The cost: a hit within `guard` samples of an edge does not reach into the neighbouring
+ * millisecond, so up to `guard` samples of a pulse's skirt on the other side of the edge stay. */
+typedef struct gyp_blanker {      /* one per stream: 16 bytes */
+    float center_re, center_im;   /* finite: the recording's offset (0 for float32 / int8; ~127.4 for offset-binary uint8) */
+    float threshold;              /* positive, finite: amplitude about the centre */
+    int32_t guard;                /* 0..64 samples blanked on either side of every hit */
+} gyp_blanker;
+#define GYP_POWER_HIST_BINS 2048
+/* n_ms milliseconds of each of n_streams streams (stream s at sample s * stream_stride_samples of both buffers), stream s with
+ * blankers_host[s].  out_dev may equal in_dev (then only blanked samples are written: one read of the block and a few percent of
+ * a write); other overlaps are not allowed.  counts_out_dev (may be NULL) receives n_streams x n_ms int32 counts of blanked
+ * samples per millisecond, stream-major.  Alignment as for gyp_iq_stats_dev: any 8-byte aligned address and any stride; rows that
+ * start on 16 bytes (in both buffers) are read 16 bytes at a time.  samples_per_ms is an argument, no stream format is needed.
+ * Enqueued on the context's stream; blankers_host may be reused as soon as the call returns.  GYP_E_BAD_ARG, before anything is
+ * launched, for NULL pointers, n_streams < 1, samples_per_ms < 1 or > 65536, n_ms < 0, a stride below n_ms * samples_per_ms when
+ * n_streams > 1, a centre that is not finite, a threshold that is not positive and finite, or a guard outside 0..64. */
+int gyp_blank_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                     int32_t samples_per_ms, const gyp_blanker* blankers_host, int32_t* counts_out_dev);
+
+/* The histogram of p (as above, about centers_host[2 s], centers_host[2 s + 1]; NULL: 0) over n_samples samples of each stream:
+ * n_streams x GYP_POWER_HIST_BINS uint32 counts into hist_out_dev, which the call zeroes first.  The bin of a sample is the bits
+ * of p without the sign, shifted right by 20 -- 8 exponent bits and 3 mantissa bits: eighth-octave bins; p is never negative, and
+ * a NaN's sign is not defined.  The lower edge of bin k is the float whose bits are k << 20.  Non-finite p lands in bins >= 2040
+ * (+inf in 2040, NaN above).  Counts are integers, added with integer atomics: the same bits for every grid size, split and
+ * alignment, and histograms of parts of a stream add up to the whole's.  Enqueued on the context's stream.  GYP_E_BAD_ARG for NULL
+ * pointers (centers_host may be NULL), n_streams < 1, n_samples < 1, a stride below n_samples when n_streams > 1, or a centre that
+ * is not finite. */
+int gyp_iq_power_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t n_samples,
+                          const float* centers_host, uint32_t* hist_out_dev);
+
+/* Host only (no GPU; errors through gyp_last_error(NULL)): the blanker whose threshold is sqrt(threshold_over_median x the median
+ * of p) from one stream's histogram.  Float64, in exactly this order, one rounding per operation:
+ *     M = the sum of bins 0 .. 2039 (the finite powers);   r = M / 2
+ *     k = the first bin whose cumulative count cum_k = h_0 + .. + h_k is >= r;   lo_k = the lower edge of bin k
+ *     median = lo_k + ((r - cum_(k-1)) / h_k) * (lo_(k+1) - lo_k)        (linear inside the bin)
+ *     t = sqrt(threshold_over_median * median)
+ * blanker_out = {center_re, center_im, (float)t, guard};  measured_out2 (may be NULL) = {median, t}.
+ * What the median means: for complex Gaussian noise p is exponential and P(p > 16 median) = 2^-16, so a factor of 16 blanks one
+ * clean sample in 65536.  Strong pulses of duty d push the estimate to the 0.5 / (1 - d) quantile of the noise: +17 % at d = 0.1,
+ * where a factor of 16 acts like about 19; usable to a duty of roughly 40 %.  An eighth-octave bin is 9 % wide; the interpolation
+ * brings the estimate to within about 1 %.
+ * GYP_E_BAD_ARG for NULL hist or blanker_out, M = 0, a median that is not positive, a factor that is not positive and finite, a
+ * centre that is not finite, a guard outside 0..64, or a threshold that float32 cannot hold. */
+int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
+                        gyp_blanker* blanker_out, double* measured_out2);
+
+/* A blanker on an ingest handle (ctx required: a host-only handle returns GYP_E_BAD_ARG from all four, and gyp_ingest_next_host
+ * returns GYP_E_BAD_ARG while a blanker is on).  CHAIN ORDER of a handle: producer (widen / unpack / resample / down-convert /
+ * copy) -> blanker -> notches -> level.  Every device block is blanked in place on the upload stream exactly as gyp_blank_iq_dev
+ * would, at the handle's output rate; gyp_ingest_find_tones and gyp_ingest_calibrate then measure the blanked output.  A pulse
+ * that a resampler or down-converter of T taps has smeared over T samples is covered by a guard of T / 2.
+ * gyp_ingest_set_blanker (NULL: off) follows gyp_ingest_set_level: it takes effect with the next block handed out, and what was
+ * uploaded ahead is dropped and read again. */
+int gyp_ingest_set_blanker(gyp_ingest* ing, const gyp_blanker* blanker);
+int gyp_ingest_get_blanker(const gyp_ingest* ing, gyp_blanker* out, int32_t* enabled_out);
+/* Measures output milliseconds [first_ms, first_ms + n_ms) of the handle (inside [0, total_ms), 1 <= n_ms <= 1000) and derives a
+ * blanker.  What is measured is the handle's output WITHOUT blanker, notches and level, read through the handle's own path into
+ * one buffer, so the result does not depend on block_ms.  The centre is the range's mean -- gyp_iq_stats_dev and the m_re, m_im
+ * arithmetic of gyp_iq_level_from_stats, rounded to float32 -- when remove_dc != 0, else 0; then gyp_iq_power_hist_dev about that
+ * centre and gyp_blank_from_hist with threshold_over_median and guard.  With install != 0 the blanker is installed as
+ * gyp_ingest_set_blanker does.  blanker_out / measured_out2 (either may be NULL) receive what gyp_blank_from_hist wrote.  The
+ * cursor is put back, the call synchronises, and blocks handed out earlier are no longer valid afterwards.  On any error the
+ * handle keeps what it had: blanker, notches, level and cursor. */
+int gyp_ingest_find_pulses(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double threshold_over_median, int32_t guard,
+                           int32_t install, gyp_blanker* blanker_out, double* measured_out2);
+/* The blanked samples per millisecond of the block most recently handed out by gyp_ingest_next_dev: min(cap, its n_ms) counts
+ * into counts_out, its n_ms into *n_ms_out (0 before the first block and after a seek).  Zeros while no blanker is on.  The call
+ * waits for that block's upload chain only, not for blocks uploaded ahead and not for the context's stream. */
+int gyp_ingest_last_blanked(gyp_ingest* ing, int32_t* counts_out, int32_t cap, int32_t* n_ms_out);
 
 /* ---------------------------------------------------------------- signal quality: C/N0 and carrier lock -- */
 /* A receiver reports a carrier-to-noise density per tracked satellite.  gyp_track_rec carries the raw prompt peak and the
