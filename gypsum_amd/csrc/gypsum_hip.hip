@@ -22,6 +22,7 @@
 #include "grid_plan.hpp"
 #include "track_plan.hpp"
 #include "acq_plan.hpp"
+#include "cond_plan.hpp"
 #include "dev_mem.hpp"
 
 using namespace gyp;
@@ -170,9 +171,7 @@ struct gyp_ctx {
     int n_xcd = 8;             // hipDeviceAttributeNumberOfXccs (workgroup b is dispatched to XCD b % n_xcd)
     // A/B switches and test hooks: gyp_debug_set / gyp_debug_get by the names in kDebugSwitches below
     bool no_pipe = false;      // A/B switch back to the two-workgroups-per-CU cells kernel
-    int widen_wg_per_cu = 2;      // workgroups per CU of the ingest widen kernel's persistent grid (1..8).  It runs on the
-                                  // upload stream BESIDE the previous block's kernels: with 8 per CU (r02-r05) it took the chip at every launch boundary of the
-                                  // trackers; 2 per CU leave them their slots -- int8-fed / resident 0.934-0.942 -> 0.949-0.953 (profiles/r06zi / r06zj_widen_grid.txt)
+    int widen_wg_per_cu = 2;      // workgroups per CU of the persistent grid of the kernels on the upload stream (1..8; cond_plan.hpp: persistent_cap)
     int resample_tile = 4096;     // "resample_tile_samples": LDS budget of one resample_kernel tile, in input samples (32 KiB: five
                                   // workgroups per CU); same output for any value
     std::vector<std::pair<ResampleDesign, DevBuf<float>>> resample_designs;   // gyp_resample_iq_dev / gyp_ingest_open_resampled: one per (fs_in, fs_out, taps), with the owner of its d_taps
@@ -688,6 +687,22 @@ static int for_rate(gyp_ctx* ctx, F&& f) {
 // a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
 template <typename F>
 static auto for_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+// behind a plain launch: what the runtime made of it
+static int launched(gyp_ctx* ctx) {
+    HIP_TRY(ctx, hipGetLastError());
+    return GYP_OK;
+}
+// The workgroups a launch on the upload stream may take beside the trackers (cond_plan.hpp says why it is capped)
+static int64_t persistent_cap(const gyp_ctx* ctx) { return gyp::persistent_cap(ctx->n_cus, ctx->widen_wg_per_cu); }
+// `count` elements from device memory to the host on the context's stream, which is then synchronised: they are there on return
+template <typename T>
+static int fetch(gyp_ctx* ctx, T* host, const T* dev, size_t count) {
+    HIP_TRY(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GYP_OK;
+}
+template <typename T>
+static int fetch(gyp_ctx* ctx, std::vector<T>& host, const T* dev) { return fetch(ctx, host.data(), dev, host.size()); }
 
 static int launch_cells(gyp_ctx* ctx, const CellsParams& p, int integration) {
     // gyp_debug_set "cells_cu_reserve" n: the correlation-cell launches of this context (acquisition levels, gyp_correlate_cells) size
@@ -1057,8 +1072,7 @@ int gyp_grid_best_bins_refined_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_
     // how many candidates there are decides the size of the per-millisecond sums: one small read-back (the host arrays above are
     // temporaries of the caller anyway: the entry point synchronises like gyp_correlate_grid_dev)
     int32_t counts[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(counts, p.n_cand, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = fetch(ctx, counts, p.n_cand, 2)) return rc;
     ctx->last_grid_refined_rows = counts[1];
     if (counts[0] == 0) return GYP_OK;
     HIP_TRY(ctx, sc.partial64.reserve((size_t)counts[0] * n_ms * 2, Slack::grow, ctx->stream));
@@ -2335,15 +2349,12 @@ static int resample_launch(gyp_ctx* ctx, hipStream_t stream, const ResampleDesig
 // Enqueue ingest_unpack_kernel on `stream` (packed I,Q words at their own rate): the request's in.n samples of every stream.
 static int unpack_launch(gyp_ctx* ctx, hipStream_t stream, const SampleRequest& rq) {
     const PackedFormat& pk = *rq.pk;
-    const int64_t kS = 64 / pk.bits, n_samples = rq.in.n;
-    const int64_t n_items = (n_samples + kS - 1) / kS * rq.out.n_streams;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu));
-    const int32_t vec4 = ((uintptr_t)rq.out.iq & 15u) == 0 && rq.out.stride % 2 == 0;   // every row starts 16-byte aligned
+    const UnpackPlan pl = unpack_plan(persistent_cap(ctx), (uintptr_t)rq.out.iq, rq.out.stride, pk.bits, rq.in.n, rq.out.n_streams);
     const float* levels = nullptr;
     if (const int rc = packed_levels_dev(ctx, pk, &levels)) return rc;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, (const uint8_t*)rq.in.raw, rq.in.stride, rq.in.bit0, n_samples, rq.out.n_streams,
-                           levels, rq.scale, pk.order, (float2*)rq.out.iq, rq.out.stride, vec4);
+        hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(256), 0, stream, (const uint8_t*)rq.in.raw, rq.in.stride, rq.in.bit0, rq.in.n, rq.out.n_streams,
+                           levels, rq.scale, pk.order, (float2*)rq.out.iq, rq.out.stride, pl.vec4);
     };
     switch (pk.bits) {
         case 1: launch(ingest_unpack_kernel<1>); break;
@@ -2498,61 +2509,80 @@ int gyp_resample_packed_dev(gyp_ctx* ctx, const gyp_packing* packing, const void
 // ---------------------------------------------------------------------------------------------------------
 // Level (kernels_level.hpp): per-millisecond statistics, y = (x - dc) * gain
 // ---------------------------------------------------------------------------------------------------------
-// Enqueue iq_stats_kernel on `stream`: one workgroup per (stream, millisecond) item over the widen kernel's persistent grid.
-static int stats_launch(gyp_ctx* ctx, hipStream_t stream, const float* iq, int32_t n_streams, int64_t stride, int32_t n_ms, int32_t n,
-                        float clip_level, gyp_iq_stats* out) {
-    const int64_t n_items = (int64_t)n_streams * n_ms;
-    const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
-    hipLaunchKernelGGL(iq_stats_kernel, dim3(grid), dim3(256), 0, stream, iq, stride, n_ms, n, n_items, clip_level, out);
-    HIP_TRY(ctx, hipGetLastError());
+// One call of a conditioning stage, by name.  A stage that only measures leaves `out` null; the level and histogram stages take a
+// count of samples in place of n_ms x n.
+struct IqWindow {
+    const float* in;        // stream 0's complex64 samples
+    float* out;             // where a stage that writes samples puts them (may be `in`); strided like `in`
+    int32_t n_streams;
+    int64_t stride;         // between streams, in samples
+    int32_t n_ms, n;        // n_ms milliseconds of n samples
+    int64_t first_index;    // the absolute index of the window's first sample: the phase reference of the tone stages
+    hipStream_t stream;
+    const float2* src(int32_t s0) const { return reinterpret_cast<const float2*>(in) + s0 * stride; }   // stream s0's row
+    float2* dst(int32_t s0) const { return reinterpret_cast<float2*>(out) + s0 * stride; }
+};
+
+// The launches of a plan in order: launch(chunk) fills the chunk's argument struct and enqueues it.  The first error ends the walk.
+template <class Launch>
+static int for_each_chunk(const StagePlan& pl, Launch&& launch) {
+    for (int32_t i = 0; i < pl.n_chunks; ++i)
+        if (const int rc = launch(stage_chunk(pl, i))) return rc;
     return GYP_OK;
 }
+// The refusals' common forms: "<who>: <why>", and rows of `extent` samples that would overlap at this stride
+static int refuse(gyp_ctx* ctx, const char* who, const std::string& why) { return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why); }
+static bool rows_overlap(int32_t n_streams, int64_t stride, int64_t extent) { return n_streams > 1 && stride < extent; }
 
-// Enqueue iq_condition_kernel on `stream`, kLevelStreams streams per launch (their levels are a kernel argument); the launches of
-// a call share the persistent grid's workgroups among their streams.
-static int condition_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride,
-                            int64_t n_samples, const gyp_iq_level* levels) {
-    const bool rows16 = n_streams == 1 || stride % 2 == 0;   // every row starts 16-byte aligned if the first one does
-    const int32_t vec4 = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0 && rows16;
-    const int64_t n_vec = vec4 ? (n_samples + 1) / 2 : n_samples;
-    for (int32_t s0 = 0; s0 < n_streams; s0 += kLevelStreams) {
-        const int32_t ns = std::min<int32_t>(kLevelStreams, n_streams - s0);
+// Enqueue iq_stats_kernel: one record per (stream, millisecond) of the window into `out`.
+static int stats_launch(gyp_ctx* ctx, const IqWindow& w, float clip_level, gyp_iq_stats* out) {
+    const StageChunk c = stage_chunk(stats_plan(persistent_cap(ctx), w.n_streams, w.n_ms), 0);
+    hipLaunchKernelGGL(iq_stats_kernel, dim3(c.grid_x), dim3(256), 0, w.stream, w.in, w.stride, w.n_ms, w.n, c.items, clip_level, out);
+    return launched(ctx);
+}
+
+// Enqueue iq_condition_kernel over the first n_samples samples of every stream; unused slots of a launch's levels repeat its last one.
+static int condition_launch(gyp_ctx* ctx, const IqWindow& w, int64_t n_samples, const gyp_iq_level* levels) {
+    const StagePlan pl = condition_plan(persistent_cap(ctx), kLevelStreams, (uintptr_t)w.in, (uintptr_t)w.out, w.n_streams, w.stride, n_samples);
+    return for_each_chunk(pl, [&](const StageChunk& c) {
         LevelArgs a{};
-        for (int32_t i = 0; i < kLevelStreams; ++i) a.v[i] = levels[s0 + std::min(i, ns - 1)];
-        const int64_t cap = std::max<int64_t>(1, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu / ns);
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_vec + 255) / 256, cap));
-        hipLaunchKernelGGL(iq_condition_kernel, dim3(grid, ns), dim3(256), 0, stream, in + 2 * s0 * stride, out + 2 * s0 * stride, stride,
-                           n_samples, a, vec4);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return GYP_OK;
+        for (int32_t i = 0; i < kLevelStreams; ++i) a.v[i] = levels[c.s0 + std::min(i, c.ns - 1)];
+        hipLaunchKernelGGL(iq_condition_kernel, dim3(c.grid_x, c.grid_y), dim3(256), 0, w.stream, w.in + 2 * c.s0 * w.stride,
+                           w.out + 2 * c.s0 * w.stride, w.stride, n_samples, a, pl.vec4);
+        return launched(ctx);
+    });
 }
 
 extern "C" {
 
 int gyp_iq_stats_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
                      int32_t samples_per_ms, float clip_level, gyp_iq_stats* out_dev) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_stats_dev: ctx is NULL");
-    if (!iq_dev || !out_dev) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: iq_dev and out_dev must not be NULL");
-    if (n_streams < 1 || n_ms < 1 || samples_per_ms < 1)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: n_streams, n_ms and samples_per_ms must be >= 1");
-    if (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_stats_dev: stream_stride_samples must be >= n_ms * samples_per_ms");
+    const char* who = "gyp_iq_stats_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!iq_dev || !out_dev) return refuse(ctx, who, "iq_dev and out_dev must not be NULL");
+    if (n_streams < 1 || n_ms < 1 || samples_per_ms < 1) return refuse(ctx, who, "n_streams, n_ms and samples_per_ms must be >= 1");
+    if (rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
+        return refuse(ctx, who, "stream_stride_samples must be >= n_ms * samples_per_ms");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return stats_launch(ctx, ctx->stream, iq_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, clip_level, out_dev);
+    IqWindow w{};
+    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms, w.stream = ctx->stream;
+    return stats_launch(ctx, w, clip_level, out_dev);
 }
 
 int gyp_condition_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
                          int64_t n_samples, const gyp_iq_level* levels_host) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_condition_iq_dev: ctx is NULL");
-    if (!in_dev || !out_dev || !levels_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_condition_iq_dev: in_dev, out_dev and levels_host must not be NULL");
-    if (n_streams < 1 || n_samples < 0 || (n_streams > 1 && stream_stride_samples < n_samples))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_condition_iq_dev: bad arguments (n_streams >= 1, n_samples >= 0, stream_stride_samples >= n_samples)");
+    const char* who = "gyp_condition_iq_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!in_dev || !out_dev || !levels_host) return refuse(ctx, who, "in_dev, out_dev and levels_host must not be NULL");
+    if (n_streams < 1 || n_samples < 0 || rows_overlap(n_streams, stream_stride_samples, n_samples))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_samples >= 0, stream_stride_samples >= n_samples)");
     for (int32_t s = 0; s < n_streams; ++s)
-        if (const char* why = level_check(&levels_host[s])) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_condition_iq_dev: ") + why);
+        if (const char* why = level_check(&levels_host[s])) return refuse(ctx, who, why);
     if (n_samples == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return condition_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, n_samples, levels_host);
+    IqWindow w{};
+    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.stream = ctx->stream;
+    return condition_launch(ctx, w, n_samples, levels_host);
 }
 
 int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms, int32_t remove_dc, double target_rms,
@@ -2577,15 +2607,13 @@ static ToneMix tone_mix(int64_t fs_hz) {
     return ToneMix{m.fs, m.q_scale, m.y_scale};
 }
 
-// Enqueue iq_tones_kernel on the context's stream for frequencies already in device memory (f mod fs each).
-static int tones_launch(gyp_ctx* ctx, const float* iq, int32_t n_streams, int64_t stride, int64_t first_index, int32_t n_blocks,
-                        int32_t block_samples, int64_t fs_hz, const int64_t* freqs_dev, int32_t n_freq, int32_t window, gyp_tone_rec* out) {
-    const int64_t n_items = (int64_t)n_streams * n_blocks * n_freq;
-    const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * 8);
-    hipLaunchKernelGGL(iq_tones_kernel, dim3(grid), dim3(256), 0, ctx->stream, reinterpret_cast<const float2*>(iq), stride, first_index,
-                       n_blocks, block_samples, freqs_dev, n_freq, tone_mix(fs_hz), window, n_items, out);
-    HIP_TRY(ctx, hipGetLastError());
-    return GYP_OK;
+// Enqueue iq_tones_kernel for the n_freq frequencies the context's table holds (tones_upload_freqs): one record per (stream, block,
+// frequency) of the window, whose n_ms x n are blocks x samples here, into `out`.
+static int tones_launch(gyp_ctx* ctx, const IqWindow& w, int64_t fs_hz, int32_t n_freq, int32_t window, gyp_tone_rec* out) {
+    const StageChunk c = stage_chunk(tones_plan(ctx->n_cus, w.n_streams, w.n_ms, n_freq), 0);
+    hipLaunchKernelGGL(iq_tones_kernel, dim3(c.grid_x), dim3(256), 0, w.stream, w.src(0), w.stride, w.first_index, w.n_ms, w.n,
+                       ctx->tone_freqs.get(), n_freq, tone_mix(fs_hz), window, c.items, out);
+    return launched(ctx);
 }
 
 // The call's frequencies as f mod fs in the context's table.  Waits for the copy: the host array is the caller's.
@@ -2597,30 +2625,20 @@ static int tones_upload_freqs(gyp_ctx* ctx, const int64_t* freqs_hz, int32_t n_f
     return GYP_OK;
 }
 
-// Enqueue iq_notch_kernel on `stream`, kNotchStreams streams per launch (their tone lists are a kernel argument): one workgroup per
-// (stream, millisecond) over the widen kernel's persistent grid.  The lists have passed notch_check.
-static int notch_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride, int64_t first_index,
-                        int32_t n_ms, int32_t n, int64_t fs_hz, const gyp_notch_tones* tones) {
-    const bool lds = n <= kNotchLdsSamples && !ctx->notch_no_lds;
-    const size_t lds_bytes = lds ? (size_t)n * sizeof(float2) : 0;
-    for (int32_t s0 = 0; s0 < n_streams; s0 += kNotchStreams) {
-        const int32_t ns = std::min<int32_t>(kNotchStreams, n_streams - s0);
+// Enqueue iq_notch_kernel for tone lists that have passed notch_check; unused slots of a launch's lists stay empty.
+static int notch_launch(gyp_ctx* ctx, const IqWindow& w, int64_t fs_hz, const gyp_notch_tones* tones) {
+    const StagePlan pl = notch_plan(persistent_cap(ctx), kNotchStreams, w.n_streams, w.n_ms, w.n, kNotchLdsSamples, ctx->notch_no_lds);
+    return for_each_chunk(pl, [&](const StageChunk& c) {
         NotchArgs a{};
-        for (int32_t i = 0; i < ns; ++i) {
-            a.count[i] = tones[s0 + i].count;
-            for (int32_t k = 0; k < a.count[i]; ++k) a.f[i][k] = tone_mod(tones[s0 + i].freq_hz[k], fs_hz);
+        for (int32_t i = 0; i < c.ns; ++i) {
+            a.count[i] = tones[c.s0 + i].count;
+            for (int32_t k = 0; k < a.count[i]; ++k) a.f[i][k] = tone_mod(tones[c.s0 + i].freq_hz[k], fs_hz);
         }
-        const int64_t n_items = (int64_t)ns * n_ms;
-        const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
-        const float2* src = reinterpret_cast<const float2*>(in) + s0 * stride;
-        float2* dst = reinterpret_cast<float2*>(out) + s0 * stride;
-        const int rc = lds ? launch_dyn(ctx, iq_notch_kernel<true>, dim3(grid), dim3(kNotchThreads), lds_bytes, stream, src, dst, stride,
-                                        first_index, n_ms, n, n_items, tone_mix(fs_hz), a)
-                           : launch_dyn(ctx, iq_notch_kernel<false>, dim3(grid), dim3(kNotchThreads), 0, stream, src, dst, stride,
-                                        first_index, n_ms, n, n_items, tone_mix(fs_hz), a);
-        if (rc) return rc;
-    }
-    return GYP_OK;
+        return for_flag(pl.lds_bytes > 0, [&](auto lds) {
+            return launch_dyn(ctx, iq_notch_kernel<decltype(lds)::value>, dim3(c.grid_x), dim3(kNotchThreads), (size_t)pl.lds_bytes, w.stream,
+                              w.src(c.s0), w.dst(c.s0), w.stride, w.first_index, w.n_ms, w.n, c.items, tone_mix(fs_hz), a);
+        });
+    });
 }
 
 extern "C" {
@@ -2628,44 +2646,47 @@ extern "C" {
 int gyp_iq_tones_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_sample_index,
                      int32_t n_blocks, int32_t block_samples, int64_t fs_hz, const int64_t* freqs_hz_host, int32_t n_freq, int32_t window,
                      gyp_tone_rec* out_dev) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_tones_dev: ctx is NULL");
-    if (!iq_dev || !out_dev || !freqs_hz_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: iq_dev, freqs_hz_host and out_dev must not be NULL");
+    const char* who = "gyp_iq_tones_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!iq_dev || !out_dev || !freqs_hz_host) return refuse(ctx, who, "iq_dev, freqs_hz_host and out_dev must not be NULL");
     if (n_streams < 1 || n_blocks < 1 || block_samples < 1 || n_freq < 1 || first_sample_index < 0)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: n_streams, n_blocks, block_samples and n_freq must be >= 1, first_sample_index >= 0");
-    if (n_streams > 1 && stream_stride_samples < (int64_t)n_blocks * block_samples)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: stream_stride_samples must be >= n_blocks * block_samples");
-    if (!tone_rate_ok(fs_hz)) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: fs_hz must lie in [1000, 2^31)");
-    if (window != GYP_WINDOW_RECT && window != GYP_WINDOW_HANN)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: window must be GYP_WINDOW_RECT or GYP_WINDOW_HANN");
+        return refuse(ctx, who, "n_streams, n_blocks, block_samples and n_freq must be >= 1, first_sample_index >= 0");
+    if (rows_overlap(n_streams, stream_stride_samples, (int64_t)n_blocks * block_samples))
+        return refuse(ctx, who, "stream_stride_samples must be >= n_blocks * block_samples");
+    if (!tone_rate_ok(fs_hz)) return refuse(ctx, who, "fs_hz must lie in [1000, 2^31)");
+    if (window != GYP_WINDOW_RECT && window != GYP_WINDOW_HANN) return refuse(ctx, who, "window must be GYP_WINDOW_RECT or GYP_WINDOW_HANN");
     for (int32_t k = 0; k < n_freq; ++k) {
         const int64_t f = freqs_hz_host[k];
-        if (f <= -fs_hz || f >= fs_hz || 2 * (f < 0 ? -f : f) >= fs_hz)
-            return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_tones_dev: every frequency must satisfy |f| < fs / 2");
+        if (f <= -fs_hz || f >= fs_hz || 2 * (f < 0 ? -f : f) >= fs_hz) return refuse(ctx, who, "every frequency must satisfy |f| < fs / 2");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (const int rc = tones_upload_freqs(ctx, freqs_hz_host, n_freq, fs_hz)) return rc;
-    return tones_launch(ctx, iq_dev, n_streams, stream_stride_samples, first_sample_index, n_blocks, block_samples, fs_hz,
-                        ctx->tone_freqs.get(), n_freq, window, out_dev);
+    IqWindow w{};
+    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_blocks, w.n = block_samples;
+    w.first_index = first_sample_index, w.stream = ctx->stream;
+    return tones_launch(ctx, w, fs_hz, n_freq, window, out_dev);
 }
 
 int gyp_notch_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
                      int64_t first_sample_index, int32_t n_ms, int32_t samples_per_ms, int64_t fs_hz, const gyp_notch_tones* tones_host) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_notch_iq_dev: ctx is NULL");
-    if (!in_dev || !out_dev || !tones_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: in_dev, out_dev and tones_host must not be NULL");
+    const char* who = "gyp_notch_iq_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!in_dev || !out_dev || !tones_host) return refuse(ctx, who, "in_dev, out_dev and tones_host must not be NULL");
     if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || first_sample_index < 0 ||
-        (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, samples_per_ms >= 1, first_sample_index >= 0, "
-                                        "stream_stride_samples >= n_ms * samples_per_ms)");
-    if (!tone_rate_ok(fs_hz)) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: fs_hz must lie in [1000, 2^31)");
+        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 0, samples_per_ms >= 1, first_sample_index >= 0, "
+                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    if (!tone_rate_ok(fs_hz)) return refuse(ctx, who, "fs_hz must lie in [1000, 2^31)");
     for (int32_t s = 0; s < n_streams; ++s) {
-        if (tones_host[s].reserved != 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_notch_iq_dev: tones.reserved must be 0");
-        if (const char* why = notch_check(tones_host[s].freq_hz, tones_host[s].count, fs_hz))
-            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_notch_iq_dev: ") + why);
+        if (tones_host[s].reserved != 0) return refuse(ctx, who, "tones.reserved must be 0");
+        if (const char* why = notch_check(tones_host[s].freq_hz, tones_host[s].count, fs_hz)) return refuse(ctx, who, why);
     }
     if (n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return notch_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, first_sample_index, n_ms, samples_per_ms, fs_hz,
-                        tones_host);
+    IqWindow w{};
+    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
+    w.first_index = first_sample_index, w.stream = ctx->stream;
+    return notch_launch(ctx, w, fs_hz, tones_host);
 }
 
 int gyp_tones_find(const double* power, int32_t n_freq, double freq_step_hz, double threshold_over_median, int32_t min_separation_bins,
@@ -2707,51 +2728,46 @@ static const char* quality_check(const void* recs, int32_t n_chan, int64_t chan_
     return nullptr;
 }
 
-// Enqueue track_quality_kernel on the context's stream, kQualityChans channels per launch (their bit offsets are a kernel
-// argument): one wavefront per (channel, window).  The arguments have passed quality_check.
+// Enqueue track_quality_kernel on the context's stream for arguments that have passed quality_check; unused slots of a launch's
+// bit offsets, and every slot without offsets, are -1.
 static int quality_launch(gyp_ctx* ctx, const gyp_track_rec* recs, int32_t n_chan, int64_t stride, int32_t n_ms, int32_t window_ms,
                           const int32_t* bit_offset, gyp_quality_sums* out) {
-    const int32_t n_win = (int32_t)(((int64_t)n_ms + window_ms - 1) / window_ms);
-    for (int32_t c0 = 0; c0 < n_chan; c0 += kQualityChans) {
-        const int32_t nc = std::min<int32_t>(kQualityChans, n_chan - c0);
+    const StagePlan pl = quality_plan(ctx->n_cus, kQualityChans, n_chan, n_ms, window_ms);
+    const int32_t n_win = (int32_t)pl.per_stream;
+    return for_each_chunk(pl, [&](const StageChunk& c) {
         QualityArgs a;
-        for (int32_t i = 0; i < kQualityChans; ++i) a.bit_offset[i] = (int8_t)(bit_offset && i < nc ? bit_offset[c0 + i] : -1);
-        const int64_t n_items = (int64_t)nc * n_win;
-        const int grid = (int)std::min<int64_t>((n_items + 3) / 4, (int64_t)ctx->n_cus * 64);
-        hipLaunchKernelGGL(track_quality_kernel, dim3(grid), dim3(256), 0, ctx->stream, recs + (int64_t)c0 * stride, stride, n_ms, window_ms,
-                           n_win, n_items, a, out + (int64_t)c0 * n_win);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return GYP_OK;
+        for (int32_t i = 0; i < kQualityChans; ++i) a.bit_offset[i] = (int8_t)(bit_offset && i < c.ns ? bit_offset[c.s0 + i] : -1);
+        hipLaunchKernelGGL(track_quality_kernel, dim3(c.grid_x), dim3(256), 0, ctx->stream, recs + (int64_t)c.s0 * stride, stride, n_ms,
+                           window_ms, n_win, c.items, a, out + (int64_t)c.s0 * n_win);
+        return launched(ctx);
+    });
 }
 
 extern "C" {
 
 int gyp_track_quality_dev(gyp_ctx* ctx, const gyp_track_rec* recs_dev, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
                           int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_dev) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_track_quality_dev: ctx is NULL");
-    if (const char* why = quality_check(recs_dev, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_dev))
-        return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_track_quality_dev: ") + why);
+    const char* who = "gyp_track_quality_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (const char* why = quality_check(recs_dev, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_dev)) return refuse(ctx, who, why);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return quality_launch(ctx, recs_dev, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_dev);
 }
 
 int gyp_track_quality(gyp_ctx* ctx, const gyp_track_rec* recs_host, int32_t n_chan, int64_t chan_stride_recs, int32_t n_ms,
                       int32_t window_ms, const int32_t* bit_offset_host, gyp_quality_sums* out_host) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_track_quality: ctx is NULL");
-    if (const char* why = quality_check(recs_host, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_host))
-        return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_track_quality: ") + why);
+    const char* who = "gyp_track_quality";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (const char* why = quality_check(recs_host, n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, out_host)) return refuse(ctx, who, why);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Scratch& sc = ctx->scratch;
     const size_t n_recs = (size_t)(n_chan - 1) * (size_t)chan_stride_recs + (size_t)n_ms;
-    const size_t n_out = (size_t)n_chan * (size_t)(((int64_t)n_ms + window_ms - 1) / window_ms);
+    const size_t n_out = (size_t)n_chan * (size_t)quality_windows(n_ms, window_ms);
     HIP_TRY(ctx, upload(sc.quality_recs, recs_host, n_recs, ctx->stream));
     HIP_TRY(ctx, sc.quality_sums.reserve(n_out, Slack::grow, ctx->stream));
     if (const int rc = quality_launch(ctx, sc.quality_recs.get(), n_chan, chan_stride_recs, n_ms, window_ms, bit_offset_host, sc.quality_sums.get()))
         return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, sc.quality_sums.get(), n_out * sizeof(gyp_quality_sums), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GYP_OK;
+    return fetch(ctx, out_host, sc.quality_sums.get(), n_out);
 }
 
 int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* out) {
@@ -2766,74 +2782,70 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
 // ---------------------------------------------------------------------------------------------------------
 // Blanker (kernels_blank.hpp): per-millisecond pulse blanking, the power histogram its threshold comes from
 // ---------------------------------------------------------------------------------------------------------
-// Enqueue iq_blank_kernel on `stream`, kBlankStreams streams per launch (their blankers are a kernel argument): one workgroup per
-// (stream, millisecond) over the widen kernel's persistent grid.  The blankers have passed blanker_check; counts may be null.
-static int blank_launch(gyp_ctx* ctx, hipStream_t stream, const float* in, float* out, int32_t n_streams, int64_t stride, int32_t n_ms,
-                        int32_t n, const gyp_blanker* blankers, int32_t* counts) {
-    for (int32_t s0 = 0; s0 < n_streams; s0 += kBlankStreams) {
-        const int32_t ns = std::min<int32_t>(kBlankStreams, n_streams - s0);
+// Enqueue iq_blank_kernel for blankers that have passed blanker_check; unused slots of a launch's blankers repeat its last one.
+// counts (may be null): one int32 per (stream, millisecond).  In place only the blanked samples are stored.
+static int blank_launch(gyp_ctx* ctx, const IqWindow& w, const gyp_blanker* blankers, int32_t* counts) {
+    const StagePlan pl = blank_plan(persistent_cap(ctx), kBlankStreams, w.n_streams, w.n_ms);
+    return for_each_chunk(pl, [&](const StageChunk& c) {
         BlankArgs a{};
-        for (int32_t i = 0; i < kBlankStreams; ++i) a.v[i] = blankers[s0 + std::min(i, ns - 1)];
-        const int64_t n_items = (int64_t)ns * n_ms;
-        const int grid = (int)std::min<int64_t>(n_items, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu);
-        const float2* src = reinterpret_cast<const float2*>(in) + s0 * stride;
-        float2* dst = reinterpret_cast<float2*>(out) + s0 * stride;
-        int32_t* cnt = counts ? counts + (int64_t)s0 * n_ms : nullptr;
-        if (in == out)   // in place: only blanked samples are stored
-            hipLaunchKernelGGL(iq_blank_kernel<false>, dim3(grid), dim3(kBlankThreads), 0, stream, src, dst, stride, n_ms, n, n_items, a, cnt);
-        else
-            hipLaunchKernelGGL(iq_blank_kernel<true>, dim3(grid), dim3(kBlankThreads), 0, stream, src, dst, stride, n_ms, n, n_items, a, cnt);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return GYP_OK;
+        for (int32_t i = 0; i < kBlankStreams; ++i) a.v[i] = blankers[c.s0 + std::min(i, c.ns - 1)];
+        int32_t* cnt = counts ? counts + (int64_t)c.s0 * w.n_ms : nullptr;
+        for_flag(w.in == w.out, [&](auto in_place) {   // the kernel's flag is `copy`
+            hipLaunchKernelGGL(iq_blank_kernel<!decltype(in_place)::value>, dim3(c.grid_x), dim3(kBlankThreads), 0, w.stream, w.src(c.s0), w.dst(c.s0),
+                               w.stride, w.n_ms, w.n, c.items, a, cnt);
+        });
+        return launched(ctx);
+    });
 }
 
-// Zero the histograms and enqueue iq_power_hist_kernel on `stream`, kBlankStreams streams per launch; the launches of a call share
-// the persistent grid's workgroups among their streams.  centres: 2 floats per stream, or null for 0.
-static int hist_launch(gyp_ctx* ctx, hipStream_t stream, const float* iq, int32_t n_streams, int64_t stride, int64_t n_samples,
-                       const float* centres, uint32_t* hist) {
-    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)n_streams * GYP_POWER_HIST_BINS * sizeof(uint32_t), stream));
-    for (int32_t s0 = 0; s0 < n_streams; s0 += kBlankStreams) {
-        const int32_t ns = std::min<int32_t>(kBlankStreams, n_streams - s0);
+// Zero the histograms and enqueue iq_power_hist_kernel over the first n_samples samples of every stream.  centres: 2 floats per
+// stream, or null for 0; unused slots of a launch's centres stay zero.
+static int hist_launch(gyp_ctx* ctx, const IqWindow& w, int64_t n_samples, const float* centres, uint32_t* hist) {
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)w.n_streams * GYP_POWER_HIST_BINS * sizeof(uint32_t), w.stream));
+    return for_each_chunk(hist_plan(persistent_cap(ctx), kBlankStreams, w.n_streams, n_samples), [&](const StageChunk& c) {
         HistArgs a{};
-        for (int32_t i = 0; i < ns; ++i) a.c[i] = centres ? make_float2(centres[2 * (s0 + i)], centres[2 * (s0 + i) + 1]) : make_float2(0.f, 0.f);
-        const int64_t cap = std::max<int64_t>(1, (int64_t)ctx->n_cus * ctx->widen_wg_per_cu / ns);
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_samples / 2 + 255) / 256, cap));
-        hipLaunchKernelGGL(iq_power_hist_kernel, dim3(grid, ns), dim3(256), 0, stream, reinterpret_cast<const float2*>(iq) + s0 * stride, stride,
-                           n_samples, a, hist + (int64_t)s0 * GYP_POWER_HIST_BINS);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return GYP_OK;
+        for (int32_t i = 0; i < c.ns; ++i) a.c[i] = centres ? make_float2(centres[2 * (c.s0 + i)], centres[2 * (c.s0 + i) + 1]) : make_float2(0.f, 0.f);
+        hipLaunchKernelGGL(iq_power_hist_kernel, dim3(c.grid_x, c.grid_y), dim3(256), 0, w.stream, w.src(c.s0), w.stride, n_samples, a,
+                           hist + (int64_t)c.s0 * GYP_POWER_HIST_BINS);
+        return launched(ctx);
+    });
 }
 
 extern "C" {
 
 int gyp_blank_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
                      int32_t samples_per_ms, const gyp_blanker* blankers_host, int32_t* counts_out_dev) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_blank_iq_dev: ctx is NULL");
-    if (!in_dev || !out_dev || !blankers_host) return fail(ctx, GYP_E_BAD_ARG, "gyp_blank_iq_dev: in_dev, out_dev and blankers_host must not be NULL");
+    const char* who = "gyp_blank_iq_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!in_dev || !out_dev || !blankers_host) return refuse(ctx, who, "in_dev, out_dev and blankers_host must not be NULL");
     if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || samples_per_ms > kBlankMaxSamples ||
-        (n_streams > 1 && stream_stride_samples < (int64_t)n_ms * samples_per_ms))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_blank_iq_dev: bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
-                                        "stream_stride_samples >= n_ms * samples_per_ms)");
+        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
+                                "stream_stride_samples >= n_ms * samples_per_ms)");
     for (int32_t s = 0; s < n_streams; ++s)
-        if (const char* why = blanker_check(&blankers_host[s])) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_blank_iq_dev: ") + why);
+        if (const char* why = blanker_check(&blankers_host[s])) return refuse(ctx, who, why);
     if (n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return blank_launch(ctx, ctx->stream, in_dev, out_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, blankers_host, counts_out_dev);
+    IqWindow w{};
+    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
+    w.stream = ctx->stream;
+    return blank_launch(ctx, w, blankers_host, counts_out_dev);
 }
 
 int gyp_iq_power_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t n_samples,
                           const float* centers_host, uint32_t* hist_out_dev) {
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: ctx is NULL");
-    if (!iq_dev || !hist_out_dev) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: iq_dev and hist_out_dev must not be NULL");
-    if (n_streams < 1 || n_samples < 1 || (n_streams > 1 && stream_stride_samples < n_samples))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: bad arguments (n_streams >= 1, n_samples >= 1, stream_stride_samples >= n_samples)");
+    const char* who = "gyp_iq_power_hist_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!iq_dev || !hist_out_dev) return refuse(ctx, who, "iq_dev and hist_out_dev must not be NULL");
+    if (n_streams < 1 || n_samples < 1 || rows_overlap(n_streams, stream_stride_samples, n_samples))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_samples >= 1, stream_stride_samples >= n_samples)");
     if (centers_host)
         for (int32_t i = 0; i < 2 * n_streams; ++i)
-            if (!std::isfinite(centers_host[i])) return fail(ctx, GYP_E_BAD_ARG, "gyp_iq_power_hist_dev: every centre must be finite");
+            if (!std::isfinite(centers_host[i])) return refuse(ctx, who, "every centre must be finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return hist_launch(ctx, ctx->stream, iq_dev, n_streams, stream_stride_samples, n_samples, centers_host, hist_out_dev);
+    IqWindow w{};
+    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.stream = ctx->stream;
+    return hist_launch(ctx, w, n_samples, centers_host, hist_out_dev);
 }
 
 int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
@@ -2862,7 +2874,7 @@ static void ingest_free(gyp_ingest* g) {
 
 // Enqueue ingest_widen_kernel on `stream`: n_words int8, uint8 or int16 words (fmt) -> float32 * scale
 static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, const void* raw, size_t n_words, float scale, float* out) {
-    const dim3 grid((unsigned)std::min<size_t>((n_words / 16 + 255) / 256 + 1, (size_t)ctx->n_cus * ctx->widen_wg_per_cu));
+    const dim3 grid(grid_widen(n_words, persistent_cap(ctx)));
     switch (fmt) {
         case kFmtI8: hipLaunchKernelGGL(ingest_widen_kernel<int8_t>, grid, dim3(256), 0, stream, (const int8_t*)raw, out, n_words, scale); break;
         case kFmtU8: hipLaunchKernelGGL(ingest_widen_kernel<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t*)raw, out, n_words, scale); break;
@@ -2872,18 +2884,17 @@ static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, co
 
 // A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
 static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms) {
-    const int32_t n = g->src.n;
-    g->slot_blanked[d] = g->cond.blank_on ? 1 : 0;
-    if (g->cond.blank_on)   // chain order: producer -> blanker -> notches -> level
-        if (const int rc = blank_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, n_ms, n, &g->cond.blanker,
-                                        g->dev_blanked[d].get()))
-            return rc;
-    if (g->cond.notches.count > 0)
-        if (const int rc = notch_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, first_ms * n, n_ms, n,
-                                        g->fs, &g->cond.notches))
-            return rc;
-    if (!g->cond.level_on) return GYP_OK;
-    return condition_launch(g->ctx, g->copy_stream.get(), g->dev_iq[d].get(), g->dev_iq[d].get(), 1, 0, (int64_t)n_ms * n, &g->cond.level);
+    const Conditioning& cond = g->cond;
+    IqWindow w{};
+    w.in = w.out = g->dev_iq[d].get();
+    w.n_streams = 1, w.n_ms = n_ms, w.n = g->src.n, w.first_index = first_ms * w.n, w.stream = g->copy_stream.get();
+    g->slot_blanked[d] = cond.blank_on ? 1 : 0;
+    if (cond.blank_on)   // chain order: producer -> blanker -> notches -> level
+        if (const int rc = blank_launch(g->ctx, w, &cond.blanker, g->dev_blanked[d].get())) return rc;
+    if (cond.notches.count > 0)
+        if (const int rc = notch_launch(g->ctx, w, g->fs, &cond.notches)) return rc;
+    if (!cond.level_on) return GYP_OK;
+    return condition_launch(g->ctx, w, (int64_t)n_ms * w.n, &cond.level);
 }
 
 // The producer of a block, on the copy stream: file-width words in `raw` (the span's slot) -> complex64 in the output slot `iq`.
@@ -3040,9 +3051,7 @@ static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, S
     const Conditioning before = g->cond;
     const int64_t back_to = g->consumer_ms;
     Conditioning next = before;
-    g->cond.level_on = false;
-    if (suspend != Suspend::level) g->cond.notches = gyp_notch_tones{};
-    if (suspend == Suspend::all) g->cond.blank_on = false;
+    g->cond = before.without(suspend);
     auto measure = [&]() -> int {
         if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
         for (int32_t done = 0; done < n_ms;) {
@@ -3064,6 +3073,129 @@ static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, S
     g->cond = rc == GYP_OK ? next : before;
     const int rc_back = gyp_ingest_seek(g, back_to);
     return rc ? fail(ctx, rc, why) : rc_back;
+}
+
+// What the entry points that need the handle's device side open with: `what` says, in the refusal, why this one needs it.
+static int ingest_device_handle(const gyp_ingest* g, const char* who, const char* what, gyp_ctx** ctx) {
+    if (!g) return refuse(nullptr, who, "handle is NULL");
+    if (!g->ctx) return refuse(nullptr, who, std::string("the handle was opened without a context (") + what + ")");
+    *ctx = g->ctx;
+    return GYP_OK;
+}
+static const char* const kBlankTooWide = "the blanker takes at most 65536 samples per millisecond";
+// A measurement's range: whole milliseconds inside the recording, at most max_ms of them.
+static int ingest_range_check(const gyp_ingest* g, const char* who, int64_t first_ms, int32_t n_ms, int32_t max_ms) {
+    if (n_ms < 1 || n_ms > max_ms || first_ms < 0 || first_ms > g->total_ms - n_ms)
+        return refuse(g->ctx, who, "[first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= " + std::to_string(max_ms));
+    return GYP_OK;
+}
+// A changed conditioning applies from the next block handed out: what was uploaded ahead carries the old one, so it is dropped and
+// read again.
+static int ingest_recondition(gyp_ingest* g) { return gyp_ingest_seek(g, g->consumer_ms); }
+// ingest_measure_range's per_block of a measurement that wants its range in one buffer: the block's `take` milliseconds go to
+// millisecond `done` of `all`.
+static int ingest_gather(const gyp_ingest* g, float* all, const float* iq, int32_t done, int32_t take) {
+    const size_t n = (size_t)g->src.n;
+    HIP_TRY(g->ctx, hipMemcpyAsync(all + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, g->ctx->stream));
+    return GYP_OK;
+}
+// One stream of n_ms milliseconds at `iq`, as the measurements on the context's stream take it
+static IqWindow ingest_window(const gyp_ingest* g, const float* iq, int32_t n_ms, int64_t first_ms) {
+    IqWindow w{};
+    w.in = iq, w.n_streams = 1, w.n_ms = n_ms, w.n = g->src.n, w.first_index = first_ms * w.n, w.stream = g->ctx->stream;
+    return w;
+}
+
+// gyp_ingest_find_tones over the gathered range: what is searched, the device buffers, the records last measured, what was found.
+struct ToneSearch {
+    const gyp_ingest* g;
+    int64_t first_ms;
+    int32_t n_ms;
+    double threshold;
+    int32_t max_tones;
+    DevBuf<float> iq_all;             // the range's samples
+    DevBuf<gyp_tone_rec> recs_dev;
+    std::vector<gyp_tone_rec> recs;   // block-major
+    std::vector<int64_t> found;
+    std::vector<double> found_db;
+    int64_t total() const { return (int64_t)n_ms * g->src.n; }
+    int32_t n_scan() const { return (int32_t)(total() / kScanBlock); }
+    int32_t n_fine() const { return (int32_t)(total() / kScanFine); }
+};
+constexpr int32_t kScanGrid = 2 * kScanHalf + 1;
+
+// records of `freqs` over n_blocks blocks of block_samples samples of the gathered range, block-major, in ts.recs
+static int tone_measure(ToneSearch& ts, const std::vector<int64_t>& freqs, int32_t n_blocks, int32_t block_samples, int32_t window) {
+    gyp_ctx* ctx = ts.g->ctx;
+    if (const int rc = tones_upload_freqs(ctx, freqs.data(), (int32_t)freqs.size(), ts.g->fs)) return rc;
+    IqWindow w = ingest_window(ts.g, ts.iq_all.get(), n_blocks, ts.first_ms);
+    w.n = block_samples;
+    if (const int rc = tones_launch(ctx, w, ts.g->fs, (int32_t)freqs.size(), window, ts.recs_dev.get())) return rc;
+    ts.recs.resize((size_t)n_blocks * freqs.size());
+    return fetch(ctx, ts.recs, ts.recs_dev.get());
+}
+// one refinement step of every tone found: the phase slope over blocks of block_samples samples, rounded to whole Hz
+static int tone_refine_found(ToneSearch& ts, int32_t n_blocks, int32_t block_samples, int32_t window) {
+    const int64_t fs = ts.g->fs;
+    std::vector<int64_t>& found = ts.found;
+    if (const int rc = tone_measure(ts, found, n_blocks, block_samples, window)) return rc;
+    std::vector<gyp_tone_rec> col((size_t)n_blocks);
+    for (size_t t = 0; t < found.size(); ++t) {
+        for (int32_t b = 0; b < n_blocks; ++b) col[(size_t)b] = ts.recs[(size_t)b * found.size() + t];
+        const double delta = tone_refine(col.data(), n_blocks, (double)block_samples / (double)fs);
+        const int64_t f = found[t] + (int64_t)std::llrint(delta);
+        if (2 * (f < 0 ? -f : f) < fs) found[t] = f;
+    }
+    return GYP_OK;
+}
+// the scan, and its candidates without the offset at 0 Hz and without what the window leaks from it and from stronger tones
+static int tone_scan(ToneSearch& ts) {
+    gyp_ctx* ctx = ts.g->ctx;
+    const int64_t fs = ts.g->fs;
+    const int32_t n_scan = ts.n_scan();
+    std::vector<int64_t> grid((size_t)kScanGrid);
+    for (int32_t k = 0; k < kScanGrid; ++k) grid[(size_t)k] = scan_freq(k - kScanHalf, fs);
+    if (const int rc = tone_measure(ts, grid, n_scan, kScanBlock, GYP_WINDOW_HANN)) return rc;
+    std::vector<double> power((size_t)kScanGrid, 0.0);
+    for (int32_t b = 0; b < n_scan; ++b)
+        for (int32_t k = 0; k < kScanGrid; ++k) {
+            const gyp_tone_rec& r = ts.recs[(size_t)b * kScanGrid + k];
+            power[(size_t)k] += r.re * r.re + r.im * r.im;
+        }
+    for (double& p : power) p /= (double)n_scan;
+    constexpr int32_t kMaxCand = 256;
+    int32_t cand[kMaxCand];
+    const char* why = nullptr;
+    double median = 0.0;
+    const int32_t min_sep = (int32_t)((kNotchMinSeparationHz * kScanDiv + fs - 1) / fs) + 2;
+    const int32_t n_cand = tones_find(power.data(), kScanGrid, ts.threshold, min_sep, kMaxCand, cand, &why, &median);
+    if (n_cand < 0) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_find_tones: the scan's spectrum: ") + why);
+    std::vector<int32_t> kept;
+    for (int32_t c = 0; c < n_cand && (int32_t)kept.size() < ts.max_tones; ++c) {
+        const int32_t k = cand[c];
+        if (std::abs(k - kScanHalf) < 4) continue;
+        bool leak = power[(size_t)k] <= 4.0 * power[(size_t)kScanHalf] * scan_leakage(k - kScanHalf);
+        for (const int32_t j : kept) leak = leak || power[(size_t)k] <= 4.0 * power[(size_t)j] * scan_leakage(k - j);
+        if (!leak) kept.push_back(k);
+    }
+    for (const int32_t k : kept) {
+        ts.found.push_back(grid[(size_t)k]);
+        ts.found_db.push_back(10.0 * std::log10(power[(size_t)k] / median));
+    }
+    return GYP_OK;
+}
+// scan, then refine what was found: over the short blocks, and over whole milliseconds where there are two
+static int tone_search(ToneSearch& ts) {
+    if (const int rc = tone_scan(ts)) return rc;
+    if (ts.found.empty()) return GYP_OK;
+    // (Hann on the short blocks: behind a rectangular window of 64 samples an offset-binary file's offset or a stronger tone
+    // leaks into a weak tone's records at -30 dB and below and bends its phase slope)
+    if (const int rc = tone_refine_found(ts, ts.n_fine(), kScanFine, GYP_WINDOW_HANN)) return rc;
+    if (ts.n_ms >= 2)
+        if (const int rc = tone_refine_found(ts, ts.n_ms, ts.g->src.n, GYP_WINDOW_RECT)) return rc;
+    return notch_check(ts.found.data(), (int32_t)ts.found.size(), ts.g->fs)
+               ? fail(ts.g->ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
+               : GYP_OK;
 }
 
 extern "C" {
@@ -3227,18 +3359,19 @@ int gyp_widen_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, uint64_t n_
 }
 
 int gyp_ingest_set_level(gyp_ingest* g, const gyp_iq_level* level) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_level: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_level: the handle was opened without a context (a level applies to device blocks)");
+    const char* who = "gyp_ingest_set_level";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "a level applies to device blocks", &ctx)) return rc;
     if (level)
-        if (const char* why = level_check(level)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_level: ") + why);
+        if (const char* why = level_check(level)) return refuse(ctx, who, why);
     g->cond.level_on = level != nullptr;
     g->cond.level = level ? *level : gyp_iq_level{0.0f, 0.0f, 1.0f, 0};
-    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old level: drop it and read it again
+    return ingest_recondition(g);
 }
 
 int gyp_ingest_get_level(const gyp_ingest* g, gyp_iq_level* out, int32_t* enabled_out) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_level: the handle was opened without a context (a level applies to device blocks)");
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_level", "a level applies to device blocks", &ctx)) return rc;
     if (out) *out = g->cond.level;
     if (enabled_out) *enabled_out = g->cond.level_on ? 1 : 0;
     return GYP_OK;
@@ -3246,29 +3379,25 @@ int gyp_ingest_get_level(const gyp_ingest* g, gyp_iq_level* out, int32_t* enable
 
 int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
                          gyp_iq_level* level_out, double* measured_out4) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_calibrate: handle is NULL");
-    gyp_ctx* ctx = g->ctx;
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_calibrate: the handle was opened without a context (the statistics are taken on the device)");
-    if (n_ms < 1 || n_ms > 10000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_calibrate: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 10000");
-    if (!(target_rms > 0.0) || !std::isfinite(target_rms))
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_calibrate: target_rms must be positive and finite");
+    const char* who = "gyp_ingest_calibrate";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "the statistics are taken on the device", &ctx)) return rc;
+    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 10000)) return rc;
+    if (!(target_rms > 0.0) || !std::isfinite(target_rms)) return refuse(ctx, who, "target_rms must be positive and finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<gyp_iq_stats> stats_dev;
     HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
     gyp_iq_stats* d_stats = stats_dev.get();
-    const int32_t n = g->src.n;
     std::vector<gyp_iq_stats> stats((size_t)n_ms);
     gyp_iq_level level{};
     // the level is put aside: the blocks measured are the handle's output without it (blanker and notches stay)
     const int rc = ingest_measure_range(
-        g, first_ms, n_ms, Suspend::level, "gyp_ingest_calibrate",
-        [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ctx->stream, iq, 1, 0, take, n, clip_level, d_stats + done); },
+        g, first_ms, n_ms, Suspend::level, who,
+        [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ingest_window(g, iq, take, 0), clip_level, d_stats + done); },
         [&](Conditioning& next) -> int {
-            HIP_TRY(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (const char* why = level_from_stats(stats.data(), n_ms, n, remove_dc, target_rms, &level, measured_out4))
-                return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_calibrate: ") + why);
+            if (const int rc = fetch(ctx, stats, d_stats)) return rc;
+            if (const char* why = level_from_stats(stats.data(), n_ms, g->src.n, remove_dc, target_rms, &level, measured_out4))
+                return refuse(ctx, who, why);
             next.level_on = true;
             next.level = level;
             return GYP_OK;
@@ -3280,20 +3409,21 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
 }
 
 int gyp_ingest_set_notches(gyp_ingest* g, const int64_t* freqs_hz, int32_t n) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_notches: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_notches: the handle was opened without a context (notches apply to device blocks)");
+    const char* who = "gyp_ingest_set_notches";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "notches apply to device blocks", &ctx)) return rc;
     if (!freqs_hz) n = 0;
-    if (const char* why = notch_check(freqs_hz, n, g->fs)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_notches: ") + why);
+    if (const char* why = notch_check(freqs_hz, n, g->fs)) return refuse(ctx, who, why);
     gyp_notch_tones t{};
     t.count = n;
     for (int32_t i = 0; i < n; ++i) t.freq_hz[i] = freqs_hz[i];
     g->cond.notches = t;
-    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old list: drop it and read it again
+    return ingest_recondition(g);
 }
 
 int gyp_ingest_get_notches(const gyp_ingest* g, int64_t* freqs_out8, int32_t* n_out) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_notches: the handle was opened without a context (notches apply to device blocks)");
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_notches", "notches apply to device blocks", &ctx)) return rc;
     if (freqs_out8)
         for (int32_t i = 0; i < g->cond.notches.count; ++i) freqs_out8[i] = g->cond.notches.freq_hz[i];
     if (n_out) *n_out = g->cond.notches.count;
@@ -3302,137 +3432,62 @@ int gyp_ingest_get_notches(const gyp_ingest* g, int64_t* freqs_out8, int32_t* n_
 
 int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double threshold, int32_t max_tones, int32_t install,
                           int64_t* freqs_out, double* power_db_out, int32_t* n_out) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_tones: handle is NULL");
-    gyp_ctx* ctx = g->ctx;
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_tones: the handle was opened without a context (the scan runs on the device)");
-    if (!n_out) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: n_out is NULL");
+    const char* who = "gyp_ingest_find_tones";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "the scan runs on the device", &ctx)) return rc;
+    if (!n_out) return refuse(ctx, who, "n_out is NULL");
     *n_out = 0;
-    if (n_ms < 1 || n_ms > 1000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 1000");
+    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
     if (!(threshold > 0.0) || !std::isfinite(threshold) || max_tones < 1 || max_tones > GYP_NOTCH_MAX_TONES)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: threshold must be positive and finite, 1 <= max_tones <= 8");
-    const int32_t n = g->src.n;
-    const int64_t fs = g->fs, total = (int64_t)n_ms * n, first_index = first_ms * n;
-    if (!tone_rate_ok(fs) || total < kScanBlock)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: the range must hold at least 1024 samples at a rate in [1000, 2^31) Hz");
+        return refuse(ctx, who, "threshold must be positive and finite, 1 <= max_tones <= 8");
+    ToneSearch ts{g, first_ms, n_ms, threshold, max_tones};
+    if (!tone_rate_ok(g->fs) || ts.total() < kScanBlock)
+        return refuse(ctx, who, "the range must hold at least 1024 samples at a rate in [1000, 2^31) Hz");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    constexpr int32_t n_grid = 2 * kScanHalf + 1;
-    const int32_t n_scan = (int32_t)(total / kScanBlock), n_fine = (int32_t)(total / kScanFine);
-    DevBuf<float> iq_all;
-    DevBuf<gyp_tone_rec> recs_dev;
-    HIP_TRY(ctx, iq_all.reserve((size_t)total * 2, Slack::exact));
-    HIP_TRY(ctx, recs_dev.reserve(std::max<size_t>((size_t)n_scan * n_grid, (size_t)n_fine * GYP_NOTCH_MAX_TONES), Slack::exact));
-    std::vector<gyp_tone_rec> recs;
-    std::vector<int64_t> found;
-    std::vector<double> found_db;
-    // records of `freqs` over n_blocks blocks of block_samples samples of the gathered range, block-major, in `recs`
-    auto measure = [&](const std::vector<int64_t>& freqs, int32_t n_blocks, int32_t block_samples, int32_t window) -> int {
-        if (const int rc = tones_upload_freqs(ctx, freqs.data(), (int32_t)freqs.size(), fs)) return rc;
-        if (const int rc = tones_launch(ctx, iq_all.get(), 1, 0, first_index, n_blocks, block_samples, fs, ctx->tone_freqs.get(),
-                                        (int32_t)freqs.size(), window, recs_dev.get()))
-            return rc;
-        recs.resize((size_t)n_blocks * freqs.size());
-        HIP_TRY(ctx, hipMemcpyAsync(recs.data(), recs_dev.get(), recs.size() * sizeof(gyp_tone_rec), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return GYP_OK;
-    };
-    // one refinement step of every tone found: the phase slope over blocks of block_samples samples, rounded to whole Hz
-    auto refine = [&](int32_t n_blocks, int32_t block_samples, int32_t window) -> int {
-        if (const int rc = measure(found, n_blocks, block_samples, window)) return rc;
-        std::vector<gyp_tone_rec> col((size_t)n_blocks);
-        for (size_t t = 0; t < found.size(); ++t) {
-            for (int32_t b = 0; b < n_blocks; ++b) col[(size_t)b] = recs[(size_t)b * found.size() + t];
-            const double delta = tone_refine(col.data(), n_blocks, (double)block_samples / (double)fs);
-            const int64_t f = found[t] + (int64_t)std::llrint(delta);
-            if (2 * (f < 0 ? -f : f) < fs) found[t] = f;
-        }
-        return GYP_OK;
-    };
+    HIP_TRY(ctx, ts.iq_all.reserve((size_t)ts.total() * 2, Slack::exact));
+    HIP_TRY(ctx, ts.recs_dev.reserve(std::max<size_t>((size_t)ts.n_scan() * kScanGrid, (size_t)ts.n_fine() * GYP_NOTCH_MAX_TONES), Slack::exact));
     // the blocks gathered are the producer's output behind the blanker, where one is on: no notches, no level
-    auto gather = [&](const float* iq, int32_t done, int32_t take) -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        return GYP_OK;
-    };
-    auto search = [&]() -> int {
-        // 1. the scan
-        std::vector<int64_t> grid((size_t)n_grid);
-        for (int32_t k = 0; k < n_grid; ++k) grid[(size_t)k] = scan_freq(k - kScanHalf, fs);
-        if (const int rc = measure(grid, n_scan, kScanBlock, GYP_WINDOW_HANN)) return rc;
-        std::vector<double> power((size_t)n_grid, 0.0);
-        for (int32_t b = 0; b < n_scan; ++b)
-            for (int32_t k = 0; k < n_grid; ++k) {
-                const gyp_tone_rec& r = recs[(size_t)b * n_grid + k];
-                power[(size_t)k] += r.re * r.re + r.im * r.im;
-            }
-        for (double& p : power) p /= (double)n_scan;
-        // 2. candidates, without the offset at 0 Hz and without what the window leaks from it and from stronger tones
-        constexpr int32_t kMaxCand = 256;
-        int32_t cand[kMaxCand];
-        const char* why = nullptr;
-        double median = 0.0;
-        const int32_t min_sep = (int32_t)((kNotchMinSeparationHz * kScanDiv + fs - 1) / fs) + 2;
-        const int32_t n_cand = tones_find(power.data(), n_grid, threshold, min_sep, kMaxCand, cand, &why, &median);
-        if (n_cand < 0) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_find_tones: the scan's spectrum: ") + why);
-        std::vector<int32_t> kept;
-        for (int32_t c = 0; c < n_cand && (int32_t)kept.size() < max_tones; ++c) {
-            const int32_t k = cand[c];
-            if (std::abs(k - kScanHalf) < 4) continue;
-            bool leak = power[(size_t)k] <= 4.0 * power[(size_t)kScanHalf] * scan_leakage(k - kScanHalf);
-            for (const int32_t j : kept) leak = leak || power[(size_t)k] <= 4.0 * power[(size_t)j] * scan_leakage(k - j);
-            if (!leak) kept.push_back(k);
-        }
-        for (const int32_t k : kept) {
-            found.push_back(grid[(size_t)k]);
-            found_db.push_back(10.0 * std::log10(power[(size_t)k] / median));
-        }
-        if (found.empty()) return GYP_OK;
-        // 3. refinement
-        // (Hann on the short blocks: behind a rectangular window of 64 samples an offset-binary file's offset or a stronger tone
-        // leaks into a weak tone's records at -30 dB and below and bends its phase slope)
-        if (const int rc = refine(n_fine, kScanFine, GYP_WINDOW_HANN)) return rc;
-        if (n_ms >= 2)
-            if (const int rc = refine(n_ms, n, GYP_WINDOW_RECT)) return rc;
-        return notch_check(found.data(), (int32_t)found.size(), fs)
-                   ? fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
-                   : GYP_OK;
-    };
-    auto search_and_install = [&](Conditioning& next) -> int {
-        if (const int rc = search()) return rc;
-        if (install) {
-            next.notches = gyp_notch_tones{};
-            next.notches.count = (int32_t)found.size();
-            for (size_t t = 0; t < found.size(); ++t) next.notches.freq_hz[t] = found[t];
-        }
-        return GYP_OK;
-    };
-    if (const int rc = ingest_measure_range(g, first_ms, n_ms, Suspend::level_notches, "gyp_ingest_find_tones", gather, search_and_install, [&] {
-            (void)iq_all.reset();
-            (void)recs_dev.reset();
-        }))
+    if (const int rc = ingest_measure_range(
+            g, first_ms, n_ms, Suspend::level_notches, who,
+            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, ts.iq_all.get(), iq, done, take); },
+            [&](Conditioning& next) -> int {
+                if (const int rc = tone_search(ts)) return rc;
+                if (install) {
+                    next.notches = gyp_notch_tones{};
+                    next.notches.count = (int32_t)ts.found.size();
+                    for (size_t t = 0; t < ts.found.size(); ++t) next.notches.freq_hz[t] = ts.found[t];
+                }
+                return GYP_OK;
+            },
+            [&] {
+                (void)ts.iq_all.reset();
+                (void)ts.recs_dev.reset();
+            }))
         return rc;
-    for (size_t t = 0; t < found.size(); ++t) {
-        if (freqs_out) freqs_out[t] = found[t];
-        if (power_db_out) power_db_out[t] = found_db[t];
+    for (size_t t = 0; t < ts.found.size(); ++t) {
+        if (freqs_out) freqs_out[t] = ts.found[t];
+        if (power_db_out) power_db_out[t] = ts.found_db[t];
     }
-    *n_out = (int32_t)found.size();
+    *n_out = (int32_t)ts.found.size();
     return GYP_OK;
 }
 
 int gyp_ingest_set_blanker(gyp_ingest* g, const gyp_blanker* blanker) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: the handle was opened without a context (a blanker applies to device blocks)");
+    const char* who = "gyp_ingest_set_blanker";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "a blanker applies to device blocks", &ctx)) return rc;
     if (blanker) {
-        if (const char* why = blanker_check(blanker)) return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_set_blanker: ") + why);
-        if (g->src.n > kBlankMaxSamples) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_set_blanker: the blanker takes at most 65536 samples per millisecond");
+        if (const char* why = blanker_check(blanker)) return refuse(ctx, who, why);
+        if (g->src.n > kBlankMaxSamples) return refuse(ctx, who, kBlankTooWide);
     }
     g->cond.blank_on = blanker != nullptr;
     g->cond.blanker = blanker ? *blanker : gyp_blanker{0.0f, 0.0f, 1.0f, 0};
-    return gyp_ingest_seek(g, g->consumer_ms);   // what was uploaded ahead carries the old blanker: drop it and read it again
+    return ingest_recondition(g);
 }
 
 int gyp_ingest_get_blanker(const gyp_ingest* g, gyp_blanker* out, int32_t* enabled_out) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_blanker: handle is NULL");
-    if (!g->ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_get_blanker: the handle was opened without a context (a blanker applies to device blocks)");
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_blanker", "a blanker applies to device blocks", &ctx)) return rc;
     if (out) *out = g->cond.blanker;
     if (enabled_out) *enabled_out = g->cond.blank_on ? 1 : 0;
     return GYP_OK;
@@ -3440,15 +3495,14 @@ int gyp_ingest_get_blanker(const gyp_ingest* g, gyp_blanker* out, int32_t* enabl
 
 int gyp_ingest_find_pulses(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double threshold_over_median, int32_t guard,
                            int32_t install, gyp_blanker* blanker_out, double* measured_out2) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: handle is NULL");
-    gyp_ctx* ctx = g->ctx;
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the handle was opened without a context (the histogram is taken on the device)");
-    if (n_ms < 1 || n_ms > 1000 || first_ms < 0 || first_ms > g->total_ms - n_ms)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: [first_ms, first_ms + n_ms) must lie in [0, total_ms), 1 <= n_ms <= 1000");
+    const char* who = "gyp_ingest_find_pulses";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "the histogram is taken on the device", &ctx)) return rc;
+    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
     if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median) || guard < 0 || guard > kBlankMaxGuard)
-        return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: threshold_over_median must be positive and finite, 0 <= guard <= 64");
+        return refuse(ctx, who, "threshold_over_median must be positive and finite, 0 <= guard <= 64");
     const int32_t n = g->src.n;
-    if (n > kBlankMaxSamples) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the blanker takes at most 65536 samples per millisecond");
+    if (n > kBlankMaxSamples) return refuse(ctx, who, kBlankTooWide);
     const int64_t total = (int64_t)n_ms * n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<float> iq_all;
@@ -3458,56 +3512,47 @@ int gyp_ingest_find_pulses(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_
     HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
     HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
     gyp_blanker found{};
-    // the blocks gathered are the producer's output: no blanker, no notches, no level
-    auto gather = [&](const float* iq, int32_t done, int32_t take) -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(iq_all.get() + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        return GYP_OK;
-    };
     auto derive = [&](Conditioning& next) -> int {
+        const IqWindow w = ingest_window(g, iq_all.get(), n_ms, first_ms);
         float centre[2] = {0.0f, 0.0f};
-        if (remove_dc) {   // the mean as gyp_iq_level_from_stats takes it
+        if (remove_dc) {
             std::vector<gyp_iq_stats> stats((size_t)n_ms);
-            if (const int rc = stats_launch(ctx, ctx->stream, iq_all.get(), 1, 0, n_ms, n, 0.0f, stats_dev.get())) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(stats.data(), stats_dev.get(), stats.size() * sizeof(gyp_iq_stats), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            double S_re = 0.0, S_im = 0.0;
-            for (const gyp_iq_stats& r : stats) {
-                S_re += r.sum_re;
-                S_im += r.sum_im;
-            }
-            const double M = (double)n_ms * n;
-            centre[0] = (float)(S_re / M);
-            centre[1] = (float)(S_im / M);
-            if (!std::isfinite(centre[0]) || !std::isfinite(centre[1]))
-                return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_find_pulses: the range's mean is not finite");
+            if (const int rc = stats_launch(ctx, w, 0.0f, stats_dev.get())) return rc;
+            if (const int rc = fetch(ctx, stats, stats_dev.get())) return rc;
+            const IqMean mean = mean_from_stats(stats.data(), n_ms, n);
+            centre[0] = (float)mean.re;
+            centre[1] = (float)mean.im;
+            if (!std::isfinite(centre[0]) || !std::isfinite(centre[1])) return refuse(ctx, who, "the range's mean is not finite");
         }
         std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
-        if (const int rc = hist_launch(ctx, ctx->stream, iq_all.get(), 1, 0, total, centre, hist_dev.get())) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(hist.data(), hist_dev.get(), hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (const int rc = hist_launch(ctx, w, total, centre, hist_dev.get())) return rc;
+        if (const int rc = fetch(ctx, hist, hist_dev.get())) return rc;
         if (const char* why = blank_from_hist(hist.data(), centre[0], centre[1], threshold_over_median, guard, &found, measured_out2))
-            return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_find_pulses: ") + why);
+            return refuse(ctx, who, why);
         if (install) {
             next.blank_on = true;
             next.blanker = found;
         }
         return GYP_OK;
     };
-    if (const int rc = ingest_measure_range(g, first_ms, n_ms, Suspend::all, "gyp_ingest_find_pulses", gather, derive, [&] {
-            (void)iq_all.reset();
-            (void)stats_dev.reset();
-            (void)hist_dev.reset();
-        }))
+    // the blocks gathered are the producer's output: no blanker, no notches, no level
+    if (const int rc = ingest_measure_range(
+            g, first_ms, n_ms, Suspend::all, who,
+            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, iq_all.get(), iq, done, take); }, derive, [&] {
+                (void)iq_all.reset();
+                (void)stats_dev.reset();
+                (void)hist_dev.reset();
+            }))
         return rc;
     if (blanker_out) *blanker_out = found;
     return GYP_OK;
 }
 
 int gyp_ingest_last_blanked(gyp_ingest* g, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
-    if (!g) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: handle is NULL");
-    gyp_ctx* ctx = g->ctx;
-    if (!ctx) return fail(nullptr, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: the handle was opened without a context (a blanker applies to device blocks)");
-    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return fail(ctx, GYP_E_BAD_ARG, "gyp_ingest_last_blanked: n_ms_out is NULL, or cap > 0 without counts_out");
+    const char* who = "gyp_ingest_last_blanked";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "a blanker applies to device blocks", &ctx)) return rc;
+    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return refuse(ctx, who, "n_ms_out is NULL, or cap > 0 without counts_out");
     *n_ms_out = g->last_n_ms;
     const int32_t take = std::min(cap, g->last_n_ms);
     if (take <= 0 || g->last_slot < 0) return GYP_OK;

@@ -332,6 +332,8 @@ static IngestExtent ingest_extent(const IngestSource& s, int64_t file_bytes) {
     return e;
 }
 
+// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); everything (gyp_ingest_find_pulses).
+enum class Suspend : int32_t { level, level_notches, all };
 // What is applied in place to every device block behind its producer, on the copy stream: the blanker, then the notches, then the
 // level.  One value, so that a measurement can put it aside and back whole (ingest_measure_range).
 struct Conditioning {
@@ -340,9 +342,16 @@ struct Conditioning {
     gyp_notch_tones notches{};   // gyp_ingest_set_notches / gyp_ingest_find_tones
     bool blank_on = false;     // gyp_ingest_set_blanker / gyp_ingest_find_pulses
     gyp_blanker blanker{0.0f, 0.0f, 1.0f, 0};
+    // The conditioning of the blocks a measurement sees.  What is put aside is off but kept (a suspended blanker or level keeps its
+    // values), except the notches, whose list is their switch.
+    Conditioning without(Suspend what) const {
+        Conditioning c = *this;
+        c.level_on = false;
+        if (what != Suspend::level) c.notches = gyp_notch_tones{};
+        if (what == Suspend::all) c.blank_on = false;
+        return c;
+    }
 };
-// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); everything (gyp_ingest_find_pulses).
-enum class Suspend : int32_t { level, level_notches, all };
 
 struct gyp_ingest {
     gyp_ingest(gyp_ctx* c, int64_t fs_hz, const IngestSource& s) : ctx(c), fs(fs_hz), src(s) {}

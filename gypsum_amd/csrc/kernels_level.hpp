@@ -139,21 +139,34 @@ static const char* level_check(const gyp_iq_level* l) {
     return nullptr;
 }
 
+// The mean of n_ms milliseconds of samples_per_ms samples from their records, as gyp_iq_level_from_stats and gyp_ingest_find_pulses
+// take it: the sums added in index order, then divided by the count, in float64 with one rounding per operation.
+struct IqMean { double re, im; };
+static IqMean mean_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms) {
+#pragma clang fp contract(off)
+    double S_re = 0.0, S_im = 0.0;
+    for (int32_t i = 0; i < n_ms; ++i) {
+        S_re += stats[i].sum_re;
+        S_im += stats[i].sum_im;
+    }
+    const double M = (double)n_ms * samples_per_ms;
+    return IqMean{S_re / M, S_im / M};
+}
+
 // gyp_iq_level_from_stats' arithmetic (the header states the order): float64, one rounding per operation -- contraction is off,
 // or the compiler would fuse a + b and P - q with the products in front of them.  nullptr, or GYP_E_BAD_ARG's reason.
 static const char* level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms, int32_t remove_dc, double target_rms,
                                     gyp_iq_level* level_out, double* measured_out4) {
 #pragma clang fp contract(off)
-    double S_re = 0.0, S_im = 0.0, S_sq = 0.0;
+    double S_sq = 0.0;
     int64_t C = 0;
     for (int32_t i = 0; i < n_ms; ++i) {
-        S_re += stats[i].sum_re;
-        S_im += stats[i].sum_im;
         S_sq += stats[i].sum_sq;
         C += stats[i].n_clip;
     }
     const double M = (double)n_ms * samples_per_ms;
-    const double m_re = S_re / M, m_im = S_im / M, P = S_sq / M;
+    const IqMean mean = mean_from_stats(stats, n_ms, samples_per_ms);
+    const double m_re = mean.re, m_im = mean.im, P = S_sq / M;
     const double d_re = remove_dc ? m_re : 0.0, d_im = remove_dc ? m_im : 0.0;
     const double a = d_re * d_re;
     const double b = d_im * d_im;

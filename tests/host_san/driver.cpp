@@ -750,6 +750,57 @@ static void resample_plans() {
     }
 }
 
+// --------------------------------------------------------------------------------------------------------- cond-plan
+// shapes.i64 rows: stage, n_cus, wg_per_cu, n, a, b, stride, in_addr, out_addr, flag (tests/cond_plan_model.py says what a and b are
+// per stage).  plans.i64 rows: the plan, its first and last launch, and over all launches the sum and the largest of their stream
+// counts, how many start where the one before ended, and the smallest and largest grid.x.
+static void cond_plans() {
+    const std::vector<int64_t> shapes = read_array<int64_t>("shapes.i64");
+    REQUIRE(shapes.size() % 10 == 0);
+    std::vector<int64_t> plans;
+    plans.reserve(shapes.size() / 10 * 20);
+    for (size_t r = 0; r * 10 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 10];
+        const int n_cus = (int)s[1];
+        const int32_t n = (int32_t)s[3];
+        const int64_t cap = persistent_cap(n_cus, (int)s[2]), a = s[4], b = s[5], stride = s[6];
+        const uintptr_t in = (uintptr_t)s[7], out = (uintptr_t)s[8];
+        if (s[0] == 7 || s[0] == 8) {   // the two single launches outside the stream loop
+            const UnpackPlan u = s[0] == 8 ? unpack_plan(cap, out, stride, (int32_t)b, a, n) : UnpackPlan{(int)grid_widen((uint64_t)a, cap), 0, 0};
+            for (int64_t v : {(int64_t)1, (int64_t)u.vec4, (int64_t)0, (int64_t)0, cap, (int64_t)0, (int64_t)0, (int64_t)u.grid, (int64_t)0, u.items}) plans.push_back(v);
+            plans.insert(plans.end(), 10, 0);
+            continue;
+        }
+        StagePlan p{};
+        switch (s[0]) {
+            case 0: p = stats_plan(cap, n, (int32_t)a); break;
+            case 1: p = condition_plan(cap, kLevelStreams, in, out, n, stride, a); break;
+            case 2: p = notch_plan(cap, kNotchStreams, n, (int32_t)a, (int32_t)b, kNotchLdsSamples, s[9] != 0); break;
+            case 3: p = blank_plan(cap, kBlankStreams, n, (int32_t)a); break;
+            case 4: p = hist_plan(cap, kBlankStreams, n, a); break;
+            case 5: p = tones_plan(n_cus, n, (int32_t)a, (int32_t)b); break;
+            case 6: p = quality_plan(n_cus, kQualityChans, n, (int32_t)a, (int32_t)b); break;
+            default: die("cond-plan: unknown stage");
+        }
+        REQUIRE(p.n_chunks >= 1);
+        const StageChunk first = stage_chunk(p, 0), last = stage_chunk(p, p.n_chunks - 1);
+        int64_t sum_ns = 0, max_ns = 0, in_order = 0, min_gx = INT64_MAX, max_gx = 0;
+        for (int32_t i = 0; i < p.n_chunks; ++i) {
+            const StageChunk c = stage_chunk(p, i);
+            in_order += c.s0 == sum_ns && c.ns >= 1;
+            sum_ns += c.ns;
+            max_ns = std::max<int64_t>(max_ns, c.ns);
+            min_gx = std::min<int64_t>(min_gx, c.grid_x);
+            max_gx = std::max<int64_t>(max_gx, c.grid_x);
+        }
+        for (int64_t v : {(int64_t)p.n_chunks, (int64_t)p.vec4, p.lds_bytes, p.per_stream, p.cap, (int64_t)first.s0, (int64_t)first.ns, (int64_t)first.grid_x,
+                          (int64_t)first.grid_y, first.items, (int64_t)last.s0, (int64_t)last.ns, (int64_t)last.grid_x, (int64_t)last.grid_y, last.items, sum_ns,
+                          max_ns, in_order, min_gx, max_gx})
+            plans.push_back(v);
+    }
+    Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+}
+
 // --------------------------------------------------------------------------------------------------------- dev-mem
 // The owners of dev_mem.hpp on a host without a device (every allocation fails), the scratch layouts, the table of debug switches on a
 // context that lives on the stack.  No kernel is launched and no context is made through gyp_create.
@@ -891,7 +942,7 @@ int main(int argc, char** argv) {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
         {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"resample-plan", drv::resample_plans},
-        {"dev-mem", drv::dev_mem},
+        {"cond-plan", drv::cond_plans}, {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, resample_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, resample_plan.hpp, cond_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -893,6 +893,130 @@ def test_resample_plan(programs, tmp_path, which):
         assert got_fs == fs and got_f == f and 0 <= got_f < fs, (fs, f_hz, got_f)
         assert q_bits == np.float64(q).view(np.int64) and y_bits == np.float64(y).view(np.int64), (fs, f_hz)
         assert q == 4.0 / fs and y == 0.5 / fs
+
+
+# ------------------------------------------------------------------------------------------------------------ cond-plan
+# Worked out by hand from the launch functions as they stood before cond_plan.hpp (stats_launch, condition_launch, notch_launch,
+# blank_launch, hist_launch, tones_launch, quality_launch, widen_launch, unpack_launch):
+# (stage, n_cus, wg_per_cu, n, a, b, stride, in_addr, out_addr, flag) -> {field: value}.  256 CUs x 2 workgroups: a cap of 512.
+def cond_literals():
+    from cond_plan_model import BLANK, CONDITION, HIST, NOTCH, QUALITY, STATS, TONES, UNPACK, WIDEN
+    big = 2 ** 31 + 5
+    return [
+        ((STATS, 256, 2, 2, 300, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 512, "gy_first": 1, "items_first": 600, "ns_first": 2}),
+        ((STATS, 256, 2, 1, 20, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 20, "items_first": 20}),
+        # one block of an ingest handle in place: 20 ms of 2046 samples as 20460 float4, 80 workgroups of 256 threads
+        ((CONDITION, 256, 2, 1, 40920, 0, 0, 4096, 4096, 0), {"n_chunks": 1, "vec4": 1, "per_stream": 20460, "gx_first": 80, "gy_first": 1}),
+        ((CONDITION, 256, 2, 1, 40920, 0, 0, 4096, 4104, 0), {"vec4": 0, "per_stream": 40920, "gx_first": 160}),
+        ((CONDITION, 256, 2, 17, 2047, 0, 2049, 4096, 4096, 0), {"n_chunks": 3, "vec4": 0, "per_stream": 2047, "gx_first": 8, "gy_first": 8,
+                                                                  "s0_last": 16, "ns_last": 1, "gx_last": 8, "gy_last": 1}),
+        ((CONDITION, 256, 2, 17, big, 0, big + 1, 4096, 4096, 0), {"vec4": 1, "per_stream": 2 ** 30 + 3, "gx_first": 64, "gy_first": 8, "gx_last": 512, "gy_last": 1}),
+        ((CONDITION, 1, 1, 8, 2047, 0, 2048, 0, 0, 0), {"n_chunks": 1, "cap": 1, "gx_first": 1, "gy_first": 8}),      # 1 / 8 workgroups: still one
+        ((NOTCH, 256, 2, 1, 20, 2046, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 20, "items_first": 20, "lds_bytes": 16368}),
+        ((NOTCH, 256, 2, 9, 250, 16384, 0, 0, 0, 0), {"n_chunks": 2, "gx_first": 512, "items_first": 2000, "gx_last": 250, "items_last": 250, "s0_last": 8,
+                                                      "lds_bytes": 131072}),
+        ((NOTCH, 256, 2, 1, 20, 16385, 0, 0, 0, 0), {"lds_bytes": 0, "gx_first": 20}),
+        ((NOTCH, 256, 2, 1, 20, 2046, 0, 0, 0, 1), {"lds_bytes": 0, "gx_first": 20}),
+        ((BLANK, 256, 2, 11, 1, 0, 0, 0, 0, 0), {"n_chunks": 2, "gx_first": 8, "gx_last": 3, "s0_last": 8, "ns_last": 3}),
+        ((HIST, 256, 2, 1, 20460, 0, 0, 0, 0, 0), {"per_stream": 10230, "gx_first": 40, "gy_first": 1}),
+        ((HIST, 256, 2, 9, 2046, 0, 0, 0, 0, 0), {"n_chunks": 2, "gx_first": 4, "gy_first": 8, "gx_last": 4, "gy_last": 1}),
+        ((TONES, 256, 2, 1, 79, 257, 0, 0, 0, 0), {"n_chunks": 1, "cap": 2048, "items_first": 20303, "gx_first": 2048}),
+        ((QUALITY, 256, 2, 2049, 1000, 20, 0, 0, 0, 0), {"n_chunks": 3, "per_stream": 50, "cap": 16384, "items_first": 51200, "gx_first": 12800,
+                                                         "s0_last": 2048, "items_last": 50, "gx_last": 13}),
+        ((QUALITY, 64, 2, 2049, 1000, 20, 0, 0, 0, 0), {"cap": 4096, "gx_first": 4096, "gx_last": 13}),
+        ((WIDEN, 256, 2, 0, 81840, 0, 0, 0, 0, 0), {"gx_first": 21}),          # 5115 whole 16s: 20 workgroups, and the one more
+        ((WIDEN, 256, 2, 0, 15, 0, 0, 0, 0, 0), {"gx_first": 1}),
+        ((WIDEN, 256, 2, 0, 2 ** 32 + 7, 0, 0, 0, 0, 0), {"gx_first": 512}),
+        ((UNPACK, 256, 2, 1, 40920, 2, 40920, 0, 4096, 0), {"items_first": 1279, "gx_first": 5, "vec4": 1}),
+        ((UNPACK, 256, 2, 3, 40920, 2, 40921, 0, 4096, 0), {"items_first": 3837, "gx_first": 15, "vec4": 0}),
+    ]
+
+
+def cond_sweep():
+    """Every stage over its own axes: 1, 64, 256, 304 CUs x 1, 2, 8 workgroups per CU; stream counts on both sides of 8 and 16 and the
+    grid's height limit, channel counts on both sides of 1024 and 2048; odd and even strides; bases at offsets 0 and 8."""
+    import cond_plan_model as m
+    streams, chans = (1, 2, 7, 8, 9, 16, 17, 65535), (1, 1023, 1024, 1025, 2049)
+    n_ms, n, big = (1, 3, 250, 10000), (1, 2, 1023, 16384, 16385, 49104, 65536), 2 ** 31 + 5
+    rows = []
+    for cus in (1, 64, 256, 304):
+        for wg in (1, 2, 8):
+            def add(stage, count, a, b=0, stride=0, in_addr=0, out_addr=0, flag=0):
+                rows.append((stage, cus, wg, count, a, b, stride, in_addr, out_addr, flag))
+            for s in streams:
+                for ms in n_ms:
+                    add(m.STATS, s, ms)
+                    add(m.BLANK, s, ms)
+                    for spm in n:
+                        for no_lds in (0, 1):
+                            add(m.NOTCH, s, ms, spm, flag=no_lds)
+                for count in (0, 1, 2, 3, 2047, big):
+                    for stride in (count | 1, (count + 2) & ~1):
+                        for i in (0, 8):
+                            for o in (0, 8):
+                                add(m.CONDITION, s, count, stride=stride, in_addr=4096 + i, out_addr=8192 + o)
+                for count in (1, 2, 3, 2046, big):
+                    add(m.HIST, s, count)
+                    for bits in (1, 2, 4):
+                        for stride in (count | 1, (count + 2) & ~1):
+                            for o in (0, 8):
+                                add(m.UNPACK, s, count, bits, stride=stride, out_addr=8192 + o)
+                if wg == 1:              # (their caps do not depend on it)
+                    for n_blocks in (1, 3, 250):
+                        for n_freq in (1, 8, 257):
+                            add(m.TONES, s, n_blocks, n_freq)
+            if wg == 1:
+                for c in chans:
+                    for ms in n_ms:
+                        for window in (1, 20, 250, 10001):
+                            add(m.QUALITY, c, ms, window)
+            for words in (1, 15, 16, 17, 4095, 4096, 4097, 81840, 2 ** 32 + 7):
+                add(m.WIDEN, 0, words)
+    return i64(rows)
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_cond_plan(programs, tmp_path, which):
+    """The plans of csrc/cond_plan.hpp against tests/cond_plan_model.py on the sweep above and on the shapes whose plans are written
+    out above, and what makes a plan correct: its launches take the streams 0 .. n - 1 in order, each once, none more than K of
+    them; every grid is at least 1 and at most its cap; a launch over rows is as high as it has streams; LDS stays within 128 KiB."""
+    import cond_plan_model as m
+
+    d = indir(tmp_path)
+    sweep, literals = cond_sweep(), cond_literals()
+    shapes = np.concatenate([sweep, i64([shape for shape, _ in literals])])
+    shapes.tofile(d / "shapes.i64")
+    out = run(programs, which, "cond-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(shapes), len(m.FIELDS))
+    want = m.plans(shapes)
+    for col, field in enumerate(m.FIELDS):
+        bad = np.flatnonzero(got[:, col] != want[:, col])
+        assert len(bad) == 0, (field, len(bad), shapes[bad[0]].tolist(), int(got[bad[0], col]), int(want[bad[0], col]))
+    plan = {f: got[:, c] for c, f in enumerate(m.FIELDS)}
+    stage, n_cus, wg, count = shapes[:, 0], shapes[:, 1], shapes[:, 2], shapes[:, 3]
+    assert set(np.unique(stage)) == set(range(9))
+    loop = (stage != m.WIDEN) & (stage != m.UNPACK)                   # the stages that walk their streams in launches
+    k = np.array([m.K.get(int(s), 0) for s in stage])
+    k = np.where(k == 0, count, k)
+    assert np.array_equal(plan["sum_ns"][loop], count[loop]) and np.array_equal(plan["in_order"][loop], plan["n_chunks"][loop])
+    assert (plan["max_ns"][loop] <= k[loop]).all() and (plan["n_chunks"][loop] == -(-count[loop] // k[loop])).all()
+    assert (plan["s0_first"] == 0).all() and np.array_equal((plan["s0_last"] + plan["ns_last"])[loop], count[loop])
+    want_cap = np.where(stage == m.TONES, 8 * n_cus, np.where(stage == m.QUALITY, 64 * n_cus, n_cus * wg))
+    assert np.array_equal(plan["cap"], want_cap)
+    assert (plan["min_gx"][loop] >= 1).all() and (plan["max_gx"][loop] <= plan["cap"][loop]).all()
+    assert (plan["gx_first"] >= 1).all() and (plan["gx_first"] <= plan["cap"]).all()          # (widen and unpack: their one launch)
+    rows = (stage == m.CONDITION) | (stage == m.HIST)
+    assert np.array_equal(plan["gy_first"][rows], plan["ns_first"][rows]) and np.array_equal(plan["gy_last"][rows], plan["ns_last"][rows])
+    assert (plan["gy_first"][loop & ~rows] == 1).all() and (plan["gy_last"][loop & ~rows] == 1).all() and plan["gy_first"].max() == 8
+    # rows side by side never take more than the cap between them, unless every one of them is down to its one workgroup
+    assert ((plan["gx_first"] * plan["gy_first"] <= plan["cap"]) | (plan["gx_first"] == 1))[rows].all()
+    assert (plan["lds_bytes"] <= 128 * 1024).all() and (plan["lds_bytes"][stage != m.NOTCH] == 0).all()
+    assert set(np.unique(plan["lds_bytes"][:len(sweep)])) == {0, 8, 16, 8 * 1023, 8 * 16384}
+    assert set(np.unique(plan["vec4"][stage == m.CONDITION])) == {0, 1} and set(np.unique(plan["vec4"][stage == m.UNPACK])) == {0, 1}
+    for row, (shape, expected) in zip(got[len(sweep):], literals):
+        p = dict(zip(m.FIELDS, row.tolist()))
+        for field, value in expected.items():
+            assert p[field] == value, (shape, field, p[field])
 
 
 # ------------------------------------------------------------------------------------------------------------ dev-mem
