@@ -60,7 +60,9 @@ QUALITY_SUMS = np.dtype([("n_used", "<i4"), ("n_locked", "<i4"), ("n_groups", "<
 QUALITY = np.dtype([("cn0_m2m4_dbhz", "<f8"), ("cn0_nwpr_dbhz", "<f8"), ("phase_lock", "<f8"), ("locked_share", "<f8"),
                     ("n_used", "<i4"), ("n_groups", "<i4")], align=True)
 BLANKER = np.dtype([("center_re", "<f4"), ("center_im", "<f4"), ("threshold", "<f4"), ("guard", "<i4")], align=True)
+EXCISOR = np.dtype([("threshold", "<f4"), ("guard", "<i4"), ("reserved", "<i4", (2,))], align=True)
 GYP_POWER_HIST_BINS = 2048
+GYP_EXCISE_FRAME = 256
 GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
 GYP_NOTCH_MAX_TONES = 8
 GYP_BIT_ZERO, GYP_BIT_ONE, GYP_BIT_UNKNOWN = 0, 1, 2
@@ -73,7 +75,8 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_params": PARAMS.itemsize, "gyp_track_rec": TRACK_REC.itemsize, "gyp_packing": PACKING.itemsize,
                 "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize,
                 "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize,
-                "gyp_quality_sums": QUALITY_SUMS.itemsize, "gyp_quality": QUALITY.itemsize, "gyp_blanker": BLANKER.itemsize}
+                "gyp_quality_sums": QUALITY_SUMS.itemsize, "gyp_quality": QUALITY.itemsize, "gyp_blanker": BLANKER.itemsize,
+                "gyp_excisor": EXCISOR.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -93,7 +96,9 @@ EXPORTS = (
     "gyp_iq_tones_dev gyp_notch_iq_dev gyp_tones_find gyp_tone_refine gyp_ingest_set_notches gyp_ingest_get_notches gyp_ingest_find_tones "
     "gyp_track_quality_dev gyp_track_quality gyp_quality_from_sums "
     "gyp_blank_iq_dev gyp_iq_power_hist_dev gyp_blank_from_hist gyp_ingest_set_blanker gyp_ingest_get_blanker gyp_ingest_find_pulses "
-    "gyp_ingest_last_blanked"
+    "gyp_ingest_last_blanked "
+    "gyp_excise_iq_dev gyp_iq_spectrum_hist_dev gyp_excise_from_hist gyp_ingest_set_excisor gyp_ingest_get_excisor gyp_ingest_find_excisor "
+    "gyp_ingest_last_excised"
 ).split()
 
 
@@ -238,6 +243,13 @@ def load() -> C.CDLL:
         "gyp_ingest_get_blanker": (C.c_int, [vp, vp, C.POINTER(i32)]),
         "gyp_ingest_find_pulses": (C.c_int, [vp, i64, i32, i32, dbl, i32, i32, vp, vp]),
         "gyp_ingest_last_blanked": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
+        "gyp_excise_iq_dev": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
+        "gyp_iq_spectrum_hist_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, vp]),
+        "gyp_excise_from_hist": (C.c_int, [vp, dbl, i32, vp, vp]),
+        "gyp_ingest_set_excisor": (C.c_int, [vp, vp]),
+        "gyp_ingest_get_excisor": (C.c_int, [vp, vp, C.POINTER(i32)]),
+        "gyp_ingest_find_excisor": (C.c_int, [vp, i64, i32, dbl, i32, i32, vp, vp]),
+        "gyp_ingest_last_excised": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

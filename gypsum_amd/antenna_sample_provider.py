@@ -208,12 +208,17 @@ class AntennaSampleProviderResampled(_CursorProvider):
     `blank` (a gypsum_amd.blanker.Blanker) or `find_pulses` (True, or a dict of `IqFileIngest.find_pulses`'s arguments; applied once
     after opening) blanks pulsed interference in every sample served (gypsum_amd.blanker); the two exclude each other.  The blanker
     stands in front of the notches and runs FIRST: tones and level are then measured on the blanked output.  Where `find_pulses`
-    names no guard it is half the filter's taps (at most 64): a T-tap resampler or down-converter smears a pulse over T samples."""
+    names no guard it is half the filter's taps (at most 64): a T-tap resampler or down-converter smears a pulse over T samples.
+
+    `excise` (a gypsum_amd.excisor.Excisor) or `find_excisor` (True, or a dict of `IqFileIngest.find_excisor`'s arguments; applied
+    once after opening, behind `find_pulses`) excises narrowband and swept interference that is no pure tone from every sample served
+    (gypsum_amd.excisor); the two exclude each other.  The excisor stands behind the blanker and in front of the notches: tones and
+    level are then measured on the excised output."""
 
     def __init__(self, path, sample_rate: float | None = None, resample_to: int | None = None, utc_start_time: float = 0.0,
                  sample_component_data_type=np.float32, scale: float = 1.0, taps: int | None = None, block_ms: int = 250,
                  engine=None, device: int = 0, if_hz: int | None = None, packing=None, level=None, calibrate: dict | None = None,
-                 notches=None, find_tones=None, blank=None, find_pulses=None) -> None:
+                 notches=None, find_tones=None, blank=None, find_pulses=None, excise=None, find_excisor=None) -> None:
         from .engine import GypsumEngine
         from .ingest import IqFileIngest
         from .resample import DEFAULT_TAPS, ddc_design, default_ddc_rate, nearest_supported_rate
@@ -235,6 +240,8 @@ class AntennaSampleProviderResampled(_CursorProvider):
             raise ValueError("notches and find_tones exclude each other: tones are either given or found")
         if blank is not None and find_pulses:
             raise ValueError("blank and find_pulses exclude each other: a blanker is either given or measured")
+        if excise is not None and find_excisor:
+            raise ValueError("excise and find_excisor exclude each other: an excisor is either given or measured")
         self.path = Path(path)
         self.input_sample_rate = int(sample_rate)
         self.if_hz = None if if_hz is None else int(if_hz)
@@ -280,6 +287,11 @@ class AntennaSampleProviderResampled(_CursorProvider):
                     filter_taps = int(taps or DEFAULT_TAPS)
                 args["guard"] = min(filter_taps // 2, 64)
             self.blanker, self.pulses = self._ingest.find_pulses(**args)
+        self.excisor, self.excised = excise, None  # excised: {"median", "threshold"} where find_excisor ran
+        if excise is not None:
+            self._ingest.set_excisor(excise)
+        elif find_excisor:
+            self.excisor, self.excised = self._ingest.find_excisor(**(find_excisor if isinstance(find_excisor, dict) else {}))
         self.tones = None                        # [(Hz, dB over the median), ...] where find_tones ran
         if notches is not None:
             self._ingest.set_notches(notches)

@@ -1,5 +1,5 @@
 // cond_plan.hpp -- what the conditioning stages behind the sample path launch for a shape: the statistics, level, tone, notch,
-// blanker, histogram and quality kernels, and the widen and unpack kernels whose persistent grid they share.  A call of n streams
+// blanker, excisor, histogram and quality kernels, and the widen and unpack kernels whose persistent grid they share.  A call of n streams
 // (channels) is cut into launches of at most k, because a launch's per-stream parameters travel by value in a kernel argument; a
 // plan says how many launches, which streams each takes, its grid, its dynamic LDS and whether rows are accessed 16 bytes at a time.
 // Plain C++17 and pure functions of their arguments: no HIP type, no context, addresses as uintptr_t
@@ -85,6 +85,9 @@ inline StagePlan notch_plan(int64_t cap, int32_t k, int32_t n_streams, int32_t n
 
 // iq_blank_kernel, k streams per launch: one workgroup per (stream, millisecond).
 inline StagePlan blank_plan(int64_t cap, int32_t k, int32_t n_streams, int32_t n_ms) { return stage_plan(n_streams, k, GridRule::per_item, n_ms, cap); }
+
+// iq_excise_kernel (k streams per launch) and iq_spectrum_hist_kernel (k = n_streams): one workgroup per (stream, millisecond).
+inline StagePlan excise_plan(int64_t cap, int32_t k, int32_t n_streams, int32_t n_ms) { return stage_plan(n_streams, k, GridRule::per_item, n_ms, cap); }
 
 // iq_power_hist_kernel, k streams per launch, sharing the persistent grid like the condition kernel: a thread takes two samples.
 inline StagePlan hist_plan(int64_t cap, int32_t k, int32_t n_streams, int64_t n_samples) { return stage_plan(n_streams, k, GridRule::per_row, n_samples / 2, cap); }

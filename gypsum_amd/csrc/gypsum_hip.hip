@@ -2862,6 +2862,82 @@ int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, 
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------------------
+// Excisor (kernels_excise.hpp): per-millisecond excision of spectral bins, the bin-power histogram its threshold comes from
+// ---------------------------------------------------------------------------------------------------------
+// Enqueue iq_excise_kernel for excisors that have passed excisor_check; unused slots of a launch's excisors repeat its last one.
+// counts (may be null): one int32 per (stream, millisecond); masks (may be null): four words per (stream, millisecond, frame).
+static int excise_launch(gyp_ctx* ctx, const IqWindow& w, const gyp_excisor* excisors, int32_t* counts, uint64_t* masks) {
+    const StagePlan pl = excise_plan(persistent_cap(ctx), kExciseStreams, w.n_streams, w.n_ms);
+    return for_each_chunk(pl, [&](const StageChunk& c) {
+        ExciseArgs a{};
+        for (int32_t i = 0; i < kExciseStreams; ++i) a.v[i] = excisors[c.s0 + std::min(i, c.ns - 1)];
+        int32_t* cnt = counts ? counts + (int64_t)c.s0 * w.n_ms : nullptr;
+        uint64_t* msk = masks ? masks + (int64_t)c.s0 * w.n_ms * excise_frames(w.n) * 4 : nullptr;
+        for_flag(w.in == w.out, [&](auto in_place) {   // the kernel's flag is `copy`
+            hipLaunchKernelGGL(iq_excise_kernel<!decltype(in_place)::value>, dim3(c.grid_x), dim3(kExciseThreads), 0, w.stream, w.src(c.s0),
+                               w.dst(c.s0), w.stride, w.n_ms, w.n, c.items, a, cnt, msk);
+        });
+        return launched(ctx);
+    });
+}
+
+// Zero the histograms and enqueue iq_spectrum_hist_kernel over the window: every stream in one launch.
+static int spectrum_hist_launch(gyp_ctx* ctx, const IqWindow& w, uint32_t* hist) {
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)w.n_streams * GYP_POWER_HIST_BINS * sizeof(uint32_t), w.stream));
+    const StageChunk c = stage_chunk(excise_plan(persistent_cap(ctx), w.n_streams, w.n_streams, w.n_ms), 0);
+    hipLaunchKernelGGL(iq_spectrum_hist_kernel, dim3(c.grid_x), dim3(kExciseThreads), 0, w.stream, w.src(0), w.stride, w.n_ms, w.n, c.items, hist);
+    return launched(ctx);
+}
+
+extern "C" {
+
+int gyp_excise_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                      int32_t samples_per_ms, const gyp_excisor* excisors_host, int32_t* counts_out_dev, uint64_t* masks_out_dev) {
+    const char* who = "gyp_excise_iq_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!in_dev || !out_dev || !excisors_host) return refuse(ctx, who, "in_dev, out_dev and excisors_host must not be NULL");
+    if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || samples_per_ms > kExciseMaxSamples ||
+        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
+                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    for (int32_t s = 0; s < n_streams; ++s)
+        if (const char* why = excisor_check(&excisors_host[s])) return refuse(ctx, who, why);
+    if (n_ms == 0) return GYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    IqWindow w{};
+    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
+    w.stream = ctx->stream;
+    return excise_launch(ctx, w, excisors_host, counts_out_dev, masks_out_dev);
+}
+
+int gyp_iq_spectrum_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                             int32_t samples_per_ms, uint32_t* hist_out_dev) {
+    const char* who = "gyp_iq_spectrum_hist_dev";
+    if (!ctx) return refuse(nullptr, who, "ctx is NULL");
+    if (!iq_dev || !hist_out_dev) return refuse(ctx, who, "iq_dev and hist_out_dev must not be NULL");
+    if (n_streams < 1 || n_ms < 1 || samples_per_ms < GYP_EXCISE_FRAME || samples_per_ms > kExciseMaxSamples ||
+        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 1, 256 <= samples_per_ms <= 65536, "
+                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    IqWindow w{};
+    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms, w.stream = ctx->stream;
+    return spectrum_hist_launch(ctx, w, hist_out_dev);
+}
+
+int gyp_excise_from_hist(const uint32_t* hist, double threshold_over_median, int32_t guard, gyp_excisor* excisor_out, double* measured_out2) {
+    if (!hist || !excisor_out) return fail(nullptr, GYP_E_BAD_ARG, "gyp_excise_from_hist: hist and excisor_out must not be NULL");
+    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median))
+        return fail(nullptr, GYP_E_BAD_ARG, "gyp_excise_from_hist: threshold_over_median must be positive and finite");
+    if (guard < 0 || guard > kExciseMaxGuard) return fail(nullptr, GYP_E_BAD_ARG, "gyp_excise_from_hist: guard must lie in 0 .. 8");
+    if (const char* why = excise_from_hist(hist, threshold_over_median, guard, excisor_out, measured_out2))
+        return fail(nullptr, GYP_E_BAD_ARG, std::string("gyp_excise_from_hist: ") + why);
+    return GYP_OK;
+}
+
+}  // extern "C"
+
 static void ingest_free(gyp_ingest* g) {
     ingest_stop_reader(g);
     if (g->ctx) {
@@ -2889,8 +2965,11 @@ static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms
     w.in = w.out = g->dev_iq[d].get();
     w.n_streams = 1, w.n_ms = n_ms, w.n = g->src.n, w.first_index = first_ms * w.n, w.stream = g->copy_stream.get();
     g->slot_blanked[d] = cond.blank_on ? 1 : 0;
-    if (cond.blank_on)   // chain order: producer -> blanker -> notches -> level
+    if (cond.blank_on)   // chain order: producer -> blanker -> excisor -> notches -> level
         if (const int rc = blank_launch(g->ctx, w, &cond.blanker, g->dev_blanked[d].get())) return rc;
+    if (!g->slot_excised.empty()) g->slot_excised[d] = cond.excise_on ? 1 : 0;
+    if (cond.excise_on)   // (an excisor is only ever on behind ingest_excise_buffers)
+        if (const int rc = excise_launch(g->ctx, w, &cond.excisor, g->dev_excised[d].get(), nullptr)) return rc;
     if (cond.notches.count > 0)
         if (const int rc = notch_launch(g->ctx, w, g->fs, &cond.notches)) return rc;
     if (!cond.level_on) return GYP_OK;
@@ -3298,6 +3377,7 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     if (g->cond.level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->cond.notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->cond.blank_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a blanker is on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    if (g->cond.excise_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: an excisor is on, and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3390,7 +3470,7 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     gyp_iq_stats* d_stats = stats_dev.get();
     std::vector<gyp_iq_stats> stats((size_t)n_ms);
     gyp_iq_level level{};
-    // the level is put aside: the blocks measured are the handle's output without it (blanker and notches stay)
+    // the level is put aside: the blocks measured are the handle's output without it (blanker, excisor and notches stay)
     const int rc = ingest_measure_range(
         g, first_ms, n_ms, Suspend::level, who,
         [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ingest_window(g, iq, take, 0), clip_level, d_stats + done); },
@@ -3446,7 +3526,7 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, ts.iq_all.reserve((size_t)ts.total() * 2, Slack::exact));
     HIP_TRY(ctx, ts.recs_dev.reserve(std::max<size_t>((size_t)ts.n_scan() * kScanGrid, (size_t)ts.n_fine() * GYP_NOTCH_MAX_TONES), Slack::exact));
-    // the blocks gathered are the producer's output behind the blanker, where one is on: no notches, no level
+    // the blocks gathered are the producer's output behind the blanker and the excisor, where they are on: no notches, no level
     if (const int rc = ingest_measure_range(
             g, first_ms, n_ms, Suspend::level_notches, who,
             [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, ts.iq_all.get(), iq, done, take); },
@@ -3565,6 +3645,104 @@ int gyp_ingest_last_blanked(gyp_ingest* g, int32_t* counts_out, int32_t cap, int
     HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
     HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
     HIP_TRY(ctx, hipMemcpyAsync(counts_out, g->dev_blanked[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
+    return GYP_OK;
+}
+
+// The per-slot counts of the excisor, made when a handle first gets one: a handle that never does allocates nothing for it.
+static int ingest_excise_buffers(gyp_ingest* g) {
+    if (!g->dev_excised.empty()) return GYP_OK;
+    gyp_ctx* ctx = g->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<DevBuf<int32_t>> bufs((size_t)g->src.depth);
+    for (auto& b : bufs) HIP_TRY(ctx, b.reserve((size_t)g->src.block_ms, Slack::exact));
+    g->dev_excised = std::move(bufs);
+    g->slot_excised.assign((size_t)g->src.depth, 0);
+    return GYP_OK;
+}
+static const char* const kExciseTooWide = "the excisor takes at most 65536 samples per millisecond";
+
+int gyp_ingest_set_excisor(gyp_ingest* g, const gyp_excisor* excisor) {
+    const char* who = "gyp_ingest_set_excisor";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "an excisor applies to device blocks", &ctx)) return rc;
+    if (excisor) {
+        if (const char* why = excisor_check(excisor)) return refuse(ctx, who, why);
+        if (g->src.n > kExciseMaxSamples) return refuse(ctx, who, kExciseTooWide);
+        if (const int rc = ingest_excise_buffers(g)) return rc;
+    }
+    g->cond.excise_on = excisor != nullptr;
+    g->cond.excisor = excisor ? *excisor : gyp_excisor{1.0f, 0, {0, 0}};
+    return ingest_recondition(g);
+}
+
+int gyp_ingest_get_excisor(const gyp_ingest* g, gyp_excisor* out, int32_t* enabled_out) {
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_excisor", "an excisor applies to device blocks", &ctx)) return rc;
+    if (out) *out = g->cond.excisor;
+    if (enabled_out) *enabled_out = g->cond.excise_on ? 1 : 0;
+    return GYP_OK;
+}
+
+int gyp_ingest_find_excisor(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double threshold_over_median, int32_t guard, int32_t install,
+                            gyp_excisor* excisor_out, double* measured_out2) {
+    const char* who = "gyp_ingest_find_excisor";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "the histogram is taken on the device", &ctx)) return rc;
+    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
+    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median) || guard < 0 || guard > kExciseMaxGuard)
+        return refuse(ctx, who, "threshold_over_median must be positive and finite, 0 <= guard <= 8");
+    const int32_t n = g->src.n;
+    if (n > kExciseMaxSamples) return refuse(ctx, who, kExciseTooWide);
+    if (n < GYP_EXCISE_FRAME) return refuse(ctx, who, "the histogram needs at least 256 samples per millisecond");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (install)
+        if (const int rc = ingest_excise_buffers(g)) return rc;
+    DevBuf<float> iq_all;
+    DevBuf<uint32_t> hist_dev;
+    HIP_TRY(ctx, iq_all.reserve((size_t)n_ms * n * 2, Slack::exact));
+    HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
+    gyp_excisor found{};
+    auto derive = [&](Conditioning& next) -> int {
+        std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
+        if (const int rc = spectrum_hist_launch(ctx, ingest_window(g, iq_all.get(), n_ms, first_ms), hist_dev.get())) return rc;
+        if (const int rc = fetch(ctx, hist, hist_dev.get())) return rc;
+        if (const char* why = excise_from_hist(hist.data(), threshold_over_median, guard, &found, measured_out2)) return refuse(ctx, who, why);
+        if (install) {
+            next.excise_on = true;
+            next.excisor = found;
+        }
+        return GYP_OK;
+    };
+    // the blocks gathered are the producer's output behind the blanker, where one is on: no excisor, no notches, no level
+    if (const int rc = ingest_measure_range(
+            g, first_ms, n_ms, Suspend::level_notches_excisor, who,
+            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, iq_all.get(), iq, done, take); }, derive, [&] {
+                (void)iq_all.reset();
+                (void)hist_dev.reset();
+            }))
+        return rc;
+    if (excisor_out) *excisor_out = found;
+    return GYP_OK;
+}
+
+int gyp_ingest_last_excised(gyp_ingest* g, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
+    const char* who = "gyp_ingest_last_excised";
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, "an excisor applies to device blocks", &ctx)) return rc;
+    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return refuse(ctx, who, "n_ms_out is NULL, or cap > 0 without counts_out");
+    *n_ms_out = g->last_n_ms;
+    const int32_t take = std::min(cap, g->last_n_ms);
+    if (take <= 0 || g->last_slot < 0) return GYP_OK;
+    const int d = g->last_slot;
+    if (g->slot_excised.empty() || !g->slot_excised[d]) {
+        std::fill(counts_out, counts_out + take, 0);
+        return GYP_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
+    HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
+    HIP_TRY(ctx, hipMemcpyAsync(counts_out, g->dev_excised[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
     HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
     return GYP_OK;
 }

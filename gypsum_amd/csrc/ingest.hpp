@@ -332,22 +332,26 @@ static IngestExtent ingest_extent(const IngestSource& s, int64_t file_bytes) {
     return e;
 }
 
-// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); everything (gyp_ingest_find_pulses).
-enum class Suspend : int32_t { level, level_notches, all };
-// What is applied in place to every device block behind its producer, on the copy stream: the blanker, then the notches, then the
-// level.  One value, so that a measurement can put it aside and back whole (ingest_measure_range).
+// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); the excisor as well
+// (gyp_ingest_find_excisor); everything (gyp_ingest_find_pulses).
+enum class Suspend : int32_t { level, level_notches, level_notches_excisor, all };
+// What is applied in place to every device block behind its producer, on the copy stream: the blanker, then the excisor, then the
+// notches, then the level.  One value, so that a measurement can put it aside and back whole (ingest_measure_range).
 struct Conditioning {
     bool level_on = false;     // gyp_ingest_set_level / gyp_ingest_calibrate
     gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
     gyp_notch_tones notches{};   // gyp_ingest_set_notches / gyp_ingest_find_tones
     bool blank_on = false;     // gyp_ingest_set_blanker / gyp_ingest_find_pulses
     gyp_blanker blanker{0.0f, 0.0f, 1.0f, 0};
-    // The conditioning of the blocks a measurement sees.  What is put aside is off but kept (a suspended blanker or level keeps its
+    bool excise_on = false;    // gyp_ingest_set_excisor / gyp_ingest_find_excisor
+    gyp_excisor excisor{1.0f, 0, {0, 0}};
+    // The conditioning of the blocks a measurement sees.  What is put aside is off but kept (a suspended blanker, excisor or level keeps its
     // values), except the notches, whose list is their switch.
     Conditioning without(Suspend what) const {
         Conditioning c = *this;
         c.level_on = false;
         if (what != Suspend::level) c.notches = gyp_notch_tones{};
+        if (what == Suspend::level_notches_excisor || what == Suspend::all) c.excise_on = false;
         if (what == Suspend::all) c.blank_on = false;
         return c;
     }
@@ -384,6 +388,8 @@ struct gyp_ingest {
     std::vector<DevBuf<float>> dev_iq;
     std::vector<DevBuf<int32_t>> dev_blanked;   // per slot: the blanker's count per millisecond of the slot's block (block_ms words)
     std::vector<uint8_t> slot_blanked;       // per slot: the block in it went through the blanker
+    std::vector<DevBuf<int32_t>> dev_excised;   // per slot, as dev_blanked: the excisor's count per millisecond (made when an excisor is first set)
+    std::vector<uint8_t> slot_excised;       // per slot: the block in it went through the excisor
     Stream counts_stream;            // gyp_ingest_last_blanked's download (made by its first call: it must not wait for anything else)
     int last_slot = -1;              // the device slot of the block most recently handed out (-1: none since open / seek)
     int32_t last_n_ms = 0;

@@ -29,6 +29,10 @@
 //   iq_blank_kernel / iq_power_hist_kernel   pulsed interference: per millisecond the hit bits of a power threshold through
 //                       __ballot into LDS, dilated by the guard and applied (in place only the blanked samples are stored), and
 //                       the eighth-octave histogram of the power the threshold is derived from, in integer atomics.
+//   iq_excise_kernel / iq_spectrum_hist_kernel   narrowband and swept interference: per millisecond half-overlapped 256-point
+//                       transforms, one wavefront per frame (radix 4, four points per lane, a 2 KiB LDS tile each); bins over a
+//                       threshold and their guard are transformed back and subtracted (in place only corrected hops are stored),
+//                       and the eighth-octave histogram of the bins' power the threshold is derived from, in integer atomics.
 //   track_quality_kernel   signal quality: per (channel, window) sums of a block's tracking records -- peak moments, lock count,
 //                       narrow/wide-band power ratios of 20-ms groups -- one wavefront each, in a fixed float64 reduction order.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
@@ -49,4 +53,5 @@
 #include "kernels_level.hpp"
 #include "kernels_notch.hpp"
 #include "kernels_blank.hpp"
+#include "kernels_excise.hpp"
 #include "kernels_quality.hpp"

@@ -247,10 +247,9 @@ static inline double blank_bin_edge(int32_t k) {
     return (double)f;
 }
 
-// gyp_blank_from_hist's arithmetic (the header states the order): float64, one rounding per operation.  nullptr, or
-// GYP_E_BAD_ARG's reason.
-static const char* blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
-                                   gyp_blanker* blanker_out, double* measured_out2) {
+// The median of a power histogram and t = sqrt(threshold_over_median * median), the arithmetic gyp_blank_from_hist and
+// gyp_excise_from_hist share (the header states the order): float64, one rounding per operation.  nullptr, or GYP_E_BAD_ARG's reason.
+static const char* hist_median_threshold(const uint32_t* hist, double threshold_over_median, double* median_out, double* t_out) {
 #pragma clang fp contract(off)
     constexpr int32_t kFinite = 2040;   // bins of finite p
     double M = 0.0;
@@ -270,7 +269,16 @@ static const char* blank_from_hist(const uint32_t* hist, float center_re, float 
     const double median = lo + step;
     if (!(median > 0.0)) return "the median power is not positive";
     const double scaled = threshold_over_median * median;
-    const double t = std::sqrt(scaled);
+    *median_out = median;
+    *t_out = std::sqrt(scaled);
+    return nullptr;
+}
+
+// gyp_blank_from_hist behind its argument checks.  nullptr, or GYP_E_BAD_ARG's reason.
+static const char* blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
+                                   gyp_blanker* blanker_out, double* measured_out2) {
+    double median = 0.0, t = 0.0;
+    if (const char* why = hist_median_threshold(hist, threshold_over_median, &median, &t)) return why;
     const gyp_blanker b = {center_re, center_im, (float)t, guard};
     if (blanker_check(&b)) return "the blanker does not fit float32 (centre not finite, or threshold zero or not finite)";
     *blanker_out = b;

@@ -433,6 +433,65 @@ class GypsumEngine:
             d_out.free()
         return out if x.ndim > 1 else out[0]
 
+    def excise_iq_dev(self, in_ptr: int, out_ptr: int, n_streams: int, stream_stride: int, n_ms: int, samples_per_ms: int, excisors,
+                      counts_ptr: int = 0, masks_ptr: int = 0) -> None:
+        """gyp_excise_iq_dev: per millisecond, half-overlapped 256-point transforms; what the bins that reach the threshold and `guard`
+        bins on either side held is subtracted, stream s with excisors[s] (gypsum_amd.excisor.Excisor); out_ptr may equal in_ptr;
+        counts_ptr (0: none) receives n_streams x n_ms int32 counts of excised (frame, bin) cells, masks_ptr (0: none) four uint64
+        words per (stream, millisecond, frame).  Enqueued, not synchronised."""
+        from .excisor import excisor_records
+        recs = excisor_records(excisors, n_streams)
+        if len(recs) != max(1, int(n_streams)):   # (a count below 1 is the library's to refuse)
+            raise ValueError(f"{len(recs)} excisors for {n_streams} streams")
+        self._check(self.lib.gyp_excise_iq_dev(self.ctx, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n_streams), int(stream_stride),
+                                               int(n_ms), int(samples_per_ms), ptr(recs), C.c_void_p(counts_ptr or None),
+                                               C.c_void_p(masks_ptr or None)))
+
+    def spectrum_hist_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, n_ms: int, samples_per_ms: int, hist_ptr: int) -> None:
+        """gyp_iq_spectrum_hist_dev: n_streams x 2048 uint32 counts of the bin powers of the frames that lie inside their millisecond,
+        in eighth-octave bins, into hist_ptr, which is zeroed first.  Enqueued, not synchronised."""
+        self._check(self.lib.gyp_iq_spectrum_hist_dev(self.ctx, C.c_void_p(iq_ptr), int(n_streams), int(stream_stride), int(n_ms),
+                                                      int(samples_per_ms), C.c_void_p(hist_ptr)))
+
+    def excise_iq(self, iq: np.ndarray, samples_per_ms: int, excisors):
+        """Host convenience: (complex64 `iq` excised over its whole milliseconds on the device, int32 counts [[n_streams,] n_ms],
+        uint64 masks [[n_streams,] n_ms, frames, 4]); 2-D = one stream per row, one excisor each or one for all; a trailing part of
+        a millisecond is returned as it is."""
+        from .excisor import n_frames
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        out = rows.copy()
+        n_ms = rows.shape[1] // int(samples_per_ms)
+        counts = np.zeros((rows.shape[0], n_ms), dtype=np.int32)
+        masks = np.zeros((rows.shape[0], n_ms, n_frames(samples_per_ms), 4), dtype=np.uint64)
+        if n_ms:
+            d = self.alloc(rows.nbytes).upload(rows)
+            d_counts, d_masks = self.alloc(counts.nbytes), self.alloc(masks.nbytes)
+            self.excise_iq_dev(d.ptr.value, d.ptr.value, rows.shape[0], rows.shape[1], n_ms, samples_per_ms, excisors, d_counts.ptr.value,
+                               d_masks.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d.ptr, out.nbytes))
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(counts), d_counts.ptr, counts.nbytes))
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(masks), d_masks.ptr, masks.nbytes))
+            for b in (d, d_counts, d_masks):
+                b.free()
+        return (out, counts, masks) if x.ndim > 1 else (out[0], counts[0], masks[0])
+
+    def spectrum_hist(self, iq: np.ndarray, samples_per_ms: int) -> np.ndarray:
+        """Host convenience: the uint32 histogram(s) [[n_streams,] 2048] of the bin powers of complex64 `iq` (2-D = one stream per
+        row) over its whole milliseconds of samples_per_ms >= 256 samples."""
+        x = _as_iq(iq)
+        rows = x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x.reshape(1, -1)
+        out = np.zeros((rows.shape[0], _lib.GYP_POWER_HIST_BINS), dtype=np.uint32)
+        d_iq = self.alloc(max(rows.nbytes, 8)).upload(rows)
+        d_out = self.alloc(out.nbytes)
+        try:
+            self.spectrum_hist_dev(d_iq.ptr.value, rows.shape[0], rows.shape[1], rows.shape[1] // int(samples_per_ms), samples_per_ms, d_out.ptr.value)
+            self._check(self.lib.gyp_memcpy_d2h(self.ctx, ptr(out), d_out.ptr, out.nbytes))
+        finally:
+            d_iq.free()
+            d_out.free()
+        return out if x.ndim > 1 else out[0]
+
     def track_quality_dev(self, rec_ptr: int, n_chan: int, chan_stride: int, n_ms: int, window_ms: int, out_ptr: int,
                           bit_offsets=None) -> None:
         """gyp_track_quality_dev: one gyp_quality_sums record per (channel, window of window_ms records) of tracking records in HBM,

@@ -24,6 +24,8 @@ produced it and the level: `calibrate` then measures the notched output.
 
 `set_blanker` / `find_pulses` (gypsum_amd.blanker) blank pulsed (wideband) interference in every device block, in front of the
 notches: `find_tones` and `calibrate` then measure the blanked output, and `last_blanked` counts what each block lost.
+`set_excisor` / `find_excisor` (gypsum_amd.excisor) excise narrowband and swept interference in every device block, behind the
+blanker and in front of the notches; `last_excised` counts the (frame, bin) cells each block lost.
 """
 from __future__ import annotations
 
@@ -208,6 +210,41 @@ class IqFileIngest:
         before the first block and after a seek; zeros while no blanker is on).  Waits for that block only (gyp_ingest_last_blanked)."""
         counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
         self._check(self._lib.gyp_ingest_last_blanked(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
+        return counts[:n_ms.value]
+
+    def set_excisor(self, excisor) -> None:
+        """A gypsum_amd.excisor.Excisor every device block is excised with from the next block handed out on, between the blanker
+        and the notches (gyp_ingest_set_excisor).  None switches it off."""
+        rec = None if excisor is None else excisor.record()
+        self._check(self._lib.gyp_ingest_set_excisor(self._h, _lib.ptr(rec)))
+
+    def get_excisor(self):
+        """The installed Excisor, or None while none is on (gyp_ingest_get_excisor)."""
+        from .excisor import EXCISOR_DTYPE, Excisor
+        rec, on = np.zeros(1, dtype=EXCISOR_DTYPE), C.c_int32()
+        self._check(self._lib.gyp_ingest_get_excisor(self._h, _lib.ptr(rec), C.byref(on)))
+        return Excisor.from_record(rec) if on.value else None
+
+    excisor = property(get_excisor)
+
+    def find_excisor(self, first_ms: int = 0, n_ms: int = 10, threshold_over_median: float = 16.0, guard: int = 1, install: bool = True):
+        """Measure output milliseconds [first_ms, first_ms + n_ms) of the handle's output (behind the blanker where one is on; no
+        excisor, no notches, no level) on the device -- the histogram of the bin powers of its 256-point frames -- and derive the
+        excisor whose threshold is sqrt(threshold_over_median x the median power).  Returns (Excisor, measured) as
+        gypsum_amd.excisor.excisor_from_hist does and installs it (install) as set_excisor does; the cursor stays where it was,
+        blocks handed out earlier are no longer valid (gyp_ingest_find_excisor)."""
+        from .excisor import EXCISOR_DTYPE, Excisor, measured_dict
+        rec, measured = np.zeros(1, dtype=EXCISOR_DTYPE), np.zeros(2)
+        self._check(self._lib.gyp_ingest_find_excisor(self._h, int(first_ms), int(n_ms), float(threshold_over_median), int(guard),
+                                                      int(bool(install)), _lib.ptr(rec), _lib.ptr(measured)))
+        return Excisor.from_record(rec), measured_dict(measured)
+
+    def last_excised(self) -> np.ndarray:
+        """int32 counts of excised (frame, bin) cells per millisecond of the block most recently handed out by next_device_block
+        (empty before the first block and after a seek; zeros while no excisor is on).  Waits for that block only
+        (gyp_ingest_last_excised)."""
+        counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
+        self._check(self._lib.gyp_ingest_last_excised(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
         return counts[:n_ms.value]
 
     def seek(self, ms: int) -> None:

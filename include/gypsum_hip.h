@@ -28,7 +28,11 @@
 extern "C" {
 #endif
 
-/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): pulsed (wideband)
+/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband and
+ *      swept interference that is no pure tone, excised in short overlapped transforms on the device: gyp_excisor, GYP_EXCISE_FRAME,
+ *      gyp_excise_iq_dev, gyp_iq_spectrum_hist_dev, gyp_excise_from_hist, gyp_ingest_set_excisor, gyp_ingest_get_excisor,
+ *      gyp_ingest_find_excisor, gyp_ingest_last_excised.  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): pulsed (wideband)
  *      interference on the device: gyp_blanker, GYP_POWER_HIST_BINS, gyp_blank_iq_dev, gyp_iq_power_hist_dev, gyp_blank_from_hist,
  *      gyp_ingest_set_blanker, gyp_ingest_get_blanker, gyp_ingest_find_pulses, gyp_ingest_last_blanked.  Opt-in.
  * 209 (additions; the number stays): gyp_debug_get's read-only "last_acq_lanes", "last_acq_levels", "last_acq_shared_levels" (what the last
@@ -934,7 +938,7 @@ int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, 
 
 /* A blanker on an ingest handle (ctx required: a host-only handle returns GYP_E_BAD_ARG from all four, and gyp_ingest_next_host
  * returns GYP_E_BAD_ARG while a blanker is on).  CHAIN ORDER of a handle: producer (widen / unpack / resample / down-convert /
- * copy) -> blanker -> notches -> level.  Every device block is blanked in place on the upload stream exactly as gyp_blank_iq_dev
+ * copy) -> blanker -> [excisor, below ->] notches -> level.  Every device block is blanked in place on the upload stream exactly as gyp_blank_iq_dev
  * would, at the handle's output rate; gyp_ingest_find_tones and gyp_ingest_calibrate then measure the blanked output.  A pulse
  * that a resampler or down-converter of T taps has smeared over T samples is covered by a guard of T / 2.
  * gyp_ingest_set_blanker (NULL: off) follows gyp_ingest_set_level: it takes effect with the next block handed out, and what was
@@ -955,6 +959,94 @@ int gyp_ingest_find_pulses(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, int3
  * into counts_out, its n_ms into *n_ms_out (0 before the first block and after a seek).  Zeros while no blanker is on.  The call
  * waits for that block's upload chain only, not for blocks uploaded ahead and not for the context's stream. */
 int gyp_ingest_last_blanked(gyp_ingest* ing, int32_t* counts_out, int32_t cap, int32_t* n_ms_out);
+
+/* ---------------------------------------------------------------- excisor: narrowband and swept interference -- */
+/* Continuous interference that is narrow but no pure tone -- a carrier with FM or AM on it, a narrowband digital signal, a spur
+ * that drifts by kHz per millisecond, a slow swept jammer, more tones than a notch list holds -- passes the notches (a
+ * one-millisecond projection onto a fixed frequency cannot follow it) and the blanker (it is always on), and the level then
+ * scales the recording by the jammer's power.  The excisor takes short overlapped transforms, zeroes the bins that stand above
+ * the noise and subtracts what they held; it adapts every 128 samples and needs no frequency list.  Three steps: a histogram of
+ * the bins' power on the device (gyp_iq_spectrum_hist_dev), a threshold from its median on the host (gyp_excise_from_hist), the
+ * excision (gyp_excise_iq_dev, or gyp_ingest_set_excisor / gyp_ingest_find_excisor on an ingest handle).  Everything is opt-in:
+ * with none of these called every other entry point gives the bits it gave before.
+ *
+ * Framing.  Per (stream, millisecond of n = samples_per_ms samples), a pure function of that millisecond's samples and the
+ * stream's excisor, so blocks, windows, seeks and call shapes give identical samples.  L = GYP_EXCISE_FRAME = 256, hop 128.
+ * Frame f covers the millisecond's samples 128 f - 128 .. 128 f + 127; samples outside 0 .. n - 1 are zero; f = 0 .. nf - 1 with
+ * nf = ceil((n + 128) / 128): every sample lies in exactly two frames.
+ * Analysis.  w[k] = sin^2(pi k / 256) (periodic Hann: w[k] + w[k + 128] = 1), evaluated in float64 and rounded to float32;
+ * X_f = FFT256(w x_f), not normalised, in float32;  p_k = re re + im im in float32, one rounding per operation.
+ * Decision.  t2 = threshold threshold (one float32 product).  Bin k is a HIT iff p_k >= t2 (equality is a hit; a NaN is not).
+ * Bin k is EXCISED iff some hit j has min(|k - j|, 256 - |k - j|) <= guard: the guard is circular, the spectrum wraps at +- fs/2.
+ * Removal.  E_f = X_f on the excised bins, 0 elsewhere;  e_f = IFFT256(E_f) / 256.  For sample i with covering frames f < f + 1:
+ * c = e_f[i] + e_(f+1)[i] (the lower frame first), y[i] = x[i] - c, float32, no contraction.  A frame without an excised bin
+ * contributes nothing (c is then the other frame's term alone), and a sample whose two frames both have none KEEPS ITS BITS, NaN
+ * payloads and -0 included; in place such a sample is not written.  The synthesis window is the identity and no re-synthesised
+ * copy of the signal is subtracted, only what the excised bins held: no float32 transform error reaches a sample that needed
+ * nothing.  The transform's own rounding (a radix-4 float32 transform, about 1e-6 of a frame's norm) is the only freedom an
+ * implementation has; decisions within that of t2 may differ between implementations, never between call shapes.
+ * Edge cost.  The first and the last frame of a millisecond see half a window of zeros: an interferer is found 3 dB later
+ * there, and up to 128 samples at either edge of a millisecond are cleaned less well -- the counterpart of the blanker's guard
+ * not crossing millisecond edges.
+ * Out of scope.  Fast "privacy device" chirps that cross the whole band within a frame (10 MHz in ~9 us) look broadband in every
+ * frame and are not addressed. */
+#define GYP_EXCISE_FRAME 256
+typedef struct gyp_excisor {      /* one per stream: 16 bytes */
+    float threshold;              /* positive, finite: an amplitude of |X_f[k]| */
+    int32_t guard;                /* 0..8 bins excised on either side of every hit, round the ring of 256 */
+    int32_t reserved[2];          /* must be 0 */
+} gyp_excisor;
+/* n_ms milliseconds of each of n_streams streams (stream s at sample s * stream_stride_samples of both buffers), stream s with
+ * excisors_host[s].  out_dev may equal in_dev (then only corrected samples are written); other overlaps are not allowed.
+ * counts_out_dev (may be NULL) receives n_streams x n_ms int32 counts of excised (frame, bin) cells per millisecond, stream-major.
+ * masks_out_dev (may be NULL) receives, per (stream, millisecond, frame) in that order, four uint64 words: bit k & 63 of word
+ * k >> 6 is set when bin k of the frame was excised -- the interference waterfall.  Any 8-byte aligned address and any stride;
+ * rows are read and written 8 bytes per lane, 512 contiguous bytes per wavefront, whatever their alignment.  samples_per_ms is an
+ * argument, no stream format is needed.  Enqueued on the context's stream; excisors_host may be reused as soon as the call
+ * returns.  GYP_E_BAD_ARG, before anything is launched, for NULL pointers, n_streams < 1, samples_per_ms < 1 or > 65536, n_ms < 0,
+ * a stride below n_ms * samples_per_ms when n_streams > 1, a threshold that is not positive and finite, a guard outside 0..8, or
+ * reserved words that are not 0. */
+int gyp_excise_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                      int32_t samples_per_ms, const gyp_excisor* excisors_host, int32_t* counts_out_dev, uint64_t* masks_out_dev);
+
+/* The histogram of p_k (as above) over n_ms milliseconds of each stream: n_streams x GYP_POWER_HIST_BINS uint32 counts into
+ * hist_out_dev, which the call zeroes first.  Binning is that of gyp_iq_power_hist_dev: the bits of p without the sign, shifted
+ * right by 20.  Only frames that lie ENTIRELY INSIDE their millisecond are counted (f >= 1 and 128 f + 128 <= n): a frame half
+ * of zeros has half the noise power and would pull the median down.  Integer atomics: histograms of parts of a stream add up to
+ * the whole's.  Enqueued on the context's stream.  GYP_E_BAD_ARG for NULL pointers, n_streams < 1, n_ms < 1, samples_per_ms < 256
+ * or > 65536, or a stride below n_ms * samples_per_ms when n_streams > 1. */
+int gyp_iq_spectrum_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t n_ms,
+                             int32_t samples_per_ms, uint32_t* hist_out_dev);
+
+/* Host only (no GPU; errors through gyp_last_error(NULL)): the excisor whose threshold is sqrt(threshold_over_median x the median
+ * of p) from one stream's histogram: the median and t arithmetic of gyp_blank_from_hist, in the same order and with the same
+ * roundings.  excisor_out = {(float)t, guard, {0, 0}};  measured_out2 (may be NULL) = {median, t}.  For complex Gaussian noise a
+ * bin's power is exponential, so a factor of 16 excises one clean bin in 65536.  GYP_E_BAD_ARG for NULL hist or excisor_out,
+ * M = 0, a median that is not positive, a factor that is not positive and finite, a guard outside 0..8, or a threshold that
+ * float32 cannot hold. */
+int gyp_excise_from_hist(const uint32_t* hist, double threshold_over_median, int32_t guard, gyp_excisor* excisor_out, double* measured_out2);
+
+/* An excisor on an ingest handle (ctx required: a host-only handle returns GYP_E_BAD_ARG from all four, and gyp_ingest_next_host
+ * returns GYP_E_BAD_ARG while an excisor is on).  CHAIN ORDER of a handle: producer -> blanker -> excisor -> notches -> level.
+ * Every device block is excised in place on the upload stream exactly as gyp_excise_iq_dev would, at the handle's output rate
+ * (at most 65536 samples per millisecond).  With an excisor installed, and only then, gyp_ingest_find_tones and
+ * gyp_ingest_calibrate measure the EXCISED output.  gyp_ingest_set_excisor (NULL: off) follows gyp_ingest_set_blanker: it takes
+ * effect with the next block handed out, and what was uploaded ahead is dropped and read again. */
+int gyp_ingest_set_excisor(gyp_ingest* ing, const gyp_excisor* excisor);
+int gyp_ingest_get_excisor(const gyp_ingest* ing, gyp_excisor* out, int32_t* enabled_out);
+/* Measures output milliseconds [first_ms, first_ms + n_ms) of the handle (inside [0, total_ms), 1 <= n_ms <= 1000; at least 256
+ * samples per millisecond) and derives an excisor.  What is measured is the handle's output WITHOUT excisor, notches and level --
+ * the blanked output where a blanker is installed -- read through the handle's own path into one buffer, so the result does not
+ * depend on block_ms: gyp_iq_spectrum_hist_dev, then gyp_excise_from_hist with threshold_over_median and guard.  With
+ * install != 0 the excisor is installed as gyp_ingest_set_excisor does.  excisor_out / measured_out2 (either may be NULL) receive
+ * what gyp_excise_from_hist wrote.  The cursor is put back, the call synchronises, and blocks handed out earlier are no longer
+ * valid afterwards.  On any error the handle keeps everything it had. */
+int gyp_ingest_find_excisor(gyp_ingest* ing, int64_t first_ms, int32_t n_ms, double threshold_over_median, int32_t guard, int32_t install,
+                            gyp_excisor* excisor_out, double* measured_out2);
+/* The excised (frame, bin) cells per millisecond of the block most recently handed out by gyp_ingest_next_dev: min(cap, its n_ms)
+ * counts into counts_out, its n_ms into *n_ms_out (0 before the first block and after a seek).  Zeros while no excisor is on.
+ * The call waits for that block's upload chain only. */
+int gyp_ingest_last_excised(gyp_ingest* ing, int32_t* counts_out, int32_t cap, int32_t* n_ms_out);
 
 /* ---------------------------------------------------------------- signal quality: C/N0 and carrier lock -- */
 /* A receiver reports a carrier-to-noise density per tracked satellite.  gyp_track_rec carries the raw prompt peak and the
