@@ -61,6 +61,11 @@ QUALITY = np.dtype([("cn0_m2m4_dbhz", "<f8"), ("cn0_nwpr_dbhz", "<f8"), ("phase_
                     ("n_used", "<i4"), ("n_groups", "<i4")], align=True)
 BLANKER = np.dtype([("center_re", "<f4"), ("center_im", "<f4"), ("threshold", "<f4"), ("guard", "<i4")], align=True)
 EXCISOR = np.dtype([("threshold", "<f4"), ("guard", "<i4"), ("reserved", "<i4", (2,))], align=True)
+HYBRID_CELL = np.dtype([("peak", "<f4"), ("argmax", "<i4"), ("second", "<f4"), ("second_argmax", "<i4"), ("n_off", "<i4"), ("set", "<i4"),
+                        ("sum_off", "<f8"), ("sumsq_off", "<f8"), ("blocks_used", "<i4"), ("reserved", "<i4")], align=True)
+WEAK_RESULT = np.dtype([("stream", "<i4"), ("sat_id", "<i4"), ("doppler_hz", "<f8"), ("code_phase", "<i4"), ("reserved0", "<i4"),
+                        ("carrier_phase", "<f8"), ("z", "<f8"), ("peak_ratio", "<f8"), ("set", "<i4"), ("reserved", "<i4")], align=True)
+GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER = 1, 2
 GYP_POWER_HIST_BINS = 2048
 GYP_EXCISE_FRAME = 256
 GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
@@ -76,7 +81,7 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize,
                 "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize,
                 "gyp_quality_sums": QUALITY_SUMS.itemsize, "gyp_quality": QUALITY.itemsize, "gyp_blanker": BLANKER.itemsize,
-                "gyp_excisor": EXCISOR.itemsize}
+                "gyp_excisor": EXCISOR.itemsize, "gyp_hybrid_cell": HYBRID_CELL.itemsize, "gyp_weak_result": WEAK_RESULT.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -98,7 +103,8 @@ EXPORTS = (
     "gyp_blank_iq_dev gyp_iq_power_hist_dev gyp_blank_from_hist gyp_ingest_set_blanker gyp_ingest_get_blanker gyp_ingest_find_pulses "
     "gyp_ingest_last_blanked "
     "gyp_excise_iq_dev gyp_iq_spectrum_hist_dev gyp_excise_from_hist gyp_ingest_set_excisor gyp_ingest_get_excisor gyp_ingest_find_excisor "
-    "gyp_ingest_last_excised"
+    "gyp_ingest_last_excised "
+    "gyp_hybrid_stats gyp_hybrid_shift gyp_correlate_grid_hybrid_dev gyp_correlate_grid_hybrid gyp_acquire_weak_dev gyp_acquire_weak"
 ).split()
 
 
@@ -250,6 +256,12 @@ def load() -> C.CDLL:
         "gyp_ingest_get_excisor": (C.c_int, [vp, vp, C.POINTER(i32)]),
         "gyp_ingest_find_excisor": (C.c_int, [vp, i64, i32, dbl, i32, i32, vp, vp]),
         "gyp_ingest_last_excised": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
+        "gyp_hybrid_stats": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
+        "gyp_hybrid_shift": (i32, [i32, i32, i32, dbl, i32]),
+        "gyp_correlate_grid_hybrid_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, i32, vp]),
+        "gyp_correlate_grid_hybrid": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
+        "gyp_acquire_weak_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, dbl, dbl, dbl, vp, i32, vp]),
+        "gyp_acquire_weak": (C.c_int, [vp, vp, i32, i32, i32, i32, dbl, dbl, dbl, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

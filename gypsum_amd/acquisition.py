@@ -16,7 +16,7 @@ from typing import Any, Dict, List
 
 import numpy as np
 
-from ._lib import CELL_DESC, GYP_NON_COHERENT
+from ._lib import CELL_DESC, GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER, GYP_NON_COHERENT
 from .antenna_sample_provider import SampleProviderAttributes
 from .engine import default_engine
 from .gps_ca_prn_codes import GpsSatelliteId
@@ -26,6 +26,13 @@ _logger = logging.getLogger(__name__)
 
 # config.py:7
 ACQUISITION_INTEGRATED_CORRELATION_STRENGTH_DETECTION_THRESHOLD = 3
+
+# The weak-signal search (detect_weak_satellites_in_antenna_data).  The default threshold on z is measured, not derived: the largest
+# z of the float64 model on noise alone at the default configuration (2.046 Msps, 10-ms blocks, both flags, 200 ms, +-7 kHz, 32
+# satellites) over 8 seeds was 10.75 (tools/hybrid_threshold.py; DESIGN.md lists the eight values), times 1.25.
+DEFAULT_WEAK_Z_THRESHOLD = 13.4375
+WEAK_SEARCH_SPREAD_HZ = 7000.0
+WEAK_SEARCH_FINE_STEP_HZ = 10.0
 
 
 @dataclass
@@ -81,6 +88,29 @@ class GpsSatelliteDetector:
                 _logger.info(f"Correlation strength above threshold, successfully detected satellite {result.satellite_id}!")
                 detected.append(result)
         return detected
+
+    def detect_weak_satellites_in_antenna_data(self, satellites_to_search_for: List[Any], antenna_data: np.ndarray,
+                                               stream_attributes: SampleProviderAttributes, coherent_ms: int = 10, n_blocks: int | None = None,
+                                               z_threshold: float = DEFAULT_WEAK_Z_THRESHOLD) -> List[SatelliteAcquisitionAttemptResult]:
+        """Satellites too weak for detect_satellites_in_antenna_data (below about 38 dB-Hz): the hybrid coherent/non-coherent search of
+        gyp_acquire_weak over n_blocks blocks of coherent_ms milliseconds (None: all the full blocks of antenna_data), alternating
+        half-bit sets and code-Doppler alignment on, +-7 kHz coarse and 10 Hz fine.  Results with z above z_threshold, in search
+        order; correlation_strength is z (NOT the strength the other method compares with 3)."""
+        n = stream_attributes.samples_per_prn_transmission
+        sats = list(satellites_to_search_for)
+        if n_blocks is None:
+            n_blocks = len(antenna_data) // (n * int(coherent_ms))
+        if not sats or n_blocks < 2:
+            if sats:
+                raise RuntimeError("the weak-signal search needs at least two full blocks of coherent_ms milliseconds")
+            return []
+        iq = np.asarray(antenna_data)[:n_blocks * int(coherent_ms) * n]
+        rec = self._engine(stream_attributes).acquire_weak(iq, 1, int(coherent_ms), int(n_blocks), GYP_HYB_ALTERNATE | GYP_HYB_CODE_DOPPLER,
+                                                           [_sv(s) for s in sats], 0.0, WEAK_SEARCH_SPREAD_HZ, WEAK_SEARCH_FINE_STEP_HZ)
+        return [SatelliteAcquisitionAttemptResult(
+            satellite_id=sid, doppler_shift=float(r["doppler_hz"]), carrier_wave_phase_shift=float(r["carrier_phase"]),
+            prn_phase_shift=int(r["code_phase"]), correlation_strength=float(r["z"]))
+            for sid, r in zip(sats, rec) if float(r["z"]) > z_threshold]
 
     def _attempt_acquisition_for_satellite_id(self, satellite_id: Any, samples_for_integration_period: np.ndarray,
                                               stream_attributes: SampleProviderAttributes) -> SatelliteAcquisitionAttemptResult:

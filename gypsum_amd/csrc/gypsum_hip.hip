@@ -135,10 +135,25 @@ static thread_local std::string g_create_error;
 //   partial64                 float64 per-millisecond sums: gyp_grid_best_bins_refined_dev, acquire_search
 //   acq_*                     acquire_search (gyp_acquire_dev, gyp_search_level_dev), sized by its AcqPlan and reserved in acq_reserve: search states, cell table, cell outputs, refined sums, float64 profiles, acq_book_layout, acq_units_layout, shared-forward spectra
 //   synth_scene, bench_sink   gyp_synth_iq_dev, gyp_debug_fft_bench
+//   hyb_sat_ids, hyb_doppler, hyb_grid_cells   gyp_correlate_grid_hybrid_dev: satellite ids, Doppler bins and the cell table made of them
+//   hyb_cell_out, hyb_profile, hyb_power   hybrid_run (behind both hybrid entry points): per chunk of cells the gyp_cell records the
+//                             cells kernel must write somewhere, a block's coherent profiles, the sets' power rows
+//   hyb_level_cells, hyb_records, hyb_taps   gyp_acquire_weak_dev: the cell tables of the coarse level, the fine level and the final
+//                             cells (back to back), the larger level's records, the final cells' gyp_cell records (their taps)
 // Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
-// wrapper calls another; of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
+// wrapper calls another (the hybrid wrappers gyp_correlate_grid_hybrid and gyp_acquire_weak use stage_iq and stage_out like the
+// others); of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
 // none calls another, and what acquire_search calls (launch_cells, launch_cells_shared, gyp_correlate_cells_dev) uses no member.
+// hybrid_run serves one of gyp_correlate_grid_hybrid_dev and gyp_acquire_weak_dev at a time, neither calls the other, and its
+// launch_cells uses no member; the hyb_* members have no user outside the hybrid entry points.
 struct Scratch {
+    DevBuf<int32_t> hyb_sat_ids;
+    DevBuf<double> hyb_doppler;
+    DevBuf<gyp_cell_desc> hyb_grid_cells, hyb_level_cells;
+    DevBuf<gyp_cell> hyb_cell_out, hyb_taps;
+    DevBuf<cf> hyb_profile;
+    DevBuf<float> hyb_power;
+    DevBuf<gyp_hybrid_cell> hyb_records;
     DevBuf<float> stage_iq, stage_profile, bench_sink;
     DevBuf<uint8_t> stage_in, stage_out, refine_list, acq_book, acq_units;
     DevBuf<double> stage_times, doppler, partial64, acq_refined, acq_profiles;
@@ -192,6 +207,8 @@ struct gyp_ctx {
     int grid_fused_waves = 12;    // 12 (default) or 8 wavefronts per workgroup of the fused flat-grid kernel (A/B)
     bool no_grid_fused = false;   // A/B switch: flat grids go through grid_fold_kernel + folded rows in HBM (r05) instead of the fused kernel
     bool no_grid_parts = false;   // A/B switch: flat-grid work items take whole units (no branch runs + merge)
+    int hybrid_scratch_mb = kHybScratchMbDefault;   // "hybrid_scratch_mb": budget of hybrid_run's profile + power scratch (same records for any value)
+    HybPlan last_hybrid_plan{};   // of the last hybrid_run; gyp_debug_get("last_hybrid_chunks") reads its n_chunks
     std::string err;
     // stream format
     int64_t fs = 0;
@@ -263,6 +280,11 @@ struct DebugFlag { const char* name; bool gyp_ctx::*field; bool inherited; };
 static const DebugFlag kDebugFlags[] = {
     {"notch_no_lds", &gyp_ctx::notch_no_lds, false},
     {"track_finish_all", &gyp_ctx::track_finish_all, true},
+};
+// The integer switches added since then: set, read and range-checked like a row of the table, with the same message.
+struct DebugInt { const char* name; int gyp_ctx::*field; int lo, hi; };
+static const DebugInt kDebugInts[] = {
+    {"hybrid_scratch_mb", &gyp_ctx::hybrid_scratch_mb, kHybScratchMbMin, kHybScratchMbMax},
 };
 
 struct gyp_bank {
@@ -1310,6 +1332,187 @@ int gyp_acquire(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n
     });
 }
 
+// ---------------------------------------------------------------- weak-signal acquisition -----------------
+}   // extern "C"
+static int refuse(gyp_ctx* ctx, const char* who, const std::string& why);
+// What both hybrid entry points refuse (hybrid_plan.hpp: hybrid_refusal), before anything is reserved or launched.
+static int hybrid_check(gyp_ctx* ctx, const char* who, const void* iq, const void* out, int32_t n_streams, int64_t stream_stride_samples,
+                        int32_t coherent_ms, int32_t n_blocks, int32_t flags, const int32_t* sat_ids_host, int32_t n_sats) {
+    if (!iq || !out || !sat_ids_host || n_streams <= 0 || n_sats <= 0 || stream_stride_samples < 0) return refuse(ctx, who, "bad argument");
+    if (const char* why = hybrid_refusal(coherent_ms, n_blocks, flags)) return refuse(ctx, who, why);
+    return check_sat_ids(ctx, sat_ids_host, n_sats);
+}
+
+// The records of n_cells cells (device table) into out_dev: the cells go through in chunks that fit the scratch budget; per chunk
+// every block's coherent profiles (the cells launch, unchanged, given the block as its whole buffer) are added into the power rows
+// of the block's set, in increasing block order, then reduced.  Enqueues only; the scratch is reserved before the first launch.
+static int hybrid_run(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, int32_t coherent_ms, int32_t n_blocks, int32_t flags,
+                      const gyp_cell_desc* cells_dev, int64_t n_cells, gyp_hybrid_cell* out_dev) {
+    const HybPlan pl = hybrid_plan(HybShape{ctx->n, n_cells, coherent_ms, n_blocks, flags}, ctx->hybrid_scratch_mb);
+    if (!pl.fits) return fail(ctx, GYP_E_BAD_ARG, "hybrid search: the request does not fit (more than 2^31 - 1 cells?)");
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.hyb_cell_out.reserve((size_t)pl.chunk_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_profile.reserve(pl.profile, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_power.reserve(pl.power, Slack::grow, ctx->stream));
+    for (int64_t c0 = 0; c0 < n_cells; c0 += pl.chunk_cells) {
+        const int32_t nc = (int32_t)std::min<int64_t>(pl.chunk_cells, n_cells - c0);
+        HybAccParams a;
+        a.profile = sc.hyb_profile.get();
+        a.power = sc.hyb_power.get();
+        a.cells = cells_dev + c0;
+        a.n = ctx->n; a.coherent_ms = coherent_ms; a.flags = flags; a.n_sets = pl.n_sets;
+        for (int32_t b = 0; b < n_blocks; ++b) {
+            const float* block = iq_dev + (int64_t)b * coherent_ms * ctx->n * 2;
+            if (const int rc = launch_cells(ctx, cells_params(ctx, block, stream_stride_samples, coherent_ms, cells_dev + c0, nc, sc.hyb_cell_out.get(),
+                                                              reinterpret_cast<float*>(sc.hyb_profile.get()), nullptr, nullptr), GYP_COHERENT))
+                return rc;
+            a.block = b;
+            hipLaunchKernelGGL(hybrid_accumulate_kernel, dim3((unsigned)pl.acc_x, (unsigned)nc), dim3(256), 0, ctx->stream, a);
+            if (const int rc = launched(ctx)) return rc;
+        }
+        hipLaunchKernelGGL(hybrid_reduce_kernel, dim3((unsigned)nc), dim3(256), 0, ctx->stream, (const float*)sc.hyb_power.get(), ctx->n, pl.n_sets,
+                           n_blocks, out_dev + c0);
+        if (const int rc = launched(ctx)) return rc;
+    }
+    ctx->last_hybrid_plan = pl;
+    return GYP_OK;
+}
+extern "C" {
+
+int gyp_hybrid_stats(const gyp_hybrid_cell* c, double* z_out, double* peak_ratio_out) {
+    if (!c) return fail(nullptr, GYP_E_BAD_ARG, "gyp_hybrid_stats: NULL record");
+    if (z_out) *z_out = hybrid_z(c->peak, c->n_off, c->sum_off, c->sumsq_off);
+    if (peak_ratio_out) *peak_ratio_out = (double)c->peak / (double)c->second;
+    return GYP_OK;
+}
+
+int gyp_hybrid_shift(int32_t n, int32_t coherent_ms, int32_t block, double doppler_hz, int32_t flags) {
+    return hybrid_shift(n, coherent_ms, block, doppler_hz, flags);
+}
+
+int gyp_correlate_grid_hybrid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t coherent_ms,
+                                  int32_t n_blocks, int32_t flags, const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host,
+                                  int32_t n_bins, gyp_hybrid_cell* out_dev) {
+    static const char* const who = "gyp_correlate_grid_hybrid_dev";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    if (!doppler_hz_host || n_bins <= 0) return refuse(ctx, who, "bad argument");
+    if (const int rc = hybrid_check(ctx, who, iq_dev, out_dev, n_streams, stream_stride_samples, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
+    for (int i = 0; i < n_bins; ++i)
+        if (!std::isfinite(doppler_hz_host[i])) return refuse(ctx, who, "a Doppler bin is not finite");
+    const int64_t n_cells = (int64_t)n_streams * n_sats * n_bins;
+    if (n_cells > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 cells");
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.hyb_grid_cells.reserve((size_t)n_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.hyb_sat_ids, sat_ids_host, (size_t)n_sats, ctx->stream));
+    HIP_TRY(ctx, upload(sc.hyb_doppler, doppler_hz_host, (size_t)n_bins, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host arrays may be temporaries
+    hipLaunchKernelGGL(hybrid_grid_cells_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t*)sc.hyb_sat_ids.get(),
+                       (const double*)sc.hyb_doppler.get(), n_sats, n_bins, (int32_t)n_cells, sc.hyb_grid_cells.get());
+    if (const int rc = launched(ctx)) return rc;
+    return hybrid_run(ctx, iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, sc.hyb_grid_cells.get(), n_cells, out_dev);
+}
+
+int gyp_correlate_grid_hybrid(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t coherent_ms, int32_t n_blocks, int32_t flags,
+                              const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host, int32_t n_bins,
+                              gyp_hybrid_cell* out_host) {
+    static const char* const who = "gyp_correlate_grid_hybrid";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    if (!doppler_hz_host || n_bins <= 0) return refuse(ctx, who, "bad argument");
+    if (const int rc = hybrid_check(ctx, who, iq_host, out_host, n_streams, 0, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
+    const int64_t n_cells = (int64_t)n_streams * n_sats * n_bins;
+    if (n_cells > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 cells");
+    Scratch& sc = ctx->scratch;
+    const int32_t n_ms = n_blocks * coherent_ms;
+    const size_t out_bytes = (size_t)n_cells * sizeof(gyp_hybrid_cell);
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    if (const int rc = gyp_correlate_grid_hybrid_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, coherent_ms, n_blocks, flags, sat_ids_host,
+                                                     n_sats, doppler_hz_host, n_bins, (gyp_hybrid_cell*)sc.stage_out.get()))
+        return rc;
+    return stage_back(ctx, out_host, out_bytes);
+}
+
+int gyp_acquire_weak_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t coherent_ms,
+                         int32_t n_blocks, int32_t flags, double center_hz, double spread_hz, double fine_step_hz,
+                         const int32_t* sat_ids_host, int32_t n_sats, gyp_weak_result* out_dev) {
+    static const char* const who = "gyp_acquire_weak_dev";
+    constexpr int kMaxLevelBins = 4096;
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    if (const int rc = hybrid_check(ctx, who, iq_dev, out_dev, n_streams, stream_stride_samples, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
+    if (n_sats > 32) return refuse(ctx, who, "at most 32 satellites per call");
+    if (!std::isfinite(center_hz) || !std::isfinite(spread_hz) || !std::isfinite(fine_step_hz) || !(spread_hz > 0.0))
+        return refuse(ctx, who, "center, spread and fine step must be finite and the spread positive");
+    const int n_coarse = hybrid_coarse_bins(center_hz, spread_hz, coherent_ms), half = hybrid_fine_half(fine_step_hz, coherent_ms);
+    const int n_fine = half >= 0 ? 2 * half + 1 : 0;
+    if (n_coarse < 1 || n_coarse > kMaxLevelBins || n_fine > kMaxLevelBins) return refuse(ctx, who, "a level must have between 1 and 4096 Doppler bins");
+    const int64_t n_states = (int64_t)n_streams * n_sats;
+    if (n_states * std::max(n_coarse, n_fine) > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 cells");
+    Scratch& sc = ctx->scratch;
+    const size_t states = (size_t)n_states, coarse_cells = states * n_coarse, fine_cells = states * n_fine;
+    HIP_TRY(ctx, sc.hyb_level_cells.reserve(coarse_cells + fine_cells + states, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_records.reserve(std::max(coarse_cells, fine_cells), Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_taps.reserve(states, Slack::grow, ctx->stream));
+    {   // hybrid_run's scratch for the larger level now: a buffer that grew between the levels would wait for the stream
+        const HybPlan big = hybrid_plan(HybShape{ctx->n, (int64_t)std::max(coarse_cells, fine_cells), coherent_ms, n_blocks, flags}, ctx->hybrid_scratch_mb);
+        HIP_TRY(ctx, sc.hyb_cell_out.reserve((size_t)big.chunk_cells, Slack::grow, ctx->stream));
+        HIP_TRY(ctx, sc.hyb_profile.reserve(big.profile, Slack::grow, ctx->stream));
+        HIP_TRY(ctx, sc.hyb_power.reserve(big.power, Slack::grow, ctx->stream));
+    }
+    gyp_cell_desc* const cells0 = sc.hyb_level_cells.get();
+    gyp_cell_desc* const cells1 = cells0 + coarse_cells;
+    gyp_cell_desc* const cells_final = cells1 + fine_cells;
+    const dim3 sgrid((unsigned)((n_states + 63) / 64));
+    HybSatIds ids{};
+    for (int i = 0; i < n_sats; ++i) ids.v[i] = sat_ids_host[i];
+    hipLaunchKernelGGL(hybrid_coarse_cells_kernel, sgrid, dim3(64), 0, ctx->stream, ids, n_sats, (int32_t)n_states, n_coarse, center_hz, spread_hz, coherent_ms, cells0);
+    if (const int rc = launched(ctx)) return rc;
+    if (const int rc = hybrid_run(ctx, iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, cells0, (int64_t)coarse_cells, sc.hyb_records.get())) return rc;
+    HybSelectParams sp;
+    sp.recs = sc.hyb_records.get();
+    sp.cells = cells0;
+    sp.n_states = (int32_t)n_states; sp.n_bins = n_coarse;
+    sp.next_half = half; sp.next_step = fine_step_hz;
+    sp.next_cells = half >= 0 ? cells1 : cells_final;
+    sp.out = out_dev;
+    hipLaunchKernelGGL(hybrid_select_kernel, sgrid, dim3(64), 0, ctx->stream, sp);
+    if (const int rc = launched(ctx)) return rc;
+    if (half >= 0) {
+        if (const int rc = hybrid_run(ctx, iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, cells1, (int64_t)fine_cells, sc.hyb_records.get())) return rc;
+        sp.cells = cells1;
+        sp.n_bins = n_fine;
+        sp.next_half = -1;
+        sp.next_cells = cells_final;
+        hipLaunchKernelGGL(hybrid_select_kernel, sgrid, dim3(64), 0, ctx->stream, sp);
+        if (const int rc = launched(ctx)) return rc;
+    }
+    // the coherent pass of the final bin over block 0, for the carrier phase at the code phase (the tap)
+    if (const int rc = launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, coherent_ms, cells_final, (int32_t)n_states, sc.hyb_taps.get(), nullptr, nullptr, nullptr), GYP_COHERENT))
+        return rc;
+    hipLaunchKernelGGL(hybrid_finish_kernel, sgrid, dim3(64), 0, ctx->stream, (const gyp_cell*)sc.hyb_taps.get(), (int32_t)n_states, out_dev);
+    return launched(ctx);
+}
+
+int gyp_acquire_weak(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t coherent_ms, int32_t n_blocks, int32_t flags,
+                     double center_hz, double spread_hz, double fine_step_hz, const int32_t* sat_ids_host, int32_t n_sats,
+                     gyp_weak_result* out_host) {
+    static const char* const who = "gyp_acquire_weak";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    if (const int rc = hybrid_check(ctx, who, iq_host, out_host, n_streams, 0, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
+    Scratch& sc = ctx->scratch;
+    const int32_t n_ms = n_blocks * coherent_ms;
+    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_weak_result);
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    if (const int rc = gyp_acquire_weak_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, coherent_ms, n_blocks, flags, center_hz, spread_hz,
+                                            fine_step_hz, sat_ids_host, n_sats, (gyp_weak_result*)sc.stage_out.get()))
+        return rc;
+    return stage_back(ctx, out_host, out_bytes);
+}
+
 // ---------------------------------------------------------------- tracking: explicit millisecond ----------
 int gyp_track_step_dev(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_samples, const double* start_time_dev,
                        const gyp_chan_in* chans_dev, int32_t n_chan, gyp_chan_out* out_dev, float* profile_out_dev) {
@@ -1923,6 +2126,7 @@ static int debug_read_only(gyp_ctx* ctx, const char* name, double* out) {
     if (is("last_acq_lanes")) { *out = (double)ctx->last_acq_plan.lanes; return GYP_OK; }
     if (is("last_acq_levels")) { *out = (double)ctx->last_acq_plan.n_levels; return GYP_OK; }
     if (is("last_acq_shared_levels")) { *out = (double)ctx->last_acq_plan.shared_levels; return GYP_OK; }
+    if (is("last_hybrid_chunks")) { *out = (double)ctx->last_hybrid_plan.n_chunks; return GYP_OK; }
     for (int w = 0; w < 3; ++w) {
         // "last_acq_units" etc.: summed over the levels of the last search; with "_l<k>" appended: its level k alone (1 .. kAcqWitnessLevels)
         static const char* const kWitness[3] = {"last_acq_units", "last_acq_shared_cells", "last_acq_unshared_cells"};
@@ -1967,6 +2171,13 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
         ctx->*(f->field) = value != 0.0;
         return GYP_OK;
     }
+    for (const DebugInt& d : kDebugInts)
+        if (std::strcmp(name, d.name) == 0) {
+            if (!std::isfinite(value) || value < d.lo || value > d.hi || value != std::floor(value))
+                return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be an integer in [" + std::to_string(d.lo) + ", " + std::to_string(d.hi) + "]");
+            ctx->*(d.field) = (int)value;
+            return GYP_OK;
+        }
     const DebugSwitch* k = debug_switch(name);
     if (!k) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);
     if (!std::isfinite(value) || value < k->lo || value > k->hi || (k->integral && value != std::floor(value)))
@@ -1983,6 +2194,8 @@ int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
     if (const DebugFlag* f = debug_flag(name)) { *out = ctx->*(f->field) ? 1.0 : 0.0; return GYP_OK; }
     if (const DebugSwitch* k = debug_switch(name)) { *out = k->get(*ctx); return GYP_OK; }
+    for (const DebugInt& d : kDebugInts)
+        if (std::strcmp(name, d.name) == 0) { *out = (double)(ctx->*(d.field)); return GYP_OK; }
     const int rc = debug_read_only(ctx, name, out);
     if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");
     if (rc != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_get: no such switch: ") + name);

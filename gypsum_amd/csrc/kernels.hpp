@@ -35,6 +35,10 @@
 //                       and the eighth-octave histogram of the bins' power the threshold is derived from, in integer atomics.
 //   track_quality_kernel   signal quality: per (channel, window) sums of a block's tracking records -- peak moments, lock count,
 //                       narrow/wide-band power ratios of 20-ms groups -- one wavefront each, in a fixed float64 reduction order.
+//   hybrid_accumulate_kernel / hybrid_reduce_kernel   weak-signal acquisition: the power of a block's coherent profiles (corr_cells_kernel's)
+//                       added at the code-Doppler-aligned lag into the row of the block's set, and per cell the arg-max, the second
+//                       peak and the off-peak float64 moments of each set in a fixed order, the set with the larger z reported; the
+//                       hybrid_*_cells / select / finish kernels are gyp_acquire_weak_dev's two-level bookkeeping.
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -55,3 +59,4 @@
 #include "kernels_blank.hpp"
 #include "kernels_excise.hpp"
 #include "kernels_quality.hpp"
+#include "kernels_hybrid.hpp"

@@ -22,6 +22,28 @@ def _as_iq(iq: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(iq, dtype=np.complex64)
 
 
+def hybrid_stats(cells: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """gyp_hybrid_stats (host only, no GPU): (z, peak_ratio) float64 arrays of the shape of the HYBRID_CELL records `cells`;
+    z = (peak - mean_off) / std_off is NaN where it is not defined."""
+    lib = _lib.load()
+    c = np.ascontiguousarray(cells, dtype=_lib.HYBRID_CELL)
+    flat = c.reshape(-1)
+    z = np.empty(flat.size, dtype=np.float64)
+    ratio = np.empty(flat.size, dtype=np.float64)
+    zz, rr = C.c_double(), C.c_double()
+    for i in range(flat.size):
+        rc = lib.gyp_hybrid_stats(ptr(flat[i:i + 1]), C.byref(zz), C.byref(rr))
+        if rc != 0:
+            raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
+        z[i], ratio[i] = zz.value, rr.value
+    return z.reshape(c.shape), ratio.reshape(c.shape)
+
+
+def hybrid_shift(n: int, coherent_ms: int, block: int, doppler_hz: float, flags: int) -> int:
+    """gyp_hybrid_shift (host only, no GPU): samples by which block `block`'s peak sits earlier than block 0's."""
+    return int(_lib.load().gyp_hybrid_shift(int(n), int(coherent_ms), int(block), float(doppler_hz), int(flags)))
+
+
 class DeviceBuffer:
     """RAII wrapper around gyp_malloc / gyp_free."""
 
@@ -642,6 +664,52 @@ class GypsumEngine:
         ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
         self._check(self.lib.gyp_acquire_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, n_ms, ptr(ids),
                                               len(ids), C.c_void_p(out_ptr)))
+
+    # ------------------------------------------------------------------ weak-signal acquisition (hybrid search)
+    def correlate_grid_hybrid(self, iq: np.ndarray, n_streams: int, coherent_ms: int, n_blocks: int, flags: int, sat_ids: Sequence[int],
+                              doppler_hz: Sequence[float]) -> np.ndarray:
+        """Flat grid of the hybrid coherent/non-coherent search: HYBRID_CELL records [n_streams, n_sats, n_bins] from
+        n_blocks blocks of coherent_ms milliseconds (iq: complex64[n_streams * n_blocks * coherent_ms * N], stream-major)."""
+        iq = _as_iq(iq).reshape(-1)
+        if coherent_ms >= 1 and n_blocks >= 1 and iq.size != n_streams * n_blocks * coherent_ms * self.n:
+            raise ValueError(f"expected {n_streams}*{n_blocks}*{coherent_ms}*{self.n} samples, got {iq.size}")
+        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        out = np.zeros((n_streams, len(ids), len(bins)), dtype=_lib.HYBRID_CELL)
+        self._check(self.lib.gyp_correlate_grid_hybrid(self.ctx, ptr(iq), n_streams, int(coherent_ms), int(n_blocks), int(flags), ptr(ids), len(ids),
+                                                        ptr(bins), len(bins), ptr(out)))
+        return out
+
+    def correlate_grid_hybrid_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, coherent_ms: int, n_blocks: int, flags: int,
+                                  sat_ids: Sequence[int], doppler_hz: Sequence[float], out_ptr: int) -> None:
+        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        self._check(self.lib.gyp_correlate_grid_hybrid_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, int(coherent_ms), int(n_blocks),
+                                                            int(flags), ptr(ids), len(ids), ptr(bins), len(bins), C.c_void_p(out_ptr)))
+
+    def acquire_weak(self, iq: np.ndarray, n_streams: int, coherent_ms: int, n_blocks: int, flags: int, sat_ids: Sequence[int],
+                     center_hz: float = 0.0, spread_hz: float = 7000.0, fine_step_hz: float = 10.0) -> np.ndarray:
+        """The two-level hybrid search per (stream, satellite): WEAK_RESULT records, stream-major, satellites in the order given.
+        The threshold on `z` is the caller's."""
+        iq = _as_iq(iq).reshape(-1)
+        if coherent_ms >= 1 and n_blocks >= 1 and iq.size != n_streams * n_blocks * coherent_ms * self.n:
+            raise ValueError(f"expected {n_streams}*{n_blocks}*{coherent_ms}*{self.n} samples, got {iq.size}")
+        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        out = np.zeros(n_streams * len(ids), dtype=_lib.WEAK_RESULT)
+        self._check(self.lib.gyp_acquire_weak(self.ctx, ptr(iq), n_streams, int(coherent_ms), int(n_blocks), int(flags), float(center_hz),
+                                               float(spread_hz), float(fine_step_hz), ptr(ids), len(ids), ptr(out)))
+        return out
+
+    def acquire_weak_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, coherent_ms: int, n_blocks: int, flags: int,
+                         sat_ids: Sequence[int], center_hz: float, spread_hz: float, fine_step_hz: float, out_ptr: int) -> None:
+        """Device-pointer form: only enqueues on the engine's stream."""
+        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        self._check(self.lib.gyp_acquire_weak_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, int(coherent_ms), int(n_blocks), int(flags),
+                                                   float(center_hz), float(spread_hz), float(fine_step_hz), ptr(ids), len(ids), C.c_void_p(out_ptr)))
+
+    def hybrid_stats(self, cells: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(z, peak_ratio) of HYBRID_CELL records, float64 (gyp_hybrid_stats; see hybrid_stats below)."""
+        return hybrid_stats(cells)
 
     def synth_iq(self, out: "DeviceBuffer", n_streams: int, stream_stride: int, n_ms: int, sats: np.ndarray,
                  noise_sigma: float, seed: int) -> None:

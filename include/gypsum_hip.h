@@ -28,7 +28,11 @@
 extern "C" {
 #endif
 
-/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband and
+/* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
+ *      acquisition, a hybrid coherent/non-coherent search on the device: gyp_hybrid_cell, gyp_weak_result, GYP_HYB_ALTERNATE,
+ *      GYP_HYB_CODE_DOPPLER, gyp_hybrid_stats, gyp_hybrid_shift, gyp_correlate_grid_hybrid(_dev), gyp_acquire_weak(_dev); gyp_debug_set
+ *      name hybrid_scratch_mb and the read-only "last_hybrid_chunks".  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): narrowband and
  *      swept interference that is no pure tone, excised in short overlapped transforms on the device: gyp_excisor, GYP_EXCISE_FRAME,
  *      gyp_excise_iq_dev, gyp_iq_spectrum_hist_dev, gyp_excise_from_hist, gyp_ingest_set_excisor, gyp_ingest_get_excisor,
  *      gyp_ingest_find_excisor, gyp_ingest_last_excised.  Opt-in.
@@ -278,6 +282,90 @@ int gyp_search_level_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, i
                          const int32_t* sat_ids_host, int32_t n_sats, double center_hz, double spread_hz, gyp_acq_result* out_dev);
 int gyp_search_level(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                      int32_t n_sats, double center_hz, double spread_hz, gyp_acq_result* out_host);
+
+/* ---------------------------------------------------------------- weak-signal acquisition ------------- */
+/* The search of gyp_acquire (ten 1-ms blocks summed as |c|, accepted at strength > 3) stops at about 38 dB-Hz.  Below that a
+ * satellite is found by integrating coherently over coherent_ms = T milliseconds (1..20) and adding the POWER of n_blocks = M such
+ * blocks.  For one stream, satellite and Doppler bin f (Hz, any double):
+ *   block b (0 <= b < M) covers milliseconds [bT, (b+1)T); C_b[l], l in [0, N), is its coherent profile: exactly what
+ *     gyp_correlate_cells_dev(..., GYP_COHERENT, profile_out) writes for the cell when given that block as its whole buffer (the
+ *     wipe-off time starts at the block's first sample);
+ *   GYP_HYB_CODE_DOPPLER: delta_b = gyp_hybrid_shift(N, T, b, f, flags) = llround((double)(b T N) * f / 1575420000.0) samples, half
+ *     away from zero (a positive Doppler shortens the code period: block b peaks at (cp_0 - delta_b) mod N); else delta_b = 0;
+ *   P_k[l] = sum over the blocks b of set k, in increasing b, of |C_b[(l - delta_b) mod N]|^2, float32 throughout (re*re, im*im and
+ *     their sum each rounded once), so P is aligned to block 0: its peak is at cp_0;
+ *   GYP_HYB_ALTERNATE (needs M >= 2): set 0 holds the even blocks, set 1 the odd ones (with T = 10 a data-bit edge every 20 ms can
+ *     fall inside the blocks of one parity only); else every block is in set 0;
+ *   per set, with "away" = circular lag distance from argmax greater than N / 1023 samples (one chip): peak = max P, argmax its
+ *     lowest index; second, second_argmax the same over the lags away (0, -1 if there are none); n_off, sum_off = sum P and
+ *     sumsq_off = sum P^2 over the lags away, float64 in a fixed order (hybrid_reduce_kernel);
+ *   the record is that of the set with the larger z (gyp_hybrid_stats); set 0 on a tie or when a z is NaN. */
+enum { GYP_HYB_ALTERNATE = 1, GYP_HYB_CODE_DOPPLER = 2 };
+
+typedef struct gyp_hybrid_cell {   /* 48 bytes */
+    float peak;
+    int32_t argmax;
+    float second;
+    int32_t second_argmax;
+    int32_t n_off;
+    int32_t set;            /* the reported set: 0, or 1 (odd blocks, GYP_HYB_ALTERNATE only) */
+    double sum_off;
+    double sumsq_off;
+    int32_t blocks_used;    /* blocks in the reported set */
+    int32_t reserved;
+} gyp_hybrid_cell;
+
+/* Host only, no GPU.  Float64, in exactly this order, one rounding per operation (no contraction):
+ *   n = (double)n_off;  mean = sum_off / n;  m2 = sumsq_off / n;  var = m2 - mean mean;  z = ((double)peak - mean) / sqrt(var),
+ *   NaN if n_off <= 0 or !(var > 0);  peak_ratio = (double)peak / (double)second (inf when second is 0 and peak is not).
+ * Either output pointer may be NULL.  GYP_E_BAD_ARG for a NULL record. */
+int gyp_hybrid_stats(const gyp_hybrid_cell* c, double* z_out, double* peak_ratio_out);
+/* Host only, no GPU: delta_b as above (0 without GYP_HYB_CODE_DOPPLER).  n = samples per millisecond. */
+int gyp_hybrid_shift(int32_t n, int32_t coherent_ms, int32_t block, double doppler_hz, int32_t flags);
+
+/* The flat-grid twin of gyp_correlate_grid_dev: iq_dev holds n_streams x (n_blocks * coherent_ms) x N samples (stream stride
+ * given), out is n_streams x n_sats x n_bins records, bins fastest.  The coherent profiles come from the correlation-cell kernel,
+ * one block at a time; cells are processed in chunks whose profile + power scratch fits gyp_debug_set "hybrid_scratch_mb" -- the
+ * records are the same bits for every budget.  GYP_E_BAD_ARG, before anything runs, for: coherent_ms outside 1..20; n_blocks < 1;
+ * n_blocks * coherent_ms > 65535; GYP_HYB_ALTERNATE with n_blocks < 2; unknown flag bits; satellite ids outside 1..32; a Doppler
+ * bin that is not finite; NULL pointers or counts < 1; more than 2^31 - 1 cells.  The _dev form waits for the stream once, after
+ * uploading the ids and bins (the host arrays may be temporaries), then only enqueues. */
+int gyp_correlate_grid_hybrid_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t coherent_ms,
+                                  int32_t n_blocks, int32_t flags, const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host,
+                                  int32_t n_bins, gyp_hybrid_cell* out_dev);
+int gyp_correlate_grid_hybrid(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t coherent_ms, int32_t n_blocks, int32_t flags,
+                              const int32_t* sat_ids_host, int32_t n_sats, const double* doppler_hz_host, int32_t n_bins,
+                              gyp_hybrid_cell* out_host);
+
+/* What the two-level search returns per (stream, satellite); converts field for field into a gyp_chan_init. */
+typedef struct gyp_weak_result {   /* 56 bytes */
+    int32_t stream;
+    int32_t sat_id;
+    double doppler_hz;       /* the final bin */
+    int32_t code_phase;      /* argmax of its reported set: the code phase at the buffer's first sample, [0, N) */
+    int32_t reserved0;
+    double carrier_phase;    /* angle(C_0[code_phase]) of the final bin: the phase at the buffer's first sample, radians (-pi, pi] */
+    double z;                /* (peak - mean_off) / std_off of the reported set: the detection statistic */
+    double peak_ratio;       /* peak / second */
+    int32_t set;
+    int32_t reserved;
+} gyp_weak_result;
+
+/* Two levels over the grid above, for every (stream, satellite); at most 32 satellites per call.
+ *   coarse: bins center_hz - spread_hz + i * (500 / T) Hz, i = 0, 1, ... while < center_hz + spread_hz (half-step scalloping loss
+ *     sinc(0.25) = -0.9 dB); the best bin per (stream, satellite) is the one with the largest z, the lowest bin on a tie (a NaN z
+ *     never wins);
+ *   fine: bins best + j * fine_step_hz for the integers j with |j * fine_step_hz| <= 250 / T, chosen the same way; fine_step_hz <= 0
+ *     skips the level.
+ * The detection threshold on z is left to the caller, as gyp_acquire leaves its own.  out: n_streams x n_sats records, stream-major,
+ * satellites in the order given.  Refusals as gyp_correlate_grid_hybrid_dev, and spread_hz <= 0, non-finite center / spread / step,
+ * or a level of more than 4096 bins.  The _dev form only enqueues: it never waits for the stream, not between the levels either. */
+int gyp_acquire_weak_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t coherent_ms,
+                         int32_t n_blocks, int32_t flags, double center_hz, double spread_hz, double fine_step_hz,
+                         const int32_t* sat_ids_host, int32_t n_sats, gyp_weak_result* out_dev);
+int gyp_acquire_weak(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t coherent_ms, int32_t n_blocks, int32_t flags,
+                     double center_hz, double spread_hz, double fine_step_hz, const int32_t* sat_ids_host, int32_t n_sats,
+                     gyp_weak_result* out_host);
 
 /* ---------------------------------------------------------------- tracking: one explicit millisecond -- */
 /* Numeric core of tracker.py:264-329 _run_prn_code_tracking_loop_iteration for a batch of channels:
@@ -1173,6 +1261,9 @@ int gyp_quality_from_sums(const gyp_quality_sums* sums, int32_t n, gyp_quality* 
  *                               profile do (the Costas loop's and the record's), in straight-line code, and the code loop's reads its two
  *                               taps; same records, states and dumps bit for bit.  Rates above 8 samples per chip ignore it; the helper
  *                               contexts of a split scan inherit it
+ *   "hybrid_scratch_mb" 16..65536 (1024)  budget, in MiB, of the profile + power scratch of gyp_correlate_grid_hybrid(_dev) and
+ *                               gyp_acquire_weak(_dev): the cells go through in chunks that fit it; same records bit for bit
+ *   "last_hybrid_chunks" (read only, gyp_debug_get)  chunks of the context's last hybrid grid (of gyp_acquire_weak: its last level's); 0 none yet
  *   "prof_wave" 0..7 (0)        which wavefront of workgroup 0 stamps the counters of gyp_debug_track_profile
  *   "symbol_tau" 0..100 (1e-4)  |Re peak| / |peak| below which dll_scan_kernel decides the pseudosymbol in float64 (test: 10 = always)
  *   "dll_prov_bias" (0)         test hook: added to the PROVISIONAL discriminator so that the repair path runs; results must not change
