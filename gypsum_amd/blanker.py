@@ -24,7 +24,7 @@ from typing import Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _records
 
 # one per stream: gyp_blanker, 16 bytes
 BLANKER_DTYPE = _lib.BLANKER
@@ -34,34 +34,19 @@ MAX_SAMPLES_PER_MS = 65536
 
 
 @dataclass(frozen=True)
-class Blanker:
+class Blanker(_records.Record):
     """A sample whose |x - centre| reaches `threshold` is replaced by the centre, with `guard` samples on either side (gyp_blanker)."""
     center_re: float = 0.0
     center_im: float = 0.0
     threshold: float = 1.0
     guard: int = 0
-
-    def record(self) -> np.ndarray:
-        rec = np.zeros(1, dtype=BLANKER_DTYPE)
-        with np.errstate(over="ignore"):                    # (a threshold beyond float32 becomes inf, which check_blanker refuses)
-            rec["center_re"], rec["center_im"], rec["threshold"] = self.center_re, self.center_im, self.threshold
-        rec["guard"] = int(self.guard)
-        return rec
-
-    @classmethod
-    def from_record(cls, rec) -> "Blanker":
-        r = np.asarray(rec, dtype=BLANKER_DTYPE).reshape(-1)[0]
-        return cls(float(r["center_re"]), float(r["center_im"]), float(r["threshold"]), int(r["guard"]))
+    DTYPE, MEASURED = BLANKER_DTYPE, ("median", "threshold")
 
 
 def blanker_records(blankers, n_streams: int = None) -> np.ndarray:
     """One gyp_blanker record per stream from `blankers`: records already, one Blanker (for one stream, or for each of n_streams
     streams) or a sequence of them."""
-    if isinstance(blankers, np.ndarray) and blankers.dtype == BLANKER_DTYPE:
-        return np.ascontiguousarray(blankers).reshape(-1)
-    if isinstance(blankers, Blanker):
-        blankers = [blankers] * (1 if n_streams is None else max(1, int(n_streams)))
-    return np.concatenate([b.record() for b in blankers])
+    return _records.records(blankers, Blanker, n_streams)
 
 
 def check_blanker(blanker: Blanker) -> None:
@@ -85,17 +70,10 @@ def bin_edges() -> np.ndarray:
 def blanker_from_hist(hist: np.ndarray, center=(0.0, 0.0), threshold_over_median: float = 16.0, guard: int = 4) -> Tuple[Blanker, dict]:
     """The blanker whose threshold is sqrt(threshold_over_median x the median power) of one stream's histogram
     (gyp_blank_from_hist: host only, no GPU).  Returns (blanker, measured) with measured = {"median", "threshold"} in float64."""
-    lib = _lib.load()
-    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(-1)
-    if len(h) != HIST_BINS:
-        raise ValueError(f"a histogram has {HIST_BINS} bins")
-    rec, measured = np.zeros(1, dtype=BLANKER_DTYPE), np.zeros(2)
-    rc = lib.gyp_blank_from_hist(_lib.ptr(h), C.c_float(center[0]), C.c_float(center[1]), float(threshold_over_median), int(guard),
-                                 _lib.ptr(rec), _lib.ptr(measured))
-    if rc != 0:
-        raise _lib.GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
-    return Blanker.from_record(rec), measured_dict(measured)
+    h = _records.one_hist(hist)
+    return _records.derived(Blanker, lambda lib, rec, measured: lib.gyp_blank_from_hist(
+        _lib.ptr(h), C.c_float(center[0]), C.c_float(center[1]), float(threshold_over_median), int(guard), rec, measured))
 
 
 def measured_dict(measured2: np.ndarray) -> dict:
-    return {"median": float(measured2[0]), "threshold": float(measured2[1])}
+    return _records.measured_dict(Blanker, measured2)

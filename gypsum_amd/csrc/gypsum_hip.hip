@@ -2732,6 +2732,8 @@ struct IqWindow {
     int32_t n_ms, n;        // n_ms milliseconds of n samples
     int64_t first_index;    // the absolute index of the window's first sample: the phase reference of the tone stages
     hipStream_t stream;
+    IqWindow(const float* in_, float* out_, int32_t n_streams_, int64_t stride_, int32_t n_ms_, int32_t n_, int64_t first_index_, hipStream_t stream_)
+        : in(in_), out(out_), n_streams(n_streams_), stride(stride_), n_ms(n_ms_), n(n_), first_index(first_index_), stream(stream_) {}
     const float2* src(int32_t s0) const { return reinterpret_cast<const float2*>(in) + s0 * stride; }   // stream s0's row
     float2* dst(int32_t s0) const { return reinterpret_cast<float2*>(out) + s0 * stride; }
 };
@@ -2746,6 +2748,13 @@ static int for_each_chunk(const StagePlan& pl, Launch&& launch) {
 // The refusals' common forms: "<who>: <why>", and rows of `extent` samples that would overlap at this stride
 static int refuse(gyp_ctx* ctx, const char* who, const std::string& why) { return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why); }
 static bool rows_overlap(int32_t n_streams, int64_t stride, int64_t extent) { return n_streams > 1 && stride < extent; }
+// The window of the stand-alone blanker, excisor and spectrum histogram, whose refusals read alike but for min_ms, lo and hi
+static int window_check(gyp_ctx* ctx, const char* who, const IqWindow& w, int32_t min_ms, int32_t lo, int32_t hi) {
+    if (w.n_streams < 1 || w.n_ms < min_ms || w.n < lo || w.n > hi || rows_overlap(w.n_streams, w.stride, (int64_t)w.n_ms * w.n))
+        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= " + std::to_string(min_ms) + ", " + std::to_string(lo) +
+                                " <= samples_per_ms <= " + std::to_string(hi) + ", stream_stride_samples >= n_ms * samples_per_ms)");
+    return GYP_OK;
+}
 
 // Enqueue iq_stats_kernel: one record per (stream, millisecond) of the window into `out`.
 static int stats_launch(gyp_ctx* ctx, const IqWindow& w, float clip_level, gyp_iq_stats* out) {
@@ -2777,9 +2786,7 @@ int gyp_iq_stats_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64
     if (rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
         return refuse(ctx, who, "stream_stride_samples must be >= n_ms * samples_per_ms");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms, w.stream = ctx->stream;
-    return stats_launch(ctx, w, clip_level, out_dev);
+    return stats_launch(ctx, IqWindow(iq_dev, nullptr, n_streams, stream_stride_samples, n_ms, samples_per_ms, 0, ctx->stream), clip_level, out_dev);
 }
 
 int gyp_condition_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t n_streams, int64_t stream_stride_samples,
@@ -2793,9 +2800,7 @@ int gyp_condition_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int3
         if (const char* why = level_check(&levels_host[s])) return refuse(ctx, who, why);
     if (n_samples == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.stream = ctx->stream;
-    return condition_launch(ctx, w, n_samples, levels_host);
+    return condition_launch(ctx, IqWindow(in_dev, out_dev, n_streams, stream_stride_samples, 0, 0, 0, ctx->stream), n_samples, levels_host);
 }
 
 int gyp_iq_level_from_stats(const gyp_iq_stats* stats, int32_t n_ms, int32_t samples_per_ms, int32_t remove_dc, double target_rms,
@@ -2874,9 +2879,7 @@ int gyp_iq_tones_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (const int rc = tones_upload_freqs(ctx, freqs_hz_host, n_freq, fs_hz)) return rc;
-    IqWindow w{};
-    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_blocks, w.n = block_samples;
-    w.first_index = first_sample_index, w.stream = ctx->stream;
+    const IqWindow w(iq_dev, nullptr, n_streams, stream_stride_samples, n_blocks, block_samples, first_sample_index, ctx->stream);
     return tones_launch(ctx, w, fs_hz, n_freq, window, out_dev);
 }
 
@@ -2896,9 +2899,7 @@ int gyp_notch_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t 
     }
     if (n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
-    w.first_index = first_sample_index, w.stream = ctx->stream;
+    const IqWindow w(in_dev, out_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, first_sample_index, ctx->stream);
     return notch_launch(ctx, w, fs_hz, tones_host);
 }
 
@@ -3031,17 +3032,12 @@ int gyp_blank_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t 
     const char* who = "gyp_blank_iq_dev";
     if (!ctx) return refuse(nullptr, who, "ctx is NULL");
     if (!in_dev || !out_dev || !blankers_host) return refuse(ctx, who, "in_dev, out_dev and blankers_host must not be NULL");
-    if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || samples_per_ms > kBlankMaxSamples ||
-        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
-        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
-                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    const IqWindow w(in_dev, out_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, 0, ctx->stream);
+    if (const int rc = window_check(ctx, who, w, 0, 1, kBlankMaxSamples)) return rc;
     for (int32_t s = 0; s < n_streams; ++s)
         if (const char* why = blanker_check(&blankers_host[s])) return refuse(ctx, who, why);
     if (n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
-    w.stream = ctx->stream;
     return blank_launch(ctx, w, blankers_host, counts_out_dev);
 }
 
@@ -3056,9 +3052,7 @@ int gyp_iq_power_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, 
         for (int32_t i = 0; i < 2 * n_streams; ++i)
             if (!std::isfinite(centers_host[i])) return refuse(ctx, who, "every centre must be finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.stream = ctx->stream;
-    return hist_launch(ctx, w, n_samples, centers_host, hist_out_dev);
+    return hist_launch(ctx, IqWindow(iq_dev, nullptr, n_streams, stream_stride_samples, 0, 0, 0, ctx->stream), n_samples, centers_host, hist_out_dev);
 }
 
 int gyp_blank_from_hist(const uint32_t* hist, float center_re, float center_im, double threshold_over_median, int32_t guard,
@@ -3110,17 +3104,12 @@ int gyp_excise_iq_dev(gyp_ctx* ctx, const float* in_dev, float* out_dev, int32_t
     const char* who = "gyp_excise_iq_dev";
     if (!ctx) return refuse(nullptr, who, "ctx is NULL");
     if (!in_dev || !out_dev || !excisors_host) return refuse(ctx, who, "in_dev, out_dev and excisors_host must not be NULL");
-    if (n_streams < 1 || n_ms < 0 || samples_per_ms < 1 || samples_per_ms > kExciseMaxSamples ||
-        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
-        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 0, 1 <= samples_per_ms <= 65536, "
-                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    const IqWindow w(in_dev, out_dev, n_streams, stream_stride_samples, n_ms, samples_per_ms, 0, ctx->stream);
+    if (const int rc = window_check(ctx, who, w, 0, 1, kExciseMaxSamples)) return rc;
     for (int32_t s = 0; s < n_streams; ++s)
         if (const char* why = excisor_check(&excisors_host[s])) return refuse(ctx, who, why);
     if (n_ms == 0) return GYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = in_dev, w.out = out_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms;
-    w.stream = ctx->stream;
     return excise_launch(ctx, w, excisors_host, counts_out_dev, masks_out_dev);
 }
 
@@ -3129,13 +3118,9 @@ int gyp_iq_spectrum_hist_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_stream
     const char* who = "gyp_iq_spectrum_hist_dev";
     if (!ctx) return refuse(nullptr, who, "ctx is NULL");
     if (!iq_dev || !hist_out_dev) return refuse(ctx, who, "iq_dev and hist_out_dev must not be NULL");
-    if (n_streams < 1 || n_ms < 1 || samples_per_ms < GYP_EXCISE_FRAME || samples_per_ms > kExciseMaxSamples ||
-        rows_overlap(n_streams, stream_stride_samples, (int64_t)n_ms * samples_per_ms))
-        return refuse(ctx, who, "bad arguments (n_streams >= 1, n_ms >= 1, 256 <= samples_per_ms <= 65536, "
-                                "stream_stride_samples >= n_ms * samples_per_ms)");
+    const IqWindow w(iq_dev, nullptr, n_streams, stream_stride_samples, n_ms, samples_per_ms, 0, ctx->stream);
+    if (const int rc = window_check(ctx, who, w, 1, GYP_EXCISE_FRAME, kExciseMaxSamples)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IqWindow w{};
-    w.in = iq_dev, w.n_streams = n_streams, w.stride = stream_stride_samples, w.n_ms = n_ms, w.n = samples_per_ms, w.stream = ctx->stream;
     return spectrum_hist_launch(ctx, w, hist_out_dev);
 }
 
@@ -3171,22 +3156,28 @@ static void widen_launch(const gyp_ctx* ctx, hipStream_t stream, int32_t fmt, co
     }
 }
 
-// A handle with a level on conditions device slot d's block in place on the copy stream, behind whatever produced it.
+// One stream of n_ms milliseconds from millisecond first_ms of the handle's output at `in`, as a stage on `stream` takes it
+static IqWindow ingest_window(const gyp_ingest* g, const float* in, float* out, int32_t n_ms, int64_t first_ms, hipStream_t stream) {
+    return IqWindow(in, out, 1, 0, n_ms, g->src.n, first_ms * g->src.n, stream);
+}
+
+// The stages that are on condition device slot d's block in place on the copy stream, behind whatever produced it, in the chain's
+// order.  (A counting stage is only on once its counts are made: ingest_counts_made.)
 static int ingest_condition(gyp_ingest* g, int d, int64_t first_ms, int32_t n_ms) {
     const Conditioning& cond = g->cond;
-    IqWindow w{};
-    w.in = w.out = g->dev_iq[d].get();
-    w.n_streams = 1, w.n_ms = n_ms, w.n = g->src.n, w.first_index = first_ms * w.n, w.stream = g->copy_stream.get();
-    g->slot_blanked[d] = cond.blank_on ? 1 : 0;
-    if (cond.blank_on)   // chain order: producer -> blanker -> excisor -> notches -> level
-        if (const int rc = blank_launch(g->ctx, w, &cond.blanker, g->dev_blanked[d].get())) return rc;
-    if (!g->slot_excised.empty()) g->slot_excised[d] = cond.excise_on ? 1 : 0;
-    if (cond.excise_on)   // (an excisor is only ever on behind ingest_excise_buffers)
-        if (const int rc = excise_launch(g->ctx, w, &cond.excisor, g->dev_excised[d].get(), nullptr)) return rc;
-    if (cond.notches.count > 0)
-        if (const int rc = notch_launch(g->ctx, w, g->fs, &cond.notches)) return rc;
-    if (!cond.level_on) return GYP_OK;
-    return condition_launch(g->ctx, w, (int64_t)n_ms * w.n, &cond.level);
+    float* iq = g->dev_iq[d].get();
+    const IqWindow w = ingest_window(g, iq, iq, n_ms, first_ms, g->copy_stream.get());
+    for (const Stage s : kChain) {
+        SlotCounts* counts = g->counts_of(s);
+        if (counts) counts->mark(d, cond.on(s));
+        if (!cond.on(s)) continue;
+        const int rc = s == Stage::blanker   ? blank_launch(g->ctx, w, &cond.blanker, counts->dev[d].get())
+                       : s == Stage::excisor ? excise_launch(g->ctx, w, &cond.excisor, counts->dev[d].get(), nullptr)
+                       : s == Stage::notches ? notch_launch(g->ctx, w, g->fs, &cond.notches)
+                                             : condition_launch(g->ctx, w, (int64_t)n_ms * w.n, &cond.level);
+        if (rc) return rc;
+    }
+    return GYP_OK;
 }
 
 // The producer of a block, on the copy stream: file-width words in `raw` (the span's slot) -> complex64 in the output slot `iq`.
@@ -3293,10 +3284,8 @@ static int ingest_finish_open(gyp_ctx* ctx, const IngestSource& src, int64_t fs,
         g->dev_iq.resize(depth);
         g->uploaded.resize(depth);
         g->ready.resize(depth);
-        g->dev_blanked.resize(depth);
-        g->slot_blanked.assign(depth, 0);
         for (int i = 0; i < depth; ++i) {
-            HIP_TRY(ctx, g->dev_blanked[i].reserve((size_t)src.block_ms, Slack::exact));
+            HIP_TRY(ctx, g->blanked.ensure(i + 1, src.block_ms));   // (slot by slot, beside the slot's other buffers)
             HIP_TRY(ctx, g->dev_raw[i].reserve(src.raw_block_bytes, Slack::exact));
             HIP_TRY(ctx, g->dev_iq[i].reserve((size_t)src.block_ms * src.n * 2, Slack::exact));
             HIP_TRY(ctx, g->uploaded[i].create(hipEventDisableTiming));
@@ -3329,21 +3318,21 @@ static int ingest_open_filtered(gyp_ctx* ctx, const char* path, int32_t fmt, int
     return ingest_finish_open(ctx, ingest_describe(fmt, nullptr, d, if_hz, block_ms, depth), d.fs_out, path, out, who);
 }
 
-// One measurement over the handle's own device blocks of [first_ms, first_ms + n_ms) with the level put aside (gyp_ingest_calibrate),
-// the notches too (gyp_ingest_find_tones) or the whole conditioning (gyp_ingest_find_pulses).  per_block(iq_dev, ms done, ms to take) is called
-// for the blocks in order; after(next) does what follows the walk (downloads, host arithmetic, further launches on the context's
+// The measurement of one stage over the handle's own device blocks of [first_ms, first_ms + n_ms): that stage and the ones behind it
+// are put aside, so the blocks are what the stage would be given (Conditioning::upstream_of).  per_block(iq_dev, ms done, ms to take) is
+// called for the blocks in order; after(next) does what follows the walk (downloads, host arithmetic, further launches on the context's
 // stream) and may write the conditioning to install into `next`, which starts as the one found.  Then, whatever happened and in
 // this order: the error text is saved (the seek overwrites ctx->err), the context's stream is synchronised (nothing may still read
 // a block or a temporary), release() lets the caller's temporaries go, the conditioning becomes `next` on success and what it was
 // otherwise, the cursor goes back to where it was, and the first error is reported with its own message.
 template <class PerBlock, class After, class Release>
-static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, Suspend suspend, const char* who, PerBlock per_block,
+static int ingest_measure_range(gyp_ingest* g, int64_t first_ms, int32_t n_ms, Stage measured, const char* who, PerBlock per_block,
                                 After after, Release release) {
     gyp_ctx* ctx = g->ctx;
     const Conditioning before = g->cond;
     const int64_t back_to = g->consumer_ms;
     Conditioning next = before;
-    g->cond = before.without(suspend);
+    g->cond = before.upstream_of(measured);
     auto measure = [&]() -> int {
         if (const int rc = gyp_ingest_seek(g, first_ms)) return rc;
         for (int32_t done = 0; done < n_ms;) {
@@ -3374,7 +3363,6 @@ static int ingest_device_handle(const gyp_ingest* g, const char* who, const char
     *ctx = g->ctx;
     return GYP_OK;
 }
-static const char* const kBlankTooWide = "the blanker takes at most 65536 samples per millisecond";
 // A measurement's range: whole milliseconds inside the recording, at most max_ms of them.
 static int ingest_range_check(const gyp_ingest* g, const char* who, int64_t first_ms, int32_t n_ms, int32_t max_ms) {
     if (n_ms < 1 || n_ms > max_ms || first_ms < 0 || first_ms > g->total_ms - n_ms)
@@ -3384,51 +3372,162 @@ static int ingest_range_check(const gyp_ingest* g, const char* who, int64_t firs
 // A changed conditioning applies from the next block handed out: what was uploaded ahead carries the old one, so it is dropped and
 // read again.
 static int ingest_recondition(gyp_ingest* g) { return gyp_ingest_seek(g, g->consumer_ms); }
-// ingest_measure_range's per_block of a measurement that wants its range in one buffer: the block's `take` milliseconds go to
-// millisecond `done` of `all`.
-static int ingest_gather(const gyp_ingest* g, float* all, const float* iq, int32_t done, int32_t take) {
-    const size_t n = (size_t)g->src.n;
-    HIP_TRY(g->ctx, hipMemcpyAsync(all + 2 * (size_t)done * n, iq, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, g->ctx->stream));
+
+// The range of a measurement that wants it in one buffer (gyp_ingest_find_pulses, _find_excisor, _find_tones): the buffer, the copy
+// of each block into it, the window over it on the context's stream, and the measurement itself.
+struct GatheredRange {
+    gyp_ingest* g;
+    int64_t first_ms;
+    int32_t n_ms;
+    DevBuf<float> iq;   // the range's samples
+    int64_t total() const { return (int64_t)n_ms * g->src.n; }
+    hipError_t reserve() { return iq.reserve((size_t)total() * 2, Slack::exact); }
+    IqWindow window() const { return ingest_window(g, iq.get(), nullptr, n_ms, first_ms, g->ctx->stream); }
+    // ingest_measure_range of `measured`, gathering every block; what is released is the buffer, then the caller's temporaries
+    template <class After, class Release>
+    int measure(Stage measured, const char* who, After after, Release release_rest) {
+        const size_t n = (size_t)g->src.n;
+        return ingest_measure_range(
+            g, first_ms, n_ms, measured, who,
+            [&](const float* block, int32_t done, int32_t take) -> int {
+                HIP_TRY(g->ctx, hipMemcpyAsync(iq.get() + 2 * (size_t)done * n, block, (size_t)take * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, g->ctx->stream));
+                return GYP_OK;
+            },
+            after, [&] { (void)iq.reset(), release_rest(); });
+    }
+};
+
+// What the record-valued stages (level, blanker, excisor) have in common: the switch and the record in a Conditioning, and why
+// their entry points need the handle's device side.  A stage that is switched off by its setter holds Conditioning{}'s record.
+template <class T>
+struct StageRecord { Stage stage; const char* applies; bool Conditioning::*on; T Conditioning::*rec; };
+static const StageRecord<gyp_iq_level> kLevelRecord{Stage::level, "a level applies to device blocks", &Conditioning::level_on, &Conditioning::level};
+static const StageRecord<gyp_blanker> kBlankerRecord{Stage::blanker, "a blanker applies to device blocks", &Conditioning::blank_on, &Conditioning::blanker};
+static const StageRecord<gyp_excisor> kExcisorRecord{Stage::excisor, "an excisor applies to device blocks", &Conditioning::excise_on, &Conditioning::excisor};
+
+// A counting stage's counts are made before it is first switched on, set or found: the blanker's at open, the excisor's here, so
+// that a handle that never gets an excisor allocates nothing for it.
+static int ingest_counts_made(gyp_ingest* g, Stage s) {
+    SlotCounts* counts = g->counts_of(s);
+    if (!counts || (int32_t)counts->dev.size() >= g->src.depth) return GYP_OK;
+    HIP_TRY(g->ctx, hipSetDevice(g->ctx->device));
+    HIP_TRY(g->ctx, counts->ensure(g->src.depth, g->src.block_ms));
     return GYP_OK;
 }
-// One stream of n_ms milliseconds at `iq`, as the measurements on the context's stream take it
-static IqWindow ingest_window(const gyp_ingest* g, const float* iq, int32_t n_ms, int64_t first_ms) {
-    IqWindow w{};
-    w.in = iq, w.n_streams = 1, w.n_ms = n_ms, w.n = g->src.n, w.first_index = first_ms * w.n, w.stream = g->ctx->stream;
-    return w;
+// The limits of the two stages whose threshold is put a factor above a histogram's median; `why`, or the rate's refusal
+struct HistStage { int32_t max_guard, max_samples; const char* too_wide; };
+static const HistStage kBlankHist{kBlankMaxGuard, kBlankMaxSamples, "the blanker takes at most 65536 samples per millisecond"};
+static const HistStage kExciseHist{kExciseMaxGuard, kExciseMaxSamples, "the excisor takes at most 65536 samples per millisecond"};
+static const char* hist_stage_check(const char* why, const gyp_ingest* g, const HistStage& hs) {
+    return why ? why : g->src.n > hs.max_samples ? hs.too_wide : nullptr;
+}
+
+// gyp_ingest_set_* and gyp_ingest_get_* of these stages: check() is why the stage does not take the record given, or nullptr
+template <class T, class Check>
+static int ingest_set_record(gyp_ingest* g, const char* who, const StageRecord<T>& st, const T* value, Check check) {
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, st.applies, &ctx)) return rc;
+    if (value) {
+        if (const char* why = check()) return refuse(ctx, who, why);
+        if (const int rc = ingest_counts_made(g, st.stage)) return rc;
+    }
+    g->cond.*st.on = value != nullptr;
+    g->cond.*st.rec = value ? *value : Conditioning{}.*st.rec;
+    return ingest_recondition(g);
+}
+template <class T>
+static int ingest_get_record(const gyp_ingest* g, const char* who, const StageRecord<T>& st, T* out, int32_t* enabled_out) {
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, st.applies, &ctx)) return rc;
+    if (out) *out = g->cond.*st.rec;
+    if (enabled_out) *enabled_out = g->cond.*st.on ? 1 : 0;
+    return GYP_OK;
+}
+
+// gyp_ingest_last_blanked / _last_excised: the stage's counts of the block most recently handed out
+template <class T>
+static int ingest_last_counts(gyp_ingest* g, const char* who, const StageRecord<T>& st, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
+    gyp_ctx* ctx;
+    if (const int rc = ingest_device_handle(g, who, st.applies, &ctx)) return rc;
+    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return refuse(ctx, who, "n_ms_out is NULL, or cap > 0 without counts_out");
+    *n_ms_out = g->last_n_ms;
+    const int32_t take = std::min(cap, g->last_n_ms);
+    if (take <= 0 || g->last_slot < 0) return GYP_OK;
+    const int d = g->last_slot;
+    const SlotCounts& counts = *g->counts_of(st.stage);
+    if (!counts.passed(d)) {
+        std::fill(counts_out, counts_out + take, 0);
+        return GYP_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
+    HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
+    HIP_TRY(ctx, hipMemcpyAsync(counts_out, counts.dev[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
+    return GYP_OK;
+}
+
+// gyp_ingest_find_pulses and gyp_ingest_find_excisor open alike, but for a HistStage's limits ...
+static int hist_find_check(const gyp_ingest* g, const char* who, const HistStage& hs, int64_t first_ms, int32_t n_ms, double factor, int32_t guard,
+                           gyp_ctx** ctx) {
+    if (const int rc = ingest_device_handle(g, who, "the histogram is taken on the device", ctx)) return rc;
+    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
+    if (!(factor > 0.0) || !std::isfinite(factor) || guard < 0 || guard > hs.max_guard)
+        return refuse(*ctx, who, "threshold_over_median must be positive and finite, 0 <= guard <= " + std::to_string(hs.max_guard));
+    const char* why = hist_stage_check(nullptr, g, hs);
+    return why ? refuse(*ctx, who, why) : GYP_OK;
+}
+// ... and end alike over their gathered range: launch(window, hist_dev) enqueues the histogram, from_hist(hist, &found) derives the
+// stage's record from it (nullptr, or the refusal's reason); the record is installed if asked and copied out.
+template <class T, class Launch, class FromHist, class Release>
+static int hist_find(GatheredRange& range, const char* who, const StageRecord<T>& st, int32_t install, T* out, Launch launch, FromHist from_hist,
+                     Release release_rest) {
+    gyp_ctx* ctx = range.g->ctx;
+    DevBuf<uint32_t> hist_dev;
+    HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
+    T found{};
+    const int rc = range.measure(
+        st.stage, who,
+        [&](Conditioning& next) -> int {
+            std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
+            if (const int rc = launch(range.window(), hist_dev.get())) return rc;
+            if (const int rc = fetch(ctx, hist, hist_dev.get())) return rc;
+            if (const char* why = from_hist(hist.data(), &found)) return refuse(ctx, who, why);
+            if (install) next.*st.on = true, next.*st.rec = found;
+            return GYP_OK;
+        },
+        [&] { release_rest(), (void)hist_dev.reset(); });
+    if (rc == GYP_OK && out) *out = found;
+    return rc;
 }
 
 // gyp_ingest_find_tones over the gathered range: what is searched, the device buffers, the records last measured, what was found.
 struct ToneSearch {
-    const gyp_ingest* g;
-    int64_t first_ms;
-    int32_t n_ms;
+    GatheredRange range;
     double threshold;
     int32_t max_tones;
-    DevBuf<float> iq_all;             // the range's samples
     DevBuf<gyp_tone_rec> recs_dev;
     std::vector<gyp_tone_rec> recs;   // block-major
     std::vector<int64_t> found;
     std::vector<double> found_db;
-    int64_t total() const { return (int64_t)n_ms * g->src.n; }
-    int32_t n_scan() const { return (int32_t)(total() / kScanBlock); }
-    int32_t n_fine() const { return (int32_t)(total() / kScanFine); }
+    int32_t n_scan() const { return (int32_t)(range.total() / kScanBlock); }
+    int32_t n_fine() const { return (int32_t)(range.total() / kScanFine); }
 };
 constexpr int32_t kScanGrid = 2 * kScanHalf + 1;
 
 // records of `freqs` over n_blocks blocks of block_samples samples of the gathered range, block-major, in ts.recs
 static int tone_measure(ToneSearch& ts, const std::vector<int64_t>& freqs, int32_t n_blocks, int32_t block_samples, int32_t window) {
-    gyp_ctx* ctx = ts.g->ctx;
-    if (const int rc = tones_upload_freqs(ctx, freqs.data(), (int32_t)freqs.size(), ts.g->fs)) return rc;
-    IqWindow w = ingest_window(ts.g, ts.iq_all.get(), n_blocks, ts.first_ms);
-    w.n = block_samples;
-    if (const int rc = tones_launch(ctx, w, ts.g->fs, (int32_t)freqs.size(), window, ts.recs_dev.get())) return rc;
+    gyp_ctx* ctx = ts.range.g->ctx;
+    if (const int rc = tones_upload_freqs(ctx, freqs.data(), (int32_t)freqs.size(), ts.range.g->fs)) return rc;
+    IqWindow w = ts.range.window();   // as n_blocks blocks of block_samples samples
+    w.n_ms = n_blocks, w.n = block_samples;
+    if (const int rc = tones_launch(ctx, w, ts.range.g->fs, (int32_t)freqs.size(), window, ts.recs_dev.get())) return rc;
     ts.recs.resize((size_t)n_blocks * freqs.size());
     return fetch(ctx, ts.recs, ts.recs_dev.get());
 }
 // one refinement step of every tone found: the phase slope over blocks of block_samples samples, rounded to whole Hz
 static int tone_refine_found(ToneSearch& ts, int32_t n_blocks, int32_t block_samples, int32_t window) {
-    const int64_t fs = ts.g->fs;
+    const int64_t fs = ts.range.g->fs;
     std::vector<int64_t>& found = ts.found;
     if (const int rc = tone_measure(ts, found, n_blocks, block_samples, window)) return rc;
     std::vector<gyp_tone_rec> col((size_t)n_blocks);
@@ -3442,8 +3541,8 @@ static int tone_refine_found(ToneSearch& ts, int32_t n_blocks, int32_t block_sam
 }
 // the scan, and its candidates without the offset at 0 Hz and without what the window leaks from it and from stronger tones
 static int tone_scan(ToneSearch& ts) {
-    gyp_ctx* ctx = ts.g->ctx;
-    const int64_t fs = ts.g->fs;
+    gyp_ctx* ctx = ts.range.g->ctx;
+    const int64_t fs = ts.range.g->fs;
     const int32_t n_scan = ts.n_scan();
     std::vector<int64_t> grid((size_t)kScanGrid);
     for (int32_t k = 0; k < kScanGrid; ++k) grid[(size_t)k] = scan_freq(k - kScanHalf, fs);
@@ -3483,10 +3582,10 @@ static int tone_search(ToneSearch& ts) {
     // (Hann on the short blocks: behind a rectangular window of 64 samples an offset-binary file's offset or a stronger tone
     // leaks into a weak tone's records at -30 dB and below and bends its phase slope)
     if (const int rc = tone_refine_found(ts, ts.n_fine(), kScanFine, GYP_WINDOW_HANN)) return rc;
-    if (ts.n_ms >= 2)
-        if (const int rc = tone_refine_found(ts, ts.n_ms, ts.g->src.n, GYP_WINDOW_RECT)) return rc;
-    return notch_check(ts.found.data(), (int32_t)ts.found.size(), ts.g->fs)
-               ? fail(ts.g->ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
+    if (ts.range.n_ms >= 2)
+        if (const int rc = tone_refine_found(ts, ts.range.n_ms, ts.range.g->src.n, GYP_WINDOW_RECT)) return rc;
+    return notch_check(ts.found.data(), (int32_t)ts.found.size(), ts.range.g->fs)
+               ? fail(ts.range.g->ctx, GYP_E_BAD_ARG, "gyp_ingest_find_tones: two refined tones lie closer than 4000 Hz")
                : GYP_OK;
 }
 
@@ -3573,7 +3672,7 @@ int gyp_ingest_seek(gyp_ingest* g, int64_t ms) {
         HIP_TRY(g->ctx, hipStreamSynchronize(g->copy_stream.get()));
         g->in_flight.clear();
         g->have_ahead = false;
-        g->last_slot = -1;   // (gyp_ingest_last_blanked: the slots are about to be refilled)
+        g->last_slot = -1;   // (ingest_last_counts: the slots are about to be refilled)
         g->last_n_ms = 0;
     }
     ingest_start_reader(g, ms);
@@ -3587,10 +3686,11 @@ int gyp_ingest_next_host(gyp_ingest* g, const void** raw_out, int64_t* first_ms_
     *n_ms_out = 0;
     if (g->src.filtered()) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a resampled handle has no host blocks (gyp_ingest_next_dev)");
     if (g->src.packed()) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a packed handle has no host blocks (gyp_ingest_next_dev)");
-    if (g->cond.level_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a level is on, and host blocks are raw file words (gyp_ingest_next_dev)");
-    if (g->cond.notches.count > 0) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: notches are on, and host blocks are raw file words (gyp_ingest_next_dev)");
-    if (g->cond.blank_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: a blanker is on, and host blocks are raw file words (gyp_ingest_next_dev)");
-    if (g->cond.excise_on) return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: an excisor is on, and host blocks are raw file words (gyp_ingest_next_dev)");
+    static const struct { Stage stage; const char* is_on; } kAsked[] = {   // in the order this call has always asked, not the chain's
+        {Stage::level, "a level is on"}, {Stage::notches, "notches are on"}, {Stage::blanker, "a blanker is on"}, {Stage::excisor, "an excisor is on"}};
+    for (const auto& a : kAsked)
+        if (g->cond.on(a.stage))
+            return fail(g->ctx, GYP_E_BAD_ARG, std::string("gyp_ingest_next_host: ") + a.is_on + ", and host blocks are raw file words (gyp_ingest_next_dev)");
     if (g->ctx && (!g->in_flight.empty() || g->have_ahead))
         return fail(g->ctx, GYP_E_BAD_ARG, "gyp_ingest_next_host: device blocks are in flight on this handle; seek first");
     ingest_release(g, g->taken);   // the block handed out by the previous call may be overwritten now
@@ -3652,22 +3752,11 @@ int gyp_widen_iq_dev(gyp_ctx* ctx, int32_t fmt, const void* raw_dev, uint64_t n_
 }
 
 int gyp_ingest_set_level(gyp_ingest* g, const gyp_iq_level* level) {
-    const char* who = "gyp_ingest_set_level";
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "a level applies to device blocks", &ctx)) return rc;
-    if (level)
-        if (const char* why = level_check(level)) return refuse(ctx, who, why);
-    g->cond.level_on = level != nullptr;
-    g->cond.level = level ? *level : gyp_iq_level{0.0f, 0.0f, 1.0f, 0};
-    return ingest_recondition(g);
+    return ingest_set_record(g, "gyp_ingest_set_level", kLevelRecord, level, [&] { return level_check(level); });
 }
 
 int gyp_ingest_get_level(const gyp_ingest* g, gyp_iq_level* out, int32_t* enabled_out) {
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_level", "a level applies to device blocks", &ctx)) return rc;
-    if (out) *out = g->cond.level;
-    if (enabled_out) *enabled_out = g->cond.level_on ? 1 : 0;
-    return GYP_OK;
+    return ingest_get_record(g, "gyp_ingest_get_level", kLevelRecord, out, enabled_out);
 }
 
 int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double target_rms, float clip_level,
@@ -3685,8 +3774,10 @@ int gyp_ingest_calibrate(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t 
     gyp_iq_level level{};
     // the level is put aside: the blocks measured are the handle's output without it (blanker, excisor and notches stay)
     const int rc = ingest_measure_range(
-        g, first_ms, n_ms, Suspend::level, who,
-        [&](const float* iq, int32_t done, int32_t take) { return stats_launch(ctx, ingest_window(g, iq, take, 0), clip_level, d_stats + done); },
+        g, first_ms, n_ms, Stage::level, who,
+        [&](const float* iq, int32_t done, int32_t take) {
+            return stats_launch(ctx, ingest_window(g, iq, nullptr, take, 0, ctx->stream), clip_level, d_stats + done);
+        },
         [&](Conditioning& next) -> int {
             if (const int rc = fetch(ctx, stats, d_stats)) return rc;
             if (const char* why = level_from_stats(stats.data(), n_ms, g->src.n, remove_dc, target_rms, &level, measured_out4))
@@ -3733,16 +3824,15 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
     if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
     if (!(threshold > 0.0) || !std::isfinite(threshold) || max_tones < 1 || max_tones > GYP_NOTCH_MAX_TONES)
         return refuse(ctx, who, "threshold must be positive and finite, 1 <= max_tones <= 8");
-    ToneSearch ts{g, first_ms, n_ms, threshold, max_tones};
-    if (!tone_rate_ok(g->fs) || ts.total() < kScanBlock)
+    ToneSearch ts{{g, first_ms, n_ms}, threshold, max_tones};
+    if (!tone_rate_ok(g->fs) || ts.range.total() < kScanBlock)
         return refuse(ctx, who, "the range must hold at least 1024 samples at a rate in [1000, 2^31) Hz");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, ts.iq_all.reserve((size_t)ts.total() * 2, Slack::exact));
+    HIP_TRY(ctx, ts.range.reserve());
     HIP_TRY(ctx, ts.recs_dev.reserve(std::max<size_t>((size_t)ts.n_scan() * kScanGrid, (size_t)ts.n_fine() * GYP_NOTCH_MAX_TONES), Slack::exact));
     // the blocks gathered are the producer's output behind the blanker and the excisor, where they are on: no notches, no level
-    if (const int rc = ingest_measure_range(
-            g, first_ms, n_ms, Suspend::level_notches, who,
-            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, ts.iq_all.get(), iq, done, take); },
+    if (const int rc = ts.range.measure(
+            Stage::notches, who,
             [&](Conditioning& next) -> int {
                 if (const int rc = tone_search(ts)) return rc;
                 if (install) {
@@ -3752,10 +3842,7 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
                 }
                 return GYP_OK;
             },
-            [&] {
-                (void)ts.iq_all.reset();
-                (void)ts.recs_dev.reset();
-            }))
+            [&] { (void)ts.recs_dev.reset(); }))
         return rc;
     for (size_t t = 0; t < ts.found.size(); ++t) {
         if (freqs_out) freqs_out[t] = ts.found[t];
@@ -3766,198 +3853,79 @@ int gyp_ingest_find_tones(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double 
 }
 
 int gyp_ingest_set_blanker(gyp_ingest* g, const gyp_blanker* blanker) {
-    const char* who = "gyp_ingest_set_blanker";
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "a blanker applies to device blocks", &ctx)) return rc;
-    if (blanker) {
-        if (const char* why = blanker_check(blanker)) return refuse(ctx, who, why);
-        if (g->src.n > kBlankMaxSamples) return refuse(ctx, who, kBlankTooWide);
-    }
-    g->cond.blank_on = blanker != nullptr;
-    g->cond.blanker = blanker ? *blanker : gyp_blanker{0.0f, 0.0f, 1.0f, 0};
-    return ingest_recondition(g);
+    return ingest_set_record(g, "gyp_ingest_set_blanker", kBlankerRecord, blanker,
+                             [&] { return hist_stage_check(blanker_check(blanker), g, kBlankHist); });
 }
 
 int gyp_ingest_get_blanker(const gyp_ingest* g, gyp_blanker* out, int32_t* enabled_out) {
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_blanker", "a blanker applies to device blocks", &ctx)) return rc;
-    if (out) *out = g->cond.blanker;
-    if (enabled_out) *enabled_out = g->cond.blank_on ? 1 : 0;
-    return GYP_OK;
+    return ingest_get_record(g, "gyp_ingest_get_blanker", kBlankerRecord, out, enabled_out);
 }
 
 int gyp_ingest_find_pulses(gyp_ingest* g, int64_t first_ms, int32_t n_ms, int32_t remove_dc, double threshold_over_median, int32_t guard,
                            int32_t install, gyp_blanker* blanker_out, double* measured_out2) {
     const char* who = "gyp_ingest_find_pulses";
     gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "the histogram is taken on the device", &ctx)) return rc;
-    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
-    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median) || guard < 0 || guard > kBlankMaxGuard)
-        return refuse(ctx, who, "threshold_over_median must be positive and finite, 0 <= guard <= 64");
-    const int32_t n = g->src.n;
-    if (n > kBlankMaxSamples) return refuse(ctx, who, kBlankTooWide);
-    const int64_t total = (int64_t)n_ms * n;
+    if (const int rc = hist_find_check(g, who, kBlankHist, first_ms, n_ms, threshold_over_median, guard, &ctx)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf<float> iq_all;
+    GatheredRange range{g, first_ms, n_ms};
     DevBuf<gyp_iq_stats> stats_dev;
-    DevBuf<uint32_t> hist_dev;
-    HIP_TRY(ctx, iq_all.reserve((size_t)total * 2, Slack::exact));
+    HIP_TRY(ctx, range.reserve());
     HIP_TRY(ctx, stats_dev.reserve((size_t)n_ms, Slack::exact));
-    HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
-    gyp_blanker found{};
-    auto derive = [&](Conditioning& next) -> int {
-        const IqWindow w = ingest_window(g, iq_all.get(), n_ms, first_ms);
-        float centre[2] = {0.0f, 0.0f};
-        if (remove_dc) {
-            std::vector<gyp_iq_stats> stats((size_t)n_ms);
-            if (const int rc = stats_launch(ctx, w, 0.0f, stats_dev.get())) return rc;
-            if (const int rc = fetch(ctx, stats, stats_dev.get())) return rc;
-            const IqMean mean = mean_from_stats(stats.data(), n_ms, n);
-            centre[0] = (float)mean.re;
-            centre[1] = (float)mean.im;
-            if (!std::isfinite(centre[0]) || !std::isfinite(centre[1])) return refuse(ctx, who, "the range's mean is not finite");
-        }
-        std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
-        if (const int rc = hist_launch(ctx, w, total, centre, hist_dev.get())) return rc;
-        if (const int rc = fetch(ctx, hist, hist_dev.get())) return rc;
-        if (const char* why = blank_from_hist(hist.data(), centre[0], centre[1], threshold_over_median, guard, &found, measured_out2))
-            return refuse(ctx, who, why);
-        if (install) {
-            next.blank_on = true;
-            next.blanker = found;
-        }
-        return GYP_OK;
-    };
-    // the blocks gathered are the producer's output: no blanker, no notches, no level
-    if (const int rc = ingest_measure_range(
-            g, first_ms, n_ms, Suspend::all, who,
-            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, iq_all.get(), iq, done, take); }, derive, [&] {
-                (void)iq_all.reset();
-                (void)stats_dev.reset();
-                (void)hist_dev.reset();
-            }))
-        return rc;
-    if (blanker_out) *blanker_out = found;
-    return GYP_OK;
+    float centre[2] = {0.0f, 0.0f};
+    // the blocks gathered are the producer's output: no blanker, no excisor, no notches, no level
+    return hist_find(
+        range, who, kBlankerRecord, install, blanker_out,
+        [&](const IqWindow& w, uint32_t* hist_dev) -> int {   // about the range's mean, where asked
+            if (remove_dc) {
+                std::vector<gyp_iq_stats> stats((size_t)n_ms);
+                if (const int rc = stats_launch(ctx, w, 0.0f, stats_dev.get())) return rc;
+                if (const int rc = fetch(ctx, stats, stats_dev.get())) return rc;
+                const IqMean mean = mean_from_stats(stats.data(), n_ms, w.n);
+                centre[0] = (float)mean.re;
+                centre[1] = (float)mean.im;
+                if (!std::isfinite(centre[0]) || !std::isfinite(centre[1])) return refuse(ctx, who, "the range's mean is not finite");
+            }
+            return hist_launch(ctx, w, range.total(), centre, hist_dev);
+        },
+        [&](const uint32_t* hist, gyp_blanker* found) {
+            return blank_from_hist(hist, centre[0], centre[1], threshold_over_median, guard, found, measured_out2);
+        },
+        [&] { (void)stats_dev.reset(); });
 }
 
 int gyp_ingest_last_blanked(gyp_ingest* g, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
-    const char* who = "gyp_ingest_last_blanked";
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "a blanker applies to device blocks", &ctx)) return rc;
-    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return refuse(ctx, who, "n_ms_out is NULL, or cap > 0 without counts_out");
-    *n_ms_out = g->last_n_ms;
-    const int32_t take = std::min(cap, g->last_n_ms);
-    if (take <= 0 || g->last_slot < 0) return GYP_OK;
-    const int d = g->last_slot;
-    if (!g->slot_blanked[d]) {
-        std::fill(counts_out, counts_out + take, 0);
-        return GYP_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
-    HIP_TRY(ctx, hipMemcpyAsync(counts_out, g->dev_blanked[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
-    HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
-    return GYP_OK;
+    return ingest_last_counts(g, "gyp_ingest_last_blanked", kBlankerRecord, counts_out, cap, n_ms_out);
 }
-
-// The per-slot counts of the excisor, made when a handle first gets one: a handle that never does allocates nothing for it.
-static int ingest_excise_buffers(gyp_ingest* g) {
-    if (!g->dev_excised.empty()) return GYP_OK;
-    gyp_ctx* ctx = g->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<DevBuf<int32_t>> bufs((size_t)g->src.depth);
-    for (auto& b : bufs) HIP_TRY(ctx, b.reserve((size_t)g->src.block_ms, Slack::exact));
-    g->dev_excised = std::move(bufs);
-    g->slot_excised.assign((size_t)g->src.depth, 0);
-    return GYP_OK;
-}
-static const char* const kExciseTooWide = "the excisor takes at most 65536 samples per millisecond";
 
 int gyp_ingest_set_excisor(gyp_ingest* g, const gyp_excisor* excisor) {
-    const char* who = "gyp_ingest_set_excisor";
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "an excisor applies to device blocks", &ctx)) return rc;
-    if (excisor) {
-        if (const char* why = excisor_check(excisor)) return refuse(ctx, who, why);
-        if (g->src.n > kExciseMaxSamples) return refuse(ctx, who, kExciseTooWide);
-        if (const int rc = ingest_excise_buffers(g)) return rc;
-    }
-    g->cond.excise_on = excisor != nullptr;
-    g->cond.excisor = excisor ? *excisor : gyp_excisor{1.0f, 0, {0, 0}};
-    return ingest_recondition(g);
+    return ingest_set_record(g, "gyp_ingest_set_excisor", kExcisorRecord, excisor,
+                             [&] { return hist_stage_check(excisor_check(excisor), g, kExciseHist); });
 }
 
 int gyp_ingest_get_excisor(const gyp_ingest* g, gyp_excisor* out, int32_t* enabled_out) {
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, "gyp_ingest_get_excisor", "an excisor applies to device blocks", &ctx)) return rc;
-    if (out) *out = g->cond.excisor;
-    if (enabled_out) *enabled_out = g->cond.excise_on ? 1 : 0;
-    return GYP_OK;
+    return ingest_get_record(g, "gyp_ingest_get_excisor", kExcisorRecord, out, enabled_out);
 }
 
 int gyp_ingest_find_excisor(gyp_ingest* g, int64_t first_ms, int32_t n_ms, double threshold_over_median, int32_t guard, int32_t install,
                             gyp_excisor* excisor_out, double* measured_out2) {
     const char* who = "gyp_ingest_find_excisor";
     gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "the histogram is taken on the device", &ctx)) return rc;
-    if (const int rc = ingest_range_check(g, who, first_ms, n_ms, 1000)) return rc;
-    if (!(threshold_over_median > 0.0) || !std::isfinite(threshold_over_median) || guard < 0 || guard > kExciseMaxGuard)
-        return refuse(ctx, who, "threshold_over_median must be positive and finite, 0 <= guard <= 8");
-    const int32_t n = g->src.n;
-    if (n > kExciseMaxSamples) return refuse(ctx, who, kExciseTooWide);
-    if (n < GYP_EXCISE_FRAME) return refuse(ctx, who, "the histogram needs at least 256 samples per millisecond");
+    if (const int rc = hist_find_check(g, who, kExciseHist, first_ms, n_ms, threshold_over_median, guard, &ctx)) return rc;
+    if (g->src.n < GYP_EXCISE_FRAME) return refuse(ctx, who, "the histogram needs at least 256 samples per millisecond");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (install)
-        if (const int rc = ingest_excise_buffers(g)) return rc;
-    DevBuf<float> iq_all;
-    DevBuf<uint32_t> hist_dev;
-    HIP_TRY(ctx, iq_all.reserve((size_t)n_ms * n * 2, Slack::exact));
-    HIP_TRY(ctx, hist_dev.reserve(GYP_POWER_HIST_BINS, Slack::exact));
-    gyp_excisor found{};
-    auto derive = [&](Conditioning& next) -> int {
-        std::vector<uint32_t> hist(GYP_POWER_HIST_BINS);
-        if (const int rc = spectrum_hist_launch(ctx, ingest_window(g, iq_all.get(), n_ms, first_ms), hist_dev.get())) return rc;
-        if (const int rc = fetch(ctx, hist, hist_dev.get())) return rc;
-        if (const char* why = excise_from_hist(hist.data(), threshold_over_median, guard, &found, measured_out2)) return refuse(ctx, who, why);
-        if (install) {
-            next.excise_on = true;
-            next.excisor = found;
-        }
-        return GYP_OK;
-    };
+        if (const int rc = ingest_counts_made(g, Stage::excisor)) return rc;
+    GatheredRange range{g, first_ms, n_ms};
+    HIP_TRY(ctx, range.reserve());
     // the blocks gathered are the producer's output behind the blanker, where one is on: no excisor, no notches, no level
-    if (const int rc = ingest_measure_range(
-            g, first_ms, n_ms, Suspend::level_notches_excisor, who,
-            [&](const float* iq, int32_t done, int32_t take) { return ingest_gather(g, iq_all.get(), iq, done, take); }, derive, [&] {
-                (void)iq_all.reset();
-                (void)hist_dev.reset();
-            }))
-        return rc;
-    if (excisor_out) *excisor_out = found;
-    return GYP_OK;
+    return hist_find(
+        range, who, kExcisorRecord, install, excisor_out,
+        [&](const IqWindow& w, uint32_t* hist_dev) { return spectrum_hist_launch(ctx, w, hist_dev); },
+        [&](const uint32_t* hist, gyp_excisor* found) { return excise_from_hist(hist, threshold_over_median, guard, found, measured_out2); }, [] {});
 }
 
 int gyp_ingest_last_excised(gyp_ingest* g, int32_t* counts_out, int32_t cap, int32_t* n_ms_out) {
-    const char* who = "gyp_ingest_last_excised";
-    gyp_ctx* ctx;
-    if (const int rc = ingest_device_handle(g, who, "an excisor applies to device blocks", &ctx)) return rc;
-    if (!n_ms_out || cap < 0 || (cap > 0 && !counts_out)) return refuse(ctx, who, "n_ms_out is NULL, or cap > 0 without counts_out");
-    *n_ms_out = g->last_n_ms;
-    const int32_t take = std::min(cap, g->last_n_ms);
-    if (take <= 0 || g->last_slot < 0) return GYP_OK;
-    const int d = g->last_slot;
-    if (g->slot_excised.empty() || !g->slot_excised[d]) {
-        std::fill(counts_out, counts_out + take, 0);
-        return GYP_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, g->counts_stream.create(hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventSynchronize(g->ready[d].get()));   // that block's chain only: not what was uploaded ahead
-    HIP_TRY(ctx, hipMemcpyAsync(counts_out, g->dev_excised[d].get(), (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost, g->counts_stream.get()));
-    HIP_TRY(ctx, hipStreamSynchronize(g->counts_stream.get()));
-    return GYP_OK;
+    return ingest_last_counts(g, "gyp_ingest_last_excised", kExcisorRecord, counts_out, cap, n_ms_out);
 }
 
 int gyp_ingest_times(const gyp_ingest* g, int64_t first_ms, int32_t n_ms, double* start_out, double* end_out) {

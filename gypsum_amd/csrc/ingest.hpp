@@ -332,11 +332,12 @@ static IngestExtent ingest_extent(const IngestSource& s, int64_t file_bytes) {
     return e;
 }
 
-// What a measurement puts aside: the level always; the notches too (gyp_ingest_find_tones); the excisor as well
-// (gyp_ingest_find_excisor); everything (gyp_ingest_find_pulses).
-enum class Suspend : int32_t { level, level_notches, level_notches_excisor, all };
-// What is applied in place to every device block behind its producer, on the copy stream: the blanker, then the excisor, then the
-// notches, then the level.  One value, so that a measurement can put it aside and back whole (ingest_measure_range).
+// The conditioning chain: what is applied in place to every device block behind its producer, on the copy stream, in this order.
+// It is written here only: ingest_condition walks it, and a measurement sees what is in front of its stage (Conditioning::upstream_of).
+enum class Stage : int32_t { blanker, excisor, notches, level };
+constexpr Stage kChain[] = {Stage::blanker, Stage::excisor, Stage::notches, Stage::level};
+// The stages' switches and values.  One value, so that a measurement can put it aside and back whole (ingest_measure_range); a
+// stage that is off holds what it is initialised with here, or what it held when a measurement switched it off.
 struct Conditioning {
     bool level_on = false;     // gyp_ingest_set_level / gyp_ingest_calibrate
     gyp_iq_level level{0.0f, 0.0f, 1.0f, 0};
@@ -345,16 +346,38 @@ struct Conditioning {
     gyp_blanker blanker{0.0f, 0.0f, 1.0f, 0};
     bool excise_on = false;    // gyp_ingest_set_excisor / gyp_ingest_find_excisor
     gyp_excisor excisor{1.0f, 0, {0, 0}};
-    // The conditioning of the blocks a measurement sees.  What is put aside is off but kept (a suspended blanker, excisor or level keeps its
-    // values), except the notches, whose list is their switch.
-    Conditioning without(Suspend what) const {
+    bool on(Stage s) const {
+        return s == Stage::blanker ? blank_on : s == Stage::excisor ? excise_on : s == Stage::notches ? notches.count > 0 : level_on;
+    }
+    // The conditioning of the blocks the measurement of stage s sees: s and everything behind it off.  What is switched off keeps
+    // its values, except the notches, whose list is their switch.
+    Conditioning upstream_of(Stage s) const {
         Conditioning c = *this;
-        c.level_on = false;
-        if (what != Suspend::level) c.notches = gyp_notch_tones{};
-        if (what == Suspend::level_notches_excisor || what == Suspend::all) c.excise_on = false;
-        if (what == Suspend::all) c.blank_on = false;
+        for (const Stage t : kChain) {
+            if (t < s) continue;
+            if (t == Stage::notches) c.notches = gyp_notch_tones{};
+            else (t == Stage::blanker ? c.blank_on : t == Stage::excisor ? c.excise_on : c.level_on) = false;
+        }
         return c;
     }
+};
+
+// What gyp_ingest_last_blanked and _last_excised read: a counting stage's count per millisecond of the block in each device slot.
+struct SlotCounts {
+    std::vector<DevBuf<int32_t>> dev;   // per slot: block_ms words
+    std::vector<uint8_t> went;          // per slot: the block in it went through the stage
+    // Slots [what there is, depth) of block_ms words each: nothing where they exist.  After a failure the slots made so far stay.
+    hipError_t ensure(int32_t depth, int32_t block_ms) {
+        while ((int32_t)dev.size() < depth) {
+            DevBuf<int32_t> slot;
+            if (const hipError_t e = slot.reserve((size_t)block_ms, Slack::exact)) return e;
+            dev.push_back(std::move(slot));
+            went.push_back(0);
+        }
+        return hipSuccess;
+    }
+    void mark(int d, bool through) { if (d < (int)went.size()) went[d] = through ? 1 : 0; }
+    bool passed(int d) const { return d < (int)went.size() && went[d]; }
 };
 
 struct gyp_ingest {
@@ -386,11 +409,10 @@ struct gyp_ingest {
     Stream copy_stream;              // (declared before everything used on it: destroyed last)
     std::vector<DevBuf<uint8_t>> dev_raw;   // file-width words (unused for float32: the upload lands in dev_iq directly)
     std::vector<DevBuf<float>> dev_iq;
-    std::vector<DevBuf<int32_t>> dev_blanked;   // per slot: the blanker's count per millisecond of the slot's block (block_ms words)
-    std::vector<uint8_t> slot_blanked;       // per slot: the block in it went through the blanker
-    std::vector<DevBuf<int32_t>> dev_excised;   // per slot, as dev_blanked: the excisor's count per millisecond (made when an excisor is first set)
-    std::vector<uint8_t> slot_excised;       // per slot: the block in it went through the excisor
-    Stream counts_stream;            // gyp_ingest_last_blanked's download (made by its first call: it must not wait for anything else)
+    SlotCounts blanked;              // the blanker's counts, made at open
+    SlotCounts excised;              // the excisor's, made when the handle first gets an excisor: one that never does allocates nothing
+    SlotCounts* counts_of(Stage s) { return s == Stage::blanker ? &blanked : s == Stage::excisor ? &excised : nullptr; }
+    Stream counts_stream;            // ingest_last_counts' download (made by its first call: it must not wait for anything else)
     int last_slot = -1;              // the device slot of the block most recently handed out (-1: none since open / seek)
     int32_t last_n_ms = 0;
     std::vector<Event> uploaded, ready;

@@ -23,7 +23,7 @@ from typing import Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _records
 
 # one per stream: gyp_excisor, 16 bytes
 EXCISOR_DTYPE = _lib.EXCISOR
@@ -40,32 +40,17 @@ def n_frames(samples_per_ms: int) -> int:
 
 
 @dataclass(frozen=True)
-class Excisor:
+class Excisor(_records.Record):
     """A bin of a 256-point frame whose |X| reaches `threshold` is excised, with `guard` bins on either side (gyp_excisor)."""
     threshold: float = 1.0
     guard: int = 1
-
-    def record(self) -> np.ndarray:
-        rec = np.zeros(1, dtype=EXCISOR_DTYPE)
-        with np.errstate(over="ignore"):                    # (a threshold beyond float32 becomes inf, which check_excisor refuses)
-            rec["threshold"] = self.threshold
-        rec["guard"] = int(self.guard)
-        return rec
-
-    @classmethod
-    def from_record(cls, rec) -> "Excisor":
-        r = np.asarray(rec, dtype=EXCISOR_DTYPE).reshape(-1)[0]
-        return cls(float(r["threshold"]), int(r["guard"]))
+    DTYPE, MEASURED = EXCISOR_DTYPE, ("median", "threshold")
 
 
 def excisor_records(excisors, n_streams: int = None) -> np.ndarray:
     """One gyp_excisor record per stream from `excisors`: records already, one Excisor (for one stream, or for each of n_streams
     streams) or a sequence of them."""
-    if isinstance(excisors, np.ndarray) and excisors.dtype == EXCISOR_DTYPE:
-        return np.ascontiguousarray(excisors).reshape(-1)
-    if isinstance(excisors, Excisor):
-        excisors = [excisors] * (1 if n_streams is None else max(1, int(n_streams)))
-    return np.concatenate([e.record() for e in excisors])
+    return _records.records(excisors, Excisor, n_streams)
 
 
 def check_excisor(excisor: Excisor) -> None:
@@ -80,16 +65,10 @@ def check_excisor(excisor: Excisor) -> None:
 def excisor_from_hist(hist: np.ndarray, threshold_over_median: float = 16.0, guard: int = 1) -> Tuple[Excisor, dict]:
     """The excisor whose threshold is sqrt(threshold_over_median x the median bin power) of one stream's histogram
     (gyp_excise_from_hist: host only, no GPU).  Returns (excisor, measured) with measured = {"median", "threshold"} in float64."""
-    lib = _lib.load()
-    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(-1)
-    if len(h) != HIST_BINS:
-        raise ValueError(f"a histogram has {HIST_BINS} bins")
-    rec, measured = np.zeros(1, dtype=EXCISOR_DTYPE), np.zeros(2)
-    rc = lib.gyp_excise_from_hist(_lib.ptr(h), float(threshold_over_median), int(guard), _lib.ptr(rec), _lib.ptr(measured))
-    if rc != 0:
-        raise _lib.GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
-    return Excisor.from_record(rec), measured_dict(measured)
+    h = _records.one_hist(hist)
+    return _records.derived(Excisor, lambda lib, rec, measured: lib.gyp_excise_from_hist(
+        _lib.ptr(h), float(threshold_over_median), int(guard), rec, measured))
 
 
 def measured_dict(measured2: np.ndarray) -> dict:
-    return {"median": float(measured2[0]), "threshold": float(measured2[1])}
+    return _records.measured_dict(Excisor, measured2)

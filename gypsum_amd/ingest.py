@@ -35,7 +35,10 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _records
+from .blanker import Blanker
+from .excisor import Excisor
+from .level import IqLevel, default_target_rms
 
 _FORMATS = {np.dtype(np.float32): _lib.GYP_FMT_F32, np.dtype(np.int8): _lib.GYP_FMT_I8,
             np.dtype(np.int16): _lib.GYP_FMT_I16, np.dtype(np.uint8): _lib.GYP_FMT_U8}
@@ -128,19 +131,35 @@ class IqFileIngest:
         """Integer recordings: device samples = word * scale (default 1 = the reference's raw values)."""
         self._check(self._lib.gyp_ingest_set_scale(self._h, float(scale)))
 
+    # What the record-valued stages (level, blanker, excisor) do alike: `cls` is IqLevel, Blanker or Excisor, `fn` the entry point
+    def _set_record(self, fn, value) -> None:
+        rec = None if value is None else value.record()
+        self._check(fn(self._h, _lib.ptr(rec)))
+
+    def _get_record(self, fn, cls):
+        rec, on = np.zeros(1, dtype=cls.DTYPE), C.c_int32()
+        self._check(fn(self._h, _lib.ptr(rec), C.byref(on)))
+        return cls.from_record(rec) if on.value else None
+
+    def _find_record(self, fn, cls, first_ms, n_ms, *args):
+        rec, measured = np.zeros(1, dtype=cls.DTYPE), np.zeros(len(cls.MEASURED))
+        self._check(fn(self._h, int(first_ms), int(n_ms), *args, _lib.ptr(rec), _lib.ptr(measured)))
+        return cls.from_record(rec), _records.measured_dict(cls, measured)
+
+    def _last_counts(self, fn) -> np.ndarray:
+        counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
+        self._check(fn(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
+        return counts[:n_ms.value]
+
     def set_level(self, level) -> None:
         """A gypsum_amd.level.IqLevel every device block is conditioned with from the next block handed out on: (x - dc) * gain behind
         whatever produced the block, x = word * scale as without a level (gyp_ingest_set_level).  None switches it off."""
-        rec = None if level is None else level.record()
-        self._check(self._lib.gyp_ingest_set_level(self._h, _lib.ptr(rec)))
+        self._set_record(self._lib.gyp_ingest_set_level, level)
 
     @property
     def level(self):
         """The installed IqLevel, or None while none is on."""
-        from .level import LEVEL_DTYPE, IqLevel
-        rec, on = np.zeros(1, dtype=LEVEL_DTYPE), C.c_int32()
-        self._check(self._lib.gyp_ingest_get_level(self._h, _lib.ptr(rec), C.byref(on)))
-        return IqLevel.from_record(rec) if on.value else None
+        return self._get_record(self._lib.gyp_ingest_get_level, IqLevel)
 
     def calibrate(self, first_ms: int = 0, n_ms: int = 100, target_rms: Optional[float] = None, remove_dc: bool = True,
                   clip_level: float = 0.0):
@@ -148,12 +167,8 @@ class IqFileIngest:
         the device and install the level that removes their mean (remove_dc) and brings the RMS of |x| to target_rms (default:
         gypsum_amd.level.default_target_rms(N)).  Returns (IqLevel, measured) as gypsum_amd.level.level_from_stats does; the
         cursor stays where it was, blocks handed out earlier are no longer valid (gyp_ingest_calibrate)."""
-        from .level import LEVEL_DTYPE, IqLevel, default_target_rms, measured_dict
-        rec, measured = np.zeros(1, dtype=LEVEL_DTYPE), np.zeros(4)
         target = default_target_rms(self.n) if target_rms is None else float(target_rms)
-        self._check(self._lib.gyp_ingest_calibrate(self._h, int(first_ms), int(n_ms), int(bool(remove_dc)), target, float(clip_level),
-                                                   _lib.ptr(rec), _lib.ptr(measured)))
-        return IqLevel.from_record(rec), measured_dict(measured)
+        return self._find_record(self._lib.gyp_ingest_calibrate, IqLevel, first_ms, n_ms, int(bool(remove_dc)), target, float(clip_level))
 
     def set_notches(self, freqs_hz) -> None:
         """Tones (whole Hz, at most 8, |f| < fs / 2, 4000 Hz apart) projected out of every device block from the next block handed
@@ -181,16 +196,12 @@ class IqFileIngest:
     def set_blanker(self, blanker) -> None:
         """A gypsum_amd.blanker.Blanker every device block is blanked with from the next block handed out on, between whatever
         produced the block and the notches (gyp_ingest_set_blanker).  None switches it off."""
-        rec = None if blanker is None else blanker.record()
-        self._check(self._lib.gyp_ingest_set_blanker(self._h, _lib.ptr(rec)))
+        self._set_record(self._lib.gyp_ingest_set_blanker, blanker)
 
     @property
     def blanker(self):
         """The installed Blanker, or None while none is on."""
-        from .blanker import BLANKER_DTYPE, Blanker
-        rec, on = np.zeros(1, dtype=BLANKER_DTYPE), C.c_int32()
-        self._check(self._lib.gyp_ingest_get_blanker(self._h, _lib.ptr(rec), C.byref(on)))
-        return Blanker.from_record(rec) if on.value else None
+        return self._get_record(self._lib.gyp_ingest_get_blanker, Blanker)
 
     def find_pulses(self, first_ms: int = 0, n_ms: int = 10, threshold_over_median: float = 16.0, guard: int = 4, remove_dc: bool = True,
                     install: bool = True):
@@ -199,31 +210,22 @@ class IqFileIngest:
         threshold is sqrt(threshold_over_median x the median power).  Returns (Blanker, measured) as
         gypsum_amd.blanker.blanker_from_hist does and installs it (install) as set_blanker does; the cursor stays where it was,
         blocks handed out earlier are no longer valid (gyp_ingest_find_pulses)."""
-        from .blanker import BLANKER_DTYPE, Blanker, measured_dict
-        rec, measured = np.zeros(1, dtype=BLANKER_DTYPE), np.zeros(2)
-        self._check(self._lib.gyp_ingest_find_pulses(self._h, int(first_ms), int(n_ms), int(bool(remove_dc)), float(threshold_over_median),
-                                                     int(guard), int(bool(install)), _lib.ptr(rec), _lib.ptr(measured)))
-        return Blanker.from_record(rec), measured_dict(measured)
+        return self._find_record(self._lib.gyp_ingest_find_pulses, Blanker, first_ms, n_ms, int(bool(remove_dc)), float(threshold_over_median),
+                                 int(guard), int(bool(install)))
 
     def last_blanked(self) -> np.ndarray:
         """int32 counts of blanked samples per millisecond of the block most recently handed out by next_device_block (empty
         before the first block and after a seek; zeros while no blanker is on).  Waits for that block only (gyp_ingest_last_blanked)."""
-        counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
-        self._check(self._lib.gyp_ingest_last_blanked(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
-        return counts[:n_ms.value]
+        return self._last_counts(self._lib.gyp_ingest_last_blanked)
 
     def set_excisor(self, excisor) -> None:
         """A gypsum_amd.excisor.Excisor every device block is excised with from the next block handed out on, between the blanker
         and the notches (gyp_ingest_set_excisor).  None switches it off."""
-        rec = None if excisor is None else excisor.record()
-        self._check(self._lib.gyp_ingest_set_excisor(self._h, _lib.ptr(rec)))
+        self._set_record(self._lib.gyp_ingest_set_excisor, excisor)
 
     def get_excisor(self):
         """The installed Excisor, or None while none is on (gyp_ingest_get_excisor)."""
-        from .excisor import EXCISOR_DTYPE, Excisor
-        rec, on = np.zeros(1, dtype=EXCISOR_DTYPE), C.c_int32()
-        self._check(self._lib.gyp_ingest_get_excisor(self._h, _lib.ptr(rec), C.byref(on)))
-        return Excisor.from_record(rec) if on.value else None
+        return self._get_record(self._lib.gyp_ingest_get_excisor, Excisor)
 
     excisor = property(get_excisor)
 
@@ -233,19 +235,14 @@ class IqFileIngest:
         excisor whose threshold is sqrt(threshold_over_median x the median power).  Returns (Excisor, measured) as
         gypsum_amd.excisor.excisor_from_hist does and installs it (install) as set_excisor does; the cursor stays where it was,
         blocks handed out earlier are no longer valid (gyp_ingest_find_excisor)."""
-        from .excisor import EXCISOR_DTYPE, Excisor, measured_dict
-        rec, measured = np.zeros(1, dtype=EXCISOR_DTYPE), np.zeros(2)
-        self._check(self._lib.gyp_ingest_find_excisor(self._h, int(first_ms), int(n_ms), float(threshold_over_median), int(guard),
-                                                      int(bool(install)), _lib.ptr(rec), _lib.ptr(measured)))
-        return Excisor.from_record(rec), measured_dict(measured)
+        return self._find_record(self._lib.gyp_ingest_find_excisor, Excisor, first_ms, n_ms, float(threshold_over_median), int(guard),
+                                 int(bool(install)))
 
     def last_excised(self) -> np.ndarray:
         """int32 counts of excised (frame, bin) cells per millisecond of the block most recently handed out by next_device_block
         (empty before the first block and after a seek; zeros while no excisor is on).  Waits for that block only
         (gyp_ingest_last_excised)."""
-        counts, n_ms = np.zeros(self.block_ms, dtype=np.int32), C.c_int32()
-        self._check(self._lib.gyp_ingest_last_excised(self._h, _lib.ptr(counts), len(counts), C.byref(n_ms)))
-        return counts[:n_ms.value]
+        return self._last_counts(self._lib.gyp_ingest_last_excised)
 
     def seek(self, ms: int) -> None:
         self._check(self._lib.gyp_ingest_seek(self._h, int(ms)))

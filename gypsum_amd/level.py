@@ -19,7 +19,7 @@ from typing import Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _records
 
 # one per (stream, millisecond): gyp_iq_stats, 32 bytes
 STATS_DTYPE = _lib.IQ_STATS
@@ -34,46 +34,27 @@ def default_target_rms(samples_per_ms: int) -> float:
 
 
 @dataclass(frozen=True)
-class IqLevel:
+class IqLevel(_records.Record):
     """y = (x - (dc_re + 1j * dc_im)) * gain, in float32 (gyp_iq_level)."""
     dc_re: float = 0.0
     dc_im: float = 0.0
     gain: float = 1.0
-
-    def record(self) -> np.ndarray:
-        rec = np.zeros(1, dtype=LEVEL_DTYPE)
-        rec["dc_re"], rec["dc_im"], rec["gain"] = self.dc_re, self.dc_im, self.gain
-        return rec
-
-    @classmethod
-    def from_record(cls, rec) -> "IqLevel":
-        r = np.asarray(rec, dtype=LEVEL_DTYPE).reshape(-1)[0]
-        return cls(float(r["dc_re"]), float(r["dc_im"]), float(r["gain"]))
+    DTYPE, MEASURED = LEVEL_DTYPE, ("mean_re", "mean_im", "rms", "clipped")
 
 
 def level_records(levels) -> np.ndarray:
     """One gyp_iq_level record per entry of `levels` (an IqLevel, a sequence of them, or records already)."""
-    if isinstance(levels, IqLevel):
-        levels = [levels]
-    if isinstance(levels, np.ndarray) and levels.dtype == LEVEL_DTYPE:
-        return np.ascontiguousarray(levels).reshape(-1)
-    return np.concatenate([l.record() for l in levels])
+    return _records.records(levels, IqLevel)
 
 
 def level_from_stats(stats: np.ndarray, samples_per_ms: int, target_rms: float, remove_dc: bool = True) -> Tuple[IqLevel, dict]:
     """The level that removes the mean (remove_dc) and brings the RMS of |x| per complex sample to target_rms, from the
     per-millisecond records of one stream (gyp_iq_level_from_stats: host only, no GPU).  Returns (level, measured) with
     measured = {"mean_re", "mean_im", "rms", "clipped"}: the mean, the RMS about the removed offset, the share of clipped components."""
-    lib = _lib.load()
     st = np.ascontiguousarray(stats, dtype=STATS_DTYPE).reshape(-1)
-    rec = np.zeros(1, dtype=LEVEL_DTYPE)
-    measured = np.zeros(4)
-    rc = lib.gyp_iq_level_from_stats(_lib.ptr(st), len(st), int(samples_per_ms), int(bool(remove_dc)), float(target_rms),
-                                     _lib.ptr(rec), _lib.ptr(measured))
-    if rc != 0:
-        raise _lib.GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
-    return IqLevel.from_record(rec), measured_dict(measured)
+    return _records.derived(IqLevel, lambda lib, rec, measured: lib.gyp_iq_level_from_stats(
+        _lib.ptr(st), len(st), int(samples_per_ms), int(bool(remove_dc)), float(target_rms), rec, measured))
 
 
 def measured_dict(measured4: np.ndarray) -> dict:
-    return {"mean_re": float(measured4[0]), "mean_im": float(measured4[1]), "rms": float(measured4[2]), "clipped": float(measured4[3])}
+    return _records.measured_dict(IqLevel, measured4)

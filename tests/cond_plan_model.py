@@ -13,6 +13,8 @@ A shape is a row of int64: (stage, n_cus, wg_per_cu, n, a, b, stride, in_addr, o
     QUALITY    n channels, a = n_ms, b = window_ms
     WIDEN      a = n_words
     UNPACK     n streams, a = n_samples, b = bits per component, stride, out_addr
+    EXCISE     n streams, a = n_ms
+    SPECTRUM   n streams, a = n_ms (the excisor's histogram: every stream in one launch)
 A plan is a row of FIELDS: the first and the last launch of the call, and over all launches the sum and the largest of their stream
 counts, how many start where the one before ended, and the smallest and largest grid.x.
 """
@@ -20,9 +22,9 @@ from __future__ import annotations
 
 import numpy as np
 
-STATS, CONDITION, NOTCH, BLANK, HIST, TONES, QUALITY, WIDEN, UNPACK = range(9)
-# streams (channels) per launch: kLevelStreams, kNotchStreams, kBlankStreams (both blanker kernels), kQualityChans
-K = {CONDITION: 8, NOTCH: 8, BLANK: 8, HIST: 8, QUALITY: 1024}
+STATS, CONDITION, NOTCH, BLANK, HIST, TONES, QUALITY, WIDEN, UNPACK, EXCISE, SPECTRUM = range(11)
+# streams (channels) per launch: kLevelStreams, kNotchStreams, kBlankStreams (both blanker kernels), kQualityChans, kExciseStreams
+K = {CONDITION: 8, NOTCH: 8, BLANK: 8, HIST: 8, QUALITY: 1024, EXCISE: 8}
 NOTCH_LDS_SAMPLES = 16384
 SHAPE_COLUMNS = ("stage", "n_cus", "wg_per_cu", "n", "a", "b", "stride", "in_addr", "out_addr", "flag")
 FIELDS = ("n_chunks", "vec4", "lds_bytes", "per_stream", "cap",
@@ -49,9 +51,9 @@ def grid_widen(n_words, cap):
 def plans(shapes: np.ndarray) -> np.ndarray:
     """int64 [rows, len(FIELDS)] for int64 shapes [rows, len(SHAPE_COLUMNS)]."""
     stage, n_cus, wg, n, a, b, stride, in_addr, out_addr, flag = np.asarray(shapes, dtype=np.int64).T
-    is_ = {s: stage == s for s in range(9)}
+    is_ = {s: stage == s for s in range(11)}
     cap = np.where(is_[TONES], n_cus * 8, np.where(is_[QUALITY], n_cus * 64, n_cus * wg))
-    k = n.copy()                                                  # statistics and tones: every stream in one launch
+    k = n.copy()                                                  # statistics, tones and the spectrum histogram: every stream in one launch
     for s, per_launch in K.items():
         k[is_[s]] = per_launch
     per_row = is_[CONDITION] | is_[HIST]
@@ -61,7 +63,7 @@ def plans(shapes: np.ndarray) -> np.ndarray:
     lds = np.where(is_[NOTCH] & (b <= NOTCH_LDS_SAMPLES) & (flag == 0), 8 * b, 0)
     with np.errstate(divide="ignore"):
         windows = ceil_div(a, np.where(is_[QUALITY], b, 1))
-    per_stream = np.select([is_[STATS] | is_[NOTCH] | is_[BLANK], is_[CONDITION], is_[HIST], is_[TONES], is_[QUALITY]],
+    per_stream = np.select([is_[STATS] | is_[NOTCH] | is_[BLANK] | is_[EXCISE] | is_[SPECTRUM], is_[CONDITION], is_[HIST], is_[TONES], is_[QUALITY]],
                            [a, np.where(vec4 == 1, (a + 1) // 2, a), a // 2, a * b, windows], 0)
     n_chunks = ceil_div(n, np.maximum(k, 1))
 
@@ -90,4 +92,25 @@ def plans(shapes: np.ndarray) -> np.ndarray:
     out[u, FIELDS.index("cap")] = cap[u]
     out[u, FIELDS.index("gx_first")] = np.maximum(1, np.minimum(ceil_div(items, 256), cap[u]))
     out[u, FIELDS.index("items_first")] = items
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the chain
+# A conditioning as a row of integers (floats as their bits), stage by stage in the chain's order: [first, end) of each stage's
+# fields, and where its switch is (the notches' is their count).
+CHAIN_FIELDS = ((0, 5), (5, 10), (10, 20), (20, 25))     # blanker, excisor, notches, level
+CHAIN_SWITCH = (0, 5, 10, 20)
+CHAIN_ROW = 25
+NOTCHES = 2
+
+
+def upstream_of(row, stage: int):
+    """The conditioning a measurement of `stage` sees: the stages in front of it unchanged, it and the ones behind it off.  What is
+    switched off keeps its values, except the notches, whose list is their switch: it is cleared."""
+    out = list(row)
+    for s in range(stage, len(CHAIN_FIELDS)):
+        first, end = CHAIN_FIELDS[s]
+        out[CHAIN_SWITCH[s]] = 0
+        if s == NOTCHES:
+            out[first:end] = [0] * (end - first)
     return out

@@ -780,6 +780,8 @@ static void cond_plans() {
             case 4: p = hist_plan(cap, kBlankStreams, n, a); break;
             case 5: p = tones_plan(n_cus, n, (int32_t)a, (int32_t)b); break;
             case 6: p = quality_plan(n_cus, kQualityChans, n, (int32_t)a, (int32_t)b); break;
+            case 9: p = excise_plan(cap, kExciseStreams, n, (int32_t)a); break;    // excise_launch's chunks
+            case 10: p = excise_plan(cap, n, n, (int32_t)a); break;                // spectrum_hist_launch's one launch
             default: die("cond-plan: unknown stage");
         }
         REQUIRE(p.n_chunks >= 1);
@@ -799,6 +801,41 @@ static void cond_plans() {
             plans.push_back(v);
     }
     Out("plans.i64").bytes(plans.data(), plans.size() * sizeof(int64_t));
+}
+
+// --------------------------------------------------------------------------------------------------------- cond-chain
+// Conditioning::upstream_of for every combination of stages on and off and every stage measured.  chain.i64 rows: the combination
+// (bit i: stage i of the chain is on), the stage, the conditioning before and after as cond_row lays it out.  A stage that is off
+// holds values of its own too (a measurement had switched it off), except the notches, whose list is their switch.
+static void cond_row(const Conditioning& c, std::vector<int64_t>& row) {
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return (int64_t)u; };
+    for (int64_t v : {(int64_t)c.blank_on, bits(c.blanker.center_re), bits(c.blanker.center_im), bits(c.blanker.threshold), (int64_t)c.blanker.guard,
+                      (int64_t)c.excise_on, bits(c.excisor.threshold), (int64_t)c.excisor.guard, (int64_t)c.excisor.reserved[0], (int64_t)c.excisor.reserved[1],
+                      (int64_t)c.notches.count, (int64_t)c.notches.reserved})
+        row.push_back(v);
+    for (int64_t f : c.notches.freq_hz) row.push_back(f);
+    for (int64_t v : {(int64_t)c.level_on, bits(c.level.dc_re), bits(c.level.dc_im), bits(c.level.gain), (int64_t)c.level.reserved}) row.push_back(v);
+}
+static void cond_chain() {
+    std::vector<int64_t> rows;
+    for (int combo = 0; combo < 16; ++combo)
+        for (const Stage s : kChain) {
+            Conditioning c;
+            c.blank_on = combo & 1, c.blanker = gyp_blanker{1.5f + combo, -2.5f, 30.0f, 4};
+            c.excise_on = (combo & 2) != 0, c.excisor = gyp_excisor{100.0f + combo, 1, {0, 0}};
+            if (combo & 4) {
+                c.notches.count = 3;
+                for (int i = 0; i < 3; ++i) c.notches.freq_hz[i] = -403000 + 5000 * i + combo;
+            }
+            c.level_on = (combo & 8) != 0, c.level = gyp_iq_level{0.25f, -0.5f, 0.03125f * (1 + combo), 0};
+            REQUIRE(c.on(Stage::blanker) == c.blank_on && c.on(Stage::excisor) == c.excise_on && c.on(Stage::notches) == ((combo & 4) != 0) &&
+                    c.on(Stage::level) == c.level_on);
+            rows.push_back(combo);
+            rows.push_back((int64_t)s);
+            cond_row(c, rows);
+            cond_row(c.upstream_of(s), rows);
+        }
+    Out("chain.i64").bytes(rows.data(), rows.size() * sizeof(int64_t));
 }
 
 // --------------------------------------------------------------------------------------------------------- dev-mem
@@ -942,7 +979,7 @@ int main(int argc, char** argv) {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
         {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"resample-plan", drv::resample_plans},
-        {"cond-plan", drv::cond_plans}, {"dev-mem", drv::dev_mem},
+        {"cond-plan", drv::cond_plans}, {"cond-chain", drv::cond_chain}, {"dev-mem", drv::dev_mem},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

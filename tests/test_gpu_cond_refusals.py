@@ -1,6 +1,7 @@
 """Every refused call of the conditioning stages and of the ingest calls that drive them, with its return code and the text
 gyp_last_error gives: gyp_iq_stats_dev, gyp_condition_iq_dev, gyp_iq_tones_dev, gyp_notch_iq_dev, gyp_blank_iq_dev,
-gyp_iq_power_hist_dev, gyp_track_quality_dev and gyp_ingest_set_* / get_* / calibrate / find_tones / find_pulses / last_blanked.
+gyp_iq_power_hist_dev, gyp_excise_iq_dev, gyp_iq_spectrum_hist_dev, gyp_track_quality_dev and gyp_ingest_set_* / get_* / calibrate /
+find_tones / find_pulses / find_excisor / last_blanked / last_excised / next_host.
 
 One table (refused_calls), one row per condition: where an `if` tests several conditions, each has a row of its own.  The expected
 (code, text) pairs are tests/golden/cond_refusals.json, recorded once from the library as it stood before these entry points' checks
@@ -41,6 +42,12 @@ def _blanker(center_re=0.0, center_im=0.0, threshold=3.0, guard=4):
     return r
 
 
+def _excisor(threshold=3.0, guard=2, reserved=(0, 0)):
+    r = np.zeros(1, dtype=_lib.EXCISOR)
+    r[0] = (threshold, guard, reserved)
+    return r
+
+
 def _tones(freqs=(), count=None, reserved=0, n=1):
     r = np.zeros(n, dtype=_lib.NOTCH_TONES)
     for row in r:
@@ -57,7 +64,9 @@ def _i64(values):
 class Env:
     """A context, a device buffer, and the handles the ingest rows need: `dev` (40 ms of int8 noise at 2.046 Msps on the context),
     `zeros` (the same length of zero words), `slow` (1200 ms at 1000 Hz: 1000 ms of it hold 1000 samples), `wide` (2 ms at
-    65.537 Msps: more samples per millisecond than the blanker takes) and `host` (opened without a context)."""
+    65.537 Msps: more samples per millisecond than the blanker takes), `host` (opened without a context), `chain` (as `dev`: the
+    handle whose stages gyp_ingest_next_host's rows switch on and off again), `resampled` (the same file read as 4.092 Msps) and
+    `packed` (the same file read as 2-bit I,Q words at the context's rate)."""
 
     def __init__(self, tmp: Path) -> None:
         self.eng = GypsumEngine(0)
@@ -75,6 +84,14 @@ class Env:
             words.tofile(tmp / f"{name}.i8")
             self.handles[name] = self._open(self.ctx, tmp / f"{name}.i8", fs, n, block_ms)
         self.handles["host"] = self._open(None, tmp / "dev.i8", FS, N, 5)
+        self.handles["chain"] = self._open(self.ctx, tmp / "dev.i8", FS, N, 5)
+        path, g = str(tmp / "dev.i8").encode(), C.c_void_p()
+        assert self.lib.gyp_ingest_open_resampled(self.ctx, path, _lib.GYP_FMT_I8, 2 * FS, 0, 5, 3, C.byref(g)) == 0 and g.value
+        self.handles["resampled"] = g
+        packing, g = np.zeros(1, dtype=_lib.PACKING), C.c_void_p()
+        packing[0]["bits"], packing[0]["order"] = 2, _lib.GYP_PACK_MSB_FIRST
+        assert self.lib.gyp_ingest_open_packed(self.ctx, path, _lib.ptr(packing), FS, 0, 0, 5, 3, C.byref(g)) == 0 and g.value
+        self.handles["packed"] = g
 
     def _open(self, ctx, path, fs, n, block_ms):
         g = C.c_void_p()
@@ -204,6 +221,39 @@ def refused_calls(env: Env):
     row("hist: centre inf", hist(centres=np.array([INF, 0.0], dtype=np.float32)))
     row("hist: second centre nan", hist(ns=2, centres=np.array([0.0, 0.0, 0.0, NAN], dtype=np.float32)))
 
+    # -------------------------------------------------------------------------------------------- gyp_excise_iq_dev
+    def excise(c=ctx, inp=p, out=p, ns=1, stride=N, n_ms=1, n=N, e=_excisor()):
+        return lambda: lib.gyp_excise_iq_dev(c, inp, out, ns, stride, n_ms, n, ptr(e), None, None)
+    row("excise: ctx NULL", excise(c=None), False)
+    row("excise: in NULL", excise(inp=None))
+    row("excise: out NULL", excise(out=None))
+    row("excise: excisors NULL", excise(e=None))
+    row("excise: n_streams 0", excise(ns=0))
+    row("excise: n_ms < 0", excise(n_ms=-1))
+    row("excise: samples_per_ms 0", excise(n=0))
+    row("excise: samples_per_ms 65537", excise(n=65537, stride=65537))
+    row("excise: stride", excise(ns=2, stride=N - 1, e=np.concatenate([_excisor(), _excisor()])))
+    row("excise: threshold 0", excise(e=_excisor(threshold=0.0)))
+    row("excise: threshold inf", excise(e=_excisor(threshold=INF)))
+    row("excise: threshold nan", excise(e=_excisor(threshold=NAN)))
+    row("excise: guard -1", excise(e=_excisor(guard=-1)))
+    row("excise: guard 9", excise(e=_excisor(guard=9)))
+    row("excise: reserved[0]", excise(e=_excisor(reserved=(1, 0))))
+    row("excise: reserved[1]", excise(e=_excisor(reserved=(0, 1))))
+    row("excise: second excisor bad", excise(ns=2, e=np.concatenate([_excisor(), _excisor(guard=9)])))
+
+    # -------------------------------------------------------------------------------------------- gyp_iq_spectrum_hist_dev
+    def spectrum(c=ctx, iq=p, ns=1, stride=N, n_ms=1, n=N, out=p):
+        return lambda: lib.gyp_iq_spectrum_hist_dev(c, iq, ns, stride, n_ms, n, out)
+    row("spectrum_hist: ctx NULL", spectrum(c=None), False)
+    row("spectrum_hist: iq NULL", spectrum(iq=None))
+    row("spectrum_hist: hist NULL", spectrum(out=None))
+    row("spectrum_hist: n_streams 0", spectrum(ns=0))
+    row("spectrum_hist: n_ms 0", spectrum(n_ms=0))
+    row("spectrum_hist: samples_per_ms 255", spectrum(n=255, stride=255))
+    row("spectrum_hist: samples_per_ms 65537", spectrum(n=65537, stride=65537))
+    row("spectrum_hist: stride", spectrum(ns=2, stride=N - 1))
+
     # -------------------------------------------------------------------------------------------- gyp_track_quality_dev
     def quality(c=ctx, recs=p, nc=1, stride=20, n_ms=20, window=20, offsets=None, out=p):
         return lambda: lib.gyp_track_quality_dev(c, recs, nc, stride, n_ms, window, ptr(offsets), out)
@@ -219,7 +269,7 @@ def refused_calls(env: Env):
 
     # -------------------------------------------------------------------------------------------- the ingest handle
     enabled, count = C.c_int32(), C.c_int32()
-    level_out, blanker_out = _level(), _blanker()
+    level_out, blanker_out, excisor_out = _level(), _blanker(), _excisor()
     freqs8, counts = np.zeros(8, dtype=np.int64), np.zeros(8, dtype=np.int32)
 
     def both(name, call):
@@ -289,6 +339,77 @@ def refused_calls(env: Env):
     row("last_blanked: n_ms_out NULL", lambda: lib.gyp_ingest_last_blanked(dev, ptr(counts), 8, None))
     row("last_blanked: cap < 0", lambda: lib.gyp_ingest_last_blanked(dev, ptr(counts), -1, C.byref(count)))
     row("last_blanked: cap without counts_out", lambda: lib.gyp_ingest_last_blanked(dev, None, 8, C.byref(count)))
+
+    both("set_excisor", lambda g: lib.gyp_ingest_set_excisor(g, ptr(_excisor())))
+    row("set_excisor: threshold 0", lambda: lib.gyp_ingest_set_excisor(dev, ptr(_excisor(threshold=0.0))))
+    row("set_excisor: threshold inf", lambda: lib.gyp_ingest_set_excisor(dev, ptr(_excisor(threshold=INF))))
+    row("set_excisor: guard 9", lambda: lib.gyp_ingest_set_excisor(dev, ptr(_excisor(guard=9))))
+    row("set_excisor: reserved", lambda: lib.gyp_ingest_set_excisor(dev, ptr(_excisor(reserved=(0, 1)))))
+    row("set_excisor: 65537 samples per ms", lambda: lib.gyp_ingest_set_excisor(wide, ptr(_excisor())))
+    both("get_excisor", lambda g: lib.gyp_ingest_get_excisor(g, ptr(excisor_out), C.byref(enabled)))
+
+    def find_excisor(g=dev, first=0, n_ms=5, threshold=16.0, guard=1):
+        return lambda: lib.gyp_ingest_find_excisor(g, first, n_ms, threshold, guard, 0, ptr(excisor_out), None)
+    both("find_excisor", lambda g: find_excisor(g=g)())
+    row("find_excisor: n_ms 0", find_excisor(n_ms=0))
+    row("find_excisor: n_ms 1001", find_excisor(n_ms=1001))
+    row("find_excisor: first < 0", find_excisor(first=-1))
+    row("find_excisor: past the end", find_excisor(first=36))
+    row("find_excisor: threshold 0", find_excisor(threshold=0.0))
+    row("find_excisor: threshold nan", find_excisor(threshold=NAN))
+    row("find_excisor: guard -1", find_excisor(guard=-1))
+    row("find_excisor: guard 9", find_excisor(guard=9))
+    row("find_excisor: 65537 samples per ms", find_excisor(g=wide, n_ms=1))
+    row("find_excisor: fewer than 256 samples per ms", find_excisor(g=slow))
+
+    both("last_excised", lambda g: lib.gyp_ingest_last_excised(g, ptr(counts), 8, C.byref(count)))
+    row("last_excised: n_ms_out NULL", lambda: lib.gyp_ingest_last_excised(dev, ptr(counts), 8, None))
+    row("last_excised: cap < 0", lambda: lib.gyp_ingest_last_excised(dev, ptr(counts), -1, C.byref(count)))
+    row("last_excised: cap without counts_out", lambda: lib.gyp_ingest_last_excised(dev, None, 8, C.byref(count)))
+
+    # gyp_ingest_next_host: a stage of `chain` is switched on for the row alone and off again behind it (a call that succeeds
+    # leaves the error text as it is)
+    chain, resampled, packed = (env.handles[k] for k in ("chain", "resampled", "packed"))
+    raw, first, n_ms = C.c_void_p(), C.c_int64(), C.c_int32()
+
+    def next_host(g=chain, raw_out=raw, first_out=first, n_out=n_ms):
+        byref = lambda x: C.byref(x) if x is not None else None   # noqa: E731
+        return lambda: lib.gyp_ingest_next_host(g, byref(raw_out), byref(first_out), byref(n_out))
+    stages = {"level": (lambda: lib.gyp_ingest_set_level(chain, ptr(_level(gain=2.0))), lambda: lib.gyp_ingest_set_level(chain, None)),
+              "notches": (lambda: lib.gyp_ingest_set_notches(chain, ptr(_i64([100_000])), 1), lambda: lib.gyp_ingest_set_notches(chain, None, 0)),
+              "blanker": (lambda: lib.gyp_ingest_set_blanker(chain, ptr(_blanker())), lambda: lib.gyp_ingest_set_blanker(chain, None)),
+              "excisor": (lambda: lib.gyp_ingest_set_excisor(chain, ptr(_excisor())), lambda: lib.gyp_ingest_set_excisor(chain, None))}
+
+    def with_stages(names, call=next_host()):
+        def run():
+            for k in names:
+                assert stages[k][0]() == 0
+            rc = call()
+            for k in names:
+                assert stages[k][1]() == 0
+            return rc
+        return run
+
+    def in_flight():
+        iq = C.c_void_p()
+        assert lib.gyp_ingest_next_dev(chain, C.byref(iq), C.byref(first), C.byref(n_ms)) == 0 and n_ms.value == 5
+        rc = next_host()()
+        assert lib.gyp_ingest_seek(chain, 0) == 0
+        return rc
+    row("next_host: handle NULL", next_host(g=None), False)
+    row("next_host: raw_out NULL", next_host(raw_out=None))
+    row("next_host: first_ms_out NULL", next_host(first_out=None))
+    row("next_host: n_ms_out NULL", next_host(n_out=None))
+    row("next_host: a resampled handle", next_host(g=resampled))
+    row("next_host: a packed handle", next_host(g=packed))
+    row("next_host: a level is on", with_stages(["level"]))
+    row("next_host: notches are on", with_stages(["notches"]))
+    row("next_host: a blanker is on", with_stages(["blanker"]))
+    row("next_host: an excisor is on", with_stages(["excisor"]))
+    row("next_host: excisor and blanker on", with_stages(["excisor", "blanker"]))
+    row("next_host: excisor, blanker and notches on", with_stages(["excisor", "blanker", "notches"]))
+    row("next_host: all four on", with_stages(["excisor", "blanker", "notches", "level"]))
+    row("next_host: device blocks in flight", in_flight)
     return rows
 
 
@@ -323,11 +444,12 @@ def test_every_refusal_keeps_its_code_and_its_text(env):
     for name, (code, text, before) in got.items():
         assert [code, text] == want[name], name
         assert code < 0 and text and text != before and text != NULL_SENTINEL, name      # refused, with a text of its own
-    # a refused call changes nothing: the handle has no level, notches or blanker, and serves its first block
+    # a refused call changes nothing: the handle has no level, notches, blanker or excisor, and serves its first block
     lib, dev = env.lib, env.handles["dev"]
     enabled, count = C.c_int32(-1), C.c_int32(-1)
     assert lib.gyp_ingest_get_level(dev, None, C.byref(enabled)) == 0 and enabled.value == 0
     assert lib.gyp_ingest_get_blanker(dev, None, C.byref(enabled)) == 0 and enabled.value == 0
+    assert lib.gyp_ingest_get_excisor(dev, None, C.byref(enabled)) == 0 and enabled.value == 0
     assert lib.gyp_ingest_get_notches(dev, None, C.byref(count)) == 0 and count.value == 0
     iq, first, n_ms = C.c_void_p(), C.c_int64(-1), C.c_int32(-1)
     assert lib.gyp_ingest_next_dev(dev, C.byref(iq), C.byref(first), C.byref(n_ms)) == 0 and (first.value, n_ms.value) == (0, 5)

@@ -900,7 +900,7 @@ def test_resample_plan(programs, tmp_path, which):
 # blank_launch, hist_launch, tones_launch, quality_launch, widen_launch, unpack_launch):
 # (stage, n_cus, wg_per_cu, n, a, b, stride, in_addr, out_addr, flag) -> {field: value}.  256 CUs x 2 workgroups: a cap of 512.
 def cond_literals():
-    from cond_plan_model import BLANK, CONDITION, HIST, NOTCH, QUALITY, STATS, TONES, UNPACK, WIDEN
+    from cond_plan_model import BLANK, CONDITION, EXCISE, HIST, NOTCH, QUALITY, SPECTRUM, STATS, TONES, UNPACK, WIDEN
     big = 2 ** 31 + 5
     return [
         ((STATS, 256, 2, 2, 300, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 512, "gy_first": 1, "items_first": 600, "ns_first": 2}),
@@ -929,6 +929,11 @@ def cond_literals():
         ((WIDEN, 256, 2, 0, 2 ** 32 + 7, 0, 0, 0, 0, 0), {"gx_first": 512}),
         ((UNPACK, 256, 2, 1, 40920, 2, 40920, 0, 4096, 0), {"items_first": 1279, "gx_first": 5, "vec4": 1}),
         ((UNPACK, 256, 2, 3, 40920, 2, 40921, 0, 4096, 0), {"items_first": 3837, "gx_first": 15, "vec4": 0}),
+        # excise_launch's chunks of 8 streams, one workgroup per (stream, millisecond); spectrum_hist_launch's one launch of them all
+        ((EXCISE, 256, 2, 11, 3, 0, 0, 0, 0, 0), {"n_chunks": 2, "gx_first": 24, "items_first": 24, "gx_last": 9, "items_last": 9, "s0_last": 8, "ns_last": 3}),
+        ((EXCISE, 256, 2, 1, 1000, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 512, "items_first": 1000}),
+        ((SPECTRUM, 256, 2, 11, 3, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 33, "items_first": 33, "ns_first": 11, "gy_first": 1}),
+        ((SPECTRUM, 256, 2, 17, 250, 0, 0, 0, 0, 0), {"n_chunks": 1, "gx_first": 512, "items_first": 4250, "ns_first": 17}),
     ]
 
 
@@ -947,6 +952,8 @@ def cond_sweep():
                 for ms in n_ms:
                     add(m.STATS, s, ms)
                     add(m.BLANK, s, ms)
+                    add(m.EXCISE, s, ms)
+                    add(m.SPECTRUM, s, ms)
                     for spm in n:
                         for no_lds in (0, 1):
                             add(m.NOTCH, s, ms, spm, flag=no_lds)
@@ -994,7 +1001,7 @@ def test_cond_plan(programs, tmp_path, which):
         assert len(bad) == 0, (field, len(bad), shapes[bad[0]].tolist(), int(got[bad[0], col]), int(want[bad[0], col]))
     plan = {f: got[:, c] for c, f in enumerate(m.FIELDS)}
     stage, n_cus, wg, count = shapes[:, 0], shapes[:, 1], shapes[:, 2], shapes[:, 3]
-    assert set(np.unique(stage)) == set(range(9))
+    assert set(np.unique(stage)) == set(range(11))
     loop = (stage != m.WIDEN) & (stage != m.UNPACK)                   # the stages that walk their streams in launches
     k = np.array([m.K.get(int(s), 0) for s in stage])
     k = np.where(k == 0, count, k)
@@ -1017,6 +1024,26 @@ def test_cond_plan(programs, tmp_path, which):
         p = dict(zip(m.FIELDS, row.tolist()))
         for field, value in expected.items():
             assert p[field] == value, (shape, field, p[field])
+
+
+# ------------------------------------------------------------------------------------------------------------ cond-chain
+@pytest.mark.parametrize("which", BOTH)
+def test_cond_chain(programs, tmp_path, which):
+    """Conditioning::upstream_of(s) (csrc/ingest.hpp) for the 16 combinations of stages on and off x the 4 stages: the stages in front
+    of s are as they were, s and the ones behind it are off, a stage that is switched off keeps its values, and the notch list,
+    which is its own switch, is cleared."""
+    import cond_plan_model as m
+
+    indir(tmp_path)
+    out = run(programs, which, "cond-chain", tmp_path)
+    rows = np.fromfile(out / "chain.i64", dtype="<i8").reshape(16 * 4, 2 + 2 * m.CHAIN_ROW)
+    assert rows[:, :2].tolist() == [[combo, s] for combo in range(16) for s in range(4)]
+    for combo, s, *both in rows.tolist():
+        before, after = both[:m.CHAIN_ROW], both[m.CHAIN_ROW:]
+        assert [int(before[i] != 0) for i in m.CHAIN_SWITCH] == [combo >> t & 1 for t in range(4)]      # the combination it says
+        assert after == m.upstream_of(before, s), (combo, s)
+        first = m.CHAIN_FIELDS[s][0]
+        assert after[:first] == before[:first] and not any(after[m.CHAIN_SWITCH[t]] for t in range(s, 4)), (combo, s)
 
 
 # ------------------------------------------------------------------------------------------------------------ dev-mem
