@@ -66,6 +66,15 @@ HYBRID_CELL = np.dtype([("peak", "<f4"), ("argmax", "<i4"), ("second", "<f4"), (
 WEAK_RESULT = np.dtype([("stream", "<i4"), ("sat_id", "<i4"), ("doppler_hz", "<f8"), ("code_phase", "<i4"), ("reserved0", "<i4"),
                         ("carrier_phase", "<f8"), ("z", "<f8"), ("peak_ratio", "<f8"), ("set", "<i4"), ("reserved", "<i4")], align=True)
 GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER = 1, 2
+WEAK_PARAMS = np.dtype([("period_ms", "<i4"), ("sync_ms", "<i4"), ("spacing", "<i8"), ("pll_bw_hz", "<f8"), ("dll_bw_hz", "<f8"),
+                        ("lose_mu", "<f8"), ("reserved", "<f8")], align=True)
+WEAK_MS_REC = np.dtype([("minus_re", "<f4"), ("minus_im", "<f4"), ("prompt_re", "<f4"), ("prompt_im", "<f4"), ("plus_re", "<f4"),
+                        ("plus_im", "<f4"), ("pos", "<i2"), ("phase", "i1"), ("status", "i1"), ("reserved", "<i4")], align=True)
+WEAK_PERIOD_REC = np.dtype([("first_ms", "<i8"), ("f", "<f8"), ("u0", "<f8"), ("c0", "<i8"), ("i", "<f8"), ("q", "<f8"), ("mu", "<f8"),
+                            ("dphi", "<f8"), ("dd", "<f8"), ("bit", "<i4"), ("status", "<i4"), ("mu_mean", "<f8")], align=True)
+WEAK_STATE = np.dtype([("f", "<f8"), ("f_int", "<f8"), ("u0", "<f8"), ("c0", "<i8"), ("phase", "<i4"), ("edge", "<i4"), ("status", "<i4"),
+                       ("pos", "<i4"), ("n_periods", "<i4"), ("reserved", "<i4"), ("mu_mean", "<f8")], align=True)
+GYP_WEAK_SYNC, GYP_WEAK_WAIT, GYP_WEAK_TRACK = 0, 1, 2
 GYP_POWER_HIST_BINS = 2048
 GYP_EXCISE_FRAME = 256
 GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
@@ -81,7 +90,9 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_iq_stats": IQ_STATS.itemsize, "gyp_iq_level": IQ_LEVEL.itemsize,
                 "gyp_tone_rec": TONE_REC.itemsize, "gyp_notch_tones": NOTCH_TONES.itemsize,
                 "gyp_quality_sums": QUALITY_SUMS.itemsize, "gyp_quality": QUALITY.itemsize, "gyp_blanker": BLANKER.itemsize,
-                "gyp_excisor": EXCISOR.itemsize, "gyp_hybrid_cell": HYBRID_CELL.itemsize, "gyp_weak_result": WEAK_RESULT.itemsize}
+                "gyp_excisor": EXCISOR.itemsize, "gyp_hybrid_cell": HYBRID_CELL.itemsize, "gyp_weak_result": WEAK_RESULT.itemsize,
+                "gyp_weak_params": WEAK_PARAMS.itemsize, "gyp_weak_ms_rec": WEAK_MS_REC.itemsize,
+                "gyp_weak_period_rec": WEAK_PERIOD_REC.itemsize, "gyp_weak_state": WEAK_STATE.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -104,7 +115,9 @@ EXPORTS = (
     "gyp_ingest_last_blanked "
     "gyp_excise_iq_dev gyp_iq_spectrum_hist_dev gyp_excise_from_hist gyp_ingest_set_excisor gyp_ingest_get_excisor gyp_ingest_find_excisor "
     "gyp_ingest_last_excised "
-    "gyp_hybrid_stats gyp_hybrid_shift gyp_correlate_grid_hybrid_dev gyp_correlate_grid_hybrid gyp_acquire_weak_dev gyp_acquire_weak"
+    "gyp_hybrid_stats gyp_hybrid_shift gyp_correlate_grid_hybrid_dev gyp_correlate_grid_hybrid gyp_acquire_weak_dev gyp_acquire_weak "
+    "gyp_weak_params_default gyp_weak_bit_sync gyp_weak_bank_create gyp_weak_bank_destroy gyp_weak_bank_size gyp_weak_bank_set_channel "
+    "gyp_weak_bank_drop_channel gyp_weak_bank_get_state gyp_weak_bank_set_state gyp_weak_track_block_dev gyp_weak_track_block"
 ).split()
 
 
@@ -262,6 +275,17 @@ def load() -> C.CDLL:
         "gyp_correlate_grid_hybrid": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
         "gyp_acquire_weak_dev": (C.c_int, [vp, vp, i32, i64, i32, i32, i32, dbl, dbl, dbl, vp, i32, vp]),
         "gyp_acquire_weak": (C.c_int, [vp, vp, i32, i32, i32, i32, dbl, dbl, dbl, vp, i32, vp]),
+        "gyp_weak_params_default": (None, [vp]),
+        "gyp_weak_bit_sync": (C.c_int, [vp, i32, i64, vp, vp]),
+        "gyp_weak_bank_create": (C.c_int, [vp, vp, i32, vp, i64, C.POINTER(vp)]),
+        "gyp_weak_bank_destroy": (None, [vp]),
+        "gyp_weak_bank_size": (C.c_int, [vp]),
+        "gyp_weak_bank_set_channel": (C.c_int, [vp, i32, vp]),
+        "gyp_weak_bank_drop_channel": (C.c_int, [vp, i32]),
+        "gyp_weak_bank_get_state": (C.c_int, [vp, vp, C.POINTER(i64)]),
+        "gyp_weak_bank_set_state": (C.c_int, [vp, i32, vp]),
+        "gyp_weak_track_block_dev": (C.c_int, [vp, vp, i64, i64, i32, vp, vp, vp]),
+        "gyp_weak_track_block": (C.c_int, [vp, vp, i32, i64, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

@@ -54,3 +54,17 @@ def one_hist(hist) -> np.ndarray:
     if len(h) != _lib.GYP_POWER_HIST_BINS:
         raise ValueError(f"a histogram has {_lib.GYP_POWER_HIST_BINS} bins")
     return h
+
+
+@dataclasses.dataclass
+class WeakParams(Record):
+    """gyp_weak_params, with the library's defaults (gyp_weak_params_default): the 20-ms period, the correlator spacing in 2^-40
+    chips, the open-loop span before the bit edge is picked, the loop bandwidths and the NBP / WBP mean below which a channel is lost."""
+    DTYPE = _lib.WEAK_PARAMS
+    period_ms: int = 20
+    sync_ms: int = 400
+    spacing: int = 1 << 39
+    pll_bw_hz: float = 8.0
+    dll_bw_hz: float = 1.0
+    lose_mu: float = 2.5
+    reserved: float = 0.0

@@ -121,9 +121,11 @@ static thread_local std::string g_create_error;
 // Device buffers of the entry points on a context, one per role.  Each is reserved (Slack::grow) and used within one call, on the
 // context's stream; nothing is kept in them between calls.  A helper context (gyp_acquire_dev) has a set of its own.
 // Staging of the host-buffer entry points; only the wrappers that take host pointers use these, never a *_dev function:
-//   stage_iq       samples: gyp_correlate_cells, gyp_correlate_grid, gyp_search_level, gyp_acquire, gyp_track_step, gyp_track_block
+//   stage_iq       samples: gyp_correlate_cells, gyp_correlate_grid, gyp_search_level, gyp_acquire, gyp_track_step, gyp_track_block, gyp_weak_track_block
 //   stage_in       descriptors: gyp_correlate_cells (gyp_cell_desc), gyp_track_step (gyp_chan_in)
 //   stage_out      results: gyp_correlate_cells, gyp_correlate_grid (gyp_cell), gyp_search_level, gyp_acquire (gyp_acq_result), gyp_track_step (gyp_chan_out), gyp_track_block (gyp_track_rec)
+//   weak_stage     results: gyp_weak_track_block (the call's millisecond records, period records and period counts, back to back; its
+//                  samples go through stage_iq like every host form's)
 //   stage_profile  optional profile rows: gyp_correlate_cells, gyp_track_step
 //   stage_times    start times: gyp_track_step (per stream), gyp_track_block (per millisecond)
 //   quality_recs, quality_sums   tracking records in, sums out: gyp_track_quality (roles of its own: its input is the kind of record
@@ -155,7 +157,7 @@ struct Scratch {
     DevBuf<float> hyb_power;
     DevBuf<gyp_hybrid_cell> hyb_records;
     DevBuf<float> stage_iq, stage_profile, bench_sink;
-    DevBuf<uint8_t> stage_in, stage_out, refine_list, acq_book, acq_units;
+    DevBuf<uint8_t> stage_in, stage_out, weak_stage, refine_list, acq_book, acq_units;
     DevBuf<double> stage_times, doppler, partial64, acq_refined, acq_profiles;
     DevBuf<int32_t> sat_ids;
     DevBuf<cf> folded, z, acq_spectra;
@@ -1921,6 +1923,201 @@ int gyp_track_block(gyp_bank* bank, const float* iq_host, int32_t n_streams, int
                                            rec_out_host ? (gyp_track_rec*)sc.stage_out.get() : nullptr))
         return rc;
     return stage_back(ctx, rec_out_host, rec_bytes);
+}
+
+// ---------------------------------------------------------------- weak-signal tracking ---------------------
+}   // extern "C"
+// A weak bank: the channels' states and the SYNC prompt rows, device resident; the cursor and the parameters on the host.
+struct gyp_weak_bank {
+    gyp_ctx* ctx = nullptr;
+    int n_chan = 0;
+    int64_t fs = 0;              // the stream format the bank was created under
+    int n = 0;
+    int64_t cursor = 0;          // absolute index of the next millisecond
+    gyp_weak_params prm{};
+    std::vector<int32_t> stream_of;
+    DevBuf<WeakChan> states;         // [n_chan]
+    DevBuf<float2> sync_prompts;     // [n_chan][sync_ms]
+};
+static int weak_put_state(gyp_weak_bank* bank, int32_t index, const WeakChan& s) {
+    gyp_ctx* ctx = bank->ctx;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(bank->states.get() + index, &s, sizeof(WeakChan), hipMemcpyHostToDevice));
+    bank->stream_of[index] = s.stream;
+    return GYP_OK;
+}
+static int weak_get_chan(gyp_weak_bank* bank, int32_t index, WeakChan* s) {
+    gyp_ctx* ctx = bank->ctx;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(s, bank->states.get() + index, sizeof(WeakChan), hipMemcpyDeviceToHost));
+    return GYP_OK;
+}
+// What both forms of gyp_weak_track_block refuse, before anything runs.
+static int weak_track_check(gyp_weak_bank* bank, const char* who, const void* iq, int64_t first_ms, int32_t n_ms) {
+    gyp_ctx* ctx = bank->ctx;
+    if (!iq) return refuse(ctx, who, "bad argument");
+    if (n_ms < 1 || n_ms > kWeakMaxMs) return refuse(ctx, who, "n_ms must be 1..65535");
+    if (ctx->fs != bank->fs || ctx->n != bank->n) return refuse(ctx, who, "the context's stream format is not the one the bank was created under");
+    if (first_ms != bank->cursor)
+        return refuse(ctx, who, "first_ms " + std::to_string(first_ms) + " is not the bank's cursor " + std::to_string(bank->cursor));
+    return GYP_OK;
+}
+extern "C" {
+
+void gyp_weak_params_default(gyp_weak_params* out) {
+    if (out) *out = weak_params_default();
+}
+
+int gyp_weak_bit_sync(const float* prompts, int32_t n_ms, int64_t first_ms, double* energies_out20, int32_t* offset_out) {
+    if (!prompts || n_ms < kWeakPeriodMs || first_ms < 0) return fail(nullptr, GYP_E_BAD_ARG, "gyp_weak_bit_sync: bad argument");
+    double en[kWeakPeriodMs];
+    for (int o = 0; o < kWeakPeriodMs; ++o) en[o] = weak_bit_energy(prompts, n_ms, first_ms, o);
+    if (energies_out20) std::memcpy(energies_out20, en, sizeof(en));
+    if (offset_out) *offset_out = weak_bit_pick(en);
+    return GYP_OK;
+}
+
+int gyp_weak_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_chan, const gyp_weak_params* params, int64_t first_ms,
+                         gyp_weak_bank** out) {
+    static const char* const who = "gyp_weak_bank_create";
+    if (!ctx || !out) return GYP_E_BAD_ARG;
+    *out = nullptr;
+    if (const int rc = need_format(ctx)) return rc;
+    if (!chans_host || n_chan < 1 || first_ms < 0) return refuse(ctx, who, "bad argument");
+    const gyp_weak_params prm = params ? *params : weak_params_default();
+    if (const char* why = weak_params_refusal(prm)) return refuse(ctx, who, why);
+    std::vector<WeakChan> init((size_t)n_chan);
+    for (int i = 0; i < n_chan; ++i) {
+        if (const char* why = weak_init_refusal(chans_host[i])) return refuse(ctx, who, why);
+        init[i] = weak_fresh_chan(chans_host[i], ctx->n, first_ms);
+    }
+    gyp_weak_bank* b = new gyp_weak_bank();
+    b->ctx = ctx; b->n_chan = n_chan; b->fs = ctx->fs; b->n = ctx->n; b->cursor = first_ms; b->prm = prm;
+    for (int i = 0; i < n_chan; ++i) b->stream_of.push_back(chans_host[i].stream);
+    hipError_t e = b->states.reserve(init.size(), Slack::exact);
+    if (e == hipSuccess) e = b->sync_prompts.reserve(init.size() * (size_t)prm.sync_ms, Slack::exact);
+    if (e == hipSuccess) e = hipMemcpy(b->states.get(), init.data(), init.size() * sizeof(WeakChan), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete b;
+        return fail(ctx, GYP_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    *out = b;
+    return GYP_OK;
+}
+
+void gyp_weak_bank_destroy(gyp_weak_bank* bank) {
+    if (!bank) return;
+    (void)hipStreamSynchronize(bank->ctx->stream);
+    delete bank;
+}
+
+int gyp_weak_bank_size(const gyp_weak_bank* bank) { return bank ? bank->n_chan : GYP_E_BAD_ARG; }
+
+int gyp_weak_bank_set_channel(gyp_weak_bank* bank, int32_t index, const gyp_chan_init* in) {
+    static const char* const who = "gyp_weak_bank_set_channel";
+    if (!bank) return GYP_E_BAD_ARG;
+    if (!in || index < 0 || index >= bank->n_chan) return refuse(bank->ctx, who, "bad argument");
+    if (const char* why = weak_init_refusal(*in)) return refuse(bank->ctx, who, why);
+    return weak_put_state(bank, index, weak_fresh_chan(*in, bank->n, bank->cursor));
+}
+
+int gyp_weak_bank_drop_channel(gyp_weak_bank* bank, int32_t index) {
+    if (!bank) return GYP_E_BAD_ARG;
+    if (index < 0 || index >= bank->n_chan) return refuse(bank->ctx, "gyp_weak_bank_drop_channel", "index out of range");
+    WeakChan s;
+    if (const int rc = weak_get_chan(bank, index, &s)) return rc;
+    s.status = 2;
+    return weak_put_state(bank, index, s);
+}
+
+int gyp_weak_bank_get_state(gyp_weak_bank* bank, gyp_weak_state* out_host, int64_t* cursor_out) {
+    if (!bank) return GYP_E_BAD_ARG;
+    gyp_ctx* ctx = bank->ctx;
+    if (cursor_out) *cursor_out = bank->cursor;
+    if (!out_host) return GYP_OK;
+    std::vector<WeakChan> s((size_t)bank->n_chan);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(s.data(), bank->states.get(), s.size() * sizeof(WeakChan), hipMemcpyDeviceToHost));
+    for (int i = 0; i < bank->n_chan; ++i) {
+        gyp_weak_state o{};
+        o.f = s[i].f; o.f_int = s[i].f_int; o.u0 = s[i].u0; o.c0 = s[i].c0;
+        o.phase = s[i].phase; o.edge = s[i].edge; o.status = s[i].status; o.pos = s[i].pos; o.n_periods = s[i].n_periods;
+        o.mu_mean = s[i].mu_mean;
+        out_host[i] = o;
+    }
+    return GYP_OK;
+}
+
+int gyp_weak_bank_set_state(gyp_weak_bank* bank, int32_t index, const gyp_weak_state* in) {
+    static const char* const who = "gyp_weak_bank_set_state";
+    if (!bank) return GYP_E_BAD_ARG;
+    gyp_ctx* ctx = bank->ctx;
+    if (!in || index < 0 || index >= bank->n_chan) return refuse(ctx, who, "bad argument");
+    if (!std::isfinite(in->f) || !std::isfinite(in->f_int) || !(in->u0 >= 0.0 && in->u0 < 1.0) || in->c0 < 0 || in->c0 >= kWeakCodeMod ||
+        in->edge < 0 || in->edge >= kWeakPeriodMs)
+        return refuse(ctx, who, "state out of range");
+    WeakChan s;
+    if (const int rc = weak_get_chan(bank, index, &s)) return rc;
+    WeakChan t{};
+    t.stream = s.stream; t.sat_id = s.sat_id;
+    t.phase = kWeakWait; t.edge = in->edge; t.sync_start = bank->cursor;
+    t.f = in->f; t.f_int = in->f_int; t.u0 = in->u0; t.c0 = in->c0;
+    return weak_put_state(bank, index, t);
+}
+
+int gyp_weak_track_block_dev(gyp_weak_bank* bank, const float* iq_dev, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                             gyp_weak_ms_rec* ms_out_dev, gyp_weak_period_rec* period_out_dev, int32_t* n_periods_out_dev) {
+    static const char* const who = "gyp_weak_track_block_dev";
+    if (!bank) return GYP_E_BAD_ARG;
+    gyp_ctx* ctx = bank->ctx;
+    if (const int rc = weak_track_check(bank, who, iq_dev, first_ms, n_ms)) return rc;
+    if (stream_stride_samples < (int64_t)n_ms * bank->n) return refuse(ctx, who, "the stream stride is below n_ms * N");
+    WeakTrackParams p{};
+    p.states = bank->states.get(); p.sync_prompts = bank->sync_prompts.get();
+    p.iq = iq_dev; p.stream_stride = stream_stride_samples; p.chips = ctx->codes.chips.get();
+    p.ms_out = ms_out_dev; p.period_out = period_out_dev; p.n_periods_out = n_periods_out_dev;
+    p.prm = bank->prm; p.fs = (double)bank->fs; p.first_ms = first_ms;
+    p.n = bank->n; p.n_ms = n_ms; p.n_chan = bank->n_chan;
+    hipLaunchKernelGGL(weak_track_kernel, dim3((unsigned)bank->n_chan), dim3(kWeakThreads), 0, ctx->stream, p);
+    if (const int rc = launched(ctx)) return rc;
+    bank->cursor += n_ms;
+    return GYP_OK;
+}
+
+int gyp_weak_track_block(gyp_weak_bank* bank, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                         gyp_weak_ms_rec* ms_out_host, gyp_weak_period_rec* period_out_host, int32_t* n_periods_out_host) {
+    static const char* const who = "gyp_weak_track_block";
+    if (!bank) return GYP_E_BAD_ARG;
+    gyp_ctx* ctx = bank->ctx;
+    if (n_streams < 1) return refuse(ctx, who, "bad argument");
+    if (const int rc = weak_track_check(bank, who, iq_host, first_ms, n_ms)) return rc;
+    for (int c = 0; c < bank->n_chan; ++c)
+        if (bank->stream_of[c] >= n_streams)
+            return refuse(ctx, who, "channel " + std::to_string(c) + " reads stream " + std::to_string(bank->stream_of[c]) + " but only " +
+                                        std::to_string(n_streams) + " were passed");
+    Scratch& sc = ctx->scratch;
+    const size_t nc = (size_t)bank->n_chan, max_periods = (size_t)n_ms / kWeakPeriodMs + 1;
+    const size_t ms_bytes = nc * n_ms * sizeof(gyp_weak_ms_rec), per_bytes = nc * max_periods * sizeof(gyp_weak_period_rec), cnt_bytes = nc * sizeof(int32_t);
+    HIP_TRY(ctx, sc.weak_stage.reserve(ms_bytes + per_bytes + cnt_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    uint8_t* const base = sc.weak_stage.get();
+    if (const int rc = gyp_weak_track_block_dev(bank, sc.stage_iq.get(), (int64_t)n_ms * ctx->n, first_ms, n_ms, (gyp_weak_ms_rec*)base,
+                                                (gyp_weak_period_rec*)(base + ms_bytes), (int32_t*)(base + ms_bytes + per_bytes)))
+        return rc;
+    if (ms_out_host) HIP_TRY(ctx, hipMemcpyAsync(ms_out_host, base, ms_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    // the period rows and their counts in one copy; only the records written go on to the caller (the rest of each row stays as it was)
+    std::vector<uint8_t> staged(period_out_host || n_periods_out_host ? per_bytes + cnt_bytes : 0);
+    if (!staged.empty()) HIP_TRY(ctx, hipMemcpyAsync(staged.data(), base + ms_bytes, staged.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (staged.empty()) return GYP_OK;
+    const int32_t* const cnt = reinterpret_cast<const int32_t*>(staged.data() + per_bytes);
+    if (n_periods_out_host) std::memcpy(n_periods_out_host, cnt, cnt_bytes);
+    if (period_out_host)
+        for (size_t c = 0; c < nc; ++c)
+            if (cnt[c] > 0)
+                std::memcpy(period_out_host + c * max_periods, staged.data() + c * max_periods * sizeof(gyp_weak_period_rec),
+                            (size_t)cnt[c] * sizeof(gyp_weak_period_rec));
+    return GYP_OK;
 }
 
 // ---------------------------------------------------------------- multi-GPU: one all-gather over RCCL ------

@@ -39,6 +39,9 @@
 //                       added at the code-Doppler-aligned lag into the row of the block's set, and per cell the arg-max, the second
 //                       peak and the off-peak float64 moments of each set in a fixed order, the set with the larger z reported; the
 //                       hybrid_*_cells / select / finish kernels are gyp_acquire_weak_dev's two-level bookkeeping.
+//   weak_track_kernel   weak-signal tracking: one workgroup per channel of a weak bank; three code lags per sample against NCO replicas,
+//                       a wavefront per millisecond in a fixed reduction order, bit synchronisation and the 20-ms PLL / DLL update
+//                       in float64 on one lane between the periods (weak_plan.hpp holds that arithmetic for host and device).
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -60,3 +63,4 @@
 #include "kernels_excise.hpp"
 #include "kernels_quality.hpp"
 #include "kernels_hybrid.hpp"
+#include "kernels_weak.hpp"

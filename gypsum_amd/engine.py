@@ -738,6 +738,109 @@ class GypsumEngine:
     def create_bank(self, inits: np.ndarray) -> "ChannelBank":
         return ChannelBank(self, inits)
 
+    def create_weak_bank(self, inits: np.ndarray, params=None, first_ms: int = 0) -> "WeakChannelBank":
+        """A weak bank (gyp_weak_bank_*): CHAN_INIT records (or WEAK_RESULT fields copied into them), a _records.WeakParams or a
+        WEAK_PARAMS record (None: the defaults), the absolute index of the first millisecond it will be given."""
+        return WeakChannelBank(self, inits, params, first_ms)
+
+
+def weak_params_default() -> np.ndarray:
+    """gyp_weak_params_default (host only, no GPU): one WEAK_PARAMS record."""
+    rec = np.zeros(1, dtype=_lib.WEAK_PARAMS)
+    _lib.load().gyp_weak_params_default(ptr(rec))
+    return rec
+
+
+def weak_bit_sync(prompts: np.ndarray, first_ms: int) -> Tuple[np.ndarray, int]:
+    """gyp_weak_bit_sync (host only, no GPU): (energies float64[20], edge offset) of the complex64 prompts of milliseconds
+    first_ms, first_ms + 1, ..."""
+    lib = _lib.load()
+    p = np.ascontiguousarray(prompts, dtype=np.complex64).reshape(-1)
+    en = np.zeros(20, dtype=np.float64)
+    off = np.zeros(1, dtype=np.int32)
+    rc = lib.gyp_weak_bit_sync(ptr(p) if p.size else None, p.size, int(first_ms), ptr(en), ptr(off))
+    if rc != 0:
+        raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
+    return en, int(off[0])
+
+
+class WeakChannelBank:
+    """Device-resident weak-signal channels (gyp_weak_bank_*): 20-ms coherent loops behind an on-device bit synchronisation."""
+
+    def __init__(self, engine: "GypsumEngine", inits: np.ndarray, params=None, first_ms: int = 0) -> None:
+        self.engine = engine
+        self.handle = None             # (a refused create raises below: close() must find the attribute)
+        inits = np.ascontiguousarray(inits, dtype=CHAN_INIT).reshape(-1)
+        if params is not None and not isinstance(params, np.ndarray):
+            params = params.record()
+        prm = None if params is None else np.ascontiguousarray(params, dtype=_lib.WEAK_PARAMS).reshape(-1)
+        h = C.c_void_p()
+        engine._check(engine.lib.gyp_weak_bank_create(engine.ctx, ptr(inits) if inits.size else None, len(inits), ptr(prm), int(first_ms), C.byref(h)))
+        self.handle = h
+        self.n_chan = len(inits)
+
+    def close(self) -> None:
+        if self.handle:
+            self.engine.lib.gyp_weak_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def max_periods(n_ms: int) -> int:
+        return n_ms // 20 + 1
+
+    def track_block(self, iq: np.ndarray, n_streams: int, first_ms: int, n_ms: int, want_ms: bool = True,
+                    want_periods: bool = True) -> Tuple[Optional[np.ndarray], Optional[list]]:
+        """Advance n_ms milliseconds from the cursor (first_ms must be it).  (WEAK_MS_REC[n_chan, n_ms] or None, a list with each
+        channel's completed WEAK_PERIOD_REC records or None)."""
+        e = self.engine
+        iq = _as_iq(iq).reshape(-1)
+        if n_ms >= 1 and iq.size != n_streams * n_ms * e.n:
+            raise ValueError(f"expected {n_streams}*{n_ms}*{e.n} samples, got {iq.size}")
+        ms = np.zeros((self.n_chan, max(n_ms, 0)), dtype=_lib.WEAK_MS_REC) if want_ms else None
+        per = np.zeros((self.n_chan, self.max_periods(max(n_ms, 0))), dtype=_lib.WEAK_PERIOD_REC) if want_periods else None
+        cnt = np.zeros(self.n_chan, dtype=np.int32)
+        e._check(e.lib.gyp_weak_track_block(self.handle, ptr(iq) if iq.size else None, int(n_streams), int(first_ms), int(n_ms), ptr(ms), ptr(per), ptr(cnt)))
+        return ms, ([per[c, :cnt[c]].copy() for c in range(self.n_chan)] if want_periods else None)
+
+    def track_block_dev(self, iq_ptr: int, stream_stride: int, first_ms: int, n_ms: int, ms_ptr: int = 0, period_ptr: int = 0,
+                        n_periods_ptr: int = 0) -> None:
+        """Device-pointer form: only enqueues on the engine's stream."""
+        e = self.engine
+        e._check(e.lib.gyp_weak_track_block_dev(self.handle, C.c_void_p(iq_ptr or None), int(stream_stride), int(first_ms), int(n_ms),
+                                                C.c_void_p(ms_ptr or None), C.c_void_p(period_ptr or None), C.c_void_p(n_periods_ptr or None)))
+
+    def set_channel(self, index: int, init) -> None:
+        """(Re)start one slot in SYNC at the cursor from an acquisition result."""
+        one = np.zeros(1, dtype=CHAN_INIT)
+        one[0] = init
+        self.engine._check(self.engine.lib.gyp_weak_bank_set_channel(self.handle, int(index), ptr(one)))
+
+    def drop_channel(self, index: int) -> None:
+        self.engine._check(self.engine.lib.gyp_weak_bank_drop_channel(self.handle, int(index)))
+
+    def set_state(self, index: int, f: float, f_int: float, u0: float, c0: int, edge: int) -> None:
+        """Put one channel's full loop state; it tracks from the first millisecond m >= cursor with m % 20 == edge."""
+        st = np.zeros(1, dtype=_lib.WEAK_STATE)
+        st["f"], st["f_int"], st["u0"], st["c0"], st["edge"] = f, f_int, u0, c0, edge
+        self.engine._check(self.engine.lib.gyp_weak_bank_set_state(self.handle, int(index), ptr(st)))
+
+    def state(self) -> np.ndarray:
+        out = np.zeros(self.n_chan, dtype=_lib.WEAK_STATE)
+        self.engine._check(self.engine.lib.gyp_weak_bank_get_state(self.handle, ptr(out), None))
+        return out
+
+    @property
+    def cursor(self) -> int:
+        cur = C.c_int64()
+        self.engine._check(self.engine.lib.gyp_weak_bank_get_state(self.handle, None, C.byref(cur)))
+        return int(cur.value)
+
 
 class ChannelBank:
     """Device-resident tracking channels (gyp_bank_*)."""

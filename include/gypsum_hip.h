@@ -29,6 +29,10 @@ extern "C" {
 #endif
 
 /* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
+ *      tracking, a second kind of channel bank with 20-ms coherent loops and bit synchronisation on the device: gyp_weak_bank,
+ *      gyp_weak_params(_default), gyp_weak_ms_rec, gyp_weak_period_rec, gyp_weak_state, gyp_weak_bit_sync, gyp_weak_bank_create / _destroy /
+ *      _size / _set_channel / _drop_channel / _get_state / _set_state, gyp_weak_track_block(_dev).  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
  *      acquisition, a hybrid coherent/non-coherent search on the device: gyp_hybrid_cell, gyp_weak_result, GYP_HYB_ALTERNATE,
  *      GYP_HYB_CODE_DOPPLER, gyp_hybrid_stats, gyp_hybrid_shift, gyp_correlate_grid_hybrid(_dev), gyp_acquire_weak(_dev); gyp_debug_set
  *      name hybrid_scratch_mb and the read-only "last_hybrid_chunks".  Opt-in.
@@ -482,6 +486,128 @@ int gyp_bank_reset_dev(gyp_bank* bank, const gyp_chan_init* inits_dev);
 /* Read back the live estimates (GpsSatelliteTrackingParameters.current_*): n_chan entries each. */
 int gyp_bank_get_state(gyp_bank* bank, double* doppler_hz, double* carrier_phase, int32_t* code_phase,
                        int32_t* lost);
+
+/* ---------------------------------------------------------------- weak-signal tracking ------------------ */
+/* A second kind of channel bank, for what gyp_acquire_weak finds: gyp_bank is the reference's 1-ms loop (arg-max of a prompt
+ * profile, a sign-driven Costas loop), and a 1-ms prompt at 30 dB-Hz has 0 dB SNR.  A weak bank correlates three code lags per
+ * sample against NCO-driven replicas, finds the data-bit edge itself and then closes its loops once per 20-ms bit.  No FFT.
+ *
+ * State of a channel, with fs the sample rate, N samples per millisecond, K = N / 1023, all float64 unless said:
+ *   u0     carrier phase in cycles, [0, 1), at the first sample of the current period; f the loop frequency (Hz), f_int its
+ *          integrator.  Sample k of the period (0 <= k < P N for a period of P milliseconds, k running across its milliseconds) is
+ *          multiplied by exp(-2 pi i (u0 + (f / fs) k)): one quotient, one product, one sum, each rounded once, then the library's
+ *          float32 sine/cosine of the reduced phase.  At the period's end u0 <- frac(u0 + (f / fs) (P N)), frac(x) = x - floor(x).
+ *   c0     code phase, int64 in units of 2^-40 chip, [0, 1023 2^40), at the CENTRE of the period's first sample.  The rate per sample
+ *          is r = llround((1023 / N) (1 + f / 1575.42e6) 2^40) (carrier aiding, from the period's f; products left to right).  The
+ *          chip of sample k at lag offset o is ((c0 + o + k r) >> 40) mod 1023, an arithmetic shift and a non-negative remainder, in
+ *          exact int64 (below 2^61 at 49.104 Msps).  At the period's end c0 <- (c0 + P N r) mod (1023 2^40).
+ *   start  from a gyp_chan_init (or, field for field, a gyp_weak_result): f = f_int = doppler_hz; u0 = frac(carrier_phase / (2 pi)), and 0
+ *          where that rounds to 1 (a carrier phase a hair below zero);
+ *          c0 = llround((0.5 - code_phase) / K 2^40) mod (1023 2^40) -- the half sample is the sample-centre convention: code_phase
+ *          is the sample at which chip 0 begins, and sample 0's centre lies half a sample past its start.
+ * Correlators.  Each millisecond yields three complex float32 sums minus, prompt, plus at o = -d, 0, +d (d = gyp_weak_params::spacing,
+ * 2^-40 chips).  A millisecond's sums are a pure function of its N samples, the period-start state and its position in the period:
+ * one 64-lane wavefront takes the millisecond; lane l adds, in increasing i, the products of samples i = l, l + 64, ... (sample times
+ * carrier in float32: re = fma(x.re, c.re, -(x.im c.im)), im = fma(x.re, c.im, x.im c.re); then +- that value by the chip), widened, into float64
+ * accumulators; the lanes are reduced in float64 by the fixed tree in which lane l takes lane l + 32, 16, 8, 4, 2, 1, and each of the
+ * six sums is rounded to float32 once.  No atomics.
+ *
+ * Phases (gyp_weak_state::phase), m being the absolute millisecond index:
+ *   0 SYNC   the first sync_ms milliseconds from the millisecond the channel was (re)started at.  Open loop: every millisecond is a
+ *            period of its own (P = 1), f fixed.  The float32 prompts are kept in the bank; with the last one in, the device picks
+ *            the bit edge (gyp_weak_bit_sync over the SYNC span) -- no host round trip.
+ *   1 WAIT   open loop as in SYNC, until the first millisecond m at or after the end of SYNC with m mod 20 == edge.
+ *   2 TRACK  periods of P = 20 milliseconds.  At the end of a period, with minus_j, prompt_j, plus_j its float32 sums widened:
+ *            I + iQ, S-, S+ the float64 sums, in order j = 0..19, of prompt, minus, plus; E- = |S-|, E+ = |S+|; wbp the sum in order
+ *            of |prompt_j|^2; bit = I >= 0 ? +1 : -1; mu = (I^2 + Q^2) / wbp (0 if wbp is 0): the NBP / WBP ratio of the "signal
+ *            quality" section;
+ *            PLL  T = 0.02, wn = pll_bw_hz / 0.53, kp = 1.414 wn, ki = wn^2: dphi = atan(Q / I) (0 when I is 0);
+ *                 f_int += ki dphi T / (2 pi); f = f_int + kp dphi / (2 pi);
+ *            DLL  dd = 0.5 (E+ - E-) / (E+ + E-) (0 when the sum is 0); after the period's advance of c0,
+ *                 c0 <- (c0 + llround(4 dll_bw_hz dd T 2^40)) mod (1023 2^40) (a replica running late makes plus larger).
+ *   LOST     once 25 periods are complete and the mean of the last 25 mu (summed oldest first, / 25) is below lose_mu the channel
+ *            is lost: that period's record has status 1, every later millisecond of the channel a status-2 record (all else zero),
+ *            as after gyp_weak_bank_drop_channel, until gyp_weak_bank_set_channel restarts the slot in SYNC at the bank's cursor.
+ *            By the NWPR relation of the signal-quality section mu = 2.5 is 19.3 dB-Hz; noise alone gives 1 +- 0.2.
+ *
+ * Invariance.  Every record is bit for bit the same however the recording is split into calls (through the SYNC -> TRACK switch and
+ * in the middle of a period as well) and whatever other channels the bank holds. */
+typedef struct gyp_weak_bank gyp_weak_bank;
+
+typedef struct gyp_weak_params {   /* 48 bytes */
+    int32_t period_ms;     /* T in milliseconds: 20 (the only value taken: one data bit) */
+    int32_t sync_ms;       /* 400; 40..2000 */
+    int64_t spacing;       /* d in 2^-40 chips: 2^39 (half a chip); 1 .. 2^40 */
+    double pll_bw_hz;      /* 8; (0, 50] */
+    double dll_bw_hz;      /* 1; (0, 10] */
+    double lose_mu;        /* 2.5; [0, 20] */
+    double reserved;       /* 0 */
+} gyp_weak_params;
+void gyp_weak_params_default(gyp_weak_params* out);
+
+typedef struct gyp_weak_ms_rec {   /* 32 bytes: one per channel per millisecond */
+    float minus_re, minus_im, prompt_re, prompt_im, plus_re, plus_im;
+    int16_t pos;           /* position in the period: 0..19 in TRACK, 0 otherwise */
+    int8_t phase;          /* 0 SYNC, 1 WAIT, 2 TRACK */
+    int8_t status;         /* 0 ok, 2 lost or dropped (every other field 0) */
+    int32_t reserved;
+} gyp_weak_ms_rec;
+
+typedef struct gyp_weak_period_rec {   /* 88 bytes: one per channel per completed 20-ms period */
+    int64_t first_ms;      /* absolute index of the period's first millisecond */
+    double f, u0;          /* what the period ran with */
+    int64_t c0;
+    double i, q, mu, dphi, dd;
+    int32_t bit;           /* +1 or -1 (the polarity is ambiguous until a preamble is found, as in the reference) */
+    int32_t status;        /* 0 ok, 1 the channel was lost at the end of this period */
+    double mu_mean;        /* mean of the last 25 mu including this one; 0 before 25 periods are complete */
+} gyp_weak_period_rec;
+
+typedef struct gyp_weak_state {   /* 64 bytes */
+    double f, f_int, u0;
+    int64_t c0;
+    int32_t phase;         /* 0 SYNC, 1 WAIT, 2 TRACK */
+    int32_t edge;          /* 0..19; -1 while in SYNC */
+    int32_t status;        /* 0 ok, 2 lost or dropped */
+    int32_t pos;           /* milliseconds of the current TRACK period already in */
+    int32_t n_periods;     /* completed since the (re)start */
+    int32_t reserved;
+    double mu_mean;        /* as in the last period record */
+} gyp_weak_state;
+
+/* Host only, no GPU: the bit edge of a SYNC span.  prompts: n_ms interleaved re,im float32 pairs, the prompt of millisecond
+ * first_ms + i at i.  For o in 0..19 the groups are the runs of 20 prompts whose head h has h mod 20 == o and that lie whole inside
+ * [first_ms, first_ms + n_ms); en[o] is the mean over those groups, taken in increasing h, of |sum of the 20 prompts|^2: float64, the
+ * prompts widened first, re and im summed in order, re re + im im, the squares added in order, one division by the group count (0 for
+ * an o without a group).  The edge is the largest en, the lowest o on a tie.  Either output may be NULL.  GYP_E_BAD_ARG for NULL
+ * prompts, n_ms < 20 or first_ms < 0. */
+int gyp_weak_bit_sync(const float* prompts, int32_t n_ms, int64_t first_ms, double* energies_out20, int32_t* offset_out);
+
+/* first_ms: the absolute index of the first millisecond the bank will be given (its cursor).  Refused with GYP_E_BAD_ARG before
+ * anything runs: NULL or counts below 1, params out of range (NULL: the defaults), stream < 0, satellite ids outside 1..32, a
+ * non-finite Doppler or carrier phase, first_ms < 0. */
+int gyp_weak_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_chan, const gyp_weak_params* params, int64_t first_ms,
+                         gyp_weak_bank** out);
+void gyp_weak_bank_destroy(gyp_weak_bank* bank);
+int gyp_weak_bank_size(const gyp_weak_bank* bank);
+/* (Re)start slot `index` in SYNC at the bank's cursor / stop it (status-2 records from then on).  Both synchronise the stream. */
+int gyp_weak_bank_set_channel(gyp_weak_bank* bank, int32_t index, const gyp_chan_init* init_host);
+int gyp_weak_bank_drop_channel(gyp_weak_bank* bank, int32_t index);
+/* The live state of all n_chan channels / the full loop state of one channel, which is put in WAIT with the given edge (TRACK begins
+ * at the first millisecond m >= cursor with m mod 20 == edge; status 0, no periods complete).  Of `state` gyp_weak_bank_set_state reads
+ * f, f_int, u0 (in [0, 1)), c0 (in [0, 1023 2^40)) and edge (0..19).  Both synchronise the stream. */
+int gyp_weak_bank_get_state(gyp_weak_bank* bank, gyp_weak_state* out_host, int64_t* cursor_out);
+int gyp_weak_bank_set_state(gyp_weak_bank* bank, int32_t index, const gyp_weak_state* state_host);
+/* Advance every channel n_ms milliseconds from the cursor.  iq_dev: (largest stream index + 1) streams of n_ms x N samples, stream
+ * stride given.  ms_out_dev: n_chan x n_ms records, channel-major; period_out_dev: n_chan x (n_ms / 20 + 1) records, channel-major,
+ * of which the first n_periods_out_dev[channel] are written; either may be NULL (n_periods_out_dev may be NULL too).  Enqueues only.
+ * GYP_E_BAD_ARG before anything runs: NULL bank or iq, n_ms < 1 or > 65535, first_ms other than the cursor (recordings with gaps are
+ * out of scope), a stride below n_ms N, a context whose stream format is no longer the one the bank was created under.  The host form
+ * also refuses a channel whose stream index is >= n_streams; its iq holds n_streams x n_ms x N samples. */
+int gyp_weak_track_block_dev(gyp_weak_bank* bank, const float* iq_dev, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                             gyp_weak_ms_rec* ms_out_dev, gyp_weak_period_rec* period_out_dev, int32_t* n_periods_out_dev);
+int gyp_weak_track_block(gyp_weak_bank* bank, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                         gyp_weak_ms_rec* ms_out_host, gyp_weak_period_rec* period_out_host, int32_t* n_periods_out_host);
 
 /* ---------------------------------------------------------------- multi-GPU ----------------------------- */
 /* The path shards by stream, satellite or (satellite x Doppler) cell with no data-path exchange except ONE all-gather
