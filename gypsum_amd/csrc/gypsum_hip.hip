@@ -120,7 +120,8 @@ static thread_local std::string g_create_error;
 
 // Device buffers of the entry points on a context, one per role.  Each is reserved (Slack::grow) and used within one call, on the
 // context's stream; nothing is kept in them between calls.  A helper context (gyp_acquire_dev) has a set of its own.
-// Staging of the host-buffer entry points; only the wrappers that take host pointers use these, never a *_dev function:
+// Staging of the host-buffer entry points; only the wrappers that take host pointers use these, never a *_dev function (the wrappers
+// that upload samples alone and return one array go through staged_call):
 //   stage_iq       samples: gyp_correlate_cells, gyp_correlate_grid, gyp_search_level, gyp_acquire, gyp_track_step, gyp_track_block, gyp_weak_track_block
 //   stage_in       descriptors: gyp_correlate_cells (gyp_cell_desc), gyp_track_step (gyp_chan_in)
 //   stage_out      results: gyp_correlate_cells, gyp_correlate_grid (gyp_cell), gyp_search_level, gyp_acquire (gyp_acq_result), gyp_track_step (gyp_chan_out), gyp_track_block (gyp_track_rec)
@@ -138,10 +139,12 @@ static thread_local std::string g_create_error;
 //   acq_*                     acquire_search (gyp_acquire_dev, gyp_search_level_dev), sized by its AcqPlan and reserved in acq_reserve: search states, cell table, cell outputs, refined sums, float64 profiles, acq_book_layout, acq_units_layout, shared-forward spectra
 //   synth_scene, bench_sink   gyp_synth_iq_dev, gyp_debug_fft_bench
 //   hyb_sat_ids, hyb_doppler, hyb_grid_cells   gyp_correlate_grid_hybrid_dev: satellite ids, Doppler bins and the cell table made of them
-//   hyb_cell_out, hyb_profile, hyb_power   hybrid_run (behind both hybrid entry points): per chunk of cells the gyp_cell records the
-//                             cells kernel must write somewhere, a block's coherent profiles, the sets' power rows
-//   hyb_level_cells, hyb_records, hyb_taps   gyp_acquire_weak_dev: the cell tables of the coarse level, the fine level and the final
-//                             cells (back to back), the larger level's records, the final cells' gyp_cell records (their taps)
+//   hyb_cell_out, hyb_profile, hyb_power   hybrid_run (behind both hybrid entry points), sized by its HybPlan and reserved in hybrid_reserve
+//                             alone: per chunk of cells the gyp_cell records the cells kernel must write somewhere, a block's coherent
+//                             profiles, the sets' power rows
+//   hyb_level_cells, hyb_records, hyb_taps   gyp_acquire_weak_dev, sized by its WeakSearchPlan: the cell tables of the coarse level, the
+//                             fine level and the final cells (back to back), the larger level's records (weak_level), the final
+//                             cells' gyp_cell records (their taps)
 // Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
 // wrapper calls another (the hybrid wrappers gyp_correlate_grid_hybrid and gyp_acquire_weak use stage_iq and stage_out like the
 // others); of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
@@ -274,28 +277,22 @@ static const DebugSwitch kDebugSwitches[] = {
     GYP_SWITCH("grid_fused_waves", grid_fused_waves, 8, 12, true, false),   // (8 or 12: gyp_debug_set)
     GYP_SWITCH("cells_cu_reserve", cells_cu_reserve, 0, 128, true, true),
     GYP_SWITCH("resample_tile_samples", resample_tile, 1024, 8192, true, false),
+    GYP_SWITCH("notch_no_lds", notch_no_lds, 0, 1, true, false),
+    GYP_SWITCH("track_finish_all", track_finish_all, 0, 1, true, true),
+    GYP_SWITCH("hybrid_scratch_mb", hybrid_scratch_mb, kHybScratchMbMin, kHybScratchMbMax, true, false),
 };
 #undef GYP_SWITCH
-// The 0 / 1 switches added since the sanitizer tests' host driver pinned the rows of kDebugSwitches (it enumerates them and counts them):
-// set, read and range-checked like a row of the table; `inherited` as there (acquire_helper).
-struct DebugFlag { const char* name; bool gyp_ctx::*field; bool inherited; };
-static const DebugFlag kDebugFlags[] = {
-    {"notch_no_lds", &gyp_ctx::notch_no_lds, false},
-    {"track_finish_all", &gyp_ctx::track_finish_all, true},
-};
-// The integer switches added since then: set, read and range-checked like a row of the table, with the same message.
-struct DebugInt { const char* name; int gyp_ctx::*field; int lo, hi; };
-static const DebugInt kDebugInts[] = {
-    {"hybrid_scratch_mb", &gyp_ctx::hybrid_scratch_mb, kHybScratchMbMin, kHybScratchMbMax},
-};
 
-struct gyp_bank {
+// What the 1-ms bank and the weak bank share on the host (bank_create, bank_put_state, bank_covers below); each has its `states` besides.
+struct BankBase {
     gyp_ctx* ctx = nullptr;
     int n_chan = 0;
     int64_t fs = 0;              // the stream format the bank was created under
     int n = 0;
     std::vector<int32_t> stream_of;   // host copy of each channel's stream index
-    Stream verify_stream;        // (declared before everything used on it: destroyed last)
+};
+struct gyp_bank : BankBase {
+    Stream verify_stream;       // (declared before everything used on it: destroyed last)
     Event ev_spec, ev_verify, ev_vring[3];
     DevBuf<ChanState> states;
     // speculative block tracking: state checkpoint, per-(channel, ms) hand-over records, failed-verification flags
@@ -387,6 +384,7 @@ static int fail(gyp_ctx* ctx, int code, const std::string& msg) {
     else g_create_error = msg;
     return code;
 }
+static int refuse(gyp_ctx* ctx, const char* who, const std::string& why) { return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why); }
 #define HIP_TRY(ctx, call)                                                                                   \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
@@ -408,6 +406,50 @@ static int stage_back(gyp_ctx* ctx, void* out_host, size_t out_bytes, float* pro
     if (out_host) HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->scratch.stage_out.get(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (profile_host) HIP_TRY(ctx, hipMemcpyAsync(profile_host, ctx->scratch.stage_profile.get(), n_prof * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GYP_OK;
+}
+// A host form that uploads only samples and returns one array: the results' staging reserved, the samples uploaded,
+// `call(iq_dev, stream_stride_samples, out_dev)` -- the _dev form -- and the results copied back.  The wrapper's own checks come first.
+template <typename F>
+static int staged_call(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, void* out_host, size_t out_bytes, F&& call) {
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    if (const int rc = call(sc.stage_iq.get(), (int64_t)n_ms * ctx->n, sc.stage_out.get())) return rc;
+    return stage_back(ctx, out_host, out_bytes);
+}
+// A bank (gyp_bank, gyp_weak_bank) from its validated host states: made, its base filled, the states reserved, `rest(bank)` for what
+// the kind has besides, the states copied; deleted again if any of that fails.
+template <class Bank, class State, class F>
+static int bank_create(gyp_ctx* ctx, const char* who, const std::vector<State>& init, Bank** out, F&& rest) {
+    Bank* b = new Bank();
+    b->ctx = ctx; b->n_chan = (int)init.size(); b->fs = ctx->fs; b->n = ctx->n;
+    for (const State& s : init) b->stream_of.push_back(s.stream);
+    hipError_t e = b->states.reserve(init.size(), Slack::exact);
+    if (e == hipSuccess) e = rest(*b);
+    if (e == hipSuccess) e = hipMemcpy(b->states.get(), init.data(), init.size() * sizeof(State), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete b;
+        return fail(ctx, GYP_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    *out = b;
+    return GYP_OK;
+}
+// One channel's state put into a bank, behind everything enqueued on the context's stream
+template <class Bank, class State>
+static int bank_put_state(Bank* bank, int32_t index, const State& s) {
+    gyp_ctx* ctx = bank->ctx;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(bank->states.get() + index, &s, sizeof(State), hipMemcpyHostToDevice));
+    bank->stream_of[index] = s.stream;
+    return GYP_OK;
+}
+// The host forms of block tracking: every channel's stream is among the n_streams passed
+static int bank_covers(const BankBase& bank, const char* who, int32_t n_streams) {
+    for (int c = 0; c < bank.n_chan; ++c)
+        if (bank.stream_of[c] >= n_streams)
+            return refuse(bank.ctx, who, "channel " + std::to_string(c) + " reads stream " + std::to_string(bank.stream_of[c]) + " but only " +
+                                             std::to_string(n_streams) + " were passed");
     return GYP_OK;
 }
 // A channel's state at the start of tracking: the acquisition's values, fresh loop state and histories
@@ -1045,14 +1087,9 @@ int gyp_correlate_grid(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, in
     if (const int rc = need_format(ctx)) return rc;
     if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0 || n_bins <= 0)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_correlate_grid: bad argument");
-    Scratch& sc = ctx->scratch;
-    const size_t out_bytes = (size_t)n_streams * n_sats * n_bins * sizeof(gyp_cell);
-    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
-    if (const int rc = gyp_correlate_grid_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, doppler_hz_host,
-                                              n_bins, integration, (gyp_cell*)sc.stage_out.get()))
-        return rc;
-    return stage_back(ctx, out_host, out_bytes);
+    return staged_call(ctx, iq_host, n_streams, n_ms, out_host, (size_t)n_streams * n_sats * n_bins * sizeof(gyp_cell), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        return gyp_correlate_grid_dev(ctx, iq_dev, n_streams, stride, n_ms, sat_ids_host, n_sats, doppler_hz_host, n_bins, integration, (gyp_cell*)out_dev);
+    });
 }
 
 int gyp_grid_best_bins_dev(gyp_ctx* ctx, const gyp_cell* cells_dev, int32_t n_rows, int32_t n_bins, gyp_best_bin* out_dev) {
@@ -1254,8 +1291,6 @@ static gyp_ctx* acquire_helper(gyp_ctx* ctx, int which) {
     // the helper runs under the caller's switches (it never read an environment of its own)
     for (const DebugSwitch& k : kDebugSwitches)
         if (k.inherited) k.set(*h, k.get(*ctx));
-    for (const DebugFlag& f : kDebugFlags)
-        if (f.inherited) h->*(f.field) = ctx->*(f.field);
     return h;
 }
 
@@ -1303,46 +1338,47 @@ int gyp_search_level_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, i
     return acquire_search(ctx, AcqCall{iq_dev, n_streams, stream_stride_samples, n_ms, sat_ids_host, n_sats, out_dev, 0}, AcqSearch{center_hz, spread_hz, true});
 }
 
-}   // extern "C"
-// gyp_search_level / gyp_acquire: the samples staged, `search(iq_dev, out_dev)`, the results copied back
-template <typename F>
-static int search_staged(gyp_ctx* ctx, const char* who, const float* iq_host, int32_t n_streams, int32_t n_ms, int32_t n_sats,
-                         gyp_acq_result* out_host, F&& search) {
+// What gyp_search_level and gyp_acquire refuse themselves
+static int search_check(gyp_ctx* ctx, const char* who, const float* iq_host, int32_t n_streams, int32_t n_ms, int32_t n_sats, const gyp_acq_result* out_host) {
     if (!ctx) return GYP_E_BAD_ARG;
     if (const int rc = need_format(ctx)) return rc;
     if (!iq_host || !out_host || n_streams <= 0 || n_ms <= 0 || n_sats <= 0) return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": bad argument");
-    Scratch& sc = ctx->scratch;
-    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_acq_result);
-    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
-    if (const int rc = search(sc.stage_iq.get(), (gyp_acq_result*)sc.stage_out.get())) return rc;
-    return stage_back(ctx, out_host, out_bytes);
+    return GYP_OK;
 }
-extern "C" {
 
 int gyp_search_level(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                      int32_t n_sats, double center_hz, double spread_hz, gyp_acq_result* out_host) {
-    return search_staged(ctx, "gyp_search_level", iq_host, n_streams, n_ms, n_sats, out_host, [&](const float* iq_dev, gyp_acq_result* out_dev) {
-        return gyp_search_level_dev(ctx, iq_dev, n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, out_dev);
+    if (const int rc = search_check(ctx, "gyp_search_level", iq_host, n_streams, n_ms, n_sats, out_host)) return rc;
+    return staged_call(ctx, iq_host, n_streams, n_ms, out_host, (size_t)n_streams * n_sats * sizeof(gyp_acq_result), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        return gyp_search_level_dev(ctx, iq_dev, n_streams, stride, n_ms, sat_ids_host, n_sats, center_hz, spread_hz, (gyp_acq_result*)out_dev);
     });
 }
 
 int gyp_acquire(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int32_t n_ms, const int32_t* sat_ids_host,
                 int32_t n_sats, gyp_acq_result* out_host) {
-    return search_staged(ctx, "gyp_acquire", iq_host, n_streams, n_ms, n_sats, out_host, [&](const float* iq_dev, gyp_acq_result* out_dev) {
-        return gyp_acquire_dev(ctx, iq_dev, n_streams, (int64_t)n_ms * ctx->n, n_ms, sat_ids_host, n_sats, out_dev);
+    if (const int rc = search_check(ctx, "gyp_acquire", iq_host, n_streams, n_ms, n_sats, out_host)) return rc;
+    return staged_call(ctx, iq_host, n_streams, n_ms, out_host, (size_t)n_streams * n_sats * sizeof(gyp_acq_result), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        return gyp_acquire_dev(ctx, iq_dev, n_streams, stride, n_ms, sat_ids_host, n_sats, (gyp_acq_result*)out_dev);
     });
 }
 
 // ---------------------------------------------------------------- weak-signal acquisition -----------------
 }   // extern "C"
-static int refuse(gyp_ctx* ctx, const char* who, const std::string& why);
 // What both hybrid entry points refuse (hybrid_plan.hpp: hybrid_refusal), before anything is reserved or launched.
 static int hybrid_check(gyp_ctx* ctx, const char* who, const void* iq, const void* out, int32_t n_streams, int64_t stream_stride_samples,
                         int32_t coherent_ms, int32_t n_blocks, int32_t flags, const int32_t* sat_ids_host, int32_t n_sats) {
     if (!iq || !out || !sat_ids_host || n_streams <= 0 || n_sats <= 0 || stream_stride_samples < 0) return refuse(ctx, who, "bad argument");
     if (const char* why = hybrid_refusal(coherent_ms, n_blocks, flags)) return refuse(ctx, who, why);
     return check_sat_ids(ctx, sat_ids_host, n_sats);
+}
+
+// hybrid_run's scratch for a plan: the one place hyb_cell_out, hyb_profile and hyb_power are reserved.
+static int hybrid_reserve(gyp_ctx* ctx, const HybPlan& pl) {
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(ctx, sc.hyb_cell_out.reserve((size_t)pl.chunk_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_profile.reserve(pl.profile, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_power.reserve(pl.power, Slack::grow, ctx->stream));
+    return GYP_OK;
 }
 
 // The records of n_cells cells (device table) into out_dev: the cells go through in chunks that fit the scratch budget; per chunk
@@ -1352,10 +1388,8 @@ static int hybrid_run(gyp_ctx* ctx, const float* iq_dev, int64_t stream_stride_s
                       const gyp_cell_desc* cells_dev, int64_t n_cells, gyp_hybrid_cell* out_dev) {
     const HybPlan pl = hybrid_plan(HybShape{ctx->n, n_cells, coherent_ms, n_blocks, flags}, ctx->hybrid_scratch_mb);
     if (!pl.fits) return fail(ctx, GYP_E_BAD_ARG, "hybrid search: the request does not fit (more than 2^31 - 1 cells?)");
+    if (const int rc = hybrid_reserve(ctx, pl)) return rc;
     Scratch& sc = ctx->scratch;
-    HIP_TRY(ctx, sc.hyb_cell_out.reserve((size_t)pl.chunk_cells, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.hyb_profile.reserve(pl.profile, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.hyb_power.reserve(pl.power, Slack::grow, ctx->stream));
     for (int64_t c0 = 0; c0 < n_cells; c0 += pl.chunk_cells) {
         const int32_t nc = (int32_t)std::min<int64_t>(pl.chunk_cells, n_cells - c0);
         HybAccParams a;
@@ -1425,75 +1459,62 @@ int gyp_correlate_grid_hybrid(gyp_ctx* ctx, const float* iq_host, int32_t n_stre
     if (const int rc = hybrid_check(ctx, who, iq_host, out_host, n_streams, 0, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
     const int64_t n_cells = (int64_t)n_streams * n_sats * n_bins;
     if (n_cells > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 cells");
-    Scratch& sc = ctx->scratch;
-    const int32_t n_ms = n_blocks * coherent_ms;
-    const size_t out_bytes = (size_t)n_cells * sizeof(gyp_hybrid_cell);
-    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
-    if (const int rc = gyp_correlate_grid_hybrid_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, coherent_ms, n_blocks, flags, sat_ids_host,
-                                                     n_sats, doppler_hz_host, n_bins, (gyp_hybrid_cell*)sc.stage_out.get()))
-        return rc;
-    return stage_back(ctx, out_host, out_bytes);
+    return staged_call(ctx, iq_host, n_streams, n_blocks * coherent_ms, out_host, (size_t)n_cells * sizeof(gyp_hybrid_cell), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        return gyp_correlate_grid_hybrid_dev(ctx, iq_dev, n_streams, stride, coherent_ms, n_blocks, flags, sat_ids_host, n_sats, doppler_hz_host, n_bins, (gyp_hybrid_cell*)out_dev);
+    });
 }
+
+}   // extern "C"
+// One level of gyp_acquire_weak_dev (0 coarse, 1 fine): hybrid_run over the level's cells, then the select kernel, which writes the next
+// level's cells around each state's best bin -- behind the last level the final cells and the results.  The one place HybSelectParams is filled.
+struct WeakCall { const float* iq; int64_t stride; int32_t coherent_ms, n_blocks, flags; double fine_step_hz; gyp_weak_result* out; };
+static int weak_level(gyp_ctx* ctx, const WeakCall& c, const WeakSearchPlan& pl, int level) {
+    Scratch& sc = ctx->scratch;
+    gyp_cell_desc* const cells = sc.hyb_level_cells.get() + (level ? pl.coarse_cells : 0);
+    const bool last = level == 1 || pl.fine_half < 0;
+    if (const int rc = hybrid_run(ctx, c.iq, c.stride, c.coherent_ms, c.n_blocks, c.flags, cells, (int64_t)(level ? pl.fine_cells : pl.coarse_cells), sc.hyb_records.get()))
+        return rc;
+    HybSelectParams sp;
+    sp.recs = sc.hyb_records.get();
+    sp.cells = cells;
+    sp.n_states = (int32_t)pl.n_states; sp.n_bins = level ? pl.n_fine : pl.n_coarse;
+    sp.next_half = last ? -1 : pl.fine_half; sp.next_step = c.fine_step_hz;
+    sp.next_cells = sc.hyb_level_cells.get() + pl.coarse_cells + (last ? pl.fine_cells : 0);
+    sp.out = c.out;
+    hipLaunchKernelGGL(hybrid_select_kernel, dim3((unsigned)((pl.n_states + 63) / 64)), dim3(64), 0, ctx->stream, sp);
+    return launched(ctx);
+}
+extern "C" {
 
 int gyp_acquire_weak_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int32_t coherent_ms,
                          int32_t n_blocks, int32_t flags, double center_hz, double spread_hz, double fine_step_hz,
                          const int32_t* sat_ids_host, int32_t n_sats, gyp_weak_result* out_dev) {
     static const char* const who = "gyp_acquire_weak_dev";
-    constexpr int kMaxLevelBins = 4096;
     if (!ctx) return GYP_E_BAD_ARG;
     if (const int rc = need_format(ctx)) return rc;
     if (const int rc = hybrid_check(ctx, who, iq_dev, out_dev, n_streams, stream_stride_samples, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
-    if (n_sats > 32) return refuse(ctx, who, "at most 32 satellites per call");
-    if (!std::isfinite(center_hz) || !std::isfinite(spread_hz) || !std::isfinite(fine_step_hz) || !(spread_hz > 0.0))
-        return refuse(ctx, who, "center, spread and fine step must be finite and the spread positive");
-    const int n_coarse = hybrid_coarse_bins(center_hz, spread_hz, coherent_ms), half = hybrid_fine_half(fine_step_hz, coherent_ms);
-    const int n_fine = half >= 0 ? 2 * half + 1 : 0;
-    if (n_coarse < 1 || n_coarse > kMaxLevelBins || n_fine > kMaxLevelBins) return refuse(ctx, who, "a level must have between 1 and 4096 Doppler bins");
-    const int64_t n_states = (int64_t)n_streams * n_sats;
-    if (n_states * std::max(n_coarse, n_fine) > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 cells");
+    const WeakSearchPlan pl = weak_search_plan(WeakSearchShape{ctx->n, n_streams, n_sats, coherent_ms, n_blocks, flags, center_hz, spread_hz, fine_step_hz}, ctx->hybrid_scratch_mb);
+    if (pl.refusal) return refuse(ctx, who, pl.refusal);
     Scratch& sc = ctx->scratch;
-    const size_t states = (size_t)n_states, coarse_cells = states * n_coarse, fine_cells = states * n_fine;
-    HIP_TRY(ctx, sc.hyb_level_cells.reserve(coarse_cells + fine_cells + states, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, sc.hyb_records.reserve(std::max(coarse_cells, fine_cells), Slack::grow, ctx->stream));
+    const size_t states = (size_t)pl.n_states;
+    HIP_TRY(ctx, sc.hyb_level_cells.reserve(pl.level_cells, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.hyb_records.reserve(pl.records, Slack::grow, ctx->stream));
     HIP_TRY(ctx, sc.hyb_taps.reserve(states, Slack::grow, ctx->stream));
-    {   // hybrid_run's scratch for the larger level now: a buffer that grew between the levels would wait for the stream
-        const HybPlan big = hybrid_plan(HybShape{ctx->n, (int64_t)std::max(coarse_cells, fine_cells), coherent_ms, n_blocks, flags}, ctx->hybrid_scratch_mb);
-        HIP_TRY(ctx, sc.hyb_cell_out.reserve((size_t)big.chunk_cells, Slack::grow, ctx->stream));
-        HIP_TRY(ctx, sc.hyb_profile.reserve(big.profile, Slack::grow, ctx->stream));
-        HIP_TRY(ctx, sc.hyb_power.reserve(big.power, Slack::grow, ctx->stream));
-    }
-    gyp_cell_desc* const cells0 = sc.hyb_level_cells.get();
-    gyp_cell_desc* const cells1 = cells0 + coarse_cells;
-    gyp_cell_desc* const cells_final = cells1 + fine_cells;
-    const dim3 sgrid((unsigned)((n_states + 63) / 64));
+    if (const int rc = hybrid_reserve(ctx, pl.run)) return rc;
+    const dim3 sgrid((unsigned)((pl.n_states + 63) / 64));
     HybSatIds ids{};
     for (int i = 0; i < n_sats; ++i) ids.v[i] = sat_ids_host[i];
-    hipLaunchKernelGGL(hybrid_coarse_cells_kernel, sgrid, dim3(64), 0, ctx->stream, ids, n_sats, (int32_t)n_states, n_coarse, center_hz, spread_hz, coherent_ms, cells0);
+    hipLaunchKernelGGL(hybrid_coarse_cells_kernel, sgrid, dim3(64), 0, ctx->stream, ids, n_sats, (int32_t)pl.n_states, pl.n_coarse, center_hz, spread_hz, coherent_ms,
+                       sc.hyb_level_cells.get());
     if (const int rc = launched(ctx)) return rc;
-    if (const int rc = hybrid_run(ctx, iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, cells0, (int64_t)coarse_cells, sc.hyb_records.get())) return rc;
-    HybSelectParams sp;
-    sp.recs = sc.hyb_records.get();
-    sp.cells = cells0;
-    sp.n_states = (int32_t)n_states; sp.n_bins = n_coarse;
-    sp.next_half = half; sp.next_step = fine_step_hz;
-    sp.next_cells = half >= 0 ? cells1 : cells_final;
-    sp.out = out_dev;
-    hipLaunchKernelGGL(hybrid_select_kernel, sgrid, dim3(64), 0, ctx->stream, sp);
-    if (const int rc = launched(ctx)) return rc;
-    if (half >= 0) {
-        if (const int rc = hybrid_run(ctx, iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, cells1, (int64_t)fine_cells, sc.hyb_records.get())) return rc;
-        sp.cells = cells1;
-        sp.n_bins = n_fine;
-        sp.next_half = -1;
-        sp.next_cells = cells_final;
-        hipLaunchKernelGGL(hybrid_select_kernel, sgrid, dim3(64), 0, ctx->stream, sp);
-        if (const int rc = launched(ctx)) return rc;
-    }
+    const WeakCall call{iq_dev, stream_stride_samples, coherent_ms, n_blocks, flags, fine_step_hz, out_dev};
+    for (int level = 0; level < (pl.fine_half >= 0 ? 2 : 1); ++level)
+        if (const int rc = weak_level(ctx, call, pl, level)) return rc;
     // the coherent pass of the final bin over block 0, for the carrier phase at the code phase (the tap)
-    if (const int rc = launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, coherent_ms, cells_final, (int32_t)n_states, sc.hyb_taps.get(), nullptr, nullptr, nullptr), GYP_COHERENT))
+    if (const int rc = launch_cells(ctx, cells_params(ctx, iq_dev, stream_stride_samples, coherent_ms, sc.hyb_level_cells.get() + pl.coarse_cells + pl.fine_cells, (int32_t)pl.n_states,
+                                                      sc.hyb_taps.get(), nullptr, nullptr, nullptr), GYP_COHERENT))
         return rc;
-    hipLaunchKernelGGL(hybrid_finish_kernel, sgrid, dim3(64), 0, ctx->stream, (const gyp_cell*)sc.hyb_taps.get(), (int32_t)n_states, out_dev);
+    hipLaunchKernelGGL(hybrid_finish_kernel, sgrid, dim3(64), 0, ctx->stream, (const gyp_cell*)sc.hyb_taps.get(), (int32_t)pl.n_states, out_dev);
     return launched(ctx);
 }
 
@@ -1504,15 +1525,9 @@ int gyp_acquire_weak(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int3
     if (!ctx) return GYP_E_BAD_ARG;
     if (const int rc = need_format(ctx)) return rc;
     if (const int rc = hybrid_check(ctx, who, iq_host, out_host, n_streams, 0, coherent_ms, n_blocks, flags, sat_ids_host, n_sats)) return rc;
-    Scratch& sc = ctx->scratch;
-    const int32_t n_ms = n_blocks * coherent_ms;
-    const size_t out_bytes = (size_t)n_streams * n_sats * sizeof(gyp_weak_result);
-    HIP_TRY(ctx, sc.stage_out.reserve(out_bytes, Slack::grow, ctx->stream));
-    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
-    if (const int rc = gyp_acquire_weak_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, coherent_ms, n_blocks, flags, center_hz, spread_hz,
-                                            fine_step_hz, sat_ids_host, n_sats, (gyp_weak_result*)sc.stage_out.get()))
-        return rc;
-    return stage_back(ctx, out_host, out_bytes);
+    return staged_call(ctx, iq_host, n_streams, n_blocks * coherent_ms, out_host, (size_t)n_streams * n_sats * sizeof(gyp_weak_result), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        return gyp_acquire_weak_dev(ctx, iq_dev, n_streams, stride, coherent_ms, n_blocks, flags, center_hz, spread_hz, fine_step_hz, sat_ids_host, n_sats, (gyp_weak_result*)out_dev);
+    });
 }
 
 // ---------------------------------------------------------------- tracking: explicit millisecond ----------
@@ -1574,20 +1589,7 @@ int gyp_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t n_cha
             return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_create: channel descriptor out of range");
         init[i] = fresh_chan_state(chans_host[i]);
     }
-    gyp_bank* b = new gyp_bank();
-    b->ctx = ctx;
-    b->n_chan = n_chan;
-    b->fs = ctx->fs;
-    b->n = ctx->n;
-    for (int i = 0; i < n_chan; ++i) b->stream_of.push_back(chans_host[i].stream);
-    hipError_t e = b->states.reserve(init.size(), Slack::exact);
-    if (e == hipSuccess) e = hipMemcpy(b->states.get(), init.data(), init.size() * sizeof(ChanState), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        delete b;
-        return fail(ctx, GYP_E_HIP, std::string("gyp_bank_create: ") + hipGetErrorString(e));
-    }
-    *out = b;
-    return GYP_OK;
+    return bank_create(ctx, "gyp_bank_create", init, out, [](gyp_bank&) { return hipSuccess; });
 }
 
 void gyp_bank_destroy(gyp_bank* bank) {
@@ -1604,11 +1606,7 @@ int gyp_bank_set_channel(gyp_bank* bank, int32_t index, const gyp_chan_init* in)
     gyp_ctx* ctx = bank->ctx;
     if (!in || index < 0 || index >= bank->n_chan || in->stream < 0 || in->sat_id < 1 || in->sat_id > 32)
         return fail(ctx, GYP_E_BAD_ARG, "gyp_bank_set_channel: bad argument");
-    const ChanState s = fresh_chan_state(*in);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(bank->states.get() + index, &s, sizeof(ChanState), hipMemcpyHostToDevice));
-    bank->stream_of[index] = in->stream;
-    return GYP_OK;
+    return bank_put_state(bank, index, fresh_chan_state(*in));
 }
 
 int gyp_bank_drop_channel(gyp_bank* bank, int32_t index) {
@@ -1909,10 +1907,7 @@ int gyp_track_block(gyp_bank* bank, const float* iq_host, int32_t n_streams, int
     if (!bank) return GYP_E_BAD_ARG;
     gyp_ctx* ctx = bank->ctx;
     if (!iq_host || !start_time_host || n_streams <= 0 || n_ms < 0) return fail(ctx, GYP_E_BAD_ARG, "gyp_track_block: bad argument");
-    for (int c = 0; c < bank->n_chan; ++c)
-        if (bank->stream_of[c] >= n_streams)
-            return fail(ctx, GYP_E_BAD_ARG, "gyp_track_block: channel " + std::to_string(c) + " reads stream " +
-                                                std::to_string(bank->stream_of[c]) + " but only " + std::to_string(n_streams) + " were passed");
+    if (const int rc = bank_covers(*bank, "gyp_track_block", n_streams)) return rc;
     if (n_ms == 0) return GYP_OK;
     Scratch& sc = ctx->scratch;
     const size_t rec_bytes = rec_out_host ? (size_t)bank->n_chan * n_ms * sizeof(gyp_track_rec) : 0;
@@ -1928,24 +1923,12 @@ int gyp_track_block(gyp_bank* bank, const float* iq_host, int32_t n_streams, int
 // ---------------------------------------------------------------- weak-signal tracking ---------------------
 }   // extern "C"
 // A weak bank: the channels' states and the SYNC prompt rows, device resident; the cursor and the parameters on the host.
-struct gyp_weak_bank {
-    gyp_ctx* ctx = nullptr;
-    int n_chan = 0;
-    int64_t fs = 0;              // the stream format the bank was created under
-    int n = 0;
+struct gyp_weak_bank : BankBase {
     int64_t cursor = 0;          // absolute index of the next millisecond
     gyp_weak_params prm{};
-    std::vector<int32_t> stream_of;
     DevBuf<WeakChan> states;         // [n_chan]
     DevBuf<float2> sync_prompts;     // [n_chan][sync_ms]
 };
-static int weak_put_state(gyp_weak_bank* bank, int32_t index, const WeakChan& s) {
-    gyp_ctx* ctx = bank->ctx;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(bank->states.get() + index, &s, sizeof(WeakChan), hipMemcpyHostToDevice));
-    bank->stream_of[index] = s.stream;
-    return GYP_OK;
-}
 static int weak_get_chan(gyp_weak_bank* bank, int32_t index, WeakChan* s) {
     gyp_ctx* ctx = bank->ctx;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1991,18 +1974,10 @@ int gyp_weak_bank_create(gyp_ctx* ctx, const gyp_chan_init* chans_host, int32_t 
         if (const char* why = weak_init_refusal(chans_host[i])) return refuse(ctx, who, why);
         init[i] = weak_fresh_chan(chans_host[i], ctx->n, first_ms);
     }
-    gyp_weak_bank* b = new gyp_weak_bank();
-    b->ctx = ctx; b->n_chan = n_chan; b->fs = ctx->fs; b->n = ctx->n; b->cursor = first_ms; b->prm = prm;
-    for (int i = 0; i < n_chan; ++i) b->stream_of.push_back(chans_host[i].stream);
-    hipError_t e = b->states.reserve(init.size(), Slack::exact);
-    if (e == hipSuccess) e = b->sync_prompts.reserve(init.size() * (size_t)prm.sync_ms, Slack::exact);
-    if (e == hipSuccess) e = hipMemcpy(b->states.get(), init.data(), init.size() * sizeof(WeakChan), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        delete b;
-        return fail(ctx, GYP_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    *out = b;
-    return GYP_OK;
+    return bank_create(ctx, who, init, out, [&](gyp_weak_bank& b) {
+        b.cursor = first_ms; b.prm = prm;
+        return b.sync_prompts.reserve(init.size() * (size_t)prm.sync_ms, Slack::exact);
+    });
 }
 
 void gyp_weak_bank_destroy(gyp_weak_bank* bank) {
@@ -2018,7 +1993,7 @@ int gyp_weak_bank_set_channel(gyp_weak_bank* bank, int32_t index, const gyp_chan
     if (!bank) return GYP_E_BAD_ARG;
     if (!in || index < 0 || index >= bank->n_chan) return refuse(bank->ctx, who, "bad argument");
     if (const char* why = weak_init_refusal(*in)) return refuse(bank->ctx, who, why);
-    return weak_put_state(bank, index, weak_fresh_chan(*in, bank->n, bank->cursor));
+    return bank_put_state(bank, index, weak_fresh_chan(*in, bank->n, bank->cursor));
 }
 
 int gyp_weak_bank_drop_channel(gyp_weak_bank* bank, int32_t index) {
@@ -2027,7 +2002,7 @@ int gyp_weak_bank_drop_channel(gyp_weak_bank* bank, int32_t index) {
     WeakChan s;
     if (const int rc = weak_get_chan(bank, index, &s)) return rc;
     s.status = 2;
-    return weak_put_state(bank, index, s);
+    return bank_put_state(bank, index, s);
 }
 
 int gyp_weak_bank_get_state(gyp_weak_bank* bank, gyp_weak_state* out_host, int64_t* cursor_out) {
@@ -2062,7 +2037,7 @@ int gyp_weak_bank_set_state(gyp_weak_bank* bank, int32_t index, const gyp_weak_s
     t.stream = s.stream; t.sat_id = s.sat_id;
     t.phase = kWeakWait; t.edge = in->edge; t.sync_start = bank->cursor;
     t.f = in->f; t.f_int = in->f_int; t.u0 = in->u0; t.c0 = in->c0;
-    return weak_put_state(bank, index, t);
+    return bank_put_state(bank, index, t);
 }
 
 int gyp_weak_track_block_dev(gyp_weak_bank* bank, const float* iq_dev, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
@@ -2091,10 +2066,7 @@ int gyp_weak_track_block(gyp_weak_bank* bank, const float* iq_host, int32_t n_st
     gyp_ctx* ctx = bank->ctx;
     if (n_streams < 1) return refuse(ctx, who, "bad argument");
     if (const int rc = weak_track_check(bank, who, iq_host, first_ms, n_ms)) return rc;
-    for (int c = 0; c < bank->n_chan; ++c)
-        if (bank->stream_of[c] >= n_streams)
-            return refuse(ctx, who, "channel " + std::to_string(c) + " reads stream " + std::to_string(bank->stream_of[c]) + " but only " +
-                                        std::to_string(n_streams) + " were passed");
+    if (const int rc = bank_covers(*bank, who, n_streams)) return rc;
     Scratch& sc = ctx->scratch;
     const size_t nc = (size_t)bank->n_chan, max_periods = (size_t)n_ms / kWeakPeriodMs + 1;
     const size_t ms_bytes = nc * n_ms * sizeof(gyp_weak_ms_rec), per_bytes = nc * max_periods * sizeof(gyp_weak_period_rec), cnt_bytes = nc * sizeof(int32_t);
@@ -2356,25 +2328,8 @@ static const DebugSwitch* debug_switch(const char* name) {
         if (std::strcmp(name, k.name) == 0) return &k;
     return nullptr;
 }
-static const DebugFlag* debug_flag(const char* name) {
-    for (const DebugFlag& f : kDebugFlags)
-        if (std::strcmp(name, f.name) == 0) return &f;
-    return nullptr;
-}
 int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
     if (!ctx || !name) return GYP_E_BAD_ARG;
-    if (const DebugFlag* f = debug_flag(name)) {
-        if (value != 0.0 && value != 1.0) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be 0 or 1");
-        ctx->*(f->field) = value != 0.0;
-        return GYP_OK;
-    }
-    for (const DebugInt& d : kDebugInts)
-        if (std::strcmp(name, d.name) == 0) {
-            if (!std::isfinite(value) || value < d.lo || value > d.hi || value != std::floor(value))
-                return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: ") + name + " must be an integer in [" + std::to_string(d.lo) + ", " + std::to_string(d.hi) + "]");
-            ctx->*(d.field) = (int)value;
-            return GYP_OK;
-        }
     const DebugSwitch* k = debug_switch(name);
     if (!k) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_set: no such switch: ") + name);
     if (!std::isfinite(value) || value < k->lo || value > k->hi || (k->integral && value != std::floor(value)))
@@ -2389,10 +2344,7 @@ int gyp_debug_set(gyp_ctx* ctx, const char* name, double value) {
 }
 int gyp_debug_get(gyp_ctx* ctx, const char* name, double* out) {
     if (!ctx || !name || !out) return GYP_E_BAD_ARG;
-    if (const DebugFlag* f = debug_flag(name)) { *out = ctx->*(f->field) ? 1.0 : 0.0; return GYP_OK; }
     if (const DebugSwitch* k = debug_switch(name)) { *out = k->get(*ctx); return GYP_OK; }
-    for (const DebugInt& d : kDebugInts)
-        if (std::strcmp(name, d.name) == 0) { *out = (double)(ctx->*(d.field)); return GYP_OK; }
     const int rc = debug_read_only(ctx, name, out);
     if (rc == GYP_E_HIP) return fail(ctx, rc, std::string("gyp_debug_get: reading the device counters of ") + name + " failed");
     if (rc != GYP_OK) return fail(ctx, GYP_E_BAD_ARG, std::string("gyp_debug_get: no such switch: ") + name);
@@ -2943,7 +2895,6 @@ static int for_each_chunk(const StagePlan& pl, Launch&& launch) {
     return GYP_OK;
 }
 // The refusals' common forms: "<who>: <why>", and rows of `extent` samples that would overlap at this stride
-static int refuse(gyp_ctx* ctx, const char* who, const std::string& why) { return fail(ctx, GYP_E_BAD_ARG, std::string(who) + ": " + why); }
 static bool rows_overlap(int32_t n_streams, int64_t stride, int64_t extent) { return n_streams > 1 && stride < extent; }
 // The window of the stand-alone blanker, excisor and spectrum histogram, whose refusals read alike but for min_ms, lo and hi
 static int window_check(gyp_ctx* ctx, const char* who, const IqWindow& w, int32_t min_ms, int32_t lo, int32_t hi) {

@@ -117,4 +117,39 @@ inline int hybrid_fine_half(double step, int coherent_ms) {
     return j;
 }
 
+// gyp_acquire_weak_dev's search for a shape: the two levels' bins, the offsets of their cell tables in Scratch::hyb_level_cells,
+// what it reserves, and hybrid_run's plan for the larger level (reserved once, up front: a buffer that grew between the levels
+// would wait for the stream).
+constexpr int kWeakMaxSats = 32, kWeakMaxLevelBins = 4096;
+struct WeakSearchShape { int n; int n_streams, n_sats, coherent_ms, n_blocks, flags; double center_hz, spread_hz, fine_step_hz; };
+struct WeakSearchPlan {
+    const char* refusal;               // nullptr: runs; else why not, in the order the entry point has always refused, and every other member is 0
+    int n_coarse, fine_half, n_fine;   // fine_half -1, n_fine 0: no fine level
+    int64_t n_states;                  // (stream, satellite) pairs
+    size_t coarse_cells, fine_cells;   // cell-table offsets: level 0 at 0, level 1 at coarse_cells, the final cells at coarse_cells + fine_cells
+    size_t level_cells, records;       // elements of hyb_level_cells and of hyb_records
+    HybPlan run;
+};
+inline WeakSearchPlan weak_search_plan(const WeakSearchShape& s, int scratch_mb) {
+    const auto refused = [](const char* why) { WeakSearchPlan r{}; r.refusal = why; return r; };
+    if (const char* why = hybrid_refusal(s.coherent_ms, s.n_blocks, s.flags)) return refused(why);
+    if (s.n_sats > kWeakMaxSats) return refused("at most 32 satellites per call");
+    if (!std::isfinite(s.center_hz) || !std::isfinite(s.spread_hz) || !std::isfinite(s.fine_step_hz) || !(s.spread_hz > 0.0))
+        return refused("center, spread and fine step must be finite and the spread positive");
+    WeakSearchPlan pl{};
+    pl.n_coarse = hybrid_coarse_bins(s.center_hz, s.spread_hz, s.coherent_ms);
+    pl.fine_half = hybrid_fine_half(s.fine_step_hz, s.coherent_ms);
+    pl.n_fine = pl.fine_half >= 0 ? 2 * pl.fine_half + 1 : 0;
+    if (pl.n_coarse < 1 || pl.n_coarse > kWeakMaxLevelBins || pl.n_fine > kWeakMaxLevelBins) return refused("a level must have between 1 and 4096 Doppler bins");
+    pl.n_states = (int64_t)s.n_streams * s.n_sats;
+    if (pl.n_states * std::max(pl.n_coarse, pl.n_fine) > INT32_MAX) return refused("more than 2^31 - 1 cells");
+    const size_t states = (size_t)pl.n_states;
+    pl.coarse_cells = states * pl.n_coarse;
+    pl.fine_cells = states * pl.n_fine;
+    pl.level_cells = pl.coarse_cells + pl.fine_cells + states;
+    pl.records = std::max(pl.coarse_cells, pl.fine_cells);
+    pl.run = hybrid_plan(HybShape{s.n, (int64_t)pl.records, s.coherent_ms, s.n_blocks, s.flags}, scratch_mb);
+    return pl;
+}
+
 }  // namespace gyp

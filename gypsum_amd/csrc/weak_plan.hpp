@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "../../include/gypsum_hip.h"
+#include "hybrid_plan.hpp"
 
 #if defined(__HIPCC__)
 #define GYP_WEAK_HD __host__ __device__
@@ -21,7 +22,7 @@ namespace gyp {
 
 constexpr int64_t kWeakOne = (int64_t)1 << 40;          // one chip
 constexpr int64_t kWeakCodeMod = 1023 * kWeakOne;
-constexpr double kWeakL1Hz = 1575.42e6;
+constexpr double kWeakL1Hz = kL1Hz;                     // (hybrid_plan.hpp: the search and the loops scale code Doppler by the same number)
 constexpr int kWeakPeriodMs = 20, kWeakMuWindow = 25;
 constexpr int kWeakSyncMin = 40, kWeakSyncMax = 2000;
 constexpr int kWeakSync = 0, kWeakWait = 1, kWeakTrack = 2;   // gyp_weak_state::phase

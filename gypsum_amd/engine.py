@@ -22,6 +22,23 @@ def _as_iq(iq: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(iq, dtype=np.complex64)
 
 
+def _iq_arg(iq: np.ndarray, factors: Sequence[int], check: bool = True) -> np.ndarray:
+    """The samples of a host form, flat complex64: as many as the product of `factors` (streams, milliseconds, samples per
+    millisecond), or ValueError; check=False where the count is not one the library takes, which is then the library's to refuse."""
+    iq = _as_iq(iq).reshape(-1)
+    if check and iq.size != int(np.prod(factors, dtype=np.int64)):
+        raise ValueError(f"expected {'*'.join(str(f) for f in factors)} samples, got {iq.size}")
+    return iq
+
+
+def _ids(sat_ids: Sequence[int]) -> np.ndarray:
+    return np.ascontiguousarray(sat_ids, dtype=np.int32)
+
+
+def _bins(doppler_hz: Sequence[float]) -> np.ndarray:
+    return np.ascontiguousarray(doppler_hz, dtype=np.float64)
+
+
 def hybrid_stats(cells: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """gyp_hybrid_stats (host only, no GPU): (z, peak_ratio) float64 arrays of the shape of the HYBRID_CELL records `cells`;
     z = (peak - mean_off) / std_off is NaN where it is not defined."""
@@ -568,9 +585,7 @@ class GypsumEngine:
     def correlate_cells(self, iq: np.ndarray, n_streams: int, n_ms: int, cells: np.ndarray, integration: int,
                         want_profiles: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """iq: complex64[n_streams * n_ms * N] stream-major.  cells: CELL_DESC records."""
-        iq = _as_iq(iq).reshape(-1)
-        if iq.size != n_streams * n_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{self.n} samples, got {iq.size}")
+        iq = _iq_arg(iq, (n_streams, n_ms, self.n))
         cells = np.ascontiguousarray(cells, dtype=CELL_DESC)
         out = np.zeros(len(cells), dtype=CELL)
         prof = None
@@ -583,11 +598,8 @@ class GypsumEngine:
     def correlate_grid(self, iq: np.ndarray, n_streams: int, n_ms: int, sat_ids: Sequence[int], doppler_hz: Sequence[float],
                        integration: int) -> np.ndarray:
         """Flat grid with shared Doppler bins: CELL records [n_streams, n_sats, n_bins]."""
-        iq = _as_iq(iq).reshape(-1)
-        if iq.size != n_streams * n_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{self.n} samples, got {iq.size}")
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
-        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        iq = _iq_arg(iq, (n_streams, n_ms, self.n))
+        ids, bins = _ids(sat_ids), _bins(doppler_hz)
         out = np.zeros((n_streams, len(ids), len(bins)), dtype=CELL)
         self._check(self.lib.gyp_correlate_grid(self.ctx, ptr(iq), n_streams, n_ms, ptr(ids), len(ids), ptr(bins), len(bins),
                                                  integration, ptr(out)))
@@ -595,8 +607,7 @@ class GypsumEngine:
 
     def correlate_grid_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, n_ms: int, sat_ids: Sequence[int],
                            doppler_hz: Sequence[float], integration: int, out_ptr: int) -> None:
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
-        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        ids, bins = _ids(sat_ids), _bins(doppler_hz)
         self._check(self.lib.gyp_correlate_grid_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, n_ms, ptr(ids),
                                                      len(ids), ptr(bins), len(bins), integration, C.c_void_p(out_ptr)))
 
@@ -608,8 +619,7 @@ class GypsumEngine:
                                    doppler_hz: Sequence[float], integration: int, cells_ptr: int, out_ptr: int) -> int:
         """The same selection with the float64 tie-break between near-equal bins (gyp_grid_best_bins_refined_dev): the grid as
         correlate_grid_dev took it + the records it wrote.  Returns the number of rows decided in float64."""
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
-        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        ids, bins = _ids(sat_ids), _bins(doppler_hz)
         self._check(self.lib.gyp_grid_best_bins_refined_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, n_ms, ptr(ids), len(ids),
                                                              ptr(bins), len(bins), integration, C.c_void_p(cells_ptr), C.c_void_p(out_ptr)))
         return int(self.debug_get("last_grid_refined_rows"))
@@ -621,10 +631,8 @@ class GypsumEngine:
 
     # ------------------------------------------------------------------ acquisition
     def acquire(self, iq: np.ndarray, n_streams: int, n_ms: int, sat_ids: Sequence[int]) -> np.ndarray:
-        iq = _as_iq(iq).reshape(-1)
-        if iq.size != n_streams * n_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{self.n} samples, got {iq.size}")
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        iq = _iq_arg(iq, (n_streams, n_ms, self.n))
+        ids = _ids(sat_ids)
         out = np.zeros(n_streams * len(ids), dtype=ACQ_RESULT)
         self._check(self.lib.gyp_acquire(self.ctx, ptr(iq), n_streams, n_ms, ptr(ids), len(ids), ptr(out)))
         return out
@@ -632,10 +640,8 @@ class GypsumEngine:
     def search_level(self, iq: np.ndarray, n_streams: int, n_ms: int, sat_ids: Sequence[int], center_hz: float,
                      spread_hz: float) -> np.ndarray:
         """One level of the search (acquisition.py:154-190): best bin, its arg-max and strength per (stream, satellite)."""
-        iq = _as_iq(iq).reshape(-1)
-        if iq.size != n_streams * n_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{self.n} samples, got {iq.size}")
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        iq = _iq_arg(iq, (n_streams, n_ms, self.n))
+        ids = _ids(sat_ids)
         out = np.zeros(n_streams * len(ids), dtype=ACQ_RESULT)
         self._check(self.lib.gyp_search_level(self.ctx, ptr(iq), n_streams, n_ms, ptr(ids), len(ids), float(center_hz),
                                                float(spread_hz), ptr(out)))
@@ -661,7 +667,7 @@ class GypsumEngine:
     def acquire_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, n_ms: int, sat_ids: Sequence[int],
                     out_ptr: int) -> None:
         """Device-pointer form (asynchronous on the engine's stream): out_ptr receives n_streams*len(sat_ids) records."""
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        ids = _ids(sat_ids)
         self._check(self.lib.gyp_acquire_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, n_ms, ptr(ids),
                                               len(ids), C.c_void_p(out_ptr)))
 
@@ -670,11 +676,8 @@ class GypsumEngine:
                               doppler_hz: Sequence[float]) -> np.ndarray:
         """Flat grid of the hybrid coherent/non-coherent search: HYBRID_CELL records [n_streams, n_sats, n_bins] from
         n_blocks blocks of coherent_ms milliseconds (iq: complex64[n_streams * n_blocks * coherent_ms * N], stream-major)."""
-        iq = _as_iq(iq).reshape(-1)
-        if coherent_ms >= 1 and n_blocks >= 1 and iq.size != n_streams * n_blocks * coherent_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_blocks}*{coherent_ms}*{self.n} samples, got {iq.size}")
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
-        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        iq = _iq_arg(iq, (n_streams, n_blocks, coherent_ms, self.n), check=coherent_ms >= 1 and n_blocks >= 1)
+        ids, bins = _ids(sat_ids), _bins(doppler_hz)
         out = np.zeros((n_streams, len(ids), len(bins)), dtype=_lib.HYBRID_CELL)
         self._check(self.lib.gyp_correlate_grid_hybrid(self.ctx, ptr(iq), n_streams, int(coherent_ms), int(n_blocks), int(flags), ptr(ids), len(ids),
                                                         ptr(bins), len(bins), ptr(out)))
@@ -682,8 +685,7 @@ class GypsumEngine:
 
     def correlate_grid_hybrid_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, coherent_ms: int, n_blocks: int, flags: int,
                                   sat_ids: Sequence[int], doppler_hz: Sequence[float], out_ptr: int) -> None:
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
-        bins = np.ascontiguousarray(doppler_hz, dtype=np.float64)
+        ids, bins = _ids(sat_ids), _bins(doppler_hz)
         self._check(self.lib.gyp_correlate_grid_hybrid_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, int(coherent_ms), int(n_blocks),
                                                             int(flags), ptr(ids), len(ids), ptr(bins), len(bins), C.c_void_p(out_ptr)))
 
@@ -691,10 +693,8 @@ class GypsumEngine:
                      center_hz: float = 0.0, spread_hz: float = 7000.0, fine_step_hz: float = 10.0) -> np.ndarray:
         """The two-level hybrid search per (stream, satellite): WEAK_RESULT records, stream-major, satellites in the order given.
         The threshold on `z` is the caller's."""
-        iq = _as_iq(iq).reshape(-1)
-        if coherent_ms >= 1 and n_blocks >= 1 and iq.size != n_streams * n_blocks * coherent_ms * self.n:
-            raise ValueError(f"expected {n_streams}*{n_blocks}*{coherent_ms}*{self.n} samples, got {iq.size}")
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        iq = _iq_arg(iq, (n_streams, n_blocks, coherent_ms, self.n), check=coherent_ms >= 1 and n_blocks >= 1)
+        ids = _ids(sat_ids)
         out = np.zeros(n_streams * len(ids), dtype=_lib.WEAK_RESULT)
         self._check(self.lib.gyp_acquire_weak(self.ctx, ptr(iq), n_streams, int(coherent_ms), int(n_blocks), int(flags), float(center_hz),
                                                float(spread_hz), float(fine_step_hz), ptr(ids), len(ids), ptr(out)))
@@ -703,7 +703,7 @@ class GypsumEngine:
     def acquire_weak_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, coherent_ms: int, n_blocks: int, flags: int,
                          sat_ids: Sequence[int], center_hz: float, spread_hz: float, fine_step_hz: float, out_ptr: int) -> None:
         """Device-pointer form: only enqueues on the engine's stream."""
-        ids = np.ascontiguousarray(sat_ids, dtype=np.int32)
+        ids = _ids(sat_ids)
         self._check(self.lib.gyp_acquire_weak_dev(self.ctx, C.c_void_p(iq_ptr), n_streams, stream_stride, int(coherent_ms), int(n_blocks), int(flags),
                                                    float(center_hz), float(spread_hz), float(fine_step_hz), ptr(ids), len(ids), C.c_void_p(out_ptr)))
 
@@ -724,9 +724,7 @@ class GypsumEngine:
     # ------------------------------------------------------------------ tracking
     def track_step(self, iq_1ms: np.ndarray, n_streams: int, start_times: Sequence[float], chans: np.ndarray,
                    want_profiles: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-        iq = _as_iq(iq_1ms).reshape(-1)
-        if iq.size != n_streams * self.n:
-            raise ValueError(f"expected {n_streams}*{self.n} samples, got {iq.size}")
+        iq = _iq_arg(iq_1ms, (n_streams, self.n))
         t0 = np.ascontiguousarray(start_times, dtype=np.float64)
         chans = np.ascontiguousarray(chans, dtype=CHAN_IN)
         out = np.zeros(len(chans), dtype=CHAN_OUT)
@@ -764,24 +762,25 @@ def weak_bit_sync(prompts: np.ndarray, first_ms: int) -> Tuple[np.ndarray, int]:
     return en, int(off[0])
 
 
-class WeakChannelBank:
-    """Device-resident weak-signal channels (gyp_weak_bank_*): 20-ms coherent loops behind an on-device bit synchronisation."""
+class _BankHandle:
+    """What the two kinds of bank share: the engine, the handle from `create(byref(handle))` and its destruction, the channel count and
+    the slot calls.  `_prefix` names the kind's entry points."""
+    _prefix = ""
 
-    def __init__(self, engine: "GypsumEngine", inits: np.ndarray, params=None, first_ms: int = 0) -> None:
+    def __init__(self, engine: "GypsumEngine", n_chan: int, create) -> None:
         self.engine = engine
         self.handle = None             # (a refused create raises below: close() must find the attribute)
-        inits = np.ascontiguousarray(inits, dtype=CHAN_INIT).reshape(-1)
-        if params is not None and not isinstance(params, np.ndarray):
-            params = params.record()
-        prm = None if params is None else np.ascontiguousarray(params, dtype=_lib.WEAK_PARAMS).reshape(-1)
         h = C.c_void_p()
-        engine._check(engine.lib.gyp_weak_bank_create(engine.ctx, ptr(inits) if inits.size else None, len(inits), ptr(prm), int(first_ms), C.byref(h)))
+        engine._check(create(C.byref(h)))
         self.handle = h
-        self.n_chan = len(inits)
+        self.n_chan = n_chan
+
+    def _entry(self, name: str):
+        return getattr(self.engine.lib, self._prefix + name)
 
     def close(self) -> None:
         if self.handle:
-            self.engine.lib.gyp_weak_bank_destroy(self.handle)
+            self._entry("destroy")(self.handle)
             self.handle = None
 
     def __del__(self) -> None:
@@ -789,6 +788,28 @@ class WeakChannelBank:
             self.close()
         except Exception:
             pass
+
+    def set_channel(self, index: int, init) -> None:
+        """(Re)start one slot from an acquisition result: fresh loop state and histories (a weak bank's slot in SYNC at the cursor)."""
+        one = np.zeros(1, dtype=CHAN_INIT)
+        one[0] = init
+        self.engine._check(self._entry("set_channel")(self.handle, int(index), ptr(one)))
+
+    def drop_channel(self, index: int) -> None:
+        self.engine._check(self._entry("drop_channel")(self.handle, int(index)))
+
+
+class WeakChannelBank(_BankHandle):
+    """Device-resident weak-signal channels (gyp_weak_bank_*): 20-ms coherent loops behind an on-device bit synchronisation."""
+    _prefix = "gyp_weak_bank_"
+
+    def __init__(self, engine: "GypsumEngine", inits: np.ndarray, params=None, first_ms: int = 0) -> None:
+        inits = np.ascontiguousarray(inits, dtype=CHAN_INIT).reshape(-1)
+        if params is not None and not isinstance(params, np.ndarray):
+            params = params.record()
+        prm = None if params is None else np.ascontiguousarray(params, dtype=_lib.WEAK_PARAMS).reshape(-1)
+        super().__init__(engine, len(inits), lambda out: engine.lib.gyp_weak_bank_create(engine.ctx, ptr(inits) if inits.size else None, len(inits), ptr(prm),
+                                                                                            int(first_ms), out))
 
     @staticmethod
     def max_periods(n_ms: int) -> int:
@@ -799,9 +820,7 @@ class WeakChannelBank:
         """Advance n_ms milliseconds from the cursor (first_ms must be it).  (WEAK_MS_REC[n_chan, n_ms] or None, a list with each
         channel's completed WEAK_PERIOD_REC records or None)."""
         e = self.engine
-        iq = _as_iq(iq).reshape(-1)
-        if n_ms >= 1 and iq.size != n_streams * n_ms * e.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{e.n} samples, got {iq.size}")
+        iq = _iq_arg(iq, (n_streams, n_ms, e.n), check=n_ms >= 1)
         ms = np.zeros((self.n_chan, max(n_ms, 0)), dtype=_lib.WEAK_MS_REC) if want_ms else None
         per = np.zeros((self.n_chan, self.max_periods(max(n_ms, 0))), dtype=_lib.WEAK_PERIOD_REC) if want_periods else None
         cnt = np.zeros(self.n_chan, dtype=np.int32)
@@ -814,15 +833,6 @@ class WeakChannelBank:
         e = self.engine
         e._check(e.lib.gyp_weak_track_block_dev(self.handle, C.c_void_p(iq_ptr or None), int(stream_stride), int(first_ms), int(n_ms),
                                                 C.c_void_p(ms_ptr or None), C.c_void_p(period_ptr or None), C.c_void_p(n_periods_ptr or None)))
-
-    def set_channel(self, index: int, init) -> None:
-        """(Re)start one slot in SYNC at the cursor from an acquisition result."""
-        one = np.zeros(1, dtype=CHAN_INIT)
-        one[0] = init
-        self.engine._check(self.engine.lib.gyp_weak_bank_set_channel(self.handle, int(index), ptr(one)))
-
-    def drop_channel(self, index: int) -> None:
-        self.engine._check(self.engine.lib.gyp_weak_bank_drop_channel(self.handle, int(index)))
 
     def set_state(self, index: int, f: float, f_int: float, u0: float, c0: int, edge: int) -> None:
         """Put one channel's full loop state; it tracks from the first millisecond m >= cursor with m % 20 == edge."""
@@ -842,23 +852,18 @@ class WeakChannelBank:
         return int(cur.value)
 
 
-class ChannelBank:
+class ChannelBank(_BankHandle):
     """Device-resident tracking channels (gyp_bank_*)."""
+    _prefix = "gyp_bank_"
 
     def __init__(self, engine: GypsumEngine, inits: np.ndarray) -> None:
-        self.engine = engine
         inits = np.ascontiguousarray(inits, dtype=CHAN_INIT)
-        h = C.c_void_p()
-        engine._check(engine.lib.gyp_bank_create(engine.ctx, ptr(inits), len(inits), C.byref(h)))
-        self.handle = h
-        self.n_chan = len(inits)
+        super().__init__(engine, len(inits), lambda out: engine.lib.gyp_bank_create(engine.ctx, ptr(inits), len(inits), out))
 
     def track_block(self, iq: np.ndarray, n_streams: int, n_ms: int, start_times: Sequence[float],
                     want_records: bool = True) -> Optional[np.ndarray]:
         e = self.engine
-        iq = _as_iq(iq).reshape(-1)
-        if iq.size != n_streams * n_ms * e.n:
-            raise ValueError(f"expected {n_streams}*{n_ms}*{e.n} samples, got {iq.size}")
+        iq = _iq_arg(iq, (n_streams, n_ms, e.n))
         t0 = np.ascontiguousarray(start_times, dtype=np.float64)
         if len(t0) != n_ms:
             raise ValueError("one start time per millisecond expected")
@@ -876,15 +881,6 @@ class ChannelBank:
         gyp_quality_sums per (channel, window) into out_ptr, on the same stream behind the tracking kernels.  Not synchronised."""
         self.engine.track_quality_dev(rec_ptr, self.n_chan, n_ms if chan_stride is None else chan_stride, n_ms, window_ms, out_ptr,
                                       bit_offsets)
-
-    def set_channel(self, index: int, init) -> None:
-        """(Re)start one slot from an acquisition result (fresh loop state and histories)."""
-        one = np.zeros(1, dtype=CHAN_INIT)
-        one[0] = init
-        self.engine._check(self.engine.lib.gyp_bank_set_channel(self.handle, int(index), ptr(one)))
-
-    def drop_channel(self, index: int) -> None:
-        self.engine._check(self.engine.lib.gyp_bank_drop_channel(self.handle, int(index)))
 
     def reset_dev(self, inits_ptr: int) -> None:
         self.engine._check(self.engine.lib.gyp_bank_reset_dev(self.handle, C.c_void_p(inits_ptr)))
@@ -923,17 +919,6 @@ class ChannelBank:
         out = np.zeros((self.n_chan, int(n_ms)), dtype=np.float64)
         self.engine._check(self.engine.lib.gyp_debug_disc_read(self.handle, int(n_ms), _lib.ptr(out)))
         return out
-
-    def close(self) -> None:
-        if getattr(self, "handle", None) is not None and self.handle.value:
-            self.engine.lib.gyp_bank_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default_engines: Dict[Tuple[int, int, int], GypsumEngine] = {}

@@ -958,6 +958,182 @@ static void dev_mem() {
     }
 }
 
+// --------------------------------------------------------------------------------------------------------- hybrid-plan
+// plans.i64 rows in: n, n_cells, scratch_mb, flags, coherent_ms, n_blocks -> out: HybPlan's members in their order.  bins.f64 rows in:
+// coherent_ms, center, spread, step -> bins.i64 out: hybrid_coarse_bins, hybrid_fine_half, the bits of the first and of the last coarse
+// bin.  shifts.f64 rows in: n, coherent_ms, block, doppler, flags -> shifts.i64.  zs.f64 rows in: peak, n_off, sum_off, sumsq_off ->
+// zs.f64 out.  searches.f64 rows in: n, n_streams, n_sats, coherent_ms, n_blocks, flags, center, spread, step, scratch_mb ->
+// searches.i64 out: WeakSearchPlan's members and its run plan's; searches.txt: the refusal, or "ok".
+static void put_plan(std::vector<int64_t>& o, const HybPlan& pl) {
+    for (int64_t v : {(int64_t)pl.fits, (int64_t)pl.n_sets, (int64_t)pl.chunk_cells, (int64_t)pl.n_chunks, (int64_t)pl.profile, (int64_t)pl.power, (int64_t)pl.acc_x}) o.push_back(v);
+}
+static void hybrid_plans() {
+    std::vector<int64_t> o;
+    const std::vector<int64_t> shapes = read_array<int64_t>("plans.i64");
+    REQUIRE(shapes.size() % 6 == 0);
+    for (size_t r = 0; r * 6 < shapes.size(); ++r) {
+        const int64_t* s = &shapes[r * 6];
+        put_plan(o, hybrid_plan(HybShape{(int)s[0], s[1], (int)s[4], (int)s[5], (int)s[3]}, (int)s[2]));
+    }
+    Out("plans.i64").bytes(o.data(), o.size() * sizeof(int64_t));
+    o.clear();
+    const std::vector<double> bins = read_array<double>("bins.f64");
+    for (size_t r = 0; r * 4 < bins.size(); ++r) {
+        const double* b = &bins[r * 4];
+        const int T = (int)b[0], n = hybrid_coarse_bins(b[1], b[2], T);
+        const double first = hybrid_coarse_bin(b[1], b[2], T, 0), last = hybrid_coarse_bin(b[1], b[2], T, std::max(n - 1, 0));
+        int64_t bits[2];
+        std::memcpy(&bits[0], &first, 8);
+        std::memcpy(&bits[1], &last, 8);
+        for (int64_t v : {(int64_t)n, (int64_t)hybrid_fine_half(b[3], T), bits[0], bits[1]}) o.push_back(v);
+    }
+    Out("bins.i64").bytes(o.data(), o.size() * sizeof(int64_t));
+    o.clear();
+    const std::vector<double> shifts = read_array<double>("shifts.f64");
+    for (size_t r = 0; r * 5 < shifts.size(); ++r) {
+        const double* s = &shifts[r * 5];
+        o.push_back(hybrid_shift((int32_t)s[0], (int32_t)s[1], (int32_t)s[2], s[3], (int32_t)s[4]));
+        REQUIRE(gyp_hybrid_shift((int32_t)s[0], (int32_t)s[1], (int32_t)s[2], s[3], (int32_t)s[4]) == o.back());
+    }
+    Out("shifts.i64").bytes(o.data(), o.size() * sizeof(int64_t));
+    o.clear();
+    const std::vector<double> zs = read_array<double>("zs.f64");
+    Out z_out("zs.f64");
+    for (size_t r = 0; r * 4 < zs.size(); ++r) {
+        gyp_hybrid_cell* c = (gyp_hybrid_cell*)std::calloc(1, sizeof(gyp_hybrid_cell));
+        c->peak = (float)zs[r * 4]; c->n_off = (int32_t)zs[r * 4 + 1]; c->sum_off = zs[r * 4 + 2]; c->sumsq_off = zs[r * 4 + 3];
+        double z = -777.0;
+        REQUIRE(gyp_hybrid_stats(c, &z, nullptr) == GYP_OK);
+        z_out.put(z);
+        z_out.put((double)hybrid_pick_set(zs[r * 4 + 2], zs[r * 4 + 3]));   // (any two numbers of the row: the NaNs and the ties are among them)
+        std::free(c);
+    }
+    const std::vector<double> searches = read_array<double>("searches.f64");
+    Out why("searches.txt");
+    for (size_t r = 0; r * 10 < searches.size(); ++r) {
+        const double* s = &searches[r * 10];
+        const WeakSearchPlan pl = weak_search_plan(WeakSearchShape{(int)s[0], (int)s[1], (int)s[2], (int)s[3], (int)s[4], (int)s[5], s[6], s[7], s[8]}, (int)s[9]);
+        why.line(pl.refusal ? pl.refusal : "ok");
+        for (int64_t v : {(int64_t)pl.n_coarse, (int64_t)pl.fine_half, (int64_t)pl.n_fine, pl.n_states, (int64_t)pl.coarse_cells, (int64_t)pl.fine_cells, (int64_t)pl.level_cells,
+                          (int64_t)pl.records})
+            o.push_back(v);
+        put_plan(o, pl.run);
+    }
+    Out("searches.i64").bytes(o.data(), o.size() * sizeof(int64_t));
+    {   // the plan's refusals reach the caller before anything is planned into the context, reserved or launched (a stream format by hand: no tables)
+        gyp_ctx ctx;
+        ctx.fs = 2046000; ctx.n = 2046; ctx.k = 2;
+        float iq = 0.0f;
+        gyp_weak_result res{};
+        const std::vector<int32_t> sats(33, 1);
+        auto refused = [&](int rc, const char* text) { return rc == GYP_E_BAD_ARG && std::string(gyp_last_error(&ctx)) == text && !ctx.last_hybrid_plan.fits && ctx.last_hybrid_plan.n_chunks == 0; };
+        REQUIRE(refused(gyp_acquire_weak_dev(&ctx, &iq, 1, 2046, 1, 1, 0, 0.0, 1024250.0, 0.0, sats.data(), 1, &res), "gyp_acquire_weak_dev: a level must have between 1 and 4096 Doppler bins"));
+        REQUIRE(refused(gyp_acquire_weak_dev(&ctx, &iq, 16385, 2046, 1, 1, 0, 0.0, 1024000.0, 0.0, sats.data(), 32, &res), "gyp_acquire_weak_dev: more than 2^31 - 1 cells"));
+        REQUIRE(refused(gyp_acquire_weak_dev(&ctx, &iq, 1, 2046, 1, 1, 0, 0.0, 500.0, 0.0, sats.data(), 33, &res), "gyp_acquire_weak_dev: at most 32 satellites per call"));
+        REQUIRE(refused(gyp_acquire_weak_dev(&ctx, &iq, 1, 2046, 1, 1, 0, 0.0, 0.0, 0.0, sats.data(), 1, &res), "gyp_acquire_weak_dev: center, spread and fine step must be finite and the spread positive"));
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- weak-plan
+// params.bin: gyp_weak_params records; inits.bin: gyp_chan_init records -> refusals.txt: a line each ("ok" where it is taken).
+// fresh.i64 rows: n, cursor, then inits_fresh.bin's record of the same index -> fresh.bin: WeakChan records.  rates.f64 rows: f, n ->
+// rates.i64.  advances.f64 rows: u0, f, fs and advances.i64 rows: c0, samples, r -> advanced.f64 (u0) and advanced.i64 (c0, and
+// weak_mod_code of the row's c0).  sync.f32: rows of 40 prompts (re, im), sync.i64: the first_ms values -> sync.f64: per row and first_ms
+// 20 energies and the pick.  loop.f32 rows: 26 x 20 milliseconds of m_re, m_im, p_re, p_im, l_re, l_im; loop.f64: f, u0, fs, pll_bw_hz, dll_bw_hz, lose_mu;
+// loop.i64: c0, n, period_first -> periods.bin: 26 gyp_weak_period_rec records, chan.bin: the final WeakChan.
+static void weak_plans() {
+    {
+        Out o("refusals.txt");
+        const std::vector<uint8_t> prm = read_bytes("params.bin"), inits = read_bytes("inits.bin");
+        for (size_t at = 0; at + sizeof(gyp_weak_params) <= prm.size(); at += sizeof(gyp_weak_params)) {
+            gyp_weak_params* p = (gyp_weak_params*)std::malloc(sizeof(gyp_weak_params));
+            std::memcpy(p, &prm[at], sizeof(*p));
+            const char* why = weak_params_refusal(*p);
+            o.line(why ? why : "ok");
+            std::free(p);
+        }
+        for (size_t at = 0; at + sizeof(gyp_chan_init) <= inits.size(); at += sizeof(gyp_chan_init)) {
+            gyp_chan_init* in = (gyp_chan_init*)std::malloc(sizeof(gyp_chan_init));
+            std::memcpy(in, &inits[at], sizeof(*in));
+            const char* why = weak_init_refusal(*in);
+            o.line(why ? why : "ok");
+            std::free(in);
+        }
+        const gyp_weak_params def = weak_params_default();
+        REQUIRE(weak_params_refusal(def) == nullptr);
+        Out("default.bin").put(def);
+    }
+    {
+        const std::vector<int64_t> rows = read_array<int64_t>("fresh.i64");
+        const std::vector<uint8_t> inits = read_bytes("inits_fresh.bin");
+        REQUIRE(inits.size() == rows.size() / 2 * sizeof(gyp_chan_init));
+        Out o("fresh.bin");
+        for (size_t r = 0; r * 2 < rows.size(); ++r) {
+            gyp_chan_init in;
+            std::memcpy(&in, &inits[r * sizeof(in)], sizeof(in));
+            o.put(weak_fresh_chan(in, (int32_t)rows[2 * r], rows[2 * r + 1]));
+        }
+    }
+    {
+        const std::vector<double> rates = read_array<double>("rates.f64"), adv = read_array<double>("advances.f64");
+        const std::vector<int64_t> adv_i = read_array<int64_t>("advances.i64");
+        Out ro("rates.i64"), af("advanced.f64"), ai("advanced.i64");
+        for (size_t r = 0; r * 2 < rates.size(); ++r) ro.i64(weak_code_rate(rates[2 * r], (int32_t)rates[2 * r + 1]));
+        REQUIRE(adv.size() == adv_i.size());
+        for (size_t r = 0; r * 3 < adv.size(); ++r) {
+            double u0 = adv[3 * r];
+            int64_t c0 = weak_mod_code(adv_i[3 * r]);
+            ai.i64(c0);
+            weak_advance(&u0, &c0, adv[3 * r + 1], adv[3 * r + 2], adv_i[3 * r + 1], adv_i[3 * r + 2]);
+            af.put(u0);
+            ai.i64(c0);
+        }
+    }
+    {
+        const std::vector<float> prompts = read_array<float>("sync.f32");
+        const std::vector<int64_t> firsts = read_array<int64_t>("sync.i64");
+        const int32_t n_ms = 40;
+        REQUIRE(prompts.size() % (2 * n_ms) == 0);
+        float* p = (float*)std::malloc(2 * n_ms * sizeof(float));   // exactly n_ms prompts: a read one past is a report
+        Out o("sync.f64");
+        for (size_t row = 0; row * 2 * n_ms < prompts.size(); ++row) {
+            std::memcpy(p, &prompts[row * 2 * n_ms], 2 * n_ms * sizeof(float));
+            for (int64_t first : firsts) {
+                double en[kWeakPeriodMs], api[kWeakPeriodMs];
+                int32_t pick = -1;
+                for (int k = 0; k < kWeakPeriodMs; ++k) o.put(en[k] = weak_bit_energy(p, n_ms, first, k));
+                o.put((double)weak_bit_pick(en));
+                REQUIRE(gyp_weak_bit_sync(p, n_ms, first, api, &pick) == GYP_OK && std::memcmp(api, en, sizeof(en)) == 0 && pick == weak_bit_pick(en));
+            }
+        }
+        std::free(p);
+    }
+    {
+        const std::vector<float> ms = read_array<float>("loop.f32");
+        const std::vector<double> d = read_array<double>("loop.f64");
+        const std::vector<int64_t> k = read_array<int64_t>("loop.i64");
+        REQUIRE(ms.size() % (6 * kWeakPeriodMs) == 0 && d.size() == 6 && k.size() == 3);
+        gyp_weak_params prm = weak_params_default();
+        prm.pll_bw_hz = d[3]; prm.dll_bw_hz = d[4]; prm.lose_mu = d[5];
+        WeakChan* s = (WeakChan*)std::calloc(1, sizeof(WeakChan));
+        s->phase = kWeakTrack; s->f = s->f_int = d[0]; s->u0 = d[1]; s->c0 = k[0];
+        Out periods("periods.bin");
+        for (size_t period = 0; period * 6 * kWeakPeriodMs < ms.size(); ++period) {
+            s->period_first = k[2] + (int64_t)period * kWeakPeriodMs;
+            for (int i = 0; i < kWeakPeriodMs; ++i) {
+                const float* m = &ms[(period * kWeakPeriodMs + i) * 6];
+                weak_fold_ms(s, m[0], m[1], m[2], m[3], m[4], m[5]);
+                s->pos += 1;
+            }
+            gyp_weak_period_rec rec;
+            weak_close_period(s, prm, d[2], (int32_t)k[1], &rec);
+            periods.put(rec);
+        }
+        Out("chan.bin").bytes(s, sizeof(WeakChan));
+        std::free(s);
+    }
+}
+
 }  // namespace drv
 
 int main(int argc, char** argv) {
@@ -979,7 +1155,8 @@ int main(int argc, char** argv) {
         {"ingest-host", drv::ingest_host}, {"ingest-races", drv::ingest_races}, {"bits", drv::bits}, {"spans", drv::spans},
         {"designs", drv::designs}, {"misc", drv::misc}, {"halo-readers", drv::halo_readers}, {"small-parsers", drv::small_parsers},
         {"grid-plan", drv::grid_plans}, {"track-plan", drv::track_plans}, {"acq-plan", drv::acq_plans}, {"resample-plan", drv::resample_plans},
-        {"cond-plan", drv::cond_plans}, {"cond-chain", drv::cond_chain}, {"dev-mem", drv::dev_mem},
+        {"cond-plan", drv::cond_plans}, {"cond-chain", drv::cond_chain}, {"dev-mem", drv::dev_mem}, {"hybrid-plan", drv::hybrid_plans},
+        {"weak-plan", drv::weak_plans},
     };
     for (const auto& s : table)
         if (std::string(argv[1]) == s.first) {

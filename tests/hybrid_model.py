@@ -173,6 +173,80 @@ def fine_bins(best: float, step: float, T: int) -> List[float]:
     return [best + float(j) * step for j in range(-J, J + 1)]
 
 
+def n_coarse(center: float, spread: float, T: int) -> int:
+    """hybrid_coarse_bins: len(coarse_bins(...)), with the loop's cap of 1,000,000 (the bins are monotone in i, so the count of a
+    prefix is the position of the first bin that is not below center + spread)."""
+    i = np.arange(1_000_000, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        below = np.float64(center) - np.float64(spread) + i * (np.float64(500.0) / np.float64(T)) < np.float64(center) + np.float64(spread)
+    return len(below) if below.all() else int(np.argmin(below))
+
+
+def fine_half(step: float, T: int) -> int:
+    """hybrid_fine_half: J of fine_bins, with the loop's cap of 500,000; -1 where there is no fine level."""
+    if not step > 0:
+        return -1
+    j = np.arange(1, 500_001, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        within = j * np.float64(step) <= np.float64(250.0) / np.float64(T)
+    return len(within) if within.all() else int(np.argmin(within))
+
+
+def refusal(T: int, M: int, flags: int) -> Optional[str]:
+    """hybrid_refusal: why a request is refused, in the header's order."""
+    if not 1 <= T <= 20:
+        return "coherent_ms must be 1..20"
+    if M < 1:
+        return "n_blocks must be at least 1"
+    if M * T > 65535:
+        return "n_blocks * coherent_ms must be at most 65535"
+    if flags & ~3:
+        return "unknown flag bits"
+    if flags & ALTERNATE and M < 2:
+        return "GYP_HYB_ALTERNATE needs at least 2 blocks"
+    return None
+
+
+PLAN_FIELDS = ("fits", "n_sets", "chunk_cells", "n_chunks", "profile", "power", "acc_x")
+
+
+def plan(n: int, n_cells: int, T: int, M: int, flags: int, scratch_mb: int) -> Tuple[int, ...]:
+    """hybrid_plan, the chunk rule restated: a cell holds a float2 profile row and n_sets float power rows of n samples; a chunk has
+    as many cells as fit the budget, at least 1, at most 65535 (the accumulate kernel's grid.y) and no more than there are."""
+    if refusal(T, M, flags) or not 1 <= n_cells <= 2 ** 31 - 1 or n < 1:
+        return (0,) * len(PLAN_FIELDS)
+    n_sets = 2 if flags & ALTERNATE else 1
+    room = max(1, (scratch_mb << 20) // (n * (8 + 4 * n_sets)))
+    chunk = min(n_cells, room, 65535)
+    return (1, n_sets, chunk, -(-n_cells // chunk), chunk * n, chunk * n * n_sets, -(-n // 256))
+
+
+SEARCH_FIELDS = ("n_coarse", "fine_half", "n_fine", "n_states", "coarse_cells", "fine_cells", "level_cells", "records") + tuple("run_" + f for f in PLAN_FIELDS)
+
+
+def weak_search_plan(n: int, n_streams: int, n_sats: int, T: int, M: int, flags: int, center: float, spread: float, step: float,
+                     scratch_mb: int) -> Tuple[Optional[str], Tuple[int, ...]]:
+    """gyp_acquire_weak_dev's arithmetic behind its pointer and satellite-id checks, as it stood inline: (why it is refused or None,
+    SEARCH_FIELDS -- all 0 when refused)."""
+    none = (0,) * len(SEARCH_FIELDS)
+    why = refusal(T, M, flags)
+    if why:
+        return why, none
+    if n_sats > 32:
+        return "at most 32 satellites per call", none
+    if not (math.isfinite(center) and math.isfinite(spread) and math.isfinite(step)) or not spread > 0.0:
+        return "center, spread and fine step must be finite and the spread positive", none
+    coarse, half = n_coarse(center, spread, T), fine_half(step, T)
+    fine = 2 * half + 1 if half >= 0 else 0
+    if coarse < 1 or coarse > 4096 or fine > 4096:
+        return "a level must have between 1 and 4096 Doppler bins", none
+    states = n_streams * n_sats
+    if states * max(coarse, fine) > 2 ** 31 - 1:
+        return "more than 2^31 - 1 cells", none
+    cc, fc = states * coarse, states * fine
+    return None, (coarse, half, fine, states, cc, fc, cc + fc + states, max(cc, fc)) + plan(n, max(cc, fc), T, M, flags, scratch_mb)
+
+
 @dataclass
 class WeakResult:
     sat_id: int

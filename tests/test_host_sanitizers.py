@@ -1,4 +1,4 @@
-"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, resample_plan.hpp, cond_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
+"""The host C++ of libgypsum_hip (gypsum_hip.hip, ingest.hpp, bit_integrator.hpp, grid_plan.hpp, track_plan.hpp, acq_plan.hpp, resample_plan.hpp, cond_plan.hpp, hybrid_plan.hpp, weak_plan.hpp, dev_mem.hpp) under ASan + UBSan and under TSan.
 
 tests/host_san/driver.cpp is one translation unit with the product and has its own main; tests/host_san_build.py compiles it twice
 (about 37 s for both, side by side; cached by content afterwards).  Each scenario below is one fresh child process that can see no
@@ -1056,7 +1056,7 @@ def test_cond_chain(programs, tmp_path, which):
 CARVE_LITERALS = [0, 1792, 2016, 2240, 2464, 2468, 2472, 2528,
                   0, 16, 28, 40, 124,
                   0, 20, 244, 468, 484]
-INHERITED_SWITCHES = {"no_pipe", "no_shared_fwd", "no_acq_shared_fwd", "symbol_tau", "cells_cu_reserve", "track_chunk_ms", "no_spec"}
+INHERITED_SWITCHES = {"no_pipe", "no_shared_fwd", "no_acq_shared_fwd", "symbol_tau", "cells_cu_reserve", "track_chunk_ms", "no_spec", "track_finish_all"}
 
 
 @pytest.mark.parametrize("which", BOTH)
@@ -1069,7 +1069,7 @@ def test_dev_mem(programs, tmp_path, which):
     assert np.fromfile(out / "carve.i64", dtype="<i8").tolist() == CARVE_LITERALS
     rows = [line.split() for line in (out / "switches.txt").read_text().splitlines()]
     names = [r[0] for r in rows]
-    assert len(rows) == 21 and len(set(names)) == len(names)
+    assert len(rows) == 24 and len(set(names)) == len(names)
     for name, lo, hi, integral, inherited, default in rows:
         assert float(lo) <= float(default) <= float(hi), name
     assert {r[0] for r in rows if r[4] == "1"} == INHERITED_SWITCHES
@@ -1077,3 +1077,221 @@ def test_dev_mem(programs, tmp_path, which):
     assert [float(x) for x in by_name["grid_fused_waves"][1:3]] == [8.0, 12.0] and float(by_name["grid_fused_waves"][5]) == 12.0
     assert [float(x) for x in by_name["track_chunk_ms"][1:3]] == [0.0, 1e6] and float(by_name["track_chunk_ms"][5]) == 250.0
     assert by_name["symbol_tau"][3] == "0" and by_name["dll_prov_bias"][3] == "0" and sum(r[3] == "0" for r in rows) == 2
+    assert [float(x) for x in by_name["hybrid_scratch_mb"][1:3]] == [16.0, 65536.0] and float(by_name["hybrid_scratch_mb"][5]) == 1024.0
+    for name in ("notch_no_lds", "track_finish_all"):
+        assert [float(x) for x in by_name[name][1:3]] == [0.0, 1.0] and by_name[name][3] == "1" and float(by_name[name][5]) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------ hybrid-plan
+def f64(rows) -> np.ndarray:
+    return np.array(rows, dtype="<f8")
+
+
+def search_rows():
+    """(n, n_streams, n_sats, T, blocks, flags, center, spread, step, scratch_mb) of the weak_search_plan rows: per T the coarse level at
+    1, 4096 and 4097 bins (bins every 500 / T Hz over [-spread, spread)) crossed with the fine level at 0, 1, 4095 and 4097 bins (2 J + 1
+    with J steps within 250 / T Hz); states x bins on both sides of 2^31 - 1; 32 and 33 satellites; and a row per refusal in front."""
+    rows = []
+    for T in (1, 2, 20):
+        bin_hz, half_hz = 500.0 / T, 250.0 / T
+        for spread in (bin_hz / 2, 2048 * bin_hz, 2048.5 * bin_hz):
+            for step in (0.0, 2 * half_hz, half_hz / 2047.5, half_hz / 2048):
+                rows.append((2046, 2, 3, T, 4, 3, 100.0, spread, step, 16))
+        # 4096 coarse bins: 524287 x 4096 = 2^31 - 4096, 524288 x 4096 = 2^31
+        rows += [(2046, ns, sats, T, 1, 0, 0.0, 2048 * bin_hz, 0.0, 1024) for ns, sats in ((524287, 1), (524288, 1), (16383, 32), (16384, 32), (16384, 33))]
+        rows += [(2046, 1, sats, T, 2, 1, 0.0, 7000.0, 10.0, 1024) for sats in (32, 33)]
+    nan, inf = float("nan"), float("inf")
+    rows += [(2046, 1, 1, T, M, flags, 0.0, 500.0, 0.0, 1024) for T, M, flags in ((0, 1, 0), (21, 1, 0), (1, 0, 0), (16, 4096, 0), (1, 2, 4), (1, 1, 1), (0, 0, 4))]
+    rows += [(2046, 1, 1, 1, 1, 0, c, s, f, 1024) for c, s, f in ((nan, 500.0, 0.0), (inf, 500.0, 0.0), (0.0, nan, 0.0), (0.0, inf, 0.0), (0.0, 500.0, nan),
+                                                                  (0.0, 500.0, -inf), (0.0, 0.0, 0.0), (0.0, -1.0, 0.0), (1e300, 1.0, 0.0), (0.0, 500.0, -1.0))]
+    rows += [(2046, 1, 33, 1, 1, 0, nan, 500.0, 0.0, 1024), (2046, 1, 1, 1, 1, 0, 0.0, 0.0, 250.0 / 2048, 1024), (49104, 4, 8, 20, 3, 3, -3000.0, 7000.0, 1.0, 16)]
+    return rows
+
+
+@pytest.mark.parametrize("which", BOTH)
+def test_hybrid_plan(programs, tmp_path, which):
+    """hybrid_plan, hybrid_coarse_bins / hybrid_coarse_bin / hybrid_fine_half, hybrid_shift, hybrid_z and weak_search_plan
+    (csrc/hybrid_plan.hpp) against tests/hybrid_model.py, every comparison exact: the model restates the same integer and float64
+    operations.  The scenario also checks on a context on the stack that gyp_acquire_weak_dev refuses with the plan's texts before
+    anything is planned into the context."""
+    import hybrid_model as hm
+
+    d = indir(tmp_path)
+    plans = [(n, cells, mb, flags, T, M) for n in (1023, 2046, 49104) for cells in (0, 1, 2, 511, 512, 513, 65535, 65536, 2 ** 31 - 1, 2 ** 31)
+             for mb in (16, 1024, 65536) for flags in (0, 1, 2, 3, 4) for T, M in ((1, 1), (20, 1), (2, 4), (21, 1), (1, 65536))]
+    i64(plans).tofile(d / "plans.i64")
+    bins = []
+    for T in (1, 2, 10, 20):
+        edge = 250.0 / T
+        for spread in (np.nextafter(edge, 0.0), edge, 7000.0, 1e9):
+            for step in (0.0, -1.0, float("nan"), 1e-9, 10.0, edge, np.nextafter(edge, np.inf)):
+                bins.append((T, 0.0, spread, step))
+                bins.append((T, -4321.5, spread, step))
+    f64(bins).tofile(d / "bins.f64")
+    shifts = [(n, T, b, sign * f, flags) for n, T, b in ((1023, 1, 1), (2046, 10, 21), (2046, 20, 3276), (8184, 4, 1000), (49104, 1, 65535), (2046, 1, 0))
+              for f in (0.0, 1.0, 4487.0, 7000.0, 200000.0, 770000.0, np.nextafter(770000.0, 0.0), 1e300, float("inf"), float("nan")) for sign in (1.0, -1.0)
+              for flags in (0, 1, 2, 3)]
+    from fractions import Fraction
+    for n, T, b in ((1023, 1, 1), (2046, 1, 1), (1023, 4, 4), (2046, 4, 2), (1023, 10, 1), (8184, 1, 2), (2046, 10, 1)):      # exact halves (test_hybrid_host.py)
+        for k in (0, 1, 7, 3000):
+            exact = Fraction((2 * k + 1) * 1575420000, 2 * b * T * n)
+            if Fraction(float(exact)) == exact:
+                shifts += [(n, T, b, sign * f, 2) for f in (float(exact), np.nextafter(float(exact), 0.0), np.nextafter(float(exact), np.inf)) for sign in (1.0, -1.0)]
+    halves = len(shifts) - 6 * 10 * 2 * 4
+    assert halves >= 6 * 20
+    f64(shifts).tofile(d / "shifts.f64")
+    zs = [(5.0, 0, 0.0, 0.0), (5.0, -1, 1.0, 1.0), (5.0, 100, 200.0, 400.0), (5.0, 3, 0.3, 0.03 * (1 - 1e-15)), (4.0, 4, 4.0, 8.0), (1.0, 10, 1.0, 1.0),
+          (0.0, 10, 1.0, 1.0), (7.5, 2045, 3.25e3, 9.5e3), (float("inf"), 10, 1.0, 2.0), (1.0, 10, float("nan"), 1.0), (1.0, 10, 1.0, float("nan")),
+          (3.0, 2 ** 31 - 1, 1e9, 1e10), (2.0, 7, 2.0, 2.0)]
+    f64(zs).tofile(d / "zs.f64")
+    searches = search_rows()
+    f64(searches).tofile(d / "searches.f64")
+
+    out = run(programs, which, "hybrid-plan", tmp_path)
+    got = np.fromfile(out / "plans.i64", dtype="<i8").reshape(len(plans), len(hm.PLAN_FIELDS)).tolist()
+    for (n, cells, mb, flags, T, M), row in zip(plans, got):
+        assert tuple(row) == hm.plan(n, cells, T, M, flags, mb), (n, cells, mb, flags, T, M)
+    fits = {p[:6]: r[0] for p, r in zip(plans, got)}
+    assert fits[2046, 1, 16, 3, 2, 4] == 1 and fits[2046, 0, 16, 0, 1, 1] == 0 and fits[2046, 2 ** 31, 16, 0, 1, 1] == 0 and fits[2046, 1, 16, 4, 1, 1] == 0
+    by_shape = {p: dict(zip(hm.PLAN_FIELDS, r)) for p, r in zip(plans, got)}
+    assert by_shape[2046, 513, 16, 3, 2, 4]["chunk_cells"] == 512 and by_shape[2046, 513, 16, 3, 2, 4]["n_chunks"] == 2      # 16 MiB / 32736 bytes
+    assert by_shape[1023, 2 ** 31 - 1, 65536, 0, 1, 1]["chunk_cells"] == 65535 and by_shape[49104, 65536, 16, 1, 2, 4]["chunk_cells"] == 21
+    got = np.fromfile(out / "bins.i64", dtype="<i8").reshape(len(bins), 4).tolist()
+    for (T, center, spread, step), (n_coarse, half, first, last) in zip(bins, got):
+        assert n_coarse == hm.n_coarse(center, spread, T) and half == hm.fine_half(step, T), (T, center, spread, step)
+        assert first == f64([center - spread]).view("<i8")[0] and last == f64([center - spread + float(max(n_coarse - 1, 0)) * (500.0 / T)]).view("<i8")[0]
+        if n_coarse < 1000:      # the lists the model's search walks, where they are short
+            assert n_coarse == len(hm.coarse_bins(center, spread, T))
+        if 0 <= half < 1000:
+            assert 2 * half + 1 == len(hm.fine_bins(0.0, step, T))
+        elif half < 0:
+            assert hm.fine_bins(0.0, step, T) == []
+    seen = {(r[0], r[1]) for r in got}
+    assert {n for n, _ in seen} >= {1, 28, 560, 1_000_000} and {h for _, h in seen} >= {-1, 0, 1, 500_000}      # both caps, both edges
+    got = np.fromfile(out / "shifts.i64", dtype="<i8").tolist()
+    assert got == [hm.shift(n, T, b, f, flags) if np.isfinite(f) and abs(float(b * T * n) * f / hm.L1_HZ) < 2147483000.0 else 0 for n, T, b, f, flags in shifts]
+    assert min(got) < -1000 and max(got) > 1000
+    got = np.fromfile(out / "zs.f64", dtype="<f8").reshape(len(zs), 2)
+    want = f64([(hm.z_of(float(np.float32(peak)), n_off, s, ss), 1.0 if ss > s else 0.0) for peak, n_off, s, ss in zs])
+    assert got.tobytes() == want.tobytes() and np.isnan(got[:4, 0]).all() and got[4, 0] == 3.0
+    why = (out / "searches.txt").read_text().splitlines()
+    got = np.fromfile(out / "searches.i64", dtype="<i8").reshape(len(searches), len(hm.SEARCH_FIELDS)).tolist()
+    for shape, text, row in zip(searches, why, got):
+        n, ns, sats, T, M, flags, center, spread, step, mb = shape
+        want_why, want_row = hm.weak_search_plan(n, ns, sats, T, M, flags, center, spread, step, mb)
+        assert text == (want_why or "ok") and tuple(row) == want_row, shape
+    assert set(why) == {"ok", "coherent_ms must be 1..20", "n_blocks must be at least 1", "n_blocks * coherent_ms must be at most 65535", "unknown flag bits",
+                        "GYP_HYB_ALTERNATE needs at least 2 blocks", "at most 32 satellites per call",
+                        "center, spread and fine step must be finite and the spread positive", "a level must have between 1 and 4096 Doppler bins",
+                        "more than 2^31 - 1 cells"}
+    ok = [dict(zip(hm.SEARCH_FIELDS, r)) for r, t in zip(got, why) if t == "ok"]
+    assert {p["n_coarse"] for p in ok} >= {1, 4096} and {p["n_fine"] for p in ok} >= {0, 1, 4095} and max(p["records"] for p in ok) == 2 ** 31 - 4096
+    assert all(p["run_fits"] == 1 and p["level_cells"] == p["coarse_cells"] + p["fine_cells"] + p["n_states"] for p in ok)
+
+
+# ------------------------------------------------------------------------------------------------------------ weak-plan
+@pytest.mark.parametrize("which", BOTH)
+def test_weak_plan(programs, tmp_path, which):
+    """The host copy of the weak bank's arithmetic (csrc/weak_plan.hpp) against tests/weak_track_model.py, every comparison exact:
+    the refusals, a channel's start-up, the code rate and the NCO advances, the bit-edge energies, and weak_fold_ms + weak_close_period
+    over 26 periods of fixed prompts -- the 25-entry mu ring wraps once and lose_mu trips."""
+    import weak_track_model as wm
+
+    d = indir(tmp_path)
+    lib = _lib.load()
+    default = np.zeros(1, dtype=_lib.WEAK_PARAMS)
+    lib.gyp_weak_params_default(_lib.ptr(default))
+    up, down = (lambda x: float(np.nextafter(x, np.inf))), (lambda x: float(np.nextafter(x, -np.inf)))
+    edges = [{}, dict(period_ms=19), dict(period_ms=21), dict(sync_ms=39), dict(sync_ms=40), dict(sync_ms=2000), dict(sync_ms=2001), dict(spacing=0),
+             dict(spacing=1), dict(spacing=wm.ONE), dict(spacing=wm.ONE + 1), dict(pll_bw_hz=0.0), dict(pll_bw_hz=up(0.0)), dict(pll_bw_hz=50.0),
+             dict(pll_bw_hz=up(50.0)), dict(pll_bw_hz=float("nan")), dict(dll_bw_hz=0.0), dict(dll_bw_hz=up(0.0)), dict(dll_bw_hz=10.0),
+             dict(dll_bw_hz=up(10.0)), dict(dll_bw_hz=float("nan")), dict(lose_mu=down(0.0)), dict(lose_mu=0.0), dict(lose_mu=20.0), dict(lose_mu=up(20.0)),
+             dict(lose_mu=float("nan")), dict(period_ms=10, sync_ms=39), dict(sync_ms=39, spacing=0), dict(spacing=0, pll_bw_hz=0.0),
+             dict(pll_bw_hz=0.0, dll_bw_hz=0.0), dict(dll_bw_hz=0.0, lose_mu=21.0)]
+    params = np.repeat(default, len(edges))
+    for rec, change in zip(params, edges):
+        for k, v in change.items():
+            rec[k] = v
+    params.tofile(d / "params.bin")
+    init_rows = [(0, 1, 0.0, 0.0), (-1, 1, 0.0, 0.0), (0, 0, 0.0, 0.0), (0, 32, 0.0, 0.0), (0, 33, 0.0, 0.0), (0, 1, float("nan"), 0.0), (0, 1, float("inf"), 0.0),
+                 (0, 1, 0.0, float("nan")), (0, 1, 0.0, -float("inf")), (-1, 0, 0.0, 0.0), (0, 0, float("nan"), 0.0), (0, 1, float("nan"), float("nan")),
+                 (2 ** 31 - 1, 1, -1e300, 1e300)]
+    inits = np.zeros(len(init_rows), dtype=_lib.CHAN_INIT)
+    for rec, (stream, sat, dop, phase) in zip(inits, init_rows):
+        rec["stream"], rec["sat_id"], rec["doppler_hz"], rec["carrier_phase"] = stream, sat, dop, phase
+    inits.tofile(d / "inits.bin")
+    fresh = [(n, cursor, stream, sat, dop, phase, code) for n in (1023, 2046, 49104) for code in (0, 1, n - 1)
+             for cursor, stream, sat, dop, phase in ((0, 0, 1, 1234.5, 0.0), (100, 3, 32, -4999.25, -1e-300), (2 ** 40, 1, 7, 0.0, 2 * np.pi), (7, 2, 9, 1e-3, -2 * np.pi),
+                                                    (19, 0, 5, 250.0, 1.0), (20, 0, 5, -250.0, -1.0))]
+    i64([(n, cursor) for n, cursor, *_ in fresh]).tofile(d / "fresh.i64")
+    fresh_inits = np.zeros(len(fresh), dtype=_lib.CHAN_INIT)
+    for rec, (_, _, stream, sat, dop, phase, code) in zip(fresh_inits, fresh):
+        rec["stream"], rec["sat_id"], rec["doppler_hz"], rec["carrier_phase"], rec["code_phase"] = stream, sat, dop, phase, code
+    fresh_inits.tofile(d / "inits_fresh.bin")
+    rates = [(f, n) for n in (1023, 2046, 49104) for f in (0.0, 1.0, -1.0, 4999.75, -4999.75, 1e5, -1e5, 1575.42e6, -1575.42e6)]
+    f64(rates).tofile(d / "rates.f64")
+    advances = [(u0, f, fs, c0, samples, r) for u0, f in ((0.0, 0.0), (0.25, 1234.5), (0.999999, -4999.75), (0.5, -1e5)) for fs in (1.023e6, 2.046e6, 49.104e6)
+                for c0, samples, r in ((0, 2046, wm.code_rate(0.0, 2046)), (-1, 1023, wm.ONE), (-wm.CODE_MOD, 20 * 49104, wm.code_rate(-4999.75, 49104)),
+                                       (wm.CODE_MOD, 0, 5), (3 * wm.CODE_MOD + 7, -2046, wm.code_rate(1e5, 2046)), (-5 * wm.CODE_MOD - 7, -1, 1))]
+    f64([a[:3] for a in advances]).tofile(d / "advances.f64")
+    i64([a[3:] for a in advances]).tofile(d / "advances.i64")
+    rng = np.random.default_rng(20261021)
+    firsts = [0, 7, 19, 20, 33, 2 ** 40 + 13]
+    prompts = {}
+    for edge in (0, 7, 19):      # 40 ms of prompts whose sign flips at the milliseconds m with m % 20 == edge, for first_ms 0: +- 1 and noise
+        m = np.arange(40)
+        sign = np.where(((m - edge) // 20) % 2 == 0, 1.0, -1.0)
+        prompts[edge] = (sign * (1.0 + 0.5j) + 0.3 * (rng.standard_normal(40) + 1j * rng.standard_normal(40))).astype(np.complex64)
+    loop_ms = (rng.standard_normal((26 * 20, 6)) * 40.0).astype(np.float32)
+    loop_ms[:, 2] += 300.0                                      # a prompt on the I axis ...
+    loop_ms[10 * 20:, 2:4] = (rng.standard_normal((16 * 20, 2)) * 300.0).astype(np.float32)      # ... that is lost from period 10 on: mu falls below lose_mu
+    loop_ms.tofile(d / "loop.f32")
+    loop_f, loop_i = (1234.5, 0.625, 2.046e6, 8.0, 1.0, 9.0), (wm.init_c0(777, 2046), 2046, 113)
+    f64(loop_f).tofile(d / "loop.f64")
+    i64(loop_i).tofile(d / "loop.i64")
+
+    np.concatenate(list(prompts.values())).view(np.float32).tofile(d / "sync.f32")
+    i64(firsts).tofile(d / "sync.i64")
+
+    out = run(programs, which, "weak-plan", tmp_path)
+    got_sync = dict(zip(prompts, np.fromfile(out / "sync.f64", dtype="<f8").reshape(len(prompts), len(firsts), 21)))
+    for edge, p in prompts.items():
+        for row, first in zip(got_sync[edge], firsts):
+            en, pick = wm.bit_sync(p, first)
+            assert row[:20].tobytes() == en.tobytes() and int(row[20]) == pick, (edge, first)
+        assert int(got_sync[edge][0, 20]) == edge and int(got_sync[edge][1, 20]) == (edge + 7) % 20      # first_ms 0 finds the edge; first_ms 7 sees it 7 later
+    lines = (out / "refusals.txt").read_text().splitlines()
+    want = [wm.params_refusal(int(r["period_ms"]), int(r["sync_ms"]), int(r["spacing"]), float(r["pll_bw_hz"]), float(r["dll_bw_hz"]), float(r["lose_mu"])) for r in params]
+    want += [wm.init_refusal(*row) for row in init_rows]
+    assert lines == [w or "ok" for w in want]
+    assert lines[:len(edges)].count("ok") == 11 and lines[len(edges):].count("ok") == 3 and len(set(lines)) == 11      # every refusal of both functions
+    assert (out / "default.bin").read_bytes() == default.tobytes()
+    chans = np.fromfile(out / "fresh.bin", dtype=wm.CHAN)
+    assert len(chans) == len(fresh)
+    for got, (n, cursor, stream, sat, dop, phase, code) in zip(chans, fresh):
+        assert got.tobytes() == wm.fresh_chan(stream, sat, dop, phase, code, n, cursor).tobytes(), (n, cursor, phase, code)
+    assert (chans["u0"] >= 0.0).all() and (chans["u0"] < 1.0).all() and (chans["c0"] >= 0).all() and (chans["c0"] < wm.CODE_MOD).all()
+    assert np.fromfile(out / "rates.i64", dtype="<i8").tolist() == [wm.code_rate(f, int(n)) for f, n in rates]
+    adv_u, adv_c = np.fromfile(out / "advanced.f64", dtype="<f8"), np.fromfile(out / "advanced.i64", dtype="<i8").reshape(-1, 2)
+    for (u0, f, fs, c0, samples, r), got_u, (got_mod, got_c) in zip(advances, adv_u.tolist(), adv_c.tolist()):
+        want_u, want_c = wm.advance(u0, c0 % wm.CODE_MOD, f, fs, samples, r)
+        assert (got_u, got_mod, got_c) == (want_u, c0 % wm.CODE_MOD, want_c), (u0, f, fs, c0, samples, r)
+    # the loop: 26 periods folded and closed
+    s = np.zeros(1, dtype=wm.CHAN)[0]
+    s["phase"], s["f"], s["f_int"], s["u0"], s["c0"] = wm.TRACK, loop_f[0], loop_f[0], loop_f[1], loop_i[0]
+    prm = wm.Params(pll_bw_hz=loop_f[3], dll_bw_hz=loop_f[4], lose_mu=loop_f[5])
+    periods = np.fromfile(out / "periods.bin", dtype=_lib.WEAK_PERIOD_REC)
+    assert len(periods) == 26
+    for k, got in enumerate(periods):
+        s["period_first"] = loop_i[2] + 20 * k
+        for row in loop_ms[20 * k:20 * k + 20]:
+            wm.fold_ms(s, complex(row[0], row[1]), complex(row[2], row[3]), complex(row[4], row[5]))
+            s["pos"] += 1
+        want = wm.close_period(s, prm, loop_f[2], loop_i[1])
+        rec = np.zeros(1, dtype=_lib.WEAK_PERIOD_REC)
+        for name in wm.PERIOD_FIELDS:
+            rec[name] = want[name]
+        assert got.tobytes() == rec.tobytes(), (k, got, rec)
+    assert (out / "chan.bin").read_bytes() == s.tobytes()
+    assert periods["mu_mean"][:24].tolist() == [0.0] * 24 and periods["mu_mean"][24] > 0.0 and int(s["n_periods"]) == 26 and int(s["status"]) == 2
+    assert 1 in periods["status"][24:].tolist() and (periods["mu"][:10] > 10.0).all() and periods["bit"][:10].tolist() == [1] * 10

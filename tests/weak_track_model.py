@@ -92,6 +92,108 @@ def bit_sync(prompts: np.ndarray, first_ms: int) -> Tuple[np.ndarray, int]:
     return en, int(np.argmax(en))               # np.argmax: the lowest index on a tie
 
 
+def params_refusal(period_ms: int, sync_ms: int, spacing: int, pll_bw_hz: float, dll_bw_hz: float, lose_mu: float) -> Optional[str]:
+    """weak_params_refusal: why a parameter set is refused, in the header's order."""
+    if period_ms != 20:
+        return "period_ms must be 20"
+    if not 40 <= sync_ms <= 2000:
+        return "sync_ms must be 40..2000"
+    if not 1 <= spacing <= ONE:
+        return "spacing must be 1 .. 2^40"
+    if not 0.0 < pll_bw_hz <= 50.0:
+        return "pll_bw_hz must be in (0, 50]"
+    if not 0.0 < dll_bw_hz <= 10.0:
+        return "dll_bw_hz must be in (0, 10]"
+    if not 0.0 <= lose_mu <= 20.0:
+        return "lose_mu must be in [0, 20]"
+    return None
+
+
+def init_refusal(stream: int, sat_id: int, doppler_hz: float, carrier_phase: float) -> Optional[str]:
+    """weak_init_refusal."""
+    if stream < 0:
+        return "a stream index is negative"
+    if not 1 <= sat_id <= 32:
+        return "satellite id out of range"
+    if not math.isfinite(doppler_hz):
+        return "a Doppler is not finite"
+    if not math.isfinite(carrier_phase):
+        return "a carrier phase is not finite"
+    return None
+
+
+def advance(u0: float, c0: int, f: float, fs: float, samples: int, r: int) -> Tuple[float, int]:
+    """weak_advance: u0 and c0 after `samples` samples at (f, r)."""
+    du = np.float64(f) / np.float64(fs)
+    return frac(float(np.float64(u0) + du * np.float64(samples))), (c0 + samples * r) % CODE_MOD
+
+
+# weak_plan.hpp's WeakChan, as the host and the device hold it
+CHAN = np.dtype([("stream", "<i4"), ("sat_id", "<i4"), ("status", "<i4"), ("phase", "<i4"), ("edge", "<i4"), ("pos", "<i4"), ("n_periods", "<i4"),
+                 ("sync_count", "<i4"), ("sync_start", "<i8"), ("period_first", "<i8"), ("f", "<f8"), ("f_int", "<f8"), ("u0", "<f8"), ("c0", "<i8"),
+                 ("s_i", "<f8"), ("s_q", "<f8"), ("m_re", "<f8"), ("m_im", "<f8"), ("p_re", "<f8"), ("p_im", "<f8"), ("wbp", "<f8"),
+                 ("mu", "<f8", (MU_WINDOW,)), ("mu_mean", "<f8")], align=True)
+PERIOD_FIELDS = ("first_ms", "f", "u0", "c0", "i", "q", "mu", "dphi", "dd", "bit", "status", "mu_mean")
+
+
+def fresh_chan(stream: int, sat_id: int, doppler_hz: float, carrier_phase: float, code_phase: int, n: int, cursor: int) -> np.ndarray:
+    """weak_fresh_chan: one CHAN record in SYNC from millisecond `cursor`."""
+    s = np.zeros(1, dtype=CHAN)[0]
+    s["stream"], s["sat_id"], s["phase"], s["edge"], s["sync_start"] = stream, sat_id, SYNC, -1, cursor
+    s["f"] = s["f_int"] = doppler_hz
+    s["u0"], s["c0"] = init_u0(carrier_phase), init_c0(code_phase, n)
+    return s
+
+
+def fold_ms(s: np.ndarray, minus: complex, prompt: complex, plus: complex) -> None:
+    """weak_fold_ms: one millisecond's float32 sums into the period's float64 sums of the CHAN record s."""
+    pr, pi = np.float64(np.float32(prompt.real)), np.float64(np.float32(prompt.imag))
+    s["s_i"] += pr
+    s["s_q"] += pi
+    s["m_re"] += np.float64(np.float32(minus.real))
+    s["m_im"] += np.float64(np.float32(minus.imag))
+    s["p_re"] += np.float64(np.float32(plus.real))
+    s["p_im"] += np.float64(np.float32(plus.imag))
+    s["wbp"] += pr * pr + pi * pi
+
+
+def close_period(s: np.ndarray, p: Params, fs: float, n: int) -> dict:
+    """weak_close_period on the CHAN record s (changed in place): the period record, as {PERIOD_FIELDS}.  Python floats and math.sqrt /
+    math.atan: one IEEE rounding per operation, in the header's order."""
+    T = p.period_ms / 1000.0
+    two_pi = 2.0 * math.pi
+    i, q = float(s["s_i"]), float(s["s_q"])
+    m_re, m_im, p_re, p_im, wbp = (float(s[k]) for k in ("m_re", "m_im", "p_re", "p_im", "wbp"))
+    e_minus, e_plus = math.sqrt(m_re * m_re + m_im * m_im), math.sqrt(p_re * p_re + p_im * p_im)
+    nbp = i * i + q * q
+    mu = nbp / wbp if wbp > 0.0 else 0.0
+    dphi = math.atan(q / i) if i != 0.0 else 0.0
+    e_sum = e_plus + e_minus
+    dd = 0.5 * (e_plus - e_minus) / e_sum if e_sum != 0.0 else 0.0
+    f = float(s["f"])
+    rec = dict(first_ms=int(s["period_first"]), f=f, u0=float(s["u0"]), c0=int(s["c0"]), i=i, q=q, mu=mu, dphi=dphi, dd=dd, bit=1 if i >= 0.0 else -1, status=0)
+    u0, c0 = advance(float(s["u0"]), int(s["c0"]), f, fs, p.period_ms * n, code_rate(f, n))
+    wn = p.pll_bw_hz / 0.53
+    kp, ki = 1.414 * wn, wn * wn
+    s["f_int"] = float(s["f_int"]) + ki * dphi * T / two_pi
+    s["f"] = float(s["f_int"]) + kp * dphi / two_pi
+    s["u0"], s["c0"] = u0, (c0 + llround(4.0 * p.dll_bw_hz * dd * T * float(ONE))) % CODE_MOD
+    s["mu"][int(s["n_periods"]) % MU_WINDOW] = mu
+    s["n_periods"] += 1
+    s["pos"] = 0
+    for k in ("s_i", "s_q", "m_re", "m_im", "p_re", "p_im", "wbp", "mu_mean"):
+        s[k] = 0.0
+    if s["n_periods"] >= MU_WINDOW:
+        total = 0.0
+        for k in range(MU_WINDOW):                        # oldest first
+            total += float(s["mu"][(int(s["n_periods"]) + k) % MU_WINDOW])
+        s["mu_mean"] = total / MU_WINDOW
+        if s["mu_mean"] < p.lose_mu:
+            s["status"], rec["status"] = 2, 1
+    rec["mu_mean"] = float(s["mu_mean"])
+    return rec
+
+
 @dataclass
 class MsRec:
     minus: complex
