@@ -68,3 +68,14 @@ class WeakParams(Record):
     dll_bw_hz: float = 1.0
     lose_mu: float = 2.5
     reserved: float = 0.0
+
+
+@dataclasses.dataclass
+class WeakRefineParams(Record):
+    """gyp_weak_refine_params, with the library's defaults (gyp_weak_refine_params_default): the half width and the step of the
+    residual-Doppler scan in Hz and the milliseconds of prompts summed before squaring."""
+    DTYPE = _lib.WEAK_REFINE_PARAMS
+    span_hz: float = 20.0
+    step_hz: float = 0.5
+    presum_ms: int = 4
+    reserved: int = 0

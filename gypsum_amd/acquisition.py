@@ -16,7 +16,7 @@ from typing import Any, Dict, List
 
 import numpy as np
 
-from ._lib import CELL_DESC, GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER, GYP_NON_COHERENT
+from ._lib import CELL_DESC, GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER, GYP_NON_COHERENT, WEAK_RESULT
 from .antenna_sample_provider import SampleProviderAttributes
 from .engine import default_engine
 from .gps_ca_prn_codes import GpsSatelliteId
@@ -111,6 +111,30 @@ class GpsSatelliteDetector:
             satellite_id=sid, doppler_shift=float(r["doppler_hz"]), carrier_wave_phase_shift=float(r["carrier_phase"]),
             prn_phase_shift=int(r["code_phase"]), correlation_strength=float(r["z"]))
             for sid, r in zip(sats, rec) if float(r["z"]) > z_threshold]
+
+    def refine_weak_satellites(self, results: List[SatelliteAcquisitionAttemptResult], antenna_data: np.ndarray,
+                               stream_attributes: SampleProviderAttributes, first_ms: int = 0, params=None) -> List[SatelliteAcquisitionAttemptResult]:
+        """Between detect_weak_satellites_in_antenna_data and a WeakSignalTracker: each result's Doppler refined to well below 1 Hz
+        and its carrier phase re-estimated (gyp_weak_refine) from the whole milliseconds of antenna_data (40..2000: the search's own
+        buffer or a longer one; its first sample is that of the search, millisecond first_ms of the recording).  One new result per
+        input, in order, none dropped; a result whose peak lay at the edge of the scanned span (status 1) is logged."""
+        results = list(results)
+        if not results:
+            return []
+        n = stream_attributes.samples_per_prn_transmission
+        n_ms = min(len(antenna_data) // n, 2000)
+        cand = np.zeros(len(results), dtype=WEAK_RESULT)
+        for c, r in zip(cand, results):
+            c["sat_id"], c["doppler_hz"], c["carrier_phase"], c["code_phase"] = _sv(r.satellite_id), r.doppler_shift, r.carrier_wave_phase_shift, r.prn_phase_shift
+        rec, _ = self._engine(stream_attributes).refine_weak(np.asarray(antenna_data)[:n_ms * n], 1, int(first_ms), cand, params)
+        for r, o in zip(results, rec):
+            log = _logger.warning if int(o["status"]) else _logger.info
+            log(f"Weak hand-over of satellite {r.satellite_id}: Doppler {r.doppler_shift} -> {float(o['doppler_hz']):.2f} Hz, status {int(o['status'])}, "
+                f"peak to mean {float(o['peak_to_mean']):.1f}, bit edge {int(o['edge'])}")
+        return [SatelliteAcquisitionAttemptResult(
+            satellite_id=r.satellite_id, doppler_shift=float(o["doppler_hz"]), carrier_wave_phase_shift=float(o["carrier_phase"]),
+            prn_phase_shift=int(o["code_phase"]), correlation_strength=r.correlation_strength)
+            for r, o in zip(results, rec)]
 
     def _attempt_acquisition_for_satellite_id(self, satellite_id: Any, samples_for_integration_period: np.ndarray,
                                               stream_attributes: SampleProviderAttributes) -> SatelliteAcquisitionAttemptResult:

@@ -145,12 +145,16 @@ static thread_local std::string g_create_error;
 //   hyb_level_cells, hyb_records, hyb_taps   gyp_acquire_weak_dev, sized by its WeakSearchPlan: the cell tables of the coarse level, the
 //                             fine level and the final cells (back to back), the larger level's records (weak_level), the final
 //                             cells' gyp_cell records (their taps)
+//   wref_cands, wref_plans, wref_prompts, wref_power   gyp_weak_refine_dev: the candidates' start-up states, one WeakMsPlan per (candidate,
+//                             millisecond), the prompts when the caller takes none, the power rows of the periodograms
 // Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
 // wrapper calls another (the hybrid wrappers gyp_correlate_grid_hybrid and gyp_acquire_weak use stage_iq and stage_out like the
 // others); of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
 // none calls another, and what acquire_search calls (launch_cells, launch_cells_shared, gyp_correlate_cells_dev) uses no member.
 // hybrid_run serves one of gyp_correlate_grid_hybrid_dev and gyp_acquire_weak_dev at a time, neither calls the other, and its
-// launch_cells uses no member; the hyb_* members have no user outside the hybrid entry points.
+// launch_cells uses no member; the hyb_* members have no user outside the hybrid entry points.  The wref_* members have no user but
+// gyp_weak_refine_dev, which calls no entry point; its wrapper gyp_weak_refine stages through stage_iq and stage_out (the records, then
+// the prompts, back to back) like the others.
 struct Scratch {
     DevBuf<int32_t> hyb_sat_ids;
     DevBuf<double> hyb_doppler;
@@ -159,6 +163,10 @@ struct Scratch {
     DevBuf<cf> hyb_profile;
     DevBuf<float> hyb_power;
     DevBuf<gyp_hybrid_cell> hyb_records;
+    DevBuf<WeakRefineCand> wref_cands;
+    DevBuf<WeakMsPlan> wref_plans;
+    DevBuf<float2> wref_prompts;
+    DevBuf<double> wref_power;
     DevBuf<float> stage_iq, stage_profile, bench_sink;
     DevBuf<uint8_t> stage_in, stage_out, weak_stage, refine_list, acq_book, acq_units;
     DevBuf<double> stage_times, doppler, partial64, acq_refined, acq_profiles;
@@ -2090,6 +2098,101 @@ int gyp_weak_track_block(gyp_weak_bank* bank, const float* iq_host, int32_t n_st
                 std::memcpy(period_out_host + c * max_periods, staged.data() + c * max_periods * sizeof(gyp_weak_period_rec),
                             (size_t)cnt[c] * sizeof(gyp_weak_period_rec));
     return GYP_OK;
+}
+
+// ---------------------------------------------------------------- weak-signal hand-over --------------------
+void gyp_weak_refine_params_default(gyp_weak_refine_params* out) {
+    if (out) *out = refine_params_default();
+}
+
+int gyp_weak_refine_estimate(const float* prompts, int32_t n_ms, int64_t first_ms, const gyp_weak_refine_params* params, gyp_weak_refined* out) {
+    static const char* const who = "gyp_weak_refine_estimate";
+    if (!prompts || !out) return refuse(nullptr, who, "bad argument");
+    const gyp_weak_refine_params prm = params ? *params : refine_params_default();
+    if (const char* why = refine_refusal(prm, n_ms, first_ms)) return refuse(nullptr, who, why);
+    gyp_weak_refined r{};
+    refine_estimate(prompts, n_ms, first_ms, prm, 0.0, 0.0, &r);
+    *out = r;
+    return GYP_OK;
+}
+
+}   // extern "C"
+// What both forms of gyp_weak_refine refuse, before anything runs (stride < 0: the host form, which has none).
+static int weak_refine_check(gyp_ctx* ctx, const char* who, const void* iq, const void* out, int32_t n_streams, int64_t stream_stride_samples,
+                             int64_t first_ms, int32_t n_ms, const gyp_weak_result* results, int32_t n_results, const gyp_weak_refine_params& prm) {
+    if (!iq || !out || !results || n_streams < 1 || n_results < 1) return refuse(ctx, who, "bad argument");
+    if (const char* why = refine_refusal(prm, n_ms, first_ms)) return refuse(ctx, who, why);
+    if (stream_stride_samples >= 0 && stream_stride_samples < (int64_t)n_ms * ctx->n) return refuse(ctx, who, "the stream stride is below n_ms * N");
+    if ((int64_t)n_results * ((n_ms + kRefineWaves - 1) / kRefineWaves) > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 workgroups");
+    for (int32_t i = 0; i < n_results; ++i) {
+        const gyp_weak_result& r = results[i];
+        const gyp_chan_init in{r.stream, r.sat_id, r.doppler_hz, r.carrier_phase, r.code_phase, 0};
+        if (const char* why = weak_init_refusal(in)) return refuse(ctx, who, why);
+        if (r.stream >= n_streams)
+            return refuse(ctx, who, "result " + std::to_string(i) + " reads stream " + std::to_string(r.stream) + " but only " + std::to_string(n_streams) + " were passed");
+        if (r.code_phase < 0 || r.code_phase >= ctx->n) return refuse(ctx, who, "a code phase is outside [0, N)");
+    }
+    return GYP_OK;
+}
+extern "C" {
+
+int gyp_weak_refine_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                        const gyp_weak_result* results_host, int32_t n_results, const gyp_weak_refine_params* params,
+                        gyp_weak_refined* out_dev, float* prompts_out_dev) {
+    static const char* const who = "gyp_weak_refine_dev";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    const gyp_weak_refine_params prm = params ? *params : refine_params_default();
+    if (stream_stride_samples < 0) return refuse(ctx, who, "bad argument");
+    if (const int rc = weak_refine_check(ctx, who, iq_dev, out_dev, n_streams, stream_stride_samples, first_ms, n_ms, results_host, n_results, prm)) return rc;
+    const RefineShape sh = refine_shape(prm, n_ms);
+    std::vector<WeakRefineCand> cands((size_t)n_results);
+    for (int32_t i = 0; i < n_results; ++i) {
+        const gyp_weak_result& r = results_host[i];
+        const WeakChan s = weak_fresh_chan(gyp_chan_init{r.stream, r.sat_id, r.doppler_hz, r.carrier_phase, r.code_phase, 0}, ctx->n, first_ms);
+        cands[i] = WeakRefineCand{r.stream, r.sat_id, r.code_phase, 0, s.f, s.u0, r.carrier_phase, s.c0};
+    }
+    Scratch& sc = ctx->scratch;
+    const size_t rows = (size_t)n_results * (size_t)n_ms;
+    HIP_TRY(ctx, sc.wref_plans.reserve(rows, Slack::grow, ctx->stream));
+    if (!prompts_out_dev) HIP_TRY(ctx, sc.wref_prompts.reserve(rows, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.wref_power.reserve((size_t)n_results * (size_t)sh.n_bins, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.wref_cands, cands.data(), cands.size(), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the candidates are a temporary
+    WeakRefineArgs p{};
+    p.cands = sc.wref_cands.get(); p.plans = sc.wref_plans.get();
+    p.prompts = prompts_out_dev ? reinterpret_cast<float2*>(prompts_out_dev) : sc.wref_prompts.get();
+    p.power = sc.wref_power.get();
+    p.iq = iq_dev; p.stream_stride = stream_stride_samples; p.chips = ctx->codes.chips.get();
+    p.out = out_dev; p.prm = prm; p.fs = (double)ctx->fs; p.first_ms = first_ms;
+    p.n = ctx->n; p.n_ms = n_ms; p.n_cand = n_results;
+    hipLaunchKernelGGL(weak_refine_plan_kernel, dim3((unsigned)((n_results + 63) / 64)), dim3(64), 0, ctx->stream, p);
+    if (const int rc = launched(ctx)) return rc;
+    const unsigned runs = (unsigned)((n_ms + kRefineWaves - 1) / kRefineWaves);
+    hipLaunchKernelGGL(weak_refine_sums_kernel, dim3((unsigned)n_results * runs), dim3(kRefineThreads), 0, ctx->stream, p);
+    if (const int rc = launched(ctx)) return rc;
+    hipLaunchKernelGGL(weak_refine_estimate_kernel, dim3((unsigned)n_results), dim3(kRefineEstThreads), 0, ctx->stream, p);
+    return launched(ctx);
+}
+
+int gyp_weak_refine(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                    const gyp_weak_result* results_host, int32_t n_results, const gyp_weak_refine_params* params,
+                    gyp_weak_refined* out_host, float* prompts_out_host) {
+    static const char* const who = "gyp_weak_refine";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    const gyp_weak_refine_params prm = params ? *params : refine_params_default();
+    if (const int rc = weak_refine_check(ctx, who, iq_host, out_host, n_streams, -1, first_ms, n_ms, results_host, n_results, prm)) return rc;
+    Scratch& sc = ctx->scratch;
+    const size_t rec_bytes = (size_t)n_results * sizeof(gyp_weak_refined), prompt_bytes = (size_t)n_results * (size_t)n_ms * sizeof(float2);
+    HIP_TRY(ctx, sc.stage_out.reserve(rec_bytes + prompt_bytes, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.stage_iq, iq_host, iq_floats(ctx, n_streams, n_ms), ctx->stream));
+    uint8_t* const base = sc.stage_out.get();
+    if (const int rc = gyp_weak_refine_dev(ctx, sc.stage_iq.get(), n_streams, (int64_t)n_ms * ctx->n, first_ms, n_ms, results_host, n_results, &prm,
+                                           (gyp_weak_refined*)base, (float*)(base + rec_bytes)))
+        return rc;
+    if (prompts_out_host) HIP_TRY(ctx, hipMemcpyAsync(prompts_out_host, base + rec_bytes, prompt_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return stage_back(ctx, out_host, rec_bytes);
 }
 
 // ---------------------------------------------------------------- multi-GPU: one all-gather over RCCL ------

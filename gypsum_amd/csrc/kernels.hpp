@@ -42,6 +42,10 @@
 //   weak_track_kernel   weak-signal tracking: one workgroup per channel of a weak bank; three code lags per sample against NCO replicas,
 //                       a wavefront per millisecond in a fixed reduction order, bit synchronisation and the 20-ms PLL / DLL update
 //                       in float64 on one lane between the periods (weak_plan.hpp holds that arithmetic for host and device).
+//   weak_refine_* kernels   weak-signal hand-over: per candidate of the weak search the open-loop prompts a weak bank would write in
+//                       SYNC, a wavefront per (candidate, millisecond) grid-wide, then one workgroup per candidate squares their
+//                       pre-sums, scans a float64 periodogram for the residual Doppler and reports the bit edge and carrier phase
+//                       (refine_plan.hpp holds that arithmetic for host and device).
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -64,3 +68,4 @@
 #include "kernels_quality.hpp"
 #include "kernels_hybrid.hpp"
 #include "kernels_weak.hpp"
+#include "kernels_refine.hpp"

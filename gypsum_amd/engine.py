@@ -711,6 +711,33 @@ class GypsumEngine:
         """(z, peak_ratio) of HYBRID_CELL records, float64 (gyp_hybrid_stats; see hybrid_stats below)."""
         return hybrid_stats(cells)
 
+    # ------------------------------------------------------------------ weak-signal hand-over (search -> refine -> weak bank)
+    def refine_weak(self, iq: np.ndarray, n_streams: int, first_ms: int, results: np.ndarray, params=None,
+                    want_prompts: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """gyp_weak_refine: the sub-Hz Doppler, the bit edge and the carrier phase of each WEAK_RESULT record from the open-loop prompts
+        of iq (complex64[n_streams * n_ms * N], stream-major, 40..2000 whole milliseconds from the absolute millisecond first_ms).
+        (WEAK_REFINED[len(results)], the complex64 prompts [len(results), n_ms] or None).  params: a _records.WeakRefineParams or a
+        WEAK_REFINE_PARAMS record (None: the defaults)."""
+        iq = _as_iq(iq).reshape(-1)
+        n_ms = iq.size // (max(int(n_streams), 1) * self.n)
+        if iq.size != max(int(n_streams), 1) * n_ms * self.n:
+            raise ValueError("a whole number of milliseconds per stream expected")
+        res = np.ascontiguousarray(results, dtype=_lib.WEAK_RESULT).reshape(-1)
+        prm = _refine_params(params)
+        out = np.zeros(len(res), dtype=_lib.WEAK_REFINED)
+        prompts = np.zeros((len(res), n_ms), dtype=np.complex64) if want_prompts else None
+        self._check(self.lib.gyp_weak_refine(self.ctx, ptr(iq) if iq.size else None, int(n_streams), int(first_ms), n_ms, ptr(res) if res.size else None,
+                                              len(res), ptr(prm), ptr(out), ptr(prompts)))
+        return out, prompts
+
+    def refine_weak_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, first_ms: int, n_ms: int, results: np.ndarray, out_ptr: int,
+                        params=None, prompts_ptr: int = 0) -> None:
+        """Device-pointer form: waits for the stream once, after uploading the candidates, then only enqueues."""
+        res = np.ascontiguousarray(results, dtype=_lib.WEAK_RESULT).reshape(-1)
+        self._check(self.lib.gyp_weak_refine_dev(self.ctx, C.c_void_p(iq_ptr or None), int(n_streams), int(stream_stride), int(first_ms), int(n_ms),
+                                                  ptr(res) if res.size else None, len(res), ptr(_refine_params(params)), C.c_void_p(out_ptr or None),
+                                                  C.c_void_p(prompts_ptr or None)))
+
     def synth_iq(self, out: "DeviceBuffer", n_streams: int, stream_stride: int, n_ms: int, sats: np.ndarray,
                  noise_sigma: float, seed: int) -> None:
         """Generate synthetic baseband straight into HBM (bench / test support). sats: SYNTH_SAT[n_streams, n_sats]."""
@@ -760,6 +787,33 @@ def weak_bit_sync(prompts: np.ndarray, first_ms: int) -> Tuple[np.ndarray, int]:
     if rc != 0:
         raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
     return en, int(off[0])
+
+
+def _refine_params(params) -> Optional[np.ndarray]:
+    """A _records.WeakRefineParams or a WEAK_REFINE_PARAMS record as the library takes it (None stays None: the defaults)."""
+    if params is not None and not isinstance(params, np.ndarray):
+        params = params.record()
+    return None if params is None else np.ascontiguousarray(params, dtype=_lib.WEAK_REFINE_PARAMS).reshape(-1)
+
+
+def weak_refine_params_default() -> np.ndarray:
+    """gyp_weak_refine_params_default (host only, no GPU): one WEAK_REFINE_PARAMS record."""
+    rec = np.zeros(1, dtype=_lib.WEAK_REFINE_PARAMS)
+    _lib.load().gyp_weak_refine_params_default(ptr(rec))
+    return rec
+
+
+def weak_refine_estimate(prompts: np.ndarray, first_ms: int, params=None) -> np.ndarray:
+    """gyp_weak_refine_estimate (host only, no GPU): one WEAK_REFINED record from the complex64 prompts of milliseconds first_ms,
+    first_ms + 1, ...: the residual Doppler (delta_hz; the input Doppler and carrier phase count as 0), the carrier-phase increment,
+    the bit edge and the quality figures."""
+    lib = _lib.load()
+    p = np.ascontiguousarray(prompts, dtype=np.complex64).reshape(-1)
+    out = np.zeros(1, dtype=_lib.WEAK_REFINED)
+    rc = lib.gyp_weak_refine_estimate(ptr(p) if p.size else None, p.size, int(first_ms), ptr(_refine_params(params)), ptr(out))
+    if rc != 0:
+        raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
+    return out[0]
 
 
 class _BankHandle:

@@ -12,7 +12,8 @@ false lock, mostly 10 Hz or more off -- bits at chance, `mu` healthy (7.6 to 8.9
 grid hands over either.  `phase_rms`, the rms of the PLL discriminator over the last 25 bits, tells the two apart: 0.13 to 0.30 rad in
 lock and 0.74 to 1.06 rad in the false lock on the float64 model over nine scenes (tests/weak_track_scene.py prints them);
 `WeakChannelStatus.false_lock` is phase_rms above FALSE_LOCK_PHASE_RMS = 0.5: that channel's bits are not to be used.  Nothing here
-repairs it; `bank.set_channel` restarts a slot from a start the caller supplies.
+repairs it; the repair comes first: GpsSatelliteDetector.refine_weak_satellites brings the search's results within a fraction of a
+hertz before they are handed to this class, and `bank.set_channel` restarts a slot from such a start.
 """
 from __future__ import annotations
 

@@ -29,6 +29,9 @@ extern "C" {
 #endif
 
 /* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
+ *      hand-over, a sub-Hz Doppler refinement between the weak search and the weak bank on the device: gyp_weak_refine_params(_default),
+ *      gyp_weak_refined, gyp_weak_refine(_dev), gyp_weak_refine_estimate.  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
  *      tracking, a second kind of channel bank with 20-ms coherent loops and bit synchronisation on the device: gyp_weak_bank,
  *      gyp_weak_params(_default), gyp_weak_ms_rec, gyp_weak_period_rec, gyp_weak_state, gyp_weak_bit_sync, gyp_weak_bank_create / _destroy /
  *      _size / _set_channel / _drop_channel / _get_state / _set_state, gyp_weak_track_block(_dev).  Opt-in.
@@ -608,6 +611,80 @@ int gyp_weak_track_block_dev(gyp_weak_bank* bank, const float* iq_dev, int64_t s
                              gyp_weak_ms_rec* ms_out_dev, gyp_weak_period_rec* period_out_dev, int32_t* n_periods_out_dev);
 int gyp_weak_track_block(gyp_weak_bank* bank, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
                          gyp_weak_ms_rec* ms_out_host, gyp_weak_period_rec* period_out_host, int32_t* n_periods_out_host);
+
+/* ---------------------------------------------------------------- weak-signal hand-over ----------------- */
+/* Between gyp_acquire_weak and a weak bank.  The search's fine level steps 10 Hz and the bank's loop pulls in from about 5 Hz, so a
+ * 30 dB-Hz candidate handed over as it is starts 7-8 Hz off about one time in four and then false-locks.  This step refines each
+ * candidate's Doppler to well below 1 Hz from the open-loop prompts of the search's own buffer (or a longer one), and reports the
+ * bit edge and the carrier phase it sees on the way.  It changes nothing in the search, the bank or their records.
+ *
+ * Inputs: one stream buffer of n_ms whole milliseconds (40..2000) whose first millisecond has the absolute index first_ms, and per
+ * candidate a gyp_weak_result, of which stream, sat_id, doppler_hz = f0, carrier_phase and code_phase are read.
+ *   1 prompts   p_m, m = 0 .. n_ms - 1, float32 pairs: exactly the prompt a weak bank writes in SYNC for millisecond first_ms + m when
+ *               it is created from this result at cursor first_ms -- the start rule, the per-millisecond advance of u0 and c0 and the
+ *               arithmetic of a millisecond's sums are those of the "weak-signal tracking" section, bit for bit.
+ *   2 pre-sum   L = presum_ms, G = n_ms / L rounded down (a tail shorter than L is dropped).  q_g = the sum, in order, of
+ *               p_{gL} .. p_{gL+L-1} widened; s_g = q_g^2: re = qr qr - qi qi, im = (2 qr) qi.  Squaring removes the data bits; s_g
+ *               rotates at twice the residual Doppler.  Float64 from here on, one rounding per operation, no contraction.
+ *   3 bins      J = floor(span_hz / step_hz); for j = -J .. J: Y_j = sum over g, in increasing g, of s_g exp(-2 pi i c) with
+ *               c = (2 (j step_hz)) t_g cycles, t_g = (g L + L / 2) / 1000 s, c reduced by rint(c) before the sine and cosine;
+ *               P_j = |Y_j|^2.
+ *   4 pick      k = arg-max of P, the lowest index on a tie.  d = 0.5 (P[k-1] - P[k+1]) / (P[k-1] - 2 P[k] + P[k+1]), clamped to
+ *               +-0.5; d = 0 when k is an end bin or the denominator is not negative.  delta_hz = (k - J + d) step_hz;
+ *               doppler_hz = f0 + delta_hz; bin = k.  status = 1 when k is an end bin: the truth may lie outside the span and the
+ *               caller should not trust the result.  A row without a positive P (all-zero prompts) has no peak: bin = J,
+ *               delta_hz = 0, peak_to_mean NaN, status 1.
+ *   5 quality   peak_to_mean = P[k] over the mean of the P_j with |j - k| > ceil(1000 / (n_ms step_hz)), summed in increasing j;
+ *               NaN if there is no such bin.  A figure, not a verdict: on the float64 model 30-60 for a 30 dB-Hz satellite over 220 ms
+ *               at the right code phase, 5-20 one sample off, 3-5 for an absent one.
+ *   6 phase     Y* = sum over g of s_g exp(-2 pi i (2 delta_hz) t_g); carrier_phase = the input's + 0.5 atan2(Im Y*, Re Y*),
+ *               wrapped to (-pi, pi]: right modulo pi, which is all a Costas loop needs.
+ *   7 bit edge  p'_m = p_m exp(-2 pi i delta_hz (m + 0.5) / 1000), each part rounded to float32 once; en[o] as gyp_weak_bit_sync
+ *               takes it over p'; edge = its pick; edge_ratio = the largest en over the second largest.
+ * The device and gyp_weak_refine_estimate share this arithmetic (csrc/refine_plan.hpp) but not their sine and cosine: they agree
+ * to about 1e-12 in delta_hz and carrier_phase, not bit for bit.  A candidate's record and prompts are the same bits whatever other
+ * candidates the call holds and in whatever order. */
+typedef struct gyp_weak_refine_params {   /* 24 bytes */
+    double span_hz;        /* 20; (0, 100], and below 250 / presum_ms: the squared sequence is sampled at 1000 / presum_ms Hz and carries 2 f */
+    double step_hz;        /* 0.5; [0.01, span_hz]; at most 4097 bins */
+    int32_t presum_ms;     /* 4; one of 1, 2, 4, 5, 10, 20 */
+    int32_t reserved;      /* 0 */
+} gyp_weak_refine_params;
+void gyp_weak_refine_params_default(gyp_weak_refine_params* out);
+
+/* Converts by field name into a gyp_chan_init, as gyp_weak_result does. */
+typedef struct gyp_weak_refined {   /* 64 bytes */
+    int32_t stream;
+    int32_t sat_id;
+    double doppler_hz;       /* f0 + delta_hz */
+    int32_t code_phase;      /* the input's, unchanged */
+    int32_t edge;            /* 0..19: a bit edge at every millisecond m with m mod 20 == edge */
+    double carrier_phase;    /* at the buffer's first sample, radians (-pi, pi], modulo pi */
+    double delta_hz;
+    double peak_to_mean;
+    double edge_ratio;
+    int32_t bin;             /* k, 0 .. 2 J */
+    int32_t status;          /* 0 ok, 1 the peak is an end bin (or there is none) */
+} gyp_weak_refined;
+
+/* iq_dev: n_streams streams of n_ms x N samples, stream stride given.  results_host: n_results candidates, a HOST array (the caller
+ * has thresholded z on the host); out_dev: n_results records in the same order; prompts_out_dev: NULL, or n_results x n_ms float32
+ * pairs, candidate-major.  params NULL: the defaults.  Refused with GYP_E_BAD_ARG before anything runs: params out of range as
+ * commented above; n_ms outside 40..2000 or fewer than 8 groups; first_ms < 0; NULL pointers or counts below 1; a result with
+ * stream < 0 or >= n_streams, a satellite id outside 1..32, a non-finite Doppler or carrier phase, or a code phase outside [0, N); a
+ * stride below n_ms N.  The _dev form waits for the stream once, after uploading the candidates (the host array may be a
+ * temporary), then only enqueues. */
+int gyp_weak_refine_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                        const gyp_weak_result* results_host, int32_t n_results, const gyp_weak_refine_params* params,
+                        gyp_weak_refined* out_dev, float* prompts_out_dev);
+int gyp_weak_refine(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                    const gyp_weak_result* results_host, int32_t n_results, const gyp_weak_refine_params* params,
+                    gyp_weak_refined* out_host, float* prompts_out_host);
+/* Host only, no GPU: steps 2-7 on given prompts (n_ms interleaved re,im float32 pairs, the prompt of millisecond first_ms + i at i),
+ * the twin of gyp_weak_bit_sync.  The input Doppler and carrier phase are taken as 0, so doppler_hz = delta_hz and carrier_phase is
+ * the increment; stream, sat_id and code_phase of *out are 0.  GYP_E_BAD_ARG, with *out untouched, for NULL prompts or out, params
+ * out of range (NULL: the defaults), n_ms outside 40..2000 or fewer than 8 groups, first_ms < 0. */
+int gyp_weak_refine_estimate(const float* prompts, int32_t n_ms, int64_t first_ms, const gyp_weak_refine_params* params, gyp_weak_refined* out);
 
 /* ---------------------------------------------------------------- multi-GPU ----------------------------- */
 /* The path shards by stream, satellite or (satellite x Doppler) cell with no data-path exchange except ONE all-gather
