@@ -79,6 +79,12 @@ WEAK_REFINE_PARAMS = np.dtype([("span_hz", "<f8"), ("step_hz", "<f8"), ("presum_
 WEAK_REFINED = np.dtype([("stream", "<i4"), ("sat_id", "<i4"), ("doppler_hz", "<f8"), ("code_phase", "<i4"), ("edge", "<i4"),
                          ("carrier_phase", "<f8"), ("delta_hz", "<f8"), ("peak_to_mean", "<f8"), ("edge_ratio", "<f8"), ("bin", "<i4"),
                          ("status", "<i4")], align=True)
+WEAK_MEASURE_PARAMS = np.dtype([("spacing", "<i8"), ("passes", "<i4"), ("reserved", "<i4")], align=True)
+WEAK_MEASURED = np.dtype([("stream", "<i4"), ("sat_id", "<i4"), ("doppler_hz", "<f8"), ("carrier_phase", "<f8"), ("c0", "<i8"),
+                          ("code_phase_samples", "<f8"), ("delta_chips", "<f8"), ("dd_last", "<f8"), ("cn0_dbhz", "<f8"), ("edge", "<i4"),
+                          ("n_groups", "<i4"), ("status", "<i4"), ("reserved", "<i4")], align=True)
+WEAK_MEASURE_FOLD = np.dtype([("e_minus", "<f8"), ("e_prompt", "<f8"), ("e_plus", "<f8"), ("wn", "<f8"), ("dd", "<f8"), ("cn0_dbhz", "<f8"),
+                              ("c0", "<i8"), ("n_groups", "<i4"), ("status", "<i4")], align=True)
 GYP_POWER_HIST_BINS = 2048
 GYP_EXCISE_FRAME = 256
 GYP_WINDOW_RECT, GYP_WINDOW_HANN = 0, 1
@@ -97,7 +103,9 @@ RECORD_SIZES = {"gyp_bit_event": BIT_EVENT.itemsize, "gyp_bits_state": BITS_STAT
                 "gyp_excisor": EXCISOR.itemsize, "gyp_hybrid_cell": HYBRID_CELL.itemsize, "gyp_weak_result": WEAK_RESULT.itemsize,
                 "gyp_weak_params": WEAK_PARAMS.itemsize, "gyp_weak_ms_rec": WEAK_MS_REC.itemsize,
                 "gyp_weak_period_rec": WEAK_PERIOD_REC.itemsize, "gyp_weak_state": WEAK_STATE.itemsize,
-                "gyp_weak_refine_params": WEAK_REFINE_PARAMS.itemsize, "gyp_weak_refined": WEAK_REFINED.itemsize}
+                "gyp_weak_refine_params": WEAK_REFINE_PARAMS.itemsize, "gyp_weak_refined": WEAK_REFINED.itemsize,
+                "gyp_weak_measure_params": WEAK_MEASURE_PARAMS.itemsize, "gyp_weak_measured": WEAK_MEASURED.itemsize,
+                "gyp_weak_measure_fold": WEAK_MEASURE_FOLD.itemsize}
 # include/gypsum_hip.h GYP_VERSION these mirrors were written against: load() refuses any other library
 GYP_VERSION = 209
 
@@ -123,7 +131,8 @@ EXPORTS = (
     "gyp_hybrid_stats gyp_hybrid_shift gyp_correlate_grid_hybrid_dev gyp_correlate_grid_hybrid gyp_acquire_weak_dev gyp_acquire_weak "
     "gyp_weak_params_default gyp_weak_bit_sync gyp_weak_bank_create gyp_weak_bank_destroy gyp_weak_bank_size gyp_weak_bank_set_channel "
     "gyp_weak_bank_drop_channel gyp_weak_bank_get_state gyp_weak_bank_set_state gyp_weak_track_block_dev gyp_weak_track_block "
-    "gyp_weak_refine_params_default gyp_weak_refine_estimate gyp_weak_refine_dev gyp_weak_refine"
+    "gyp_weak_refine_params_default gyp_weak_refine_estimate gyp_weak_refine_dev gyp_weak_refine "
+    "gyp_weak_measure_params_default gyp_weak_measure_estimate gyp_weak_measured_state gyp_weak_measure_dev gyp_weak_measure"
 ).split()
 
 
@@ -296,6 +305,11 @@ def load() -> C.CDLL:
         "gyp_weak_refine_estimate": (C.c_int, [vp, i32, i64, vp, vp]),
         "gyp_weak_refine_dev": (C.c_int, [vp, vp, i32, i64, i64, i32, vp, i32, vp, vp, vp]),
         "gyp_weak_refine": (C.c_int, [vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]),
+        "gyp_weak_measure_params_default": (None, [vp]),
+        "gyp_weak_measure_estimate": (C.c_int, [vp, vp, i32, i64, i32, i64, i64, vp]),
+        "gyp_weak_measured_state": (C.c_int, [vp, i64, i32, i32, vp]),
+        "gyp_weak_measure_dev": (C.c_int, [vp, vp, i32, i64, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "gyp_weak_measure": (C.c_int, [vp, vp, i32, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here == the library does not export what the header declares

@@ -79,3 +79,13 @@ class WeakRefineParams(Record):
     step_hz: float = 0.5
     presum_ms: int = 4
     reserved: int = 0
+
+
+@dataclasses.dataclass
+class WeakMeasureParams(Record):
+    """gyp_weak_measure_params, with the library's defaults (gyp_weak_measure_params_default): the early / late spacing in 2^-40 chips
+    and the number of passes, each of which corrects the code phase once."""
+    DTYPE = _lib.WEAK_MEASURE_PARAMS
+    spacing: int = 1 << 39
+    passes: int = 2
+    reserved: int = 0

@@ -16,7 +16,7 @@ from typing import Any, Dict, List
 
 import numpy as np
 
-from ._lib import CELL_DESC, GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER, GYP_NON_COHERENT, WEAK_RESULT
+from ._lib import CELL_DESC, GYP_HYB_ALTERNATE, GYP_HYB_CODE_DOPPLER, GYP_NON_COHERENT, WEAK_MEASURED, WEAK_RESULT
 from .antenna_sample_provider import SampleProviderAttributes
 from .engine import default_engine
 from .gps_ca_prn_codes import GpsSatelliteId
@@ -50,6 +50,22 @@ class SatelliteAcquisitionAttemptResult:
     carrier_wave_phase_shift: float
     prn_phase_shift: int
     correlation_strength: float
+
+
+@dataclass
+class WeakMeasurement:
+    """What measure_weak_satellites reports per result (gyp_weak_measured beside the search's z): figures, not verdicts."""
+    satellite_id: GpsSatelliteId
+    doppler_shift: float             # Hz, refined
+    carrier_wave_phase_shift: float  # radians at the buffer's first sample, modulo pi
+    c0: int                          # code phase in 2^-40 chips at the centre of the buffer's first sample
+    code_phase_samples: float        # the same as the sample, with its fraction, at which chip 0 begins: [0, N)
+    bit_edge: int                    # a data-bit edge at every millisecond m with m % 20 == bit_edge
+    cn0_dbhz: float                  # nan when the prompt's energy does not exceed the noise share
+    dd_last: float                   # the last pass's correction in chips: the residual
+    status: int                      # 0 ok; bit 1: no envelope above the noise in some pass
+    correlation_strength: float      # the search's z
+    record: np.ndarray               # the WEAK_MEASURED record itself (engine.weak_measured_state takes it)
 
 
 def _sv(satellite_id: Any) -> int:
@@ -135,6 +151,37 @@ class GpsSatelliteDetector:
             satellite_id=r.satellite_id, doppler_shift=float(o["doppler_hz"]), carrier_wave_phase_shift=float(o["carrier_phase"]),
             prn_phase_shift=int(o["code_phase"]), correlation_strength=r.correlation_strength)
             for r, o in zip(results, rec)]
+
+    def measure_weak_satellites(self, results: List[SatelliteAcquisitionAttemptResult], antenna_data: np.ndarray,
+                                stream_attributes: SampleProviderAttributes, first_ms: int = 0, refine_params=None,
+                                measure_params=None) -> List[WeakMeasurement]:
+        """Between detect_weak_satellites_in_antenna_data and WeakSignalTracker.from_measurements: the hand-over (gyp_weak_refine: Doppler,
+        carrier phase, bit edge) and then the measurement (gyp_weak_measure: the code phase to a fraction of a sample, the C/N0) of each
+        result over the whole milliseconds of antenna_data (40..2000; its first sample is that of the search, millisecond first_ms of
+        the recording).  One WeakMeasurement per input, in order, none dropped; a status other than 0 of either step is logged."""
+        results = list(results)
+        if not results:
+            return []
+        n = stream_attributes.samples_per_prn_transmission
+        n_ms = min(len(antenna_data) // n, 2000)
+        iq = np.asarray(antenna_data)[:n_ms * n]
+        cand = np.zeros(len(results), dtype=WEAK_RESULT)
+        for c, r in zip(cand, results):
+            c["sat_id"], c["doppler_hz"], c["carrier_phase"], c["code_phase"] = _sv(r.satellite_id), r.doppler_shift, r.carrier_wave_phase_shift, r.prn_phase_shift
+        eng = self._engine(stream_attributes)
+        refined, _ = eng.refine_weak(iq, 1, int(first_ms), cand, refine_params)
+        rec, _, _, _ = eng.measure_weak(iq, 1, int(first_ms), refined, measure_params)
+        out = []
+        for r, h, o in zip(results, refined, rec):
+            log = _logger.warning if int(h["status"]) or int(o["status"]) else _logger.info
+            log(f"Weak measurement of satellite {r.satellite_id}: Doppler {float(o['doppler_hz']):.2f} Hz, code phase {r.prn_phase_shift} -> "
+                f"{float(o['code_phase_samples']):.3f} samples, residual {float(o['dd_last']):+.4f} chip, C/N0 {float(o['cn0_dbhz']):.1f} dB-Hz, "
+                f"bit edge {int(o['edge'])}, status {int(h['status'])} / {int(o['status'])}")
+            out.append(WeakMeasurement(
+                satellite_id=r.satellite_id, doppler_shift=float(o["doppler_hz"]), carrier_wave_phase_shift=float(o["carrier_phase"]), c0=int(o["c0"]),
+                code_phase_samples=float(o["code_phase_samples"]), bit_edge=int(o["edge"]), cn0_dbhz=float(o["cn0_dbhz"]), dd_last=float(o["dd_last"]),
+                status=int(o["status"]), correlation_strength=r.correlation_strength, record=np.array(o, dtype=WEAK_MEASURED)))
+        return out
 
     def _attempt_acquisition_for_satellite_id(self, satellite_id: Any, samples_for_integration_period: np.ndarray,
                                               stream_attributes: SampleProviderAttributes) -> SatelliteAcquisitionAttemptResult:

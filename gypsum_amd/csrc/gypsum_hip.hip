@@ -147,6 +147,9 @@ static thread_local std::string g_create_error;
 //                             cells' gyp_cell records (their taps)
 //   wref_cands, wref_plans, wref_prompts, wref_power   gyp_weak_refine_dev: the candidates' start-up states, one WeakMsPlan per (candidate,
 //                             millisecond), the prompts when the caller takes none, the power rows of the periodograms
+//   wmeas_cands, wmeas_states, wmeas_plans, wmeas_sums, wmeas_w   gyp_weak_measure_dev: the candidates' start-up states, what each carries
+//                             from pass to pass (c0, the corrections' sum, the status), one WeakMsPlan per (candidate, millisecond),
+//                             and one pass's sums and W_m when the caller takes none
 // Members with more than one user, and why no call path holds two of them: the stage_* members serve one wrapper at a time and no
 // wrapper calls another (the hybrid wrappers gyp_correlate_grid_hybrid and gyp_acquire_weak use stage_iq and stage_out like the
 // others); of gyp_correlate_grid_dev, gyp_grid_best_bins_refined_dev (sat_ids, doppler) and acquire_search (partial64)
@@ -154,7 +157,8 @@ static thread_local std::string g_create_error;
 // hybrid_run serves one of gyp_correlate_grid_hybrid_dev and gyp_acquire_weak_dev at a time, neither calls the other, and its
 // launch_cells uses no member; the hyb_* members have no user outside the hybrid entry points.  The wref_* members have no user but
 // gyp_weak_refine_dev, which calls no entry point; its wrapper gyp_weak_refine stages through stage_iq and stage_out (the records, then
-// the prompts, back to back) like the others.
+// the prompts, back to back) like the others.  The wmeas_* members have no user but gyp_weak_measure_dev, which calls no entry point;
+// its wrapper gyp_weak_measure goes through staged_call (the records, then the sums, the W_m and the folds it was asked for, back to back).
 struct Scratch {
     DevBuf<int32_t> hyb_sat_ids;
     DevBuf<double> hyb_doppler;
@@ -167,6 +171,11 @@ struct Scratch {
     DevBuf<WeakMsPlan> wref_plans;
     DevBuf<float2> wref_prompts;
     DevBuf<double> wref_power;
+    DevBuf<WeakMeasureCand> wmeas_cands;
+    DevBuf<WeakMeasureState> wmeas_states;
+    DevBuf<WeakMsPlan> wmeas_plans;
+    DevBuf<gyp_weak_ms_rec> wmeas_sums;
+    DevBuf<double> wmeas_w;
     DevBuf<float> stage_iq, stage_profile, bench_sink;
     DevBuf<uint8_t> stage_in, stage_out, weak_stage, refine_list, acq_book, acq_units;
     DevBuf<double> stage_times, doppler, partial64, acq_refined, acq_profiles;
@@ -2193,6 +2202,133 @@ int gyp_weak_refine(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64
         return rc;
     if (prompts_out_host) HIP_TRY(ctx, hipMemcpyAsync(prompts_out_host, base + rec_bytes, prompt_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return stage_back(ctx, out_host, rec_bytes);
+}
+
+// ---------------------------------------------------------------- weak-signal measurement ------------------
+void gyp_weak_measure_params_default(gyp_weak_measure_params* out) {
+    if (out) *out = measure_params_default();
+}
+
+int gyp_weak_measure_estimate(const gyp_weak_ms_rec* sums, const double* w, int32_t n_ms, int64_t first_ms, int32_t edge, int64_t spacing,
+                              int64_t c0, gyp_weak_measure_fold* out) {
+    static const char* const who = "gyp_weak_measure_estimate";
+    if (!sums || !w || !out) return refuse(nullptr, who, "bad argument");
+    gyp_weak_measure_params prm = measure_params_default();
+    prm.spacing = spacing;
+    if (const char* why = measure_refusal(prm, n_ms, first_ms)) return refuse(nullptr, who, why);
+    if (const char* why = measure_edge_refusal(edge, n_ms, first_ms)) return refuse(nullptr, who, why);
+    if (c0 < 0 || c0 >= kWeakCodeMod) return refuse(nullptr, who, "c0 is outside [0, 1023 * 2^40)");
+    *out = measure_estimate(sums, w, n_ms, first_ms, edge, spacing, c0);
+    return GYP_OK;
+}
+
+int gyp_weak_measured_state(const gyp_weak_measured* rec, int64_t fs, int32_t samples_per_ms, int32_t ms_ahead, gyp_weak_state* out) {
+    static const char* const who = "gyp_weak_measured_state";
+    if (!rec || !out) return refuse(nullptr, who, "bad argument");
+    if (fs < 1) return refuse(nullptr, who, "fs must be positive");
+    if (samples_per_ms < 1023 || samples_per_ms % 1023 != 0) return refuse(nullptr, who, "N must be a positive multiple of 1023");
+    if (ms_ahead < 0 || ms_ahead > kWeakMaxMs) return refuse(nullptr, who, "ms_ahead must be 0..65535");
+    if (!std::isfinite(rec->doppler_hz)) return refuse(nullptr, who, "a Doppler is not finite");
+    if (!std::isfinite(rec->carrier_phase)) return refuse(nullptr, who, "a carrier phase is not finite");
+    if (rec->c0 < 0 || rec->c0 >= kWeakCodeMod) return refuse(nullptr, who, "c0 is outside [0, 1023 * 2^40)");
+    if (rec->edge < 0 || rec->edge >= kWeakPeriodMs) return refuse(nullptr, who, "an edge is outside 0..19");
+    *out = measure_state(*rec, (double)fs, samples_per_ms, ms_ahead);
+    return GYP_OK;
+}
+
+}   // extern "C"
+// What both forms of gyp_weak_measure refuse, before anything runs (stride < 0: the host form, which has none).
+static int weak_measure_check(gyp_ctx* ctx, const char* who, const void* iq, const void* out, int32_t n_streams, int64_t stream_stride_samples,
+                              int64_t first_ms, int32_t n_ms, const gyp_weak_refined* refined, int32_t n_results, const gyp_weak_measure_params& prm) {
+    if (!iq || !out || !refined || n_streams < 1 || n_results < 1) return refuse(ctx, who, "bad argument");
+    if (const char* why = measure_refusal(prm, n_ms, first_ms)) return refuse(ctx, who, why);
+    if (stream_stride_samples >= 0 && stream_stride_samples < (int64_t)n_ms * ctx->n) return refuse(ctx, who, "the stream stride is below n_ms * N");
+    if ((int64_t)n_results * ((n_ms + kMeasureWaves - 1) / kMeasureWaves) > INT32_MAX) return refuse(ctx, who, "more than 2^31 - 1 workgroups");
+    for (int32_t i = 0; i < n_results; ++i) {
+        const gyp_weak_refined& r = refined[i];
+        if (const char* why = measure_cand_refusal(r, ctx->n, n_ms, first_ms)) return refuse(ctx, who, why);
+        if (r.stream >= n_streams)
+            return refuse(ctx, who, "candidate " + std::to_string(i) + " reads stream " + std::to_string(r.stream) + " but only " + std::to_string(n_streams) + " were passed");
+    }
+    return GYP_OK;
+}
+// Where a pass's rows of sums (or W_m) go: the caller's array is [candidate][pass][n_ms], the scratch [candidate][n_ms].
+template <typename T>
+static WeakMeasureRows<T> weak_measure_rows(T* callers, T* scratch, int32_t passes, int32_t pass) {
+    return callers ? WeakMeasureRows<T>{callers, passes, pass} : WeakMeasureRows<T>{scratch, 1, 0};
+}
+extern "C" {
+
+int gyp_weak_measure_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                         const gyp_weak_refined* refined_host, int32_t n_results, const gyp_weak_measure_params* params,
+                         gyp_weak_measured* out_dev, gyp_weak_ms_rec* sums_out_dev, double* w_out_dev, gyp_weak_measure_fold* folds_out_dev) {
+    static const char* const who = "gyp_weak_measure_dev";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    const gyp_weak_measure_params prm = params ? *params : measure_params_default();
+    if (stream_stride_samples < 0) return refuse(ctx, who, "bad argument");
+    if (const int rc = weak_measure_check(ctx, who, iq_dev, out_dev, n_streams, stream_stride_samples, first_ms, n_ms, refined_host, n_results, prm)) return rc;
+    std::vector<WeakMeasureCand> cands((size_t)n_results);
+    for (int32_t i = 0; i < n_results; ++i) {
+        const gyp_weak_refined& r = refined_host[i];
+        const WeakChan s = weak_fresh_chan(gyp_chan_init{r.stream, r.sat_id, r.doppler_hz, r.carrier_phase, r.code_phase, 0}, ctx->n, first_ms);
+        cands[i] = WeakMeasureCand{r.stream, r.sat_id, r.edge, 0, s.f, s.u0, r.carrier_phase, s.c0};
+    }
+    Scratch& sc = ctx->scratch;
+    const size_t rows = (size_t)n_results * (size_t)n_ms;
+    HIP_TRY(ctx, sc.wmeas_plans.reserve(rows, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, sc.wmeas_states.reserve((size_t)n_results, Slack::grow, ctx->stream));
+    if (!sums_out_dev) HIP_TRY(ctx, sc.wmeas_sums.reserve(rows, Slack::grow, ctx->stream));
+    if (!w_out_dev) HIP_TRY(ctx, sc.wmeas_w.reserve(rows, Slack::grow, ctx->stream));
+    HIP_TRY(ctx, upload(sc.wmeas_cands, cands.data(), cands.size(), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the candidates are a temporary
+    WeakMeasureArgs p{};
+    p.cands = sc.wmeas_cands.get(); p.states = sc.wmeas_states.get(); p.plans = sc.wmeas_plans.get();
+    p.folds = folds_out_dev;
+    p.iq = iq_dev; p.stream_stride = stream_stride_samples; p.chips = ctx->codes.chips.get();
+    p.out = out_dev; p.spacing = prm.spacing; p.fs = (double)ctx->fs; p.first_ms = first_ms;
+    p.n = ctx->n; p.n_ms = n_ms; p.n_cand = n_results; p.passes = prm.passes;
+    const unsigned runs = (unsigned)((n_ms + kMeasureWaves - 1) / kMeasureWaves);
+    for (int32_t pass = 0; pass < prm.passes; ++pass) {
+        p.pass = pass;
+        // the sums and the W_m each go to the caller's row of this pass, or to the one scratch row a candidate has
+        p.sums = weak_measure_rows(sums_out_dev, sc.wmeas_sums.get(), prm.passes, pass);
+        p.w = weak_measure_rows(w_out_dev, sc.wmeas_w.get(), prm.passes, pass);
+        hipLaunchKernelGGL(weak_measure_plan_kernel, dim3((unsigned)((n_results + 63) / 64)), dim3(64), 0, ctx->stream, p);
+        if (const int rc = launched(ctx)) return rc;
+        hipLaunchKernelGGL(weak_measure_sums_kernel, dim3((unsigned)n_results * runs), dim3(kMeasureThreads), 0, ctx->stream, p);
+        if (const int rc = launched(ctx)) return rc;
+        hipLaunchKernelGGL(weak_measure_fold_kernel, dim3((unsigned)n_results), dim3(kMeasureFoldThreads), 0, ctx->stream, p);
+        if (const int rc = launched(ctx)) return rc;
+    }
+    return GYP_OK;
+}
+
+int gyp_weak_measure(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                     const gyp_weak_refined* refined_host, int32_t n_results, const gyp_weak_measure_params* params,
+                     gyp_weak_measured* out_host, gyp_weak_ms_rec* sums_out_host, double* w_out_host, gyp_weak_measure_fold* folds_out_host) {
+    static const char* const who = "gyp_weak_measure";
+    if (!ctx) return GYP_E_BAD_ARG;
+    if (const int rc = need_format(ctx)) return rc;
+    const gyp_weak_measure_params prm = params ? *params : measure_params_default();
+    if (const int rc = weak_measure_check(ctx, who, iq_host, out_host, n_streams, -1, first_ms, n_ms, refined_host, n_results, prm)) return rc;
+    // the staged results: the records, then what was asked for of the sums, the W_m and the folds, back to back (all multiples of 8 bytes)
+    const size_t rows = (size_t)n_results * (size_t)prm.passes * (size_t)n_ms;
+    const size_t rec_bytes = (size_t)n_results * sizeof(gyp_weak_measured), sums_bytes = sums_out_host ? rows * sizeof(gyp_weak_ms_rec) : 0;
+    const size_t w_bytes = w_out_host ? rows * sizeof(double) : 0, fold_bytes = folds_out_host ? (size_t)n_results * prm.passes * sizeof(gyp_weak_measure_fold) : 0;
+    std::vector<uint8_t> staged(rec_bytes + sums_bytes + w_bytes + fold_bytes);
+    const int rc = staged_call(ctx, iq_host, n_streams, n_ms, staged.data(), staged.size(), [&](const float* iq_dev, int64_t stride, void* out_dev) {
+        uint8_t* const base = static_cast<uint8_t*>(out_dev);
+        return gyp_weak_measure_dev(ctx, iq_dev, n_streams, stride, first_ms, n_ms, refined_host, n_results, &prm, (gyp_weak_measured*)base,
+                                    sums_bytes ? (gyp_weak_ms_rec*)(base + rec_bytes) : nullptr, w_bytes ? (double*)(base + rec_bytes + sums_bytes) : nullptr,
+                                    fold_bytes ? (gyp_weak_measure_fold*)(base + rec_bytes + sums_bytes + w_bytes) : nullptr);
+    });
+    if (rc) return rc;
+    std::memcpy(out_host, staged.data(), rec_bytes);
+    if (sums_bytes) std::memcpy(sums_out_host, staged.data() + rec_bytes, sums_bytes);
+    if (w_bytes) std::memcpy(w_out_host, staged.data() + rec_bytes + sums_bytes, w_bytes);
+    if (fold_bytes) std::memcpy(folds_out_host, staged.data() + rec_bytes + sums_bytes + w_bytes, fold_bytes);
+    return GYP_OK;
 }
 
 // ---------------------------------------------------------------- multi-GPU: one all-gather over RCCL ------

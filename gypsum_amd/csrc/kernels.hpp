@@ -46,6 +46,10 @@
 //                       SYNC, a wavefront per (candidate, millisecond) grid-wide, then one workgroup per candidate squares their
 //                       pre-sums, scans a float64 periodogram for the residual Doppler and reports the bit edge and carrier phase
 //                       (refine_plan.hpp holds that arithmetic for host and device).
+//   weak_measure_* kernels   weak-signal measurement: per candidate of the hand-over and per pass the three-lag sums a weak bank would
+//                       write and sum |x|^2 beside them, a wavefront per (candidate, millisecond) grid-wide, then one workgroup per
+//                       candidate folds them over the data bits into early / prompt / late envelopes, corrects the code phase on the
+//                       device for the next pass and reports it with the C/N0 (measure_plan.hpp holds that arithmetic for host and device).
 //   acq_* kernels       the level-to-level bookkeeping of acquisition.py:70-152 on the device: plan, work list, record
 //                       reuse (optional), float64 tie-breaks within a level (refine) and across levels (exact).
 //
@@ -69,3 +73,4 @@
 #include "kernels_hybrid.hpp"
 #include "kernels_weak.hpp"
 #include "kernels_refine.hpp"
+#include "kernels_measure.hpp"

@@ -738,6 +738,37 @@ class GypsumEngine:
                                                   ptr(res) if res.size else None, len(res), ptr(_refine_params(params)), C.c_void_p(out_ptr or None),
                                                   C.c_void_p(prompts_ptr or None)))
 
+    # ------------------------------------------------------------------ weak-signal measurement (refine -> measure -> weak bank)
+    def measure_weak(self, iq: np.ndarray, n_streams: int, first_ms: int, refined: np.ndarray, params=None,
+                     want_sums: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
+        """gyp_weak_measure: the fractional code phase and the C/N0 of each WEAK_REFINED record from the early / prompt / late sums of
+        iq (complex64[n_streams * n_ms * N], stream-major, 40..2000 whole milliseconds from the absolute millisecond first_ms).
+        (WEAK_MEASURED[len(refined)], and with want_sums the WEAK_MS_REC sums [len(refined), passes, n_ms], the float64 W_m of the same
+        shape and the WEAK_MEASURE_FOLD records [len(refined), passes]; None each otherwise).  params: a _records.WeakMeasureParams or a
+        WEAK_MEASURE_PARAMS record (None: the defaults)."""
+        iq = _as_iq(iq).reshape(-1)
+        n_ms = iq.size // (max(int(n_streams), 1) * self.n)
+        if iq.size != max(int(n_streams), 1) * n_ms * self.n:
+            raise ValueError("a whole number of milliseconds per stream expected")
+        ref = np.ascontiguousarray(refined, dtype=_lib.WEAK_REFINED).reshape(-1)
+        prm = _measure_params(params)
+        passes = max(1, min(4, int(prm[0]["passes"]))) if prm is not None else 2
+        out = np.zeros(len(ref), dtype=_lib.WEAK_MEASURED)
+        sums = np.zeros((len(ref), passes, n_ms), dtype=_lib.WEAK_MS_REC) if want_sums else None
+        w = np.zeros((len(ref), passes, n_ms), dtype=np.float64) if want_sums else None
+        folds = np.zeros((len(ref), passes), dtype=_lib.WEAK_MEASURE_FOLD) if want_sums else None
+        self._check(self.lib.gyp_weak_measure(self.ctx, ptr(iq) if iq.size else None, int(n_streams), int(first_ms), n_ms, ptr(ref) if ref.size else None,
+                                               len(ref), ptr(prm), ptr(out), ptr(sums), ptr(w), ptr(folds)))
+        return out, sums, w, folds
+
+    def measure_weak_dev(self, iq_ptr: int, n_streams: int, stream_stride: int, first_ms: int, n_ms: int, refined: np.ndarray, out_ptr: int,
+                         params=None, sums_ptr: int = 0, w_ptr: int = 0, folds_ptr: int = 0) -> None:
+        """Device-pointer form: waits for the stream once, after uploading the candidates, then only enqueues."""
+        ref = np.ascontiguousarray(refined, dtype=_lib.WEAK_REFINED).reshape(-1)
+        self._check(self.lib.gyp_weak_measure_dev(self.ctx, C.c_void_p(iq_ptr or None), int(n_streams), int(stream_stride), int(first_ms), int(n_ms),
+                                                   ptr(ref) if ref.size else None, len(ref), ptr(_measure_params(params)), C.c_void_p(out_ptr or None),
+                                                   C.c_void_p(sums_ptr or None), C.c_void_p(w_ptr or None), C.c_void_p(folds_ptr or None)))
+
     def synth_iq(self, out: "DeviceBuffer", n_streams: int, stream_stride: int, n_ms: int, sats: np.ndarray,
                  noise_sigma: float, seed: int) -> None:
         """Generate synthetic baseband straight into HBM (bench / test support). sats: SYNTH_SAT[n_streams, n_sats]."""
@@ -811,6 +842,48 @@ def weak_refine_estimate(prompts: np.ndarray, first_ms: int, params=None) -> np.
     p = np.ascontiguousarray(prompts, dtype=np.complex64).reshape(-1)
     out = np.zeros(1, dtype=_lib.WEAK_REFINED)
     rc = lib.gyp_weak_refine_estimate(ptr(p) if p.size else None, p.size, int(first_ms), ptr(_refine_params(params)), ptr(out))
+    if rc != 0:
+        raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
+    return out[0]
+
+
+def _measure_params(params) -> Optional[np.ndarray]:
+    """A _records.WeakMeasureParams or a WEAK_MEASURE_PARAMS record as the library takes it (None stays None: the defaults)."""
+    if params is not None and not isinstance(params, np.ndarray):
+        params = params.record()
+    return None if params is None else np.ascontiguousarray(params, dtype=_lib.WEAK_MEASURE_PARAMS).reshape(-1)
+
+
+def weak_measure_params_default() -> np.ndarray:
+    """gyp_weak_measure_params_default (host only, no GPU): one WEAK_MEASURE_PARAMS record."""
+    rec = np.zeros(1, dtype=_lib.WEAK_MEASURE_PARAMS)
+    _lib.load().gyp_weak_measure_params_default(ptr(rec))
+    return rec
+
+
+def weak_measure_estimate(sums: np.ndarray, w: np.ndarray, first_ms: int, edge: int, c0: int, spacing: int = 1 << 39) -> np.ndarray:
+    """gyp_weak_measure_estimate (host only, no GPU): one WEAK_MEASURE_FOLD record -- the envelopes' energies over the data bits at
+    `edge`, the noise share, the correction dd, the corrected c0 and the C/N0 -- from one pass's WEAK_MS_REC sums and float64 W_m of
+    milliseconds first_ms, first_ms + 1, ... and the pass's c0."""
+    lib = _lib.load()
+    s = np.ascontiguousarray(sums, dtype=_lib.WEAK_MS_REC).reshape(-1)
+    ww = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if len(s) != len(ww):
+        raise ValueError("one W per millisecond record expected")
+    out = np.zeros(1, dtype=_lib.WEAK_MEASURE_FOLD)
+    rc = lib.gyp_weak_measure_estimate(ptr(s) if s.size else None, ptr(ww) if ww.size else None, len(s), int(first_ms), int(edge), int(spacing), int(c0), ptr(out))
+    if rc != 0:
+        raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
+    return out[0]
+
+
+def weak_measured_state(measured, fs: int, samples_per_ms: int, ms_ahead: int = 0) -> np.ndarray:
+    """gyp_weak_measured_state (host only, no GPU): the WEAK_STATE record WeakChannelBank.set_state takes, from one WEAK_MEASURED record,
+    advanced ms_ahead milliseconds open loop (0: a bank whose cursor is the buffer's first millisecond; n_ms: one that continues behind it)."""
+    lib = _lib.load()
+    rec = np.ascontiguousarray(measured, dtype=_lib.WEAK_MEASURED).reshape(-1)[:1]
+    out = np.zeros(1, dtype=_lib.WEAK_STATE)
+    rc = lib.gyp_weak_measured_state(ptr(rec), int(fs), int(samples_per_ms), int(ms_ahead), ptr(out))
     if rc != 0:
         raise GypsumHipError(rc, (lib.gyp_last_error(None) or b"").decode())
     return out[0]

@@ -28,7 +28,7 @@ from ._lib import CHAN_INIT
 from ._records import WeakParams
 from .acquisition import SatelliteAcquisitionAttemptResult
 from .antenna_sample_provider import SampleProviderAttributes
-from .engine import WeakChannelBank, default_engine
+from .engine import WeakChannelBank, default_engine, weak_measured_state
 from .navigation_bit_intergrator import EmitNavigationBitEvent
 from .tracker import BitValue
 
@@ -83,6 +83,26 @@ class WeakSignalTracker:
         self.bank: WeakChannelBank = self._engine.create_weak_bank(inits, params, first_ms)
         self.cursor_ms = int(first_ms)
         self._dphi = [collections.deque(maxlen=_PHASE_WINDOW) for _ in results]
+
+    @classmethod
+    def from_measurements(cls, measurements: Sequence, stream_attributes: SampleProviderAttributes, first_ms: int = 0,
+                          params: Optional[WeakParams] = None, ms_ahead: int = 0, engine=None) -> "WeakSignalTracker":
+        """measurements: what GpsSatelliteDetector.measure_weak_satellites returned for a buffer whose first millisecond is
+        first_ms of the recording.  Every channel is put in WAIT from its measured state (engine.weak_measured_state ->
+        gyp_weak_bank_set_state): no SYNC, the first bit comes with the first whole data bit.  ms_ahead = 0: process() is given
+        the recording from first_ms on (the measured buffer again, then what follows); ms_ahead = the buffer's milliseconds: from
+        behind the buffer."""
+        if not measurements:
+            raise ValueError("no measurements to track")
+        results = [SatelliteAcquisitionAttemptResult(satellite_id=m.satellite_id, doppler_shift=m.doppler_shift,
+                                                     carrier_wave_phase_shift=m.carrier_wave_phase_shift,
+                                                     prn_phase_shift=int(m.code_phase_samples), correlation_strength=m.correlation_strength)
+                   for m in measurements]
+        trk = cls(results, stream_attributes, params, int(first_ms) + int(ms_ahead), engine)
+        for c, m in enumerate(measurements):
+            st = weak_measured_state(m.record, trk.fs, trk.n, int(ms_ahead))
+            trk.bank.set_state(c, float(st["f"]), float(st["f_int"]), float(st["u0"]), int(st["c0"]), int(st["edge"]))
+        return trk
 
     def process(self, antenna_data: np.ndarray) -> List[Tuple[int, EmitNavigationBitEvent]]:
         x = np.asarray(antenna_data).reshape(-1)

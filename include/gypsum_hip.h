@@ -29,6 +29,10 @@ extern "C" {
 #endif
 
 /* 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
+ *      measurement, the fractional code phase and the C/N0 of a weak candidate between the hand-over and the weak bank on the device:
+ *      gyp_weak_measure_params(_default), gyp_weak_measured, gyp_weak_measure_fold, gyp_weak_measure(_dev), gyp_weak_measure_estimate,
+ *      gyp_weak_measured_state.  Opt-in.
+ * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
  *      hand-over, a sub-Hz Doppler refinement between the weak search and the weak bank on the device: gyp_weak_refine_params(_default),
  *      gyp_weak_refined, gyp_weak_refine(_dev), gyp_weak_refine_estimate.  Opt-in.
  * 209 (additions; the number stays, nothing that existed changes and a binding looks the new symbols up by name): weak-signal
@@ -685,6 +689,105 @@ int gyp_weak_refine(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64
  * the increment; stream, sat_id and code_phase of *out are 0.  GYP_E_BAD_ARG, with *out untouched, for NULL prompts or out, params
  * out of range (NULL: the defaults), n_ms outside 40..2000 or fewer than 8 groups, first_ms < 0. */
 int gyp_weak_refine_estimate(const float* prompts, int32_t n_ms, int64_t first_ms, const gyp_weak_refine_params* params, gyp_weak_refined* out);
+
+/* ---------------------------------------------------------------- weak-signal measurement --------------- */
+/* Between gyp_weak_refine and a weak bank.  The hand-over leaves the code phase on the sample grid (+-0.25 chip at 2.046 Msps) and
+ * gives no signal level.  This step measures, open loop over the same buffer, the code phase to a fraction of a sample with the
+ * bank's own early / late replicas and the C/N0 from the bit-wide coherent sums, and hands the bank a full state
+ * (gyp_weak_measured_state -> gyp_weak_bank_set_state), so that it needs no SYNC.  It changes nothing in the search, the hand-over,
+ * the bank or their records.
+ *
+ * Inputs: one stream buffer of n_ms whole milliseconds (40..2000) whose first millisecond has the absolute index first_ms, and per
+ * candidate a gyp_weak_refined, of which stream, sat_id, doppler_hz = f, carrier_phase, code_phase and edge are read.  d = spacing / 2^40.
+ *   1 start     f, u0, c0 exactly as a weak bank starts ("weak-signal tracking", start) from the candidate read as a gyp_chan_init at
+ *               cursor first_ms; per millisecond u0 and c0 advance as in SYNC, with r from f.
+ *   2 sums      pass p = 1 .. passes: for every millisecond m the float32 sums minus, prompt, plus at o = -d, 0, +d from the pass's c0, by
+ *               the arithmetic of a millisecond's sums of the "weak-signal tracking" section: in pass 1 they are bit for bit the SYNC
+ *               gyp_weak_ms_rec of a weak bank created from the candidate at cursor first_ms with this spacing; in a later pass the
+ *               six sums are those of a bank put at the pass's c0 through gyp_weak_bank_set_state, while it waits.  In the same loop
+ *               W_m = sum |x|^2: lane l adds, in increasing i, (re re + im im) of the widened samples i = l, l + 64, ... in float64
+ *               (two products, one sum, one addition, each rounded once); the lanes are reduced by the same tree; a float64.
+ *   3 fold      the groups are gyp_weak_bit_sync's for o = edge: heads h = first_ms + ((edge - first_ms) mod 20), h + 20, ... with
+ *               h + 20 <= first_ms + n_ms; n_groups of them.  Float64 from here on, one rounding per operation, no contraction.
+ *               Per group, with S the sum in order of its 20 float32 sums widened (re and im apart): e = S.re S.re + S.im S.im for
+ *               each of minus, prompt, plus; w = the sum in order of its 20 W_m.  E-, E0, E+ and Wn are the sums, in increasing h, of
+ *               the groups' e and w.  Wn is what white noise alone is expected to leave in each E (|chip| = |carrier| = 1).
+ *               A. = sqrt(max(E. - Wn, 0)).
+ *   4 correct   dd = (1 - d) (A+ - A-) / (A+ + A-), d = (double)spacing / 2^40; with d = 1/2 the bank's DLL discriminator.  When
+ *               A+ + A- is not positive, dd = 0 and status bit 1 is set.  c0 <- (c0 + llround(dd 2^40)) mod (1023 2^40): a replica
+ *               running late makes plus larger, as in the bank.  The next pass starts from the corrected c0 with f and u0 unchanged;
+ *               the correction stays on the device between passes.
+ *   5 record    c0 after the last pass's correction; code_phase_samples = 0.5 - K (c0 / 2^40), + N when negative (and 0 where that
+ *               rounds to N): the inverse of the start rule, in [0, N); delta_chips = the sum, in order, of the passes' dd;
+ *               dd_last = the last pass's dd: the residual by which the caller judges convergence;
+ *               cn0_dbhz = 10 log10(((E0 - Wn) / Wn) / 0.020) of the last pass, NaN when E0 <= Wn or Wn is 0.
+ * Figures, not verdicts.  The sample-lattice limit: every supported rate has a whole number of samples per chip, so where the code
+ * drifts less than one sample across the buffer (about 0.65 chip/s per kHz of Doppler: below 3.6 kHz over 220 ms at 2.046 Msps) the
+ * envelope is a staircase in the code offset, the early-late difference has a dead zone and the error stays near the grid's
+ * ("weak-signal measurement").  That is a property of the recording and the bank's DLL has it too.
+ * The device and gyp_weak_measure_estimate share this arithmetic (csrc/measure_plan.hpp); + - x / and sqrt are correctly rounded on
+ * both, so dd and c0 agree bit for bit on the same sums, cn0_dbhz (the platform's log10) to about 1e-12.  A candidate's record, sums
+ * and folds are the same bits whatever other candidates the call holds and in whatever order. */
+typedef struct gyp_weak_measure_params {   /* 16 bytes */
+    int64_t spacing;       /* d in 2^-40 chips: 2^39 (half a chip); 2^36 .. 2^39 */
+    int32_t passes;        /* 2; 1..4 */
+    int32_t reserved;      /* 0 */
+} gyp_weak_measure_params;
+void gyp_weak_measure_params_default(gyp_weak_measure_params* out);
+
+typedef struct gyp_weak_measured {   /* 80 bytes */
+    int32_t stream;              /* offset 0 */
+    int32_t sat_id;              /* 4 */
+    double doppler_hz;           /* 8: the input's */
+    double carrier_phase;        /* 16: the input's */
+    int64_t c0;                  /* 24: 2^-40 chips at the centre of the buffer's first sample, [0, 1023 2^40) */
+    double code_phase_samples;   /* 32: [0, N) */
+    double delta_chips;          /* 40 */
+    double dd_last;              /* 48 */
+    double cn0_dbhz;             /* 56 */
+    int32_t edge;                /* 64: the input's */
+    int32_t n_groups;            /* 68 */
+    int32_t status;              /* 72: 0 ok; bit 1 (value 1): no envelope above the noise in some pass -- c0 is the start plus whatever
+                                    corrections were made */
+    int32_t reserved;            /* 76 */
+} gyp_weak_measured;
+
+/* One pass's fold and correction (steps 3-4). */
+typedef struct gyp_weak_measure_fold {   /* 64 bytes */
+    double e_minus, e_prompt, e_plus;   /* 0, 8, 16: E-, E0, E+ */
+    double wn;                          /* 24 */
+    double dd;                          /* 32 */
+    double cn0_dbhz;                    /* 40: as in the record, of this pass */
+    int64_t c0;                         /* 48: after this pass's correction */
+    int32_t n_groups;                   /* 56 */
+    int32_t status;                     /* 60: 0, or 1 when A+ + A- is not positive */
+} gyp_weak_measure_fold;
+
+/* iq_dev: n_streams streams of n_ms x N samples, stream stride given.  refined_host: n_results candidates, a HOST array; out_dev:
+ * n_results records in the same order.  Optional outputs, each NULL or candidate-major, pass-major within a candidate:
+ * sums_out_dev n_results x passes x n_ms gyp_weak_ms_rec (phase 0, pos 0, status 0), w_out_dev as many
+ * float64 W_m, folds_out_dev n_results x passes records.  params NULL: the defaults.  Refused with GYP_E_BAD_ARG before anything runs:
+ * spacing outside 2^36 .. 2^39 or passes outside 1..4; n_ms outside 40..2000, or no whole group of 20 milliseconds at a candidate's
+ * edge; first_ms < 0; NULL pointers or counts below 1; a candidate with stream < 0 or >= n_streams, a satellite id outside 1..32, a
+ * non-finite Doppler or carrier phase, a code phase outside [0, N) or an edge outside 0..19; a stride below n_ms N.  The _dev form
+ * waits for the stream once, after uploading the candidates (the host array may be a temporary), then only enqueues: 3 launches a pass. */
+int gyp_weak_measure_dev(gyp_ctx* ctx, const float* iq_dev, int32_t n_streams, int64_t stream_stride_samples, int64_t first_ms, int32_t n_ms,
+                         const gyp_weak_refined* refined_host, int32_t n_results, const gyp_weak_measure_params* params,
+                         gyp_weak_measured* out_dev, gyp_weak_ms_rec* sums_out_dev, double* w_out_dev, gyp_weak_measure_fold* folds_out_dev);
+int gyp_weak_measure(gyp_ctx* ctx, const float* iq_host, int32_t n_streams, int64_t first_ms, int32_t n_ms,
+                     const gyp_weak_refined* refined_host, int32_t n_results, const gyp_weak_measure_params* params,
+                     gyp_weak_measured* out_host, gyp_weak_ms_rec* sums_out_host, double* w_out_host, gyp_weak_measure_fold* folds_out_host);
+/* Host only, no GPU: steps 3-4 of one pass on given sums (n_ms records, that of millisecond first_ms + i at i; of each the six sums
+ * are read) and w (n_ms float64), from the pass's c0.  GYP_E_BAD_ARG, with *out untouched, for NULL sums, w or out, spacing outside
+ * 2^36 .. 2^39, n_ms outside 40..2000, first_ms < 0, edge outside 0..19, no whole group, c0 outside [0, 1023 2^40). */
+int gyp_weak_measure_estimate(const gyp_weak_ms_rec* sums, const double* w, int32_t n_ms, int64_t first_ms, int32_t edge, int64_t spacing,
+                              int64_t c0, gyp_weak_measure_fold* out);
+/* Host only, no GPU: the state gyp_weak_bank_set_state takes, from a record, advanced ms_ahead milliseconds as in SYNC (f = f_int =
+ * doppler_hz, u0 by the start rule from carrier_phase, c0 the record's; phase 1, the record's edge, all else 0).  ms_ahead 0: for a
+ * bank whose cursor is the buffer's first_ms; n_ms: for one that continues behind the buffer.  fs: samples per second, N: samples
+ * per millisecond.  GYP_E_BAD_ARG for NULL, fs < 1, N not a positive multiple of 1023, ms_ahead outside 0..65535, a non-finite
+ * Doppler or carrier phase, c0 outside [0, 1023 2^40), edge outside 0..19. */
+int gyp_weak_measured_state(const gyp_weak_measured* rec, int64_t fs, int32_t samples_per_ms, int32_t ms_ahead, gyp_weak_state* out);
 
 /* ---------------------------------------------------------------- multi-GPU ----------------------------- */
 /* The path shards by stream, satellite or (satellite x Doppler) cell with no data-path exchange except ONE all-gather
