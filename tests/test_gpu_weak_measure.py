@@ -18,6 +18,7 @@ import pytest
 import weak_measure_model as mm
 import weak_track_model as wm
 from gypsum_amd import _lib, _records, engine, synth
+from weak_shapes_scene import inits_of, refined_of      # shared with tests/test_gpu_weak_shapes_*.py
 
 pytestmark = pytest.mark.gpu
 
@@ -40,21 +41,6 @@ def candidates(n: int):
 def true_edge(bit_offset: int) -> int:
     """Millisecond i of the buffer is the absolute millisecond FIRST_MS + i and starts a bit when (i + bit_offset) % 20 == 0."""
     return (FIRST_MS - bit_offset) % 20
-
-
-def refined_of(rows) -> np.ndarray:
-    """WEAK_REFINED records from (stream, sat_id, doppler_hz, carrier_phase, code_phase, edge) rows."""
-    out = np.zeros(len(rows), dtype=_lib.WEAK_REFINED)
-    for r, (stream, sv, f, phase, cp, edge) in zip(out, rows):
-        r["stream"], r["sat_id"], r["doppler_hz"], r["carrier_phase"], r["code_phase"], r["edge"] = stream, sv, f, phase, cp, edge
-    return out
-
-
-def inits_of(refined: np.ndarray) -> np.ndarray:
-    out = np.zeros(len(refined), dtype=_lib.CHAN_INIT)
-    for name in ("stream", "sat_id", "doppler_hz", "carrier_phase", "code_phase"):      # by field name
-        out[name] = refined[name]
-    return out
 
 
 def prm(passes: int, spacing: int) -> _records.WeakMeasureParams:

@@ -16,27 +16,13 @@ import weak_track_model as wm
 import weak_track_scene as ws
 from gypsum_amd import _lib, _records, engine, synth
 from gypsum_amd.gps_ca_prn_codes import generate_ca_code_table
+from weak_shapes_scene import close_to, inits_of, results_of      # shared with tests/test_gpu_weak_shapes_*.py
 
 pytestmark = pytest.mark.gpu
 
 BAD_ARG = _lib.GYP_E_BAD_ARG
 N_MS, FIRST_MS = 40, 7
 MULTIPLES = (1, 2, 48)
-
-
-def results_of(rows) -> np.ndarray:
-    """WEAK_RESULT records from (stream, sat_id, doppler_hz, carrier_phase, code_phase) rows."""
-    out = np.zeros(len(rows), dtype=_lib.WEAK_RESULT)
-    for r, (stream, sv, f, phase, cp) in zip(out, rows):
-        r["stream"], r["sat_id"], r["doppler_hz"], r["carrier_phase"], r["code_phase"] = stream, sv, f, phase, cp
-    return out
-
-
-def inits_of(results: np.ndarray) -> np.ndarray:
-    out = np.zeros(len(results), dtype=_lib.CHAN_INIT)
-    for name in ("stream", "sat_id", "doppler_hz", "carrier_phase", "code_phase"):      # by field name
-        out[name] = results[name]
-    return out
 
 
 def candidates(n: int):
@@ -108,18 +94,6 @@ def test_prompts_are_the_sync_prompts_of_a_weak_bank_bit_for_bit(engine_factory,
             assert err <= 1e-4 * norm, (mult, i, m, err, norm)
     assert wm.init_u0(float(c["results"][2]["carrier_phase"])) == 0.0                                     # the hair below zero
     print(f"{fs} Hz: largest |device - model| / ||x_ms||_2 = {worst:.3g}")
-
-
-def close_to(got: np.ndarray, want: rm.Refined, f0: float, phase0: float) -> None:
-    """The tolerances of tests/test_weak_refine_host.py: bin, edge and status equal, delta_hz and carrier_phase within 1e-6, the two
-    ratios within 1e-9 relative."""
-    assert (int(got["bin"]), int(got["edge"]), int(got["status"])) == (want.bin, want.edge, want.status)
-    assert abs(float(got["delta_hz"]) - want.delta_hz) <= 1e-6
-    assert abs(float(got["doppler_hz"]) - (f0 + want.delta_hz)) <= 1e-6 + abs(f0) * 2.0 ** -52
-    turn = float(got["carrier_phase"]) - rm.wrap_phase(phase0 + want.carrier_phase)
-    assert abs(turn - 2 * math.pi * round(turn / (2 * math.pi))) <= 1e-6 and -math.pi < float(got["carrier_phase"]) <= math.pi
-    for name, w in (("peak_to_mean", want.peak_to_mean), ("edge_ratio", want.edge_ratio)):
-        assert (math.isnan(float(got[name])) and math.isnan(w)) or abs(float(got[name]) - w) <= 1e-9 * abs(w), name
 
 
 @pytest.mark.parametrize("mult", MULTIPLES)
